@@ -7,6 +7,11 @@
 
 One "step" = forward + per-pixel BCE + metrics + backward + (DP: gradient all-reduce) + Adam on one synthetic
 minibatch that is already resident in HBM.  Rank 0 prints ONE JSON line (Measurement).
+
+A plain run sets up, warms up, times exactly --steps steps and prints the line.  --full adds everything else: the per-launch
+profile pass and roofline block, the single-stream schedule comparison, the CPU baseline and (N > 1) the second workload.
+--dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy; that step starts from the seeded initial state
+(see dump_outputs).
 """
 import argparse
 import ctypes as C
@@ -312,14 +317,28 @@ class Workload:
         self.opt.step()
         return met
 
+    def snapshot(self):
+        """Device copies of the seeded training state (weights, BN running statistics and counters, Adam moments and step)."""
+        m, o = self.model, self.opt
+        self._seed_state = ([t.clone() for t in (m.param_arena, m._buffer_arena, m._tracked_arena, o.exp_avg, o.exp_avg_sq)],
+                            o.step_count)
+
+    def restore(self):
+        """Back to the snapshot, enqueued on the compute stream: the next step computes from the same state in every run."""
+        m, o = self.model, self.opt
+        saved, o.step_count = self._seed_state
+        for dst, src in zip((m.param_arena, m._buffer_arena, m._tracked_arena, o.exp_avg, o.exp_avg_sq), saved):
+            dst.copy_(src)
+
     @property
     def plan(self):
         return self.model._last[0]
 
 
-def timed_region(w, steps, distributed, device):
+def timed_region(w, steps, distributed, device, restore_last=False):
     """EXACTLY `steps` steps between barrier + synchronize on both sides; per-step durations from events recorded on the
-    compute stream between steps (no host synchronisation inside the region).  Returns (elapsed s, max over ranks; per-step ms)."""
+    compute stream between steps (no host synchronisation inside the region).  Returns (elapsed s, max over ranks; per-step ms).
+    `restore_last`: the last step starts from w.snapshot()'s state (--dump-outputs)."""
     import torch.distributed as dist
     marks = [torch.cuda.Event(enable_timing=True) for _ in range(steps + 1)]
     if distributed:
@@ -329,6 +348,8 @@ def timed_region(w, steps, distributed, device):
     marks[0].record()
     met = None
     for i in range(steps):
+        if restore_last and i == steps - 1:
+            w.restore()
         met = w.step()
         marks[i + 1].record()
     torch.cuda.synchronize()
@@ -343,6 +364,39 @@ def timed_region(w, steps, distributed, device):
     return elapsed, per_step, met
 
 
+DUMP_SAMPLE = 1 << 22   # elements kept of a larger output (16 MB in fp32); three such arrays stay under 64 MB in all
+
+
+def _dump_array(t, k=DUMP_SAMPLE):
+    """The whole tensor as a flat float32 / float64 array, or a fixed sample of `k` elements of a larger one: the indices are a
+    seeded function of the element count alone, so every build draws the same elements."""
+    t = t.detach().reshape(-1)
+    if t.numel() > k:
+        idx = torch.randperm(t.numel(), generator=torch.Generator().manual_seed(0))[:k].sort().values
+        t = t[idx.to(t.device)]
+    dt = torch.float64 if t.dtype == torch.float64 else torch.float32
+    return t.to(dt).cpu().numpy()
+
+
+def dump_outputs(w, met, out_dir):
+    """What a caller of the timed step receives after its last step: the logits of the forward, the loss / metric tensors of
+    loss_backward(), the gradient arena, and the parameters and BN running statistics after Adam.  That step starts from the
+    seeded state (timed_region's restore_last): one step is reproducible up to the order of the fp32 weight-gradient atomics,
+    while steps chained through fp16 storage and Adam carry that rounding further with every step."""
+    import numpy as np
+    m = w.model
+    arrays = {"logits": m._last[1], "params": m.param_arena, "grads": m.grad_arena, "bn_buffers": m._buffer_arena}
+    arrays.update(met)
+    os.makedirs(out_dir, exist_ok=True)
+    total = 0
+    for name, t in arrays.items():
+        a = _dump_array(t)
+        total += a.nbytes
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
+    assert total <= 64 << 20, total
+    print(f"[bench] wrote {len(arrays)} arrays ({total / 2 ** 20:.1f} MB) to {out_dir}", file=sys.stderr, flush=True)
+
+
 def step_stats(per_step):
     return {"median": round(percentile(per_step, 0.5), 3), "p10": round(percentile(per_step, 0.1), 3),
             "p90": round(percentile(per_step, 0.9), 3), "n": len(per_step)}
@@ -355,14 +409,27 @@ def main():
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--config", default="c2", choices=sorted(CONFIGS))
     ap.add_argument("--also", default=None, choices=sorted(CONFIGS) + ["none"],
-                    help="N > 1 only: a second workload measured after the main one and reported under 'also' (default c3, BASELINE's 8-GPU d121 configuration)")
+                    help="N > 1 only: a second workload measured after the main one and reported under 'also' (default with --full: c3, BASELINE's 8-GPU d121 configuration)")
     ap.add_argument("--dtype", default=None, choices=["fp16", "bf16", "fp32"])
     ap.add_argument("--batch", type=int, default=None)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-profile", action="store_true")
-    ap.add_argument("--table", action="store_true", help="also print the per-kernel-class table to stderr")
-    ap.add_argument("--ops", type=int, default=0, help="print the N most expensive launches (per step) to stderr")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: profile pass + roofline, single-stream schedule, CPU baseline, (N > 1) the 'also' workload")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (float32 / float64, < 64 MB in all); "
+                         "that step starts from the seeded initial state, so runs with the same arguments agree up to rounding")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-profile", action="store_true", help="with --full: skip the profile pass, roofline and schedule comparison")
+    ap.add_argument("--table", action="store_true", help="also print the per-kernel-class table to stderr (implies --full)")
+    ap.add_argument("--ops", type=int, default=0, help="print the N most expensive launches (per step) to stderr (implies --full)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if args.table or args.ops:
+        args.full = True
+    if not args.full:
+        args.no_profile = args.no_cpu_baseline = True
+    if args.full and not args.no_profile and args.warmup < 1:
+        ap.error("the profile pass of --full needs --warmup >= 1")
 
     if args.gpus > 1 and "RANK" not in os.environ and not os.environ.get("DMM_FORCE_DIST"):
         sys.exit(spawn_ranks(args.gpus))
@@ -405,11 +472,13 @@ def main():
         c["batch"] = args.batch
     force = world == 1 and distributed  # DMM_FORCE_DIST: the N > 1 code path, collectives included, on one GPU
     w = Workload(c, device, rank, distributed, force)
+    if args.dump_outputs:
+        w.snapshot()
     step = w.step
 
     for _ in range(args.warmup):
         step()
-    plan = w.plan
+    plan = w.plan if args.warmup else None
     L = _lib.lib()
     full_classes, ops_list, dom_prefix = None, None, None
     if not args.no_profile:
@@ -434,7 +503,10 @@ def main():
         _lib.check(L.dmm_plan_profile_begin(plan.handle, min(EVENT_PASSES, args.steps)))
     if distributed:
         w.tail_events = []
-    elapsed, per_step, met = timed_region(w, args.steps, distributed, device)
+    elapsed, per_step, met = timed_region(w, args.steps, distributed, device, restore_last=bool(args.dump_outputs))
+    plan = w.plan
+    if args.dump_outputs and rank == 0:
+        dump_outputs(w, met, args.dump_outputs)
     loss = met["loss_per_class"].sum().item()
     comm = None
     if distributed and w.tail_events:
@@ -467,7 +539,7 @@ def main():
                     "single_stream_steps": 6}
 
     also = None
-    also_name = args.also or ("c3" if world > 1 and args.config == "c2" else "none")
+    also_name = args.also or ("c3" if args.full and world > 1 and args.config == "c2" else "none")
     if world > 1 and also_name != "none" and also_name != args.config:
         # BASELINE's multi-GPU configurations are the mid-fusion networks; `value` stays on the 1-GPU workload so that the 1 -> N
         # series is one weak-scaling curve, and the named 8-GPU configuration is measured right behind it on the same ranks

@@ -157,6 +157,19 @@ def put(store, name, d):
         store[f"{name}/{k}"] = v
 
 
+# The reference module runs in float64 for G2 / G3 / G4 / G7: an fp32 CPU run depends on the host's kernels and thread count
+# (summation order, amplified through up to 201 BatchNorm layers), an fp64 one does not.  Stored values are rounded to float32.
+GOLD_DTYPE = torch.float64
+
+
+def f64(*ts):
+    return tuple(t.to(GOLD_DTYPE) for t in ts)
+
+
+def f32np(t):
+    return t.detach().to(torch.float32).numpy().copy()
+
+
 def ref_config(H, arch: R.Arch):
     cfg = H.create_config("/tmp/dmmfods_golden")
     cfg = sys.modules["easydict"].EasyDict(cfg)
@@ -218,7 +231,7 @@ def run_reference_steps(M, H, arch, B, Hh, Ww, nsteps, weight_seed=123, data_see
     sd0 = R.make_state(arch, seed=weight_seed)
     model.load_state_dict(sd0, strict=True)
     assert int(model.num_params) == R.num_params(arch)
-    model.train()
+    model.to(GOLD_DTYPE).train()
     loss_fn = torch.nn.BCEWithLogitsLoss(reduction="none")  # A:54
     opt = torch.optim.Adam(model.parameters(), lr=cfg.optimizer.learning_rate,
                            betas=(cfg.optimizer.beta1, cfg.optimizer.beta2), eps=cfg.optimizer.eps,
@@ -226,7 +239,7 @@ def run_reference_steps(M, H, arch, B, Hh, Ww, nsteps, weight_seed=123, data_see
     thr = cfg.agent.iou_threshold
     store = {}
     for step in range(nsteps):
-        rgb, lidar, tgt = R.make_inputs(arch, B, Hh, Ww, seed=data_seed + step)
+        rgb, lidar, tgt = f64(*R.make_inputs(arch, B, Hh, Ww, seed=data_seed + step))
         pred = model(rgb, lidar)                                               # A:244
         cur = loss_fn(pred, tgt)                                               # A:247
         lpc = torch.sum(cur.detach(), dim=(0, 2, 3))                           # A:248
@@ -235,37 +248,37 @@ def run_reference_steps(M, H, arch, B, Hh, Ww, nsteps, weight_seed=123, data_see
         opt.zero_grad()                                                        # A:263
         cur.backward(torch.ones_like(cur.detach()))                            # A:264
         if step == 0:
-            store["logits_full"] = pred.detach().numpy().copy()
+            store["logits_full"] = f32np(pred)
             for k, p in model.named_parameters():
                 put(store, f"grad0/{k}", digest(p.grad, nsample=192))
         opt.step()                                                             # A:265
         put(store, f"step{step}/logits", digest(pred))
         store[f"step{step}/loss_per_class"] = lpc.numpy().astype(np.float64)
-        store[f"step{step}/iou"] = iou.numpy().copy()
-        store[f"step{step}/acc"] = acc.numpy().copy()
+        store[f"step{step}/iou"] = f32np(iou)
+        store[f"step{step}/acc"] = f32np(acc)
         if step in (0, nsteps - 1):
             for k, v in model.state_dict().items():
                 put(store, f"state{step}/{k}", digest(v.float(), nsample=192))
     # tight eval-mode pin: fresh weights, ONE train-mode forward (sets running stats), no optimiser step
     m2 = M.Dense_U_Net_lidar(ref_config(H, arch))
     m2.load_state_dict(R.make_state(arch, seed=weight_seed), strict=True)
-    m2.train()
+    m2.to(GOLD_DTYPE).train()
     with torch.no_grad():
-        rgb, lidar, tgt = R.make_inputs(arch, B, Hh, Ww, seed=data_seed)
+        rgb, lidar, tgt = f64(*R.make_inputs(arch, B, Hh, Ww, seed=data_seed))
         m2(rgb, lidar)
         m2.eval()
-        rgb, lidar, tgt = R.make_inputs(arch, B, Hh, Ww, seed=data_seed + 50)
-        store["eval1/logits_full"] = m2(rgb, lidar).numpy().copy()
+        rgb, lidar, tgt = f64(*R.make_inputs(arch, B, Hh, Ww, seed=data_seed + 50))
+        store["eval1/logits_full"] = f32np(m2(rgb, lidar))
         for k, v in m2.state_dict().items():
             if "running" in k or "tracked" in k:
                 put(store, f"eval1_state/{k}", digest(v.float(), nsample=192))
     model.eval()
     with torch.no_grad():
-        rgb, lidar, tgt = R.make_inputs(arch, B, Hh, Ww, seed=data_seed + 100)
+        rgb, lidar, tgt = f64(*R.make_inputs(arch, B, Hh, Ww, seed=data_seed + 100))
         pred = model(rgb, lidar)
-        store["eval/logits_full"] = pred.numpy().copy()
-        store["eval/iou"] = H.compute_IoU_whole_img_batch(pred, tgt, thr).numpy().copy()
-        store["eval/acc"] = H.compute_accuracy(tgt, pred, thr).numpy().copy()
+        store["eval/logits_full"] = f32np(pred)
+        store["eval/iou"] = f32np(H.compute_IoU_whole_img_batch(pred, tgt, thr))
+        store["eval/acc"] = f32np(H.compute_accuracy(tgt, pred, thr))
     return store
 
 
@@ -275,9 +288,13 @@ def g2_tiny(M, H):
         store = run_reference_steps(M, H, arch, B=2, Hh=64, Ww=96, nsteps=3)
         store["meta/arch"] = np.frombuffer(json.dumps(dict(TINY, variant=vname, B=2, H=64, W=96, nsteps=3,
                                                           weight_seed=123, data_seed=0)).encode(), dtype=np.uint8)
+        # the per-tensor state digests go to a file of their own: every committed file stays under 1 MiB
+        state = {k: store.pop(k) for k in [k for k in store if k.startswith(("state", "eval1_state"))]}
         path = os.path.join(GOLD, f"g2_tiny_{vname}.npz")
         np.savez_compressed(path, **store)
-        print("G2", vname, "->", os.path.getsize(path) // 1024, "KiB")
+        np.savez_compressed(os.path.join(GOLD, f"g2_tiny_{vname}_state.npz"), **state)
+        print("G2", vname, "->", os.path.getsize(path) // 1024, "KiB +",
+              os.path.getsize(os.path.join(GOLD, f"g2_tiny_{vname}_state.npz")) // 1024, "KiB")
 
 
 # ------------------------------------------------------------------ G4 C1 checksum
@@ -286,8 +303,8 @@ def g4_c1(M, H):
     cfg = ref_config(H, arch)
     model = M.densenet121_u_lidar(pretrained=False, config=cfg)
     model.load_state_dict(R.make_state(arch, seed=123), strict=True)
-    model.train()
-    rgb, lidar, tgt = R.make_inputs(arch, 1, 256, 384, seed=0)
+    model.to(GOLD_DTYPE).train()
+    rgb, lidar, tgt = f64(*R.make_inputs(arch, 1, 256, 384, seed=0))
     pred = model(rgb, lidar)
     cur = torch.nn.BCEWithLogitsLoss(reduction="none")(pred, tgt)
     cur.backward(torch.ones_like(cur.detach()))
@@ -320,17 +337,17 @@ def g3_layers(M, H):
         arch = variant_arch(G3_ARCH, vname)
         model = M.Dense_U_Net_lidar(ref_config(H, arch))
         model.load_state_dict(R.make_state(arch, seed=321), strict=True)
-        model.train()
+        model.to(GOLD_DTYPE).train()
         outs = {}
         mods = dict(model.named_modules())
         for name in G3_MODULES:
             if name in mods:
                 mods[name].register_forward_hook(lambda m, i, o, name=name: outs.__setitem__(name, o.detach()))
-        rgb, lidar, tgt = R.make_inputs(arch, 2, 64, 96, seed=7)
+        rgb, lidar, tgt = f64(*R.make_inputs(arch, 2, 64, 96, seed=7))
         pred = model(rgb, lidar)
         cur = torch.nn.BCEWithLogitsLoss(reduction="none")(pred, tgt)
         cur.backward(torch.ones_like(cur.detach()))
-        store = {"logits_full": pred.detach().numpy().copy()}
+        store = {"logits_full": f32np(pred)}
         for name, t in outs.items():
             put(store, f"out/{name}", digest(t, nsample=4096))
         for k, p_ in model.named_parameters():
@@ -396,16 +413,16 @@ def g7_configs(M, H):
         cfg = ref_config(H, arch)
         model = getattr(M, f"densenet{dn}_u_lidar")(pretrained=False, config=cfg)
         model.load_state_dict(R.make_state(arch, seed=wseed), strict=True)
-        model.train()
-        rgb, lidar, tgt = R.make_inputs(arch, B, Hh, Ww, seed=dseed)
+        model.to(GOLD_DTYPE).train()
+        rgb, lidar, tgt = f64(*R.make_inputs(arch, B, Hh, Ww, seed=dseed))
         pred = model(rgb, lidar)
         cur = torch.nn.BCEWithLogitsLoss(reduction="none")(pred, tgt)
         cur.backward(torch.ones_like(cur.detach()))
         thr = cfg.agent.iou_threshold
-        store = {"logits_full": pred.detach().numpy().copy(),
+        store = {"logits_full": f32np(pred),
                  "loss_per_class": torch.sum(cur.detach(), dim=(0, 2, 3)).numpy().astype(np.float64),
-                 "iou": H.compute_IoU_whole_img_batch(pred.detach(), tgt, thr).numpy().copy(),
-                 "acc": H.compute_accuracy(tgt, pred.detach(), thr).numpy().copy()}
+                 "iou": f32np(H.compute_IoU_whole_img_batch(pred.detach(), tgt, thr)),
+                 "acc": f32np(H.compute_accuracy(tgt, pred.detach(), thr))}
         for k, p_ in model.named_parameters():
             put(store, f"grad/{k}", digest(p_.grad, nsample=64))
         store["meta/case"] = np.frombuffer(json.dumps(dict(densenet=dn, variant=vname, B=B, H=Hh, W=Ww, weight_seed=wseed,

@@ -179,8 +179,8 @@ def test_bench_two_ranks_rehearsal():
     timing, MAX over ranks, one JSON line from rank 0 with n_gpus = 2 and the whole-job image rate."""
     import json
     root = os.path.dirname(os.path.dirname(__file__))
-    r = _torchrun([os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--config", "c1", "--no-cpu-baseline"],
-                  {"DMM_DIST_BACKEND": "gloo", "DMM_DIST_SAME_DEVICE": "1"})
+    r = _torchrun([os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--config", "c1", "--no-cpu-baseline",
+                   "--full"], {"DMM_DIST_BACKEND": "gloo", "DMM_DIST_SAME_DEVICE": "1"})
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
     assert len(lines) == 1 and lines[0].startswith("{"), r.stdout      # ONE line on stdout, whatever native libraries print

@@ -8,7 +8,7 @@ SRC="$HERE/../../dmmfods_amd/csrc"
 OUT="${1:-$HERE/_build}"
 mkdir -p "$OUT"
 CLANG=/opt/rocm/lib/llvm/bin/clang++
-FLAGS="-x hip --offload-host-only --offload-arch=gfx950 -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=undefined -fno-omit-frame-pointer -I/opt/rocm/include -D__HIP_PLATFORM_AMD__ -w $DRIVE_EXTRA_FLAGS"
+FLAGS="-x hip --offload-host-only --offload-arch=gfx950 -std=c++17 -O1 -g -fsanitize=address,undefined -fno-gpu-sanitize -fno-sanitize-recover=undefined -fno-omit-frame-pointer -I/opt/rocm/include -D__HIP_PLATFORM_AMD__ -w $DRIVE_EXTRA_FLAGS"
 pids=()
 cc() { $CLANG $FLAGS "${@:3}" -c "$1" -o "$OUT/$2" & pids+=($!); if [ ${#pids[@]} -ge 8 ]; then wait "${pids[0]}"; pids=("${pids[@]:1}"); fi; }
 for f in bw1 cf conv3 cvp cvw halo hf pig pointwise thin wg3 wg5 wgp wgpw; do cc "$SRC/$f.hip" "$f.o"; done
@@ -20,5 +20,5 @@ cc "$HERE/fake_hip.cpp" fake_hip.o
 cc "$HERE/drive.cpp" drive.o
 for p in "${pids[@]}"; do wait "$p"; done
 # (the host-only objects reference their embedded device image, which does not exist here: leave those symbols unresolved)
-$CLANG -fsanitize=address,undefined -o "$OUT/drive" "$OUT"/*.o -Wl,--unresolved-symbols=ignore-in-object-files -lpthread
+$CLANG -fsanitize=address,undefined -fno-gpu-sanitize -o "$OUT/drive" "$OUT"/*.o -Wl,--unresolved-symbols=ignore-in-object-files -lpthread
 echo "built $OUT/drive"

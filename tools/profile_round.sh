@@ -3,7 +3,7 @@
 set -o pipefail
 tag=${1:-r01}; out=gpurun_out/$tag; mkdir -p $out; export TMPDIR=/tmp
 B="python3 bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-profile"
-timeout -k 10 300 python3 bench.py --table --ops 2000 > $out/bench.json 2> $out/bench_classes_and_ops.txt || exit 1
+timeout -k 10 300 python3 bench.py --full --table --ops 2000 > $out/bench.json 2> $out/bench_classes_and_ops.txt || exit 1
 cat $out/bench.json
 timeout -k 10 200 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof -o run -- $B > $out/prof.log 2>&1 || exit 2
 cp $(find /tmp/prof -name "*kernel_stats.csv" | head -1) $out/kernel_stats.csv
@@ -32,7 +32,7 @@ python3 tools/pmc_sq.py /tmp/pmcS $out/pmc_sq_summary.csv || exit 7
 timeout -k 10 200 rocprofv3 --pmc SQ_LDS_BANK_CONFLICT SQ_ACTIVE_INST_LDS SQ_WAVE_CYCLES --output-format csv -d /tmp/pmcL -o run -- $B > $out/pmcL.log 2>&1 || exit 7
 python3 tools/pmc_lds.py /tmp/pmcL > $out/pmc_lds_bank_conflicts.txt || exit 7
 for cfg in c1 c3 c4 c5; do
-  timeout -k 10 240 python3 bench.py --config $cfg --steps 5 --warmup 2 --no-cpu-baseline --table > $out/bench_$cfg.json 2> $out/bench_${cfg}_classes.txt || exit 8
+  timeout -k 10 240 python3 bench.py --full --config $cfg --steps 5 --warmup 2 --no-cpu-baseline --table > $out/bench_$cfg.json 2> $out/bench_${cfg}_classes.txt || exit 8
 done
 DMM_FORCE_DIST=1 timeout -k 10 200 python3 bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-profile > $out/bench_c2_forced_dist_world1.json 2> $out/bench_c2_forced_dist.log || exit 9
 ls -la $out

@@ -4,7 +4,7 @@
 tag=$1; var=$2; shift 2; out=gpurun_out/$tag; mkdir -p $out
 for v in "$@"; do
   if [ "$v" = - ]; then unset $var; else export $var=$v; fi
-  timeout -k 10 200 python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline --table ${AB_ARGS} > $out/bench_$v.json 2> $out/bench_$v.txt || exit 1
+  timeout -k 10 200 python3 bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --table ${AB_ARGS} > $out/bench_$v.json 2> $out/bench_$v.txt || exit 1
   python3 - "$var=$v" $out/bench_$v.json $out/bench_$v.txt <<'PY'
 import json, sys, os
 tag, j, t = sys.argv[1:4]
