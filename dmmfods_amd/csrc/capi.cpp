@@ -251,6 +251,23 @@ int dmm_plan_bind(dmm_plan* plan, void* workspace, size_t workspace_bytes, float
   return DMM_OK;
 }
 
+// The invariant behind Op::impl: the family a plan recorded for a convolution launch (and shaped its launch list around: merged
+// phases, finish launches, compact gradients) is the family that took it.  `ran` = the families the launch noted.  Returns the
+// complaint, or an empty string.  The generic family beside another one is a launch that fell through; the ONE launch where that is
+// the design is wgp's two-segment form, whose 8-channel raw-input remainder stays with the generic kernel (launch_wgrad reports that
+// launch as wgp alone today; should the remainder ever be noted as well, the launch stays allowed - by this clause, not by silence).
+static std::string family_check(const Op& o, unsigned ran) {
+  if ((o.kind == OP_IGEMM ? o.c.M : o.w.M) <= 0) return std::string();   // an empty launch notes nothing
+  const bool recorded_ran = (ran >> o.impl) & 1u;
+  const bool generic_ran = (ran >> IMPL_GENERIC) & 1u;
+  const bool wgp_remainder = o.kind == OP_WGRAD && o.impl == IMPL_WGP && o.w.nseg == 2 && o.w.nphase == 0;
+  if (recorded_ran && (o.impl == IMPL_GENERIC || !generic_ran || wgp_remainder)) return std::string();
+  std::string names;
+  for (int f = 1; f < IMPL_COUNT; ++f)
+    if ((ran >> f) & 1u) names += (names.empty() ? "" : "+") + std::string(dmm_impl_name(f));
+  return std::string("launch '") + o.label + "': the plan recorded family " + dmm_impl_name(o.impl) + ", " + (names.empty() ? "none" : names) + " ran";
+}
+
 // Launches ops[begin, end) in order (end = 0: to the end of the list).
 // capturing: the calls are being recorded into a hipGraph (no profiling, no bucket events: launch_list records those behind the graph).
 static int run_ops(dmm_plan* p, std::vector<Op>& ops, hipStream_t st, int prof_which = -1, size_t begin = 0, size_t end = 0, bool capturing = false) {
@@ -347,6 +364,10 @@ static int run_ops(dmm_plan* p, std::vector<Op>& ops, hipStream_t st, int prof_w
     }
     const bool sel = selected(o);
     if (sel) hipEventRecord((hipEvent_t)(*evs)[2 * (ev_offset + i)], lst);
+    // the families noted by THIS launch: the thread's mask is set aside, read behind the launch and merged back (family_check)
+    const bool fam_check = (o.kind == OP_IGEMM || o.kind == OP_WGRAD) && o.impl != IMPL_AUTO;
+    const unsigned mask_before = g_impl_mask;
+    if (fam_check) g_impl_mask = 0;
     switch (o.kind) {
       case OP_MEMSET: e = hipMemsetAsync(o.ms.p, 0, o.ms.bytes, lst); break;
       case OP_COPY: e = hipMemcpyAsync(o.cp.dst, o.cp.src, o.cp.bytes, hipMemcpyDeviceToDevice, lst); break;
@@ -370,7 +391,14 @@ static int run_ops(dmm_plan* p, std::vector<Op>& ops, hipStream_t st, int prof_w
     }
     if (host_prof && o.kind < 32) { const double t2 = now(); hp_fork[o.kind] += hp_t1 - hp_t0; hp_launch[o.kind] += t2 - hp_t1; hp_n[o.kind]++; }
     if (e != hipSuccess) join();  // leave the main stream ordered after whatever the side stream already got
+    if (e != hipSuccess && fam_check) g_impl_mask |= mask_before;  // (the thread's mask keeps what earlier launches noted)
     if (e != hipSuccess) return fail(DMM_ERR_HIP, "op " + std::to_string(i) + " kind " + std::to_string(o.kind) + ": " + hipGetErrorString(e));
+    if (fam_check) {
+      const unsigned ran = g_impl_mask;
+      g_impl_mask = mask_before | ran;
+      const std::string why = family_check(o, ran);
+      if (!why.empty()) { join(); return fail(DMM_ERR_STATE, why); }
+    }
     if (sel) hipEventRecord((hipEvent_t)(*evs)[2 * (ev_offset + i) + 1], lst);
     if (pack_pending && o.leaf == 2) hipEventRecord((hipEvent_t)p->join_events[nside], lst);
     if (o.signal >= 0 && !capturing) {  // a gradient bucket is final on this stream from here on

@@ -253,6 +253,7 @@ void wgp_set_enabled(bool on) { g_wgp = on; }
 // the wave-specialised form (wgpw.hip)
 hipError_t launch_wgpw(const WgradArgs& a, int dtype, int ntap, int nj, int tiles_y, int tiles_x, int ntiles, int tiles_per_wg, int nsplit, int nct,
                        int ncot, int dymin, int dxmin, const int* ph_dymin, const int* ph_dxmin, int nwg, hipStream_t st);
+bool wgpw_accepts(const WgradArgs& a, int ntap, int nj);   // what launch_wgpw takes (operands below 4 GiB, its instantiations)
 
 
 template <typename T, int NTAP, int NJ, int PQ>
@@ -332,6 +333,13 @@ hipError_t launch_wgp(const WgradArgs& a, int dtype, hipStream_t st) {
   }
   const int ntap = x.ntaps;
   const int nj = (ntap <= 2 && a.N % 128 == 0 && a.nphase == 0) ? 4 : 2;   // (multi-phase launches: 64 output channels per workgroup in every phase)
+  // Which form takes the launch is decided HERE, in front of the dry return: the family a plan records (wgrad_pick) must be one that
+  // really runs.  The wave-specialised form where it accepts; else this file's kernel, which forms its addresses in 64 bits (operands
+  // of 4 GiB and more) but has neither a one-tap form nor phases of different tap counts - those launches are refused, the plan then
+  // keeps the phases apart and picks per phase.
+  const int pq = y.q ? 2 : 0;
+  const bool use_ws = ws && pq == 0 && wgpw_accepts(a, ntap, nj);
+  if (!use_ws && (mixed || !((ntap == 4 && nj == 2) || (ntap == 2 && (nj == 4 || nj == 2))))) return hipErrorNotSupported;
   if (g_ctl.dry) return hipSuccess;
   WgpArgs g;
   g.w = a;
@@ -355,8 +363,7 @@ hipError_t launch_wgp(const WgradArgs& a, int dtype, hipStream_t st) {
   g.nsplit = (g.ntiles + g.tiles_per_wg - 1) / g.tiles_per_wg;
   const int units = g.nsplit * pairs;
   const int nwg = a.nphase > 0 ? ((units + 7) / 8) * 8 * nph : units;
-  const int pq = y.q ? 2 : 0;
-  if (ws && pq == 0) {
+  if (use_ws) {
     note_impl(IMPL_WGPW);   // (beside IMPL_WGP, which the dispatcher notes: the family is wgp, this says which form ran)
     return launch_wgpw(a, dtype, ntap, nj, g.tiles_y, g.tiles_x, g.ntiles, g.tiles_per_wg, g.nsplit, g.nct, g.ncot, dymin, dxmin, ph_dymin, ph_dxmin,
                        nwg, st);

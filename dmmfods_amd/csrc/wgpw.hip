@@ -366,21 +366,29 @@ static hipError_t launch_wgpw_t(const WgpwArgs& g, int nwg, hipStream_t st) {
   return hipGetLastError();
 }
 
+// What this form covers of the launches launch_wgp (wgp.hip) has validated: both operands below 4 GiB (32-bit byte offsets in the
+// loaders) and the kernel instantiations at the end of launch_wgpw.  launch_wgp asks BEFORE its dry return, so that the family a plan
+// records is decided with the same test the launch will meet; launch_wgpw asks again - one predicate, two callers, no second copy.
+bool wgpw_accepts(const WgradArgs& a, int ntap, int nj) {
+  if ((double)a.B * a.seg[0].Hs * a.seg[0].Ws * a.seg[0].ld * 2.0 >= 4294967296.0 || (double)a.B * a.dy.Hs * a.dy.Ws * a.dy.ld * 2.0 >= 4294967296.0)
+    return false;
+  if (a.nphase == 4) return nj == 2;
+  if (a.nphase != 0) return false;
+  return (ntap == 4 && nj == 2) || (ntap == 2 && (nj == 4 || nj == 2)) || (ntap == 1 && (nj == 4 || nj == 2));
+}
+
 // Called by launch_wgp (wgp.hip) with a launch it has already validated and laid out; returns hipErrorNotSupported for the shapes this
-// form does not cover.
+// form does not cover (wgpw_accepts).
 hipError_t launch_wgpw(const WgradArgs& a, int dtype, int ntap, int nj, int tiles_y, int tiles_x, int ntiles, int tiles_per_wg, int nsplit, int nct,
                        int ncot, int dymin, int dxmin, const int* ph_dymin, const int* ph_dxmin, int nwg, hipStream_t st) {
-  // (32-bit byte offsets in the loaders)
-  if ((double)a.B * a.seg[0].Hs * a.seg[0].Ws * a.seg[0].ld * 2.0 >= 4294967296.0 || (double)a.B * a.dy.Hs * a.dy.Ws * a.dy.ld * 2.0 >= 4294967296.0)
-    return hipErrorNotSupported;
+  if (!wgpw_accepts(a, ntap, nj)) return hipErrorNotSupported;
   WgpwArgs g;
   g.w = a;
   g.tiles_y = tiles_y; g.tiles_x = tiles_x; g.ntiles = ntiles; g.tiles_per_wg = tiles_per_wg; g.nsplit = nsplit;
   g.nct = nct; g.ncot = ncot; g.dymin = dymin; g.dxmin = dxmin;
   for (int ph = 0; ph < 4; ++ph) { g.ph_dymin[ph] = ph_dymin[ph]; g.ph_dxmin[ph] = ph_dxmin[ph]; }
   const bool f = dtype == DT_F16;
-  if (a.nphase == 4) return nj == 2 ? (f ? launch_wgpw_multi_t<f16>(g, nwg, st) : launch_wgpw_multi_t<bf16>(g, nwg, st)) : hipErrorNotSupported;
-  if (a.nphase != 0) return hipErrorNotSupported;
+  if (a.nphase == 4) return f ? launch_wgpw_multi_t<f16>(g, nwg, st) : launch_wgpw_multi_t<bf16>(g, nwg, st);
   if (ntap == 4 && nj == 2) return f ? launch_wgpw_t<f16, 4, 2>(g, nwg, st) : launch_wgpw_t<bf16, 4, 2>(g, nwg, st);
   if (ntap == 2 && nj == 4) return f ? launch_wgpw_t<f16, 2, 4>(g, nwg, st) : launch_wgpw_t<bf16, 2, 4>(g, nwg, st);
   if (ntap == 2 && nj == 2) return f ? launch_wgpw_t<f16, 2, 2>(g, nwg, st) : launch_wgpw_t<bf16, 2, 2>(g, nwg, st);

@@ -477,6 +477,11 @@ hipError_t launch_wgrad(WgradArgs a, int dtype, bool mfma, hipStream_t st, int i
       a.rows_per_split = 0;
     } else if (e != hipErrorNotSupported) return e;
   }
+  // what the generic kernel does not implement must fail here, not compute something else (as launch_igemm): merged parity phases
+  // and per-phase tap counts belong to wgp, the factor forms (sbuf) to wg5 - the generic kernel would compute phase 0 alone / write dpack
+  if (a.nphase != 0 || a.sbuf != nullptr) return hipErrorNotSupported;
+  for (int ph = 0; ph < 4; ++ph)
+    if (a.ph_ntaps[ph] != 0) return hipErrorNotSupported;
   if (!wgp_took) note_impl(IMPL_GENERIC);  // (wgp for segment 0 + the generic kernel for the raw-input remainder reports wgp)
   const int BK = dtype == DT_F32 ? 16 : 32;
   const int bmw = dtype == DT_F32 ? 32 : 64;

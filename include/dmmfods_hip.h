@@ -35,7 +35,7 @@ typedef enum {
   DMM_ERR_INVALID = -1,      /* bad argument / unsupported configuration (Python raises AttributeError/ValueError) */
   DMM_ERR_SHAPE = -2,        /* spatial size not a multiple of 32 (reference: ValueError from ConvTranspose2d) */
   DMM_ERR_HIP = -3,          /* a HIP call failed */
-  DMM_ERR_STATE = -4,        /* plan not bound / wrong call order */
+  DMM_ERR_STATE = -4,        /* plan not bound / wrong call order / a launch that the kernel family its plan recorded did not take */
   DMM_ERR_NO_DEVICE = -5
 } dmm_status;
 

@@ -296,6 +296,182 @@ def test_bind_checks_the_bound_pass_against_the_sizing_pass(host_drive):
     assert r.returncode == 2 and "-> -4" in r.stderr and "sizing pass" in r.stderr, (r.stdout + r.stderr)[-2000:]
 
 
+def _picks(host_drive, arch, dtype, b, h, w, envx=None):
+    """tools/hoststub/drive `picks`: (returncode, disagreement lines, one record per convolution launch, whole output)."""
+    env = {k: v for k, v in os.environ.items() if not k.startswith("DMM_")}
+    env.update(envx or {}, ASAN_OPTIONS="detect_leaks=0:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
+    r = subprocess.run([host_drive, "picks", arch, dtype, str(b), str(h), str(w)], env=env, capture_output=True, text=True, timeout=600)
+    picks = []
+    for ln in r.stdout.splitlines():
+        m = re.match(r"(\w+) PICK (\w+) (\S+) recorded (\w+) mask (0x[0-9a-f]+|0) nphase (\d+) x_bytes (\d+) dy_bytes (\d+)$", ln)
+        if m:
+            picks.append(dict(list=m[1], kind=m[2], label=m[3], recorded=m[4], mask=int(m[5], 16), nphase=int(m[6]), x_bytes=int(m[7]),
+                              dy_bytes=int(m[8])))
+    return r.returncode, [ln for ln in r.stdout.splitlines() if " MISMATCH " in ln], picks, r.stdout + r.stderr
+
+
+FAMILY_BIT = {n: 1 << i for i, n in enumerate(["auto", "generic", "thin", "conv3", "cvp", "halo", "wg3", "wg5", "wgp", "pig", "bw1", "hf", "cf",
+                                                "wgpw", "cvw"])}
+GIB4 = 1 << 32
+
+
+def test_recorded_family_takes_every_launch(host_drive):
+    """A plan decides the kernel family of every convolution launch while it is built (igemm_pick / wgrad_pick: a dry call of the
+    launchers) and shapes its launch list around the decision - merged parity phases, finish launches, compact gradients.  The family
+    that takes the launch at run time must be that one.  `drive picks` binds the plan to address space that is never touched and calls
+    the launcher of every OP_IGEMM / OP_WGRAD / OP_BW1 record with the recorded family under the fake runtime: the recorded family must
+    be among those that noted the launch, the generic family must not be noted beside another (but for wgp's two-segment launch, whose
+    8-channel remainder is the generic kernel's), the call must succeed.
+
+    Before this test: d121e fp16 at 14 / 28 / 56 x 1280 x 1920 had 1 / 3 / 4 launches (`wgp.n64/h.refine0`, `wgp.n128/d.TC_4`, `d.TC_3`,
+    `d.TC_2`) recorded as wgp with four merged phases that wgpw.hip refused at run time (an operand of 4 GiB or more: 32-bit byte offsets)
+    and the generic kernel then took WITHOUT implementing phases: three quarters of the weight gradient stayed zero, no error.
+
+    `drive picks` on the commit before the fix (d121e f16, batch x 1280 x 1920; 13 and 27-without-the-head-line agree):
+        14: bwd MISMATCH wgp.n64/h.refine0   recorded wgp  ran-last generic  mask 0x2002 rc 0 nphase 4      -> 1 disagree, PICKS FAILED
+        28: the same line + wgp.n128/d.TC_4 + wgp.n128/d.TC_3 (same fields)                                   -> 3 disagree
+        56: + wgp.n128/d.TC_2                                                                                 -> 4 disagree
+
+    The first 4 GiB crossing of every architecture here is the head's: the full-resolution 64-channel gradient of `refine0` (and the
+    equally large input of `refine1`), 2 * 64 * B * H * W bytes - twice the next largest operand with a guard (TC_4's 128 channels at
+    half resolution) - so B * H * W >= 2**25: batch 14 at 1280 x 1920, batch 55 at 640 x 960.  The test checks that from the records
+    (largest operand below 4 GiB on one side, at or above on the other) instead of trusting the arithmetic."""
+    cases = [(a, d, b, h, w, e) for a, d, b, h, w, e in HOST_DRIVE_CASES]
+    first = lambda h, w: -(-GIB4 // (2 * 64 * h * w))
+    assert first(1280, 1920) == 14 and first(640, 960) == 55
+    # the next crossing: 128 channels at half resolution - the head's forward input (hf.hip:382) and the last decoder stage's gradient
+    first_half = -(-GIB4 // (2 * 128 * 640 * 960))
+    assert first_half == 28
+    cases += [("d121e", dt, b, 1280, 1920, {}) for dt in ("f16", "bf16") for b in (13, 14, first_half - 1, first_half, 56)]
+    crossing = [("d201m", "bf16", first(640, 960) - 1, 640, 960, {}), ("d201m", "bf16", first(640, 960), 640, 960, {}),
+                ("d169m", "f16", first(1280, 1920) - 1, 1280, 1920, {}), ("d169m", "f16", first(1280, 1920), 1280, 1920, {})]
+    cases += crossing
+    largest = {}
+    for case in cases:
+        arch, dtype, b, h, w, envx = case
+        rc, bad, picks, out = _picks(host_drive, arch, dtype, b, h, w, envx)
+        assert not bad and rc == 0 and "PICKS OK" in out, (case, bad, out[-3000:])
+        assert {p["list"] for p in picks} == {"fwd", "eval", "bwd"} and len(picks) > 20, (case, len(picks))
+        assert all(p["recorded"] != "auto" for p in picks), case
+        largest[(arch, dtype, b, h, w)] = max(max(p["x_bytes"], p["dy_bytes"]) for p in picks)
+        for p in picks:
+            # no merged wgp launch is left on an operand of 4 GiB or more unless a kernel that accepts it ran: wgp.hip's own kernel
+            # (64-bit addresses), i.e. wgp noted WITHOUT its wave-specialised form and without the generic kernel
+            if p["kind"] == "wgrad" and p["label"].startswith("wgp.") and p["nphase"] > 0 and max(p["x_bytes"], p["dy_bytes"]) >= GIB4:
+                assert p["mask"] == FAMILY_BIT["wgp"], (case, p)
+            if p["mask"] & FAMILY_BIT["wgpw"]:
+                assert max(p["x_bytes"], p["dy_bytes"]) < GIB4 and p["recorded"] == "wgp", (case, p)
+            if p["mask"] & (FAMILY_BIT["pig"] | FAMILY_BIT["cf"] | FAMILY_BIT["hf"] | FAMILY_BIT["cvw"]):
+                assert p["x_bytes"] < GIB4, (case, p)
+        if arch == "d121e" and h == 1280:
+            head = {p["label"]: p for p in picks if p["list"] == "bwd" and p["kind"] == "wgrad"}
+            r0 = head["wgp.n64/h.refine0"]
+            # the head's weight gradient stays ONE merged launch on either side of the limit; the form of the kernel changes
+            assert r0["nphase"] == 4 and r0["mask"] == (FAMILY_BIT["wgp"] | (FAMILY_BIT["wgpw"] if b < 14 else 0)), (case, r0)
+            # hf.hip:382 (the head's forward; no single-kernel entry point builds its two segments): hf below 4 GiB of half-resolution
+            # input (batch 27: 4246732800 bytes), conv3 from batch 28 on
+            hf = [p for p in picks if p["list"] == "fwd" and p["label"].endswith("/h.refine0")]
+            assert len(hf) == 1 and hf[0]["recorded"] == ("hf" if b < first_half else "conv3"), (case, hf)
+            assert (hf[0]["x_bytes"] < GIB4) == (b < first_half), (case, hf)
+            # ConvTranspose stages (1, 2, 2, 4 taps): merged below the limit; per phase above it, the one-tap phase on the generic kernel
+            tc4 = [p for p in picks if p["list"] == "bwd" and p["kind"] == "wgrad" and p["label"].endswith("/d.TC_4")]
+            if b < first_half:
+                assert len(tc4) == 1 and tc4[0]["nphase"] == 4 and tc4[0]["mask"] == FAMILY_BIT["wgp"] | FAMILY_BIT["wgpw"], (case, tc4)
+            else:
+                assert sorted(p["recorded"] for p in tc4) == ["generic", "wgp", "wgp", "wgp"] and all(p["nphase"] == 0 for p in tc4), (case, tc4)
+    for arch, dtype, b, h, w, _ in crossing:
+        below = b == first(h, w) - 1
+        assert (largest[(arch, dtype, b, h, w)] < GIB4) == below, (arch, b, largest[(arch, dtype, b, h, w)])
+
+
+def test_a_launch_its_recorded_family_did_not_take_is_an_error(host_drive):
+    """The check itself: dmm_plan_forward / _loss_backward compare, at every convolution launch, the family the plan recorded with the
+    families that noted the launch.  Provoked by rewriting one record after bind (a dense 3x3 weight gradient, wg3, recorded as wg5:
+    wg5 refuses the shape and the generic kernel takes it): the pass returns DMM_ERR_STATE (-4) and names label, recorded family and
+    what ran.  Without the check the generic kernel would run a launch list that was shaped for another family, silently."""
+    env = {k: v for k, v in os.environ.items() if not k.startswith("DMM_")}
+    env.update(ASAN_OPTIONS="detect_leaks=0", DRIVE_TAMPER_RECORDED_FAMILY="1")
+    r = subprocess.run([host_drive, "d121e", "f16", "2", "64", "96", "1"], env=env, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 2 and "-> -4" in r.stderr, (r.stdout + r.stderr)[-2000:]
+    assert re.search(r"launch 'wg3\.\S+': the plan recorded family wg5, generic ran", r.stderr), r.stderr[-2000:]
+
+
+def _single(host_drive, entry, dtype, B, H, W, Cin, Cout, R, pad, transposed=0, mode=0):
+    env = {k: v for k, v in os.environ.items() if not k.startswith("DMM_")}
+    env.update(ASAN_OPTIONS="detect_leaks=0:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
+    r = subprocess.run([host_drive, "single", entry, dtype] + [str(v) for v in (B, H, W, Cin, Cout, R, pad, transposed, mode)], env=env,
+                       capture_output=True, text=True, timeout=600)
+    m = re.search(r"^SINGLE \w+ rc (-?\d+) last (\w+) ran (\S+) launches (\d+) x_bytes (\d+) y_bytes (\d+)", r.stdout, re.M)
+    assert r.returncode == 0 and m, (r.stdout + r.stderr)[-3000:]
+    return dict(rc=int(m[1]), last=m[2], ran=set(m[3].split("+")), x_bytes=int(m[5]), y_bytes=int(m[6]), out=r.stdout)
+
+
+def test_family_refusal_boundaries_single_launch(host_drive):
+    """Every family that addresses an operand with 32-bit byte offsets refuses operands of 4 GiB and more.  Through the single-kernel
+    entry points under the fake runtime (the large operands are PROT_NONE address space: a host access would be a fault; what the entry
+    points zero or upload is real memory), one shape just below each guard and one at it, all in 16-bit storage (2 bytes):
+      pig.hip:255      1x1 forward, 128 channels:          2 * M * 128             -> M = 4095 * 4096 | 4096 * 4096;  fallback generic
+      bw1.hip:438-439  fused 1x1 backward, 128 -> 128:     2 * M * 128 (x, gx, dy)  -> the same M;  at the limit DMM_ERR_INVALID (header), and
+                       the pair of entry points a caller uses instead (dmm_conv_dgrad_ex, dmm_conv_wgrad_ex) runs the generic kernels
+      cf.hip:258       dense 3x3 forward, 128 -> 32:       2 * B * H * W * 128     -> 4088 x 4096 | 4096 x 4096 (whole 8 x 16 tiles);  conv3
+      cvw.hip:389      ConvTranspose forward, 128 -> 128:  2 * B * H * W * 128     -> 4095 x 4096 | 4096 x 4096;  cvp without its cvw form
+                       (cvw.hip:390, the packed weights' span, cannot be reached: cvw takes at most 256 input channels)
+      wgpw.hip:374     ConvTranspose weight gradient:      2 * B * 2H * 2W * 128 (dy) -> 2047 x 2048 | 2048 x 2048;  wgp.hip's own kernel for
+                       the 2- and 4-tap phases, the generic kernel for the one-tap phase (wgp.hip has no one-tap form)
+    hf.hip:382 needs the head's two-segment launch, which no entry point builds: test_recorded_family_takes_every_launch covers it in a plan.
+    dmm_last_impl names the dispatcher's family (cvp, wgp) with either form; the mask says which form ran."""
+    below = _single(host_drive, "fwd", "f16", 1, 4095, 4096, 128, 128, 1, 0)
+    at = _single(host_drive, "fwd", "f16", 1, 4096, 4096, 128, 128, 1, 0)
+    assert below["x_bytes"] < GIB4 == at["x_bytes"]
+    assert (below["rc"], below["last"], below["ran"]) == (0, "pig", {"pig"}), below
+    assert (at["rc"], at["last"], at["ran"]) == (0, "generic", {"generic"}), at
+
+    below = _single(host_drive, "fused", "bf16", 1, 4095, 4096, 128, 128, 1, 0)
+    at = _single(host_drive, "fused", "bf16", 1, 4096, 4096, 128, 128, 1, 0)
+    assert below["x_bytes"] < GIB4 == at["x_bytes"]
+    assert (below["rc"], below["last"], below["ran"]) == (0, "bw1", {"bw1"}), below
+    assert at["rc"] == -1 and at["ran"] == {"none"} and "not a pair bw1.hip fuses" in at["out"], at      # DMM_ERR_INVALID, nothing launched
+    for entry in ("dgrad", "wgrad"):
+        alt = _single(host_drive, entry, "bf16", 1, 4096, 4096, 128, 128, 1, 0)
+        assert (alt["rc"], alt["last"], alt["ran"]) == (0, "generic", {"generic"}), (entry, alt)
+
+    below = _single(host_drive, "fwd", "bf16", 1, 4088, 4096, 128, 32, 3, 1)
+    at = _single(host_drive, "fwd", "bf16", 1, 4096, 4096, 128, 32, 3, 1)
+    assert below["x_bytes"] < GIB4 == at["x_bytes"]
+    assert (below["rc"], below["last"], below["ran"]) == (0, "cf", {"cf"}), below
+    assert (at["rc"], at["last"], at["ran"]) == (0, "conv3", {"conv3"}), at
+
+    below = _single(host_drive, "fwd", "f16", 1, 4095, 4096, 128, 128, 3, 1, transposed=1)
+    at = _single(host_drive, "fwd", "f16", 1, 4096, 4096, 128, 128, 3, 1, transposed=1)
+    assert below["x_bytes"] < GIB4 == at["x_bytes"]
+    assert (below["rc"], below["last"], below["ran"]) == (0, "cvp", {"cvp", "cvw"}), below
+    assert (at["rc"], at["last"], at["ran"]) == (0, "cvp", {"cvp"}), at
+
+    below = _single(host_drive, "wgrad", "f16", 1, 2047, 2048, 128, 128, 3, 1, transposed=1)
+    at = _single(host_drive, "wgrad", "f16", 1, 2048, 2048, 128, 128, 3, 1, transposed=1)
+    assert below["y_bytes"] < GIB4 == at["y_bytes"] and at["x_bytes"] < GIB4
+    assert (below["rc"], below["last"], below["ran"]) == (0, "wgp", {"wgp", "wgpw"}), below
+    assert (at["rc"], at["last"], at["ran"]) == (0, "wgp", {"wgp", "generic"}), at
+
+
+def test_generic_weight_gradient_refuses_what_it_does_not_implement(host_drive):
+    """the generic weight-gradient kernel computes ONE phase with the launch's own taps into dpack.  Handed merged
+    phases (nphase = 4), per-phase tap counts (ph_ntaps) or wg5's factor form (sbuf) it used to run anyway and return hipSuccess - which is
+    what let a wgp launch that wgpw.hip refused finish as a quarter of a weight gradient.  launch_wgrad(..., IMPL_GENERIC) now returns
+    hipErrorNotSupported (801) for each, launches nothing (the fake runtime's launch counter stands still) and notes no family (the
+    thread's mask stays empty: a family that launched nothing is not named); plain arguments launch and note `generic`."""
+    env = {k: v for k, v in os.environ.items() if not k.startswith("DMM_")}
+    env.update(ASAN_OPTIONS="detect_leaks=0:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
+    r = subprocess.run([host_drive, "refuse"], env=env, capture_output=True, text=True, timeout=600)
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("REFUSE ")]
+    assert r.returncode == 0, (r.stdout + r.stderr)[-3000:]
+    assert lines[:4] == ["REFUSE variant 0 rc 0 launches 1 mask 0x2 ok", "REFUSE variant 1 rc 801 launches 0 mask 0 ok",
+                         "REFUSE variant 2 rc 801 launches 0 mask 0 ok", "REFUSE variant 3 rc 801 launches 0 mask 0 ok"], lines
+    # the one launch where the generic kernel runs beside another family by design (wgp's two-segment form): passes the per-launch
+    # check with the families it notes today - wgp and its wave-specialised form (1 << 8 | 1 << 13)
+    assert len(lines) == 5 and lines[4].startswith("REFUSE variant 4 rc 0 ") and lines[4].endswith(" mask 0x2100 ok"), lines
+
+
 def test_config_fields_match_reference():
     from dmmfods_amd.utils.Dense_U_Net_lidar_helper import create_config, get_config
     cfg = get_config("/tmp/x")
@@ -439,6 +615,13 @@ def test_inline_assembly_loads_are_waited_for_before_use():
                         os.path.join(root, "dmmfods_amd", "csrc", "cf.hip"), "cf_kernel"], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-2000:]
     assert r.stdout.count("0 violations") == 2, r.stdout     # cf.hip (the dense 3x3 forward on the large maps): f16 / bf16
+    # round 5's wave-specialised forms of the parity-phase kernels: the same loader pattern (instantiations: merged phases f16 / bf16;
+    # (1, 2, 2, 2, 4 taps) x (2 or 4 column tiles) x f16 / bf16; ConvTranspose forward f16 / bf16)
+    for src, kern, count in (("wgpw.hip", "wgpw_multi_kernel", 2), ("wgpw.hip", "wgpw_kernel", 10), ("cvw.hip", "cvw_kernel", 2)):
+        r = subprocess.run([sys.executable, os.path.join(root, "tools", "check_asm_loads.py"),
+                            os.path.join(root, "dmmfods_amd", "csrc", src), kern], capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, (kern, r.stdout[-3000:] + r.stderr[-2000:])
+        assert r.stdout.count("0 violations") == count, (kern, r.stdout)
 
 
 def test_fold_lane_algebra():

@@ -149,6 +149,126 @@ def test_eight_channel_and_upsampled_kernels_against_torch(lab, dtype):
     assert lab.backward_case("up2 3x3 128->64 q", dtype, 1, 9, 7, 128, 64, 3, 3, 1, mode=1, with_q=1, what="dgrad", expect="generic")
 
 
+LARGE_OPERANDS = [
+    # name, entry, dtypes, B (images of 512 x 512), Cin, Cout, R, pad, transposed, mode, families that must note the launch(es) - exactly
+    # weight gradients whose dy spans 4 GiB (wgpw.hip:374 refuses): the head's 3x3 over the upsampled map as this ABI builds it (ONE launch,
+    # nine taps on the upsampled source: the generic kernel) and the same widths as ConvTranspose phases (wgp.hip's own kernel, the <4, 2>
+    # instantiation of the head's merged launch, for the 2- and 4-tap phases; the generic kernel for the one-tap phase)
+    # (NOT the plan's route: the plan splits this convolution into four parity phases on wgp - the plan-level test below, fp16 and bf16)
+    ("up2 3x3 128->64 as one nine-tap launch, dy 4 GiB", "wgrad", (1, 2), 32, 128, 64, 3, 1, 0, 1, {"generic"}),
+    ("convT 128->64, dy 4 GiB", "wgrad", (1, 2), 32, 128, 64, 3, 1, 1, 0, {"wgp", "generic"}),
+    ("convT 128->128, dy 4 GiB", "wgrad", (1,), 16, 128, 128, 3, 1, 1, 0, {"wgp", "generic"}),       # the last decoder stage's
+    ("1x1 128->128, x 4 GiB", "fwd", (1,), 64, 128, 128, 1, 0, 0, 0, {"generic"}),                   # pig.hip:255 refuses
+    ("3x3 128->32, x 4 GiB", "fwd", (1,), 64, 128, 32, 3, 1, 0, 0, {"conv3"}),                       # cf.hip:258 refuses
+    ("convT 128->128, x 4 GiB", "fwd", (1,), 64, 128, 128, 3, 1, 1, 0, {"cvp"}),                     # cvw.hip:389 refuses: cvp.hip's own kernel
+    ("1x1 128->128, x 4 GiB", "dgrad", (1,), 64, 128, 128, 1, 0, 0, 0, {"generic"}),                 # bw1.hip:438 refuses the fused pair:
+    ("1x1 128->128, x 4 GiB", "wgrad", (1,), 64, 128, 128, 1, 0, 0, 0, {"generic"}),                 # its two halves, one entry point each
+]
+
+
+@pytest.mark.parametrize("case", [c[:2] + (dt,) + c[3:] for c in LARGE_OPERANDS for dt in c[2]],
+                         ids=[f"{c[1]}-{c[0].replace(' ', '_').replace(',', '').replace('->', 'to')}-{'fp16' if dt == 1 else 'bf16'}" for c in LARGE_OPERANDS for dt in c[2]])
+def test_fallback_kernels_on_operands_of_4_gib(lab, case):
+    """The families that address an operand with 32-bit byte offsets (pig, cf, cvw, wgpw, bw1) refuse operands of 4 GiB and more, and
+    the generic / conv3 / cvp / wgp kernels take those launches (64-bit addresses: DESIGN 2).  No test had run them there.  Each case is
+    the smallest whole number of 512 x 512 images that reaches its guard (B * 512 * 512 * C * 2 bytes = 4 GiB exactly), through the C ABI,
+    the families that ran asserted as a set, against torch fp32 on the GPU on the same 16-bit-rounded operands, chunk by chunk
+    (tools/gpu_lab.py large_operand_case) at the per-kernel tolerances of this file: 3e-3 (fp16) / 2.5e-2 (bf16) of the tensor's maximum.
+    (The head's own merged four-phase launch exists only inside a plan: test_plan_whose_head_gradient_spans_4_gib_... below.)
+    Every operand here is exactly 2**32 bytes = 2**31 16-bit elements (only the ConvTranspose output, 16 GiB, goes beyond), where a signed
+    32-bit ELEMENT index would still pass: these cases show the kernels right at the smallest size the guards hand them; that the
+    addresses are formed in 64 bits beyond it rests on the reading of the sources ("Operands of 4 GiB and more").
+
+    The reference's own error over 8.4 (4.2) million pixels per weight, measured on the reference alone and asserted below a tenth of the
+    tolerance: the summed weight gradient from chunks of one against chunks of two images, and fp32 against fp64 accumulation of the
+    per-chunk results.  Chunks are added up in fp64 whatever the measurement says.  Measured on an MI355X (every run prints them as
+    [ref_chunkings=...] [ref_fp32_accumulation=...]): two chunkings 7e-7 ... 2.2e-6, fp32 against fp64 accumulation 1.3e-7 ... 2.4e-7
+    of the tensor's maximum - against tolerances of 3e-3 / 2.5e-2; the kernels themselves: weight gradients 1.4e-5 ... 1.9e-5 (fp16) and
+    1.7e-6 ... 2.6e-6 (bf16), forward outputs 3.0e-4 ... 3.5e-4, the data gradient 4.2e-4, its two sums 3.5e-6 / 2.9e-6.  Peak memory
+    5.3 ... 13.9 GiB, 23.0 GiB for the ConvTranspose forward (16 GiB of output)."""
+    name, what, dtype, B, Cin, Cout, R, pad, transposed, mode, expect = case
+    out = lab.large_operand_case(name, what, dtype, B, 512, 512, Cin, Cout, R, pad, transposed=transposed, mode=mode, expect=expect)
+    assert out["ran"] == expect, out["ran"]
+    assert out["peak_gib"] < 24.0, out["peak_gib"]
+    for k, v in out["extra"].items():
+        assert v < out["tol"] / 10, (k, v)          # the yardstick is at least ten times finer than what it measures
+    assert out["ok"], out
+
+
+@pytest.mark.parametrize("dtype", ["fp16", "bf16"])
+def test_plan_whose_head_gradient_spans_4_gib_matches_the_generic_weight_gradients(dtype):
+    """The configuration that was silently wrong: a plan whose head gradient (64 channels at full resolution) spans 4 GiB.  The plan
+    recorded ONE merged four-phase wgp launch for the head's weight gradient, wgpw.hip refused the operand at run time, the generic
+    kernel took the launch and computed phase 0 alone.  Now wgp.hip's own kernel (64-bit addresses) takes the merged launch, and
+    dmm_plan_* checks at every launch that the recorded family ran (DMM_ERR_STATE otherwise: _lib.check would raise).
+
+    The two-block net of test_two_block_net_layer_level_16bit (DenseNet-121 head and last-stage widths; 20.0 GiB of workspace against
+    38.8 GiB for DenseNet-121 early fusion, from dmm_plan_workspace_bytes) in fp16 and bf16 at 16 x 1024 x 2048 = 2**25 pixels, the smallest
+    input whose head gradient reaches 2**32 bytes.  One training forward + loss_backward with the default switches and one with
+    dmm_set_option("wgp", 0) (generic kernels, one launch per phase; nothing upstream of a weight gradient changes with the switch):
+      * every gradient is finite;
+      * refine0.weight and every Transposed_Convolution_*.weight agree within 2e-4 relative L2 - the bound of
+        test_parity_phase_weight_gradient_kernel_matches_generic for this pair of kernels on identical operands;
+      * every output-parity phase contributed to refine0.weight.  For the 128 upsampled input channels the 3x3 taps of phase (e, f) merge
+        onto 2x2 half-resolution taps, rows {0 | 1, 2} for e = 0 and {0, 1 | 2} for e = 1 (columns alike), so the mixed second difference
+        g[r, s] - g[1, s] - g[r, 1] + g[1, 1] at the corner (r, s) in {0, 2}^2 receives phase (r / 2, s / 2) ALONE (checked in fp64 against
+        torch autograd with the gradient masked to one parity).  A missing phase leaves its corner at exactly zero; a present one at
+        the size of the gradient itself.  Asserted: every corner above 1e-3 of the tensor's maximum.
+    Measured on an MI355X, fp16 / bf16: rel L2 1.4e-7 / 1.3e-7 and 7.8e-7 / 6.1e-7 (the two ConvTranspose stages), 1.7e-6 / 6.3e-7
+    (refine0); corners 0.63 ... 0.91 of the maximum in both plans; peak memory 21.5 GiB."""
+    from oracle import restatement as R
+    from dmmfods_amd import _lib
+    L = _lib.lib()
+    arch = R.Arch(growth_rate=32, block_config=(1, 1), num_init_features=64, concat_before_block_num=1, stream_2_in_channels=3)
+    B, H, W = 16, 1024, 2048
+    assert B * H * W * 64 * 2 == 1 << 32
+    model = _model(arch, dtype)
+    model.load_state_dict(R.make_state(arch, seed=11))
+    model = model.to(DEV).train()
+    g = torch.Generator(device=DEV).manual_seed(5)
+    kw = dict(generator=g, device=DEV)
+    # R.make_inputs' distributions, generated on the device (400 MB per tensor)
+    rgb = torch.rand(B, 3, H, W, **kw) * 255.0
+    lidar = torch.where(torch.rand(B, 3, H, W, **kw) > 0.9, torch.rand(B, 3, H, W, **kw) * 255.0, torch.zeros((), device=DEV))
+    tgt = (torch.rand(B, arch.num_classes, H, W, **kw) > 0.9).float()
+    torch.cuda.synchronize()
+    torch.cuda.reset_peak_memory_stats()
+    grads, labels = {}, {}
+    keep = lambda k: k.endswith("refine0.weight") or ("Transposed_Convolution_" in k and k.endswith(".weight") and "Sequence" not in k)  # noqa: E731
+    try:
+        for on in (1, 0):
+            _lib.check(L.dmm_set_option(b"wgp", on))
+            model.close()                     # a plan fixes the kernel family of every launch when it is bound
+            model(rgb, lidar)
+            model.loss_backward(tgt)
+            torch.cuda.synchronize()
+            labels[on] = plan_labels(model._last[0])
+            for k, p in model.named_parameters():
+                assert torch.isfinite(p.grad).all(), (on, k)
+            grads[on] = {k: p.grad.detach().double().clone() for k, p in model.named_parameters() if keep(k)}
+    finally:
+        _lib.check(L.dmm_set_option(b"wgp", 1))
+        model.close()
+    print(f"plan at {B} x {H} x {W} {dtype}: peak memory {torch.cuda.max_memory_allocated() / 2 ** 30:.1f} GiB; weight-gradient launches of the head and decoder: "
+          + " ".join(lab for lab in labels[1] if lab.startswith(("wgp.", "wgrad.")) and ("/h." in lab or "/d.TC" in lab))
+          + " | wgp off: " + " ".join(lab for lab in labels[0] if lab.startswith(("wgp.", "wgrad.")) and ("/h." in lab or "/d.TC" in lab)))
+    assert sum(lab.startswith("wgp.") and lab.endswith("/h.refine0") for lab in labels[1]) == 1, "the head's phases are not one wgp launch"
+    assert not any(lab.startswith("wgp.") for lab in labels[0])
+    assert len(grads[1]) >= 3, sorted(grads[1])
+    for k in grads[1]:
+        e = float((grads[1][k] - grads[0][k]).norm() / grads[0][k].norm())
+        print(f"   {k}: wgp vs generic rel L2 {e:.3e}")
+        assert e < 2e-4, (k, e)
+    for on in (1, 0):
+        gw = grads[on]["dec_out_to_heat_maps.refine0.weight"][:, :128]
+        top = float(gw.abs().max())
+        for r in (0, 2):
+            for s_ in (0, 2):
+                q = float((gw[:, :, r, s_] - gw[:, :, 1, s_] - gw[:, :, r, 1] + gw[:, :, 1, 1]).abs().max())
+                print(f"   wgp {on}: phase ({r // 2}, {s_ // 2}) of refine0.weight: {q / top:.3e} of the tensor's maximum")
+                assert q > 1e-3 * top, (on, r, s_, q, top)
+
+
 # ------------------------------------------------------------------------------------------------ (2) the timed networks, fp16
 def _model(arch, dtype, factory=None):
     from dmmfods_amd.graphs.models import Dense_U_Net_lidar as M

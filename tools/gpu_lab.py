@@ -290,6 +290,146 @@ def production_forward_case(name, dtype, B, H, W, Cin, Cout, R, stride, pad, bn,
     return ok
 
 
+def _maxabs(t):
+    """max |t|, infinite if any element is not finite (Python's max() drops a NaN silently)."""
+    m = float(t.abs().max())
+    return m if m == m else float("inf")
+
+
+def large_operand_case(name, what, dtype, B, H, W, Cin, Cout, R, pad, transposed=0, mode=0, expect=None, chunk=1):
+    """One convolution launch on operands of 4 GiB and more through the C ABI, where the 32-bit-offset families refuse and the fallback
+    kernels take over.  backward_case / production_forward_case keep fp32 copies of every operand; here the operands are generated per
+    batch chunk directly in 16 bits on the GPU, and the reference - torch fp32 on the GPU on the same rounded operands - runs per chunk:
+    forward outputs and data gradients are compared chunk by chunk, weight gradients and the BatchNorm-backward sums are added up over
+    the chunks in fp64.  what = "fwd" (dmm_conv_forward), "wgrad" (dmm_conv_wgrad_ex, normal form, materialised gradient), "dgrad"
+    (dmm_conv_dgrad_ex, assign).  expect: the exact set of families that must have noted the launch(es).
+    For "wgrad" the reference is also measured against itself: the same sum from chunks of twice the size, and fp32 against fp64
+    accumulation of the per-chunk results (printed; returned in the result for the test to look at)."""
+    dt = {1: torch.float16, 2: torch.bfloat16}[dtype]
+    tol = {1: 3e-3, 2: 2.5e-2}[dtype]
+    torch.cuda.synchronize()
+    torch.cuda.empty_cache()
+    torch.cuda.reset_peak_memory_stats()
+    g = torch.Generator(device=DEV).manual_seed(7)
+    kw = dict(generator=g, device=DEV)
+    scale = torch.rand(Cin, **kw) + 0.5
+    shift = torch.randn(Cin, **kw) * 0.5
+    mean = torch.randn(Cin, **kw)
+    invstd = torch.rand(Cin, **kw) + 0.5
+    wshape = (Cin, Cout, 3, 3) if transposed else (Cout, Cin, R, R)
+    w = torch.randn(wshape, **kw) / (Cin * R * R) ** 0.5
+    wq = w.to(dt).float()
+    up = 2 if (transposed or mode == 1) else 1
+    Ho, Wo = H * up, W * up
+    x = torch.empty(B, H, W, Cin, dtype=dt, device=DEV)
+    for b in range(B):
+        x[b] = (torch.randn(H, W, Cin, **kw) * 2 + 0.5).to(dt)
+    dy = None
+    if what != "fwd":
+        dy = torch.empty(B, Ho, Wo, Cout, dtype=dt, device=DEV)
+        for b in range(B):
+            dy[b] = torch.randn(Ho, Wo, Cout, **kw).to(dt)
+
+    def act(b0, b1):   # relu(bn(x)) of a chunk, NCHW fp32, rounded to the storage type as the kernels hold it
+        z = x[b0:b1].permute(0, 3, 1, 2).float() * scale.view(1, -1, 1, 1) + shift.view(1, -1, 1, 1)
+        return z, F.relu(z).to(dt).float()
+
+    def conv(a, wt):
+        if transposed:
+            return F.conv_transpose2d(a, wt, stride=2, padding=1, output_padding=1)
+        if mode == 1:
+            return F.conv2d(F.interpolate(a, scale_factor=2, mode="nearest"), wt, padding=pad)
+        return F.conv2d(a, wt, padding=pad)
+
+    d = _lib.ConvDesc(dtype=dtype, use_mfma=1, B=B, H=H, W=W, Cin=Cin, Cout=Cout, R=R, S=R, stride=2 if transposed else 1, pad=pad,
+                      transposed=transposed, mode=mode, bn_relu=1)
+    scratch = torch.zeros(L.dmm_conv_scratch_bytes(C.byref(d)), dtype=torch.uint8, device=DEV)
+    hd = torch.cat([shift, mean, invstd])
+    st = _lib.stream_ptr()
+    res, extra = {}, {}
+    _lib.impls_since_reset()
+    if what == "fwd":
+        yd = torch.full((B, Ho, Wo, Cout), float("nan"), dtype=dt, device=DEV)
+        stats = torch.zeros(2 * Cout, dtype=torch.float64, device=DEV)
+        _lib.check(L.dmm_conv_forward(C.byref(d), x.data_ptr(), w.data_ptr(), scale.data_ptr(), hd.data_ptr(), yd.data_ptr(), stats.data_ptr(),
+                                      scratch.data_ptr(), st))
+        torch.cuda.synchronize()
+        ran = _lib.impls_since_reset()
+        err = top = 0.0
+        ssum = torch.zeros(Cout, dtype=torch.float64, device=DEV)
+        ssq = torch.zeros(Cout, dtype=torch.float64, device=DEV)
+        for b0 in range(0, B, chunk):
+            ref = conv(act(b0, b0 + chunk)[1], wq)
+            o = yd[b0:b0 + chunk].permute(0, 3, 1, 2).float()
+            err = max(err, _maxabs(o - ref))
+            top = max(top, float(ref.abs().max()))
+            ssum += o.double().sum(dim=(0, 2, 3))
+            ssq += (o.double() ** 2).sum(dim=(0, 2, 3))
+            del ref, o
+        res["fwd"] = err / top
+        res["sum"] = relerr(stats[:Cout], ssum)
+        res["sq"] = relerr(stats[Cout:], ssq)
+    elif what == "wgrad":
+        dwd = torch.full(wshape, float("nan"), device=DEV)
+        _lib.check(L.dmm_conv_wgrad_ex(C.byref(d), x.data_ptr(), dy.data_ptr(), scale.data_ptr(), hd.data_ptr(), None, None, None, 0,
+                                       dwd.data_ptr(), scratch.data_ptr(), st))
+        torch.cuda.synchronize()
+        ran = _lib.impls_since_reset()
+
+        def ref_sum(ch):
+            s64 = torch.zeros(wshape, dtype=torch.float64, device=DEV)
+            s32 = torch.zeros(wshape, dtype=torch.float32, device=DEV)
+            for b0 in range(0, B, ch):
+                wt = wq.clone().requires_grad_(True)
+                (conv(act(b0, b0 + ch)[1], wt) * dy[b0:b0 + ch].permute(0, 3, 1, 2).float()).sum().backward()
+                s64 += wt.grad.double()
+                s32 += wt.grad
+            return s64, s32
+        ref64, ref32 = ref_sum(chunk)
+        alt64, _ = ref_sum(2 * chunk)
+        extra["ref_chunkings"] = relerr(alt64, ref64)       # the fp32 reference against itself: another chunking ...
+        extra["ref_fp32_accumulation"] = relerr(ref32, ref64)  # ... and fp32 against fp64 accumulation of the chunks
+        res["wgrad"] = relerr(dwd, ref64)
+    else:
+        gxd = torch.full((B, H, W, Cin), float("nan"), dtype=dt, device=DEV)
+        red = torch.zeros(2 * Cin, dtype=torch.float64, device=DEV)
+        _lib.check(L.dmm_conv_dgrad_ex(C.byref(d), x.data_ptr(), dy.data_ptr(), w.data_ptr(), scale.data_ptr(), hd.data_ptr(), None, None, None,
+                                       gxd.data_ptr(), 0, red.data_ptr(), scratch.data_ptr(), st))
+        torch.cuda.synchronize()
+        ran = _lib.impls_since_reset()
+        err = top = 0.0
+        r1 = torch.zeros(Cin, dtype=torch.float64, device=DEV)
+        r2 = torch.zeros(Cin, dtype=torch.float64, device=DEV)
+        for b0 in range(0, B, chunk):
+            z, _ = act(b0, b0 + chunk)
+            a = F.relu(z).requires_grad_(True)          # (as backward_case: the data gradient does not depend on the activation's rounding)
+            (conv(a, wq) * dy[b0:b0 + chunk].permute(0, 3, 1, 2).float()).sum().backward()
+            dz = a.grad * (z > 0)
+            gx_ref = dz * scale.view(1, -1, 1, 1)
+            o = gxd[b0:b0 + chunk].permute(0, 3, 1, 2).float()
+            err = max(err, _maxabs(o - gx_ref))
+            top = max(top, float(gx_ref.abs().max()))
+            xq = x[b0:b0 + chunk].permute(0, 3, 1, 2).double()
+            xhat = (xq - mean.double().view(1, -1, 1, 1)) * invstd.double().view(1, -1, 1, 1)
+            r1 += dz.double().sum(dim=(0, 2, 3))
+            r2 += (dz.double() * xhat).sum(dim=(0, 2, 3))
+            del z, a, dz, gx_ref, o, xq, xhat
+        res["dgrad"] = err / top
+        res["red1"] = relerr(red[:Cin], r1)
+        res["red2"] = relerr(red[Cin:], r2)
+    fam_ok = expect is None or ran == set(expect)
+    if not fam_ok:
+        print(f"FAIL {what} {name}: expected kernel families {sorted(expect)}, ran {sorted(ran)}", flush=True)
+    peak = torch.cuda.max_memory_allocated() / 2 ** 30
+    big = max(x.numel() * 2, (dy.numel() * 2) if dy is not None else 0, Ho * Wo * B * Cout * 2) / 2 ** 30
+    bad = [k for k, v in res.items() if not (v < tol)]
+    print(f"{'FAIL' if bad else 'ok  '} large {what:5s} {name:30s} dt={dtype} " + " ".join(f"{k}={v:.2e}" for k, v in res.items()) +
+          "".join(f" [{k}={v:.2e}]" for k, v in extra.items()) + f" ran={'+'.join(sorted(ran))} largest operand {big:.2f} GiB peak {peak:.1f} GiB", flush=True)
+    del x, dy, scratch
+    torch.cuda.empty_cache()
+    return dict(ok=not bad and fam_ok, res=res, extra=extra, ran=ran, peak_gib=peak, tol=tol)
+
+
 CASES = [
     # name, B,H,W,Cin,Cout,R,S,stride,pad, transposed, mode, bn
     ("1x1 72->32", 2, 12, 20, 72, 32, 1, 1, 1, 0, 0, 0, 1),

@@ -10,15 +10,26 @@
 //
 //   drive <arch> <dtype> <batch> <H> <W> [repeat]
 //   arch: d121e d121m d169m d201m d121n tiny_mid tiny_early tiny_no g8_mid     dtype: f32 f16 bf16
+// Three more modes check the kernel-family bookkeeping (Op::impl, dmm_last_impl) where no GPU test reaches - operands of 4 GiB and
+// more cost only address space here:
+//   drive picks <arch> <dtype> <batch> <H> <W>     every convolution launch of a bound plan, re-run through its launcher: the family
+//                                                  that takes it must be the one the plan recorded (workspace: reserved, never touched)
+//   drive single <fwd|wgrad|dgrad|fused> <dtype> <B> <H> <W> <Cin> <Cout> <R> <pad> <transposed> <mode>
+//                                                  one call of a single-kernel entry point on operands that are addresses only
+//   drive refuse                                   launch_wgrad(..., IMPL_GENERIC) on arguments the generic kernel does not implement
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <string>
 #include <vector>
 
+#include <sys/mman.h>
+
 #include "../../dmmfods_amd/csrc/plan.h"
+#include "../../dmmfods_amd/csrc/pointwise.h"
 
 extern "C" long fakehip_launches();
+extern "C" void fakehip_skip_large_memset(int on);
 extern "C" long fakehip_violations();
 extern "C" long fakehip_live_objects();
 extern "C" long fakehip_live_streams();
@@ -144,6 +155,11 @@ static int one_life(const dmm_model_desc& d, int life) {
   // (test of the bind-time check: a plan whose switches were tampered with after it was sized reserves other bytes -> DMM_ERR_STATE)
   if (getenv("DRIVE_FLIP_SWITCH_BETWEEN_CREATE_AND_BIND")) plan->sw.no_eff_compact = !plan->sw.no_eff_compact;
   MUST(dmm_plan_bind(plan, ws, wsb, params, grads, buffers));
+  // (test of the per-launch family check: a launch whose record names a family that will not take it - here a dense 3x3 weight
+  // gradient recorded as wg5, which refuses it, so the generic kernel runs - makes the backward pass return DMM_ERR_STATE)
+  if (getenv("DRIVE_TAMPER_RECORDED_FAMILY"))
+    for (Op& o : plan->bwd)
+      if (o.kind == OP_WGRAD && o.impl == IMPL_WG3) { o.impl = IMPL_WG5; break; }
   const long l0 = fakehip_launches();
   void* st = nullptr;  // the caller's stream: the null stream, as torch's default
   for (int rep = 0; rep < 2; ++rep) {
@@ -184,7 +200,185 @@ static int one_life(const dmm_model_desc& d, int life) {
   return 0;
 }
 
+// Address space without memory behind it: reserved, never committed; PROT_NONE where nothing at all may touch it.
+static void* reserve(size_t bytes, int prot) {
+  void* p = mmap(nullptr, bytes + 4096, prot, MAP_PRIVATE | MAP_ANONYMOUS | MAP_NORESERVE, -1, 0);
+  if (p == MAP_FAILED) { perror("[drive] mmap"); exit(3); }
+  return p;
+}
+static double seg_bytes(int B, const Seg& s, int esz) { return (double)B * s.Hs * s.Ws * s.ld * esz; }
+
+// ---- picks: the recorded family takes every launch ----
+// One line per convolution launch ("PICK ..."), one per disagreement ("MISMATCH ..."); returns the number of disagreements.
+// The test is capi.cpp's family_check, written out again on purpose: the recorded family is among those noted, and the generic family
+// is noted beside another one only for wgp's two-segment launch (8-channel remainder).
+static bool family_agrees(int kind, int impl, const WgradArgs* w, unsigned m) {
+  const bool recorded_ran = (m >> impl) & 1u, generic_ran = (m >> IMPL_GENERIC) & 1u;
+  const bool remainder = kind == OP_WGRAD && impl == IMPL_WGP && w->nseg == 2 && w->nphase == 0;
+  return impl != IMPL_AUTO && recorded_ran && (impl == IMPL_GENERIC || !generic_ran || remainder);
+}
+
+static int check_list(const std::vector<Op>& ops, int dt, bool mfma, const char* name) {
+  int bad = 0, n = 0;
+  const int esz = dt == DT_F32 ? 4 : 2;
+  for (const Op& o : ops) {
+    if (o.kind == OP_BW1) {   // decided by bw1_eligible when the plan was built: the pair must still be eligible, and the launch must succeed
+      WgradArgs w;
+      memset(&w, 0, sizeof(w));
+      const ConvArgs& c = o.b1.c;
+      w.nseg = 1;
+      Seg& x = w.seg[0];
+      x.src = c.bx; x.ld = c.ldbx; x.scale = c.bscale; x.shift = c.bshift; x.mode = G_PLAIN; x.istride = 1; x.ntaps = 1; x.C = o.b1.wC; x.Cpad = o.b1.wC;
+      x.Hs = c.Ho; x.Ws = c.Wo;
+      w.dy = c.seg[0]; w.dy.C = 128;
+      w.B = c.B; w.Ho = c.Ho; w.Wo = c.Wo; w.M = c.M; w.N = 128; w.Npad = o.b1.dNpad; w.dpack = o.b1.dpack;
+      dmm_impl_mask(1);
+      const hipError_t e = launch_bw1(o.b1, dt, nullptr);
+      const unsigned m = dmm_impl_mask(1);
+      ++n;
+      if (e != hipSuccess || m != (1u << IMPL_BW1) || !bw1_eligible(w, c, dt)) {
+        ++bad;
+        printf("%s MISMATCH %-40s recorded bw1 ran mask %#x rc %d eligible %d\n", name, o.label, m, (int)e, (int)bw1_eligible(w, c, dt));
+      }
+      continue;
+    }
+    if (o.kind != OP_IGEMM && o.kind != OP_WGRAD) continue;
+    dmm_impl_mask(1);
+    const hipError_t e = o.kind == OP_IGEMM ? launch_igemm(o.c, dt, o.epi, mfma, nullptr, o.impl) : launch_wgrad(o.w, dt, mfma, nullptr, o.impl);
+    const unsigned m = dmm_impl_mask(1);
+    const int last = dmm_last_impl();
+    ++n;
+    const bool wg = o.kind == OP_WGRAD;
+    const bool agree = e == hipSuccess && family_agrees(o.kind, o.impl, wg ? &o.w : nullptr, m);
+    const int B = wg ? o.w.B : o.c.B;
+    const double xb = seg_bytes(B, wg ? o.w.seg[0] : o.c.seg[0], esz), yb = wg ? seg_bytes(B, o.w.dy, esz) : 0.0;
+    printf("%s PICK %s %s recorded %s mask %#x nphase %d x_bytes %.0f dy_bytes %.0f\n", name, wg ? "wgrad" : "igemm", o.label, dmm_impl_name(o.impl), m,
+           wg ? o.w.nphase : o.c.nphase, xb, yb);
+    if (!agree) {
+      ++bad;
+      printf("%s MISMATCH %-40s recorded %-8s ran-last %-8s mask %#x rc %d nphase %d\n", name, o.label, dmm_impl_name(o.impl), dmm_impl_name(last), m, (int)e,
+             wg ? o.w.nphase : o.c.nphase);
+    }
+  }
+  printf("%s: %d conv launches, %d disagree\n", name, n, bad);
+  return bad;
+}
+
+static int picks_main(int argc, char** argv) {
+  if (argc < 7) return 64;
+  dmm_model_desc d;
+  if (!fill_desc(argv[2], d)) { fprintf(stderr, "unknown arch %s\n", argv[2]); return 64; }
+  const std::string dt = argv[3];
+  d.dtype = dt == "f32" ? DMM_F32 : (dt == "f16" ? DMM_F16 : DMM_BF16);
+  d.batch = atoi(argv[4]); d.height = atoi(argv[5]); d.width = atoi(argv[6]);
+  dmm_plan* plan = nullptr;
+  MUST(dmm_plan_create(&d, &plan));
+  const size_t wsb = dmm_plan_workspace_bytes(plan);
+  // (the op lists exist only in a BOUND plan: the sizing pass keeps none)
+  void* ws = reserve(wsb, PROT_READ | PROT_WRITE);
+  fakehip_skip_large_memset(1);   // (bind clears the workspace through the runtime: not this one)
+  const int64_t np = dmm_plan_num_params(plan), nb = std::max<int64_t>(dmm_plan_num_buffer_elems(plan), 1);
+  float* params = (float*)calloc(np, 4); float* grads = (float*)calloc(np, 4); float* buffers = (float*)calloc(nb, 4);
+  MUST(dmm_plan_bind(plan, ws, wsb, params, grads, buffers));
+  printf("workspace %.1f GiB, %zu + %zu + %zu launch records\n", wsb / 1073741824.0, plan->fwd_train.size(), plan->fwd_eval.size(), plan->bwd.size());
+  const bool mfma = d.use_mfma != 0;
+  const int bad = check_list(plan->fwd_train, d.dtype, mfma, "fwd") + check_list(plan->fwd_eval, d.dtype, mfma, "eval") + check_list(plan->bwd, d.dtype, mfma, "bwd");
+  MUST(dmm_plan_destroy(plan));
+  munmap(ws, wsb + 4096);
+  free(params); free(grads); free(buffers);
+  printf("%s\n", bad ? "PICKS FAILED" : "PICKS OK");
+  return bad ? 1 : 0;
+}
+
+// ---- single: one call of a single-kernel entry point; the large operands are addresses nothing may touch ----
+static int single_main(int argc, char** argv) {
+  if (argc < 13) return 64;
+  const std::string entry = argv[2], dt = argv[3];
+  dmm_conv_desc d;
+  memset(&d, 0, sizeof(d));
+  d.dtype = dt == "f32" ? DMM_F32 : (dt == "f16" ? DMM_F16 : DMM_BF16);
+  d.use_mfma = 1;
+  d.B = atoi(argv[4]); d.H = atoi(argv[5]); d.W = atoi(argv[6]); d.Cin = atoi(argv[7]); d.Cout = atoi(argv[8]);
+  d.R = d.S = atoi(argv[9]); d.stride = 1; d.pad = atoi(argv[10]); d.transposed = atoi(argv[11]); d.mode = atoi(argv[12]); d.bn_relu = 1;
+  const size_t esz = d.dtype == DMM_F32 ? 4 : 2;
+  const size_t up = (d.transposed || d.mode == 1) ? 4 : 1;
+  const size_t xin = (size_t)d.B * d.H * d.W * d.Cin * esz, yout = (size_t)d.B * d.H * d.W * up * d.Cout * esz;
+  void* x = reserve(xin, PROT_NONE); void* y = reserve(yout, PROT_NONE); void* gx = reserve(xin, PROT_NONE);
+  // what the entry points zero or fill from the host side of the runtime is real memory
+  const size_t wn = (size_t)d.Cin * d.Cout * d.R * d.S;
+  float* w = (float*)calloc(wn, 4); float* dw = (float*)calloc(wn, 4);
+  float* scale = (float*)calloc(d.Cin, 4); float* shift = (float*)calloc(3 * (size_t)d.Cin, 4);
+  double* stats = (double*)calloc(2 * (size_t)d.Cout, 8); double* red = (double*)calloc(2 * (size_t)d.Cin, 8);
+  const size_t sb = dmm_conv_scratch_bytes(&d);
+  void* scratch = calloc(sb ? sb : 1, 1);
+  dmm_impl_mask(1);
+  const long l0 = fakehip_launches();
+  int rc = -99;
+  if (entry == "fwd") rc = dmm_conv_forward(&d, x, w, scale, shift, y, stats, scratch, nullptr);
+  else if (entry == "wgrad") rc = dmm_conv_wgrad_ex(&d, x, y, scale, shift, nullptr, nullptr, nullptr, 0, dw, scratch, nullptr);
+  else if (entry == "dgrad") rc = dmm_conv_dgrad_ex(&d, x, y, w, scale, shift, nullptr, nullptr, nullptr, gx, 0, red, scratch, nullptr);
+  else if (entry == "fused") rc = dmm_conv1x1_backward_fused(&d, x, y, w, scale, shift, nullptr, nullptr, nullptr, gx, 0, dw, red, scratch, nullptr);
+  else return 64;
+  const unsigned m = dmm_impl_mask(1);
+  std::string names;
+  for (int f = 1; f < 32; ++f)
+    if ((m >> f) & 1u) names += (names.empty() ? "" : "+") + std::string(dmm_impl_name(f));
+  printf("SINGLE %s rc %d last %s ran %s launches %ld x_bytes %zu y_bytes %zu%s%s\n", entry.c_str(), rc, dmm_impl_name(dmm_last_impl()), names.empty() ? "none" : names.c_str(),
+         fakehip_launches() - l0, xin, yout, rc ? " error: " : "", rc ? dmm_last_error() : "");
+  hipDeviceSynchronize();
+  return fakehip_violations() ? 1 : 0;
+}
+
+// ---- refuse: the generic weight-gradient kernel implements one phase, the launch's own taps and a packed gradient - nothing else ----
+// variant 0: plain (the control: must launch, noted as generic); 1: merged phases, 2: per-phase tap counts, 3: factor form - each refused with
+// nothing launched and NOTHING noted; 4: the one launch where the generic kernel runs beside another family by design - wgp's two-segment
+// form (a 128-channel segment with 2x2 taps + the 8-channel raw-input remainder) with the recorded family wgp: it succeeds, and the
+// families noted must pass the per-launch check (today: wgp and its wave-specialised form, the remainder is not noted on its own).
+static int refuse_main() {
+  int bad = 0;
+  static float dpack[64 * 64 * 32], sbuf[16], scale[128], shift[128];
+  for (int variant = 0; variant < 5; ++variant) {
+    WgradArgs a;
+    memset(&a, 0, sizeof(a));
+    a.nseg = 1;
+    Seg& x = a.seg[0];
+    x.src = reserve(1 << 20, PROT_NONE); x.ld = 128; x.Hs = 8; x.Ws = 16; x.C = 128; x.Cpad = 128; x.ntaps = 1; x.nchunks = 4; x.mode = G_PLAIN; x.istride = 1;
+    a.dy.src = reserve(1 << 20, PROT_NONE); a.dy.ld = 64; a.dy.Hs = 8; a.dy.Ws = 16; a.dy.C = 64; a.dy.Cpad = 64; a.dy.ntaps = 1; a.dy.nchunks = 1; a.dy.mode = G_PLAIN;
+    a.dy.istride = 1;
+    a.B = 1; a.Ho = 8; a.Wo = 16; a.M = 128; a.N = 64; a.Npad = 64; a.dpack = dpack;
+    if (variant == 1) { a.nphase = 4; for (int ph = 0; ph < 4; ++ph) a.ph_dpack[ph] = dpack; }
+    if (variant == 2) a.ph_ntaps[2] = 2;
+    if (variant == 3) a.sbuf = sbuf;
+    if (variant == 4) {
+      x.scale = scale; x.shift = shift; x.ntaps = 4; x.nchunks = 16;
+      const int t4[4][2] = {{0, 0}, {0, 1}, {1, 0}, {1, 1}};
+      for (int t = 0; t < 4; ++t) x.taps[t] = (short)((t4[t][0] & 0xff) | ((t4[t][1] & 0xff) << 8));
+      a.nseg = 2;
+      Seg& r = a.seg[1];
+      r.src = reserve(1 << 20, PROT_NONE); r.ld = 8; r.Hs = 8; r.Ws = 16; r.C = 8; r.Cpad = 8; r.ntaps = 1; r.nchunks = 1; r.mode = G_PLAIN; r.istride = 1;
+      r.scale = scale; r.shift = shift;
+    }
+    const int impl = variant == 4 ? IMPL_WGP : IMPL_GENERIC;
+    const long l0 = fakehip_launches();
+    dmm_impl_mask(1);
+    const hipError_t e = launch_wgrad(a, DT_F16, true, nullptr, impl);
+    const unsigned m = dmm_impl_mask(1);
+    const long dl = fakehip_launches() - l0;
+    bool ok;
+    if (variant == 0) ok = e == hipSuccess && dl == 1 && m == (1u << IMPL_GENERIC);
+    else if (variant == 4) ok = e == hipSuccess && dl >= 1 /* the remainder's launch at least */ && ((m >> IMPL_WGP) & 1u) && family_agrees(OP_WGRAD, impl, &a, m);
+    else ok = e == hipErrorNotSupported && dl == 0 && m == 0;
+    printf("REFUSE variant %d rc %d launches %ld mask %#x %s\n", variant, (int)e, dl, m, ok ? "ok" : "WRONG");
+    bad += !ok;
+  }
+  hipDeviceSynchronize();
+  return bad ? 1 : 0;
+}
+
 int main(int argc, char** argv) {
+  if (argc > 1 && std::string(argv[1]) == "picks") return picks_main(argc, argv);
+  if (argc > 1 && std::string(argv[1]) == "single") return single_main(argc, argv);
+  if (argc > 1 && std::string(argv[1]) == "refuse") return refuse_main();
   if (argc < 6) { fprintf(stderr, "usage: drive <arch> <dtype> <batch> <H> <W> [lives]\n"); return 64; }
   dmm_model_desc d;
   if (!fill_desc(argv[1], d)) { fprintf(stderr, "unknown arch %s\n", argv[1]); return 64; }

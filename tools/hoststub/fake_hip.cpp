@@ -113,7 +113,11 @@ hipError_t hipDeviceSynchronize(void) {
 }
 
 // ---- memory: device memory is host memory ----
-hipError_t hipMemset(void* p, int v, size_t n) { memset(p, v, n); return hipSuccess; }
+// (drive.cpp `picks` binds a plan to address space that was reserved and never committed and says so through fakehip_skip_large_memset:
+// from 1 GiB on nothing is written then; every other mode keeps the sanitizer's view of the whole write)
+static bool g_skip_large_memset = false;
+extern "C" void fakehip_skip_large_memset(int on) { g_skip_large_memset = on != 0; }
+hipError_t hipMemset(void* p, int v, size_t n) { if (!(g_skip_large_memset && n >= (1ull << 30))) memset(p, v, n); return hipSuccess; }
 hipError_t hipMemsetAsync(void* p, int v, size_t n, hipStream_t st) {
   { std::lock_guard<std::mutex> l(g_mu); FakeStream* s = S(st); if (!s) return hipErrorInvalidResourceHandle; ++s->pending; }
   memset(p, v, n);
