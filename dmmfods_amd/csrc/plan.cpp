@@ -300,26 +300,87 @@ struct ConvRec {
 };
 struct PoolRec { int y0buf, bn, obuf, och0; uint8_t* argmax; int C; };
 struct Rec { int type; int idx; };  // 0 conv, 1 pool
+struct BucketRec {  // a gradient bucket while backward is emitted (data-parallel overlap)
+  int64_t off = 0, n = 0;
+  int convs_left = 0, bns_left = 0;
+  int first_desc = 0, ndesc = 0, rows = 0;
+  int tile0 = 0, nt1 = 0, nt9 = 0;   // the bucket's range of P.unpack_tiles (descriptor indices relative to P.unpacks)
+  int last_main = -1, last_side = -1;
+};
+
+// What a launch is, for its label: with the family that took it (Op::impl) it selects the class string (launch_class).
+enum LaunchRole { ROLE_STORE, ROLE_BNBWD, ROLE_LOGITS, ROLE_WGRAD /* forward-shaped packed gradient */, ROLE_WGRAD_T /* transposed form */ };
+// The class strings bench.py, the profile tools and the GPU tests key on.  IMPL_AUTO rows: every family without a row of its own
+// (so a logits launch on any family but thin / halo is `igemm.logits`, and the transposed generic weight gradient is `wgradT`).
+const char* launch_class(int impl, LaunchRole role) {
+  static const struct { LaunchRole role; int impl; const char* cls; } table[] = {
+      {ROLE_STORE, IMPL_CONV3, "conv3.store"}, {ROLE_STORE, IMPL_CVP, "cvp.store"},     {ROLE_STORE, IMPL_CF, "cf.store"},
+      {ROLE_STORE, IMPL_HALO, "halo.store"},   {ROLE_STORE, IMPL_PIG, "pig.store"},     {ROLE_STORE, IMPL_HF, "hf.store"},
+      {ROLE_STORE, IMPL_AUTO, "igemm.store"},  {ROLE_BNBWD, IMPL_CONV3, "conv3.bnbwd"}, {ROLE_BNBWD, IMPL_CVP, "cvp.bnbwd"},
+      {ROLE_BNBWD, IMPL_HALO, "halo.bnbwd"},   {ROLE_BNBWD, IMPL_BW1, "bw1"},           {ROLE_BNBWD, IMPL_AUTO, "igemm.bnbwd"},
+      {ROLE_LOGITS, IMPL_THIN, "thin.logits"}, {ROLE_LOGITS, IMPL_HALO, "halo.logits"}, {ROLE_LOGITS, IMPL_AUTO, "igemm.logits"},
+      {ROLE_WGRAD, IMPL_WGP, "wgp"},           {ROLE_WGRAD, IMPL_WG5, "wg5"},           {ROLE_WGRAD, IMPL_AUTO, "wgrad"},
+      {ROLE_WGRAD_T, IMPL_WG3, "wg3"},         {ROLE_WGRAD_T, IMPL_WG5, "wg5"},         {ROLE_WGRAD_T, IMPL_AUTO, "wgradT"},
+  };
+  for (auto& row : table)
+    if (row.role == role && (row.impl == impl || row.impl == IMPL_AUTO)) return row.cls;
+  return "?";
+}
 
 struct Builder {
+  // ---- the plan, its description and the two passes (constructor; never change) ----
   dmm_plan& P;
   const dmm_model_desc& d;
   Geo g;
   const int dtype, esz, SLOT, BK;
   const bool sizing;
+  // ---- arenas and bump allocators (bases: constructor; offsets: every new_buf / new_bn / add_pack / wptr / zptr / zbptr call, in the
+  // SAME order in the sizing and the bound pass - each call is an ordering constraint) ----
   uint8_t *zbase, *zbbase, *wbase;
   float *Pp, *Pg, *Pb;  // bases of the parameter / gradient / buffer arenas (see the constructor)
   Bump Z, ZB, W;  // Z: forward accumulators (BN statistics); ZB: backward accumulators (reductions, q/r, packed dW, metrics)
+  float* wg3_part = nullptr;  // wg3.hip's slots, shared by every launch of the family (taken by the first thin 3x3 weight gradient)
+  bool wg3_part_taken = false;
+  // ---- topology records (build() and its helpers write them; the emitters read them; backward emission updates Buf::ginit /
+  // materialized / mat_front) ----
   std::map<std::string, const TensorInfo*> tmap;
   std::vector<Buf> bufs;
   std::vector<Bn> bns;
   std::vector<ConvRec> convs;
   std::vector<PoolRec> pools;
   std::vector<Rec> recs;
+  int in1 = -1, in2 = -1, inH = -1, dl = -1;
+  size_t s2_recs = 0, concat_rec = 0;  // mid fusion: records [0, s2_recs) are the second encoder's, record concat_rec reads both
+  double flops = 0;
+  // ---- pack tables (emit_all, before the first launch list; plan_bind uploads through the *_dev pointers) ----
+  PackDesc* pack_dev = nullptr;
+  int* prefix_dev = nullptr;
+  PackTile* ptiles_dev = nullptr;
+  int total_rows = 0;          // rows of the pack launch behind the split (all rows without a split)
+  int pack_split = 0, pack_rows0 = 0;
+  size_t pack_cut_rec = 0;     // the first forward record whose weights the second pack launch holds
+  int pt_early1 = 0, pt_early9 = 0, pt_late1 = 0, pt_late9 = 0;
+  static constexpr double PACK_EARLY_ELEMS = 3.0e6;
+  // ---- gradient buckets (make_buckets fills them; conv_grad_done / bn_grad_done count them down while backward is emitted;
+  // finish_buckets turns them into P.buckets) ----
+  std::vector<BucketRec> brecs;
+  PackDesc* unpack_dev = nullptr;
+  int* unprefix_dev = nullptr;
+  PackTile* utiles_dev = nullptr;
+  // ---- emission scopes (emit_all selects the list and the mode; the emitters set and restore leaf_scope around their pushes) ----
   std::vector<Op>* ops = nullptr;
   bool training = true;
-  int in1 = -1, in2 = -1, inH = -1, dl = -1;
-  double flops = 0;
+  bool leaf_scope = false;  // ops emitted now feed only parameter gradients (stem / raw-input branches) or run on the side stream
+  bool s2_chain_started = false;  // (emit_forward_records) the second encoder's side-stream chain has its first launch
+  // ---- switches of this plan and lab knobs, read once ----
+  const bool pack_tiles_on = !P.sw.no_pack_tiles;
+  const bool s2_interleave = !P.sw.no_s2_interleave;
+  const bool s2_overlap = !lab_flag("DMM_NO_S2_OVERLAP");  // lab knob
+  const bool front_matz = !lab_flag("DMM_NO_FRONT_MATZ");  // lab knob
+  // which multi-consumer gradients are materialised (q + r*y applied once by applycorr) instead of corrected by every consumer's
+  // prologue: 1 the decoder's conv_reduce outputs, 2 the last ConvTranspose's output, 4 refine0's output (A/B knob)
+  const int matz_mask = lab_int("DMM_MATZ_MASK", 7);
+  const bool pad_pitch = lab_flag("DMM_PITCH_PAD");  // measured: no effect on MI355X for this access pattern; off
 
   Builder(dmm_plan& p, bool sizing_, uint8_t* ws)
       : P(p), d(p.desc), g(p.desc), dtype(p.desc.dtype), esz((int)dtype_size(p.desc.dtype)), SLOT(16 / esz), BK(4 * (16 / esz)),
@@ -431,65 +492,37 @@ struct Builder {
     const size_t elems = (size_t)chunks * pd.Npad * BK;
     pd.dst = wptr<uint8_t>(elems * esz);
     if (!dgrad_seg) pd.dpack = zbptr<float>(elems);
-    if (!dgrad_seg && pd.gw) pd.gw += 0;
     P.packs.push_back(pd);
     return (int)P.packs.size() - 1;
   }
 
   // -------------------------------------------------------------------------------- op emission
-  bool leaf_scope = false;  // ops emitted now feed only parameter gradients (stem / raw-input branches)
-  float* wg3_part = nullptr;  // wg3.hip's slots, shared by every launch of the family
-  bool wg3_part_taken = false;
-  const bool front_matz = !lab_flag("DMM_NO_FRONT_MATZ");  // lab knob
-  // which multi-consumer gradients are materialised (q + r*y applied once by applycorr) instead of corrected by every consumer's
-  // prologue: 1 the decoder's conv_reduce outputs, 2 the last ConvTranspose's output, 4 refine0's output (A/B knob)
-  const int matz_mask = lab_int("DMM_MATZ_MASK", 7);
-  // Deferred weight gradients (round 4).  The head's and the decoder's multi-tap weight gradients (wgp / wg5: 4 ms of work alone)
-  // are the FIRST things backward can start on the weight-gradient stream - and they then run beside the head's and the decoder's
-  // data gradients, the heaviest stretch of the main chain: measured with the launches skipped, they cost 3.2 ms of a 27.8 ms step,
-  // i.e. they were hardly hidden at all, while the encoder's weight gradients (3.6 ms alone) cost 1.2 ms.  Nothing needs them before
-  // their bucket's unpack, so they CAN be held back and enter the list where the main chain reaches the encoder (DMM_DEFER_WGRAD=1;
-  // DMM_DEFER_AT=<substring of a weight name> moves the point): there the main chain is a sequence of small launches (blocks 4-3).
-  // Their operands are final by then and stay so: a weight gradient reads forward activations and the gradient of its convolution's
-  // OUTPUT, which nothing writes after that convolution's own backward has been emitted.
-  // MEASURED (C2, one box): 27.71 ms in the old order, 28.14 deferred to the first encoder convolution, 28.65-28.77 deferred further
-  // (transition 3, block 3, block 2).  The chip is work-conserving: the deferred launches cost their 3 ms wherever they run and the
-  // encoder's own weight gradients then pile up behind them at the end of backward.  OFF by default; kept as a switch and a test.
-  bool defer_scope = false;
-  std::vector<Op> deferred_ops;
-  std::vector<const ConvRec*> deferred_convs;
   Op& push(int kind) {
-    if (defer_scope && kind == OP_WGRAD) {
-      deferred_ops.reserve(256);   // (references returned earlier stay valid: one reservation, far above the ~30 launches held)
-      deferred_ops.emplace_back();
-      deferred_ops.back().kind = kind;
-      deferred_ops.back().leaf = leaf_scope ? 1 : 0;
-      return deferred_ops.back();
-    }
     ops->emplace_back();
     ops->back().kind = kind;
     ops->back().leaf = leaf_scope ? 1 : 0;
     return ops->back();
   }
-  void flush_deferred() {
-    if (deferred_ops.empty() && deferred_convs.empty()) return;
-    for (auto& o : deferred_ops) ops->push_back(o);
-    deferred_ops.clear();
-    const bool keep = defer_scope;
-    defer_scope = false;
-    for (const ConvRec* c : deferred_convs) conv_grad_done(*c);
-    deferred_convs.clear();
-    defer_scope = keep;
+  // leaf_scope for the pushes of one block, restored at its end
+  struct LeafScope {
+    bool& flag;
+    const bool outer;
+    LeafScope(Builder& b, bool on) : flag(b.leaf_scope), outer(b.leaf_scope) { flag = on; }
+    ~LeafScope() { flag = outer; }
+  };
+  Op& push(int kind, bool leaf) {  // one push under its own leaf_scope
+    LeafScope scope(*this, leaf);
+    return push(kind);
   }
   bool is_raw_input(int buf) const { return buf == in1 || buf == in2 || buf == inH; }
-  void tag(Op& o, const char* cls, const std::string& layer, double flops, double bytes) {
-    snprintf(o.label, sizeof(o.label), "%s/%s", cls, layer.c_str());
+  void tag(Op& o, const std::string& cls, const std::string& layer, double flops, double bytes) {
+    snprintf(o.label, sizeof(o.label), "%s/%s", cls.c_str(), layer.c_str());
     o.flops = flops;
     o.bytes = bytes;
   }
-  static const char* ncls(const char* base, int npad, char* buf) {
-    snprintf(buf, 32, "%s.n%d", base, npad % 128 == 0 ? 128 : (npad % 64 == 0 ? 64 : 32));
-    return buf;
+  // class of a convolution-family launch: <family.role>.n<tile width of the launch's N>
+  static std::string ncls(int impl, LaunchRole role, int npad) {
+    return std::string(launch_class(impl, role)) + ".n" + std::to_string(npad % 128 == 0 ? 128 : (npad % 64 == 0 ? 64 : 32));
   }
   std::string short_name(const std::string& w) const {
     std::string s = w;
@@ -557,20 +590,46 @@ struct Builder {
     fill_seg_taps(s, taps, BK);
   }
 
+  // The last four launch records as ONE launch of four phases - if they are four phases of one convolution (`eligible(record, first)`
+  // for each: kind, family, tap counts, the operands of the first; all on one stream) and the launcher's dry pick still takes the merged
+  // launch (`accept(merged)`, which may also settle its family and label; the pick refuses e.g. operands of 4 GiB and more, and the
+  // four launches then stay).  `copy_phase(merged, record, ph)` moves what differs between the phases into the merged record's ph_* arrays.
+  template <typename Eligible, typename CopyPhase, typename Accept>
+  void merge_last_four_phases(Eligible eligible, CopyPhase copy_phase, Accept accept) {
+    if (ops->size() < 4) return;
+    const size_t first = ops->size() - 4;
+    for (size_t k = first; k < ops->size(); ++k)
+      if ((*ops)[k].leaf != (*ops)[first].leaf || !eligible((*ops)[k], (*ops)[first])) return;
+    Op merged = (*ops)[first];
+    merged.flops = 0; merged.bytes = 0;
+    for (int ph = 0; ph < 4; ++ph) {
+      const Op& po = (*ops)[first + ph];
+      copy_phase(merged, po, ph);
+      merged.flops += po.flops; merged.bytes += po.bytes;
+    }
+    if (!accept(merged)) return;
+    ops->resize(first);
+    ops->push_back(merged);
+  }
+  static void copy_fwd_phase(ConvArgs& m, const ConvArgs& po, int ph, int ntaps0) {  // what every merged forward launch carries per phase
+    m.nphase = 4;
+    for (int t = 0; t < 4; ++t) m.ph_taps0[ph][t] = po.seg[0].taps[t < ntaps0 ? t : 0];
+    m.ph_wpack[ph] = po.wpack;
+    m.ph_py[ph] = (signed char)po.py; m.ph_px[ph] = (signed char)po.px;
+  }
+
   void emit_conv_fwd(ConvRec& c) {
-    int done[2] = {-1, -1};
     for (int s = 0; s < c.nseg; ++s) {
       const int bn = c.seg[s].bn;
-      if (bn < 0 || bn == done[0]) continue;
+      if (bn < 0 || (s == 1 && bn == c.seg[0].bn)) continue;   // (the head's two segments stand under ONE norm: finalized once)
       emit_bn_finalize(bn);
-      done[s] = bn;
     }
     const Buf& ob = bufs[c.obuf];
+    const bool mfma = d.use_mfma != 0;
     for (auto& ph : c.phases) {
       Op& o = push(OP_IGEMM);
       o.epi = c.epi;
       ConvArgs& a = o.c;
-      memset(&a, 0, sizeof(a));
       a.nseg = c.nseg;
       for (int s = 0; s < c.nseg; ++s) fill_fwd_seg(a.seg[s], c.seg[s], (s == 1 && !ph.taps1.empty()) ? ph.taps1 : ph.taps);
       a.B = c.B; a.Ho = c.Ho; a.Wo = c.Wo; a.M = c.B * c.Ho * c.Wo;
@@ -581,83 +640,47 @@ struct Builder {
       a.ldo = ob.ld; a.Hout = ob.H; a.Wout = ob.W;
       a.ostride = c.ostride; a.py = ph.py; a.px = ph.px;
       if (c.stats && ob.ssum) { a.stat_sum = ob.ssum + c.och0; a.stat_sq = ob.ssq + c.och0; a.stat_stride = ob.ld; }
-      {
-        char cb[32];
-        const double np = (double)c.phases.size();
-        o.impl = igemm_pick(a, dtype, c.epi, d.use_mfma != 0);
-        const bool c3 = o.impl == IMPL_CONV3, cp = o.impl == IMPL_CVP;
-        const char* lcls = o.impl == IMPL_THIN ? "thin.logits" : (o.impl == IMPL_HALO ? "halo.logits" : "igemm.logits");
-        tag(o, ncls(c.epi == EPI_LOGITS ? lcls : (c3 ? "conv3.store" : (cp ? "cvp.store" : (o.impl == IMPL_CF ? "cf.store" : (o.impl == IMPL_HALO ? "halo.store" : (o.impl == IMPL_PIG ? "pig.store" : "igemm.store"))))), pd.Npad, cb), short_name(c.wname), conv_flops(c, c.phases.size()),
-            (src_bytes(c) + out_bytes(c)) / np + w_bytes(c) / np);
-      }
+      const double np = (double)c.phases.size();
+      o.impl = igemm_pick(a, dtype, c.epi, mfma);
+      tag(o, ncls(o.impl, c.epi == EPI_LOGITS ? ROLE_LOGITS : ROLE_STORE, pd.Npad), short_name(c.wname), conv_flops(c, c.phases.size()),
+          (src_bytes(c) + out_bytes(c)) / np + w_bytes(c) / np);
       if (c.epi == EPI_LOGITS) {
         if (training) P.logits_op_train = (int)ops->size() - 1; else P.logits_op_eval = (int)ops->size() - 1;
       }
     }
+    if (c.phases.size() != 4) return;
     // Four phases of the two-segment head convolution, all on conv3.hip: ONE launch that walks (tile, phase) pairs - the four phases of
     // a tile run side by side on one XCD and the half-resolution input (0.8 GB at C2) comes from HBM once instead of four times.
-    if (c.phases.size() == 4 && c.nseg == 2 && ops->size() >= 4 && !P.sw.no_c3_merge) {
-      const size_t first = ops->size() - 4;
-      bool ok = true;
-      for (size_t k = first; k < ops->size(); ++k) {
-        const Op& po = (*ops)[k];
-        ok = ok && po.kind == OP_IGEMM && po.epi == EPI_STORE && po.impl == IMPL_CONV3 && po.c.nseg == 2 && po.c.seg[0].ntaps == 4 &&
-             po.c.seg[1].ntaps == 9 && po.leaf == (*ops)[first].leaf;
-      }
-      if (ok) {
-        Op merged = (*ops)[first];
-        merged.c.nphase = 4;
-        merged.flops = 0; merged.bytes = 0;
-        for (int ph = 0; ph < 4; ++ph) {
-          const Op& po = (*ops)[first + ph];
-          for (int t = 0; t < 4; ++t) merged.c.ph_taps0[ph][t] = po.c.seg[0].taps[t];
-          for (int t = 0; t < 9; ++t) merged.c.ph_taps1[ph][t] = po.c.seg[1].taps[t];
-          merged.c.ph_wpack[ph] = po.c.wpack;
-          merged.c.ph_py[ph] = (signed char)po.c.py; merged.c.ph_px[ph] = (signed char)po.c.px;
-          merged.flops += po.flops; merged.bytes += po.bytes;
-        }
-        const int took = igemm_pick(merged.c, dtype, EPI_STORE, d.use_mfma != 0);
-        if (took == IMPL_CONV3 || took == IMPL_HF) {   // hf.hip (wave-specialised, one phase per workgroup) where its shape fits, else conv3.hip
-          merged.impl = took;
-          if (took == IMPL_HF) {
-            char lb[56];
-            snprintf(lb, sizeof(lb), "hf.store%s", strchr(merged.label, '.') && strstr(merged.label, ".n") ? strstr(merged.label, ".n") : "");
-            snprintf(merged.label, sizeof(merged.label), "%s", lb);
-          }
-          ops->resize(first);
-          ops->push_back(merged);
-        }
-      }
-    }
+    if (c.nseg == 2 && !P.sw.no_c3_merge)
+      merge_last_four_phases(
+          [](const Op& po, const Op&) {
+            return po.kind == OP_IGEMM && po.epi == EPI_STORE && po.impl == IMPL_CONV3 && po.c.nseg == 2 && po.c.seg[0].ntaps == 4 && po.c.seg[1].ntaps == 9;
+          },
+          [](Op& m, const Op& po, int ph) {
+            copy_fwd_phase(m.c, po.c, ph, 4);
+            for (int t = 0; t < 9; ++t) m.c.ph_taps1[ph][t] = po.c.seg[1].taps[t];
+          },
+          [&](Op& m) {   // hf.hip (wave-specialised, one phase per workgroup) where its shape fits, else conv3.hip
+            const int took = igemm_pick(m.c, dtype, EPI_STORE, mfma);
+            if (took != IMPL_CONV3 && took != IMPL_HF) return false;
+            m.impl = took;
+            if (took == IMPL_HF) tag(m, ncls(IMPL_HF, ROLE_STORE, m.c.Npad), short_name(c.wname), m.flops, m.bytes);
+            return true;
+          });
     // The four parity phases of a ConvTranspose (1, 2, 2, 4 taps), all on cvp.hip: ONE launch.  A phase of the first decoder stage is 600
     // workgroups of 128 x 128 outputs for 512 slots on the chip (two per CU) - two rounds, the second 17 % full; 1200 in the second stage - three
     // rounds.  One launch deals the 2400 (4800) workgroups of all phases, the 4-tap phase first, and the slots stay full.
-    if (c.phases.size() == 4 && c.nseg == 1 && c.transposed && ops->size() >= 4 && !P.sw.no_cvp_merge) {
-      const size_t first = ops->size() - 4;
-      bool ok = true;
-      for (size_t k = first; k < ops->size(); ++k) {
-        const Op& po = (*ops)[k];
-        ok = ok && po.kind == OP_IGEMM && po.epi == EPI_STORE && po.impl == IMPL_CVP && po.c.nseg == 1 && po.c.seg[0].ntaps <= 4 &&
-             po.c.nphase == 0 && po.leaf == (*ops)[first].leaf && po.c.out == (*ops)[first].c.out && po.c.seg[0].src == (*ops)[first].c.seg[0].src;
-      }
-      if (ok) {
-        Op merged = (*ops)[first];
-        merged.c.nphase = 4;
-        merged.flops = 0; merged.bytes = 0;
-        for (int ph = 0; ph < 4; ++ph) {
-          const Op& po = (*ops)[first + ph];
-          merged.c.ph_ntaps[ph] = (signed char)po.c.seg[0].ntaps;
-          for (int t = 0; t < 4; ++t) merged.c.ph_taps0[ph][t] = po.c.seg[0].taps[t < po.c.seg[0].ntaps ? t : 0];
-          merged.c.ph_wpack[ph] = po.c.wpack;
-          merged.c.ph_py[ph] = (signed char)po.c.py; merged.c.ph_px[ph] = (signed char)po.c.px;
-          merged.flops += po.flops; merged.bytes += po.bytes;
-        }
-        if (igemm_pick(merged.c, dtype, EPI_STORE, d.use_mfma != 0) == IMPL_CVP) {
-          ops->resize(first);
-          ops->push_back(merged);
-        }
-      }
-    }
+    if (c.nseg == 1 && c.transposed && !P.sw.no_cvp_merge)
+      merge_last_four_phases(
+          [](const Op& po, const Op& f) {
+            return po.kind == OP_IGEMM && po.epi == EPI_STORE && po.impl == IMPL_CVP && po.c.nseg == 1 && po.c.seg[0].ntaps <= 4 && po.c.nphase == 0 &&
+                   po.c.out == f.c.out && po.c.seg[0].src == f.c.seg[0].src;
+          },
+          [](Op& m, const Op& po, int ph) {
+            copy_fwd_phase(m.c, po.c, ph, po.c.seg[0].ntaps);
+            m.c.ph_ntaps[ph] = (signed char)po.c.seg[0].ntaps;
+          },
+          [&](Op& m) { return igemm_pick(m.c, dtype, EPI_STORE, mfma) == IMPL_CVP; });
   }
 
   void fill_grad_seg(Seg& s, int buf, int ch0, int C, const std::vector<Tap>& taps, int istride) {
@@ -677,10 +700,7 @@ struct Builder {
     Bn& b = bns[bn];
     const size_t first_op = ops->size();
     for (auto& rg : b.ranges) {
-      const bool outer = leaf_scope;
-      leaf_scope = outer || is_raw_input(rg.buf);
-      Op& o = push(OP_BNBWD);
-      leaf_scope = outer;
+      Op& o = push(OP_BNBWD, leaf_scope || is_raw_input(rg.buf));
       BnBwdFinalizeArgs& a = o.bb;
       a.red1 = b.red1 + rg.c0; a.red2 = b.red2 + rg.c0;
       a.stat_stride = b.cp;
@@ -722,93 +742,114 @@ struct Builder {
     }
   }
 
-  void emit_conv_bwd(ConvRec& c) {
-    {
-      const bool defer_on = P.sw.defer_wgrad;   // (OFF by default, see above)
-      const char* defer_at = lab_str("DMM_DEFER_AT");
-      const bool late = c.wname.rfind("decoder.", 0) == 0 || c.wname.rfind("dec_out_to_heat_maps.", 0) == 0;
-      const bool flush_here = defer_at ? c.wname.find(defer_at) != std::string::npos : !late;
-      if (flush_here) flush_deferred();
-      // multi-tap convolutions only: the decoder's 1x1 convolutions keep their place (the 128-wide one is fused with its data gradient)
-      defer_scope = defer_on && late && d.use_mfma && dtype != DT_F32 && c.R * c.S > 1 && (deferred_ops.size() + 40 < 256) &&
-                    !(defer_at && flush_here);
+  // -------------------------------------------------------------------------------- backward of one convolution
+  // Shape tests that BOTH reserve memory (every pass, by shape alone) and select what is emitted: one definition each.
+  // The dense 3x3 convolution in 16-bit storage (128 bottleneck channels -> 32 growth channels; thin output, so wgrad_transposed).
+  bool is_dense3x3(const ConvRec& c) const {
+    return c.wgrad_transposed && dtype != DT_F32 && c.R == 3 && c.S == 3 && rup(c.N, 8) == 32 && c.seg[0].C == 128;
+  }
+  // The head's 5x5 convolution onto the classes in 16-bit storage.
+  bool is_head5x5(const ConvRec& c) const { return c.nseg == 1 && c.R == 5 && c.S == 5 && dtype != DT_F32; }
+  // A 1x1 convolution over one plain segment whose data gradient flips no taps: the pair bw1.hip may fuse.
+  bool is_1x1_pair(const ConvRec& c) const {
+    return !c.wgrad_transposed && c.phases.size() == 1 && c.nseg == 1 && c.seg[0].dgrad == DG_FLIP && c.R == 1 && c.S == 1;
+  }
+  static std::vector<Tap> dgrad_taps(const ConvRec& c, int kind) {
+    switch (kind) {
+      case DG_FLIP: return taps_conv_dgrad(c.R, c.S, c.pad);
+      case DG_POOL2: return taps_conv(1, 1, 0);
+      case DG_CONVT: return taps_convT_dgrad();
+      case DG_UP2: return taps_up2_merged_dgrad();
     }
-    struct ScopeEnd { bool& f; ~ScopeEnd() { f = false; } } scope_end{defer_scope};
+    return {};
+  }
+  // How often a launch that gathers this convolution's output gradient reads an output-sized tensor: twice while the deferred
+  // BatchNorm-backward correction is still applied by the gather's prologue (gradient + forward output), once when it is materialised.
+  double grad_reads(const ConvRec& c) const {
     const Buf& ob = bufs[c.obuf];
-    const int Nst = rup(c.N, 8);  // storage channels of the output gradient
-    // ---- weight gradient, one launch per phase ----
-    auto one_tap_seg = [&](Seg& s, int py, int px) {
-      s.ntaps = 1; s.nchunks = 1;
-      s.taps[0] = (short)((py & 0xff) | ((px & 0xff) << 8));
-    };
-    // The dense 3x3 convolution in 16-bit storage: its data gradient (conv3.hip) holds the effective output gradient of every tile in
-    // LDS and writes the interior out as a compact [pixel][32] tensor, which the weight gradient (wg3.hip) reads INSTEAD of gathering
-    // 64 of every row's bytes from the block's gradient and activation buffers (128-byte lines: 4x the bytes).  One buffer per
-    // convolution: the weight gradient runs on the other stream, later than the next layer's data gradient.  Reserved by the
-    // shape alone (the sizing pass and the bound pass must take the same bytes); the weight-gradient launch then FOLLOWS the data
-    // gradient in the list.
+    return (ob.q && !ob.materialized && c.och0 + rup(c.N, 8) > ob.mat_front) ? 2.0 : 1.0;
+  }
+  static void one_tap_seg(Seg& s, int py, int px) {
+    s.ntaps = 1; s.nchunks = 1;
+    s.taps[0] = (short)((py & 0xff) | ((px & 0xff) << 8));
+  }
+
+  // What the steps of one convolution's backward hand to each other (lives for one emit_conv_bwd call).
+  struct ConvBwd {
+    // wg3: the dense 3x3 weight gradient, taken off the list to be emitted BEHIND the data gradient, whose compact copy of the
+    // effective output gradient (eff_compact) it reads instead of gathering from the block buffers
     void* eff_compact = nullptr;
-    bool wt_deferred = false;
-    Op wt_op;
-    bool have_second = false;
-    bool r1_stats = false;    // (round 5) norm1's sums come from the 5x5 weight gradient: the reductions-only pass is not emitted
-    bool raw_stats = false;   // (round 5) the raw-input channels' BatchNorm sums come from the weight gradient: no data gradient towards them
-    Op second_pass;
-    int second_buf = -1;
-    if (c.wgrad_transposed && dtype != DT_F32 && c.R == 3 && c.S == 3 && Nst == 32 && c.nseg == 1 && c.seg[0].C == 128 &&
-        c.seg[0].dgrad == DG_FLIP && !P.sw.no_eff_compact)
-      eff_compact = wptr<uint8_t>((size_t)c.B * c.Ho * c.Wo * 32 * esz);
-    // Round 5 (second half): the head's 5x5 convolution onto the classes.  Its two-pass data gradient (below) ran a reductions-only
-    // FIRST pass over the 64-channel full-resolution activation for norm1's two sums; its weight gradient (wg5.hip) reads the same
-    // activation and the same logits gradient.  With the activation entered as its two factors (wg5.hip, PA = 3) the weight-gradient
-    // launch yields dW AND both sums (wg5_fin64_kernel): the first pass is not emitted, and the weight gradient - now the producer of
-    // what the chain needs next - runs on the main stream (Op::chain).  The buffer is reserved by shape alone.
+    bool wg3_held = false;
+    Op wg3_op;
+    // bw1: the 1x1 weight gradient, taken off the list to be folded into the data-gradient launch (or put back in front of it:
+    // then dgrad_behind holds the data gradient, which follows the weight gradient and its bucket bookkeeping)
+    bool w1_held = false, dgrad_behind = false;
+    Op w1_op, dgrad_op;
+    // fin64: the head 5x5 weight gradient (index r1_idx in the list) that can yield norm1's sums into r1_sbuf; decided with the
+    // two-pass split of the data gradient, whose first pass then becomes the finish launch
     float* r1_sbuf = nullptr;
     int r1_idx = -1;
-    if (c.wgrad_transposed && dtype != DT_F32 && c.R == 5 && c.S == 5 && Nst == 8 && c.nseg == 1 && c.seg[0].C == 64 &&
-        c.seg[0].dgrad == DG_FLIP && c.N <= 4 && !P.sw.no_r1_stats && !P.sw.no_two_pass)
-      r1_sbuf = zbptr<float>(W5_SBUF64_FLOATS);
-    if (c.wgrad_transposed) {
-      Op& o = push(OP_WGRAD);
-      WgradArgs& a = o.w;
-      memset(&a, 0, sizeof(a));
-      a.nseg = 1;
-      fill_grad_seg(a.seg[0], c.obuf, c.och0, Nst, taps_conv_dgrad(c.R, c.S, c.pad), 1);   // Q: dY with flipped taps
-      a.B = c.B; a.Ho = c.Ho; a.Wo = c.Wo; a.M = c.B * c.Ho * c.Wo;
-      fill_fwd_seg(a.dy, c.seg[0], taps_conv(1, 1, 0));                                      // P: activated input, once
-      const PackDesc& pd = P.packs[c.dpack[0]];
-      a.N = c.seg[0].C; a.Npad = pd.Npad;
-      a.dpack = (float*)pd.dpack;
-      // wg3.hip's per-workgroup slots: ONE buffer for all launches of the family (they run in order on one stream, each followed
-      // by its reduction).  Reserved by the shape alone: the sizing pass and the bound pass must take the same bytes.
-      if (dtype != DT_F32 && c.R == 3 && c.S == 3 && Nst == 32 && c.seg[0].C == 128 && !lab_flag("DMM_WG3_SLOTS_OFF")) {
-        if (!wg3_part_taken) { wg3_part = wptr<float>((size_t)W3_MAX_SLOTS * W3_SLOT_FLOATS); wg3_part_taken = true; }
-        a.part = wg3_part;
-        a.part_slots = W3_MAX_SLOTS;
-      }
-      char cb[32];
-      o.impl = wgrad_pick(a, dtype, d.use_mfma != 0);
-      tag(o, ncls(o.impl == IMPL_WG3 ? "wg3" : (o.impl == IMPL_WG5 ? "wg5" : "wgradT"), pd.Npad, cb), short_name(c.wname), conv_flops(c, 1),
-          src_bytes(c) + ((ob.q && !ob.materialized && c.och0 + rup(c.N, 8) > ob.mat_front) ? 2.0 : 1.0) * out_bytes(c) + w_bytes(c) * 4.0 / esz);
-      if (eff_compact != nullptr && o.impl == IMPL_WG3 && !leaf_scope) {  // emitted behind the data gradient, reading its compact copy
-        wt_op = o;
-        ops->pop_back();
-        wt_deferred = true;
-      }
-      // the head's 5x5 convolution: a candidate for norm1's sums from the factor correlations (decided with the data gradient below)
-      if (r1_sbuf != nullptr && o.impl == IMPL_WG5 && !leaf_scope && !defer_scope && c.seg[0].bn >= 0) r1_idx = (int)ops->size() - 1;
-    } else {
-    // The head's first convolution (two segments, four output-parity phases): the phase split exists for the upsampled decoder
-    // segment; the 8-channel raw-input segment is a plain 3x3 convolution over the full-resolution grid, whose weight gradient is ONE
-    // pass over the output gradient (wg5.hip) instead of four generic launches that each re-gather a quarter of it tap by tap.  Its
-    // result goes to phase 0's packed gradient (the phases' packed gradients are summed into the master weights by unpack).
-    const bool raw_once = c.nseg == 2 && c.phases.size() == 4 && c.shared_master && c.seg[1].C == 8 && c.seg[1].istride == 2 &&
-                          c.ostride == 2 && !lab_flag("DMM_NO_RAW_ONCE");
-    const int wseg = raw_once ? 1 : c.nseg;
+    // rawfin has produced the raw-input channels' BatchNorm sums: no data gradient towards the raw input
+    bool raw_stats = false;
+    // two-pass BatchNorm backward: the storing second pass, emitted behind the finalize of second_buf's norm
+    bool have_second = false;
+    Op second_pass;
+    int second_buf = -1;
+    // some weight-gradient-side launch of this convolution is still to come behind the data gradient
+    bool wgrad_side_open() const { return wg3_held || w1_held || r1_idx >= 0; }
+  };
+
+  // Thin outputs (transposed form, one launch): P = the activated input once, Q = dY with flipped taps.
+  // The dense 3x3 convolution in 16-bit storage: its data gradient (conv3.hip) holds the effective output gradient of every tile in
+  // LDS and writes the interior out as a compact [pixel][32] tensor, which the weight gradient (wg3.hip) reads INSTEAD of gathering
+  // 64 of every row's bytes from the block's gradient and activation buffers (128-byte lines: 4x the bytes).  One buffer per
+  // convolution: the weight gradient runs on the other stream, later than the next layer's data gradient.  Reserved by the
+  // shape alone (the sizing pass and the bound pass must take the same bytes); the weight-gradient launch then FOLLOWS the data
+  // gradient in the list.
+  // The head's 5x5 convolution onto the classes: its two-pass data gradient (split_two_pass) ran a reductions-only FIRST pass over the
+  // 64-channel full-resolution activation for norm1's two sums; its weight gradient (wg5.hip) reads the same activation and the same
+  // logits gradient.  With the activation entered as its two factors (wg5.hip, PA = 3) the weight-gradient launch yields dW AND both
+  // sums (wg5_fin64_kernel): the first pass is not emitted, and the weight gradient - now the producer of what the chain needs next -
+  // runs on the main stream (Op::chain).  The buffer is reserved by shape alone.
+  void emit_wgrad_thin(ConvRec& c, ConvBwd& st) {
+    const int Nst = rup(c.N, 8);  // storage channels of the output gradient
+    if (is_dense3x3(c) && !P.sw.no_eff_compact) st.eff_compact = wptr<uint8_t>((size_t)c.B * c.Ho * c.Wo * 32 * esz);
+    if (is_head5x5(c) && Nst == 8 && c.seg[0].C == 64 && c.N <= 4 && !P.sw.no_r1_stats && !P.sw.no_two_pass)
+      st.r1_sbuf = zbptr<float>(W5_SBUF64_FLOATS);
+    Op& o = push(OP_WGRAD);
+    WgradArgs& a = o.w;
+    a.nseg = 1;
+    fill_grad_seg(a.seg[0], c.obuf, c.och0, Nst, taps_conv_dgrad(c.R, c.S, c.pad), 1);   // Q: dY with flipped taps
+    a.B = c.B; a.Ho = c.Ho; a.Wo = c.Wo; a.M = c.B * c.Ho * c.Wo;
+    fill_fwd_seg(a.dy, c.seg[0], taps_conv(1, 1, 0));                                      // P: activated input, once
+    const PackDesc& pd = P.packs[c.dpack[0]];
+    a.N = c.seg[0].C; a.Npad = pd.Npad;
+    a.dpack = (float*)pd.dpack;
+    // wg3.hip's per-workgroup slots: ONE buffer for all launches of the family (they run in order on one stream, each followed
+    // by its reduction).  Reserved by the shape alone: the sizing pass and the bound pass must take the same bytes.
+    if (is_dense3x3(c) && !lab_flag("DMM_WG3_SLOTS_OFF")) {
+      if (!wg3_part_taken) { wg3_part = wptr<float>((size_t)W3_MAX_SLOTS * W3_SLOT_FLOATS); wg3_part_taken = true; }
+      a.part = wg3_part;
+      a.part_slots = W3_MAX_SLOTS;
+    }
+    o.impl = wgrad_pick(a, dtype, d.use_mfma != 0);
+    tag(o, ncls(o.impl, ROLE_WGRAD_T, pd.Npad), short_name(c.wname), conv_flops(c, 1),
+        src_bytes(c) + grad_reads(c) * out_bytes(c) + w_bytes(c) * 4.0 / esz);
+    if (st.eff_compact != nullptr && o.impl == IMPL_WG3 && !leaf_scope) {  // emitted behind the data gradient, reading its compact copy
+      st.wg3_op = o;
+      ops->pop_back();
+      st.wg3_held = true;
+    } else if (st.r1_sbuf != nullptr && o.impl == IMPL_WG5 && !leaf_scope && c.seg[0].bn >= 0) {
+      st.r1_idx = (int)ops->size() - 1;   // a candidate for norm1's sums from the factor correlations (decided in split_two_pass)
+    }
+  }
+
+  // Normal form: one launch per phase, over the first `wseg` segments.
+  void emit_wgrad_phases(ConvRec& c, int wseg) {
+    const int Nst = rup(c.N, 8);
     for (auto& ph : c.phases) {
       Op& o = push(OP_WGRAD);
       WgradArgs& a = o.w;
-      memset(&a, 0, sizeof(a));
       a.nseg = wseg;
       for (int s = 0; s < wseg; ++s) fill_fwd_seg(a.seg[s], c.seg[s], (s == 1 && !ph.taps1.empty()) ? ph.taps1 : ph.taps);
       a.B = c.B; a.Ho = c.Ho; a.Wo = c.Wo; a.M = c.B * c.Ho * c.Wo;
@@ -817,262 +858,278 @@ struct Builder {
       const PackDesc& pd = P.packs[ph.pack];
       a.N = c.N; a.Npad = pd.Npad;
       a.dpack = (float*)pd.dpack;
-      {
-        char cb[32];
-        const double np = (double)c.phases.size();
-        // reads: forward operand, output gradient and (for the deferred correction) the forward output; writes dW
-        o.impl = wgrad_pick(a, dtype, d.use_mfma != 0);
-        tag(o, ncls(o.impl == IMPL_WGP ? "wgp" : (o.impl == IMPL_WG5 ? "wg5" : "wgrad"), pd.Npad, cb), short_name(c.wname),
-            conv_flops(c, c.phases.size()) * (raw_once ? (double)c.seg[0].Cw / c.Kin : 1.0),
-            (src_bytes(c) + ((ob.q && !ob.materialized && c.och0 + rup(c.N, 8) > ob.mat_front) ? 2.0 : 1.0) * out_bytes(c)) / np + w_bytes(c) * 4.0 / esz / np);
-      }
+      const double np = (double)c.phases.size();
+      // reads: forward operand, output gradient and (for the deferred correction) the forward output; writes dW
+      o.impl = wgrad_pick(a, dtype, d.use_mfma != 0);
+      tag(o, ncls(o.impl, ROLE_WGRAD, pd.Npad), short_name(c.wname), conv_flops(c, c.phases.size()) * (wseg < c.nseg ? (double)c.seg[0].Cw / c.Kin : 1.0),
+          (src_bytes(c) + grad_reads(c) * out_bytes(c)) / np + w_bytes(c) * 4.0 / esz / np);
     }
     // Four phases, all on wgp.hip: ONE launch, the phases of a tile range side by side on one XCD - the input comes from HBM once
-    // instead of four times.  Round 4: the head's 3x3 over the upsampled decoder output (four taps in every phase; 0.8 GB of
-    // half-resolution input at C2).  Round 5: the decoder's ConvTranspose stages as well (1, 2, 2, 4 taps: WgradArgs::ph_ntaps; the
-    // wave-specialised form of the kernel, wgpw.hip, takes the phase's tap count per workgroup).
-    if (!defer_scope && c.phases.size() == 4 && wseg == 1 && ops->size() >= 4 && !P.sw.no_wgp_merge) {
-      const size_t first = ops->size() - 4;
-      bool ok = true, all4 = true;
-      for (size_t k = first; k < ops->size(); ++k) {
-        const Op& po = (*ops)[k];
-        const int nt = po.w.seg[0].ntaps;
-        ok = ok && po.kind == OP_WGRAD && po.impl == IMPL_WGP && po.w.nseg == 1 && (nt == 1 || nt == 2 || nt == 4) && po.leaf == (*ops)[first].leaf &&
-             po.w.seg[0].src == (*ops)[first].w.seg[0].src && po.w.dy.src == (*ops)[first].w.dy.src;
-        all4 = all4 && nt == 4;
-      }
-      if (ok) {
-        Op merged = (*ops)[first];
-        merged.w.nphase = 4;
-        merged.flops = 0; merged.bytes = 0;
-        for (int ph = 0; ph < 4; ++ph) {
-          const Op& po = (*ops)[first + ph];
-          for (int t = 0; t < 4; ++t) merged.w.ph_xtaps[ph][t] = po.w.seg[0].taps[t < po.w.seg[0].ntaps ? t : 0];
-          merged.w.ph_ntaps[ph] = all4 ? 0 : (signed char)po.w.seg[0].ntaps;
-          merged.w.ph_ytap[ph] = po.w.dy.taps[0];
-          merged.w.ph_dpack[ph] = po.w.dpack;
-          merged.flops += po.flops; merged.bytes += po.bytes;
-        }
-        if (wgrad_pick(merged.w, dtype, d.use_mfma != 0) == IMPL_WGP) {
-          ops->resize(first);
-          ops->push_back(merged);
-        }
-      }
-    }
-    // Round 5: with the raw-input segment's weight gradient on wg5.hip, that launch correlates the output gradient with the two FACTORS
-    // of the activation (wg5.hip, PY = 2) and a one-workgroup launch turns the result into the packed weight gradient AND the
-    // BatchNorm-backward sums of the raw-input channels - the reductions-only data gradient towards the raw input (a leaf launch: one
-    // more pass over the full-resolution gradient, 0.69 ms at C2) is not emitted.  The buffer is reserved by shape alone.
+    // instead of four times: the head's 3x3 over the upsampled decoder output (four taps in every phase; 0.8 GB of half-resolution
+    // input at C2) and the decoder's ConvTranspose stages (1, 2, 2, 4 taps: WgradArgs::ph_ntaps; the wave-specialised form of the
+    // kernel, wgpw.hip, takes the phase's tap count per workgroup).
+    if (c.phases.size() == 4 && wseg == 1 && !P.sw.no_wgp_merge)
+      merge_last_four_phases(
+          [](const Op& po, const Op& f) {
+            const int nt = po.w.seg[0].ntaps;
+            return po.kind == OP_WGRAD && po.impl == IMPL_WGP && po.w.nseg == 1 && (nt == 1 || nt == 2 || nt == 4) && po.w.seg[0].src == f.w.seg[0].src &&
+                   po.w.dy.src == f.w.dy.src;
+          },
+          [](Op& m, const Op& po, int ph) {
+            m.w.nphase = 4;
+            for (int t = 0; t < 4; ++t) m.w.ph_xtaps[ph][t] = po.w.seg[0].taps[t < po.w.seg[0].ntaps ? t : 0];
+            m.w.ph_ntaps[ph] = (signed char)po.w.seg[0].ntaps;
+            m.w.ph_ytap[ph] = po.w.dy.taps[0];
+            m.w.ph_dpack[ph] = po.w.dpack;
+          },
+          [&](Op& m) {
+            bool all4 = true;   // four taps in every phase: ph_ntaps stays 0 (= seg[0].ntaps each)
+            for (int ph = 0; ph < 4; ++ph) all4 = all4 && m.w.ph_ntaps[ph] == 4;
+            if (all4) m.w.ph_ntaps[0] = m.w.ph_ntaps[1] = m.w.ph_ntaps[2] = m.w.ph_ntaps[3] = 0;
+            return wgrad_pick(m.w, dtype, d.use_mfma != 0) == IMPL_WGP;
+          });
+  }
+
+  // The head's first convolution (two segments, four output-parity phases): the phase split exists for the upsampled decoder
+  // segment; the 8-channel raw-input segment is a plain 3x3 convolution over the full-resolution grid, whose weight gradient is ONE
+  // pass over the output gradient (wg5.hip) instead of four generic launches that each re-gather a quarter of it tap by tap.  Its
+  // result goes to phase 0's packed gradient (the phases' packed gradients are summed into the master weights by unpack).
+  bool raw_segment_once(const ConvRec& c) const {
+    return c.nseg == 2 && c.phases.size() == 4 && c.shared_master && c.seg[1].C == 8 && c.seg[1].istride == 2 && c.ostride == 2 &&
+           !lab_flag("DMM_NO_RAW_ONCE");
+  }
+  // With the raw-input segment's weight gradient on wg5.hip, that launch correlates the output gradient with the two FACTORS of the
+  // activation (wg5.hip, PY = 2) and a one-workgroup launch (rawfin) turns the result into the packed weight gradient AND the
+  // BatchNorm-backward sums of the raw-input channels - the reductions-only data gradient towards the raw input (a leaf launch: one
+  // more pass over the full-resolution gradient, 0.69 ms at C2) is not emitted.  The buffer is reserved by shape alone.
+  void emit_wgrad_raw(ConvRec& c, ConvBwd& st) {
+    const Buf& ob = bufs[c.obuf];
+    const SegRec& sr = c.seg[1];
     float* raw_sbuf = nullptr;
-    if (raw_once && dtype != DT_F32 && c.N == 64 && !P.sw.no_raw_stats) raw_sbuf = zbptr<float>(W5_SBUF_FLOATS);
-    if (raw_once) {
-      Op& o = push(OP_WGRAD);
-      WgradArgs& a = o.w;
-      memset(&a, 0, sizeof(a));
-      a.nseg = 1;
-      fill_fwd_seg(a.seg[0], c.seg[1], taps_conv(3, 3, 1));
-      a.seg[0].istride = 1;                                  // the row grid is the full-resolution output grid
-      a.B = c.B; a.Ho = ob.H; a.Wo = ob.W; a.M = c.B * ob.H * ob.W;
-      fill_grad_seg(a.dy, c.obuf, c.och0, Nst, taps_conv(1, 1, 0), 1);
-      one_tap_seg(a.dy, 0, 0);
-      const PackDesc& pd = P.packs[c.phases[0].pack];
-      a.N = c.N; a.Npad = pd.Npad;
-      a.dpack = (float*)pd.dpack + (size_t)pd.seg[0].nchunks * pd.Npad * BK;   // behind segment 0's chunks
-      char cb[32];
-      o.impl = wgrad_pick(a, dtype, d.use_mfma != 0);
-      if (raw_sbuf != nullptr && o.impl == IMPL_WG5 && c.seg[1].bn >= 0 && !defer_scope) {   // (a held-back launch would run behind its finish)
-        WgradArgs f = a;
-        f.sbuf = raw_sbuf;
-        f.t_mean = bns[c.seg[1].bn].mean + c.seg[1].bn_c0;
-        f.t_invstd = bns[c.seg[1].bn].invstd + c.seg[1].bn_c0;
-        if (wgrad_pick(f, dtype, d.use_mfma != 0) == IMPL_WG5) { a = f; raw_stats = true; }
-      }
-      const Buf& rb = bufs[c.seg[1].buf];
-      tag(o, ncls(o.impl == IMPL_WG5 ? "wg5" : "wgrad", pd.Npad, cb), short_name(c.wname) + ".raw", conv_flops(c, 1) * ((double)c.seg[1].Cw / c.Kin),
-          (double)rb.B * rb.H * rb.W * 8 * esz + ((ob.q && !ob.materialized) ? 2.0 : 1.0) * out_bytes(c));
-      if (raw_stats) {   // right behind it on the same stream: packed gradient of the segment + the norm's sums for these channels
-        const WgradArgs wa = o.w;
-        const bool leaf_of = o.leaf;
-        Op& fo = push(OP_RAWFIN);
-        fo.leaf = leaf_of ? leaf_of : 1;
-        RawFinArgs& r = fo.rf;
-        memset(&r, 0, sizeof(r));
-        r.sbuf = wa.sbuf; r.dpack = wa.dpack; r.Npad = wa.Npad;
-        r.w = Pp + T(c.wname).off; r.Kin = c.Kin; r.koff = c.seg[1].koff; r.nreal = c.seg[1].Cw;
-        for (int t = 0; t < 9; ++t) r.tapw[t] = (int)(pd.seg[1].tapw[t] & 0xff);
-        const Bn& bn = bns[c.seg[1].bn];
-        r.gamma = bn.gamma + c.seg[1].bn_c0; r.beta = bn.beta + c.seg[1].bn_c0;
-        r.red1 = bn.red1 + c.seg[1].bn_c0; r.red2 = bn.red2 + c.seg[1].bn_c0;
-        tag(fo, "wg5.rawfin", short_name(c.wname) + ".raw", 0, W5_SBUF_FLOATS * 4.0);
-      }
+    if (dtype != DT_F32 && c.N == 64 && !P.sw.no_raw_stats) raw_sbuf = zbptr<float>(W5_SBUF_FLOATS);
+    Op& o = push(OP_WGRAD);
+    WgradArgs& a = o.w;
+    a.nseg = 1;
+    fill_fwd_seg(a.seg[0], sr, taps_conv(3, 3, 1));
+    a.seg[0].istride = 1;                                  // the row grid is the full-resolution output grid
+    a.B = c.B; a.Ho = ob.H; a.Wo = ob.W; a.M = c.B * ob.H * ob.W;
+    fill_grad_seg(a.dy, c.obuf, c.och0, rup(c.N, 8), taps_conv(1, 1, 0), 1);
+    one_tap_seg(a.dy, 0, 0);
+    const PackDesc& pd = P.packs[c.phases[0].pack];
+    a.N = c.N; a.Npad = pd.Npad;
+    a.dpack = (float*)pd.dpack + (size_t)pd.seg[0].nchunks * pd.Npad * BK;   // behind segment 0's chunks
+    o.impl = wgrad_pick(a, dtype, d.use_mfma != 0);
+    if (raw_sbuf != nullptr && o.impl == IMPL_WG5 && sr.bn >= 0) {
+      WgradArgs f = a;
+      f.sbuf = raw_sbuf;
+      f.t_mean = bns[sr.bn].mean + sr.bn_c0;
+      f.t_invstd = bns[sr.bn].invstd + sr.bn_c0;
+      if (wgrad_pick(f, dtype, d.use_mfma != 0) == IMPL_WG5) { a = f; st.raw_stats = true; }
     }
+    const Buf& rb = bufs[sr.buf];
+    tag(o, ncls(o.impl, ROLE_WGRAD, pd.Npad), short_name(c.wname) + ".raw", conv_flops(c, 1) * ((double)sr.Cw / c.Kin),
+        (double)rb.B * rb.H * rb.W * 8 * esz + grad_reads(c) * out_bytes(c));
+    if (!st.raw_stats) return;
+    // right behind it on the same stream: packed gradient of the segment + the norm's sums for these channels
+    const WgradArgs wa = o.w;   // (copies: `o` dangles after the push)
+    const int leaf_of = o.leaf;
+    Op& fo = push(OP_RAWFIN);
+    fo.leaf = leaf_of ? leaf_of : 1;
+    RawFinArgs& r = fo.rf;
+    r.sbuf = wa.sbuf; r.dpack = wa.dpack; r.Npad = wa.Npad;
+    r.w = Pp + T(c.wname).off; r.Kin = c.Kin; r.koff = sr.koff; r.nreal = sr.Cw;
+    for (int t = 0; t < 9; ++t) r.tapw[t] = (int)(pd.seg[1].tapw[t] & 0xff);
+    const Bn& bn = bns[sr.bn];
+    r.gamma = bn.gamma + sr.bn_c0; r.beta = bn.beta + sr.bn_c0;
+    r.red1 = bn.red1 + sr.bn_c0; r.red2 = bn.red2 + sr.bn_c0;
+    tag(fo, "wg5.rawfin", short_name(c.wname) + ".raw", 0, W5_SBUF_FLOATS * 4.0);
+  }
+
+  // One segment's data gradient with the fused BN+ReLU backward (EPI_BNBWD); the launch is the last record of the list afterwards.
+  void emit_dgrad_seg(ConvRec& c, int s, ConvBwd& st) {
+    const SegRec& sr = c.seg[s];
+    const Buf& sb = bufs[sr.buf];
+    const bool pool2 = sr.dgrad == DG_POOL2, up = sr.dgrad == DG_CONVT || sr.dgrad == DG_UP2;
+    const int rH = pool2 ? sb.H / 2 : sb.H, rW = pool2 ? sb.W / 2 : sb.W;
+    // the gradient w.r.t. a raw input is only needed for the BatchNorm parameter gradients of the norm in front of the
+    // conv: its launch reduces sum(dz), sum(dz*xhat), stores nothing, and is a leaf of the backward graph
+    const bool raw = is_raw_input(sr.buf);
+    Op& o = push(OP_IGEMM, raw);
+    o.epi = EPI_BNBWD;
+    ConvArgs& a = o.c;
+    a.nseg = 1;
+    fill_grad_seg(a.seg[0], c.obuf, c.och0, rup(c.N, 8), dgrad_taps(c, sr.dgrad), up ? 2 : 1);
+    a.B = sb.B; a.Ho = rH; a.Wo = rW; a.M = sb.B * rH * rW;
+    const PackDesc& pd = P.packs[c.dpack[s]];
+    a.wpack = pd.dst;
+    a.N = sr.C; a.Npad = pd.Npad;
+    a.out = raw ? nullptr : gat(sr.buf, sr.ch0);
+    a.ldo = sb.ld; a.Hout = sb.H; a.Wout = sb.W; a.ostride = pool2 ? 2 : 1; a.py = 0; a.px = 0;
+    a.bx = xat(sr.buf, sr.ch0);
+    a.ldbx = sb.ld;
+    const Bn& bn = bns[sr.bn];
+    a.bscale = bn.scale + sr.bn_c0; a.bshift = bn.shift + sr.bn_c0;
+    a.bmean = bn.mean + sr.bn_c0; a.binvstd = bn.invstd + sr.bn_c0;
+    a.red1 = bn.red1 + sr.bn_c0; a.red2 = bn.red2 + sr.bn_c0;
+    a.stat_stride = bn.cp;
+    a.accumulate = (sb.ginit && !raw) ? 1 : 0;
+    a.pool2 = pool2 ? 1 : 0;
+    // reads: output gradient (+ forward output for the correction), x for the ReLU mask, (old gradient); writes gradient
+    const double srcb = (double)sb.B * sb.H * sb.W * sr.C * esz;
+    const double segf = conv_flops(c, 1) * ((double)sr.Cw / c.Kin) * (sr.dgrad == DG_UP2 ? 16.0 / 36.0 : 1.0);
+    o.impl = igemm_pick(a, dtype, EPI_BNBWD, d.use_mfma != 0);
+    if (st.wg3_held && o.impl == IMPL_CONV3) {  // hand the effective gradient over: the weight gradient reads the compact copy, no prologue
+      a.eff_out = st.eff_compact;
+      Seg& q = st.wg3_op.w.seg[0];
+      q.src = st.eff_compact; q.ld = 32;
+      q.src2 = nullptr; q.ld2 = 0; q.q = q.r = q.ql = q.rl = nullptr;
     }
-    // A dense layer's 1x1 bottleneck convolution: its weight gradient and its data gradient read the same three tensors; when the
-    // pair qualifies (bw1.hip) the weight-gradient launch is taken back here and folded into the data-gradient launch below.
-    bool pending_w = false;
-    Op saved_w;
-    if (d.use_mfma && !c.wgrad_transposed && c.phases.size() == 1 && c.nseg == 1 && c.seg[0].dgrad == DG_FLIP && c.R == 1 && c.S == 1 &&
-        !ops->empty() && ops->back().kind == OP_WGRAD && !leaf_scope) {
-      saved_w = ops->back();
+    tag(o, ncls(o.impl, ROLE_BNBWD, pd.Npad), short_name(c.wname), segf,
+        grad_reads(c) * out_bytes(c) + srcb * (sb.ginit ? 3.0 : 2.0) + w_bytes(c));
+  }
+
+  // Two-pass BatchNorm backward where the data gradient is cheap to run twice and its result would otherwise be corrected by a
+  // pass of its own (apply_corr: read g, read x, write g).  The head's 5x5 convolution onto the classes: its data gradient
+  // reads the 3-channel logits gradient and, for the ReLU mask, the 64-channel full-resolution activation x.  First pass:
+  // reductions only (nothing stored); finalize (q, r); second pass: the same launch stores the FINAL gradient
+  // s*dz + q + r*x.  Traffic 2 x |x| + |g| instead of |x| + |g| (store) + 2 |g| + |x| (apply_corr).
+  // Works on the data-gradient launch emit_dgrad_seg has just emitted (the last record): it becomes the first pass, the second goes to
+  // `st` for the driver to emit behind the norm's finalize.
+  void split_two_pass(ConvRec& c, int s, ConvBwd& st) {
+    const SegRec& sr = c.seg[s];
+    const Buf& sb = bufs[sr.buf];
+    Op& o = ops->back();
+    if (!(o.impl == IMPL_CONV3 && !is_raw_input(sr.buf) && sb.matz && sb.q && !sb.ginit && !sb.materialized && is_head5x5(c) && !P.sw.no_two_pass)) return;
+    const double srcb = (double)sb.B * sb.H * sb.W * sr.C * esz;
+    Op first_pass = o;                     // reductions only: stores nothing
+    first_pass.c.out = nullptr;
+    Op second_pass = o;                    // stores; no reductions
+    second_pass.c.red1 = nullptr; second_pass.c.red2 = nullptr;
+    second_pass.c.eq = sb.q + sr.ch0; second_pass.c.er = sb.r + sr.ch0;
+    // both MUTATED launches must still be conv3.hip's (the only kernel whose epilogue knows eq / er)
+    if (igemm_pick(first_pass.c, dtype, EPI_BNBWD, d.use_mfma != 0) != IMPL_CONV3 ||
+        igemm_pick(second_pass.c, dtype, EPI_BNBWD, d.use_mfma != 0) != IMPL_CONV3)
+      return;
+    st.have_second = true;
+    st.second_buf = sr.buf;
+    st.second_pass = second_pass;
+    st.second_pass.bytes = out_bytes(c) + srcb * 2.0 + w_bytes(c);
+    o.c.out = nullptr;
+    o.bytes = out_bytes(c) + srcb + w_bytes(c);          // reads dy and x, writes nothing
+    if (st.r1_idx < 0) return;
+    // norm1's sums from the weight gradient's factor correlations: the first pass becomes the finish launch (fin64)
+    const Bn& bn = bns[sr.bn];
+    WgradArgs f = (*ops)[st.r1_idx].w;
+    f.sbuf = st.r1_sbuf;
+    f.t_mean = bn.mean + sr.bn_c0; f.t_invstd = bn.invstd + sr.bn_c0;   // (mark of the factor form; the kernel needs scale / shift only)
+    if (wgrad_pick(f, dtype, d.use_mfma != 0) != IMPL_WG5) return;
+    Op& wo = (*ops)[st.r1_idx];
+    wo.w = f;
+    wo.chain = 1;
+    const PackDesc& wpd = P.packs[c.dpack[0]];
+    Fin64Args r = {};
+    r.sbuf = st.r1_sbuf; r.dpack = f.dpack; r.Npad = f.Npad;
+    r.w = Pp + T(c.wname).off; r.Kin = c.Kin; r.nreal = c.N; r.dtype = dtype;
+    for (int t = 0; t < 25; ++t) r.tapw[t] = (unsigned char)(wpd.seg[0].tapw[t] & 0xff);
+    r.scale = bn.scale + sr.bn_c0; r.shift = bn.shift + sr.bn_c0;
+    r.mean = bn.mean + sr.bn_c0; r.invstd = bn.invstd + sr.bn_c0;
+    r.red1 = bn.red1 + sr.bn_c0; r.red2 = bn.red2 + sr.bn_c0;
+    o.kind = OP_FIN64; o.epi = 0; o.impl = IMPL_AUTO; o.chain = 1;
+    o.f64 = r;     // (overwrites the first pass's convolution arguments)
+    tag(o, "wg5.fin64", short_name(c.wname), 0, W5_SBUF64_FLOATS * 4.0);
+  }
+
+  // A dense layer's 1x1 bottleneck convolution: its weight gradient and its data gradient read the same three tensors.  The
+  // weight-gradient launch, just emitted, is taken back here; fold_bw1 folds it into the data-gradient launch when the pair qualifies.
+  void take_back_1x1_wgrad(const ConvRec& c, ConvBwd& st) {
+    if (!(d.use_mfma && is_1x1_pair(c) && !ops->empty() && ops->back().kind == OP_WGRAD && !leaf_scope)) return;
+    st.w1_op = ops->back();
+    ops->pop_back();
+    st.w1_held = true;
+  }
+  // The data gradient emit_dgrad_seg has just emitted (the last record) + the held-back weight gradient -> ONE bw1 launch (and the
+  // reduction of its slots beside the data-gradient chain), or, where the pair does not qualify, the original order: weight gradient,
+  // (the driver's bucket bookkeeping), data gradient - the latter handed to the driver in st.dgrad_op.
+  void fold_bw1(const ConvRec& c, ConvBwd& st) {
+    const bool raw = is_raw_input(c.seg[0].buf);
+    const Op dgrad_op = ops->back();
+    const Op& saved_w = st.w1_op;
+    // slots for the weight-gradient partials of the fused launch (pointwise.h: Bw1Args::part).  Reserved by the shape of the pair
+    // alone - the sizing pass and the bound pass must take the same bytes, and bw1_eligible looks at pointers
+    float* part = nullptr;
+    int part_slots = 0;
+    if (!raw && dtype != DT_F32 && c.N == 128) {
+      const Bw1Geom q = bw1_geometry(dgrad_op.c);
+      part_slots = q.nsplit * q.nct;
+      part = wptr<float>((size_t)part_slots * B1_SLOT_FLOATS);
+    }
+    if (raw || !bw1_eligible(saved_w.w, dgrad_op.c, dtype)) {   // not this time
       ops->pop_back();
-      pending_w = true;
+      ops->push_back(saved_w);
+      st.dgrad_op = dgrad_op;
+      st.dgrad_behind = true;
+      return;
     }
-    const bool r1_wait = r1_idx >= 0;   // (the finish launch may still add into this convolution's packed gradient)
-    if (!pending_w && !wt_deferred && !r1_wait) conv_grad_done(c);
+    Op& f = ops->back();
+    f.kind = OP_BW1;
+    f.b1.dpack = saved_w.w.dpack;
+    f.b1.dNpad = saved_w.w.Npad;
+    f.b1.wC = saved_w.w.seg[0].C;
+    f.b1.part = part;
+    f.b1.part_slots = part_slots;
+    f.b1.nct = f.b1.ntiles = f.b1.tiles_per_wg = f.b1.xcd_group = f.b1.nsplit = 0;
+    // the pair's traffic with every operand read once: the data gradient's bytes + the packed weight gradient
+    tag(f, ncls(IMPL_BW1, ROLE_BNBWD, f.c.Npad), short_name(c.wname), dgrad_op.flops + saved_w.flops, dgrad_op.bytes + w_bytes(c) * 4.0 / esz);
+    if (part == nullptr) return;
+    // the slots are added up beside the data-gradient chain (weight-gradient stream)
+    const Bw1Args b1 = f.b1;   // (a copy: `f` dangles after the push)
+    Op& rop = push(OP_BW1RED);
+    rop.leaf = 1;
+    rop.b1 = b1;
+    tag(rop, "bw1.reduce", short_name(c.wname), 0, ((double)part_slots + b1.nct) * B1_SLOT_FLOATS * 4.0);
+  }
+
+  void emit_conv_bwd(ConvRec& c) {
+    ConvBwd st;
+    // ---- weight gradient ----
+    if (c.wgrad_transposed) {
+      emit_wgrad_thin(c, st);
+    } else {
+      const bool raw_once = raw_segment_once(c);
+      emit_wgrad_phases(c, raw_once ? 1 : c.nseg);
+      if (raw_once) emit_wgrad_raw(c, st);
+      take_back_1x1_wgrad(c, st);
+    }
+    // conv_grad_done runs ONCE per convolution, behind its last weight-gradient-side launch (it may append the bucket's unpack, which
+    // reads every packed gradient of the bucket on the same stream).  Normally that launch is in the list by now ...
+    if (!st.wgrad_side_open()) conv_grad_done(c);
     // ---- data gradients with fused BN+ReLU backward ----
     for (int s = 0; s < c.nseg; ++s) {
-      SegRec& sr = c.seg[s];
+      const SegRec& sr = c.seg[s];
       if (sr.dgrad == DG_NONE) continue;
-      if (raw_stats && s == 1 && is_raw_input(sr.buf)) continue;   // its only purpose were the two sums wg5.rawfin has just produced
-      Buf& sb = bufs[sr.buf];
-      std::vector<Tap> taps;
-      int istride = 1, rB = sb.B, rH = sb.H, rW = sb.W, pool2 = 0, ostride = 1;
-      switch (sr.dgrad) {
-        case DG_FLIP: taps = taps_conv_dgrad(c.R, c.S, c.pad); break;
-        case DG_POOL2: taps = taps_conv(1, 1, 0); rH = sb.H / 2; rW = sb.W / 2; pool2 = 1; ostride = 2; break;
-        case DG_CONVT: taps = taps_convT_dgrad(); istride = 2; break;
-        case DG_UP2: taps = taps_up2_merged_dgrad(); istride = 2; break;
-      }
-      // the gradient w.r.t. a raw input is only needed for the BatchNorm parameter gradients of the norm in front of the
-      // conv: its launch reduces sum(dz), sum(dz*xhat), stores nothing, and is a leaf of the backward graph
-      const bool raw = is_raw_input(sr.buf);
-      leaf_scope = raw;
-      Op& o = push(OP_IGEMM);
-      leaf_scope = false;
-      o.epi = EPI_BNBWD;
-      ConvArgs& a = o.c;
-      memset(&a, 0, sizeof(a));
-      a.nseg = 1;
-      fill_grad_seg(a.seg[0], c.obuf, c.och0, Nst, taps, istride);
-      a.B = rB; a.Ho = rH; a.Wo = rW; a.M = rB * rH * rW;
-      const PackDesc& pd = P.packs[c.dpack[s]];
-      a.wpack = pd.dst;
-      a.N = sr.C; a.Npad = pd.Npad;
-      a.out = raw ? nullptr : gat(sr.buf, sr.ch0);
-      a.ldo = sb.ld; a.Hout = sb.H; a.Wout = sb.W; a.ostride = ostride; a.py = 0; a.px = 0;
-      a.bx = xat(sr.buf, sr.ch0);
-      a.ldbx = sb.ld;
-      const Bn& bn = bns[sr.bn];
-      a.bscale = bn.scale + sr.bn_c0; a.bshift = bn.shift + sr.bn_c0;
-      a.bmean = bn.mean + sr.bn_c0; a.binvstd = bn.invstd + sr.bn_c0;
-      a.red1 = bn.red1 + sr.bn_c0; a.red2 = bn.red2 + sr.bn_c0;
-      a.stat_stride = bn.cp;
-      a.accumulate = (sb.ginit && !raw) ? 1 : 0;
-      a.pool2 = pool2;
-      {
-        char cb[32];
-        // reads: output gradient (+ forward output for the correction), x for the ReLU mask, (old gradient); writes gradient
-        const double srcb = (double)sb.B * sb.H * sb.W * sr.C * esz;
-        const double segf = conv_flops(c, 1) * ((double)sr.Cw / c.Kin) * (sr.dgrad == DG_UP2 ? 16.0 / 36.0 : 1.0);
-        o.impl = igemm_pick(a, dtype, EPI_BNBWD, d.use_mfma != 0);
-        const bool c3 = o.impl == IMPL_CONV3, cp = o.impl == IMPL_CVP;
-        if (wt_deferred && c3) {  // hand the effective gradient over: the weight gradient reads the compact copy, no prologue
-          a.eff_out = eff_compact;
-          Seg& q = wt_op.w.seg[0];
-          q.src = eff_compact; q.ld = 32;
-          q.src2 = nullptr; q.ld2 = 0; q.q = q.r = q.ql = q.rl = nullptr;
-        }
-        tag(o, ncls(c3 ? "conv3.bnbwd" : (cp ? "cvp.bnbwd" : (o.impl == IMPL_HALO ? "halo.bnbwd" : "igemm.bnbwd")), pd.Npad, cb), short_name(c.wname), segf,
-            ((ob.q && !ob.materialized && c.och0 + rup(c.N, 8) > ob.mat_front) ? 2.0 : 1.0) * out_bytes(c) + srcb * (sb.ginit ? 3.0 : 2.0) + w_bytes(c));
-        // Two-pass BatchNorm backward where the data gradient is cheap to run twice and its result would otherwise be corrected by a
-        // pass of its own (apply_corr: read g, read x, write g).  The head's 5x5 convolution onto the classes: its data gradient
-        // reads the 3-channel logits gradient and, for the ReLU mask, the 64-channel full-resolution activation x.  First pass:
-        // reductions only (nothing stored); finalize (q, r); second pass: the same launch stores the FINAL gradient
-        // s*dz + q + r*x.  Traffic 2 x |x| + |g| instead of |x| + |g| (store) + 2 |g| + |x| (apply_corr).
-        if (c3 && !raw && sb.matz && sb.q && !sb.ginit && !sb.materialized && c.nseg == 1 && c.R == 5 && c.S == 5 && dtype != DT_F32 &&
-            !P.sw.no_two_pass) {
-          Op first_pass = o;                     // reductions only: stores nothing
-          first_pass.c.out = nullptr;
-          second_pass = o;                       // stores; no reductions
-          second_pass.c.red1 = nullptr; second_pass.c.red2 = nullptr;
-          second_pass.c.eq = sb.q + sr.ch0; second_pass.c.er = sb.r + sr.ch0;
-          // both MUTATED launches must still be conv3.hip's (the only kernel whose epilogue knows eq / er)
-          if (igemm_pick(first_pass.c, dtype, EPI_BNBWD, d.use_mfma != 0) == IMPL_CONV3 &&
-              igemm_pick(second_pass.c, dtype, EPI_BNBWD, d.use_mfma != 0) == IMPL_CONV3) {
-            have_second = true;
-            second_buf = sr.buf;
-            a.out = nullptr;
-            o.bytes = out_bytes(c) + srcb + w_bytes(c);          // reads dy and x, writes nothing
-            second_pass.bytes = out_bytes(c) + srcb * 2.0 + w_bytes(c);
-            if (r1_idx >= 0) {   // norm1's sums from the weight gradient's factor correlations: the first pass becomes the finish launch
-              WgradArgs f = (*ops)[r1_idx].w;
-              f.sbuf = r1_sbuf;
-              f.t_mean = bn.mean + sr.bn_c0; f.t_invstd = bn.invstd + sr.bn_c0;   // (mark of the factor form; the kernel needs scale / shift only)
-              if (wgrad_pick(f, dtype, d.use_mfma != 0) == IMPL_WG5) {
-                Op& wo = (*ops)[r1_idx];
-                wo.w = f;
-                wo.chain = 1;
-                const PackDesc& wpd = P.packs[c.dpack[0]];
-                Fin64Args r;
-                memset(&r, 0, sizeof(r));
-                r.sbuf = r1_sbuf; r.dpack = f.dpack; r.Npad = f.Npad;
-                r.w = Pp + T(c.wname).off; r.Kin = c.Kin; r.nreal = c.N; r.dtype = dtype;
-                for (int t = 0; t < 25; ++t) r.tapw[t] = (unsigned char)(wpd.seg[0].tapw[t] & 0xff);
-                r.scale = bn.scale + sr.bn_c0; r.shift = bn.shift + sr.bn_c0;
-                r.mean = bn.mean + sr.bn_c0; r.invstd = bn.invstd + sr.bn_c0;
-                r.red1 = bn.red1 + sr.bn_c0; r.red2 = bn.red2 + sr.bn_c0;
-                o.kind = OP_FIN64; o.epi = 0; o.impl = IMPL_AUTO; o.chain = 1;
-                o.f64 = r;     // (overwrites the first pass's arguments: `a` is dead from here on)
-                tag(o, "wg5.fin64", short_name(c.wname), 0, W5_SBUF64_FLOATS * 4.0);
-                r1_stats = true;
-              }
-            }
-          }
-        }
-      }
-      if (pending_w) {
-        pending_w = false;
-        Op dgrad_op = ops->back();
-        // slots for the weight-gradient partials of the fused launch (pointwise.h: Bw1Args::part).  Reserved by the shape of the pair
-        // alone - the sizing pass and the bound pass must take the same bytes, and bw1_eligible looks at pointers
-        float* part = nullptr;
-        int part_slots = 0;
-        if (!raw && dtype != DT_F32 && c.R == 1 && c.S == 1 && c.N == 128 && c.nseg == 1) {
-          const Bw1Geom q = bw1_geometry(dgrad_op.c);
-          part_slots = q.nsplit * q.nct;
-          part = wptr<float>((size_t)part_slots * B1_SLOT_FLOATS);
-        }
-        if (!raw && bw1_eligible(saved_w.w, dgrad_op.c, dtype)) {
-          Op& f = ops->back();
-          f.kind = OP_BW1;
-          f.b1.dpack = saved_w.w.dpack;
-          f.b1.dNpad = saved_w.w.Npad;
-          f.b1.wC = saved_w.w.seg[0].C;
-          f.b1.part = part;
-          f.b1.part_slots = part_slots;
-          f.b1.nct = f.b1.ntiles = f.b1.tiles_per_wg = f.b1.xcd_group = f.b1.nsplit = 0;
-          char cb[32];
-          // the pair's traffic with every operand read once: the data gradient's bytes + the packed weight gradient
-          tag(f, ncls("bw1", f.c.Npad, cb), short_name(c.wname), dgrad_op.flops + saved_w.flops, dgrad_op.bytes + w_bytes(c) * 4.0 / esz);
-          if (part != nullptr) {  // the slots are added up beside the data-gradient chain (weight-gradient stream)
-            const Bw1Args b1 = f.b1;
-            Op& rop = push(OP_BW1RED);
-            rop.leaf = 1;
-            rop.b1 = b1;
-            tag(rop, "bw1.reduce", short_name(c.wname), 0, ((double)part_slots + b1.nct) * B1_SLOT_FLOATS * 4.0);
-          }
-          conv_grad_done(c);
-        } else {  // not this time: weight gradient, bucket bookkeeping, data gradient - in the original order
-          ops->pop_back();
-          ops->push_back(saved_w);
-          conv_grad_done(c);
-          ops->push_back(dgrad_op);
-        }
-      }
-      if (!raw) sb.ginit = true;
+      if (st.raw_stats && s == 1 && is_raw_input(sr.buf)) continue;   // its only purpose were the two sums wg5.rawfin has just produced
+      emit_dgrad_seg(c, s, st);
+      split_two_pass(c, s, st);
+      if (st.w1_held) fold_bw1(c, st);   // (a 1x1 pair has one segment with a data gradient: this runs once)
+      if (!is_raw_input(sr.buf)) bufs[sr.buf].ginit = true;
     }
-    if (pending_w) { ops->push_back(saved_w); conv_grad_done(c); pending_w = false; }  // (no data gradient was emitted)
-    if (wt_deferred) { ops->push_back(wt_op); conv_grad_done(c); }
-    if (r1_wait) conv_grad_done(c);
+    // ... but three steps move it behind the data gradient: the held-back wg3 launch (it reads the data gradient's compact copy: the
+    // last launch is wg3 itself, emitted here); the bw1 fold (the last launch is bw1's slot reduction, or bw1 itself without slots;
+    // unfolded, the weight gradient put back, with the data gradient following the bookkeeping); fin64 (the finish launch, the former
+    // first pass, adds into this convolution's packed gradient: it is the last).
+    if (st.wg3_held) ops->push_back(st.wg3_op);
+    if (st.wgrad_side_open()) conv_grad_done(c);
+    if (st.dgrad_behind) ops->push_back(st.dgrad_op);
+    // ---- BatchNorm backward of the norms in front of the segments ----
+    if (st.have_second) bufs[st.second_buf].materialized = true;   // (no apply_corr behind the finalize: the second pass stores the final gradient)
     int done = -1;
-    if (have_second) bufs[second_buf].materialized = true;   // (no apply_corr behind the finalize: the second pass stores the final gradient)
     for (int s = 0; s < c.nseg; ++s) {
       const int bn = c.seg[s].bn;
       if (bn < 0 || bn == done || c.seg[s].dgrad == DG_NONE) continue;
       emit_bn_bwd_finalize(bn);
       done = bn;
     }
-    if (have_second) ops->push_back(second_pass);
+    if (st.have_second) ops->push_back(st.second_pass);
   }
 
   void emit_pool_fwd(PoolRec& p) {
@@ -1089,7 +1146,7 @@ struct Builder {
   }
   void emit_pool_bwd(PoolRec& p) {
     // the stem: pool0 backward, norm0's reductions and conv0's weight gradient feed parameter gradients only
-    leaf_scope = true;
+    LeafScope leaf(*this, true);
     Op& o = push(OP_POOLBWD);
     MaxpoolBwdArgs& a = o.mpb;
     Buf &yb = bufs[p.y0buf];
@@ -1106,7 +1163,6 @@ struct Builder {
     tag(o, "maxpool.bwd", "pool0", 0, (2.0 * yb.B * yb.H * yb.W + 2.0 * ob.B * ob.H * ob.W) * p.C * esz + (double)ob.B * ob.H * ob.W * p.C);
     yb.ginit = true;
     emit_bn_bwd_finalize(p.bn);
-    leaf_scope = false;
   }
 
   // -------------------------------------------------------------------------------- layer records
@@ -1128,15 +1184,7 @@ struct Builder {
     // forward packs (one per phase) and dgrad packs (one per segment that needs a data gradient)
     for (auto& ph : c.phases) ph.pack = add_pack(c, ph.taps, false, 0, &ph.taps1);
     for (int s = 0; s < c.nseg; ++s) {
-      std::vector<Tap> t;
-      switch (c.seg[s].dgrad) {
-        case DG_FLIP: t = taps_conv_dgrad(c.R, c.S, c.pad); break;
-        case DG_POOL2: t = taps_conv(1, 1, 0); break;
-        case DG_CONVT: t = taps_convT_dgrad(); break;
-        case DG_UP2: t = taps_up2_merged_dgrad(); break;
-        default: continue;
-      }
-      c.dpack[s] = add_pack(c, t, true, s);
+      if (c.seg[s].dgrad != DG_NONE) c.dpack[s] = add_pack(c, dgrad_taps(c, c.seg[s].dgrad), true, s);
     }
     // thin outputs: compute the weight gradient in the transposed form; it fills the dgrad-shaped packed gradient
     if (c.nseg == 1 && !c.transposed && c.seg[0].mode == G_PLAIN && c.seg[0].istride == 1 && c.seg[0].dgrad == DG_FLIP &&
@@ -1152,6 +1200,16 @@ struct Builder {
     // FLOPs (2*MACs) in the reference's formulation
     flops += conv_flops(c, 1);
   }
+  // A convolution of ONE segment and ONE phase (R x R, stride `istride`, output at the resolution Ho x Wo of the row grid): record,
+  // segment, geometry, phase and packs in one go.
+  void plain_conv(const std::string& wname, int N, int Kin, int R, int pad, int buf, int ch0, int mode, int istride, int bn, int dgrad,
+                  int Ho, int Wo, int obuf, int och0) {
+    ConvRec& c = new_conv(wname, false, N, Kin, R, R, pad);
+    set_seg(c, 0, buf, ch0, Kin, 0, mode, istride, bn, 0, dgrad);
+    c.B = bufs[buf].B; c.Ho = Ho; c.Wo = Wo; c.obuf = obuf; c.och0 = och0;
+    c.phases.push_back({0, 0, taps_conv(R, R, pad), -1});
+    finish_conv(c);
+  }
   void set_seg(ConvRec& c, int s, int buf, int ch0, int Cw, int koff, int mode, int istride, int bn, int bn_c0, int dgrad) {
     SegRec& sr = c.seg[s];
     sr.buf = buf; sr.ch0 = ch0; sr.Cw = Cw; sr.C = rup(Cw, 8); sr.koff = koff; sr.mode = mode; sr.istride = istride;
@@ -1162,12 +1220,7 @@ struct Builder {
   void stem(const std::string& p, int inbuf, int in_ch, int obuf, int och0) {
     const Buf ib = bufs[inbuf];  // by value: new_buf() may reallocate `bufs`
     const int y0 = new_buf(ib.B, ib.H / 2, ib.W / 2, g.nif, true, true);
-    ConvRec& c = new_conv(p + ".conv0.weight", false, g.nif, in_ch, 7, 7, 3);
-    set_seg(c, 0, inbuf, 0, in_ch, 0, G_PLAIN, 2, -1, 0, DG_NONE);
-    c.B = ib.B; c.Ho = ib.H / 2; c.Wo = ib.W / 2;
-    c.obuf = y0; c.och0 = 0;
-    c.phases.push_back({0, 0, taps_conv(7, 7, 3), -1});
-    finish_conv(c);
+    plain_conv(p + ".conv0.weight", g.nif, in_ch, 7, 3, inbuf, 0, G_PLAIN, 2, -1, DG_NONE, ib.H / 2, ib.W / 2, y0, 0);
     PoolRec pr;
     pr.y0buf = y0;
     pr.bn = new_bn(p + ".norm0", g.nif);
@@ -1191,22 +1244,10 @@ struct Builder {
       const int y1 = new_buf(X.B, X.H, X.W, rup(bw, 8), true, true, /*matz=*/K >= matz_k);
       const int n1 = new_bn(q + ".norm1", K);
       bn_range(n1, xb, base, 0, K);
-      {
-        ConvRec& c = new_conv(q + ".conv1.weight", false, bw, K, 1, 1, 0);
-        set_seg(c, 0, xb, base, K, 0, G_PLAIN, 1, n1, 0, DG_FLIP);
-        c.B = X.B; c.Ho = X.H; c.Wo = X.W; c.obuf = y1; c.och0 = 0;
-        c.phases.push_back({0, 0, taps_conv(1, 1, 0), -1});
-        finish_conv(c);
-      }
+      plain_conv(q + ".conv1.weight", bw, K, 1, 0, xb, base, G_PLAIN, 1, n1, DG_FLIP, X.H, X.W, y1, 0);
       const int n2 = new_bn(q + ".norm2", bw);
       bn_range(n2, y1, 0, 0, bw);
-      {
-        ConvRec& c = new_conv(q + ".conv2.weight", false, g.k, bw, 3, 3, 1);
-        set_seg(c, 0, y1, 0, bw, 0, G_PLAIN, 1, n2, 0, DG_FLIP);
-        c.B = X.B; c.Ho = X.H; c.Wo = X.W; c.obuf = xb; c.och0 = base + K;
-        c.phases.push_back({0, 0, taps_conv(3, 3, 1), -1});
-        finish_conv(c);
-      }
+      plain_conv(q + ".conv2.weight", g.k, bw, 3, 1, y1, 0, G_PLAIN, 1, n2, DG_FLIP, X.H, X.W, xb, base + K);
     }
   }
 
@@ -1214,11 +1255,7 @@ struct Builder {
     const Buf X = bufs[xb];
     const int n = new_bn(p + ".norm", C);
     bn_range(n, xb, base, 0, C);
-    ConvRec& c = new_conv(p + ".conv.weight", false, C / 2, C, 1, 1, 0);
-    set_seg(c, 0, xb, base, C, 0, G_POOL2, 1, n, 0, DG_POOL2);
-    c.B = X.B; c.Ho = X.H / 2; c.Wo = X.W / 2; c.obuf = obuf; c.och0 = och0;
-    c.phases.push_back({0, 0, taps_conv(1, 1, 0), -1});
-    finish_conv(c);
+    plain_conv(p + ".conv.weight", C / 2, C, 1, 0, xb, base, G_POOL2, 1, n, DG_POOL2, X.H / 2, X.W / 2, obuf, och0);
   }
 
   void build() {
@@ -1263,11 +1300,7 @@ struct Builder {
         concat_rec = recs.size();
         const int n = new_bn("concat_module.norm", 2 * C);
         bn_range(n, F, 0, 0, 2 * C);
-        ConvRec& c = new_conv("concat_module.conv.weight", false, C, 2 * C, 1, 1, 0);
-        set_seg(c, 0, F, 0, 2 * C, 0, G_PLAIN, 1, n, 0, DG_FLIP);
-        c.B = B; c.Ho = bufs[F].H; c.Wo = bufs[F].W; c.obuf = X[b]; c.och0 = base[b];
-        c.phases.push_back({0, 0, taps_conv(1, 1, 0), -1});
-        finish_conv(c);
+        plain_conv("concat_module.conv.weight", C, 2 * C, 1, 0, F, 0, G_PLAIN, 1, n, DG_FLIP, bufs[F].H, bufs[F].W, X[b], base[b]);
       }
       dense_block("features.denseblock" + std::to_string(b + 1), X[b], base[b], b);
       if (b < g.nb - 1) {
@@ -1288,13 +1321,7 @@ struct Builder {
       const int n0 = new_bn(p + ".norm0", nin);
       bn_range(n0, inb, 0, 0, nin);
       const int Rb = new_buf(I.B, I.H, I.W, nf, true, true, /*matz=*/(matz_mask & 1) != 0);
-      {
-        ConvRec& c = new_conv(p + ".conv_reduce.weight", false, nf, nin, 1, 1, 0);
-        set_seg(c, 0, inb, 0, nin, 0, G_PLAIN, 1, n0, 0, DG_FLIP);
-        c.B = I.B; c.Ho = I.H; c.Wo = I.W; c.obuf = Rb; c.och0 = 0;
-        c.phases.push_back({0, 0, taps_conv(1, 1, 0), -1});
-        finish_conv(c);
-      }
+      plain_conv(p + ".conv_reduce.weight", nf, nin, 1, 0, inb, 0, G_PLAIN, 1, n0, DG_FLIP, I.H, I.W, Rb, 0);
       const int n1 = new_bn(p + ".norm1", nf);
       bn_range(n1, Rb, 0, 0, nf);
       int ob;
@@ -1355,7 +1382,6 @@ struct Builder {
   // one K segment that spans the whole master, whole 32-channel groups, 1x1 or 3x3, the master contiguous along (k, tap) or (n, tap),
   // and every master tap covered by the group (the parity phases of a ConvTranspose together).  Marks PackDesc::tiled and appends the
   // tiles - 1x1 masters first, then 3x3 (one launch per instantiation) - with descriptor indices relative to `v`.
-  const bool pack_tiles_on = !P.sw.no_pack_tiles;
   void make_tiles(std::vector<PackDesc>& v, size_t begin, size_t end, std::vector<PackTile>& out, int& nt1, int& nt9) {
     nt1 = nt9 = 0;
     for (size_t i = begin; i < end; ++i) v[i].tiled = 0;
@@ -1407,16 +1433,12 @@ struct Builder {
     for (int s = 0; s < pd.nseg; ++s) chunks += pd.seg[s].nchunks;
     return chunks * pd.Npad;
   }
-  PackTile* ptiles_dev = nullptr;
-  PackTile* utiles_dev = nullptr;
-  int pt_early1 = 0, pt_early9 = 0, pt_late1 = 0, pt_late9 = 0;
 
   // -------------------------------------------------------------------------------- launch lists
   void emit_convert(std::vector<int>& idx) {
     auto one = [&](int buf, int c1, int c2, int which) {
       Op& o = push(OP_CONVERT);
       ConvertArgs& a = o.cv;
-      memset(&a, 0, sizeof(a));
       a.C1 = c1; a.C2 = c2;
       a.scale = 1.0f;
       a.dst = bufs[buf].x;
@@ -1459,21 +1481,18 @@ struct Builder {
   // (leaf 3: no fork event per launch).  Emitted one encoder after the other, the host fed ~1 ms of side-stream launches before the
   // first stream's first launch reached the queue; together with the join behind the full weight pack the main queue sat idle for
   // 2.2 ms at the start of every C3/C4/C5 step (tools/probes/dump_first.py; profiles/r04/ablations.txt section 8).
-  size_t s2_recs = 0, concat_rec = 0;
-  const bool s2_overlap = !lab_flag("DMM_NO_S2_OVERLAP");  // lab knob
-  const bool s2_interleave = !P.sw.no_s2_interleave;
   void emit_record(size_t ri, bool on_side) {
     const Rec& r = recs[ri];
     if (pack_split > 0 && ri == pack_cut_rec) { Op& o = push(OP_JOIN); o.epi = 1; tag(o, "other", "join.pack", 0, 0); }
     const size_t first = ops->size();
-    leaf_scope = on_side;
-    if (r.type == 0) emit_conv_fwd(convs[r.idx]); else emit_pool_fwd(pools[r.idx]);
-    leaf_scope = false;
+    {
+      LeafScope leaf(*this, on_side);
+      if (r.type == 0) emit_conv_fwd(convs[r.idx]); else emit_pool_fwd(pools[r.idx]);
+    }
     if (on_side && s2_interleave)
       for (size_t i = first; i < ops->size(); ++i)
         if ((*ops)[i].leaf == 1) { if (s2_chain_started) (*ops)[i].leaf = 3; s2_chain_started = true; }
   }
-  bool s2_chain_started = false;
   void emit_forward_records() {
     const bool beside = g.fusion == 2 && s2_overlap && s2_recs > 0;
     s2_chain_started = false;
@@ -1493,16 +1512,6 @@ struct Builder {
   }
 
   // ---------------------------------------------------------------- gradient buckets (data-parallel overlap)
-  struct BucketRec {
-    int64_t off = 0, n = 0;
-    int convs_left = 0, bns_left = 0;
-    int first_desc = 0, ndesc = 0, rows = 0;
-    int tile0 = 0, nt1 = 0, nt9 = 0;   // the bucket's range of P.unpack_tiles (descriptor indices relative to P.unpacks)
-    int last_main = -1, last_side = -1;
-  };
-  std::vector<BucketRec> brecs;
-  PackDesc* unpack_dev = nullptr;
-  int* unprefix_dev = nullptr;
   int bucket_of(int64_t off) const {
     for (size_t b = 0; b < brecs.size(); ++b)
       if (off >= brecs[b].off && off < brecs[b].off + brecs[b].n) return (int)b;
@@ -1570,7 +1579,6 @@ struct Builder {
     if (o.kind == OP_WGRAD || o.kind == OP_UNPACK || o.leaf) brecs[b].last_side = op_index; else brecs[b].last_main = op_index;
   }
   void conv_grad_done(const ConvRec& c) {  // called behind the weight-gradient launch(es) of a convolution
-    if (defer_scope) { deferred_convs.push_back(&c); return; }
     const int b = bucket_of(T(c.wname).off);
     BucketRec& bk = brecs[b];
     if (--bk.convs_left > 0 || bk.ndesc == 0) return;   // (ndesc counts the tile kernels' descriptors as well)
@@ -1605,14 +1613,6 @@ struct Builder {
     }
     std::stable_sort(P.buckets.begin(), P.buckets.end(), [](const GradBucket& a, const GradBucket& b) { return a.ready < b.ready; });
   }
-
-  bool pad_pitch = lab_flag("DMM_PITCH_PAD");  // measured: no effect on MI355X for this access pattern; off
-  PackDesc* pack_dev = nullptr;
-  int* prefix_dev = nullptr;
-  int total_rows = 0;          // rows of the pack launch behind the split (all rows without a split)
-  int pack_split = 0, pack_rows0 = 0;
-  size_t pack_cut_rec = 0;     // the first forward record whose weights the second pack launch holds
-  static constexpr double PACK_EARLY_ELEMS = 3.0e6;
 
   void emit_all() {
     // pack tables live in the workspace
@@ -1692,7 +1692,6 @@ struct Builder {
     {
       Op& o = push(OP_BCE);
       BceArgs& a = o.bce;
-      memset(&a, 0, sizeof(a));
       a.dlogits = bufs[dl].x;
       a.out = P.metrics;
       a.B = d.batch; a.NC = g.nc; a.H = d.height; a.W = d.width;
@@ -1707,7 +1706,6 @@ struct Builder {
     for (int i = (int)recs.size() - 1; i >= 0; --i) {
       if (recs[i].type == 0) emit_conv_bwd(convs[recs[i].idx]); else emit_pool_bwd(pools[recs[i].idx]);
     }
-    flush_deferred();
     finish_buckets();
   }
 };
@@ -1729,7 +1727,6 @@ PlanSwitches PlanSwitches::from_environment() {
   s.no_two_pass = on("DMM_NO_TWO_PASS");
   s.no_eff_compact = on("DMM_NO_EFF_COMPACT");
   s.no_s2_interleave = on("DMM_NO_S2_INTERLEAVE");
-  s.defer_wgrad = on("DMM_DEFER_WGRAD");
   s.no_raw_stats = on("DMM_NO_RAW_STATS");
   s.no_r1_stats = on("DMM_NO_R1_STATS");
   const char* pc = getenv("DMM_PACK_CUT");

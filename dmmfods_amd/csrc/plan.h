@@ -1,5 +1,6 @@
 // Host-side plan of the Dense_U_Net_lidar training step: topology -> buffers -> kernel launch list.
 #pragma once
+#include <cstring>
 #include <stdexcept>
 #include <string>
 #include <vector>
@@ -75,7 +76,8 @@ struct Op {
     RawFinArgs rf;
     Fin64Args f64;
   };
-  Op() : kind(0), epi(0), leaf(0), chain(0), signal(-1), impl(IMPL_AUTO), flops(0), bytes(0) { label[0] = 0; }
+  // A record starts out all zero - the argument union included, so an emitter assigns only what its launch uses.
+  Op() { memset(static_cast<void*>(this), 0, sizeof(*this)); signal = -1; impl = IMPL_AUTO; }
 };
 
 }  // namespace dmm
@@ -101,7 +103,6 @@ struct GradBucket {
 //   DMM_NO_EFF_COMPACT=1    wg3.hip gathers its gradient operand from the block buffers instead of reading conv3.hip's compact copy
 //   DMM_NO_S2_INTERLEAVE=1  mid fusion: the second encoder's launch records behind the first's instead of alternating
 //   DMM_PACK_CUT=<n>        the forward record in front of which the late layers' weight pack is joined (1 = behind the stem)
-//   DMM_DEFER_WGRAD=1       the head's / decoder's multi-tap weight gradients held back until backward reaches the encoder
 //   DMM_NO_R1_STATS=1       the BatchNorm-backward sums of the head's norm1 from the reductions-only first pass of the 5x5 data gradient
 //                           instead of from the 5x5 weight gradient's factor correlations (wg5.hip, PA = 3)
 //   DMM_NO_RAW_STATS=1      the BatchNorm-backward sums of the head's raw-input channels from a data-gradient pass of their own
@@ -110,7 +111,7 @@ struct GradBucket {
 // diagnostics: DMM_TRACE_DESTROY.  Everything else that used to be an environment switch is a compile-time lab knob (common.h).
 struct PlanSwitches {
   bool no_pack_tiles = false, no_hf = false, no_c3_merge = false, no_cvp_merge = false, no_wgp_merge = false, no_two_pass = false,
-       no_eff_compact = false, no_s2_interleave = false, defer_wgrad = false, no_raw_stats = false, no_r1_stats = false;
+       no_eff_compact = false, no_s2_interleave = false, no_raw_stats = false, no_r1_stats = false;
   int pack_cut = 0;  // 0: by weight count
   static PlanSwitches from_environment();
 };

@@ -248,7 +248,6 @@ HOST_DRIVE_CASES = [
     ("d121e", "bf16", 2, 64, 96, {"DMM_NO_RAW_STATS": "1"}),
     ("d121e", "f16", 2, 64, 96, {"DMM_NO_R1_STATS": "1"}),
     ("d121e", "f16", 2, 64, 96, {"DMM_NO_HF": "1", "DMM_NO_C3_MERGE": "1", "DMM_NO_CVP_MERGE": "1", "DMM_NO_WGP_MERGE": "1"}),
-    ("d121e", "f16", 2, 64, 96, {"DMM_DEFER_WGRAD": "1", "DMM_NO_WGP_MERGE": "1"}),
     ("d121m", "f16", 2, 128, 192, {}),
     ("d121m2", "f16", 2, 64, 96, {}),
     ("d169m", "f16", 2, 64, 96, {}),
@@ -276,6 +275,43 @@ def test_plan_life_under_sanitizers_and_the_teardown_contract(host_drive):
         lives = [ln for ln in r.stdout.splitlines() if ln.startswith("life ")]
         assert len(lives) == 3 and all(", 0 bad," in ln and ln.endswith("violations 0") for ln in lives), lives
         assert "streams alive 2 (created 2)" in lives[-1], lives[-1]          # the side and the pack stream, once per process
+
+
+def test_plan_dump_is_canonical(host_drive):
+    """`drive dump` prints a bound plan as text - sizes, every field of every launch record, pack / unpack tables, buckets - so that two
+    builds of the plan builder can be compared byte for byte without a GPU (a refactor of plan.cpp is checked that way).  For that the
+    text must depend on the plan alone: two runs agree, and so does a third with the workspace and the three arenas mapped somewhere
+    else (pointers are printed as region+offset); no pointer lies outside the plan's regions; and the lists it prints are the lists the
+    life-cycle run of the same case executes (same record counts)."""
+    base = {k: v for k, v in os.environ.items() if not k.startswith("DMM_") and not k.startswith("DRIVE_")}
+    base.update(ASAN_OPTIONS="detect_leaks=0:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
+    for case in (("tiny_mid", "bf16", 2, 96, 160, {}), ("d121e", "f16", 2, 64, 96, {})):
+        assert case in HOST_DRIVE_CASES
+        arch, dtype, b, h, w, envx = case
+        args = [arch, dtype, str(b), str(h), str(w)]
+        outs = []
+        for extra in ({}, {}, {"DRIVE_MAP_SHIFT_MIB": "6"}):
+            r = subprocess.run([host_drive, "dump"] + args, env=dict(base, **envx, **extra), capture_output=True, text=True, timeout=600)
+            assert r.returncode == 0, (case, extra, (r.stdout[-500:] + r.stderr)[-3000:])
+            outs.append(r.stdout)
+        assert outs[0] == outs[1] == outs[2], case
+        assert "OUTSIDE" not in outs[0] and "ws+" in outs[0] and "params+" in outs[0] and "grads+" in outs[0] and "buffers+" in outs[0]
+        records = {m[1]: int(m[2]) for m in re.finditer(r"^list (\w+) records=(\d+)$", outs[0], re.M)}
+        assert set(records) == {"fwd_train", "fwd_eval", "bwd"}, records
+        blocks = {}
+        cur = None
+        for ln in outs[0].splitlines():
+            if ln.startswith("list "):
+                cur = ln.split()[1]
+            elif not ln.startswith(" "):
+                cur = None
+            elif ln.startswith("  op ") and cur:
+                blocks[cur] = blocks.get(cur, 0) + 1
+        assert blocks == records, (blocks, records)
+        r = subprocess.run([host_drive] + args + ["1"], env=dict(base, **envx), capture_output=True, text=True, timeout=600)
+        m = re.search(r"(\d+) \+ (\d+) launch records", r.stdout)
+        assert r.returncode == 0 and m, (r.stdout + r.stderr)[-2000:]
+        assert (records["fwd_train"], records["bwd"]) == (int(m[1]), int(m[2])), (records, m[0])
 
 
 def test_bind_checks_the_bound_pass_against_the_sizing_pass(host_drive):

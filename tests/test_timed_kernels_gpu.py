@@ -485,45 +485,6 @@ def test_two_pass_batchnorm_backward_of_the_head(dtype, tol, monkeypatch):
         assert torch.isfinite(grads[0][k]).all(), k
 
 
-def test_deferred_head_and_decoder_weight_gradients(monkeypatch):
-    """Round 4 experiment, kept as a switch (DMM_DEFER_WGRAD=1; measured slower, plan.cpp): the head's / decoder's multi-tap weight
-    gradients enter the backward list where the main chain reaches the encoder instead of at the front.  Same launches, same
-    operands: against the default order the gradients agree to the order of their fp32 atomics, the launch multiset is the same
-    and the first weight-gradient launch of the head then FOLLOWS the decoder's last data gradient."""
-    from oracle import restatement as R
-    arch = R.Arch(growth_rate=32, block_config=(1, 1), num_init_features=64, concat_before_block_num=1, stream_2_in_channels=3)
-    model = _model(arch, "fp16")
-    model.load_state_dict(R.make_state(arch, seed=11))
-    model = model.to(DEV).train()
-    rgb, lidar, tgt = (t.to(DEV) for t in R.make_inputs(arch, 2, 64, 96, seed=3))
-    grads, labels = {}, {}
-    monkeypatch.setenv("DMM_NO_WGP_MERGE", "1")     # (held-back phase launches are not merged into one: compare like with like)
-    monkeypatch.setenv("DMM_NO_RAW_STATS", "1")     # (nor does a held-back raw-segment weight gradient feed the norm's sums: round 5)
-    monkeypatch.setenv("DMM_NO_R1_STATS", "1")      # (nor the held-back 5x5 weight gradient norm1's: the data-gradient chain would wait for it)
-    for off in (0, 1):
-        if off:
-            monkeypatch.delenv("DMM_DEFER_WGRAD", raising=False)
-        else:
-            monkeypatch.setenv("DMM_DEFER_WGRAD", "1")
-        model.close()
-        model(rgb, lidar)
-        model.loss_backward(tgt)
-        torch.cuda.synchronize()
-        labels[off] = plan_labels(model._last[0])
-        grads[off] = {k: p.grad.detach().clone() for k, p in model.named_parameters()}
-    monkeypatch.delenv("DMM_DEFER_WGRAD", raising=False)
-    monkeypatch.delenv("DMM_NO_WGP_MERGE", raising=False)
-    monkeypatch.delenv("DMM_NO_RAW_STATS", raising=False)
-    monkeypatch.delenv("DMM_NO_R1_STATS", raising=False)
-    model.close()
-    assert sorted(labels[0]) == sorted(labels[1])
-    first_head_w = {o: next(i for i, lab in enumerate(labels[o]) if lab.startswith(("wgp.", "wg5.")) and "/h." in lab) for o in (0, 1)}
-    last_dec_dgrad = {o: max(i for i, lab in enumerate(labels[o]) if ".bnbwd" in lab and "/d." in lab) for o in (0, 1)}
-    assert first_head_w[0] > last_dec_dgrad[0] and first_head_w[1] < last_dec_dgrad[1], (first_head_w, last_dec_dgrad)
-    for k in grads[0]:
-        assert _rel(grads[0][k], grads[1][k]) < 2e-3, k
-
-
 @pytest.mark.parametrize("dtype,tol", [("fp16", 1e-3), ("bf16", 1e-3)])
 def test_head_weight_gradient_phases_in_one_launch(dtype, tol, monkeypatch):
     """Round 4: the four output-parity phases of the head's 3x3 weight gradient (wgp.hip) run as ONE launch - phase p of a tile range

@@ -2,13 +2,14 @@
 # Builds the HOST code of libdmmfods_hip.so (plan.cpp, capi.cpp and the host side - launchers, eligibility tests - of every kernel
 # file) with AddressSanitizer + UndefinedBehaviorSanitizer against the fake HIP runtime of this directory, plus the driver.
 # No GPU, no device code: `-x hip --offload-host-only`.  Output: tools/hoststub/_build/drive   (about 20 s with 8 jobs)
+# DRIVE_SRC=<dir>: build the library's sources from another csrc directory (a checkout of another commit, to compare `drive dump`).
 set -e
 HERE="$(cd "$(dirname "$0")" && pwd)"
-SRC="$HERE/../../dmmfods_amd/csrc"
+SRC="${DRIVE_SRC:-$HERE/../../dmmfods_amd/csrc}"
 OUT="${1:-$HERE/_build}"
 mkdir -p "$OUT"
 CLANG=/opt/rocm/lib/llvm/bin/clang++
-FLAGS="-x hip --offload-host-only --offload-arch=gfx950 -std=c++17 -O1 -g -fsanitize=address,undefined -fno-gpu-sanitize -fno-sanitize-recover=undefined -fno-omit-frame-pointer -I/opt/rocm/include -D__HIP_PLATFORM_AMD__ -w $DRIVE_EXTRA_FLAGS"
+FLAGS="-x hip --offload-host-only --offload-arch=gfx950 -std=c++17 -O1 -g -fsanitize=address,undefined -fno-gpu-sanitize -fno-sanitize-recover=undefined -fno-omit-frame-pointer -I/opt/rocm/include -I$SRC -D__HIP_PLATFORM_AMD__ -w $DRIVE_EXTRA_FLAGS"
 pids=()
 cc() { $CLANG $FLAGS "${@:3}" -c "$1" -o "$OUT/$2" & pids+=($!); if [ ${#pids[@]} -ge 8 ]; then wait "${pids[0]}"; pids=("${pids[@]:1}"); fi; }
 for f in bw1 cf conv3 cvp cvw halo hf pig pointwise thin wg3 wg5 wgp wgpw; do cc "$SRC/$f.hip" "$f.o"; done

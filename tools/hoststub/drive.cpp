@@ -17,6 +17,12 @@
 //   drive single <fwd|wgrad|dgrad|fused> <dtype> <B> <H> <W> <Cin> <Cout> <R> <pad> <transposed> <mode>
 //                                                  one call of a single-kernel entry point on operands that are addresses only
 //   drive refuse                                   launch_wgrad(..., IMPL_GENERIC) on arguments the generic kernel does not implement
+// And one prints what a plan IS, so that two builds of the plan builder can be compared byte for byte without a GPU:
+//   drive dump <arch> <dtype> <batch> <H> <W>      a bound plan (workspace reserved, never touched; nothing launched) as canonical text:
+//                                                  sizes, every field of every launch record, pack / unpack tables, buckets.  Pointers
+//                                                  are printed as region+offset, so the text does not depend on where anything is mapped
+//                                                  (DRIVE_MAP_SHIFT_MIB=<n> moves the workspace and the three arenas, to show that).
+// DRIVE_NO_MFMA=1 (any mode): the description asks for use_mfma = 0.
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -25,8 +31,8 @@
 
 #include <sys/mman.h>
 
-#include "../../dmmfods_amd/csrc/plan.h"
-#include "../../dmmfods_amd/csrc/pointwise.h"
+#include "plan.h"        // dmmfods_amd/csrc, or the csrc directory build.sh was pointed at (DRIVE_SRC)
+#include "pointwise.h"
 
 extern "C" long fakehip_launches();
 extern "C" void fakehip_skip_large_memset(int on);
@@ -121,6 +127,7 @@ bool fill_desc(const std::string& arch, dmm_model_desc& d) {
   else if (arch == "tiny_no") { cfg({2, 2, 2}); d.concat_before_block_num = 1; d.stream_2_in_channels = 0; }
   else if (arch == "g8_mid") { cfg({2, 2, 2, 2}); d.growth_rate = 8; d.num_init_features = 16; d.concat_before_block_num = 3; d.stream_2_in_channels = 3; }  // smoke()'s net
   else return false;
+  if (getenv("DRIVE_NO_MFMA")) d.use_mfma = 0;
   return true;
 }
 
@@ -290,6 +297,191 @@ static int picks_main(int argc, char** argv) {
   return bad ? 1 : 0;
 }
 
+// ---- dump: the plan as canonical text ----
+// Every field of the argument struct a record's kind uses is printed (a Seg's taps up to ntaps, the ph_* arrays up to nphase, a
+// PackSeg's tapw up to ntaps); every emitter assigns or zeroes every field of its struct, so no printed field is indeterminate.
+// NOT printed: bytes of a record's union outside the member its kind uses, and the characters of `label` behind its terminator.
+namespace {
+struct Dumper {
+  Region reg[4];   // ws, params, grads, buffers
+  long outside = 0;
+  void ptr(const char* name, const void* p) {
+    if (p == nullptr) { printf(" %s=null", name); return; }
+    const uint8_t* q = (const uint8_t*)p;
+    for (auto& r : reg)
+      if (q >= r.lo && q < r.hi) { printf(" %s=%s+%zu", name, r.name, (size_t)(q - r.lo)); return; }
+    ++outside;
+    printf(" %s=OUTSIDE", name);
+  }
+#define DP(f) ptr(#f, (const void*)(a.f))
+#define DI(f) printf(" " #f "=%lld", (long long)(a.f))
+#define DU(f) printf(" " #f "=%llu", (unsigned long long)(a.f))
+#define DD(f) printf(" " #f "=%.17g", (double)(a.f))
+  void seg(const char* name, const Seg& a) {
+    printf("    %s:", name);
+    DP(src); DP(src2); DP(scale); DP(shift); DP(q); DP(r); DP(ql); DP(rl); DI(ld); DI(ld2); DI(Hs); DI(Ws); DI(C); DI(Cpad); DI(ntaps); DI(nchunks);
+    DI(mode); DI(istride);
+    printf(" taps=");
+    for (int t = 0; t < a.ntaps && t < MAX_TAPS; ++t) printf("%s%d", t ? "," : "", (int)a.taps[t]);
+    printf("\n");
+  }
+  void conv(const ConvArgs& a) {
+    for (int s = 0; s < a.nseg && s < 2; ++s) seg(s ? "seg1" : "seg0", a.seg[s]);
+    printf("    conv:");
+    DI(nseg); DI(B); DI(Ho); DI(Wo); DI(M); DP(wpack); DI(N); DI(Npad); DP(out); DI(ldo); DI(coff); DI(Hout); DI(Wout); DI(ostride); DI(py); DI(px);
+    DP(stat_sum); DP(stat_sq); DP(logits); DP(bx); DI(ldbx); DP(bscale); DP(bshift); DP(bmean); DP(binvstd); DP(red1); DP(red2); DI(accumulate);
+    DI(stat_stride); DI(pool2); DP(eff_out); DP(eq); DP(er); DI(nphase);
+    printf("\n");
+    for (int p = 0; p < a.nphase && p < 4; ++p) {
+      printf("    phase%d:", p);
+      DP(ph_wpack[p]); DI(ph_py[p]); DI(ph_px[p]); DI(ph_ntaps[p]);
+      printf(" ph_taps0=");
+      for (int t = 0; t < 4; ++t) printf("%s%d", t ? "," : "", (int)a.ph_taps0[p][t]);
+      printf(" ph_taps1=");
+      for (int t = 0; t < 9; ++t) printf("%s%d", t ? "," : "", (int)a.ph_taps1[p][t]);
+      printf("\n");
+    }
+  }
+  void wgrad(const WgradArgs& a) {
+    for (int s = 0; s < a.nseg && s < 2; ++s) seg(s ? "seg1" : "seg0", a.seg[s]);
+    seg("dy", a.dy);
+    printf("    wgrad:");
+    DI(nseg); DI(B); DI(Ho); DI(Wo); DI(M); DI(N); DI(Npad); DP(dpack); DI(rows_per_split); DI(kgroups); DP(part); DI(part_slots); DI(nphase);
+    DP(t_mean); DP(t_invstd); DP(sbuf);
+    printf("\n");
+    for (int p = 0; p < a.nphase && p < 4; ++p) {
+      printf("    phase%d:", p);
+      DP(ph_dpack[p]); DI(ph_ytap[p]); DI(ph_ntaps[p]);
+      printf(" ph_xtaps=");
+      for (int t = 0; t < 4; ++t) printf("%s%d", t ? "," : "", (int)a.ph_xtaps[p][t]);
+      printf("\n");
+    }
+  }
+  void op(const Op& o) {
+    printf("  op kind=%d epi=%d leaf=%d chain=%d signal=%d impl=%s label=%s flops=%.17g bytes=%.17g\n", o.kind, o.epi, o.leaf, o.chain, o.signal,
+           dmm_impl_name(o.impl), o.label, o.flops, o.bytes);
+    switch (o.kind) {
+      case OP_MEMSET: { const MemsetArgs& a = o.ms; printf("    memset:"); DP(p); DU(bytes); printf("\n"); break; }
+      case OP_COPY: { const CopyArgs& a = o.cp; printf("    copy:"); DP(dst); DP(src); DU(bytes); printf("\n"); break; }
+      case OP_CONVERT: { const ConvertArgs& a = o.cv; printf("    convert:"); DP(src1); DP(src2); DI(C1); DI(C2); DP(dst); DI(B); DI(H); DI(W); DP(stat_sum);
+                         DP(stat_sq); DD(scale); printf("\n"); break; }
+      case OP_IGEMM: conv(o.c); break;
+      case OP_WGRAD: wgrad(o.w); break;
+      case OP_BW1: case OP_BW1RED: { conv(o.b1.c); const Bw1Args& a = o.b1; printf("    bw1:"); DP(dpack); DI(dNpad); DI(wC); DP(part); DI(part_slots); DI(nct);
+                                     DI(ntiles); DI(tiles_per_wg); DI(xcd_group); DI(nsplit); printf("\n"); break; }
+      case OP_BNFIN: { const BnFinalizeArgs& a = o.bf; printf("    bnfin:"); DP(sum); DP(sq); DI(stat_stride); DD(count); DD(count_unbiased); DP(gamma); DP(beta);
+                       DP(running_mean); DP(running_var); DP(scale); DP(shift); DP(mean); DP(invstd); DI(C); DI(training); DD(momentum); DD(eps); printf("\n"); break; }
+      case OP_BNBWD: { const BnBwdFinalizeArgs& a = o.bb; printf("    bnbwd:"); DP(red1); DP(red2); DI(stat_stride); DP(mean); DP(invstd); DP(scale); DP(dgamma);
+                       DP(dbeta); DP(qd); DP(rd); DP(q); DP(r); DP(ql); DP(rl); DD(count); DD(grad_scale); DI(C); printf("\n"); break; }
+      case OP_POOL: { const MaxpoolArgs& a = o.mp; printf("    pool:"); DP(y0); DI(ld0); DI(H0); DI(W0); DI(B); DI(C); DP(scale); DP(shift); DP(out); DI(ldo); DI(Hp);
+                      DI(Wp); DP(argmax); DP(stat_sum); DP(stat_sq); DI(stat_stride); printf("\n"); break; }
+      case OP_POOLBWD: { const MaxpoolBwdArgs& a = o.mpb; printf("    poolbwd:"); DP(y0); DI(ld0); DI(H0); DI(W0); DI(B); DI(C); DP(scale); DP(shift); DP(gpool);
+                         DP(xpool); DP(q); DP(r); DP(ql); DP(rl); DP(mean); DP(invstd); DI(ldg); DI(Hp); DI(Wp); DP(argmax); DP(gy0); DP(red1); DP(red2);
+                         DI(stat_stride); printf("\n"); break; }
+      case OP_BCE: { const BceArgs& a = o.bce; printf("    bce:"); DP(logits); DP(target); DP(dlogits); DP(out); DI(B); DI(NC); DI(H); DI(W); DD(thr); DD(loss_scale);
+                     DI(kind); DI(from_prob);
+                     for (int k = 0; k < 8; ++k) { DD(alpha[k]); DD(gamma[k]); }
+                     DP(loss_out); DP(dx_out); DI(metrics); printf("\n"); break; }
+      case OP_PACK: case OP_UNPACK: { const PackArgs& a = o.pk; printf("    pack:"); DP(descs); DP(prefix); DI(ndesc); DI(total_rows); DD(grad_scale); DP(tdescs);
+                                      DP(tiles); DI(nt1); DI(nt9); printf("\n"); break; }
+      case OP_APPLYCORR: { const ApplyCorrArgs& a = o.ac; printf("    applycorr:"); DP(g); DP(y); DP(q); DP(r); DP(ql); DP(rl); DU(npix); DI(C); DI(ldg); DI(ldy);
+                           printf("\n"); break; }
+      case OP_FIN64: { const Fin64Args& a = o.f64; printf("    fin64:"); DP(sbuf); DP(dpack); DI(Npad); DP(w); DI(Kin); DI(nreal); DI(dtype); DP(scale); DP(shift);
+                       DP(mean); DP(invstd); DP(red1); DP(red2); printf(" tapw=");
+                       for (int t = 0; t < 28; ++t) printf("%s%d", t ? "," : "", (int)a.tapw[t]);
+                       printf("\n"); break; }
+      case OP_RAWFIN: { const RawFinArgs& a = o.rf; printf("    rawfin:"); DP(sbuf); DP(dpack); DI(Npad); DP(w); DI(Kin); DI(koff); DI(nreal); DP(gamma); DP(beta);
+                        DP(red1); DP(red2); printf(" tapw=");
+                        for (int t = 0; t < 9; ++t) printf("%s%d", t ? "," : "", a.tapw[t]);
+                        printf("\n"); break; }
+      case OP_JOIN: break;
+      default: ++outside; printf("    UNKNOWN KIND OUTSIDE\n");
+    }
+  }
+  void list(const char* name, const std::vector<Op>& ops) {
+    printf("list %s records=%zu\n", name, ops.size());
+    for (const Op& o : ops) op(o);
+  }
+  void descs(const char* name, const std::vector<PackDesc>& v) {
+    printf("table %s entries=%zu\n", name, v.size());
+    for (const PackDesc& a : v) {
+      printf("  desc:");
+      DP(w); DP(dst); DP(gw); DP(dpack); DI(N); DI(Npad); DI(nseg); DI(shared_master); DI(sn); DI(sk); DI(st); DI(rs); DI(tiled);
+      printf("\n");
+      for (int s = 0; s < a.nseg && s < 2; ++s) {
+        const PackSeg& g = a.seg[s];
+        printf("    packseg%d: Creal=%d Cpad=%d ntaps=%d nchunks=%d koff=%d tapw=", s, g.Creal, g.Cpad, g.ntaps, g.nchunks, g.koff);
+        for (int t = 0; t < g.ntaps && t < MAX_TAPS; ++t) printf("%s%08x", t ? "," : "", g.tapw[t]);
+        printf("\n");
+      }
+    }
+  }
+  static void ints(const char* name, const std::vector<int>& v) {
+    printf("%s n=%zu:", name, v.size());
+    for (int x : v) printf(" %d", x);
+    printf("\n");
+  }
+  static void tiles(const char* name, const std::vector<PackTile>& v) {
+    printf("table %s entries=%zu\n", name, v.size());
+    for (const PackTile& t : v) printf("  tile desc=%d nsib=%d n0=%d cg=%d\n", t.desc, t.nsib, t.n0, t.cg);
+  }
+#undef DP
+#undef DI
+#undef DU
+#undef DD
+};
+}  // namespace
+
+static int dump_main(int argc, char** argv) {
+  if (argc < 7) return 64;
+  dmm_model_desc d;
+  if (!fill_desc(argv[2], d)) { fprintf(stderr, "unknown arch %s\n", argv[2]); return 64; }
+  const std::string dt = argv[3];
+  d.dtype = dt == "f32" ? DMM_F32 : (dt == "f16" ? DMM_F16 : DMM_BF16);
+  d.batch = atoi(argv[4]); d.height = atoi(argv[5]); d.width = atoi(argv[6]);
+  const char* sh = getenv("DRIVE_MAP_SHIFT_MIB");
+  const size_t shift = sh ? (size_t)atoi(sh) << 20 : 0;   // (whole MiB: the alignment of every region stays what it was)
+  dmm_plan* plan = nullptr;
+  MUST(dmm_plan_create(&d, &plan));
+  const size_t wsb = dmm_plan_workspace_bytes(plan);
+  uint8_t* ws0 = (uint8_t*)reserve(wsb + shift, PROT_READ | PROT_WRITE);
+  fakehip_skip_large_memset(1);
+  const int64_t np = dmm_plan_num_params(plan), nb = std::max<int64_t>(dmm_plan_num_buffer_elems(plan), 1);
+  float* params0 = (float*)calloc(np + shift / 4, 4); float* grads0 = (float*)calloc(np + 2 * shift / 4, 4); float* buffers0 = (float*)calloc(nb + 3 * shift / 4, 4);
+  uint8_t* ws = ws0 + shift;
+  float *params = params0 + shift / 4, *grads = grads0 + 2 * shift / 4, *buffers = buffers0 + 3 * shift / 4;
+  MUST(dmm_plan_bind(plan, ws, wsb, params, grads, buffers));
+  Dumper D;
+  D.reg[0] = {ws, ws + wsb, "ws"};
+  D.reg[1] = {(uint8_t*)params, (uint8_t*)(params + np), "params"};
+  D.reg[2] = {(uint8_t*)grads, (uint8_t*)(grads + np), "grads"};
+  D.reg[3] = {(uint8_t*)buffers, (uint8_t*)(buffers + nb), "buffers"};
+  printf("plan zero_bytes=%zu zero_bwd_bytes=%zu main_bytes=%zu nparams=%lld nbuf=%lld fwd_flops=%.17g metrics_bytes=%zu bucket_bytes=%zu\n", plan->zero_bytes,
+         plan->zero_bwd_bytes, plan->main_bytes, (long long)plan->nparams, (long long)plan->nbuf, plan->fwd_flops, plan->metrics_bytes, plan->bucket_bytes);
+  D.ptr("metrics", plan->metrics);
+  printf(" logits_op_train=%d logits_op_eval=%d bce_op=%d\n", plan->logits_op_train, plan->logits_op_eval, plan->bce_op);
+  Dumper::ints("convert_ops_train", plan->convert_ops_train);
+  Dumper::ints("convert_ops_eval", plan->convert_ops_eval);
+  D.list("fwd_train", plan->fwd_train);
+  D.list("fwd_eval", plan->fwd_eval);
+  D.list("bwd", plan->bwd);
+  printf("bce_only\n");
+  D.op(plan->bce_only);
+  D.descs("packs", plan->packs);
+  Dumper::ints("pack_prefix", plan->pack_prefix);
+  D.descs("unpacks", plan->unpacks);
+  Dumper::ints("unpack_prefix", plan->unpack_prefix);
+  Dumper::tiles("pack_tiles", plan->pack_tiles);
+  Dumper::tiles("unpack_tiles", plan->unpack_tiles);
+  printf("table buckets entries=%zu\n", plan->buckets.size());
+  for (const GradBucket& b : plan->buckets) printf("  bucket off=%lld n=%lld ev_main=%d ev_side=%d ready=%d\n", (long long)b.off, (long long)b.n, b.ev_main, b.ev_side, b.ready);
+  MUST(dmm_plan_destroy(plan));
+  munmap(ws0, wsb + shift + 4096);
+  free(params0); free(grads0); free(buffers0);
+  if (D.outside) { fprintf(stderr, "[drive] FAIL: %ld pointers of the plan lie in none of its regions\n", D.outside); return 1; }
+  return 0;
+}
+
 // ---- single: one call of a single-kernel entry point; the large operands are addresses nothing may touch ----
 static int single_main(int argc, char** argv) {
   if (argc < 13) return 64;
@@ -377,6 +569,7 @@ static int refuse_main() {
 
 int main(int argc, char** argv) {
   if (argc > 1 && std::string(argv[1]) == "picks") return picks_main(argc, argv);
+  if (argc > 1 && std::string(argv[1]) == "dump") return dump_main(argc, argv);
   if (argc > 1 && std::string(argv[1]) == "single") return single_main(argc, argv);
   if (argc > 1 && std::string(argv[1]) == "refuse") return refuse_main();
   if (argc < 6) { fprintf(stderr, "usage: drive <arch> <dtype> <batch> <H> <W> [lives]\n"); return 64; }
