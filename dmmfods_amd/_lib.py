@@ -28,6 +28,17 @@ class ConvDesc(C.Structure):
         "dtype", "use_mfma", "B", "H", "W", "Cin", "Cout", "R", "S", "stride", "pad", "transposed", "mode", "bn_relu")]
 
 
+class GuardState(C.Structure):
+    """dmm_guard_state (include/dmmfods_hip.h): the 64-byte device block of the guarded optimiser step."""
+    _fields_ = [("scale", C.c_float), ("grad_scale", C.c_float), ("sumsq", C.c_double), ("grad_norm", C.c_float),
+                ("found_inf", C.c_int32), ("applied_steps", C.c_int64), ("skipped_steps", C.c_int64),
+                ("growth_tracker", C.c_int32), ("step_size", C.c_float), ("bc2_sqrt", C.c_float), ("clip_coef", C.c_float),
+                ("reserved", C.c_int32 * 2)]
+
+
+assert C.sizeof(GuardState) == 64
+
+
 class DmmError(RuntimeError):
     pass
 
@@ -94,6 +105,12 @@ def lib():
     L.dmm_plan_profile_op.argtypes = [vp, C.c_int, C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_double), C.POINTER(C.c_double)]
     L.dmm_plan_profile_collect.argtypes = [vp, C.c_int, C.POINTER(C.c_double), C.c_int, C.POINTER(C.c_int)]
     L.dmm_adam_step.argtypes = [vp, vp, vp, vp, i64, f32, f32, f32, f32, f32, i64, f32, vp]
+    L.dmm_grad_guard_scratch_bytes.argtypes = [i64]
+    L.dmm_grad_guard_scratch_bytes.restype = sz
+    L.dmm_guard_state_init.argtypes = [vp, f32, i64, i32, vp]
+    L.dmm_adam_step_guarded.argtypes = [vp, vp, vp, vp, i64, f32, f32, f32, f32, f32, f32, f32, f32, i32, vp, vp, vp]
+    L.dmm_grad_sumsq.argtypes = [vp, i64, i64, C.c_int, vp, vp]
+    L.dmm_plan_set_dynamic_loss_scale.argtypes = [vp, vp]
     L.dmm_conv_scratch_bytes.argtypes = [C.POINTER(ConvDesc)]
     L.dmm_conv_scratch_bytes.restype = sz
     L.dmm_conv_forward.argtypes = [C.POINTER(ConvDesc), vp, vp, vp, vp, vp, vp, vp, vp]
@@ -115,6 +132,7 @@ EXPORTS = [
     "dmm_plan_grad_bucket_wait", "dmm_plan_profile_begin", "dmm_plan_profile_filter", "dmm_plan_profile_num_ops", "dmm_plan_profile_op",
     "dmm_plan_profile_collect", "dmm_adam_step", "dmm_conv_scratch_bytes", "dmm_conv_forward", "dmm_conv_wgrad",
     "dmm_conv_dgrad", "dmm_conv_wgrad_ex", "dmm_conv_dgrad_ex", "dmm_conv1x1_backward_fused", "dmm_conv5_wgrad_stats", "dmm_last_impl", "dmm_impl_name", "dmm_impl_mask",
+    "dmm_grad_guard_scratch_bytes", "dmm_guard_state_init", "dmm_adam_step_guarded", "dmm_grad_sumsq", "dmm_plan_set_dynamic_loss_scale",
 ]
 
 

@@ -4,7 +4,8 @@
 
 Differences, all on purpose: the step body uses the fused HIP tail (``model.loss_backward``), so loss sums, IoU and accuracy
 come back as device tensors without the per-iteration host syncs of A:252-260 / H:359-363; TensorBoard is optional (not
-installed here); ``compute_dtype`` / data parallelism are new."""
+installed here); ``compute_dtype`` / data parallelism are new, and so is the guarded optimiser step (``max_grad_norm``, ``loss_scaler``:
+clipping by global norm, a dynamic loss scale and a skipped step on overflow, dmmfods_amd/optim.py)."""
 import logging
 import os
 import warnings
@@ -15,7 +16,7 @@ import torch
 
 from ..datasets.WaymoData import WaymoDataset_Loader
 from ..graphs.models.Dense_U_Net_lidar import densenet121_u_lidar
-from ..optim import FusedAdam
+from ..optim import DynamicLossScaler, FusedAdam
 from ..utils import Dense_U_Net_lidar_helper as utils
 
 try:  # pragma: no cover - tensorboard is not installed in the build image
@@ -51,7 +52,8 @@ class _StepLR:
 
 
 class Dense_U_Net_lidar_Agent:
-    def __init__(self, config=None, torchvision_init=True, compute_dtype=None, data_loader=None, loss=None):
+    def __init__(self, config=None, torchvision_init=True, compute_dtype=None, data_loader=None, loss=None, max_grad_norm=None,
+                 loss_scaler=None):
         self.logger = logging.getLogger("Agent")
         # the reference always builds DenseNet-121 (A:44); torchvision_init=True would download ImageNet weights (no network)
         self.model = densenet121_u_lidar(pretrained=False, config=config, compute_dtype=compute_dtype)
@@ -64,8 +66,22 @@ class Dense_U_Net_lidar_Agent:
         elif not isinstance(self.loss, torch.nn.BCEWithLogitsLoss):
             raise ValueError("loss must be BCEWithLogitsLoss(reduction='none') or a dmmfods_amd focal loss")
         o = self.config.optimizer
+        # New here: not fields of the reference's create_config, read only if a config carries them.  dynamic_loss_scale: True
+        # (GradScaler's defaults), an initial scale, or a dict of DynamicLossScaler arguments.
+        if max_grad_norm is None:
+            max_grad_norm = self._optional(o, "max_grad_norm")
+        if loss_scaler is None:
+            dyn = self._optional(o, "dynamic_loss_scale")
+            if isinstance(dyn, bool):
+                loss_scaler = DynamicLossScaler() if dyn else None
+            elif isinstance(dyn, (int, float)):
+                loss_scaler = DynamicLossScaler(init_scale=float(dyn))
+            elif dyn is not None:
+                loss_scaler = DynamicLossScaler(**dict(dyn))
+        self.loss_scaler = loss_scaler
         self.optimizer = FusedAdam(self.model, lr=o.learning_rate, betas=(o.beta1, o.beta2), eps=o.eps,
-                                   weight_decay=o.weight_decay, amsgrad=o.amsgrad)
+                                   weight_decay=o.weight_decay, amsgrad=o.amsgrad, max_grad_norm=max_grad_norm,
+                                   loss_scaler=loss_scaler)
         self.lr_scheduler = None
         if o.lr_scheduler.want:
             self.lr_scheduler = _StepLR(self.optimizer, o.lr_scheduler.every_n_epochs, o.lr_scheduler.gamma)
@@ -84,6 +100,13 @@ class Dense_U_Net_lidar_Agent:
         Path(self.config.dir.current_run.summary).mkdir(exist_ok=True, parents=True)
         mk = (lambda: SummaryWriter(log_dir=self.config.dir.current_run.summary, comment="Dense_U_Net")) if SummaryWriter else _NullWriter
         self.train_summary_writer, self.val_summary_writer = mk(), mk()
+
+    @staticmethod
+    def _optional(section, name):
+        try:
+            return getattr(section, name)
+        except (AttributeError, KeyError):
+            return None
 
     # ------------------------------------------------------------------ checkpoints (A:96-163)
     def save_checkpoint(self, filename="checkpoint.pth.tar", is_best=False):
@@ -167,6 +190,8 @@ class Dense_U_Net_lidar_Agent:
         n = self.data_loader.train_iterations
         nc = self.config.model.num_classes
         ep = {k: torch.zeros((n, nc), device=self.device) for k in ("loss", "iou", "nans", "acc")}
+        guard = self.optimizer._guard   # the guarded step's state (None on the plain path); read ONCE per epoch, below
+        skipped0 = guard.skipped_steps if guard is not None else 0
         for b, (image, lidar, ht_map) in enumerate(self.data_loader.train_loader):
             image, lidar, ht_map = self._to_device(image, lidar, ht_map)
             with torch.no_grad():
@@ -181,6 +206,11 @@ class Dense_U_Net_lidar_Agent:
             self.lr_scheduler.step()
         self.train_history.append({"epoch": self.current_epoch, "loss": ep["loss"].mean(0).cpu(), "iou": ep["iou"].mean(0).cpu(),
                                    "nans": ep["nans"].sum(0).cpu(), "acc": ep["acc"].mean(0).cpu()})
+        if guard is not None:   # one synchronisation per epoch, none per step
+            gs = guard.state_dict()
+            self.train_history[-1].update(loss_scale=gs["scale"], skipped_steps=gs["skipped_steps"] - skipped0)
+            self.logger.info("Training at Epoch-%d | Loss scale: %g | Skipped steps: %d (of %d)", self.current_epoch, gs["scale"],
+                             gs["skipped_steps"] - skipped0, n)
         self.logger.info("Training at Epoch-%d | Average Loss: %s | Average IoU: %s | Number of NaNs: %s | Average Accuracy: %s",
                          self.current_epoch, ep["loss"].mean(0).tolist(), ep["iou"].mean(0).tolist(), ep["nans"].sum(0).tolist(),
                          ep["acc"].mean(0).tolist())

@@ -109,7 +109,7 @@ void trace_destroy(const char* what) {
 extern "C" {
 
 const char* dmm_last_error(void) { return g_err.c_str(); }
-int dmm_version(void) { return 100; }
+int dmm_version(void) { return 101; }
 
 int dmm_set_option(const char* name, int value) {
   if (!name) return fail(DMM_ERR_INVALID, "null argument");
@@ -558,6 +558,7 @@ int dmm_plan_loss_backward(dmm_plan* plan, const float* logits, const float* tar
   b.bce.logits = logits;
   b.bce.target = target;
   set_loss_fields(plan, b.bce);
+  b.bce.dyn_scale = plan->dyn_scale;
   // the loss kernel (caller pointers, loss parameters) stays eager; everything behind it is the replayed segment
   int rc = launch_list(plan, 1, plan->bwd, (size_t)plan->bce_op + 1, plan->bwd.size(), (hipStream_t)stream);
   if (rc) return rc;
@@ -574,6 +575,7 @@ int dmm_plan_backward(dmm_plan* plan, const float* dlogits, void* stream) {
   memset(&cv, 0, sizeof(cv));
   cv.src1 = dlogits; cv.C1 = b.NC; cv.dst = b.dlogits; cv.B = b.B; cv.H = b.H; cv.W = b.W;
   cv.scale = plan->desc.loss_scale;
+  cv.dyn_scale = plan->dyn_scale;
   // everything the fused path runs in front of the loss kernel (backward accumulators AND the gradient arena: unpack adds
   // into it for merged-tap / shared-master weights), then the external d(loss)/d(logit) instead of the loss kernel
   int rc = run_ops(plan, plan->bwd, st, -1, 0, (size_t)plan->bce_op);
@@ -683,6 +685,68 @@ int dmm_adam_step(float* params, const float* grads, float* exp_avg, float* exp_
   a.bc2_sqrt = (float)std::sqrt(bc2);
   a.grad_scale = grad_scale;
   HIPCHK(launch_adam(a, (hipStream_t)stream));
+  return DMM_OK;
+}
+
+int dmm_plan_set_dynamic_loss_scale(dmm_plan* plan, const float* scale_dev) {
+  if (!plan) return fail(DMM_ERR_INVALID, "null plan");
+  if (((uintptr_t)scale_dev & 3) != 0) return fail(DMM_ERR_INVALID, "dynamic loss scale pointer must be 4-byte aligned");
+  plan->dyn_scale = scale_dev;
+  // the loss record of a bound plan shows it at once (dmm_plan_loss_backward sets it again at every call: bind rebuilds the list).
+  // bce_only (validation: no gradient) never takes it.
+  if (plan->bound && plan->bce_op >= 0) plan->bwd[plan->bce_op].bce.dyn_scale = scale_dev;
+  return DMM_OK;
+}
+
+size_t dmm_grad_guard_scratch_bytes(int64_t n) {
+  (void)n;  // one partial per workgroup of a fixed grid, whatever the arena's size
+  return (size_t)GUARD_PARTIALS * sizeof(double);
+}
+
+int dmm_guard_state_init(dmm_guard_state* dev, float init_scale, int64_t applied_steps, int32_t growth_tracker, void* stream) {
+  if (!dev) return fail(DMM_ERR_INVALID, "null guard state");
+  if (((uintptr_t)dev & 7) != 0) return fail(DMM_ERR_INVALID, "guard state must be 8-byte aligned");
+  if (!(init_scale > 0.f) || !std::isfinite(init_scale)) return fail(DMM_ERR_INVALID, "init_scale must be a finite number > 0");
+  if (applied_steps < 0 || growth_tracker < 0) return fail(DMM_ERR_INVALID, "applied_steps and growth_tracker must be >= 0");
+  HIPCHK(launch_guard_init(dev, init_scale, applied_steps, growth_tracker, (hipStream_t)stream));
+  return DMM_OK;
+}
+
+int dmm_grad_sumsq(const float* grads, int64_t offset, int64_t count, int accumulate, void* scratch, void* stream) {
+  if (!grads || !scratch) return fail(DMM_ERR_INVALID, "null argument");
+  if (offset < 0 || count < 0) return fail(DMM_ERR_INVALID, "offset and count must be >= 0");
+  if ((((uintptr_t)grads) & 3) != 0 || (((uintptr_t)scratch) & 7) != 0) return fail(DMM_ERR_INVALID, "misaligned gradient or scratch pointer");
+  GradSumsqArgs r;
+  r.g = grads + offset; r.n = (size_t)count; r.partials = (double*)scratch; r.accumulate = accumulate ? 1 : 0;
+  HIPCHK(launch_grad_sumsq(r, (hipStream_t)stream));
+  return DMM_OK;
+}
+
+int dmm_adam_step_guarded(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, int64_t n, float lr, float beta1,
+                          float beta2, float eps, float weight_decay, float max_norm, float growth_factor, float backoff_factor,
+                          int32_t growth_interval, dmm_guard_state* state, void* scratch, void* stream) {
+  if (!params || !grads || !exp_avg || !exp_avg_sq || !state || !scratch) return fail(DMM_ERR_INVALID, "null argument of the guarded Adam step");
+  if (n < 0) return fail(DMM_ERR_INVALID, "n must be >= 0");
+  if ((((uintptr_t)grads) & 3) != 0 || (((uintptr_t)state) & 7) != 0 || (((uintptr_t)scratch) & 7) != 0)
+    return fail(DMM_ERR_INVALID, "misaligned gradient, state or scratch pointer");
+  if (!(growth_factor >= 1.f) || !std::isfinite(growth_factor)) return fail(DMM_ERR_INVALID, "growth_factor must be a finite number >= 1");
+  if (!(backoff_factor > 0.f) || !(backoff_factor <= 1.f)) return fail(DMM_ERR_INVALID, "backoff_factor must lie in (0, 1]");
+  if (growth_interval < 0) return fail(DMM_ERR_INVALID, "growth_interval must be >= 0");
+  if (std::isnan(max_norm)) return fail(DMM_ERR_INVALID, "max_norm is NaN");
+  if (!(beta1 >= 0.f && beta1 < 1.f) || !(beta2 >= 0.f && beta2 < 1.f)) return fail(DMM_ERR_INVALID, "betas must lie in [0, 1)");
+  hipStream_t st = (hipStream_t)stream;
+  GradSumsqArgs r;
+  r.g = grads; r.n = (size_t)n; r.partials = (double*)scratch; r.accumulate = 0;
+  HIPCHK(launch_grad_sumsq(r, st));
+  GuardFinalizeArgs f;
+  f.partials = (const double*)scratch; f.state = state; f.lr = lr; f.beta1 = beta1; f.beta2 = beta2; f.max_norm = max_norm;
+  f.growth_factor = growth_factor; f.backoff_factor = backoff_factor; f.growth_interval = growth_interval;
+  HIPCHK(launch_guard_finalize(f, st));
+  AdamArgs a;
+  a.p = params; a.g = grads; a.m = exp_avg; a.v = exp_avg_sq; a.n = (size_t)n;
+  a.beta1 = beta1; a.beta2 = beta2; a.eps = eps; a.weight_decay = weight_decay;
+  a.step_size = 0.f; a.bc2_sqrt = 1.f; a.grad_scale = 0.f;   // read from *state by the kernel
+  HIPCHK(launch_adam_guarded(a, state, st));
   return DMM_OK;
 }
 

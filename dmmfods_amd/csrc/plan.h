@@ -135,6 +135,7 @@ struct dmm_plan {
   dmm::Op bce_only;     // loss + metrics without gradient
   int loss_kind = 0;          // 0 BCE, 1 focal (dmm_plan_set_loss)
   float loss_alpha[8] = {1, 1, 1, 1, 1, 1, 1, 1}, loss_gamma[8] = {2, 2, 2, 2, 2, 2, 2, 2};
+  const float* dyn_scale = nullptr;  // device; the dynamic loss scale the loss kernel multiplies by (dmm_plan_set_dynamic_loss_scale), null = none
   double* metrics = nullptr;  // device, inside the zero region
   size_t metrics_bytes = 0;
   std::vector<dmm::PackDesc> packs;

@@ -1,5 +1,6 @@
 // Argument blocks and launchers of the helper kernels (see pointwise.hip) and of the two GEMM kernels.
 #pragma once
+#include "../../include/dmmfods_hip.h"   // dmm_guard_state
 #include "common.h"
 
 namespace dmm {
@@ -13,6 +14,7 @@ struct ConvertArgs {
   double* stat_sum;   // 8 doubles each (nullable)
   double* stat_sq;
   float scale;        // multiplies every value (1 for inputs; loss_scale for an external d(loss)/d(logit))
+  const float* dyn_scale;  // device; multiplies on top of `scale` (the dynamic loss scale, dmm_plan_set_dynamic_loss_scale); null = none
 };
 
 struct BnFinalizeArgs {
@@ -103,6 +105,8 @@ struct BceArgs {
   float* loss_out;  // fp32 NCHW unreduced loss (nullable)
   float* dx_out;    // fp32 NCHW d(sum loss)/d(input), unscaled (nullable)
   int metrics;      // 0: skip the loss sums / metric counts (out may be null)
+  const float* dyn_scale;  // device; dlogits = (sigmoid(x) - t) * loss_scale * (*dyn_scale) (the dynamic loss scale); null = none.
+                           // loss_out, dx_out, the loss sums and the metric counts never see it
 };
 
 struct ApplyCorrArgs {
@@ -123,6 +127,23 @@ struct AdamArgs {
   float* v;
   size_t n;
   float beta1, beta2, eps, weight_decay, step_size, bc2_sqrt, grad_scale;
+};
+
+// ---- guarded optimiser step (guard.hip) ----
+constexpr int GUARD_PARTIALS = 512;  // workgroups of the arena reduction = fp64 partial sums in its scratch: two per compute unit
+struct GradSumsqArgs {
+  const float* g;     // a range of the gradient arena (any 4-byte alignment)
+  size_t n;
+  double* partials;   // GUARD_PARTIALS doubles; workgroup w owns partials[w]
+  int accumulate;     // 0: partials[w] = sum of this range's share; 1: += (a later range of the same step, e.g. the next gradient bucket)
+};
+struct GuardFinalizeArgs {
+  const double* partials;
+  dmm_guard_state* state;
+  float lr, beta1, beta2;
+  float max_norm;                       // <= 0: no clipping
+  float growth_factor, backoff_factor;
+  int growth_interval;                  // 0: the scale never grows
 };
 
 struct PackSeg {
@@ -193,6 +214,10 @@ hipError_t launch_maxpool_fwd(const MaxpoolArgs& a, int dtype, hipStream_t st);
 hipError_t launch_maxpool_bwd(const MaxpoolBwdArgs& a, int dtype, hipStream_t st);
 hipError_t launch_bce_metrics(const BceArgs& a, int dtype, hipStream_t st);
 hipError_t launch_adam(const AdamArgs& a, hipStream_t st);
+hipError_t launch_grad_sumsq(const GradSumsqArgs& a, hipStream_t st);
+hipError_t launch_guard_finalize(const GuardFinalizeArgs& a, hipStream_t st);
+hipError_t launch_adam_guarded(const AdamArgs& a, const dmm_guard_state* state, hipStream_t st);  // a.grad_scale / step_size / bc2_sqrt: from *state
+hipError_t launch_guard_init(dmm_guard_state* dev, float scale, int64_t applied, int32_t tracker, hipStream_t st);
 hipError_t launch_apply_corr(const ApplyCorrArgs& a, int dtype, hipStream_t st);
 hipError_t launch_pack(const PackDesc* descs_dev, const int* prefix_dev, int ndesc, int total_rows, int dtype, hipStream_t st,
                        const PackDesc* tile_descs = nullptr, const PackTile* tiles_dev = nullptr, int nt1 = 0, int nt9 = 0);

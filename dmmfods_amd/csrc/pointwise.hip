@@ -30,6 +30,7 @@ __global__ __launch_bounds__(256) void convert_input_kernel(ConvertArgs a) {
   double s1[8], s2[8];  // fp64 from the first add (see igemm.hip)
 #pragma unroll
   for (int c = 0; c < 8; ++c) { s1[c] = 0.0; s2[c] = 0.0; }
+  const float scale = a.dyn_scale != nullptr ? a.scale * *a.dyn_scale : a.scale;
   for (size_t p = (size_t)blockIdx.x * blockDim.x + threadIdx.x; p < npix; p += (size_t)gridDim.x * blockDim.x) {
     const size_t b = p / plane, rem = p - b * plane;
     float v[8];
@@ -38,7 +39,7 @@ __global__ __launch_bounds__(256) void convert_input_kernel(ConvertArgs a) {
       float x = 0.f;
       if (c < a.C1) x = a.src1[(b * a.C1 + c) * plane + rem];
       else if (c < a.C1 + a.C2) x = a.src2[(b * a.C2 + (c - a.C1)) * plane + rem];
-      v[c] = x * a.scale;
+      v[c] = x * scale;
     }
     T* d = (T*)a.dst + p * 8;
 #pragma unroll
@@ -371,6 +372,7 @@ __global__ __launch_bounds__(256) void bce_metrics_kernel(BceArgs a) {
   // serves planes that are not.
   const bool vec4 = (plane & 3) == 0 && ((((uintptr_t)a.logits) | ((uintptr_t)a.target)) & 15) == 0 && a.loss_out == nullptr && a.dx_out == nullptr;
   const size_t nthreads = (size_t)gridDim.x * blockDim.x, gid = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const float gscale = a.dyn_scale != nullptr ? a.loss_scale * *a.dyn_scale : a.loss_scale;
   if (vec4) {
     for (size_t p = gid * 4; p < plane; p += nthreads * 4) {
       f32x4 xv[8], tv[8];
@@ -393,7 +395,7 @@ __global__ __launch_bounds__(256) void bce_metrics_kernel(BceArgs a) {
             float l, d;
             loss_elem(a, n, x, t, l, d);
             ls[n] += l;
-            g[j][n] = d * a.loss_scale;
+            g[j][n] = d * gscale;
             const bool pp = x >= a.thr, gg = t >= a.thr;
             eq[n] += (pp == gg) ? 1.f : 0.f;
             in_[n] += (pp && gg) ? 1.f : 0.f;
@@ -421,7 +423,7 @@ __global__ __launch_bounds__(256) void bce_metrics_kernel(BceArgs a) {
         float l, d;
         loss_elem(a, n, x, t, l, d);
         ls[n] += l;
-        g[n] = d * a.loss_scale;
+        g[n] = d * gscale;
         if (a.loss_out != nullptr) a.loss_out[idx] = l;
         if (a.dx_out != nullptr) a.dx_out[idx] = d;
         const bool pp = x >= a.thr, gg = t >= a.thr;

@@ -93,6 +93,7 @@ class _Plan:
             self.close()
             raise
         self.loss_key = None
+        self.scaler_ptr = None   # the dynamic loss scale this plan's loss kernel reads (None: none)
         # gradient buckets in the order backward finishes them: (offset, count) in elements of the gradient arena
         self.grad_buckets = []
         for i in range(L.dmm_plan_num_grad_buckets(self.handle)):
@@ -248,6 +249,31 @@ class Dense_U_Net_lidar(nn.Module):
         self._plans = OrderedDict()
         self._last = None
         self._loss = (_lib.LOSS_BCE, None, None)
+        self._loss_scaler = None
+
+    # ------------------------------------------------------------------ dynamic loss scale
+    def set_loss_scaler(self, scaler):
+        """Attach a dmmfods_amd.optim.DynamicLossScaler (None: detach).  From then on the loss kernel of loss_backward() and the
+        external-gradient path (logits.backward(gradient=...)) multiply d(loss)/d(logit) by the scaler's current scale, read from
+        device memory when the kernel runs, on top of the static ``loss_scale``; the gradient arena then holds scale x the
+        gradients, which FusedAdam(..., loss_scaler=scaler) divides out (it calls this method itself).  Every plan the model holds
+        or creates later is pointed at the scale.  Losses and metrics are never scaled."""
+        if scaler is not None and not hasattr(scaler, "_scale_ptr"):
+            raise ValueError("set_loss_scaler() takes a DynamicLossScaler or None")
+        self._loss_scaler = scaler
+        plans = list(self._plans.values())
+        if self._last is not None and self._last[0] not in plans:
+            plans.append(self._last[0])
+        for plan in plans:
+            if not plan.closed:
+                self._apply_scaler(plan)
+        return self
+
+    def _apply_scaler(self, plan):
+        ptr = None if self._loss_scaler is None else self._loss_scaler._scale_ptr(self._param_arena.device)
+        if ptr != plan.scaler_ptr:
+            _lib.check(_lib.lib().dmm_plan_set_dynamic_loss_scale(plan.handle, ptr))
+            plan.scaler_ptr = ptr
 
     # ------------------------------------------------------------------ loss epilogue
     def set_loss(self, kind="bce", alpha=None, gamma=None):
@@ -364,6 +390,8 @@ class Dense_U_Net_lidar(nn.Module):
                 old.close()
             plan = _Plan(self, batch, height, width)
             self._plans[key] = plan
+            if self._loss_scaler is not None:
+                self._apply_scaler(plan)
         else:
             self._plans.move_to_end(key)
         return plan

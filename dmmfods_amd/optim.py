@@ -1,25 +1,218 @@
 """Flat fused Adam over the model's parameter arena (reference: torch.optim.Adam built at
 agents/Dense_U_Net_lidar_Agent.py:57-61 and stepped at :265).  One kernel launch updates every parameter;
-state_dict()/load_state_dict() use torch.optim.Adam's layout so reference checkpoints round-trip."""
+state_dict()/load_state_dict() use torch.optim.Adam's layout so reference checkpoints round-trip.
+
+New here (the reference trains in fp32 with a bare Adam): the GUARDED step - a dynamic loss scale (torch.amp.GradScaler's rule),
+a skipped step when the gradient arena holds an inf or a NaN, and clipping by the global gradient norm
+(torch.nn.utils.clip_grad_norm_'s formula).  ``FusedAdam(model, max_grad_norm=..., loss_scaler=DynamicLossScaler())`` turns it
+on; everything is decided on the device (include/dmmfods_hip.h, dmm_adam_step_guarded), so step() never waits for the GPU."""
+import ctypes as C
+import math
+
 import torch
 
 from . import _lib
 
+_STATE_KEY = "loss_scaler"   # the one extra top-level key of FusedAdam.state_dict() on the guarded path
+
+
+class DynamicLossScaler:
+    """Dynamic loss scale S with torch.amp.GradScaler's rule and defaults.  The loss kernel multiplies d(loss)/d(logit) by S
+    (on top of the model's static ``loss_scale``), so the gradient arena holds S x the gradients; the optimiser divides it out.
+    A step whose arena holds an inf / NaN is skipped: parameters, moments and the optimiser's step count stay, S *= backoff_factor.
+    After ``growth_interval`` applied steps in a row S *= growth_factor; ``growth_interval=0``: S never grows (it still backs off).
+    S may fall below 1.  As with torch.amp, the forward of a skipped step has already updated the BatchNorm running statistics and
+    ``num_batches_tracked``.
+
+    The state (dmm_guard_state: scale, counters, the last step's norm and flag) lives in one 64-byte device block that is created
+    on the model's device when first needed; reading ``get_scale()``, ``skipped_steps`` or ``state_dict()`` waits for the GPU, the
+    device tensors ``loss_scale`` / ``last_grad_norm`` / ``last_found_inf`` do not."""
+
+    def __init__(self, init_scale=65536.0, growth_factor=2.0, backoff_factor=0.5, growth_interval=2000):
+        if not (math.isfinite(init_scale) and init_scale > 0):
+            raise ValueError("init_scale must be a finite number > 0")
+        if not (math.isfinite(growth_factor) and growth_factor > 1):
+            raise ValueError("growth_factor must be > 1")
+        if not 0 < backoff_factor < 1:
+            raise ValueError("backoff_factor must lie in (0, 1)")
+        if int(growth_interval) != growth_interval or growth_interval < 0:
+            raise ValueError("growth_interval must be an integer >= 0 (0: the scale never grows)")
+        self.growth_factor, self.backoff_factor, self.growth_interval = float(growth_factor), float(backoff_factor), int(growth_interval)
+        self._fixed = False
+        self._reset(float(init_scale))
+
+    @classmethod
+    def _fixed_unit(cls):
+        """S = 1 for ever: the state block of a FusedAdam that clips (or only guards) without a loss scale."""
+        s = cls.__new__(cls)
+        s.growth_factor, s.backoff_factor, s.growth_interval = 1.0, 1.0, 0
+        s._fixed = True
+        s._reset(1.0)
+        return s
+
+    def _reset(self, scale):
+        self._host = {"scale": scale, "growth_tracker": 0, "skipped_steps": 0, "applied_steps": 0}   # valid while _state is None
+        self._state = None        # int32[16] = dmm_guard_state
+        self._skipped_base = 0    # skipped steps before the device block was (re)initialised
+        self._scratch = None
+
+    # ---- the device block ----
+    def _views(self):
+        s = self._state
+        return s.view(torch.float32), s.view(torch.int64), s.view(torch.float64)
+
+    def _push(self):
+        """(Re)initialise the device block from the host values."""
+        h, dev = self._host, self._state.device
+        _lib.check(_lib.lib().dmm_guard_state_init(self._state.data_ptr(), float(h["scale"]), int(h["applied_steps"]),
+                                                   int(h["growth_tracker"]), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+        self._skipped_base = int(h["skipped_steps"])
+
+    def _pull(self):
+        """Host copy of the counters (waits for the GPU)."""
+        if self._state is not None:
+            raw = self._state.cpu()
+            f, i64 = raw.view(torch.float32), raw.view(torch.int64)
+            self._host = {"scale": float(f[0]), "growth_tracker": int(raw[10]), "skipped_steps": self._skipped_base + int(i64[4]),
+                          "applied_steps": int(i64[3])}
+        return self._host
+
+    def _materialize(self, device):
+        device = torch.device(device)
+        if device.type != "cuda":
+            raise RuntimeError("the loss scaler's state lives on the GPU (no CPU fallback)")
+        if device.index is None:
+            device = torch.device("cuda", torch.cuda.current_device())
+        if self._state is not None and self._state.device == device:
+            return self._state
+        self._pull()
+        self._state = torch.zeros(16, dtype=torch.int32, device=device)
+        self._scratch = None
+        self._push()
+        return self._state
+
+    def _scale_ptr(self, device):
+        return self._materialize(device).data_ptr()   # `scale` is the block's first field
+
+    def _scratch_for(self, n):
+        nbytes = _lib.lib().dmm_grad_guard_scratch_bytes(int(n))
+        if self._scratch is None or self._scratch.device != self._state.device or self._scratch.numel() * 8 < nbytes:
+            self._scratch = torch.zeros((nbytes + 7) // 8, dtype=torch.float64, device=self._state.device)
+        return self._scratch
+
+    def _set_applied(self, n):
+        self._host["applied_steps"] = int(n)
+        if self._state is not None:
+            self._views()[1][3:4].fill_(int(n))
+
+    def _applied(self):
+        return int(self._views()[1][3]) if self._state is not None else int(self._host["applied_steps"])
+
+    # ---- public surface ----
+    @property
+    def loss_scale(self):
+        """Device tensor (1 element): the scale of the next backward.  None until the state exists on a device."""
+        return None if self._state is None else self._views()[0][0:1]
+
+    @property
+    def last_grad_norm(self):
+        """Device tensor: global gradient norm of the last step, unscaled, before clipping (inf / NaN when it was skipped)."""
+        return None if self._state is None else self._views()[0][4:5]
+
+    @property
+    def last_found_inf(self):
+        """Device tensor (int32): 1 when the last step was skipped."""
+        return None if self._state is None else self._state[5:6]
+
+    @property
+    def last_clip_coef(self):
+        return None if self._state is None else self._views()[0][13:14]
+
+    def get_scale(self):
+        return float(self._pull()["scale"])
+
+    def set_scale(self, scale):
+        """Rewrite the scale (on the device, without waiting for it); the counters stay."""
+        if not (math.isfinite(scale) and scale > 0):
+            raise ValueError("scale must be a finite number > 0")
+        self._host["scale"] = float(scale)
+        if self._state is not None:
+            self._views()[0][0:1].fill_(float(scale))
+
+    @property
+    def skipped_steps(self):
+        return int(self._pull()["skipped_steps"])
+
+    @property
+    def growth_tracker(self):
+        return int(self._pull()["growth_tracker"])
+
+    def state_dict(self):
+        h = self._pull()
+        return {"scale": float(h["scale"]), "growth_tracker": int(h["growth_tracker"]), "skipped_steps": int(h["skipped_steps"])}
+
+    def load_state_dict(self, sd):
+        applied = self._applied()
+        scale, tracker = (1.0, 0) if self._fixed else (float(sd["scale"]), int(sd.get("growth_tracker", 0)))
+        if not (math.isfinite(scale) and scale > 0) or tracker < 0:
+            raise ValueError("bad loss scaler state")
+        self._host = {"scale": scale, "growth_tracker": tracker, "skipped_steps": int(sd.get("skipped_steps", 0)), "applied_steps": applied}
+        if self._state is not None:
+            self._push()
+
 
 class FusedAdam:
-    def __init__(self, model, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, amsgrad=False):
+    def __init__(self, model, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, amsgrad=False, max_grad_norm=None,
+                 loss_scaler=None):
         if amsgrad:
             raise ValueError("amsgrad=True is not supported (reference default False, H:156)")
+        if max_grad_norm is not None and not (float(max_grad_norm) > 0 and math.isfinite(float(max_grad_norm))):
+            raise ValueError("max_grad_norm must be a finite number > 0 (None: no clipping)")
+        if loss_scaler is not None and not isinstance(loss_scaler, DynamicLossScaler):
+            raise ValueError("loss_scaler must be a DynamicLossScaler")
         self.model = model
         self.defaults = dict(lr=lr, betas=tuple(betas), eps=eps, weight_decay=weight_decay, amsgrad=False)
         self.param_groups = [dict(self.defaults, params=list(range(sum(1 for _ in model.parameters()))))]
-        self.step_count = 0
+        self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
+        self.loss_scaler = loss_scaler
+        # the guarded path's state block: the scaler's, or a private S = 1 one for clipping alone; None = the plain step
+        self._guard = loss_scaler if loss_scaler is not None else (DynamicLossScaler._fixed_unit() if max_grad_norm is not None else None)
+        self._step_count = 0
+        if loss_scaler is not None:
+            model.set_loss_scaler(loss_scaler)
         self._alloc()
 
     def _alloc(self):
         p = self.model.param_arena
         self.exp_avg = torch.zeros_like(p)
         self.exp_avg_sq = torch.zeros_like(p)
+
+    @property
+    def step_count(self):
+        """Optimiser steps APPLIED so far.  On the guarded path the count lives on the device (a skipped step does not count) and
+        reading it waits for the GPU; step() itself never does."""
+        if self._guard is not None:
+            return self._guard._applied()
+        return self._step_count
+
+    @step_count.setter
+    def step_count(self, n):
+        self._step_count = int(n)
+        if self._guard is not None:
+            self._guard._set_applied(int(n))
+
+    # device tensors for logging without a synchronisation (None on the plain path / before the first guarded step)
+    @property
+    def last_grad_norm(self):
+        return None if self._guard is None else self._guard.last_grad_norm
+
+    @property
+    def last_found_inf(self):
+        return None if self._guard is None else self._guard.last_found_inf
+
+    @property
+    def loss_scale(self):
+        return None if self._guard is None else self._guard.loss_scale
 
     def zero_grad(self, set_to_none=False):
         """The HIP backward overwrites the gradient arena, so there is nothing to clear (kept for API parity)."""
@@ -31,25 +224,46 @@ class FusedAdam:
             self.exp_avg = self.exp_avg.to(m.param_arena.device)
             self.exp_avg_sq = self.exp_avg_sq.to(m.param_arena.device)
         g = self.param_groups[0]
+        if self._guard is not None:
+            return self._step_guarded(g, grad_scale)
         self.step_count += 1
         _lib.check(_lib.lib().dmm_adam_step(
             m.param_arena.data_ptr(), m.grad_arena.data_ptr(), self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(),
             m.param_arena.numel(), float(g["lr"]), float(g["betas"][0]), float(g["betas"][1]), float(g["eps"]),
             float(g["weight_decay"]), self.step_count, float(grad_scale), _lib.stream_ptr()))
 
+    def _step_guarded(self, g, grad_scale):
+        """Arena reduction -> decision -> Adam, three launches, no host synchronisation.  In a data-parallel job call it after
+        GradAllReduce.wait(works): every rank then reads the same summed arena and takes the same decision."""
+        if grad_scale != 1.0:
+            raise ValueError("grad_scale is not available on the guarded path (the loss scaler divides its scale out itself)")
+        m, gd = self.model, self._guard
+        n = m.param_arena.numel()
+        state = gd._materialize(m.param_arena.device)
+        scratch = gd._scratch_for(n)
+        _lib.check(_lib.lib().dmm_adam_step_guarded(
+            m.param_arena.data_ptr(), m.grad_arena.data_ptr(), self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(), n,
+            float(g["lr"]), float(g["betas"][0]), float(g["betas"][1]), float(g["eps"]), float(g["weight_decay"]),
+            float(self.max_grad_norm or 0.0), gd.growth_factor, gd.backoff_factor, gd.growth_interval,
+            state.data_ptr(), scratch.data_ptr(), _lib.stream_ptr()))
+
     # ---- torch.optim.Adam-compatible checkpoint format ----
     def state_dict(self):
         state, off = {}, 0
+        step_count = self.step_count
         for i, p in enumerate(self.model.parameters()):
             n = p.numel()
-            if self.step_count > 0:
-                state[i] = {"step": torch.tensor(float(self.step_count)),
+            if step_count > 0:
+                state[i] = {"step": torch.tensor(float(step_count)),
                             "exp_avg": self.exp_avg[off:off + n].view(p.shape).clone(),
                             "exp_avg_sq": self.exp_avg_sq[off:off + n].view(p.shape).clone()}
             off += n
         g = dict(self.param_groups[0])
         g.update(maximize=False, foreach=None, capturable=False, differentiable=False, fused=None)
-        return {"state": state, "param_groups": [g]}
+        sd = {"state": state, "param_groups": [g]}
+        if self._guard is not None:   # torch.optim.Adam.load_state_dict ignores a key it does not know
+            sd[_STATE_KEY] = self._guard.state_dict()
+        return sd
 
     def load_state_dict(self, sd):
         off = 0
@@ -65,3 +279,5 @@ class FusedAdam:
         for k in ("lr", "betas", "eps", "weight_decay"):
             if k in sd["param_groups"][0]:
                 self.param_groups[0][k] = sd["param_groups"][0][k]
+        if self._guard is not None and sd.get(_STATE_KEY) is not None:   # (a checkpoint of the plain path has none: the scaler keeps its state)
+            self._guard.load_state_dict(sd[_STATE_KEY])

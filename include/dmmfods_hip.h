@@ -13,6 +13,8 @@
  *                                          agents/Dense_U_Net_lidar_Agent.py:247-264, utils/...helper.py:311-401
  *   dmm_plan_set_loss / dmm_loss_forward . FocalLoss / ClassWiseFocalLoss  graphs/losses/FocalLoss.py:9-91
  *   dmm_adam_step ........................ torch.optim.Adam.step        agents/Dense_U_Net_lidar_Agent.py:57-61,265
+ *   dmm_adam_step_guarded / dmm_guard_* .. nothing upstream (the reference trains in fp32 with a bare Adam, :263-265); the rule is
+ *                                          torch.amp.GradScaler's and the clip formula torch.nn.utils.clip_grad_norm_'s
  *   dmm_conv_forward / dmm_conv_wgrad .... single-kernel entry points for unit tests (torch.nn.functional.conv2d,
  *                                          conv_transpose2d as dispatched by the modules built at :72-131)
  *
@@ -172,6 +174,56 @@ long long dmm_plan_num_graph_replays(const dmm_plan* plan, int which);
 /* Flat fused Adam over n fp32 elements (amsgrad unsupported).  step is 1-based. */
 int dmm_adam_step(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, int64_t n, float lr, float beta1,
                   float beta2, float eps, float weight_decay, int64_t step, float grad_scale, void* stream);
+
+/* ---- guarded optimiser step: dynamic loss scale, skipped step on overflow, clipping by global norm ----
+ * Everything is decided on the device; no call below synchronises with the host.  The state lives in one 64-byte device block owned
+ * by the caller.  S = `scale` is the dynamic loss scale in force during the backward that filled the gradient arena, which therefore
+ * holds S x the true gradients (the plan's static dmm_model_desc.loss_scale is applied and removed inside the plan as before; S
+ * multiplies on top, see dmm_plan_set_dynamic_loss_scale).  Per step:
+ *   sumsq = sum g^2 over the arena as stored (squares and sum in fp64);  found_inf = sumsq is inf or NaN
+ *   found_inf:  params, exp_avg, exp_avg_sq, applied_steps unchanged;  scale = S * backoff_factor, growth_tracker = 0, skipped_steps += 1
+ *   otherwise:  grad_norm = sqrt(sumsq) / S;  clip_coef = min(1, max_norm / (grad_norm + 1e-6)) (1 without max_norm);
+ *               Adam on g * clip_coef / S with the bias corrections of step applied_steps + 1;  applied_steps += 1;
+ *               growth_tracker += 1, and when it reaches growth_interval: scale = S * growth_factor, growth_tracker = 0.
+ * A skipped step's forward has already updated the BatchNorm running statistics (as with torch.amp). */
+typedef struct dmm_guard_state {
+  float scale;            /*  0: dynamic loss scale S of the NEXT backward (what the plan's loss kernel reads); may fall below 1 */
+  float grad_scale;       /*  4: clip_coef / S of the last step: what its Adam multiplied every gradient by (0 on a skipped step) */
+  double sumsq;           /*  8: sum of squares of the arena as stored (scaled by S), fp64; inf / NaN on a skipped step */
+  float grad_norm;        /* 16: sqrt(sumsq) / S, the global gradient norm before clipping (inf / NaN on a skipped step) */
+  int32_t found_inf;      /* 20: 1 = the last step was skipped */
+  int64_t applied_steps;  /* 24: optimiser steps applied so far (Adam's t) */
+  int64_t skipped_steps;  /* 32: steps skipped since dmm_guard_state_init */
+  int32_t growth_tracker; /* 40: applied steps since the scale last changed */
+  float step_size;        /* 44: lr / (1 - beta1^t) of the last applied step */
+  float bc2_sqrt;         /* 48: sqrt(1 - beta2^t) of the last applied step */
+  float clip_coef;        /* 52: clip coefficient of the last step (1 = not clipped, 0 on a skipped step) */
+  int32_t reserved[2];    /* 56: padding to 64 bytes */
+} dmm_guard_state;
+
+/* Bytes of the reduction scratch for an arena of n elements (one fp64 partial sum per workgroup; device memory, 8-byte aligned). */
+size_t dmm_grad_guard_scratch_bytes(int64_t n);
+/* Fills *dev (device memory, 8-byte aligned) on `stream`: start of training, checkpoint load.  init_scale > 0. */
+int dmm_guard_state_init(dmm_guard_state* dev, float init_scale, int64_t applied_steps, int32_t growth_tracker, void* stream);
+/* Enqueues three kernels: the arena reduction (16-byte loads, a workgroup owns its partial: no floating-point atomics, so the result
+ * is bit-reproducible), the finalize kernel (partials added in a fixed order; the rule above; bias corrections computed in fp64 on the
+ * device from applied_steps, which the host does not know without a synchronisation), and Adam, which reads its scalars from *state
+ * and writes nothing on a skipped step.  max_norm <= 0: no clipping.  growth_interval 0: the scale never grows (it still backs off).
+ * growth_factor >= 1, 0 < backoff_factor <= 1 (1 and 1 with growth_interval 0 keep S fixed, e.g. clipping alone with S = 1).
+ * scratch: >= dmm_grad_guard_scratch_bytes(n). */
+int dmm_adam_step_guarded(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, int64_t n, float lr, float beta1,
+                          float beta2, float eps, float weight_decay, float max_norm, float growth_factor, float backoff_factor,
+                          int32_t growth_interval, dmm_guard_state* state, void* scratch, void* stream);
+/* The reduction alone, on elements [offset, offset + count) of `grads`: scratch = (accumulate ? scratch : 0) + partial sums of the
+ * range.  dmm_adam_step_guarded runs it once over the whole arena; a data-parallel trainer can run it per gradient bucket behind
+ * that bucket's all-reduce instead (not wired up yet).  Also what the unit tests and the cost measurement call. */
+int dmm_grad_sumsq(const float* grads, int64_t offset, int64_t count, int accumulate, void* scratch, void* stream);
+/* Points the plan's loss kernel and the external-gradient conversion of dmm_plan_backward at a device float (&state->scale):
+ * d(loss)/d(logit) is multiplied by loss_scale * (*scale_dev), read on the device when the kernel runs.  NULL = off: the code path
+ * and the numbers of a plan that never had one.  Loss sums, metric counts and the unreduced outputs stay unscaled.  Both kernels
+ * are launched eagerly in FRONT of the replayed segment of the backward list (dmm_plan_num_graph_replays), so a captured graph
+ * holds no copy of the pointer and replay is unaffected; the setting survives dmm_plan_bind. */
+int dmm_plan_set_dynamic_loss_scale(dmm_plan* plan, const float* scale_dev);
 
 /* ---- single-kernel entry points (unit tests) ---- */
 typedef struct {

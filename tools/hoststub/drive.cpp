@@ -23,6 +23,8 @@
 //                                                  are printed as region+offset, so the text does not depend on where anything is mapped
 //                                                  (DRIVE_MAP_SHIFT_MIB=<n> moves the workspace and the three arenas, to show that).
 // DRIVE_NO_MFMA=1 (any mode): the description asks for use_mfma = 0.
+// DRIVE_DYN_SCALE=1 (life-cycle run and dump): the plan gets a dynamic loss scale (dmm_plan_set_dynamic_loss_scale, pointing into a
+// guard state block the driver owns: region "guard"); the life-cycle run also takes the guarded optimiser step after every backward.
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -81,7 +83,7 @@ void chk_ops(const std::vector<Op>& ops) {
     switch (o.kind) {
       case OP_MEMSET: CHK(o.ms.p); if (o.ms.bytes) chk((const uint8_t*)o.ms.p + o.ms.bytes - 1, "ms.p + bytes - 1", o.label); break;
       case OP_COPY: CHK(o.cp.dst); CHK(o.cp.src); break;
-      case OP_CONVERT: CHK(o.cv.src1); CHK(o.cv.src2); CHK(o.cv.dst); CHK(o.cv.stat_sum); CHK(o.cv.stat_sq); break;
+      case OP_CONVERT: CHK(o.cv.src1); CHK(o.cv.src2); CHK(o.cv.dst); CHK(o.cv.stat_sum); CHK(o.cv.stat_sq); CHK(o.cv.dyn_scale); break;
       case OP_IGEMM: chk_conv(o.c, o); break;
       case OP_WGRAD: chk_wgrad(o.w, o); break;
       case OP_BW1: case OP_BW1RED: chk_conv(o.b1.c, o); CHK(o.b1.dpack); CHK(o.b1.part); break;
@@ -93,7 +95,7 @@ void chk_ops(const std::vector<Op>& ops) {
       case OP_POOLBWD: CHK(o.mpb.y0); CHK(o.mpb.scale); CHK(o.mpb.shift); CHK(o.mpb.gpool); CHK(o.mpb.xpool); CHK(o.mpb.q); CHK(o.mpb.r);
                        CHK(o.mpb.ql); CHK(o.mpb.rl); CHK(o.mpb.mean); CHK(o.mpb.invstd); CHK(o.mpb.argmax); CHK(o.mpb.gy0); CHK(o.mpb.red1);
                        CHK(o.mpb.red2); break;
-      case OP_BCE: CHK(o.bce.logits); CHK(o.bce.target); CHK(o.bce.dlogits); CHK(o.bce.out); CHK(o.bce.loss_out); CHK(o.bce.dx_out); break;
+      case OP_BCE: CHK(o.bce.logits); CHK(o.bce.target); CHK(o.bce.dlogits); CHK(o.bce.out); CHK(o.bce.loss_out); CHK(o.bce.dx_out); CHK(o.bce.dyn_scale); break;
       case OP_PACK: case OP_UNPACK: CHK(o.pk.descs); CHK(o.pk.prefix); CHK(o.pk.tdescs); CHK(o.pk.tiles); break;
       case OP_APPLYCORR: CHK(o.ac.g); CHK(o.ac.y); CHK(o.ac.q); CHK(o.ac.r); CHK(o.ac.ql); CHK(o.ac.rl); break;
       case OP_FIN64: CHK(o.f64.sbuf); CHK(o.f64.dpack); CHK(o.f64.w); CHK(o.f64.scale); CHK(o.f64.shift); CHK(o.f64.mean); CHK(o.f64.invstd); CHK(o.f64.red1); CHK(o.f64.red2); break;
@@ -169,10 +171,25 @@ static int one_life(const dmm_model_desc& d, int life) {
       if (o.kind == OP_WGRAD && o.impl == IMPL_WG3) { o.impl = IMPL_WG5; break; }
   const long l0 = fakehip_launches();
   void* st = nullptr;  // the caller's stream: the null stream, as torch's default
+  // the guarded optimiser step's state block, scratch and moment arenas ("device" memory = heap: ASan sees every host-side touch)
+  const bool dyn = getenv("DRIVE_DYN_SCALE") != nullptr;
+  dmm_guard_state* gstate = (dmm_guard_state*)aligned_alloc(64, sizeof(dmm_guard_state));
+  void* gscratch = malloc(dmm_grad_guard_scratch_bytes(np));
+  float* mom1 = (float*)malloc(np * 4); float* mom2 = (float*)malloc(np * 4);
+  if (dyn) {
+    g_regions.push_back({(uint8_t*)gstate, (uint8_t*)(gstate + 1), "guard"});
+    MUST(dmm_guard_state_init(gstate, 65536.f, 0, 0, st));
+    MUST(dmm_plan_set_dynamic_loss_scale(plan, &gstate->scale));
+  }
   for (int rep = 0; rep < 2; ++rep) {
     MUST(dmm_plan_forward(plan, in1, d.stream_2_in_channels ? in2 : nullptr, logits, 1, st));
     MUST(dmm_plan_loss_backward(plan, logits, target, metrics, st));
+    if (dyn) {
+      MUST(dmm_adam_step_guarded(params, grads, mom1, mom2, np, 1e-3f, 0.9f, 0.999f, 1e-8f, 0.f, 1.0f, 2.f, 0.5f, 2000, gstate, gscratch, st));
+      MUST(dmm_grad_sumsq(grads, np / 2, np - np / 2, 1, gscratch, st));
+    }
   }
+  if (dyn && plan->bwd[plan->bce_op].bce.dyn_scale != &gstate->scale) { fprintf(stderr, "[drive] the loss record lost its dynamic scale\n"); return 2; }
   chk_ops(plan->fwd_train); chk_ops(plan->fwd_eval); chk_ops(plan->bwd); chk_descs(plan);
   MUST(dmm_plan_forward(plan, in1, d.stream_2_in_channels ? in2 : nullptr, logits, 1, st));
   MUST(dmm_plan_backward(plan, target /*stands for d(loss)/d(logit)*/, st));
@@ -201,6 +218,7 @@ static int one_life(const dmm_model_desc& d, int life) {
   const size_t nf = plan->fwd_train.size(), nbw = plan->bwd.size();
   MUST(dmm_plan_destroy(plan));
   free(ws); free(params); free(grads); free(buffers); free(in1); free(in2); free(logits); free(target); free(metrics);
+  free(gstate); free(gscratch); free(mom1); free(mom2);
   printf("life %d: workspace %.1f MiB, %zu + %zu launch records, %ld launches, %ld pointers checked, %ld bad, streams alive %ld (created %ld), events alive %ld (created %ld), violations %ld\n",
          life, wsb / 1048576.0, nf, nbw, launches, g_checked, g_bad, fakehip_live_streams(), fakehip_stream_creates(), fakehip_live_events(),
          fakehip_event_creates(), fakehip_violations());
@@ -303,7 +321,7 @@ static int picks_main(int argc, char** argv) {
 // NOT printed: bytes of a record's union outside the member its kind uses, and the characters of `label` behind its terminator.
 namespace {
 struct Dumper {
-  Region reg[4];   // ws, params, grads, buffers
+  Region reg[5] = {};   // ws, params, grads, buffers, guard (the driver's guard state block; empty without DRIVE_DYN_SCALE)
   long outside = 0;
   void ptr(const char* name, const void* p) {
     if (p == nullptr) { printf(" %s=null", name); return; }
@@ -364,7 +382,7 @@ struct Dumper {
       case OP_MEMSET: { const MemsetArgs& a = o.ms; printf("    memset:"); DP(p); DU(bytes); printf("\n"); break; }
       case OP_COPY: { const CopyArgs& a = o.cp; printf("    copy:"); DP(dst); DP(src); DU(bytes); printf("\n"); break; }
       case OP_CONVERT: { const ConvertArgs& a = o.cv; printf("    convert:"); DP(src1); DP(src2); DI(C1); DI(C2); DP(dst); DI(B); DI(H); DI(W); DP(stat_sum);
-                         DP(stat_sq); DD(scale); printf("\n"); break; }
+                         DP(stat_sq); DD(scale); DP(dyn_scale); printf("\n"); break; }
       case OP_IGEMM: conv(o.c); break;
       case OP_WGRAD: wgrad(o.w); break;
       case OP_BW1: case OP_BW1RED: { conv(o.b1.c); const Bw1Args& a = o.b1; printf("    bw1:"); DP(dpack); DI(dNpad); DI(wC); DP(part); DI(part_slots); DI(nct);
@@ -381,7 +399,7 @@ struct Dumper {
       case OP_BCE: { const BceArgs& a = o.bce; printf("    bce:"); DP(logits); DP(target); DP(dlogits); DP(out); DI(B); DI(NC); DI(H); DI(W); DD(thr); DD(loss_scale);
                      DI(kind); DI(from_prob);
                      for (int k = 0; k < 8; ++k) { DD(alpha[k]); DD(gamma[k]); }
-                     DP(loss_out); DP(dx_out); DI(metrics); printf("\n"); break; }
+                     DP(loss_out); DP(dx_out); DI(metrics); DP(dyn_scale); printf("\n"); break; }
       case OP_PACK: case OP_UNPACK: { const PackArgs& a = o.pk; printf("    pack:"); DP(descs); DP(prefix); DI(ndesc); DI(total_rows); DD(grad_scale); DP(tdescs);
                                       DP(tiles); DI(nt1); DI(nt9); printf("\n"); break; }
       case OP_APPLYCORR: { const ApplyCorrArgs& a = o.ac; printf("    applycorr:"); DP(g); DP(y); DP(q); DP(r); DP(ql); DP(rl); DU(npix); DI(C); DI(ldg); DI(ldy);
@@ -456,6 +474,11 @@ static int dump_main(int argc, char** argv) {
   D.reg[1] = {(uint8_t*)params, (uint8_t*)(params + np), "params"};
   D.reg[2] = {(uint8_t*)grads, (uint8_t*)(grads + np), "grads"};
   D.reg[3] = {(uint8_t*)buffers, (uint8_t*)(buffers + nb), "buffers"};
+  static dmm_guard_state gstate;
+  if (getenv("DRIVE_DYN_SCALE")) {
+    D.reg[4] = {(uint8_t*)&gstate, (uint8_t*)(&gstate + 1), "guard"};
+    MUST(dmm_plan_set_dynamic_loss_scale(plan, &gstate.scale));
+  }
   printf("plan zero_bytes=%zu zero_bwd_bytes=%zu main_bytes=%zu nparams=%lld nbuf=%lld fwd_flops=%.17g metrics_bytes=%zu bucket_bytes=%zu\n", plan->zero_bytes,
          plan->zero_bwd_bytes, plan->main_bytes, (long long)plan->nparams, (long long)plan->nbuf, plan->fwd_flops, plan->metrics_bytes, plan->bucket_bytes);
   D.ptr("metrics", plan->metrics);
