@@ -16,6 +16,7 @@
 #include <type_traits>
 
 #include "common.h"
+#include "dispatch.h"
 #include "gather.h"
 #include "pointwise.h"
 
@@ -410,15 +411,7 @@ bool bw1_enabled() { return g_bw1; }
 
 template <typename T, int PQ, bool ACC, bool PART>
 static hipError_t launch_bw1_t(const Bw1Args& g, int nwg, hipStream_t st) {
-  auto kern = bw1_kernel<T, PQ, ACC, PART>;
-  static bool attr_done = false;
-  if (!attr_done) {
-    const hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, B1_LDS);
-    if (e != hipSuccess) return e;
-    attr_done = true;
-  }
-  hipLaunchKernelGGL(kern, dim3(nwg), dim3(NTHREADS), B1_LDS, st, g);
-  return hipGetLastError();
+  return launch_lds<bw1_kernel<T, PQ, ACC, PART>>(B1_LDS, nwg, NTHREADS, B1_LDS, st, g);
 }
 
 // Do these two launches - the weight gradient `w` (normal form) and the data gradient `d` (EPI_BNBWD) of one convolution - form

@@ -10,6 +10,7 @@
 #include <string>
 #include <unistd.h>
 
+#include "dispatch.h"
 #include "plan.h"
 
 using namespace dmm;
@@ -953,7 +954,8 @@ int dmm_conv_wgrad_ex(const dmm_conv_desc* d, const void* x, const void* dy, con
     a.N = g.Cst; a.Npad = pd.Npad;
     a.dpack = (float*)pd.dpack;
     void* part = nullptr;
-    if (d->use_mfma && wg3_handles(a, d->dtype)) {  // the plan gives the family its slots; so does this entry point
+    Resolved wg3;
+    if (d->use_mfma && wg3_enabled() && wg3_resolve(a, d->dtype, wg3)) {  // the plan gives the family its slots; so does this entry point
       HIPCHK(hipMallocAsync(&part, (size_t)W3_MAX_SLOTS * W3_SLOT_FLOATS * sizeof(float), st));
       a.part = (float*)part;
       a.part_slots = W3_MAX_SLOTS;

@@ -18,6 +18,7 @@
 #include <cstdlib>
 
 #include "common.h"
+#include "dispatch.h"
 #include "gather.h"
 
 namespace dmm {
@@ -233,53 +234,47 @@ __global__ __launch_bounds__(CF_NT, 2) void cf_kernel(const CfArgs g) {
   }
 }
 
-template <typename T>
-static hipError_t launch_cf_t(const CfArgs& g, int nwg, hipStream_t st) {
-  auto kern = cf_kernel<T>;
-  static bool attr_done = false;
-  if (!attr_done) {
-    const hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, CF_LDS);
-    if (e != hipSuccess) return e;
-    attr_done = true;
-  }
-  hipLaunchKernelGGL(kern, dim3(nwg), dim3(CF_NT), CF_LDS, st, g);
-  return hipGetLastError();
-}
+bool cf_enabled() { return !lab_flag("DMM_NO_CF"); }
 
 // Takes the forward launch (EPI_STORE) of a 3x3 unit-stride convolution over ONE plain segment of 128 BN+ReLU-normalised channels with 32
 // output channels, whole 8 x 16 tiles and at least DMM_CF_MIN_TILES of them (default: eight per CU - measured: 4800 tiles 87 -> 70 us, 1200 tiles 29 -> 30 us), 16-bit storage.
-// hipErrorNotSupported otherwise (conv3.hip takes the launch then).
-hipError_t launch_cf(const ConvArgs& a, int dtype, int epi, hipStream_t st) {
-  if (!family_on(!lab_flag("DMM_NO_CF"), IMPL_CF) || dtype == DT_F32 || epi != EPI_STORE || a.nphase != 0 || a.nseg != 1 || a.pool2) return hipErrorNotSupported;
+// Refused otherwise (conv3.hip takes the launch then).
+bool cf_resolve(const ConvArgs& a, int dtype, int epi, Resolved& r) {
+  if (dtype == DT_F32 || epi != EPI_STORE || a.nphase != 0 || a.nseg != 1 || a.pool2) return false;
   const Seg& u = a.seg[0];
-  if (u.mode != G_PLAIN || u.istride != 1 || u.C != 128 || u.Cpad != 128 || u.Hs != a.Ho || u.Ws != a.Wo || u.scale == nullptr || u.ntaps != CF_NTAP) return hipErrorNotSupported;
-  if (a.N != CF_BN || a.Npad != CF_BN || a.out == nullptr || a.ostride != 1 || a.Hout != a.Ho || a.Wout != a.Wo) return hipErrorNotSupported;
-  if (a.Ho % CF_TH || a.Wo % CF_TW || a.ldo % 8) return hipErrorNotSupported;
-  if (2.0 * a.B * u.Hs * u.Ws * u.ld >= 4294967296.0) return hipErrorNotSupported;   // 32-bit byte offsets
+  if (u.mode != G_PLAIN || u.istride != 1 || u.C != 128 || u.Cpad != 128 || u.Hs != a.Ho || u.Ws != a.Wo || u.scale == nullptr || u.ntaps != CF_NTAP) return false;
+  if (a.N != CF_BN || a.Npad != CF_BN || a.out == nullptr || a.ostride != 1 || a.Hout != a.Ho || a.Wout != a.Wo) return false;
+  if (a.Ho % CF_TH || a.Wo % CF_TW || a.ldo % 8) return false;
+  if (2.0 * a.B * u.Hs * u.Ws * u.ld >= 4294967296.0) return false;   // 32-bit byte offsets
   int dymin = 127, dxmin = 127, dymax = -128, dxmax = -128;
   bool seen[9] = {false};
   for (int t = 0; t < CF_NTAP; ++t) {
     const int dy = (int)(signed char)(u.taps[t] & 0xff), dx = (int)(signed char)((u.taps[t] >> 8) & 0xff);
     dymin = std::min(dymin, dy); dymax = std::max(dymax, dy); dxmin = std::min(dxmin, dx); dxmax = std::max(dxmax, dx);
   }
-  if (dymax - dymin != 2 || dxmax - dxmin != 2) return hipErrorNotSupported;
+  if (dymax - dymin != 2 || dxmax - dxmin != 2) return false;
   for (int t = 0; t < CF_NTAP; ++t) {   // every offset of the box exactly once
     const int i = ((int)(signed char)(u.taps[t] & 0xff) - dymin) * 3 + ((int)(signed char)((u.taps[t] >> 8) & 0xff) - dxmin);
-    if (seen[i]) return hipErrorNotSupported;
+    if (seen[i]) return false;
     seen[i] = true;
   }
-  CfArgs g;
+  LdsLaunch<CfArgs>& l = r.put<LdsLaunch<CfArgs>>();
+  CfArgs& g = l.g;
   g.tiles_y = a.Ho / CF_TH;
   g.tiles_x = a.Wo / CF_TW;
   g.ntiles = a.B * g.tiles_y * g.tiles_x;
   static const int min_tiles = lab_int("DMM_CF_MIN_TILES", 8 * DESIGN_CUS);
-  if (g.ntiles < min_tiles) return hipErrorNotSupported;   // a few tiles per CU: 72 KB of weights per workgroup do not pay
-  if (g_ctl.dry) return hipSuccess;
+  if (g.ntiles < min_tiles) return false;   // a few tiles per CU: 72 KB of weights per workgroup do not pay
   g.c = a;
   g.dymin = dymin; g.dxmin = dxmin;
-  const int nwg = DESIGN_CUS;   // one workgroup per CU (140 KB of LDS), whole groups of 8 (one per XCD)
-  g.per = (g.ntiles + nwg - 1) / nwg;
-  return dtype == DT_F16 ? launch_cf_t<f16>(g, nwg, st) : launch_cf_t<bf16>(g, nwg, st);
+  l.nwg = DESIGN_CUS;   // one workgroup per CU (140 KB of LDS), whole groups of 8 (one per XCD)
+  g.per = (g.ntiles + l.nwg - 1) / l.nwg;
+  l.attr_bytes = l.lds = CF_LDS;
+  l.nthreads = CF_NT;
+  l.run = dtype == DT_F16 ? launch_lds<cf_kernel<f16>, CfArgs> : launch_lds<cf_kernel<bf16>, CfArgs>;
+  return true;
 }
+
+hipError_t cf_launch(const Resolved& r, hipStream_t st) { return r.get<LdsLaunch<CfArgs>>().go(st); }
 
 }  // namespace dmm

@@ -192,22 +192,15 @@ constexpr int W3_SLOT_FLOATS = 9 * 128 * 32;  // one workgroup's partial result 
 constexpr int W3_MAX_SLOTS = 256;             // = workgroups of a launch at most (device-independent: plans are sized without a GPU)
 
 // Kernel family of a convolution / weight-gradient launch.  A plan decides it ONCE per launch when it is built (igemm_pick /
-// wgrad_pick walk the dispatch without launching and honour the dmm_set_option switches of that moment) and the executor
-// dispatches from the recorded value, so a plan's labels, its profile classes and the kernels it runs cannot drift apart when an
-// option is toggled afterwards.  IMPL_AUTO (the single-kernel test entry points): decide at the call.
+// wgrad_pick ask every family's resolve, in dispatch order, and honour the dmm_set_option switches of that moment: dispatch.h) and the
+// executor asks the recorded family's resolve alone, so a plan's labels, its profile classes and the kernels it runs cannot drift
+// apart when an option is toggled afterwards.  IMPL_AUTO (the single-kernel test entry points): decide at the call.
 enum Impl { IMPL_AUTO = 0, IMPL_GENERIC = 1, IMPL_THIN, IMPL_CONV3, IMPL_CVP, IMPL_HALO, IMPL_WG3, IMPL_WG5, IMPL_WGP, IMPL_PIG, IMPL_BW1, IMPL_HF, IMPL_CF, IMPL_WGPW /* wgp in its wave-specialised form: noted beside IMPL_WGP */, IMPL_CVW /* likewise cvp forward (cvw.hip) */, IMPL_COUNT };
-struct LaunchCtl {
-  bool dry = false;      // walk the eligibility tests, launch nothing
-  int impl = IMPL_AUTO;  // the one family allowed to take the launch (IMPL_AUTO: every enabled family, in dispatch order)
-  unsigned deny = 0;     // 1 << family for families a plan under construction must not pick (PlanSwitches, plan.h)
-};
-extern thread_local LaunchCtl g_ctl;  // (defined in pointwise.hip)
 // The family that took the calling thread's most recent convolution / weight-gradient / fused-backward launch (dmm_last_impl):
 // a per-kernel test asserts the family it names really ran - IMPL_AUTO falls back to the generic kernels silently.
 extern thread_local int g_last_impl;
 extern thread_local unsigned g_impl_mask;  // 1 << family for every launch since the mask was last reset (dmm_impl_mask)
 inline void note_impl(int impl) { g_last_impl = impl; g_impl_mask |= 1u << impl; }
-inline bool family_on(bool enabled, int family) { return g_ctl.impl == IMPL_AUTO ? (enabled && !((g_ctl.deny >> family) & 1u)) : g_ctl.impl == family; }
 
 // Lab knobs: launch-geometry and ablation switches whose experiments are recorded (profiles/*/ablations.txt).  The
 // shipped library fixes them at their defaults - no getenv, nothing an embedding process can trip over; a lab build

@@ -26,6 +26,7 @@
 #include <type_traits>
 
 #include "common.h"
+#include "dispatch.h"
 #include "gather.h"
 
 namespace dmm {
@@ -504,53 +505,50 @@ __global__ __launch_bounds__(NTHREADS, 2) void conv3_kernel(const Conv3Args g) {
 // ------------------------------------------------------------------------------------------------ host side
 static bool g_conv3 = !lab_flag("DMM_NO_CONV3");
 void conv3_set_enabled(bool on) { g_conv3 = on; }
+bool conv3_enabled() { return g_conv3; }
 
+// The launcher of one instantiation (what conv3_resolve hands to conv3_launch beside the kernel's arguments).
+typedef hipError_t (*C3Inst)(const Conv3Args& g, hipStream_t st);
 
 template <typename T, int CS, int SPAN, int TSPAN, int TSTR, int NT, int GC, int EPI, int PRO>
 static hipError_t launch_c3(const Conv3Args& g, hipStream_t st) {
   typedef Conv3Cfg<T, CS, SPAN, TSPAN, TSTR, NT, GC> SM;
   static_assert(SM::bytes <= 80 * 1024, "two workgroups per CU");
-  if (g_ctl.dry) return hipSuccess;
-  auto kern = conv3_kernel<T, CS, SPAN, TSPAN, TSTR, NT, GC, EPI, PRO>;
-  static bool attr_done = false;
-  if (SM::bytes > 48 * 1024 && !attr_done) {
-    hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, SM::bytes);
-    if (e != hipSuccess) return e;
-    attr_done = true;
-  }
+  constexpr auto kern = conv3_kernel<T, CS, SPAN, TSPAN, TSTR, NT, GC, EPI, PRO>;
+  const hipError_t e = lds_limit<kern>(SM::bytes > 48 * 1024 ? SM::bytes : 0);
+  if (e != hipSuccess) return e;
   // persistent: the workgroups a CU holds at a time (LDS, <= 4) x CUs x 2 rounds' worth of slots, in whole groups of 8 (one per XCD);
   // a launch with fewer tiles than that runs one tile per workgroup, as before
-  static const int cus = [] { hipDeviceProp_t pr; int dev = 0; hipGetDevice(&dev);
-                              return (hipGetDeviceProperties(&pr, dev) == hipSuccess && pr.multiProcessorCount > 0) ? pr.multiProcessorCount : 256; }();
+  static const int cus = device_cus();
   static const int rounds = lab_int("DMM_C3_ROUNDS", 1);
   const int per_cu = std::min(4, (160 * 1024) / SM::bytes);
   int nwg = g.ntiles * (g.c.nphase > 0 ? g.c.nphase : 1);
   if (EPI == EPI_STORE && rounds > 0 && nwg > per_cu * cus * rounds) nwg = per_cu * cus * rounds / 8 * 8;
-  hipLaunchKernelGGL(kern, dim3(nwg), dim3(NTHREADS), SM::bytes, st, g);
-  return hipGetLastError();
+  return launch_lds<kern>(0, nwg, NTHREADS, SM::bytes, st, g);
 }
 
+// The instantiations built (nullptr: none for this shape).
 template <typename T>
-static hipError_t launch_c3_type(const Conv3Args& g, int epi, int pro, int cs, int span, int tspan, int tstr, int nt, hipStream_t st) {
+static C3Inst c3_instance(int epi, int pro, int cs, int span, int tspan, int tstr, int nt) {
   if (epi == EPI_STORE && pro == 1) {
-    if (tspan < 0 && span == 2 && nt == 1 && cs == 16) return launch_c3<T, 16, 2, -1, 1, 1, 4, EPI_STORE, 1>(g, st);  // dense conv2
-    if (tspan < 0 && span == 2 && nt == 1 && cs == 8) return launch_c3<T, 8, 2, -1, 1, 1, 2, EPI_STORE, 1>(g, st);
-    if (tspan == 2 && tstr == 2 && span == 1 && nt == 2 && cs == 16) return launch_c3<T, 16, 1, 2, 2, 2, 2, EPI_STORE, 1>(g, st);  // refine0 phase
+    if (tspan < 0 && span == 2 && nt == 1 && cs == 16) return launch_c3<T, 16, 2, -1, 1, 1, 4, EPI_STORE, 1>;  // dense conv2
+    if (tspan < 0 && span == 2 && nt == 1 && cs == 8) return launch_c3<T, 8, 2, -1, 1, 1, 2, EPI_STORE, 1>;
+    if (tspan == 2 && tstr == 2 && span == 1 && nt == 2 && cs == 16) return launch_c3<T, 16, 1, 2, 2, 2, 2, EPI_STORE, 1>;  // refine0 phase
   }
   if (epi == EPI_BNBWD && tspan < 0 && span == 2) {
-    if (cs == 4 && nt == 4 && pro == 2) return launch_c3<T, 4, 2, -1, 1, 4, 1, EPI_BNBWD, 2>(g, st);              // dense conv2 dgrad
-    if (cs == 4 && nt == 4 && pro == 0) return launch_c3<T, 4, 2, -1, 1, 4, 1, EPI_BNBWD, 0>(g, st);
-    if (cs == 4 && nt == 2 && pro == 2) return launch_c3<T, 4, 2, -1, 1, 2, 1, EPI_BNBWD, 2>(g, st);
-    if (cs == 4 && nt == 2 && pro == 0) return launch_c3<T, 4, 2, -1, 1, 2, 1, EPI_BNBWD, 0>(g, st);
-    if (cs == 8 && nt == 1 && pro == 0) return launch_c3<T, 8, 2, -1, 1, 1, 2, EPI_BNBWD, 0>(g, st);              // refine0 -> raw input
-    if (cs == 8 && nt == 1 && pro == 2) return launch_c3<T, 8, 2, -1, 1, 1, 2, EPI_BNBWD, 2>(g, st);
+    if (cs == 4 && nt == 4 && pro == 2) return launch_c3<T, 4, 2, -1, 1, 4, 1, EPI_BNBWD, 2>;              // dense conv2 dgrad
+    if (cs == 4 && nt == 4 && pro == 0) return launch_c3<T, 4, 2, -1, 1, 4, 1, EPI_BNBWD, 0>;
+    if (cs == 4 && nt == 2 && pro == 2) return launch_c3<T, 4, 2, -1, 1, 2, 1, EPI_BNBWD, 2>;
+    if (cs == 4 && nt == 2 && pro == 0) return launch_c3<T, 4, 2, -1, 1, 2, 1, EPI_BNBWD, 0>;
+    if (cs == 8 && nt == 1 && pro == 0) return launch_c3<T, 8, 2, -1, 1, 1, 2, EPI_BNBWD, 0>;              // refine0 -> raw input
+    if (cs == 8 && nt == 1 && pro == 2) return launch_c3<T, 8, 2, -1, 1, 1, 2, EPI_BNBWD, 2>;
   }
-  if (epi == EPI_STORE && cs == 0 && tspan == 6 && tstr == 2 && pro == 0 && nt == 2) return launch_c3<T, 0, 0, 6, 2, 2, 2, EPI_STORE, 0>(g, st);  // stem conv0 (7x7 stride 2)
+  if (epi == EPI_STORE && cs == 0 && tspan == 6 && tstr == 2 && pro == 0 && nt == 2) return launch_c3<T, 0, 0, 6, 2, 2, 2, EPI_STORE, 0>;  // stem conv0 (7x7 stride 2)
   if (epi == EPI_BNBWD && cs == 0 && tspan == 4 && tstr == 1 && pro == 0) {                                          // refine1 dgrad (5x5)
-    if (nt == 2) return launch_c3<T, 0, 0, 4, 1, 2, 2, EPI_BNBWD, 0>(g, st);
-    if (nt == 1) return launch_c3<T, 0, 0, 4, 1, 1, 2, EPI_BNBWD, 0>(g, st);
+    if (nt == 2) return launch_c3<T, 0, 0, 4, 1, 2, 2, EPI_BNBWD, 0>;
+    if (nt == 1) return launch_c3<T, 0, 0, 4, 1, 1, 2, EPI_BNBWD, 0>;
   }
-  return hipErrorNotSupported;
+  return nullptr;
 }
 
 static bool tap_box(const Seg& sg, int& dymin, int& dxmin, int& span) {
@@ -572,13 +570,20 @@ static bool tap_box(const Seg& sg, int& dymin, int& dxmin, int& span) {
   return true;
 }
 
-// Returns hipErrorNotSupported when the layer is not one of the shapes built (16-bit storage, unit-stride multi-tap segment of
-// C % 32 == 0 channels on the row grid, optionally the 8-channel stride-2 raw-input segment of the head).
-hipError_t launch_conv3(const ConvArgs& a, int dtype, int epi, hipStream_t st) {
-  if (!family_on(g_conv3, IMPL_CONV3) || dtype == DT_F32 || a.nseg < 1 || a.nseg > 2 || a.pool2 || (epi != EPI_STORE && epi != EPI_BNBWD)) return hipErrorNotSupported;
-  const Seg& sg = a.seg[0];
-  if (a.Npad % 32 || a.Npad > 128) return hipErrorNotSupported;
+struct Conv3Launch {
   Conv3Args g;
+  C3Inst run;
+  int shape[8];   // (DMM_C3_TRACE) epi, pro, cs, span, tspan, tstr, nt, M
+};
+
+// Refused when the layer is not one of the shapes built (16-bit storage, unit-stride multi-tap segment of
+// C % 32 == 0 channels on the row grid, optionally the 8-channel stride-2 raw-input segment of the head).
+bool conv3_resolve(const ConvArgs& a, int dtype, int epi, Resolved& r) {
+  if (dtype == DT_F32 || a.nseg < 1 || a.nseg > 2 || a.pool2 || (epi != EPI_STORE && epi != EPI_BNBWD)) return false;
+  const Seg& sg = a.seg[0];
+  if (a.Npad % 32 || a.Npad > 128) return false;
+  Conv3Launch& l = r.put<Conv3Launch>();
+  Conv3Args& g = l.g;
   g.c = a;
   g.dymin0 = g.dxmin0 = g.dymin1 = g.dxmin1 = 0;
   int cs = 0, span = 0, tspan = -1, tstr = 1;
@@ -588,21 +593,21 @@ hipError_t launch_conv3(const ConvArgs& a, int dtype, int epi, hipStream_t st) {
   };
   if (a.nseg == 1 && sg.C == 8 && sg.istride == 2) {  // thin segment only, stride 2: the stem's 7x7 convolution over the raw input
     tstr = 2;
-    if (epi != EPI_STORE || !thin_ok(sg, 2) || tspan != 6 || sg.scale != nullptr) return hipErrorNotSupported;
+    if (epi != EPI_STORE || !thin_ok(sg, 2) || tspan != 6 || sg.scale != nullptr) return false;
   } else if (a.nseg == 1 && sg.C == 8) {   // thin segment only: the logits gradient under the 5x5 head convolution
-    if (!thin_ok(sg, 1) || tspan != 4 || sg.scale != nullptr) return hipErrorNotSupported;
+    if (!thin_ok(sg, 1) || tspan != 4 || sg.scale != nullptr) return false;
   } else {
-    if (sg.mode != G_PLAIN || sg.istride != 1 || sg.C % 32 || sg.Cpad != sg.C || sg.Hs != a.Ho || sg.Ws != a.Wo) return hipErrorNotSupported;
-    if (!tap_box(sg, g.dymin0, g.dxmin0, span) || span < 1 || span > 2) return hipErrorNotSupported;
+    if (sg.mode != G_PLAIN || sg.istride != 1 || sg.C % 32 || sg.Cpad != sg.C || sg.Hs != a.Ho || sg.Ws != a.Wo) return false;
+    if (!tap_box(sg, g.dymin0, g.dxmin0, span) || span < 1 || span > 2) return false;
     cs = sg.C / 8;
     if (a.nseg == 2) {
       tstr = 2;
-      if (!thin_ok(a.seg[1], 2) || tspan != 2 || (a.seg[1].scale != nullptr) != (sg.scale != nullptr)) return hipErrorNotSupported;
+      if (!thin_ok(a.seg[1], 2) || tspan != 2 || (a.seg[1].scale != nullptr) != (sg.scale != nullptr)) return false;
     }
   }
-  if (a.nphase < 0 || a.nphase > 4) return hipErrorNotSupported;
+  if (a.nphase < 0 || a.nphase > 4) return false;
   if (a.nphase > 0) {  // several output-parity phases in one launch: the forward of the two-segment head convolution only
-    if (epi != EPI_STORE || a.nseg != 2 || sg.ntaps != 4 || a.seg[1].ntaps != 9) return hipErrorNotSupported;
+    if (epi != EPI_STORE || a.nseg != 2 || sg.ntaps != 4 || a.seg[1].ntaps != 9) return false;
     for (int ph = 0; ph < a.nphase; ++ph) {
       Seg t0 = sg, t1 = a.seg[1];
       for (int t = 0; t < 4; ++t) t0.taps[t] = a.ph_taps0[ph][t];
@@ -610,36 +615,36 @@ hipError_t launch_conv3(const ConvArgs& a, int dtype, int epi, hipStream_t st) {
       int y0, x0, y1, x1, sp0, sp1;
       if (!tap_box(t0, y0, x0, sp0) || sp0 != span || !tap_box(t1, y1, x1, sp1) || sp1 != tspan || a.ph_wpack[ph] == nullptr ||
           a.ph_py[ph] < 0 || a.ph_py[ph] >= a.ostride || a.ph_px[ph] < 0 || a.ph_px[ph] >= a.ostride)
-        return hipErrorNotSupported;
+        return false;
       g.ph_dymin0[ph] = (signed char)y0; g.ph_dxmin0[ph] = (signed char)x0; g.ph_dymin1[ph] = (signed char)y1; g.ph_dxmin1[ph] = (signed char)x1;
     }
   }
-  if (a.nseg == 1 && (a.ostride != 1 || a.Hout != a.Ho || a.Wout != a.Wo)) return hipErrorNotSupported;
-  if (cs == 0 && tspan == 6 && a.Npad != 64) return hipErrorNotSupported;
+  if (a.nseg == 1 && (a.ostride != 1 || a.Hout != a.Ho || a.Wout != a.Wo)) return false;
+  if (cs == 0 && tspan == 6 && a.Npad != 64) return false;
   const int pro = sg.scale ? 1 : (sg.q ? 2 : 0);
-  if (epi == EPI_BNBWD && a.accumulate && a.out == nullptr) return hipErrorNotSupported;
+  if (epi == EPI_BNBWD && a.accumulate && a.out == nullptr) return false;
   // the final-gradient epilogue (eq / er) exists in ONE variant: the thin-only 5x5 data gradient, not accumulating, with an output
-  if ((a.eq != nullptr) != (a.er != nullptr)) return hipErrorNotSupported;
+  if ((a.eq != nullptr) != (a.er != nullptr)) return false;
   if (a.eq != nullptr && !(epi == EPI_BNBWD && cs == 0 && tspan == 4 && tstr == 1 && pro == 0 && a.out != nullptr && !a.accumulate &&
                            a.red1 == nullptr && a.red2 == nullptr))
-    return hipErrorNotSupported;
+    return false;
   g.tiles_y = (a.Ho + C3_TH - 1) / C3_TH;
   g.tiles_x = (a.Wo + C3_TW - 1) / C3_TW;
   g.ntiles = a.B * g.tiles_y * g.tiles_x;
   const int nt = a.Npad / 32;
-  static const bool trace = lab_flag("DMM_C3_TRACE");
-  if (trace && !g_ctl.dry) fprintf(stderr, "conv3: epi %d pro %d cs %d span %d tspan %d tstr %d nt %d M %d\n", epi, pro, cs, span, tspan, tstr, nt, a.M);
-  return dtype == DT_F16 ? launch_c3_type<f16>(g, epi, pro, cs, span, tspan, tstr, nt, st)
-                         : launch_c3_type<bf16>(g, epi, pro, cs, span, tspan, tstr, nt, st);
+  const int shape[8] = {epi, pro, cs, span, tspan, tstr, nt, a.M};
+  std::copy(shape, shape + 8, l.shape);
+  l.run = dtype == DT_F16 ? c3_instance<f16>(epi, pro, cs, span, tspan, tstr, nt) : c3_instance<bf16>(epi, pro, cs, span, tspan, tstr, nt);
+  return l.run != nullptr;
 }
 
-// Does launch_conv3 take this launch?  (the plan labels its launches by the kernel family that runs them)
-bool conv3_handles(const ConvArgs& a, int dtype, int epi) {
-  const LaunchCtl keep = g_ctl;
-  g_ctl.dry = true;
-  const hipError_t e = launch_conv3(a, dtype, epi, nullptr);
-  g_ctl = keep;
-  return e == hipSuccess;
+hipError_t conv3_launch(const Resolved& r, hipStream_t st) {
+  const Conv3Launch& l = r.get<Conv3Launch>();
+  static const bool trace = lab_flag("DMM_C3_TRACE");
+  const int* s = l.shape;
+  if (trace) fprintf(stderr, "conv3: epi %d pro %d cs %d span %d tspan %d tstr %d nt %d M %d\n", s[0], s[1], s[2], s[3], s[4], s[5], s[6], s[7]);
+  return l.run(l.g, st);
 }
+
 
 }  // namespace dmm

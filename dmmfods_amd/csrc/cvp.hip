@@ -18,6 +18,7 @@
 #include <cstdlib>
 
 #include "common.h"
+#include "dispatch.h"
 #include "gather.h"
 
 namespace dmm {
@@ -747,28 +748,14 @@ __global__ __launch_bounds__(NTHREADS, 3) void cvd3_kernel(const CvdArgs g) {
 
 static bool g_cvp = !lab_flag("DMM_NO_CVP");
 void cvp_set_enabled(bool on) { g_cvp = on; }
+bool cvp_enabled() { return g_cvp; }
 
-
-template <typename T, int NTAP>
-static hipError_t launch_cvp_t(const CvpArgs& g, int nwg, hipStream_t st) {
-  auto kern = cvp_kernel<T, NTAP>;
-  static bool attr_done = false;
-  if (!attr_done) {
-    const hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, CP_LDS);
-    if (e != hipSuccess) return e;
-    attr_done = true;
-  }
-  hipLaunchKernelGGL(kern, dim3(nwg), dim3(NTHREADS), CP_LDS, st, g);
-  return hipGetLastError();
-}
-
-static hipError_t launch_cvd(const ConvArgs& a, int dtype, hipStream_t st);
-// the wave-specialised forward (cvw.hip, round 5)
-hipError_t launch_cvw(const ConvArgs& a, int dtype, const int* ph_dymin, const int* ph_dxmin, hipStream_t st);
+// the wave-specialised form of the forward (cvw.hip, round 5): noted as IMPL_CVW beside IMPL_CVP when it runs
+bool cvw_resolve(const ConvArgs& a, int dtype, const int* ph_dymin, const int* ph_dxmin, Resolved& r);
+hipError_t cvw_launch(const Resolved& r, hipStream_t st);
 static const bool g_cvw = !lab_flag("DMM_NO_CVW");
+constexpr int CVP_FORM_CVD = -1;   // Resolved::form of the data gradient (0: this file's forward kernels, IMPL_CVW: cvw.hip's)
 
-// Takes a forward launch (EPI_STORE) with one plain segment of a multiple of 128 BN+ReLU-normalised input channels whose 1, 2 or
-// 4 taps lie in a 2x2 box, a multiple of 128 padded output columns, 16-bit storage.  Returns hipErrorNotSupported otherwise.
 static bool cvp_tap_box(const short* taps, int ntaps, int& dymin, int& dxmin) {
   int dymax = -128, dxmax = -128;
   dymin = 127; dxmin = 127;
@@ -779,150 +766,122 @@ static bool cvp_tap_box(const short* taps, int ntaps, int& dymin, int& dxmin) {
   return dymax - dymin <= 1 && dxmax - dxmin <= 1;
 }
 
-template <typename T>
-static hipError_t launch_cvp_multi_t(const CvpArgs& g, int nwg, hipStream_t st) {
-  auto kern = cvp_multi_kernel<T>;
-  static bool attr_done = false;
-  if (!attr_done) {
-    const hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, CP_LDS);
-    if (e != hipSuccess) return e;
-    attr_done = true;
-  }
-  hipLaunchKernelGGL(kern, dim3(nwg), dim3(NTHREADS), CP_LDS, st, g);
-  return hipGetLastError();
+static bool cvd_resolve(const ConvArgs& a, int dtype, Resolved& r);
+template <typename G> static void cvp_tiles(const ConvArgs& a, G& g) {   // the launch and its pixel / column tiles (CvpArgs, CvdArgs)
+  g.c = a;
+  g.tiles_y = (a.Ho + CP_TH - 1) / CP_TH;
+  g.tiles_x = (a.Wo + CP_TW - 1) / CP_TW;
+  g.ntn = a.Npad / CP_BN;
 }
 
-hipError_t launch_cvp(const ConvArgs& a, int dtype, int epi, hipStream_t st) {
-  if (!family_on(g_cvp, IMPL_CVP) || dtype == DT_F32) return hipErrorNotSupported;
-  if (epi == EPI_BNBWD) return launch_cvd(a, dtype, st);
-  if (epi != EPI_STORE || a.nseg != 1 || a.pool2) return hipErrorNotSupported;
+// Takes a forward launch (EPI_STORE) with one plain segment of a multiple of 128 BN+ReLU-normalised input channels whose 1, 2 or
+// 4 taps lie in a 2x2 box, a multiple of 128 padded output columns, 16-bit storage - in cvw.hip's form where that accepts the launch,
+// else in this file's - and the stride-2 data gradients (EPI_BNBWD: cvd_resolve).  Refused otherwise.
+bool cvp_resolve(const ConvArgs& a, int dtype, int epi, Resolved& r) {
+  if (dtype == DT_F32) return false;
+  if (epi == EPI_BNBWD) return cvd_resolve(a, dtype, r);
+  if (epi != EPI_STORE || a.nseg != 1 || a.pool2) return false;
   const Seg& x = a.seg[0];
   if (x.mode != G_PLAIN || x.istride != 1 || x.Hs != a.Ho || x.Ws != a.Wo || x.scale == nullptr || x.C % CP_CA || x.Cpad != x.C)
-    return hipErrorNotSupported;
+    return false;
+  const bool f16t = dtype == DT_F16;
   if (a.nphase != 0) {   // the parity phases of a ConvTranspose in one launch
-    if (a.nphase != 4 || a.ostride != 2 || a.Npad % CP_BN || a.out == nullptr) return hipErrorNotSupported;
-    CvpArgs g;
-    int nt[4];
+    if (a.nphase != 4 || a.ostride != 2 || a.Npad % CP_BN || a.out == nullptr) return false;
+    int nt[4], dy4[4], dx4[4];
     for (int ph = 0; ph < 4; ++ph) {
       nt[ph] = a.ph_ntaps[ph];
-      int dy0, dx0;
-      if ((nt[ph] != 1 && nt[ph] != 2 && nt[ph] != 4) || a.ph_wpack[ph] == nullptr || !cvp_tap_box(a.ph_taps0[ph], nt[ph], dy0, dx0) ||
+      if ((nt[ph] != 1 && nt[ph] != 2 && nt[ph] != 4) || a.ph_wpack[ph] == nullptr || !cvp_tap_box(a.ph_taps0[ph], nt[ph], dy4[ph], dx4[ph]) ||
           a.ph_py[ph] < 0 || a.ph_py[ph] > 1 || a.ph_px[ph] < 0 || a.ph_px[ph] > 1)
-        return hipErrorNotSupported;
-      g.ph_dymin[ph] = (signed char)dy0; g.ph_dxmin[ph] = (signed char)dx0;
+        return false;
     }
-    if (g_ctl.dry) return hipSuccess;
-    if (g_cvw) {
-      const int dy4[4] = {g.ph_dymin[0], g.ph_dymin[1], g.ph_dymin[2], g.ph_dymin[3]}, dx4[4] = {g.ph_dxmin[0], g.ph_dxmin[1], g.ph_dxmin[2], g.ph_dxmin[3]};
-      const hipError_t e = launch_cvw(a, dtype, dy4, dx4, st);
-      if (e != hipErrorNotSupported) return e;
-    }
-    g.c = a;
+    if (g_cvw && cvw_resolve(a, dtype, dy4, dx4, r)) { r.form = IMPL_CVW; return true; }
+    LdsLaunch<CvpArgs>& l = r.put<LdsLaunch<CvpArgs>>();
+    CvpArgs& g = l.g;
+    for (int ph = 0; ph < 4; ++ph) { g.ph_dymin[ph] = (signed char)dy4[ph]; g.ph_dxmin[ph] = (signed char)dx4[ph]; }
+    cvp_tiles(a, g);
     g.dymin = g.dxmin = 0;
-    g.tiles_y = (a.Ho + CP_TH - 1) / CP_TH;
-    g.tiles_x = (a.Wo + CP_TW - 1) / CP_TW;
-    g.ntn = a.Npad / CP_BN;
     g.per = a.B * g.tiles_y * g.tiles_x * g.ntn;
     g.per8 = (g.per + 7) / 8;
     int idx[4] = {0, 1, 2, 3};
     std::stable_sort(idx, idx + 4, [&](int p, int q) { return nt[p] > nt[q]; });   // most taps first
     for (int k = 0; k < 4; ++k) g.order[k] = (signed char)idx[k];
-    const int nwg = 8 * g.per8 * 4;
-    return dtype == DT_F16 ? launch_cvp_multi_t<f16>(g, nwg, st) : launch_cvp_multi_t<bf16>(g, nwg, st);
+    l.nwg = 8 * g.per8 * 4;
+    l.nthreads = NTHREADS;
+    l.attr_bytes = l.lds = CP_LDS;
+    l.run = f16t ? launch_lds<cvp_multi_kernel<f16>, CvpArgs> : launch_lds<cvp_multi_kernel<bf16>, CvpArgs>;
+    return true;
   }
-  if (x.ntaps != 1 && x.ntaps != 2 && x.ntaps != 4) return hipErrorNotSupported;
-  if (x.ntaps == 1 && a.ostride == 1) return hipErrorNotSupported;  // plain 1x1 convolutions stay with igemm's lean path
-  if (a.Npad % CP_BN || a.out == nullptr) return hipErrorNotSupported;
-  int dymin = 127, dxmin = 127, dymax = -128, dxmax = -128;
-  for (int t = 0; t < x.ntaps; ++t) {
-    const int dy = (int)(signed char)(x.taps[t] & 0xff), dx = (int)(signed char)((x.taps[t] >> 8) & 0xff);
-    dymin = dy < dymin ? dy : dymin; dymax = dy > dymax ? dy : dymax; dxmin = dx < dxmin ? dx : dxmin; dxmax = dx > dxmax ? dx : dxmax;
-  }
-  if (dymax - dymin > 1 || dxmax - dxmin > 1) return hipErrorNotSupported;
-  if (g_ctl.dry) return hipSuccess;
+  if (x.ntaps != 1 && x.ntaps != 2 && x.ntaps != 4) return false;
+  if (x.ntaps == 1 && a.ostride == 1) return false;  // plain 1x1 convolutions stay with igemm's lean path
+  if (a.Npad % CP_BN || a.out == nullptr) return false;
+  int dymin, dxmin;
+  if (!cvp_tap_box(x.taps, x.ntaps, dymin, dxmin)) return false;
   if (g_cvw && a.ostride == 2) {
     const int dy4[4] = {dymin, 0, 0, 0}, dx4[4] = {dxmin, 0, 0, 0};
-    const hipError_t e = launch_cvw(a, dtype, dy4, dx4, st);
-    if (e != hipErrorNotSupported) return e;
+    if (cvw_resolve(a, dtype, dy4, dx4, r)) { r.form = IMPL_CVW; return true; }
   }
-  CvpArgs g;
-  g.c = a;
+  LdsLaunch<CvpArgs>& l = r.put<LdsLaunch<CvpArgs>>();
+  CvpArgs& g = l.g;
+  cvp_tiles(a, g);
   g.dymin = dymin; g.dxmin = dxmin;
-  g.tiles_y = (a.Ho + CP_TH - 1) / CP_TH;
-  g.tiles_x = (a.Wo + CP_TW - 1) / CP_TW;
-  g.ntn = a.Npad / CP_BN;
-  const int nwg = a.B * g.tiles_y * g.tiles_x * g.ntn;
-  if (dtype == DT_F16) return x.ntaps == 4 ? launch_cvp_t<f16, 4>(g, nwg, st) : (x.ntaps == 2 ? launch_cvp_t<f16, 2>(g, nwg, st) : launch_cvp_t<f16, 1>(g, nwg, st));
-  return x.ntaps == 4 ? launch_cvp_t<bf16, 4>(g, nwg, st) : (x.ntaps == 2 ? launch_cvp_t<bf16, 2>(g, nwg, st) : launch_cvp_t<bf16, 1>(g, nwg, st));
-}
-
-template <typename T, bool UP2>
-static hipError_t launch_cvd3_t(const CvdArgs& g, int nwg, hipStream_t st) {
-  auto kern = cvd3_kernel<T, UP2>;
-  static bool attr_done = false;
-  if (!attr_done) {
-    const hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, C3D_LDS);
-    if (e != hipSuccess) return e;
-    attr_done = true;
+  l.nwg = a.B * g.tiles_y * g.tiles_x * g.ntn;
+  l.nthreads = NTHREADS;
+  l.attr_bytes = l.lds = CP_LDS;
+  if (f16t) {
+    if (x.ntaps == 4) l.run = launch_lds<cvp_kernel<f16, 4>, CvpArgs>;
+    else if (x.ntaps == 2) l.run = launch_lds<cvp_kernel<f16, 2>, CvpArgs>;
+    else l.run = launch_lds<cvp_kernel<f16, 1>, CvpArgs>;
+  } else {
+    if (x.ntaps == 4) l.run = launch_lds<cvp_kernel<bf16, 4>, CvpArgs>;
+    else if (x.ntaps == 2) l.run = launch_lds<cvp_kernel<bf16, 2>, CvpArgs>;
+    else l.run = launch_lds<cvp_kernel<bf16, 1>, CvpArgs>;
   }
-  hipLaunchKernelGGL(kern, dim3(nwg), dim3(NTHREADS), C3D_LDS, st, g);
-  return hipGetLastError();
-}
-
-template <typename T, int CA, bool UP2>
-static hipError_t launch_cvd_t(const CvdArgs& g, int nwg, hipStream_t st) {
-  auto kern = cvd_kernel<T, CA, UP2>;
-  static bool attr_done = false;
-  if (!attr_done) {
-    const hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, CP_LDS);
-    if (e != hipSuccess) return e;
-    attr_done = true;
-  }
-  hipLaunchKernelGGL(kern, dim3(nwg), dim3(NTHREADS), CP_LDS, st, g);
-  return hipGetLastError();
+  return true;
 }
 
 // Stride-2 data gradients with the fused BN+ReLU backward (EPI_BNBWD): one plain segment (the materialised output gradient), the
 // gradient stored (not only reduced), a multiple of 128 output columns, and either the ConvTranspose's nine taps (-1..1)^2 over
 // a multiple of 128 channels or the upsampled 3x3's sixteen merged taps (-1..2)^2 over 64 channels.
-static hipError_t launch_cvd(const ConvArgs& a, int dtype, hipStream_t st) {
+static bool cvd_resolve(const ConvArgs& a, int dtype, Resolved& r) {
   const Seg& y = a.seg[0];
-  if (a.nseg != 1 || a.pool2 || y.mode != G_PLAIN || y.istride != 2 || y.scale != nullptr || y.q != nullptr) return hipErrorNotSupported;
+  if (a.nseg != 1 || a.pool2 || y.mode != G_PLAIN || y.istride != 2 || y.scale != nullptr || y.q != nullptr) return false;
   const bool up2 = y.ntaps == 16;
-  if (!up2 && y.ntaps != 9) return hipErrorNotSupported;
-  if (y.Hs != 2 * a.Ho || y.Ws != 2 * a.Wo || y.Cpad != y.C || (up2 ? y.C != 64 : y.C % CP_CA != 0)) return hipErrorNotSupported;
-  if (a.Npad % CP_BN || a.out == nullptr || a.bx == nullptr || a.ostride != 1 || a.Hout != a.Ho || a.Wout != a.Wo) return hipErrorNotSupported;
-  CvdArgs g;
+  if (!up2 && y.ntaps != 9) return false;
+  if (y.Hs != 2 * a.Ho || y.Ws != 2 * a.Wo || y.Cpad != y.C || (up2 ? y.C != 64 : y.C % CP_CA != 0)) return false;
+  if (a.Npad % CP_BN || a.out == nullptr || a.bx == nullptr || a.ostride != 1 || a.Hout != a.Ho || a.Wout != a.Wo) return false;
+  LdsLaunch<CvdArgs>& l = r.put<LdsLaunch<CvdArgs>>();
+  CvdArgs& g = l.g;
   int cnt[4] = {0, 0, 0, 0};
   const int base9[4] = {0, 1, 3, 5}, base16[4] = {0, 4, 8, 12};
   for (int t = 0; t < y.ntaps; ++t) {
     const int dy = (int)(signed char)(y.taps[t] & 0xff), dx = (int)(signed char)((y.taps[t] >> 8) & 0xff);
-    if (dy < -1 || dx < -1 || dy > (up2 ? 2 : 1) || dx > (up2 ? 2 : 1)) return hipErrorNotSupported;
+    if (dy < -1 || dx < -1 || dy > (up2 ? 2 : 1) || dx > (up2 ? 2 : 1)) return false;
     const int cls = (dy & 1) * 2 + (dx & 1);
     const int cap = up2 ? 4 : (cls == 0 ? 1 : (cls == 3 ? 4 : 2));
-    if (cnt[cls] >= cap) return hipErrorNotSupported;
+    if (cnt[cls] >= cap) return false;
     g.tapidx[(up2 ? base16 : base9)[cls] + cnt[cls]++] = t;
   }
-  if (g_ctl.dry) return hipSuccess;
-  g.c = a;
-  g.tiles_y = (a.Ho + CP_TH - 1) / CP_TH;
-  g.tiles_x = (a.Wo + CP_TW - 1) / CP_TW;
-  g.ntn = a.Npad / CP_BN;
-  const int nwg = a.B * g.tiles_y * g.tiles_x * g.ntn;
+  cvp_tiles(a, g);
+  l.nwg = a.B * g.tiles_y * g.tiles_x * g.ntn;
+  l.nthreads = NTHREADS;
   static const bool three = !lab_flag("DMM_NO_CVD3");
   static const bool three_ct = !lab_flag("DMM_NO_CVD3_CT");
-  if (up2 && three) return dtype == DT_F16 ? launch_cvd3_t<f16, true>(g, nwg, st) : launch_cvd3_t<bf16, true>(g, nwg, st);
-  if (!up2 && three && three_ct) return dtype == DT_F16 ? launch_cvd3_t<f16, false>(g, nwg, st) : launch_cvd3_t<bf16, false>(g, nwg, st);
-  if (up2) return dtype == DT_F16 ? launch_cvd_t<f16, 64, true>(g, nwg, st) : launch_cvd_t<bf16, 64, true>(g, nwg, st);
-  return dtype == DT_F16 ? launch_cvd_t<f16, 128, false>(g, nwg, st) : launch_cvd_t<bf16, 128, false>(g, nwg, st);
+  const bool f16t = dtype == DT_F16;
+  l.attr_bytes = l.lds = CP_LDS;
+  if (up2 && three) { l.attr_bytes = l.lds = C3D_LDS; l.run = f16t ? launch_lds<cvd3_kernel<f16, true>, CvdArgs> : launch_lds<cvd3_kernel<bf16, true>, CvdArgs>; }
+  else if (!up2 && three && three_ct) { l.attr_bytes = l.lds = C3D_LDS; l.run = f16t ? launch_lds<cvd3_kernel<f16, false>, CvdArgs> : launch_lds<cvd3_kernel<bf16, false>, CvdArgs>; }
+  else if (up2) l.run = f16t ? launch_lds<cvd_kernel<f16, 64, true>, CvdArgs> : launch_lds<cvd_kernel<bf16, 64, true>, CvdArgs>;
+  else l.run = f16t ? launch_lds<cvd_kernel<f16, 128, false>, CvdArgs> : launch_lds<cvd_kernel<bf16, 128, false>, CvdArgs>;
+  r.form = CVP_FORM_CVD;
+  return true;
 }
 
-bool cvp_handles(const ConvArgs& a, int dtype, int epi) {
-  const LaunchCtl keep = g_ctl;
-  g_ctl.dry = true;
-  const hipError_t e = launch_cvp(a, dtype, epi, nullptr);
-  g_ctl = keep;
-  return e == hipSuccess;
+hipError_t cvp_launch(const Resolved& r, hipStream_t st) {
+  if (r.form == IMPL_CVW) {
+    note_impl(IMPL_CVW);   // (beside IMPL_CVP, which the dispatcher notes: the family is cvp, this says which form ran)
+    return cvw_launch(r, st);
+  }
+  return r.form == CVP_FORM_CVD ? r.get<LdsLaunch<CvdArgs>>().go(st) : r.get<LdsLaunch<CvpArgs>>().go(st);
 }
 
 }  // namespace dmm

@@ -24,6 +24,7 @@
 #include <cstdlib>
 
 #include "common.h"
+#include "dispatch.h"
 #include "gather.h"
 
 #ifndef CW_DBG
@@ -367,35 +368,22 @@ __global__ __launch_bounds__(CW_NT, 1) void cvw_kernel(const CvwArgs g) {
   }
 }
 
-template <typename T>
-static hipError_t launch_cvw_t(const CvwArgs& g, int nwg, hipStream_t st) {
-  auto kern = cvw_kernel<T>;
-  static bool attr_done = false;
-  if (!attr_done) {
-    const hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e != hipSuccess) return e;
-    attr_done = true;
-  }
-  const int lds = CW_OFF_K + 8 * g.c.seg[0].C;
-  hipLaunchKernelGGL(kern, dim3(nwg), dim3(CW_NT), lds, st, g);
-  return hipGetLastError();
-}
-
-// Called by launch_cvp (cvp.hip) with a forward launch it has validated: one plain BN+ReLU segment of a multiple of 128 channels on the
+// Asked by cvp_resolve (cvp.hip) with a forward launch it has validated: one plain BN+ReLU segment of a multiple of 128 channels on the
 // row grid, a multiple of 128 padded output columns, 1 / 2 / 4 taps per phase inside a 2 x 2 box, output stride 2.  nphase = 0: the
-// launch's own taps / weights / parity; 4: ConvArgs::ph_*.  Returns hipErrorNotSupported for what this form does not cover.
-hipError_t launch_cvw(const ConvArgs& a, int dtype, const int* ph_dymin, const int* ph_dxmin, hipStream_t st) {
+// launch's own taps / weights / parity; 4: ConvArgs::ph_*.  Refuses what this form does not cover (cvp.hip's own kernels run then).
+bool cvw_resolve(const ConvArgs& a, int dtype, const int* ph_dymin, const int* ph_dxmin, Resolved& r) {
   const Seg& x = a.seg[0];
-  if ((double)a.B * x.Hs * x.Ws * x.ld * 2.0 >= 4294967296.0) return hipErrorNotSupported;          // 32-bit byte offsets in the loaders
-  if ((double)x.Cpad / 32 * 4 * a.Npad * 64.0 >= 4294967296.0 || x.C > CW_MAX_C) return hipErrorNotSupported;
+  if ((double)a.B * x.Hs * x.Ws * x.ld * 2.0 >= 4294967296.0) return false;          // 32-bit byte offsets in the loaders
+  if ((double)x.Cpad / 32 * 4 * a.Npad * 64.0 >= 4294967296.0 || x.C > CW_MAX_C) return false;
   // Measured (round 5, C2's four stages, ms alone, cvp.hip -> this kernel): 128 channels @320x480 0.47 -> 0.36, 256 @160x240 0.30 -> 0.30,
   // 512 @80x120 0.26 -> 0.28, 1024 @40x60 0.24 -> 0.27.  With many channel groups per tile the four loader waves' halo prologue (10 slots
   // x ~25 instructions per group, in front of the group's first barrier) sets the pace - ablations in profiles/r05/ablations.txt: without ANY
   // global request the deep stages take 0.25 ms, with idle matrix waves 0.19 - where cvp.hip's two workgroups per CU share that work
   // among eight waves.  So: the stages with one or two channel groups; DMM_CVW_MAX_GROUPS (lab) moves the limit.
   static const int max_groups = lab_int("DMM_CVW_MAX_GROUPS", 2);
-  if (x.C / CW_CA > max_groups) return hipErrorNotSupported;
-  CvwArgs g;
+  if (x.C / CW_CA > max_groups) return false;
+  LdsLaunch<CvwArgs>& l = r.put<LdsLaunch<CvwArgs>>();
+  CvwArgs& g = l.g;
   g.c = a;
   g.tiles_y = (a.Ho + CW_TH - 1) / CW_TH;
   g.tiles_x = (a.Wo + CW_TW - 1) / CW_TW;
@@ -416,12 +404,17 @@ hipError_t launch_cvw(const ConvArgs& a, int dtype, const int* ph_dymin, const i
       for (int t = 0; t < 4; ++t) P.taps[t] = x.taps[t < x.ntaps ? t : 0];
     }
     P.dymin = ph_dymin[p]; P.dxmin = ph_dxmin[p];
-    if (P.ntaps != 1 && P.ntaps != 2 && P.ntaps != 4) return hipErrorNotSupported;
+    if (P.ntaps != 1 && P.ntaps != 2 && P.ntaps != 4) return false;
   }
   for (int k = g.nphase; k < 4; ++k) g.ph[k] = g.ph[0];
-  const int nwg = std::min(DESIGN_CUS, g.per * g.nphase);
-  note_impl(IMPL_CVW);   // (beside IMPL_CVP, which the dispatcher notes: the family is cvp, this says which form ran)
-  return dtype == DT_F16 ? launch_cvw_t<f16>(g, nwg, st) : launch_cvw_t<bf16>(g, nwg, st);
+  l.nwg = std::min(DESIGN_CUS, g.per * g.nphase);
+  l.nthreads = CW_NT;
+  l.attr_bytes = 160 * 1024;
+  l.lds = CW_OFF_K + 8 * x.C;
+  l.run = dtype == DT_F16 ? launch_lds<cvw_kernel<f16>, CvwArgs> : launch_lds<cvw_kernel<bf16>, CvwArgs>;
+  return true;
 }
+
+hipError_t cvw_launch(const Resolved& r, hipStream_t st) { return r.get<LdsLaunch<CvwArgs>>().go(st); }
 
 }  // namespace dmm

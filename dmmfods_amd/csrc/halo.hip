@@ -13,6 +13,7 @@
 #include <cstring>
 
 #include "common.h"
+#include "dispatch.h"
 #include "gather.h"
 
 namespace dmm {
@@ -346,16 +347,7 @@ __global__ __launch_bounds__(NTHREADS) void halo_kernel(const HaloArgs h) {
 }
 
 // ------------------------------------------------------------------------------------------------ host side
-static int halo_cus() {
-  static int n = 0;
-  if (!n) {
-    hipDeviceProp_t p;
-    int dev = 0;
-    hipGetDevice(&dev);
-    n = (hipGetDeviceProperties(&p, dev) == hipSuccess && p.multiProcessorCount > 0) ? p.multiProcessorCount : 256;
-  }
-  return n;
-}
+static int halo_cus() { static const int n = device_cus(); return n; }
 
 // Fills `h`; returns false when the layer does not fit the halo kernel (caller falls back to igemm).
 static bool halo_plan(const ConvArgs& a, int dtype, int epi, HaloArgs& h) {
@@ -418,6 +410,10 @@ static bool halo_plan(const ConvArgs& a, int dtype, int epi, HaloArgs& h) {
   return h.ntiles > 0;
 }
 
+// The launcher of one (storage type, column tile, epilogue) instantiation: what halo_resolve hands to halo_launch beside the kernel's
+// arguments.  It picks the slots-per-thread variant, raises its LDS limit (every time: four kernels share the launcher) and launches.
+typedef hipError_t (*HaloInst)(const HaloArgs& h, hipStream_t st);
+
 template <typename T, int BN, int EPI, bool EFF>
 static hipError_t launch_halo_ns(const HaloArgs& h, hipStream_t st) {
   const int ns = (h.nsl_total + NTHREADS - 1) / NTHREADS;
@@ -435,45 +431,55 @@ static hipError_t launch_halo_ns(const HaloArgs& h, hipStream_t st) {
   return go(halo_kernel<T, BN, EPI, EFF, HALO_MAX_NS>);
 }
 
-// Variants built: forward (EPI_STORE) for N <= 64, logits for N <= 32, data gradients for N <= 128.
+// Variants built: forward (EPI_STORE) for N <= 64, logits for N <= 32, data gradients for N <= 128 (nullptr: none for this width).
 template <typename T>
-static hipError_t launch_halo_type(const HaloArgs& h, int epi, hipStream_t st) {
-  const int bn = h.c.Npad;
+static HaloInst halo_instance(int bn, int epi) {
   if (epi == EPI_STORE) {
-    if (bn == 64) return launch_halo_ns<T, 64, EPI_STORE, false>(h, st);
-    if (bn == 32) return launch_halo_ns<T, 32, EPI_STORE, false>(h, st);
+    if (bn == 64) return launch_halo_ns<T, 64, EPI_STORE, false>;
+    if (bn == 32) return launch_halo_ns<T, 32, EPI_STORE, false>;
   } else if (epi == EPI_LOGITS) {
-    if (bn == 32) return launch_halo_ns<T, 32, EPI_LOGITS, false>(h, st);
+    if (bn == 32) return launch_halo_ns<T, 32, EPI_LOGITS, false>;
   } else {
-    if (bn == 128) return launch_halo_ns<T, 128, EPI_BNBWD, true>(h, st);
-    if (bn == 64) return launch_halo_ns<T, 64, EPI_BNBWD, true>(h, st);
-    if (bn == 32) return launch_halo_ns<T, 32, EPI_BNBWD, true>(h, st);
+    if (bn == 128) return launch_halo_ns<T, 128, EPI_BNBWD, true>;
+    if (bn == 64) return launch_halo_ns<T, 64, EPI_BNBWD, true>;
+    if (bn == 32) return launch_halo_ns<T, 32, EPI_BNBWD, true>;
   }
-  return hipErrorNotSupported;
+  return nullptr;
 }
 
 #if defined(HALO_F32_PART)
-hipError_t launch_halo_f32(const HaloArgs& h, int epi, hipStream_t st) { return launch_halo_type<float>(h, epi, st); }
+HaloInst halo_instance_f32(int bn, int epi) { return halo_instance<float>(bn, epi); }
 #else
-hipError_t launch_halo_f32(const HaloArgs& h, int epi, hipStream_t st);  // halo32.o (same source, -DHALO_F32_PART)
+HaloInst halo_instance_f32(int bn, int epi);  // halo32.o (same source, -DHALO_F32_PART)
 
-// Returns hipErrorNotSupported when the layer is not eligible.
-hipError_t launch_halo(const ConvArgs& a, int dtype, int epi, hipStream_t st) {
+struct HaloLaunch {
   HaloArgs h;
-  static const bool no_halo = lab_flag("DMM_NO_HALO");
-  if (!family_on(!no_halo, IMPL_HALO) || dtype == DT_BF16) return hipErrorNotSupported;  // bf16 layers take the generic / thin kernels
-  if (a.pool2 || !halo_plan(a, dtype, epi, h)) return hipErrorNotSupported;
-  if (epi != EPI_BNBWD && a.seg[0].q != nullptr) return hipErrorNotSupported;
-  if (epi == EPI_STORE && a.Npad > 64) return hipErrorNotSupported;
-  if (epi == EPI_LOGITS && a.Npad > 32) return hipErrorNotSupported;
+  HaloInst run;
+};
+
+bool halo_enabled() { static const bool no_halo = lab_flag("DMM_NO_HALO"); return !no_halo; }
+
+// Multi-tap layers whose weights fit in LDS (fp32 / f16).  Refused when the layer is not eligible.
+bool halo_resolve(const ConvArgs& a, int dtype, int epi, Resolved& r) {
+  HaloLaunch& l = r.put<HaloLaunch>();
+  HaloArgs& h = l.h;
+  if (dtype == DT_BF16) return false;  // bf16 layers take the generic / thin kernels
+  if (a.pool2 || !halo_plan(a, dtype, epi, h)) return false;
+  if (epi != EPI_BNBWD && a.seg[0].q != nullptr) return false;
+  if (epi == EPI_STORE && a.Npad > 64) return false;
+  if (epi == EPI_LOGITS && a.Npad > 32) return false;
   // Measured on MI355X (C2, b4): with one wave per SIMD the tile phases of this kernel do not overlap yet, so it only beats
   // the generic kernel (2-3 workgroups per CU) where the tap count is large: the 5x5 logits conv (7.9 -> 4.3 ms).  The
   // other eligible layers stay on igemm unless DMM_HALO_ALL is set.
   static const bool all = lab_flag("DMM_HALO_ALL");
-  if (!all && epi != EPI_LOGITS) return hipErrorNotSupported;
-  if (g_ctl.dry) return (epi == EPI_STORE && (h.c.Npad == 64 || h.c.Npad == 32)) || (epi == EPI_LOGITS && h.c.Npad == 32) ||
-                        (epi == EPI_BNBWD && (h.c.Npad == 128 || h.c.Npad == 64 || h.c.Npad == 32)) ? hipSuccess : hipErrorNotSupported;
-  return dtype == DT_F16 ? launch_halo_type<f16>(h, epi, st) : launch_halo_f32(h, epi, st);
+  if (!all && epi != EPI_LOGITS) return false;
+  l.run = dtype == DT_F16 ? halo_instance<f16>(h.c.Npad, epi) : halo_instance_f32(h.c.Npad, epi);
+  return l.run != nullptr;
+}
+
+hipError_t halo_launch(const Resolved& r, hipStream_t st) {
+  const HaloLaunch& l = r.get<HaloLaunch>();
+  return l.run(l.h, st);
 }
 #endif
 

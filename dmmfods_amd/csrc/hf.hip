@@ -29,6 +29,7 @@
 #include <cstdlib>
 
 #include "common.h"
+#include "dispatch.h"
 #include "gather.h"
 
 #ifndef HF_DBG
@@ -336,20 +337,6 @@ __global__ __launch_bounds__(HF_NT, 2) void hf_kernel(const HfArgs g) {
   }
 }
 
-template <typename T>
-static hipError_t launch_hf_t(const HfArgs& g, int nwg, hipStream_t st) {
-  auto kern = hf_kernel<T>;
-  const int lds = H2_LDS;
-  static bool attr_done = false;
-  if (!attr_done) {
-    const hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    if (e != hipSuccess) return e;
-    attr_done = true;
-  }
-  hipLaunchKernelGGL(kern, dim3(nwg), dim3(HF_NT), lds, st, g);
-  return hipGetLastError();
-}
-
 static bool hf_tap_box(const short* taps, int ntaps, int want_span, int& dymin, int& dxmin) {
   int dymax = -128, dxmax = -128;
   dymin = 127; dxmin = 127;
@@ -367,38 +354,43 @@ static bool hf_tap_box(const short* taps, int ntaps, int want_span, int& dymin, 
   return true;
 }
 
+bool hf_enabled() { return true; }   // (DMM_NO_HF is a plan's switch: PlanSwitches::no_hf, plan.h - it reaches igemm_pick as `deny`)
+
 // Takes the four-phase forward launch of the head's first convolution (ConvArgs::nphase = 4): a 128-channel BN+ReLU-normalised
 // half-resolution segment with 2x2 taps per phase, an 8-channel raw segment with 3x3 taps at stride 2, 64 output channels stored at
-// stride 2, whole 8 x 16 tiles, 16-bit storage.  hipErrorNotSupported otherwise (conv3.hip takes the launch then).
-hipError_t launch_hf(const ConvArgs& a, int dtype, int epi, hipStream_t st) {
-  // (DMM_NO_HF: read when a plan is created - PlanSwitches::no_hf, plan.h - and applied through g_ctl.deny while it is built)
-  if (!family_on(true, IMPL_HF) || dtype == DT_F32 || epi != EPI_STORE || a.nphase != 4 || a.nseg != 2 || a.pool2) return hipErrorNotSupported;
+// stride 2, whole 8 x 16 tiles, 16-bit storage.  Refused otherwise (conv3.hip takes the launch then).
+bool hf_resolve(const ConvArgs& a, int dtype, int epi, Resolved& r) {
+  if (dtype == DT_F32 || epi != EPI_STORE || a.nphase != 4 || a.nseg != 2 || a.pool2) return false;
   const Seg& u = a.seg[0];
   const Seg& t = a.seg[1];
-  if (u.mode != G_PLAIN || u.istride != 1 || u.C != 128 || u.Cpad != 128 || u.Hs != a.Ho || u.Ws != a.Wo || u.scale == nullptr || u.ntaps != 4) return hipErrorNotSupported;
-  if (t.mode != G_PLAIN || t.istride != 2 || t.C != 8 || t.Cpad != 8 || t.Hs != 2 * a.Ho || t.Ws != 2 * a.Wo || t.scale == nullptr || t.ntaps != 9 || t.q != nullptr) return hipErrorNotSupported;
-  if (a.N != HF_BN || a.Npad != HF_BN || a.out == nullptr || a.ostride != 2 || a.Hout != 2 * a.Ho || a.Wout != 2 * a.Wo) return hipErrorNotSupported;
-  if (a.Ho % HF_TH || a.Wo % HF_TW || a.ldo % 8) return hipErrorNotSupported;
-  if (2.0 * a.B * u.Hs * u.Ws * u.ld >= 4294967296.0 || 2.0 * a.B * t.Hs * t.Ws * t.ld >= 4294967296.0) return hipErrorNotSupported;   // 32-bit byte offsets
-  HfArgs g;
+  if (u.mode != G_PLAIN || u.istride != 1 || u.C != 128 || u.Cpad != 128 || u.Hs != a.Ho || u.Ws != a.Wo || u.scale == nullptr || u.ntaps != 4) return false;
+  if (t.mode != G_PLAIN || t.istride != 2 || t.C != 8 || t.Cpad != 8 || t.Hs != 2 * a.Ho || t.Ws != 2 * a.Wo || t.scale == nullptr || t.ntaps != 9 || t.q != nullptr) return false;
+  if (a.N != HF_BN || a.Npad != HF_BN || a.out == nullptr || a.ostride != 2 || a.Hout != 2 * a.Ho || a.Wout != 2 * a.Wo) return false;
+  if (a.Ho % HF_TH || a.Wo % HF_TW || a.ldo % 8) return false;
+  if (2.0 * a.B * u.Hs * u.Ws * u.ld >= 4294967296.0 || 2.0 * a.B * t.Hs * t.Ws * t.ld >= 4294967296.0) return false;   // 32-bit byte offsets
+  LdsLaunch<HfArgs>& l = r.put<LdsLaunch<HfArgs>>();
+  HfArgs& g = l.g;
   for (int ph = 0; ph < 4; ++ph) {
     int y0, x0, y1, x1;
     if (a.ph_wpack[ph] == nullptr || !hf_tap_box(a.ph_taps0[ph], 4, 1, y0, x0) || !hf_tap_box(a.ph_taps1[ph], 9, 2, y1, x1) ||
         a.ph_py[ph] < 0 || a.ph_py[ph] > 1 || a.ph_px[ph] < 0 || a.ph_px[ph] > 1)
-      return hipErrorNotSupported;
+      return false;
     g.ph_dymin0[ph] = (signed char)y0; g.ph_dxmin0[ph] = (signed char)x0; g.ph_dymin1[ph] = (signed char)y1; g.ph_dxmin1[ph] = (signed char)x1;
   }
-  if (g_ctl.dry) return hipSuccess;
   g.c = a;
   g.tiles_y = a.Ho / HF_TH;
   g.tiles_x = a.Wo / HF_TW;
   g.ntiles = a.B * g.tiles_y * g.tiles_x;
   // one workgroup per CU (152 KB of LDS), in whole groups of 4 phases x 8 XCDs; launches with fewer tile groups than that: one item each
   static const int cus = lab_int("DMM_HF_WGS", DESIGN_CUS);
-  int nwg = std::max(32, cus / 32 * 32);
   const int need = (g.ntiles + 7) / 8 * 32;   // ntiles groups rounded up to whole XCD rows
-  nwg = std::min(nwg, need);
-  return dtype == DT_F16 ? launch_hf_t<f16>(g, nwg, st) : launch_hf_t<bf16>(g, nwg, st);
+  l.nwg = std::min(std::max(32, cus / 32 * 32), need);
+  l.attr_bytes = l.lds = H2_LDS;
+  l.nthreads = HF_NT;
+  l.run = dtype == DT_F16 ? launch_lds<hf_kernel<f16>, HfArgs> : launch_lds<hf_kernel<bf16>, HfArgs>;
+  return true;
 }
+
+hipError_t hf_launch(const Resolved& r, hipStream_t st) { return r.get<LdsLaunch<HfArgs>>().go(st); }
 
 }  // namespace dmm

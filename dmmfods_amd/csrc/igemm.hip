@@ -30,6 +30,7 @@
 #define IGEMM_F32_FOLD 0  // experiment builds only: the lane-swap fold in the fp32 instantiations too (see the comment at the fold)
 #endif
 #include "common.h"
+#include "dispatch.h"
 #include "gather.h"
 
 namespace dmm {
@@ -759,14 +760,6 @@ static hipError_t launch_epi(const ConvArgs& a, bool mfma, hipStream_t st) {
   return launch_bn<T, 32, EPI>(a, mfma, st);
 }
 
-hipError_t launch_halo(const ConvArgs& a, int dtype, int epi, hipStream_t st);  // halo.hip
-hipError_t launch_thin_logits(const ConvArgs& a, int dtype, int epi, hipStream_t st);  // thin.hip
-hipError_t launch_conv3(const ConvArgs& a, int dtype, int epi, hipStream_t st);        // conv3.hip
-hipError_t launch_cvp(const ConvArgs& a, int dtype, int epi, hipStream_t st);          // cvp.hip
-hipError_t launch_hf(const ConvArgs& a, int dtype, int epi, hipStream_t st);           // hf.hip
-hipError_t launch_cf(const ConvArgs& a, int dtype, int epi, hipStream_t st);           // cf.hip
-hipError_t launch_pig(const ConvArgs& a, int dtype, int epi, hipStream_t st);          // pig.hip
-
 // One translation unit per storage type (IGEMM_PART = 0 fp32, 1 f16, 2 bf16; see the Makefile): the ~50 kernel instantiations
 // of a type compile in parallel with the other types'.
 template <typename T>
@@ -789,31 +782,25 @@ template hipError_t launch_igemm_type<bf16>(const ConvArgs&, int, bool, hipStrea
 extern template hipError_t launch_igemm_type<float>(const ConvArgs&, int, bool, hipStream_t);
 extern template hipError_t launch_igemm_type<bf16>(const ConvArgs&, int, bool, hipStream_t);
 
-// The special-case families in dispatch order; `took` = the family that accepted the launch (IMPL_GENERIC: none did).
-static hipError_t dispatch_special(const ConvArgs& a, int dtype, int epi, hipStream_t st, int& took) {
-  hipError_t e;
-  if (a.eq != nullptr || a.er != nullptr) {  // second pass of a two-pass BatchNorm backward: ONE kernel variant stores s*dz + q + r*x
-    took = IMPL_CONV3;                       // (conv3.hip's thin-only data gradient); every other family would silently store s*dz
-    if ((e = launch_conv3(a, dtype, epi, st)) != hipErrorNotSupported) return e;
-    took = IMPL_GENERIC;
-    return hipErrorNotSupported;
-  }
-  took = IMPL_THIN;   // few output channels x many taps: gather once, reduce the taps in LDS
-  if ((e = launch_thin_logits(a, dtype, epi, st)) != hipErrorNotSupported) return e;
-  took = IMPL_HF;     // the head's first convolution, four parity phases in one launch: wave-specialised, phase weights resident in LDS
-  if ((e = launch_hf(a, dtype, epi, st)) != hipErrorNotSupported) return e;
-  took = IMPL_CF;     // the dense 3x3 forward on the large maps: wave-specialised, weights resident in LDS
-  if ((e = launch_cf(a, dtype, epi, st)) != hipErrorNotSupported) return e;
-  took = IMPL_CONV3;  // 3x3 convolutions of the dense layers (16-bit storage): LDS halo tile, prologue once per element
-  if ((e = launch_conv3(a, dtype, epi, st)) != hipErrorNotSupported) return e;
-  took = IMPL_CVP;    // forward of the ConvTranspose parity phases: halo tile per 128-channel group, a tap is a fragment address
-  if ((e = launch_cvp(a, dtype, epi, st)) != hipErrorNotSupported) return e;
-  took = IMPL_PIG;    // plain 1x1 convolutions, forward: persistent workgroups (next tile's loads under this tile's epilogue)
-  if ((e = launch_pig(a, dtype, epi, st)) != hipErrorNotSupported) return e;
-  took = IMPL_HALO;   // multi-tap layers whose weights fit in LDS may take the halo-tile kernel
-  if ((e = launch_halo(a, dtype, epi, st)) != hipErrorNotSupported) return e;
-  took = IMPL_GENERIC;
-  return hipErrorNotSupported;
+// The special-case families in dispatch order.
+static const ConvFamily kConvFamilies[] = {
+    {IMPL_THIN, thin_enabled, thin_resolve, thin_launch},      // few output channels x many taps: gather once, reduce the taps in LDS
+    {IMPL_HF, hf_enabled, hf_resolve, hf_launch},              // the head's first convolution, four parity phases in one launch: wave-specialised, phase weights resident in LDS
+    {IMPL_CF, cf_enabled, cf_resolve, cf_launch},              // the dense 3x3 forward on the large maps: wave-specialised, weights resident in LDS
+    {IMPL_CONV3, conv3_enabled, conv3_resolve, conv3_launch},  // 3x3 convolutions of the dense layers (16-bit storage): LDS halo tile, prologue once per element
+    {IMPL_CVP, cvp_enabled, cvp_resolve, cvp_launch},          // forward of the ConvTranspose parity phases: halo tile per 128-channel group, a tap is a fragment address
+    {IMPL_PIG, pig_enabled, pig_resolve, pig_launch},          // plain 1x1 convolutions, forward: persistent workgroups (next tile's loads under this tile's epilogue)
+    {IMPL_HALO, halo_enabled, halo_resolve, halo_launch},      // multi-tap layers whose weights fit in LDS may take the halo-tile kernel
+};
+
+// The first family that may take the launch (family_allowed) and resolves it; nullptr: none does - the launch is the generic kernel's.
+static const ConvFamily* conv_family(const ConvArgs& a, int dtype, int epi, int impl, unsigned deny, Resolved& r) {
+  // second pass of a two-pass BatchNorm backward: ONE kernel variant stores s*dz + q + r*x (conv3.hip's thin-only data gradient);
+  // every other family would silently store s*dz
+  const bool conv3_only = a.eq != nullptr || a.er != nullptr;
+  for (const ConvFamily& f : kConvFamilies)
+    if ((!conv3_only || f.family == IMPL_CONV3) && family_allowed(f, impl, deny) && f.resolve(a, dtype, epi, r)) return &f;
+  return nullptr;
 }
 
 // impl = IMPL_AUTO: every enabled family may take the launch (the single-kernel test entry points); otherwise the family a plan
@@ -821,13 +808,12 @@ static hipError_t dispatch_special(const ConvArgs& a, int dtype, int epi, hipStr
 hipError_t launch_igemm(const ConvArgs& a, int dtype, int epi, bool mfma, hipStream_t st, int impl) {
   if (a.M <= 0) return hipSuccess;
   if (mfma && impl != IMPL_GENERIC) {
-    const LaunchCtl keep = g_ctl;
-    g_ctl.dry = false;
-    g_ctl.impl = impl;
-    int took;
-    const hipError_t e = dispatch_special(a, dtype, epi, st, took);
-    g_ctl = keep;
-    if (e != hipErrorNotSupported) { note_impl(took); return e; }
+    Resolved r;
+    if (const ConvFamily* f = conv_family(a, dtype, epi, impl, 0, r)) {
+      const hipError_t e = f->launch(r, st);
+      note_impl(f->family);
+      return e;
+    }
   }
   note_impl(IMPL_GENERIC);
   // what the generic kernels do not implement must fail here, not compute something else
@@ -839,16 +825,13 @@ hipError_t launch_igemm(const ConvArgs& a, int dtype, int epi, bool mfma, hipStr
   return launch_igemm_type<float>(a, epi, mfma, st);
 }
 
-// Which family launch_igemm(..., IMPL_AUTO) would run for this launch right now (nothing is launched).
-int igemm_pick(const ConvArgs& a, int dtype, int epi, bool mfma) {
+// Which family launch_igemm(..., IMPL_AUTO) would run for this launch right now, `deny` taken out (nothing is launched, the runtime
+// is not asked anything).
+int igemm_pick(const ConvArgs& a, int dtype, int epi, bool mfma, unsigned deny) {
   if (!mfma) return IMPL_GENERIC;
-  const LaunchCtl keep = g_ctl;
-  g_ctl.dry = true;
-  g_ctl.impl = IMPL_AUTO;
-  int took;
-  dispatch_special(a, dtype, epi, nullptr, took);
-  g_ctl = keep;
-  return took;
+  Resolved r;
+  const ConvFamily* f = conv_family(a, dtype, epi, IMPL_AUTO, deny, r);
+  return f ? f->family : IMPL_GENERIC;
 }
 #endif
 

@@ -19,6 +19,7 @@
 #include <cstdlib>
 
 #include "common.h"
+#include "dispatch.h"
 #include "gather.h"
 #include "pointwise.h"
 
@@ -244,38 +245,43 @@ __global__ __launch_bounds__(NTHREADS, 2) void pig_kernel(const PigArgs g) {
 static bool g_pig = !lab_flag("DMM_NO_PIG");
 void pig_set_enabled(bool on) { g_pig = on; }
 
+bool pig_enabled() { return g_pig; }
+
+// What pig_resolve hands to pig_launch: the kernel's arguments but for the walkers, the workgroups a CU holds, the instantiation.
+struct PigLaunch {
+  PigArgs g;
+  int lds, fit;
+  LdsLauncher<PigArgs> run;
+};
+
 // Takes a forward launch (EPI_STORE) of a plain 1x1 convolution behind BN+ReLU in a 16-bit storage type whose padded output width
-// is a multiple of 128 and whose rows are the pixels of the output tensor themselves.  Returns hipErrorNotSupported otherwise.
-hipError_t launch_pig(const ConvArgs& a, int dtype, int epi, hipStream_t st) {
-  if (!family_on(g_pig, IMPL_PIG) || dtype == DT_F32 || epi != EPI_STORE || a.nseg != 1 || a.pool2) return hipErrorNotSupported;
+// is a multiple of 128 and whose rows are the pixels of the output tensor themselves.  Refused otherwise.
+bool pig_resolve(const ConvArgs& a, int dtype, int epi, Resolved& r) {
+  if (dtype == DT_F32 || epi != EPI_STORE || a.nseg != 1 || a.pool2) return false;
   const Seg& s = a.seg[0];
   if (s.mode != G_PLAIN || s.istride != 1 || s.ntaps != 1 || s.taps[0] != 0 || s.Hs != a.Ho || s.Ws != a.Wo || s.scale == nullptr || s.q != nullptr)
-    return hipErrorNotSupported;
-  if (s.C % 8 || s.Cpad != s.C || a.Npad % PG_BN || a.out == nullptr) return hipErrorNotSupported;
-  if (2.0 * (double)a.M * s.ld >= 4294967296.0) return hipErrorNotSupported;  // 32-bit byte offsets into the operand
-  if (a.ostride != 1 || a.Hout != a.Ho || a.Wout != a.Wo || a.py != 0 || a.px != 0) return hipErrorNotSupported;
-  const int lds = PG_MAIN + PG_EXTRA + 2 * s.C * 4 + 16;
-  if (lds > 160 * 1024) return hipErrorNotSupported;
-  const int fit = lds <= 80 * 1024 ? 2 : 1;  // workgroups per CU (K > 1278 channels: the prologue constants push it past 80 KB)
-  if (g_ctl.dry) return hipSuccess;
-  PigArgs g;
-  g.c = a;
-  g.mtiles = (a.M + BM - 1) / BM;
-  g.ntiles = a.Npad / PG_BN;
-  static const int cus = [] { hipDeviceProp_t pr; int dev = 0; hipGetDevice(&dev);
-                              return (hipGetDeviceProperties(&pr, dev) == hipSuccess && pr.multiProcessorCount > 0) ? pr.multiProcessorCount : 256; }();
+    return false;
+  if (s.C % 8 || s.Cpad != s.C || a.Npad % PG_BN || a.out == nullptr) return false;
+  if (2.0 * (double)a.M * s.ld >= 4294967296.0) return false;  // 32-bit byte offsets into the operand
+  if (a.ostride != 1 || a.Hout != a.Ho || a.Wout != a.Wo || a.py != 0 || a.px != 0) return false;
+  PigLaunch& l = r.put<PigLaunch>();
+  l.lds = PG_MAIN + PG_EXTRA + 2 * s.C * 4 + 16;
+  if (l.lds > 160 * 1024) return false;
+  l.fit = l.lds <= 80 * 1024 ? 2 : 1;  // workgroups per CU (K > 1278 channels: the prologue constants push it past 80 KB)
+  l.g.c = a;
+  l.g.mtiles = (a.M + BM - 1) / BM;
+  l.g.ntiles = a.Npad / PG_BN;
+  l.run = dtype == DT_F16 ? launch_lds<pig_kernel<f16>, PigArgs> : launch_lds<pig_kernel<bf16>, PigArgs>;
+  return true;
+}
+
+hipError_t pig_launch(const Resolved& r, hipStream_t st) {
+  const PigLaunch& l = r.get<PigLaunch>();
+  PigArgs g = l.g;
+  static const int cus = device_cus();
   static const int per_cu = lab_int("DMM_PIG_PER_CU", 2);
-  g.walkers = std::max(1, std::min(g.mtiles, (std::min(per_cu, fit) * cus) / g.ntiles));
-  const int nwg = g.walkers * g.ntiles;
-  auto kern = dtype == DT_F16 ? pig_kernel<f16> : pig_kernel<bf16>;
-  static bool attr_done[2] = {false, false};
-  if (!attr_done[dtype == DT_F16 ? 0 : 1]) {
-    const hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e != hipSuccess) return e;
-    attr_done[dtype == DT_F16 ? 0 : 1] = true;
-  }
-  hipLaunchKernelGGL(kern, dim3(nwg), dim3(NTHREADS), lds, st, g);
-  return hipGetLastError();
+  g.walkers = std::max(1, std::min(g.mtiles, (std::min(per_cu, l.fit) * cus) / g.ntiles));
+  return l.run(160 * 1024, g.walkers * g.ntiles, NTHREADS, l.lds, st, g);
 }
 
 }  // namespace dmm

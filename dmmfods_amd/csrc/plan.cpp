@@ -375,6 +375,7 @@ struct Builder {
   // ---- switches of this plan and lab knobs, read once ----
   const bool pack_tiles_on = !P.sw.no_pack_tiles;
   const bool s2_interleave = !P.sw.no_s2_interleave;
+  const unsigned deny = P.sw.no_hf ? 1u << IMPL_HF : 0u;   // families the plan's switches rule out (igemm_pick / wgrad_pick)
   const bool s2_overlap = !lab_flag("DMM_NO_S2_OVERLAP");  // lab knob
   const bool front_matz = !lab_flag("DMM_NO_FRONT_MATZ");  // lab knob
   // which multi-consumer gradients are materialised (q + r*y applied once by applycorr) instead of corrected by every consumer's
@@ -641,7 +642,7 @@ struct Builder {
       a.ostride = c.ostride; a.py = ph.py; a.px = ph.px;
       if (c.stats && ob.ssum) { a.stat_sum = ob.ssum + c.och0; a.stat_sq = ob.ssq + c.och0; a.stat_stride = ob.ld; }
       const double np = (double)c.phases.size();
-      o.impl = igemm_pick(a, dtype, c.epi, mfma);
+      o.impl = igemm_pick(a, dtype, c.epi, mfma, deny);
       tag(o, ncls(o.impl, c.epi == EPI_LOGITS ? ROLE_LOGITS : ROLE_STORE, pd.Npad), short_name(c.wname), conv_flops(c, c.phases.size()),
           (src_bytes(c) + out_bytes(c)) / np + w_bytes(c) / np);
       if (c.epi == EPI_LOGITS) {
@@ -661,7 +662,7 @@ struct Builder {
             for (int t = 0; t < 9; ++t) m.c.ph_taps1[ph][t] = po.c.seg[1].taps[t];
           },
           [&](Op& m) {   // hf.hip (wave-specialised, one phase per workgroup) where its shape fits, else conv3.hip
-            const int took = igemm_pick(m.c, dtype, EPI_STORE, mfma);
+            const int took = igemm_pick(m.c, dtype, EPI_STORE, mfma, deny);
             if (took != IMPL_CONV3 && took != IMPL_HF) return false;
             m.impl = took;
             if (took == IMPL_HF) tag(m, ncls(IMPL_HF, ROLE_STORE, m.c.Npad), short_name(c.wname), m.flops, m.bytes);
@@ -680,7 +681,7 @@ struct Builder {
             copy_fwd_phase(m.c, po.c, ph, po.c.seg[0].ntaps);
             m.c.ph_ntaps[ph] = (signed char)po.c.seg[0].ntaps;
           },
-          [&](Op& m) { return igemm_pick(m.c, dtype, EPI_STORE, mfma) == IMPL_CVP; });
+          [&](Op& m) { return igemm_pick(m.c, dtype, EPI_STORE, mfma, deny) == IMPL_CVP; });
   }
 
   void fill_grad_seg(Seg& s, int buf, int ch0, int C, const std::vector<Tap>& taps, int istride) {
@@ -832,7 +833,7 @@ struct Builder {
       a.part = wg3_part;
       a.part_slots = W3_MAX_SLOTS;
     }
-    o.impl = wgrad_pick(a, dtype, d.use_mfma != 0);
+    o.impl = wgrad_pick(a, dtype, d.use_mfma != 0, deny);
     tag(o, ncls(o.impl, ROLE_WGRAD_T, pd.Npad), short_name(c.wname), conv_flops(c, 1),
         src_bytes(c) + grad_reads(c) * out_bytes(c) + w_bytes(c) * 4.0 / esz);
     if (st.eff_compact != nullptr && o.impl == IMPL_WG3 && !leaf_scope) {  // emitted behind the data gradient, reading its compact copy
@@ -860,7 +861,7 @@ struct Builder {
       a.dpack = (float*)pd.dpack;
       const double np = (double)c.phases.size();
       // reads: forward operand, output gradient and (for the deferred correction) the forward output; writes dW
-      o.impl = wgrad_pick(a, dtype, d.use_mfma != 0);
+      o.impl = wgrad_pick(a, dtype, d.use_mfma != 0, deny);
       tag(o, ncls(o.impl, ROLE_WGRAD, pd.Npad), short_name(c.wname), conv_flops(c, c.phases.size()) * (wseg < c.nseg ? (double)c.seg[0].Cw / c.Kin : 1.0),
           (src_bytes(c) + grad_reads(c) * out_bytes(c)) / np + w_bytes(c) * 4.0 / esz / np);
     }
@@ -886,7 +887,7 @@ struct Builder {
             bool all4 = true;   // four taps in every phase: ph_ntaps stays 0 (= seg[0].ntaps each)
             for (int ph = 0; ph < 4; ++ph) all4 = all4 && m.w.ph_ntaps[ph] == 4;
             if (all4) m.w.ph_ntaps[0] = m.w.ph_ntaps[1] = m.w.ph_ntaps[2] = m.w.ph_ntaps[3] = 0;
-            return wgrad_pick(m.w, dtype, d.use_mfma != 0) == IMPL_WGP;
+            return wgrad_pick(m.w, dtype, d.use_mfma != 0, deny) == IMPL_WGP;
           });
   }
 
@@ -918,13 +919,13 @@ struct Builder {
     const PackDesc& pd = P.packs[c.phases[0].pack];
     a.N = c.N; a.Npad = pd.Npad;
     a.dpack = (float*)pd.dpack + (size_t)pd.seg[0].nchunks * pd.Npad * BK;   // behind segment 0's chunks
-    o.impl = wgrad_pick(a, dtype, d.use_mfma != 0);
+    o.impl = wgrad_pick(a, dtype, d.use_mfma != 0, deny);
     if (raw_sbuf != nullptr && o.impl == IMPL_WG5 && sr.bn >= 0) {
       WgradArgs f = a;
       f.sbuf = raw_sbuf;
       f.t_mean = bns[sr.bn].mean + sr.bn_c0;
       f.t_invstd = bns[sr.bn].invstd + sr.bn_c0;
-      if (wgrad_pick(f, dtype, d.use_mfma != 0) == IMPL_WG5) { a = f; st.raw_stats = true; }
+      if (wgrad_pick(f, dtype, d.use_mfma != 0, deny) == IMPL_WG5) { a = f; st.raw_stats = true; }
     }
     const Buf& rb = bufs[sr.buf];
     tag(o, ncls(o.impl, ROLE_WGRAD, pd.Npad), short_name(c.wname) + ".raw", conv_flops(c, 1) * ((double)sr.Cw / c.Kin),
@@ -977,7 +978,7 @@ struct Builder {
     // reads: output gradient (+ forward output for the correction), x for the ReLU mask, (old gradient); writes gradient
     const double srcb = (double)sb.B * sb.H * sb.W * sr.C * esz;
     const double segf = conv_flops(c, 1) * ((double)sr.Cw / c.Kin) * (sr.dgrad == DG_UP2 ? 16.0 / 36.0 : 1.0);
-    o.impl = igemm_pick(a, dtype, EPI_BNBWD, d.use_mfma != 0);
+    o.impl = igemm_pick(a, dtype, EPI_BNBWD, d.use_mfma != 0, deny);
     if (st.wg3_held && o.impl == IMPL_CONV3) {  // hand the effective gradient over: the weight gradient reads the compact copy, no prologue
       a.eff_out = st.eff_compact;
       Seg& q = st.wg3_op.w.seg[0];
@@ -1007,8 +1008,8 @@ struct Builder {
     second_pass.c.red1 = nullptr; second_pass.c.red2 = nullptr;
     second_pass.c.eq = sb.q + sr.ch0; second_pass.c.er = sb.r + sr.ch0;
     // both MUTATED launches must still be conv3.hip's (the only kernel whose epilogue knows eq / er)
-    if (igemm_pick(first_pass.c, dtype, EPI_BNBWD, d.use_mfma != 0) != IMPL_CONV3 ||
-        igemm_pick(second_pass.c, dtype, EPI_BNBWD, d.use_mfma != 0) != IMPL_CONV3)
+    if (igemm_pick(first_pass.c, dtype, EPI_BNBWD, d.use_mfma != 0, deny) != IMPL_CONV3 ||
+        igemm_pick(second_pass.c, dtype, EPI_BNBWD, d.use_mfma != 0, deny) != IMPL_CONV3)
       return;
     st.have_second = true;
     st.second_buf = sr.buf;
@@ -1022,7 +1023,7 @@ struct Builder {
     WgradArgs f = (*ops)[st.r1_idx].w;
     f.sbuf = st.r1_sbuf;
     f.t_mean = bn.mean + sr.bn_c0; f.t_invstd = bn.invstd + sr.bn_c0;   // (mark of the factor form; the kernel needs scale / shift only)
-    if (wgrad_pick(f, dtype, d.use_mfma != 0) != IMPL_WG5) return;
+    if (wgrad_pick(f, dtype, d.use_mfma != 0, deny) != IMPL_WG5) return;
     Op& wo = (*ops)[st.r1_idx];
     wo.w = f;
     wo.chain = 1;
@@ -1734,18 +1735,8 @@ PlanSwitches PlanSwitches::from_environment() {
   return s;
 }
 
-namespace {
-// families the plan's switches rule out, in force (thread-local launch control) while a Builder picks kernel families
-struct DenyScope {
-  unsigned saved;
-  explicit DenyScope(const PlanSwitches& sw) : saved(g_ctl.deny) { if (sw.no_hf) g_ctl.deny |= 1u << IMPL_HF; }
-  ~DenyScope() { g_ctl.deny = saved; }
-};
-}  // namespace
-
 void plan_build_tables(dmm_plan* p) {
   build_tensor_table(p->desc, p->tensors, p->nparams, p->nbuf);
-  DenyScope deny(p->sw);
   Builder b(*p, true, nullptr);
   b.build();
   b.emit_all();
@@ -1759,7 +1750,6 @@ void plan_build_tables(dmm_plan* p) {
 void plan_bind(dmm_plan* p, void* ws) {
   p->packs.clear();
   p->fwd_train.clear(); p->fwd_eval.clear(); p->bwd.clear();
-  DenyScope deny(p->sw);
   Builder b(*p, false, (uint8_t*)ws);
   b.build();
   b.emit_all();

@@ -190,8 +190,9 @@ hipError_t launch_bw1(const Bw1Args& g, int dtype, hipStream_t st);
 hipError_t launch_bw1_reduce(const Bw1Args& g, hipStream_t st);  // dpack = sum of the slots (no-op without `part`)
 hipError_t launch_igemm(const ConvArgs& a, int dtype, int epi, bool mfma, hipStream_t st, int impl = IMPL_AUTO);
 hipError_t launch_wgrad(WgradArgs a, int dtype, bool mfma, hipStream_t st, int impl = IMPL_AUTO);
-int igemm_pick(const ConvArgs& a, int dtype, int epi, bool mfma);   // the family (enum Impl) that would run the launch now
-int wgrad_pick(const WgradArgs& a, int dtype, bool mfma);
+// the family (enum Impl) that would run the launch now; deny: 1 << family for families the asking plan's switches rule out
+int igemm_pick(const ConvArgs& a, int dtype, int epi, bool mfma, unsigned deny);
+int wgrad_pick(const WgradArgs& a, int dtype, bool mfma, unsigned deny);
 void thin_set_enabled(bool on);  // thin.hip
 void conv3_set_enabled(bool on);  // conv3.hip
 void wg3_set_enabled(bool on);    // wg3.hip
@@ -200,11 +201,6 @@ void wg5_set_enabled(bool on);    // wg5.hip
 void cvp_set_enabled(bool on);    // cvp.hip
 void bw1_set_enabled(bool on);    // bw1.hip
 void pig_set_enabled(bool on);    // pig.hip
-bool cvp_handles(const ConvArgs& a, int dtype, int epi);
-bool conv3_handles(const ConvArgs& a, int dtype, int epi);
-bool wg3_handles(const WgradArgs& a, int dtype);
-bool wgp_handles(const WgradArgs& a, int dtype);
-bool wg5_handles(const WgradArgs& a, int dtype);
 hipError_t launch_wg5_rawfin(const RawFinArgs& a, hipStream_t st);
 hipError_t launch_wg5_fin64(const Fin64Args& a, hipStream_t st);
 hipError_t launch_convert_input(const ConvertArgs& a, int dtype, hipStream_t st);

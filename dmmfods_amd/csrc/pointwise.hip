@@ -14,7 +14,6 @@
 
 namespace dmm {
 
-thread_local LaunchCtl g_ctl;  // see common.h
 thread_local int g_last_impl = IMPL_AUTO;
 thread_local unsigned g_impl_mask = 0;
 

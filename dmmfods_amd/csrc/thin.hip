@@ -16,6 +16,7 @@
 #include <type_traits>
 
 #include "common.h"
+#include "dispatch.h"
 #include "gather.h"
 
 namespace dmm {
@@ -203,16 +204,25 @@ __global__ __launch_bounds__(NTHREADS, 2) void thin_logits_kernel(const ThinArgs
 static bool g_no_thin = false;
 void thin_set_enabled(bool on) { g_no_thin = !on; }
 
-// Returns hipErrorNotSupported when the layer is not eligible.
-hipError_t launch_thin_logits(const ConvArgs& c, int dtype, int epi, hipStream_t st) {
-  if (!family_on(!g_no_thin, IMPL_THIN) || dtype == DT_F32 || epi != EPI_LOGITS || c.nseg != 1) return hipErrorNotSupported;
+bool thin_enabled() { return !g_no_thin; }
+
+// What thin_resolve hands to thin_launch: the kernel's arguments and the instantiation (storage type, tap radius, classes) that runs.
+struct ThinLaunch {
+  ThinArgs a;
+  void (*kern)(const ThinArgs);
+};
+
+// Few output channels x many taps (the 5x5 logits convolution): refused unless there is an instantiation for the layer.
+bool thin_resolve(const ConvArgs& c, int dtype, int epi, Resolved& r) {
+  if (dtype == DT_F32 || epi != EPI_LOGITS || c.nseg != 1) return false;
   const Seg& sg = c.seg[0];
   if (sg.mode != G_PLAIN || sg.istride != 1 || sg.Hs != c.Ho || sg.Ws != c.Wo || c.ostride != 1 || c.py != 0 || c.px != 0 ||
       c.Hout != c.Ho || c.Wout != c.Wo)
-    return hipErrorNotSupported;
-  if (sg.C != 64 || sg.Cpad != 64 || sg.scale == nullptr || sg.q != nullptr) return hipErrorNotSupported;
-  if (c.N < 1 || c.N > 4 || sg.ntaps > TH_MAXTAPS || sg.ntaps * c.N > TH_COLS) return hipErrorNotSupported;
-  ThinArgs a;
+    return false;
+  if (sg.C != 64 || sg.Cpad != 64 || sg.scale == nullptr || sg.q != nullptr) return false;
+  if (c.N < 1 || c.N > 4 || sg.ntaps > TH_MAXTAPS || sg.ntaps * c.N > TH_COLS) return false;
+  ThinLaunch& l = r.put<ThinLaunch>();
+  ThinArgs& a = l.a;
   a.src = sg.src; a.ld = sg.ld; a.B = c.B; a.H = c.Ho; a.W = c.Wo;
   a.scale = sg.scale; a.shift = sg.shift;
   a.wpack = c.wpack; a.Npad = c.Npad; a.N = c.N; a.ntaps = sg.ntaps;
@@ -221,19 +231,18 @@ hipError_t launch_thin_logits(const ConvArgs& c, int dtype, int epi, hipStream_t
   int R = 0;
   for (int t = 0; t < sg.ntaps; ++t) R = std::max(R, abs((int)(signed char)(sg.taps[t] & 0xff)));
   const int kw = 2 * R + 1;
-  if (sg.ntaps != kw * kw) return hipErrorNotSupported;
+  if (sg.ntaps != kw * kw) return false;
   for (int t = 0; t < sg.ntaps; ++t) {
     const int dy = (int)(signed char)(sg.taps[t] & 0xff), dx = (int)(signed char)((sg.taps[t] >> 8) & 0xff);
-    if (dy != t / kw - R || dx != t % kw - R) return hipErrorNotSupported;
+    if (dy != t / kw - R || dx != t % kw - R) return false;
     a.dy[t] = (signed char)dy; a.dx[t] = (signed char)dx;
   }
-  void (*kern)(const ThinArgs) = nullptr;
+  l.kern = nullptr;
   const bool bf = dtype == DT_BF16;
-  if (R == 2 && c.N == 3) kern = bf ? thin_logits_kernel<bf16, 2, 3> : thin_logits_kernel<f16, 2, 3>;
-  else if (R == 2 && c.N == 1) kern = bf ? thin_logits_kernel<bf16, 2, 1> : thin_logits_kernel<f16, 2, 1>;
-  else if (R == 2 && c.N == 2) kern = bf ? thin_logits_kernel<bf16, 2, 2> : thin_logits_kernel<f16, 2, 2>;
-  if (kern == nullptr) return hipErrorNotSupported;
-  if (g_ctl.dry) return hipSuccess;
+  if (R == 2 && c.N == 3) l.kern = bf ? thin_logits_kernel<bf16, 2, 3> : thin_logits_kernel<f16, 2, 3>;
+  else if (R == 2 && c.N == 1) l.kern = bf ? thin_logits_kernel<bf16, 2, 1> : thin_logits_kernel<f16, 2, 1>;
+  else if (R == 2 && c.N == 2) l.kern = bf ? thin_logits_kernel<bf16, 2, 2> : thin_logits_kernel<f16, 2, 2>;
+  if (l.kern == nullptr) return false;
   a.R = R;
   const int wout = TH_PX - 2 * R;
   a.nxs = (a.W + wout - 1) / wout;
@@ -251,13 +260,18 @@ hipError_t launch_thin_logits(const ConvArgs& c, int dtype, int epi, hipStream_t
       if (best < 0 || cost <= best) { best = cost; a.rows_per_wg = rows; a.nys = (a.H + rows - 1) / rows; }
     }
   }
-  static const void* attr = nullptr;
-  if (attr != (const void*)kern) {
-    hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, ThinSmem::bytes);
+  return true;
+}
+
+hipError_t thin_launch(const Resolved& r, hipStream_t st) {
+  const ThinLaunch& l = r.get<ThinLaunch>();
+  static const void* attr = nullptr;   // (the last instantiation whose LDS limit was raised)
+  if (attr != (const void*)l.kern) {
+    hipError_t e = hipFuncSetAttribute((const void*)l.kern, hipFuncAttributeMaxDynamicSharedMemorySize, ThinSmem::bytes);
     if (e != hipSuccess) return e;
-    attr = (const void*)kern;
+    attr = (const void*)l.kern;
   }
-  hipLaunchKernelGGL(kern, dim3(a.B * a.nys * a.nxs), dim3(NTHREADS), ThinSmem::bytes, st, a);
+  hipLaunchKernelGGL(l.kern, dim3(l.a.B * l.a.nys * l.a.nxs), dim3(NTHREADS), ThinSmem::bytes, st, l.a);
   return hipGetLastError();
 }
 

@@ -27,6 +27,7 @@
 #include <cstdlib>
 
 #include "common.h"
+#include "dispatch.h"
 #include "gather.h"
 #include "pointwise.h"
 
@@ -343,54 +344,49 @@ __global__ __launch_bounds__(256) void wg3_reduce_kernel(const float* __restrict
 
 static bool g_wg3 = !lab_flag("DMM_NO_WG3");
 void wg3_set_enabled(bool on) { g_wg3 = on; }
+bool wg3_enabled() { return g_wg3; }
 
-template <typename T, int PQ>
-static hipError_t launch_wg3_t(const Wg3Args& g, int nwg, hipStream_t st) {
-  if (g_ctl.dry) return hipSuccess;
-  auto kern = wg3_kernel<T, PQ>;
-  static bool attr_done = false;  // (one flag per instantiation)
-  if (!attr_done) {
-    const hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, W3_LDS);
-    if (e != hipSuccess) return e;
-    attr_done = true;
-  }
-  hipLaunchKernelGGL(kern, dim3(nwg), dim3(W3_NT), W3_LDS, st, g);
-  hipError_t e = hipGetLastError();
-  if (e == hipSuccess && g.part != nullptr) {  // same stream: the slots are reused by the next launch of the family
-    hipLaunchKernelGGL(wg3_reduce_kernel, dim3(W3_SLOT_FLOATS / 4 / 32), dim3(256), 0, st, g.part, g.w.dpack, nwg);
-    e = hipGetLastError();
-  }
-  return e;
-}
+// What wg3_resolve hands to wg3_launch: the kernel's arguments but for the split over workgroups, and the instantiation that runs.
+struct Wg3Launch {
+  Wg3Args g;
+  LdsLauncher<Wg3Args> run;
+};
 
-// Returns hipErrorNotSupported unless this is the transposed-form weight gradient of a 128 -> 32 channel 3x3 convolution in a
-// 16-bit storage type.
-hipError_t launch_wg3(const WgradArgs& a, int dtype, hipStream_t st) {
-  if (!family_on(g_wg3, IMPL_WG3) || dtype == DT_F32 || a.nseg != 1) return hipErrorNotSupported;
+// Refused unless this is the transposed-form weight gradient of a 128 -> 32 channel 3x3 convolution in a 16-bit storage type.
+bool wg3_resolve(const WgradArgs& a, int dtype, Resolved& r) {
+  if (dtype == DT_F32 || a.nseg != 1) return false;
   const Seg& q = a.seg[0];
   const Seg& p = a.dy;
   if (q.mode != G_PLAIN || q.istride != 1 || q.ntaps != 9 || q.C != W3_CY || q.Cpad != W3_CY || q.Hs != a.Ho || q.Ws != a.Wo || q.scale != nullptr)
-    return hipErrorNotSupported;
+    return false;
   if (p.mode != G_PLAIN || p.istride != 1 || p.ntaps != 1 || p.taps[0] != 0 || p.C != W3_CA || p.Hs != a.Ho || p.Ws != a.Wo || p.scale == nullptr)
-    return hipErrorNotSupported;
-  if (a.N != W3_CA || a.Npad != W3_CA) return hipErrorNotSupported;
+    return false;
+  if (a.N != W3_CA || a.Npad != W3_CA) return false;
   bool seen[9] = {false, false, false, false, false, false, false, false, false};
   for (int t = 0; t < 9; ++t) {
     const int dy = (int)(signed char)(q.taps[t] & 0xff), dx = (int)(signed char)((q.taps[t] >> 8) & 0xff);
-    if (dy < -1 || dy > 1 || dx < -1 || dx > 1 || seen[(dy + 1) * 3 + dx + 1]) return hipErrorNotSupported;
+    if (dy < -1 || dy > 1 || dx < -1 || dx > 1 || seen[(dy + 1) * 3 + dx + 1]) return false;
     seen[(dy + 1) * 3 + dx + 1] = true;
   }
-  Wg3Args g;
+  Wg3Launch& l = r.put<Wg3Launch>();
+  Wg3Args& g = l.g;
   g.w = a;
   g.tiles_y = (a.Ho + W3_TH - 1) / W3_TH;
   g.tiles_x = (a.Wo + W3_TW - 1) / W3_TW;
   g.ntiles = a.B * g.tiles_y * g.tiles_x;
-  if (g_ctl.dry) return hipSuccess;
+  if (dtype == DT_F16) l.run = q.q ? launch_lds<wg3_kernel<f16, 2>, Wg3Args> : launch_lds<wg3_kernel<f16, 0>, Wg3Args>;
+  else l.run = q.q ? launch_lds<wg3_kernel<bf16, 2>, Wg3Args> : launch_lds<wg3_kernel<bf16, 0>, Wg3Args>;
+  return true;
+}
+
+hipError_t wg3_launch(const Resolved& r, hipStream_t st) {
+  const Wg3Launch& l = r.get<Wg3Launch>();
+  Wg3Args g = l.g;
+  const WgradArgs& a = g.w;
   // Workgroups.  With slots: one per compute unit (8 waves each; W3_MAX_SLOTS caps it), every workgroup stores its 147 KB partial
   // and the reduction reads them once.  With atomics (no slots, DMM_WG3_SLOTS=0): time ~ tiles/nwg * t_tile + nwg * (147 KB of
   // fp32 atomics at the chip-wide atomic rate of 1.3 TB/s = 0.11 us): minimum at nwg ~ sqrt(t_tile / 0.11 us * tiles), t_tile ~ 1.3 us.
-  static const int cus = [] { hipDeviceProp_t pr; int dev = 0; hipGetDevice(&dev);
-                              return (hipGetDeviceProperties(&pr, dev) == hipSuccess && pr.multiProcessorCount > 0) ? pr.multiProcessorCount : 256; }();
+  static const int cus = device_cus();
   static const bool use_slots = lab_int("DMM_WG3_SLOTS", 1) != 0;
   static const int wgs_cap = lab_int("DMM_WG3_WGS", 0);
   g.part = (use_slots && a.part != nullptr) ? a.part : nullptr;
@@ -399,17 +395,12 @@ hipError_t launch_wg3(const WgradArgs& a, int dtype, hipStream_t st) {
   nwg = std::max(1, std::min(std::min(nwg, cus), g.ntiles));
   g.tiles_per_wg = (g.ntiles + nwg - 1) / nwg;
   nwg = (g.ntiles + g.tiles_per_wg - 1) / g.tiles_per_wg;
-  const int pq = q.q ? 2 : 0;
-  if (dtype == DT_F16) return pq ? launch_wg3_t<f16, 2>(g, nwg, st) : launch_wg3_t<f16, 0>(g, nwg, st);
-  return pq ? launch_wg3_t<bf16, 2>(g, nwg, st) : launch_wg3_t<bf16, 0>(g, nwg, st);
-}
-
-bool wg3_handles(const WgradArgs& a, int dtype) {
-  const LaunchCtl keep = g_ctl;
-  g_ctl.dry = true;
-  const hipError_t e = launch_wg3(a, dtype, nullptr);
-  g_ctl = keep;
-  return e == hipSuccess;
+  hipError_t e = l.run(W3_LDS, nwg, W3_NT, W3_LDS, st, g);
+  if (e == hipSuccess && g.part != nullptr) {  // same stream: the slots are reused by the next launch of the family
+    hipLaunchKernelGGL(wg3_reduce_kernel, dim3(W3_SLOT_FLOATS / 4 / 32), dim3(256), 0, st, g.part, g.w.dpack, nwg);
+    e = hipGetLastError();
+  }
+  return e;
 }
 
 }  // namespace dmm

@@ -14,6 +14,7 @@
 #include <cstdlib>
 
 #include "common.h"
+#include "dispatch.h"
 #include "gather.h"
 
 namespace dmm {
@@ -345,8 +346,10 @@ __global__ __launch_bounds__(NTHREADS, (TR == 3 ? 1 : ((PA == 3 || (PA == 0 && P
 
 static bool g_wg5 = !lab_flag("DMM_NO_WG5");
 void wg5_set_enabled(bool on) { g_wg5 = on; }
+bool wg5_enabled() { return g_wg5; }
 
-
+// The launcher of one instantiation (no LDS attribute: every form fits the default limit).
+typedef hipError_t (*Wg5Inst)(const Wg5Args& g, int nwg, hipStream_t st);
 template <typename T, int TR, int STR, int PA, int PY = 0>
 static hipError_t launch_wg5_t(const Wg5Args& g, int nwg, hipStream_t st) {
   auto kern = wg5_kernel<T, TR, STR, PA, PY>;
@@ -355,62 +358,76 @@ static hipError_t launch_wg5_t(const Wg5Args& g, int nwg, hipStream_t st) {
   return hipGetLastError();
 }
 
+// What wg5_resolve hands to wg5_launch: the kernel's arguments but for the split over workgroups, the workgroups a CU holds
+// (0: DMM_WG5_PER_CU), the instantiation that runs.
+struct Wg5Launch {
+  Wg5Args g;
+  int per_cu;
+  Wg5Inst run;
+};
+
 // Takes a weight gradient whose tapped operand (seg[0]) is ONE 8-channel slot and whose pixel-aligned operand (dy) has 64 channels,
 // 16-bit storage:  (a) 25 taps at stride 1, the 64 channels an activation (BN+ReLU): the head's 5x5 convolution, transposed form;
 // (b) 49 taps at stride 2 over the raw input, the 64 channels an output gradient (plain or with the deferred correction): the
 // stem's 7x7 convolution, normal form;  (c) 9 taps at stride 1 over the BN+ReLU-normalised raw input, the 64 channels an output
 // gradient: the raw-input segment of the head's first convolution (reference M:126-127), normal form, all four output parities of
-// the plan's phase decomposition in one pass over the full-resolution gradient.  Returns hipErrorNotSupported otherwise.
-hipError_t launch_wg5(const WgradArgs& a, int dtype, hipStream_t st) {
-  if (!family_on(g_wg5, IMPL_WG5) || dtype == DT_F32 || a.nseg != 1) return hipErrorNotSupported;
+// the plan's phase decomposition in one pass over the full-resolution gradient.  Refused otherwise.
+bool wg5_resolve(const WgradArgs& a, int dtype, Resolved& r) {
+  if (dtype == DT_F32 || a.nseg != 1) return false;
   const Seg& q = a.seg[0];
   const Seg& p = a.dy;
   const bool stem = q.ntaps == 49, raw3 = q.ntaps == 9;
   const int tr = stem ? 3 : (raw3 ? 1 : 2), str = stem ? 2 : 1;
   if (q.mode != G_PLAIN || q.istride != str || (q.ntaps != 25 && q.ntaps != 49 && q.ntaps != 9) || q.C != 8 || q.Cpad != 8 || q.Hs != str * a.Ho ||
       q.Ws != str * a.Wo || (q.scale != nullptr) != raw3 || q.q != nullptr)
-    return hipErrorNotSupported;
-  if (q.nchunks != (q.ntaps * 8 + 31) / 32) return hipErrorNotSupported;
+    return false;
+  if (q.nchunks != (q.ntaps * 8 + 31) / 32) return false;
   const bool factors = a.sbuf != nullptr;   // PY = 2: the activation's two factors, results to sbuf
   const bool head5 = !stem && !raw3;
-  if (factors && !((raw3 || head5) && a.t_mean != nullptr && a.t_invstd != nullptr)) return hipErrorNotSupported;
-  if (p.mode != G_PLAIN || p.istride != 1 || p.ntaps != 1 || p.taps[0] != 0 || p.C != W5_CA || p.Hs != a.Ho || p.Ws != a.Wo) return hipErrorNotSupported;
-  if ((stem || raw3) ? p.scale != nullptr : (p.scale == nullptr || p.q != nullptr)) return hipErrorNotSupported;
-  if (a.N != W5_CA || a.Npad != W5_CA) return hipErrorNotSupported;
+  if (factors && !((raw3 || head5) && a.t_mean != nullptr && a.t_invstd != nullptr)) return false;
+  if (p.mode != G_PLAIN || p.istride != 1 || p.ntaps != 1 || p.taps[0] != 0 || p.C != W5_CA || p.Hs != a.Ho || p.Ws != a.Wo) return false;
+  if ((stem || raw3) ? p.scale != nullptr : (p.scale == nullptr || p.q != nullptr)) return false;
+  if (a.N != W5_CA || a.Npad != W5_CA) return false;
   bool seen[49];
   for (int t = 0; t < 49; ++t) seen[t] = false;
   for (int t = 0; t < q.ntaps; ++t) {
     const int dy = (int)(signed char)(q.taps[t] & 0xff), dx = (int)(signed char)((q.taps[t] >> 8) & 0xff);
-    if (dy < -tr || dy > tr || dx < -tr || dx > tr || seen[(dy + tr) * (2 * tr + 1) + dx + tr]) return hipErrorNotSupported;
+    if (dy < -tr || dy > tr || dx < -tr || dx > tr || seen[(dy + tr) * (2 * tr + 1) + dx + tr]) return false;
     seen[(dy + tr) * (2 * tr + 1) + dx + tr] = true;
   }
-  if (g_ctl.dry) return hipSuccess;
-  Wg5Args g;
+  Wg5Launch& l = r.put<Wg5Launch>();
+  Wg5Args& g = l.g;
   g.w = a;
   g.tiles_y = (a.Ho + W5_TH - 1) / W5_TH;
   g.tiles_x = (a.Wo + W5_TW - 1) / W5_TW;
   g.ntiles = a.B * g.tiles_y * g.tiles_x;
-  static const int cus = [] { hipDeviceProp_t pr; int dev = 0; hipGetDevice(&dev);
-                              return (hipGetDeviceProperties(&pr, dev) == hipSuccess && pr.multiProcessorCount > 0) ? pr.multiProcessorCount : 256; }();
-  static const int per_cu = lab_int("DMM_WG5_PER_CU", 2);
   // every workgroup ends with 57 (stem: 106) KB of atomics; a tile costs ~1 us: two workgroups per CU unless the picture is small
   const bool three = (head5 && factors) || (raw3 && factors && !p.q);
-  int nwg = std::max(1, std::min((stem ? 1 : (three ? W5_F_PER_CU : per_cu)) * cus, g.ntiles / 8));  // (the stem form holds one workgroup per CU)
-  g.tiles_per_wg = (g.ntiles + nwg - 1) / nwg;
-  nwg = (g.ntiles + g.tiles_per_wg - 1) / g.tiles_per_wg;
+  l.per_cu = stem ? 1 : (three ? W5_F_PER_CU : 0);  // (the stem form holds one workgroup per CU)
   const bool f16t = dtype == DT_F16;
   if (raw3 && factors) {
-    if (p.q) return f16t ? launch_wg5_t<f16, 1, 1, 2, 2>(g, nwg, st) : launch_wg5_t<bf16, 1, 1, 2, 2>(g, nwg, st);
-    return f16t ? launch_wg5_t<f16, 1, 1, 0, 2>(g, nwg, st) : launch_wg5_t<bf16, 1, 1, 0, 2>(g, nwg, st);
+    if (p.q) l.run = f16t ? launch_wg5_t<f16, 1, 1, 2, 2> : launch_wg5_t<bf16, 1, 1, 2, 2>;
+    else l.run = f16t ? launch_wg5_t<f16, 1, 1, 0, 2> : launch_wg5_t<bf16, 1, 1, 0, 2>;
+  } else if (raw3) {
+    if (p.q) l.run = f16t ? launch_wg5_t<f16, 1, 1, 2, 1> : launch_wg5_t<bf16, 1, 1, 2, 1>;
+    else l.run = f16t ? launch_wg5_t<f16, 1, 1, 0, 1> : launch_wg5_t<bf16, 1, 1, 0, 1>;
   }
-  if (raw3) {
-    if (p.q) return f16t ? launch_wg5_t<f16, 1, 1, 2, 1>(g, nwg, st) : launch_wg5_t<bf16, 1, 1, 2, 1>(g, nwg, st);
-    return f16t ? launch_wg5_t<f16, 1, 1, 0, 1>(g, nwg, st) : launch_wg5_t<bf16, 1, 1, 0, 1>(g, nwg, st);
-  }
-  if (head5 && factors) return f16t ? launch_wg5_t<f16, 2, 1, 3>(g, nwg, st) : launch_wg5_t<bf16, 2, 1, 3>(g, nwg, st);
-  if (!stem) return f16t ? launch_wg5_t<f16, 2, 1, 1>(g, nwg, st) : launch_wg5_t<bf16, 2, 1, 1>(g, nwg, st);
-  if (p.q) return f16t ? launch_wg5_t<f16, 3, 2, 2>(g, nwg, st) : launch_wg5_t<bf16, 3, 2, 2>(g, nwg, st);
-  return f16t ? launch_wg5_t<f16, 3, 2, 0>(g, nwg, st) : launch_wg5_t<bf16, 3, 2, 0>(g, nwg, st);
+  else if (head5 && factors) l.run = f16t ? launch_wg5_t<f16, 2, 1, 3> : launch_wg5_t<bf16, 2, 1, 3>;
+  else if (!stem) l.run = f16t ? launch_wg5_t<f16, 2, 1, 1> : launch_wg5_t<bf16, 2, 1, 1>;
+  else if (p.q) l.run = f16t ? launch_wg5_t<f16, 3, 2, 2> : launch_wg5_t<bf16, 3, 2, 2>;
+  else l.run = f16t ? launch_wg5_t<f16, 3, 2, 0> : launch_wg5_t<bf16, 3, 2, 0>;
+  return true;
+}
+
+hipError_t wg5_launch(const Resolved& r, hipStream_t st) {
+  const Wg5Launch& l = r.get<Wg5Launch>();
+  Wg5Args g = l.g;
+  static const int cus = device_cus();
+  static const int per_cu = lab_int("DMM_WG5_PER_CU", 2);
+  int nwg = std::max(1, std::min((l.per_cu ? l.per_cu : per_cu) * cus, g.ntiles / 8));
+  g.tiles_per_wg = (g.ntiles + nwg - 1) / nwg;
+  nwg = (g.ntiles + g.tiles_per_wg - 1) / g.tiles_per_wg;
+  return l.run(g, nwg, st);
 }
 
 // From the factor correlations S (wg5_kernel, PY = 2; layout [chunk][64 output channels c][32 columns], column 32 chunk + k = 16 tap +
@@ -442,7 +459,6 @@ __global__ __launch_bounds__(256) void wg5_rawfin_kernel(const RawFinArgs a) {
 }
 
 hipError_t launch_wg5_rawfin(const RawFinArgs& a, hipStream_t st) {
-  if (g_ctl.dry) return hipSuccess;
   hipLaunchKernelGGL(wg5_rawfin_kernel, dim3(1), dim3(256), 0, st, a);
   return hipGetLastError();
 }
@@ -486,17 +502,8 @@ __global__ __launch_bounds__(256) void wg5_fin64_kernel(const Fin64Args a) {
 }
 
 hipError_t launch_wg5_fin64(const Fin64Args& a, hipStream_t st) {
-  if (g_ctl.dry) return hipSuccess;
   hipLaunchKernelGGL(wg5_fin64_kernel, dim3(8), dim3(256), 0, st, a);
   return hipGetLastError();
-}
-
-bool wg5_handles(const WgradArgs& a, int dtype) {
-  const LaunchCtl keep = g_ctl;
-  g_ctl.dry = true;
-  const hipError_t e = launch_wg5(a, dtype, nullptr);
-  g_ctl = keep;
-  return e == hipSuccess;
 }
 
 }  // namespace dmm

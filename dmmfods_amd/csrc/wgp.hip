@@ -16,6 +16,7 @@
 #include <cstdlib>
 
 #include "common.h"
+#include "dispatch.h"
 #include "gather.h"
 
 namespace dmm {
@@ -250,134 +251,131 @@ __global__ __launch_bounds__(NTHREADS, 1) void wgp_kernel(const WgpArgs g) {
 
 static bool g_wgp = !lab_flag("DMM_NO_WGP");
 void wgp_set_enabled(bool on) { g_wgp = on; }
-// the wave-specialised form (wgpw.hip)
-hipError_t launch_wgpw(const WgradArgs& a, int dtype, int ntap, int nj, int tiles_y, int tiles_x, int ntiles, int tiles_per_wg, int nsplit, int nct,
-                       int ncot, int dymin, int dxmin, const int* ph_dymin, const int* ph_dxmin, int nwg, hipStream_t st);
-bool wgpw_accepts(const WgradArgs& a, int ntap, int nj);   // what launch_wgpw takes (operands below 4 GiB, its instantiations)
+bool wgp_enabled() { return g_wgp; }
+// the wave-specialised form (wgpw.hip): noted as IMPL_WGPW beside IMPL_WGP when it runs
+bool wgpw_resolve(const WgradArgs& a, int dtype, int ntap, int nj, const WgpGeom& q, Resolved& r);   // operands below 4 GiB, its instantiations
+hipError_t wgpw_launch(const Resolved& r, hipStream_t st);
 
-
-template <typename T, int NTAP, int NJ, int PQ>
-static hipError_t launch_wgp_t(const WgpArgs& g, int nwg, hipStream_t st) {
-  auto kern = wgp_kernel<T, NTAP, NJ, PQ>;
-  static bool attr_done = false;
-  if (!attr_done) {
-    const hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, WP_LDS);
-    if (e != hipSuccess) return e;
-    attr_done = true;
-  }
-  hipLaunchKernelGGL(kern, dim3(nwg), dim3(NTHREADS), WP_LDS, st, g);
-  return hipGetLastError();
-}
-
+// The instantiations built (nullptr: none for these taps / output channels per workgroup).
 template <typename T>
-static hipError_t launch_wgp_type(const WgpArgs& g, int ntap, int nj, int pq, int nwg, hipStream_t st) {
-  if (ntap == 4 && nj == 2) return pq ? launch_wgp_t<T, 4, 2, 2>(g, nwg, st) : launch_wgp_t<T, 4, 2, 0>(g, nwg, st);
-  if (ntap == 2 && nj == 4) return pq ? launch_wgp_t<T, 2, 4, 2>(g, nwg, st) : launch_wgp_t<T, 2, 4, 0>(g, nwg, st);
-  if (ntap == 2 && nj == 2) return pq ? launch_wgp_t<T, 2, 2, 2>(g, nwg, st) : launch_wgp_t<T, 2, 2, 0>(g, nwg, st);
-  return hipErrorNotSupported;
+static LdsLauncher<WgpArgs> wgp_instance(int ntap, int nj, int pq) {
+  if (ntap == 4 && nj == 2) return pq ? launch_lds<wgp_kernel<T, 4, 2, 2>, WgpArgs> : launch_lds<wgp_kernel<T, 4, 2, 0>, WgpArgs>;
+  if (ntap == 2 && nj == 4) return pq ? launch_lds<wgp_kernel<T, 2, 4, 2>, WgpArgs> : launch_lds<wgp_kernel<T, 2, 4, 0>, WgpArgs>;
+  if (ntap == 2 && nj == 2) return pq ? launch_lds<wgp_kernel<T, 2, 2, 2>, WgpArgs> : launch_lds<wgp_kernel<T, 2, 2, 0>, WgpArgs>;
+  return nullptr;
 }
+
+// What wgp_resolve hands to wgp_launch when this file's kernel runs (wgpw.hip's form: WgpwLaunch there).
+struct WgpLaunch {
+  WgpArgs g;
+  LdsLauncher<WgpArgs> run;
+};
 
 // Takes the first segment of a normal-form weight gradient whose taps (2 or 4) lie in a 2x2 box, in a 16-bit storage type, with
-// the input a multiple of 128 channels and the output a multiple of 64.  Returns hipErrorNotSupported otherwise.  A second
+// the input a multiple of 128 channels and the output a multiple of 64.  Refused otherwise.  A second
 // (8-channel raw-input) segment is NOT covered: the caller runs it through the generic kernel (see launch_wgrad).
-hipError_t launch_wgp(const WgradArgs& a, int dtype, hipStream_t st) {
-  if (!family_on(g_wgp, IMPL_WGP) || dtype == DT_F32 || a.nseg < 1 || a.nseg > 2) return hipErrorNotSupported;
+bool wgp_resolve(const WgradArgs& a, int dtype, Resolved& r) {
+  if (dtype == DT_F32 || a.nseg < 1 || a.nseg > 2) return false;
   const Seg& x = a.seg[0];
   const Seg& y = a.dy;
-  static const bool trace = lab_flag("DMM_WGP_TRACE");
-  if (trace && !g_ctl.dry)
-    fprintf(stderr, "wgp? nseg %d x: mode %d istride %d Hs %d Ws %d (Ho %d Wo %d) scale %d C %d Cpad %d ntaps %d | y: mode %d ntaps %d istride %d Hs %d Ws %d C %d | N %d Npad %d\n",
-            a.nseg, x.mode, x.istride, x.Hs, x.Ws, a.Ho, a.Wo, x.scale != nullptr, x.C, x.Cpad, x.ntaps, y.mode, y.ntaps, y.istride, y.Hs, y.Ws, y.C, a.N, a.Npad);
-  if (x.mode != G_PLAIN || x.istride != 1 || x.Hs != a.Ho || x.Ws != a.Wo || x.scale == nullptr || x.C % WP_CA || x.Cpad != x.C) return hipErrorNotSupported;
+  if (x.mode != G_PLAIN || x.istride != 1 || x.Hs != a.Ho || x.Ws != a.Wo || x.scale == nullptr || x.C % WP_CA || x.Cpad != x.C) return false;
   static const bool ws = !lab_flag("DMM_NO_WGPW");   // wave-specialised form (wgpw.hip) for the materialised output gradient
   // one tap: the (0, 0) parity phase of a ConvTranspose (stride-2 gradient rows) and the decoder's plain 1x1 convolutions conv_reduce
   // (reference M:150-153; C_in = 1024 ... 256 -> C_in / 2 at the block resolutions), only in the wave-specialised form.  (The dense layers'
   // 128-wide bottlenecks never come here: bw1.hip fuses their weight gradient with the data gradient.)
   static const bool ws1x1 = lab_flag("DMM_WGPW_1X1");   // measured (round 5): 0.198 / 0.192 / 0.066 ms against the generic kernel's 0.178 / 0.171 / 0.064: off
   if (x.ntaps == 1 && !(ws && (y.istride == 2 || (ws1x1 && y.istride == 1 && x.taps[0] == 0)) && y.q == nullptr && (a.nphase == 0 || a.nphase == 4) && a.nseg == 1))
-    return hipErrorNotSupported;
-  if (x.ntaps != 1 && x.ntaps != 2 && x.ntaps != 4) return hipErrorNotSupported;
-  if (a.nseg == 2 && !(a.seg[1].C == 8 && a.seg[1].nchunks >= 1)) return hipErrorNotSupported;
-  if (y.mode != G_PLAIN || y.ntaps != 1 || y.scale != nullptr || (y.istride != 1 && y.istride != 2)) return hipErrorNotSupported;
-  if (y.Hs != a.Ho * y.istride || y.Ws != a.Wo * y.istride) return hipErrorNotSupported;
-  if (a.N % 64 || a.Npad < a.N || y.C != a.N) return hipErrorNotSupported;
-  if (a.nphase < 0 || a.nphase > 4 || (a.nphase > 0 && a.nseg != 1)) return hipErrorNotSupported;
-  int dymin = 127, dxmin = 127;
-  int ph_dymin[4] = {0, 0, 0, 0}, ph_dxmin[4] = {0, 0, 0, 0};
+    return false;
+  if (x.ntaps != 1 && x.ntaps != 2 && x.ntaps != 4) return false;
+  if (a.nseg == 2 && !(a.seg[1].C == 8 && a.seg[1].nchunks >= 1)) return false;
+  if (y.mode != G_PLAIN || y.ntaps != 1 || y.scale != nullptr || (y.istride != 1 && y.istride != 2)) return false;
+  if (y.Hs != a.Ho * y.istride || y.Ws != a.Wo * y.istride) return false;
+  if (a.N % 64 || a.Npad < a.N || y.C != a.N) return false;
+  if (a.nphase < 0 || a.nphase > 4 || (a.nphase > 0 && a.nseg != 1)) return false;
+  WgpGeom q = {};
+  q.dymin = q.dxmin = 127;
   // a multi-phase launch whose phases differ in their tap counts (the ConvTranspose's 1, 2, 2, 4: WgradArgs::ph_ntaps): wgpw.hip only
   bool mixed = false;
   for (int ph = 0; ph < a.nphase; ++ph) mixed = mixed || (a.ph_ntaps[ph] != 0 && a.ph_ntaps[ph] != x.ntaps);
-  if (mixed && !(ws && y.q == nullptr && a.nphase == 4 && y.istride == 2)) return hipErrorNotSupported;
+  if (mixed && !(ws && y.q == nullptr && a.nphase == 4 && y.istride == 2)) return false;
   for (int ph = 0; ph < std::max(1, a.nphase); ++ph) {   // every phase: taps inside a 2x2 box, each offset once; parity inside the stride
     const short* taps = a.nphase > 0 ? a.ph_xtaps[ph] : x.taps;
     const int pnt = (a.nphase > 0 && a.ph_ntaps[ph] != 0) ? a.ph_ntaps[ph] : x.ntaps;
-    if (pnt != 1 && pnt != 2 && pnt != 4) return hipErrorNotSupported;
+    if (pnt != 1 && pnt != 2 && pnt != 4) return false;
     int ymin = 127, xmin = 127, ymax = -128, xmax = -128;
     bool seen[4] = {false, false, false, false};
     for (int t = 0; t < pnt; ++t) {
       const int dy = (int)(signed char)(taps[t] & 0xff), dx = (int)(signed char)((taps[t] >> 8) & 0xff);
       ymin = std::min(ymin, dy); ymax = std::max(ymax, dy); xmin = std::min(xmin, dx); xmax = std::max(xmax, dx);
     }
-    if (ymax - ymin > 1 || xmax - xmin > 1) return hipErrorNotSupported;
+    if (ymax - ymin > 1 || xmax - xmin > 1) return false;
     for (int t = 0; t < pnt; ++t) {
       const int dy = (int)(signed char)(taps[t] & 0xff) - ymin, dx = (int)(signed char)((taps[t] >> 8) & 0xff) - xmin;
-      if (seen[dy * 2 + dx]) return hipErrorNotSupported;
+      if (seen[dy * 2 + dx]) return false;
       seen[dy * 2 + dx] = true;
     }
     const int yt = a.nphase > 0 ? a.ph_ytap[ph] : y.taps[0];
     const int py = (int)(signed char)(yt & 0xff), px = (int)(signed char)((yt >> 8) & 0xff);
-    if (py < 0 || px < 0 || py >= y.istride || px >= y.istride) return hipErrorNotSupported;
-    if (a.nphase > 0 && a.ph_dpack[ph] == nullptr) return hipErrorNotSupported;
-    ph_dymin[ph] = ymin; ph_dxmin[ph] = xmin;
-    if (ph == 0) { dymin = ymin; dxmin = xmin; }
+    if (py < 0 || px < 0 || py >= y.istride || px >= y.istride) return false;
+    if (a.nphase > 0 && a.ph_dpack[ph] == nullptr) return false;
+    q.ph_dymin[ph] = ymin; q.ph_dxmin[ph] = xmin;
+    if (ph == 0) { q.dymin = ymin; q.dxmin = xmin; }
   }
   const int ntap = x.ntaps;
   const int nj = (ntap <= 2 && a.N % 128 == 0 && a.nphase == 0) ? 4 : 2;   // (multi-phase launches: 64 output channels per workgroup in every phase)
-  // Which form takes the launch is decided HERE, in front of the dry return: the family a plan records (wgrad_pick) must be one that
-  // really runs.  The wave-specialised form where it accepts; else this file's kernel, which forms its addresses in 64 bits (operands
-  // of 4 GiB and more) but has neither a one-tap form nor phases of different tap counts - those launches are refused, the plan then
-  // keeps the phases apart and picks per phase.
+  q.tiles_y = (a.Ho + WP_TH - 1) / WP_TH;
+  q.tiles_x = (a.Wo + WP_TW - 1) / WP_TW;
+  q.ntiles = a.B * q.tiles_y * q.tiles_x;
+  q.nct = x.C / WP_CA;
+  q.ncot = a.N / (32 * nj);
+  // Which form takes the launch: the wave-specialised one where it accepts; else this file's kernel, which forms its addresses in 64
+  // bits (operands of 4 GiB and more) but has neither a one-tap form nor phases of different tap counts - those launches are refused,
+  // the plan then keeps the phases apart and picks per phase.
   const int pq = y.q ? 2 : 0;
-  const bool use_ws = ws && pq == 0 && wgpw_accepts(a, ntap, nj);
-  if (!use_ws && (mixed || !((ntap == 4 && nj == 2) || (ntap == 2 && (nj == 4 || nj == 2))))) return hipErrorNotSupported;
-  if (g_ctl.dry) return hipSuccess;
-  WgpArgs g;
+  if (ws && pq == 0 && wgpw_resolve(a, dtype, ntap, nj, q, r)) { r.form = IMPL_WGPW; return true; }
+  if (mixed) return false;
+  WgpLaunch& l = r.put<WgpLaunch>();
+  WgpArgs& g = l.g;
   g.w = a;
-  g.dymin = dymin; g.dxmin = dxmin;
-  g.tiles_y = (a.Ho + WP_TH - 1) / WP_TH;
-  g.tiles_x = (a.Wo + WP_TW - 1) / WP_TW;
-  g.ntiles = a.B * g.tiles_y * g.tiles_x;
-  g.nct = x.C / WP_CA;
-  g.ncot = a.N / (32 * nj);
-  // one workgroup per CU (its accumulators fill the register file); every workgroup ends with NTAP x 128 x NCO x 4 bytes of atomics
-  static const int cus = [] { hipDeviceProp_t pr; int dev = 0; hipGetDevice(&dev);
-                              return (hipGetDeviceProperties(&pr, dev) == hipSuccess && pr.multiProcessorCount > 0) ? pr.multiProcessorCount : 256; }();
-  static const int target = lab_int("DMM_WGP_WGS", 0);
-  const int pairs = g.nct * g.ncot;
-  const int nph = std::max(1, a.nphase);
-  for (int ph = 0; ph < 4; ++ph) { g.ph_dymin[ph] = ph_dymin[ph]; g.ph_dxmin[ph] = ph_dxmin[ph]; }
-  // (multi-phase: the workgroups of all phases together fill the chip once; whole groups of 8 units, see the kernel)
-  int nsplit = std::max(1, ((target > 0 ? target : cus) / nph + pairs - 1) / pairs);
-  nsplit = std::min(nsplit, g.ntiles);
-  g.tiles_per_wg = (g.ntiles + nsplit - 1) / nsplit;
-  g.nsplit = (g.ntiles + g.tiles_per_wg - 1) / g.tiles_per_wg;
-  const int units = g.nsplit * pairs;
-  const int nwg = a.nphase > 0 ? ((units + 7) / 8) * 8 * nph : units;
-  if (use_ws) {
-    note_impl(IMPL_WGPW);   // (beside IMPL_WGP, which the dispatcher notes: the family is wgp, this says which form ran)
-    return launch_wgpw(a, dtype, ntap, nj, g.tiles_y, g.tiles_x, g.ntiles, g.tiles_per_wg, g.nsplit, g.nct, g.ncot, dymin, dxmin, ph_dymin, ph_dxmin,
-                       nwg, st);
-  }
-  if (trace) fprintf(stderr, "wgp: ntap %d nj %d pq %d pairs %d nsplit %d tiles/wg %d\n", ntap, nj, pq, pairs, g.nsplit, g.tiles_per_wg);
-  return dtype == DT_F16 ? launch_wgp_type<f16>(g, ntap, nj, pq, nwg, st) : launch_wgp_type<bf16>(g, ntap, nj, pq, nwg, st);
+  g.tiles_y = q.tiles_y; g.tiles_x = q.tiles_x; g.ntiles = q.ntiles; g.nct = q.nct; g.ncot = q.ncot; g.dymin = q.dymin; g.dxmin = q.dxmin;
+  for (int ph = 0; ph < 4; ++ph) { g.ph_dymin[ph] = q.ph_dymin[ph]; g.ph_dxmin[ph] = q.ph_dxmin[ph]; }
+  l.run = dtype == DT_F16 ? wgp_instance<f16>(ntap, nj, pq) : wgp_instance<bf16>(ntap, nj, pq);
+  return l.run != nullptr;
 }
 
-bool wgp_handles(const WgradArgs& a, int dtype) {
-  const LaunchCtl keep = g_ctl;
-  g_ctl.dry = true;
-  const hipError_t e = launch_wgp(a, dtype, nullptr);
-  g_ctl = keep;
-  return e == hipSuccess;
+// The device-dependent part of a launch of either form: the split of the tiles over workgroups.  Returns the workgroups.
+int wgp_split(int ntiles, int nct, int ncot, int nphase, int& tiles_per_wg, int& nsplit) {
+  // one workgroup per CU (its accumulators fill the register file); every workgroup ends with NTAP x 128 x NCO x 4 bytes of atomics
+  static const int cus = device_cus();
+  static const int target = lab_int("DMM_WGP_WGS", 0);
+  const int pairs = nct * ncot;
+  const int nph = std::max(1, nphase);
+  // (multi-phase: the workgroups of all phases together fill the chip once; whole groups of 8 units, see the kernel)
+  nsplit = std::max(1, ((target > 0 ? target : cus) / nph + pairs - 1) / pairs);
+  nsplit = std::min(nsplit, ntiles);
+  tiles_per_wg = (ntiles + nsplit - 1) / nsplit;
+  nsplit = (ntiles + tiles_per_wg - 1) / tiles_per_wg;
+  const int units = nsplit * pairs;
+  return nphase > 0 ? ((units + 7) / 8) * 8 * nph : units;
+}
+
+hipError_t wgp_launch(const Resolved& r, hipStream_t st) {
+  static const bool trace = lab_flag("DMM_WGP_TRACE");
+  if (trace) {
+    const WgradArgs& a = r.get<WgradArgs>();   // (the first member of either form's block)
+    const Seg &x = a.seg[0], &y = a.dy;
+    fprintf(stderr, "wgp? nseg %d x: mode %d istride %d Hs %d Ws %d (Ho %d Wo %d) scale %d C %d Cpad %d ntaps %d | y: mode %d ntaps %d istride %d Hs %d Ws %d C %d | N %d Npad %d\n",
+            a.nseg, x.mode, x.istride, x.Hs, x.Ws, a.Ho, a.Wo, x.scale != nullptr, x.C, x.Cpad, x.ntaps, y.mode, y.ntaps, y.istride, y.Hs, y.Ws, y.C, a.N, a.Npad);
+  }
+  if (r.form == IMPL_WGPW) {
+    note_impl(IMPL_WGPW);   // (beside IMPL_WGP, which the dispatcher notes: the family is wgp, this says which form ran)
+    return wgpw_launch(r, st);
+  }
+  const WgpLaunch& l = r.get<WgpLaunch>();
+  WgpArgs g = l.g;
+  const int nwg = wgp_split(g.ntiles, g.nct, g.ncot, g.w.nphase, g.tiles_per_wg, g.nsplit);
+  if (trace) fprintf(stderr, "wgp: ntap %d nj %d pq %d pairs %d nsplit %d tiles/wg %d\n", g.w.seg[0].ntaps, g.w.N / (32 * g.ncot), g.w.dy.q ? 2 : 0, g.nct * g.ncot, g.nsplit, g.tiles_per_wg);
+  return l.run(WP_LDS, nwg, NTHREADS, WP_LDS, st, g);
 }
 
 }  // namespace dmm

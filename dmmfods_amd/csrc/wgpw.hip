@@ -17,6 +17,7 @@
 #include <cstdlib>
 
 #include "common.h"
+#include "dispatch.h"
 #include "gather.h"
 
 namespace dmm {
@@ -340,61 +341,38 @@ __global__ __launch_bounds__(WW_NT, 1) void wgpw_multi_kernel(const WgpwArgs g) 
   else wgpw_body<T, 1, 2>(g, unit, P);
 }
 
-template <typename T>
-static hipError_t launch_wgpw_multi_t(const WgpwArgs& g, int nwg, hipStream_t st) {
-  auto kern = wgpw_multi_kernel<T>;
-  static bool attr_done = false;
-  if (!attr_done) {
-    const hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, WW_LDS);
-    if (e != hipSuccess) return e;
-    attr_done = true;
-  }
-  hipLaunchKernelGGL(kern, dim3(nwg), dim3(WW_NT), WW_LDS, st, g);
-  return hipGetLastError();
-}
+struct WgpwLaunch {
+  WgpwArgs g;
+  LdsLauncher<WgpwArgs> run;
+};
+int wgp_split(int ntiles, int nct, int ncot, int nphase, int& tiles_per_wg, int& nsplit);   // wgp.hip
 
-template <typename T, int NTAP, int NJ>
-static hipError_t launch_wgpw_t(const WgpwArgs& g, int nwg, hipStream_t st) {
-  auto kern = wgpw_kernel<T, NTAP, NJ>;
-  static bool attr_done = false;
-  if (!attr_done) {
-    const hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, WW_LDS);
-    if (e != hipSuccess) return e;
-    attr_done = true;
-  }
-  hipLaunchKernelGGL(kern, dim3(nwg), dim3(WW_NT), WW_LDS, st, g);
-  return hipGetLastError();
-}
-
-// What this form covers of the launches launch_wgp (wgp.hip) has validated: both operands below 4 GiB (32-bit byte offsets in the
-// loaders) and the kernel instantiations at the end of launch_wgpw.  launch_wgp asks BEFORE its dry return, so that the family a plan
-// records is decided with the same test the launch will meet; launch_wgpw asks again - one predicate, two callers, no second copy.
-bool wgpw_accepts(const WgradArgs& a, int ntap, int nj) {
+// Asked by wgp_resolve (wgp.hip) with a launch it has validated and cut up (`q`).  This form covers: both operands below 4 GiB (32-bit
+// byte offsets in the loaders) and the instantiations below; what it refuses stays with wgp.hip's own kernel.
+bool wgpw_resolve(const WgradArgs& a, int dtype, int ntap, int nj, const WgpGeom& q, Resolved& r) {
   if ((double)a.B * a.seg[0].Hs * a.seg[0].Ws * a.seg[0].ld * 2.0 >= 4294967296.0 || (double)a.B * a.dy.Hs * a.dy.Ws * a.dy.ld * 2.0 >= 4294967296.0)
     return false;
-  if (a.nphase == 4) return nj == 2;
-  if (a.nphase != 0) return false;
-  return (ntap == 4 && nj == 2) || (ntap == 2 && (nj == 4 || nj == 2)) || (ntap == 1 && (nj == 4 || nj == 2));
+  WgpwLaunch& l = r.put<WgpwLaunch>();
+  WgpwArgs& g = l.g;
+  g.w = a;
+  g.tiles_y = q.tiles_y; g.tiles_x = q.tiles_x; g.ntiles = q.ntiles; g.nct = q.nct; g.ncot = q.ncot; g.dymin = q.dymin; g.dxmin = q.dxmin;
+  for (int ph = 0; ph < 4; ++ph) { g.ph_dymin[ph] = q.ph_dymin[ph]; g.ph_dxmin[ph] = q.ph_dxmin[ph]; }
+  const bool f = dtype == DT_F16;
+  l.run = nullptr;
+  if (a.nphase == 4 && nj == 2) l.run = f ? launch_lds<wgpw_multi_kernel<f16>, WgpwArgs> : launch_lds<wgpw_multi_kernel<bf16>, WgpwArgs>;
+  else if (a.nphase != 0) return false;
+  else if (ntap == 4 && nj == 2) l.run = f ? launch_lds<wgpw_kernel<f16, 4, 2>, WgpwArgs> : launch_lds<wgpw_kernel<bf16, 4, 2>, WgpwArgs>;
+  else if (ntap == 2 && nj == 4) l.run = f ? launch_lds<wgpw_kernel<f16, 2, 4>, WgpwArgs> : launch_lds<wgpw_kernel<bf16, 2, 4>, WgpwArgs>;
+  else if (ntap == 2 && nj == 2) l.run = f ? launch_lds<wgpw_kernel<f16, 2, 2>, WgpwArgs> : launch_lds<wgpw_kernel<bf16, 2, 2>, WgpwArgs>;
+  else if (ntap == 1 && nj == 4) l.run = f ? launch_lds<wgpw_kernel<f16, 1, 4>, WgpwArgs> : launch_lds<wgpw_kernel<bf16, 1, 4>, WgpwArgs>;
+  else if (ntap == 1 && nj == 2) l.run = f ? launch_lds<wgpw_kernel<f16, 1, 2>, WgpwArgs> : launch_lds<wgpw_kernel<bf16, 1, 2>, WgpwArgs>;
+  return l.run != nullptr;
 }
 
-// Called by launch_wgp (wgp.hip) with a launch it has already validated and laid out; returns hipErrorNotSupported for the shapes this
-// form does not cover (wgpw_accepts).
-hipError_t launch_wgpw(const WgradArgs& a, int dtype, int ntap, int nj, int tiles_y, int tiles_x, int ntiles, int tiles_per_wg, int nsplit, int nct,
-                       int ncot, int dymin, int dxmin, const int* ph_dymin, const int* ph_dxmin, int nwg, hipStream_t st) {
-  if (!wgpw_accepts(a, ntap, nj)) return hipErrorNotSupported;
-  WgpwArgs g;
-  g.w = a;
-  g.tiles_y = tiles_y; g.tiles_x = tiles_x; g.ntiles = ntiles; g.tiles_per_wg = tiles_per_wg; g.nsplit = nsplit;
-  g.nct = nct; g.ncot = ncot; g.dymin = dymin; g.dxmin = dxmin;
-  for (int ph = 0; ph < 4; ++ph) { g.ph_dymin[ph] = ph_dymin[ph]; g.ph_dxmin[ph] = ph_dxmin[ph]; }
-  const bool f = dtype == DT_F16;
-  if (a.nphase == 4) return f ? launch_wgpw_multi_t<f16>(g, nwg, st) : launch_wgpw_multi_t<bf16>(g, nwg, st);
-  if (ntap == 4 && nj == 2) return f ? launch_wgpw_t<f16, 4, 2>(g, nwg, st) : launch_wgpw_t<bf16, 4, 2>(g, nwg, st);
-  if (ntap == 2 && nj == 4) return f ? launch_wgpw_t<f16, 2, 4>(g, nwg, st) : launch_wgpw_t<bf16, 2, 4>(g, nwg, st);
-  if (ntap == 2 && nj == 2) return f ? launch_wgpw_t<f16, 2, 2>(g, nwg, st) : launch_wgpw_t<bf16, 2, 2>(g, nwg, st);
-  if (ntap == 1 && nj == 4) return f ? launch_wgpw_t<f16, 1, 4>(g, nwg, st) : launch_wgpw_t<bf16, 1, 4>(g, nwg, st);
-  if (ntap == 1 && nj == 2) return f ? launch_wgpw_t<f16, 1, 2>(g, nwg, st) : launch_wgpw_t<bf16, 1, 2>(g, nwg, st);
-  return hipErrorNotSupported;
+hipError_t wgpw_launch(const Resolved& r, hipStream_t st) {
+  WgpwArgs g = r.get<WgpwLaunch>().g;
+  const int nwg = wgp_split(g.ntiles, g.nct, g.ncot, g.w.nphase, g.tiles_per_wg, g.nsplit);
+  return r.get<WgpwLaunch>().run(WW_LDS, nwg, WW_NT, WW_LDS, st, g);
 }
 
 }  // namespace dmm

@@ -16,6 +16,7 @@
 #include <type_traits>
 
 #include "common.h"
+#include "dispatch.h"
 #include "gather.h"
 
 namespace dmm {
@@ -426,56 +427,45 @@ template hipError_t launch_wt<bf16>(const WgradArgs&, bool, hipStream_t);
 extern template hipError_t launch_wt<float>(const WgradArgs&, bool, hipStream_t);
 extern template hipError_t launch_wt<bf16>(const WgradArgs&, bool, hipStream_t);
 
-hipError_t launch_wg3(const WgradArgs& a, int dtype, hipStream_t st);  // wg3.hip
-hipError_t launch_wgp(const WgradArgs& a, int dtype, hipStream_t st);  // wgp.hip
-hipError_t launch_wg5(const WgradArgs& a, int dtype, hipStream_t st);  // wg5.hip
-
-// Fills rows_per_split / kgroups (if zero) and launches.
-// Which family launch_wgrad(..., IMPL_AUTO) would run right now (nothing is launched).
-int wgrad_pick(const WgradArgs& a, int dtype, bool mfma) {
-  if (!mfma || a.M <= 0) return IMPL_GENERIC;
-  const LaunchCtl keep = g_ctl;
-  g_ctl.dry = true;
-  g_ctl.impl = IMPL_AUTO;
-  int took = IMPL_GENERIC;
-  if (launch_wg3(a, dtype, nullptr) == hipSuccess) took = IMPL_WG3;
-  else if (launch_wg5(a, dtype, nullptr) == hipSuccess) took = IMPL_WG5;
-  else if (launch_wgp(a, dtype, nullptr) == hipSuccess) took = IMPL_WGP;
-  g_ctl = keep;
-  return took;
-}
-
-struct CtlScope {  // the family a plan recorded is the only one allowed to take the launch while this is alive
-  LaunchCtl keep;
-  explicit CtlScope(int impl) : keep(g_ctl) { g_ctl.dry = false; g_ctl.impl = impl; }
-  ~CtlScope() { g_ctl = keep; }
+// The special-case families in dispatch order.
+static const WgradFamily kWgradFamilies[] = {
+    {IMPL_WG3, wg3_enabled, wg3_resolve, wg3_launch},  // the dense layers' 3x3 growth convolution: persistent tiles, the whole result in registers
+    {IMPL_WG5, wg5_enabled, wg5_resolve, wg5_launch},  // the head's 5x5 convolution onto 3 classes: persistent tiles, the 25 x 8 (tap, class) columns as per-lane addresses
+    {IMPL_WGP, wgp_enabled, wgp_resolve, wgp_launch},  // parity-phase convolutions (ConvTranspose stages, the head's 3x3 over the upsampled map): all taps of a phase per tile
 };
 
+// The first family that may take the launch (family_allowed) and resolves it; nullptr: none does - the launch is the generic kernel's.
+static const WgradFamily* wgrad_family(const WgradArgs& a, int dtype, int impl, unsigned deny, Resolved& r) {
+  for (const WgradFamily& f : kWgradFamilies)
+    if (family_allowed(f, impl, deny) && f.resolve(a, dtype, r)) return &f;
+  return nullptr;
+}
+
+// Which family launch_wgrad(..., IMPL_AUTO) would run right now, `deny` taken out (nothing is launched, the runtime is not asked anything).
+int wgrad_pick(const WgradArgs& a, int dtype, bool mfma, unsigned deny) {
+  if (!mfma || a.M <= 0) return IMPL_GENERIC;
+  Resolved r;
+  const WgradFamily* f = wgrad_family(a, dtype, IMPL_AUTO, deny, r);
+  return f ? f->family : IMPL_GENERIC;
+}
+
+// Fills rows_per_split / kgroups (if zero) and launches.  impl: as launch_igemm.
 hipError_t launch_wgrad(WgradArgs a, int dtype, bool mfma, hipStream_t st, int impl) {
   if (a.M <= 0) return hipSuccess;
-  const CtlScope scope(impl);
-  const bool special = mfma && impl != IMPL_GENERIC;
   bool wgp_took = false;
-  if (special) {  // the dense layers' 3x3 growth convolution: persistent tiles, the whole result in registers
-    const hipError_t e = launch_wg3(a, dtype, st);
-    if (e != hipErrorNotSupported) { note_impl(IMPL_WG3); return e; }
-  }
-  if (special) {  // the head's 5x5 convolution onto 3 classes: persistent tiles, the 25 x 8 (tap, class) columns as per-lane addresses
-    const hipError_t e = launch_wg5(a, dtype, st);
-    if (e != hipErrorNotSupported) { note_impl(IMPL_WG5); return e; }
-  }
-  if (special) {  // parity-phase convolutions (ConvTranspose stages, the head's 3x3 over the upsampled map): all taps of a phase per tile
-    const hipError_t e = launch_wgp(a, dtype, st);
-    if (e == hipSuccess) {
-      note_impl(IMPL_WGP);
-      wgp_took = true;
-      if (a.nseg == 1) return e;
-      // the 8-channel raw-input segment of the head convolution stays with the generic kernel: its chunks follow segment 0's
-      a.dpack += (size_t)a.seg[0].nchunks * a.Npad * 32;
-      a.seg[0] = a.seg[1];
-      a.nseg = 1;
-      a.rows_per_split = 0;
-    } else if (e != hipErrorNotSupported) return e;
+  Resolved r;
+  if (const WgradFamily* f = (mfma && impl != IMPL_GENERIC) ? wgrad_family(a, dtype, impl, 0, r) : nullptr) {
+    const hipError_t e = f->launch(r, st);
+    if (f->family != IMPL_WGP) { note_impl(f->family); return e; }
+    if (e != hipSuccess) return e;
+    note_impl(IMPL_WGP);
+    wgp_took = true;
+    if (a.nseg == 1) return e;
+    // the 8-channel raw-input segment of the head convolution stays with the generic kernel: its chunks follow segment 0's
+    a.dpack += (size_t)a.seg[0].nchunks * a.Npad * 32;
+    a.seg[0] = a.seg[1];
+    a.nseg = 1;
+    a.rows_per_split = 0;
   }
   // what the generic kernel does not implement must fail here, not compute something else (as launch_igemm): merged parity phases
   // and per-phase tap counts belong to wgp, the factor forms (sbuf) to wg5 - the generic kernel would compute phase 0 alone / write dpack

@@ -282,7 +282,8 @@ def test_plan_dump_is_canonical(host_drive):
     builds of the plan builder can be compared byte for byte without a GPU (a refactor of plan.cpp is checked that way).  For that the
     text must depend on the plan alone: two runs agree, and so does a third with the workspace and the three arenas mapped somewhere
     else (pointers are printed as region+offset); no pointer lies outside the plan's regions; and the lists it prints are the lists the
-    life-cycle run of the same case executes (same record counts)."""
+    life-cycle run of the same case executes (same record counts).  A fourth run has the fake runtime trace every launch, attribute
+    and device-property call (DRIVE_TRACE_LAUNCHES): building and binding a plan makes none - picking kernel families is free of the runtime."""
     base = {k: v for k, v in os.environ.items() if not k.startswith("DMM_") and not k.startswith("DRIVE_")}
     base.update(ASAN_OPTIONS="detect_leaks=0:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
     for case in (("tiny_mid", "bf16", 2, 96, 160, {}), ("d121e", "f16", 2, 64, 96, {})):
@@ -290,11 +291,12 @@ def test_plan_dump_is_canonical(host_drive):
         arch, dtype, b, h, w, envx = case
         args = [arch, dtype, str(b), str(h), str(w)]
         outs = []
-        for extra in ({}, {}, {"DRIVE_MAP_SHIFT_MIB": "6"}):
+        for extra in ({}, {}, {"DRIVE_MAP_SHIFT_MIB": "6"}, {"DRIVE_TRACE_LAUNCHES": "1"}):
             r = subprocess.run([host_drive, "dump"] + args, env=dict(base, **envx, **extra), capture_output=True, text=True, timeout=600)
             assert r.returncode == 0, (case, extra, (r.stdout[-500:] + r.stderr)[-3000:])
             outs.append(r.stdout)
-        assert outs[0] == outs[1] == outs[2], case
+        assert "[fakehip]" not in r.stderr, (case, r.stderr[-2000:])
+        assert outs[0] == outs[1] == outs[2] == outs[3], case
         assert "OUTSIDE" not in outs[0] and "ws+" in outs[0] and "params+" in outs[0] and "grads+" in outs[0] and "buffers+" in outs[0]
         records = {m[1]: int(m[2]) for m in re.finditer(r"^list (\w+) records=(\d+)$", outs[0], re.M)}
         assert set(records) == {"fwd_train", "fwd_eval", "bwd"}, records
@@ -352,9 +354,9 @@ GIB4 = 1 << 32
 
 
 def test_recorded_family_takes_every_launch(host_drive):
-    """A plan decides the kernel family of every convolution launch while it is built (igemm_pick / wgrad_pick: a dry call of the
-    launchers) and shapes its launch list around the decision - merged parity phases, finish launches, compact gradients.  The family
-    that takes the launch at run time must be that one.  `drive picks` binds the plan to address space that is never touched and calls
+    """A plan decides the kernel family of every convolution launch while it is built (igemm_pick / wgrad_pick: the first
+    family of the dispatch table whose resolve accepts the launch) and shapes its launch list around the decision - merged parity
+    phases, finish launches, compact gradients.  The family that takes the launch at run time must be that one.  `drive picks` binds the plan to address space that is never touched and calls
     the launcher of every OP_IGEMM / OP_WGRAD / OP_BW1 record with the recorded family under the fake runtime: the recorded family must
     be among those that noted the launch, the generic family must not be noted beside another (but for wgp's two-segment launch, whose
     8-channel remainder is the generic kernel's), the call must succeed.
@@ -375,7 +377,7 @@ def test_recorded_family_takes_every_launch(host_drive):
     cases = [(a, d, b, h, w, e) for a, d, b, h, w, e in HOST_DRIVE_CASES]
     first = lambda h, w: -(-GIB4 // (2 * 64 * h * w))
     assert first(1280, 1920) == 14 and first(640, 960) == 55
-    # the next crossing: 128 channels at half resolution - the head's forward input (hf.hip:382) and the last decoder stage's gradient
+    # the next crossing: 128 channels at half resolution - the head's forward input (hf.hip:370) and the last decoder stage's gradient
     first_half = -(-GIB4 // (2 * 128 * 640 * 960))
     assert first_half == 28
     cases += [("d121e", dt, b, 1280, 1920, {}) for dt in ("f16", "bf16") for b in (13, 14, first_half - 1, first_half, 56)]
@@ -404,7 +406,7 @@ def test_recorded_family_takes_every_launch(host_drive):
             r0 = head["wgp.n64/h.refine0"]
             # the head's weight gradient stays ONE merged launch on either side of the limit; the form of the kernel changes
             assert r0["nphase"] == 4 and r0["mask"] == (FAMILY_BIT["wgp"] | (FAMILY_BIT["wgpw"] if b < 14 else 0)), (case, r0)
-            # hf.hip:382 (the head's forward; no single-kernel entry point builds its two segments): hf below 4 GiB of half-resolution
+            # hf.hip:370 (the head's forward; no single-kernel entry point builds its two segments): hf below 4 GiB of half-resolution
             # input (batch 27: 4246732800 bytes), conv3 from batch 28 on
             hf = [p for p in picks if p["list"] == "fwd" and p["label"].endswith("/h.refine0")]
             assert len(hf) == 1 and hf[0]["recorded"] == ("hf" if b < first_half else "conv3"), (case, hf)
@@ -446,15 +448,15 @@ def test_family_refusal_boundaries_single_launch(host_drive):
     """Every family that addresses an operand with 32-bit byte offsets refuses operands of 4 GiB and more.  Through the single-kernel
     entry points under the fake runtime (the large operands are PROT_NONE address space: a host access would be a fault; what the entry
     points zero or upload is real memory), one shape just below each guard and one at it, all in 16-bit storage (2 bytes):
-      pig.hip:255      1x1 forward, 128 channels:          2 * M * 128             -> M = 4095 * 4096 | 4096 * 4096;  fallback generic
-      bw1.hip:438-439  fused 1x1 backward, 128 -> 128:     2 * M * 128 (x, gx, dy)  -> the same M;  at the limit DMM_ERR_INVALID (header), and
+      pig.hip:265      1x1 forward, 128 channels:          2 * M * 128             -> M = 4095 * 4096 | 4096 * 4096;  fallback generic
+      bw1.hip:431-432  fused 1x1 backward, 128 -> 128:     2 * M * 128 (x, gx, dy)  -> the same M;  at the limit DMM_ERR_INVALID (header), and
                        the pair of entry points a caller uses instead (dmm_conv_dgrad_ex, dmm_conv_wgrad_ex) runs the generic kernels
-      cf.hip:258       dense 3x3 forward, 128 -> 32:       2 * B * H * W * 128     -> 4088 x 4096 | 4096 x 4096 (whole 8 x 16 tiles);  conv3
-      cvw.hip:389      ConvTranspose forward, 128 -> 128:  2 * B * H * W * 128     -> 4095 x 4096 | 4096 x 4096;  cvp without its cvw form
-                       (cvw.hip:390, the packed weights' span, cannot be reached: cvw takes at most 256 input channels)
-      wgpw.hip:374     ConvTranspose weight gradient:      2 * B * 2H * 2W * 128 (dy) -> 2047 x 2048 | 2048 x 2048;  wgp.hip's own kernel for
+      cf.hip:248       dense 3x3 forward, 128 -> 32:       2 * B * H * W * 128     -> 4088 x 4096 | 4096 x 4096 (whole 8 x 16 tiles);  conv3
+      cvw.hip:376      ConvTranspose forward, 128 -> 128:  2 * B * H * W * 128     -> 4095 x 4096 | 4096 x 4096;  cvp without its cvw form
+                       (cvw.hip:377, the packed weights' span, cannot be reached: cvw takes at most 256 input channels)
+      wgpw.hip:353     ConvTranspose weight gradient:      2 * B * 2H * 2W * 128 (dy) -> 2047 x 2048 | 2048 x 2048;  wgp.hip's own kernel for
                        the 2- and 4-tap phases, the generic kernel for the one-tap phase (wgp.hip has no one-tap form)
-    hf.hip:382 needs the head's two-segment launch, which no entry point builds: test_recorded_family_takes_every_launch covers it in a plan.
+    hf.hip:370 needs the head's two-segment launch, which no entry point builds: test_recorded_family_takes_every_launch covers it in a plan.
     dmm_last_impl names the dispatcher's family (cvp, wgp) with either form; the mask says which form ran."""
     below = _single(host_drive, "fwd", "f16", 1, 4095, 4096, 128, 128, 1, 0)
     at = _single(host_drive, "fwd", "f16", 1, 4096, 4096, 128, 128, 1, 0)

@@ -14,6 +14,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <map>
 #include <mutex>
 #include <set>
 #include <string>
@@ -32,6 +33,12 @@ long g_launches = 0, g_violations = 0, g_stream_creates = 0, g_event_creates = 0
 int g_next_id = 1;
 std::vector<std::string> g_violation_log;
 bool g_trace = getenv("FAKEHIP_TRACE") != nullptr;
+// DRIVE_TRACE_LAUNCHES: one line on stderr per hipLaunchKernel (kernel name, grid, block, dynamic LDS bytes), per hipFuncSetAttribute
+// (kernel name, value) and per hipGetDeviceProperties - what the launchers ask of the runtime, to compare two builds line for line
+bool launch_trace() { static const bool on = getenv("DRIVE_TRACE_LAUNCHES") != nullptr; return on; }
+// host stub -> device name of every registered kernel (filled by static constructors of other translation units: no global object)
+std::map<const void*, std::string>& kernel_names() { static auto* m = new std::map<const void*, std::string>(); return *m; }
+const char* kernel_name(const void* func) { auto it = kernel_names().find(func); return it == kernel_names().end() ? "?" : it->second.c_str(); }
 
 void violation(const std::string& what) {
   ++g_violations;
@@ -67,7 +74,7 @@ extern "C" {
 // ---- registration stubs emitted by the host side of a HIP translation unit ----
 void** __hipRegisterFatBinary(const void*) { static void* h = nullptr; return &h; }
 void __hipUnregisterFatBinary(void**) {}
-void __hipRegisterFunction(void**, const void*, char*, const char*, unsigned, void*, void*, void*, void*, int*) {}
+void __hipRegisterFunction(void**, const void* host, char*, const char* name, unsigned, void*, void*, void*, void*, int*) { kernel_names()[host] = name; }
 void __hipRegisterVar(void**, void*, char*, const char*, int, size_t, int, int) {}
 static thread_local struct { dim3 g, b; size_t sh; hipStream_t st; } t_cfg;
 hipError_t __hipPushCallConfiguration(dim3 g, dim3 b, size_t sh, hipStream_t st) { t_cfg = {g, b, sh, st}; return hipSuccess; }
@@ -83,6 +90,7 @@ hipError_t hipLaunchKernel(const void* func, dim3 grid, dim3 block, void** args,
   if (shmem > 160 * 1024) { violation("hipLaunchKernel: more than 160 KB of dynamic LDS"); return hipErrorInvalidConfiguration; }
   if ((unsigned long long)grid.x * grid.y * grid.z > 0x7fffffffull) { violation("hipLaunchKernel: grid too large"); return hipErrorInvalidConfiguration; }
   (void)args;
+  if (launch_trace()) fprintf(stderr, "[fakehip] launch %s grid %u %u %u block %u %u %u lds %zu\n", kernel_name(func), grid.x, grid.y, grid.z, block.x, block.y, block.z, shmem);
   ++g_launches;
   ++s->pending;
   return hipSuccess;
@@ -90,10 +98,14 @@ hipError_t hipLaunchKernel(const void* func, dim3 grid, dim3 block, void** args,
 
 hipError_t hipGetLastError(void) { return hipSuccess; }
 const char* hipGetErrorString(hipError_t e) { return e == hipSuccess ? "no error" : "fake HIP error"; }
-hipError_t hipFuncSetAttribute(const void*, hipFuncAttribute, int) { return hipSuccess; }
+hipError_t hipFuncSetAttribute(const void* func, hipFuncAttribute attr, int value) {
+  if (launch_trace()) fprintf(stderr, "[fakehip] attribute %s %d = %d\n", kernel_name(func), (int)attr, value);
+  return hipSuccess;
+}
 hipError_t hipGetDevice(int* d) { *d = 0; return hipSuccess; }
 hipError_t hipGetDeviceCount(int* n) { *n = 1; return hipSuccess; }
 hipError_t hipGetDevicePropertiesR0600(hipDeviceProp_tR0600* p, int) {
+  if (launch_trace()) fprintf(stderr, "[fakehip] device properties\n");
   memset(p, 0, sizeof(*p));
   p->multiProcessorCount = 256;
   p->sharedMemPerBlock = 160 * 1024;
