@@ -332,7 +332,9 @@ hipError_t launch_maxpool_bwd(const MaxpoolBwdArgs& a, int dtype, hipStream_t st
 // ---------------------------------------------------------------------------------------------------
 // out[] (doubles): [0..NC) loss sums, [NC..2NC) equal counts, then per image b: inter[NC], union[NC]
 // Per-element loss and its derivative.  kind 0: BCE; kind 1: focal  F = alpha*(1-pt)^gamma*bce with pt = exp(-bce), so
-// dF/dx = alpha*(1-pt)^(gamma-1) * bce' * (gamma*pt*bce + (1-pt))   (d(1-pt)/dx = pt*bce').
+// dF/dx = alpha*(1-pt)^gamma * bce' * (gamma*pt*bce/(1-pt) + 1)   (d(1-pt)/dx = pt*bce').
+// Only (1-pt)^gamma is ever formed: (1-pt)^(gamma-1) overflows for gamma < 0.14 once 1-pt is a denormal (a confidently right logit of
+// magnitude 88.8 .. 103; gamma = 0, plain alpha-weighted BCE, then gives loss = inf), while bce/(1-pt) runs from 1 (bce -> 0) to bce.
 __device__ __forceinline__ void loss_elem(const BceArgs& a, int n, float x, float t, float& loss, float& dx) {
   float bce, dbce;
   if (!a.from_prob) {
@@ -340,19 +342,20 @@ __device__ __forceinline__ void loss_elem(const BceArgs& a, int n, float x, floa
     bce = fmaxf(x, 0.f) - x * t + log1pf(e);
     const float sig = x >= 0.f ? 1.f / (1.f + e) : e / (1.f + e);
     dbce = sig - t;
-  } else {  // torch.binary_cross_entropy: logs clamped at -100
-    const float lp = fmaxf(logf(x), -100.f), lq = fmaxf(logf(1.f - x), -100.f);
+  } else {  // torch.binary_cross_entropy: logs clamped at -100; its derivative (x - t) / (x (1 - x)) with the denominator clamped at 1e-12
+    // log(1 - x) as log1pf(-x): below x = 1e-4 the rounding of 1 - x alone is 1e-3 of the result and more
+    const float lp = fmaxf(logf(x), -100.f), lq = fmaxf(log1pf(-x), -100.f);
     bce = -(t * lp + (1.f - t) * lq);
-    dbce = -(t * (lp > -100.f ? 1.f / x : 0.f) - (1.f - t) * (lq > -100.f ? 1.f / (1.f - x) : 0.f));
+    dbce = (x - t) / fmaxf((1.f - x) * x, 1e-12f);
   }
   if (a.kind == 0) { loss = bce; dx = dbce; return; }
   const float al = a.alpha[n], ga = a.gamma[n];
-  const float omp = -expm1f(-bce);  // 1 - pt, without cancellation for small bce
+  const float omp = fmaxf(-expm1f(-bce), 0.f);  // 1 - pt, without cancellation for small bce (bce may round to -0)
   const float pt = 1.f - omp;
-  if (!(omp > 0.f)) { loss = 0.f; dx = 0.f; return; }
-  const float pw1 = powf(omp, ga - 1.f);
-  loss = al * pw1 * omp * bce;
-  dx = al * pw1 * dbce * fmaf(ga * pt, bce, omp);
+  const float pw = powf(omp, ga);   // (0^0 = 1: gamma = 0 stays BCE where bce rounds to 0)
+  const float ratio = omp > 0.f ? bce / omp : 1.f;
+  loss = al * pw * bce;
+  dx = al * pw * dbce * fmaf(ga * pt, ratio, 1.f);
 }
 
 template <typename T>
