@@ -18,6 +18,7 @@
 #include "common.h"
 #include "dispatch.h"
 #include "gather.h"
+#include "isa.h"
 #include "pointwise.h"
 
 namespace dmm {
@@ -54,19 +55,6 @@ constexpr int B1_LDS = 2 * B1_IMG + B1_W + 2 * B1_CT * 8 + 6 * B1_CT * 4;  // + 
 // GEMM).  The 64-byte granule is XOR-ed with (row & 3), the slot inside it with (row >> 2) & 3: 16 rows hit 16 different slots, 4
 // consecutive rows 4 different granules, and a 32-byte span stays inside its granule.  Rows 16 apart share the permutation.
 __device__ __forceinline__ int b1_swz(int row, int slot) { return ((((slot >> 2) ^ (row & 3)) << 2) | ((slot & 3) ^ ((row >> 2) & 3))); }
-
-typedef unsigned b1_u32x2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ b1_u32x2 b1_tr16(const unsigned char* p) {
-  typedef __fp16 h4 __attribute__((__vector_size__(4 * sizeof(__fp16))));
-  h4 r = __builtin_amdgcn_ds_read_tr16_b64_v4f16((__attribute__((address_space(3))) h4*)(p));
-  return __builtin_bit_cast(b1_u32x2, r);
-}
-template <typename T>
-__device__ __forceinline__ typename TT<T>::vec b1_frag(const b1_u32x2& lo, const b1_u32x2& hi) {
-  typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-  const u32x4 v = {lo[0], lo[1], hi[0], hi[1]};
-  return __builtin_bit_cast(typename TT<T>::vec, v);
-}
 
 // PQ = prologue of G: 0 none (materialised gradient), 2 effective gradient.  ACC = the gradient of x is accumulated (an earlier
 // consumer of the block buffer has already written it).
@@ -262,10 +250,10 @@ __global__ __launch_bounds__(NTHREADS, 2) void bw1_kernel(const Bw1Args g) {
     if (!(B1_DBG & 2))
 #pragma unroll
     for (int ms = 0; ms < B1_TM / 16; ++ms) {
-      const V af = b1_frag<T>(b1_tr16(Ai + aoff1 + ms * 4096), b1_tr16(Ai + second(aoff1) + ms * 4096));
+      const V af = frag16<T>(lds_tr16(Ai + aoff1 + ms * 4096), lds_tr16(Ai + second(aoff1) + ms * 4096));
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
-        const V gf = b1_frag<T>(b1_tr16(Gi + goff1[j] + ms * 4096), b1_tr16(Gi + second(goff1[j]) + ms * 4096));
+        const V gf = frag16<T>(lds_tr16(Gi + goff1[j] + ms * 4096), lds_tr16(Gi + second(goff1[j]) + ms * 4096));
         accw[j] = mma16(gf, af, accw[j]);  // rows: bottleneck channel n, columns: input channel c
       }
     }
@@ -285,10 +273,9 @@ __global__ __launch_bounds__(NTHREADS, 2) void bw1_kernel(const Bw1Args g) {
 #endif
 #if B1_RAW_BAR
     // (experiment) The next tile's operands, requested BEHIND the old gradient: the epilogue's wait for the old gradient then leaves these twelve
-    // loads in flight, and the barriers from here to the end of the tile are raw s_barrier instructions behind an LDS-only wait -
-    // __syncthreads() is a fence (s_waitcnt vmcnt(0) on gfx9) and drained the prefetch at the first barrier behind it, half a
-    // microsecond after it had been issued.
-    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");  // all waves done with the images: stage the data-gradient tile over them
+    // loads in flight, and the barriers from here to the end of the tile are raw barriers behind an LDS-only wait (isa.h):
+    // __syncthreads() drained the prefetch at the first barrier behind it, half a microsecond after it had been issued.
+    lds_barrier();  // all waves done with the images: stage the data-gradient tile over them
 #else
     __syncthreads();  // all waves done with the images: stage the data-gradient tile over them
 #endif
@@ -311,7 +298,7 @@ __global__ __launch_bounds__(NTHREADS, 2) void bw1_kernel(const Bw1Args g) {
         Cs[row * B1_CT + ((dcb + 32 * t + r) ^ (h << 5))] = accd[t][i];
       }
 #if B1_RAW_BAR
-    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+    lds_barrier();
 #else
     __syncthreads();
 #endif
@@ -360,7 +347,7 @@ __global__ __launch_bounds__(NTHREADS, 2) void bw1_kernel(const Bw1Args g) {
     fold_to_lds<16, SLOT, B1_CT>(s1, s2, red, cs, cvalid, lane);
     }  // (epilogue)
 #if B1_RAW_BAR
-    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");  // staging read: the next tile's images may be written
+    lds_barrier();  // staging read: the next tile's images may be written
 #else
     __syncthreads();  // staging read: the next tile's images may be written
 #endif

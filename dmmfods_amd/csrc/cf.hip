@@ -6,7 +6,7 @@
 // CU whose halo / K loop / epilogue stretches add up.  Here a workgroup is EIGHT waves, one per CU, persistent over a contiguous range
 // of 8 x 16-pixel tiles:
 //   * the packed weights (36 chunks x 32 columns = 72 KB) are copied to LDS once and stay;
-//   * waves 4-7 (loader waves) own the global loads (inline assembly, FOUR register sets: two items ahead, counted waits - wg3.hip),
+//   * waves 4-7 (loader waves) own the global loads (inline assembly, FOUR register sets: two items ahead, counted waits - isa.h),
 //     the BN+ReLU prologue and the LDS images; waves 0-3 (matrix waves) do fragment reads, MFMAs and a wave-local epilogue;
 //   * an item is TWO K stretches over 64-channel half images of the 10 x 18-pixel halo (144-byte pixel pitch): while the matrix waves
 //     multiply one half the loaders fill the other - two raw barriers per item;
@@ -20,6 +20,7 @@
 #include "common.h"
 #include "dispatch.h"
 #include "gather.h"
+#include "isa.h"
 
 namespace dmm {
 
@@ -35,7 +36,7 @@ constexpr int CF_OFF_A0 = CF_W, CF_OFF_A1 = CF_OFF_A0 + CF_HALF, CF_OFF_STG = CF
 constexpr int CF_LDS = CF_OFF_STG + 4 * CF_STG;             // 140288
 constexpr int CF_NT = 512, CF_NL = 256;
 constexpr int CF_NU = (CF_HH * CF_HW * 8 + CF_NL - 1) / CF_NL;   // 6 half-image slots per loader thread
-static_assert(CF_LDS <= 160 * 1024 && CF_NU == 6, "LDS budget / operand lists of the waits");
+static_assert(CF_LDS <= 160 * 1024, "LDS budget");
 
 struct CfArgs {
   ConvArgs c;
@@ -43,19 +44,12 @@ struct CfArgs {
   int dymin, dxmin;                    // origin of the tap box
 };
 
-__device__ __forceinline__ void cf_bar() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-template <typename V>
-__device__ __forceinline__ void cf_load(V& dst, unsigned off, const void* base) {
-  asm volatile("global_load_dwordx4 %0, %1, %2" : "=v"(dst) : "v"(off), "s"(base));
-}
-// Four sets of 6 requests in flight, issued set by set (see hf.hip / wg3.hip): the oldest set is followed by 18 younger requests.
-template <typename V>
-__device__ __forceinline__ void cf_wait(V (&u)[CF_NU]) {
-  asm volatile("s_waitcnt vmcnt(18)" : "+v"(u[0]), "+v"(u[1]), "+v"(u[2]), "+v"(u[3]), "+v"(u[4]), "+v"(u[5]));
-}
-template <typename V>
-__device__ __forceinline__ void cf_hold(V (&u)[CF_NU]) {   // everything lands; the set is alive until here
-  asm volatile("s_waitcnt vmcnt(0)" : "+v"(u[0]), "+v"(u[1]), "+v"(u[2]), "+v"(u[3]), "+v"(u[4]), "+v"(u[5]));
+// FOUR sets of CF_NU requests in flight (isa.h: inline assembly, uniform base + 32-bit offset), issued set by set.
+// LAND false: the oldest set has landed, the three younger ones stay in flight; true: everything lands, the set is alive until here
+template <bool LAND, typename V>
+__device__ __forceinline__ void cf_sync(V (&u)[CF_NU]) {
+  static_assert(CF_NU == 6, "DMM_V6 below");
+  DMM_VM_WAIT(LAND ? 0 : 3 * CF_NU, DMM_V6(u));
 }
 
 template <typename T>
@@ -118,14 +112,15 @@ __global__ __launch_bounds__(CF_NT, 2) void cf_kernel(const CfArgs g) {
         const int sy = yb + hyu[i], sx = xb + hxu[i];
         if (px0 + 32 * i < CF_HH * CF_HW && (unsigned)sy < (unsigned)sg.Hs && (unsigned)sx < (unsigned)sg.Ws) R.ok |= 1u << i;
         const unsigned pix = (unsigned)((row0 + min(max(sy, 0), sg.Hs - 1)) * sg.Ws + min(max(sx, 0), sg.Ws - 1));
-        cf_load(R.u[i], pix * upix + ucol + half_off, ubase);
+        const unsigned off = pix * upix + ucol + half_off;
+        gload16(R.u[i], ubase, off);
       }
     };
     V z;
 #pragma unroll
     for (int e = 0; e < SLOT; ++e) z[e] = (T)0;
     auto store = [&](Set& R, const SlotK<SLOT>& k, unsigned char* img) {
-      cf_wait(R.u);
+      cf_sync<false>(R.u);
 #pragma unroll
       for (int i = 0; i < CF_NU; ++i)
         if (px0 + 32 * i < CF_HH * CF_HW) *(V*)(img + ldsu[i]) = ((R.ok >> i) & 1) ? bn_relu_slot(R.u[i], k) : z;   // zero padding AFTER the prologue
@@ -141,10 +136,10 @@ __global__ __launch_bounds__(CF_NT, 2) void cf_kernel(const CfArgs g) {
     // one item: barrier X (half 0 complete / half 1 free), request half 0 of item it + 2 into the set just emptied, write half 1;
     // barrier Y (half 1 complete / half 0 free), request half 1 of item it + 2, write half 0 of item it + 1
     auto item = [&](int it, Set& P, Set& Q, Set& Pn) {
-      cf_bar();
+      lds_barrier();
       issue(P, it + 2, 0u);
       store(Q, k1, smem + CF_OFF_A1);
-      cf_bar();
+      lds_barrier();
       issue(Q, it + 2, 128u);
       store(Pn, k0, smem + CF_OFF_A0);
     };
@@ -154,7 +149,7 @@ __global__ __launch_bounds__(CF_NT, 2) void cf_kernel(const CfArgs g) {
       item(it + 1, Pb, Qb, Pa);
     }
     if (nit & 1) item(nit - 1, Pa, Qa, Pb);
-    cf_hold(Pa.u); cf_hold(Pb.u); cf_hold(Qa.u); cf_hold(Qb.u);
+    cf_sync<true>(Pa.u); cf_sync<true>(Pb.u); cf_sync<true>(Qa.u); cf_sync<true>(Qb.u);
     return;
   }
 
@@ -178,7 +173,7 @@ __global__ __launch_bounds__(CF_NT, 2) void cf_kernel(const CfArgs g) {
     f32x16 acc;
 #pragma unroll
     for (int i = 0; i < 16; ++i) acc[i] = 0.f;
-    cf_bar();   // barrier X(it)
+    lds_barrier();   // barrier X(it)
     {
       const unsigned char* A = smem + CF_OFF_A0 + abase;
 #pragma unroll
@@ -192,7 +187,7 @@ __global__ __launch_bounds__(CF_NT, 2) void cf_kernel(const CfArgs g) {
             acc = mma16(av, bv, acc);
           }
     }
-    cf_bar();   // barrier Y(it)
+    lds_barrier();   // barrier Y(it)
     {
       const unsigned char* A = smem + CF_OFF_A1 + abase;
 #pragma unroll

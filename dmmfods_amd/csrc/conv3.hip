@@ -13,7 +13,7 @@
 //      applied ONCE per element and the result is written to an LDS image [halo row][halo pixel][channel]; pixels outside the
 //      picture are zero AFTER the prologue, as in conv(relu(bn(x)));
 //   2. the K loop walks the packed-weight chunks in groups: a tap only shifts the LDS address of the A fragment, the weights
-//      stream through a 3-deep ring filled by LDS-DMA two groups ahead (global_load_lds_dwordx4 from inline asm, swizzle on the
+//      stream through a 3-deep ring filled by LDS-DMA two groups ahead (isa.h lds_dma16: from inline asm, swizzle on the
 //      source address; counted vmcnt + raw s_barrier, so the DMA stays in flight across the barrier);
 //   3. epilogues as in igemm.hip: store + BatchNorm statistics (forward; the statistics are reduced straight from the
 //      accumulator layout), or fused BN/ReLU backward (data gradient).
@@ -28,6 +28,7 @@
 #include "common.h"
 #include "dispatch.h"
 #include "gather.h"
+#include "isa.h"
 
 namespace dmm {
 
@@ -137,8 +138,7 @@ __global__ __launch_bounds__(NTHREADS, 2) void conv3_kernel(const Conv3Args g) {
   decode(lt);
 
   // ---- the first two weight groups start streaming now ----
-  // LDS-DMA issued from inline asm: hipcc does not count it, so it does not drain it (vmcnt(0)) in front of the next ds_read
-  // as it does for the builtin (it cannot prove that the LDS ranges differ); the waits are the counted ones in the K loop.
+  // LDS-DMA issued from inline asm (isa.h lds_dma16: hipcc does not count it); the waits are the counted ones in the K loop.
   const T* wp = (const T*)a.wpack;   // (per phase in a multi-phase launch: set at the top of the tile loop)
   int woff[NPW];   // per-lane source offset (elements) inside a group's block (the group's chunks are contiguous: Npad == BN)
 #pragma unroll
@@ -157,9 +157,7 @@ __global__ __launch_bounds__(NTHREADS, 2) void conv3_kernel(const Conv3Args g) {
       // a piece of a chunk past the end of the pack (last, partial group) re-reads the chunk before it: never used
       const int gc = (wave * NPW + q) / PPC;
       const T* s = (grp * GC + gc < NCH) ? src : src - (size_t)(grp * GC + gc - (NCH - 1)) * (BN * 32);
-      unsigned keep;
-      asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                   : "=&s"(keep) : "v"(s + woff[q]), "s"(dst + q * 1024) : "memory");
+      lds_dma16(s + woff[q], dst + q * 1024);
     }
   };
   // ---- halo: every slot loaded once, all loads in flight together ----
@@ -374,9 +372,9 @@ __global__ __launch_bounds__(NTHREADS, 2) void conv3_kernel(const Conv3Args g) {
     // the slot they read (WAR).  The data dependence of the MFMAs does not give that: hipcc sinks a group's last MFMAs - and the
     // wait for their operands - below the barrier, and with the stem's small, L2-resident weights the refill can land (~250 cycles)
     // before a queued ds_read has executed (seen as 0.1 % wrong outputs of the 7x7 stem convolution at 4 x 1280 x 1920, run to run
-    // different, never at parity-test sizes).  Wait and barrier are ONE asm statement so that nothing is scheduled between them.
-    if (grp + 2 < NGRP) asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)\n\ts_barrier" ::"n"(NPW) : "memory");
-    else asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
+    // different, never at parity-test sizes).  Wait and barrier are ONE asm statement (isa.h) so that nothing is scheduled between them.
+    if (grp + 2 < NGRP) vm_lds_barrier<NPW>();
+    else vm_lds_barrier<0>();
   }
   // all waves are past the last barrier: the images and the ring are dead.  The next tile's halo is requested NOW, so that the loads
   // fly under this tile's epilogue; rowpix / ppre of this tile stay valid (b, y0, x0 are only read again at the top of the loop).
@@ -410,9 +408,9 @@ __global__ __launch_bounds__(NTHREADS, 2) void conv3_kernel(const Conv3Args g) {
       wpart[(wave * 2 + h) * BN + 32 * t + r] = fold_swap32(ps1[t], ps2[t]);  // lane half 0: the sum, half 1: the sum of squares
     }
   }
-  // (forward variants: a raw barrier behind an LDS-only wait - __syncthreads() is a fence, s_waitcnt vmcnt(0) on gfx9, and drained the
-  // next tile's halo loads here, a few hundred cycles after they had been requested)
-  if constexpr (PERSIST && C3_RAW_EPI_BAR) asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+  // (forward variants: a raw barrier behind an LDS-only wait - __syncthreads() drained the next tile's halo loads here, a few hundred
+  // cycles after they had been requested)
+  if constexpr (PERSIST && C3_RAW_EPI_BAR) lds_barrier();
   else __syncthreads();
 
   if constexpr (EPI == EPI_STORE) {
@@ -488,7 +486,7 @@ __global__ __launch_bounds__(NTHREADS, 2) void conv3_kernel(const Conv3Args g) {
   if (!more) break;
   lt = lnext;
   // staging / reduction scratch read: the next tile may overwrite the images, the ring, rowpix and red
-  if constexpr (PERSIST && C3_RAW_EPI_BAR) asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+  if constexpr (PERSIST && C3_RAW_EPI_BAR) lds_barrier();
   else __syncthreads();
   }  // (tile loop)
   if constexpr (EPI == EPI_STORE) {

@@ -6,12 +6,12 @@
 //     fragment read per MFMA instead of cvp.hip's 1.25) - nothing but fragment reads and MFMAs between two barriers; the epilogue of a
 //     tile is wave-local (a wave stages, reads back and stores its own 64 x 64 block: no barrier) and the BatchNorm sums stay in fp64
 //     registers until the column tile changes;
-//   * waves 4-7 (loader waves) own every global load of the K loop, issued from inline assembly with counted waits (wg3.hip explains
+//   * waves 4-7 (loader waves) own every global load of the K loop, issued from inline assembly with counted waits (isa.h explains
 //     why): the halo of the NEXT channel group (10 slots per thread, BN+ReLU once per element on the way into LDS) and the weight stages
 //     two ahead (4 pieces per thread), two halo images and a ring of two weight stages in LDS;
-//   * ONE raw s_barrier per weight stage (16 MFMAs per matrix wave) for all eight waves: stage s is complete / stage s - 1 has been
-//     read.  The stream of stages runs on across channel groups AND tiles: while the matrix waves are in a tile's epilogue the loaders
-//     are already a stage ahead in the next tile.
+//   * ONE raw barrier (isa.h lds_barrier) per weight stage (16 MFMAs per matrix wave) for all eight waves: stage s is complete /
+//     stage s - 1 has been read.  The stream of stages runs on across channel groups AND tiles: while the matrix waves are in a
+//     tile's epilogue the loaders are already a stage ahead in the next tile.
 // cvp.hip spent 10 vector instructions per MFMA (addresses of the weight loads, of the LDS writes, the halo prologue, the epilogue) in
 // the same four waves that issue the MFMAs, two workgroups per CU: 570 - 750 TF/s on stages that are 181 GFLOP each (0.23 of the dense
 // fp16 peak, profiles/r04).  Same arithmetic and K order as cvp.hip per output element: results are bit-equal to cvp.hip's.
@@ -26,6 +26,7 @@
 #include "common.h"
 #include "dispatch.h"
 #include "gather.h"
+#include "isa.h"
 
 #ifndef CW_DBG
 #define CW_DBG 0  // timing experiments only (tools/build_variant.sh): 1 no MFMA, 2 no weight requests, 4 no halo requests, 8 no epilogue, 16 no fragment reads
@@ -55,26 +56,21 @@ struct CvwArgs {
   CwPhase ph[4];                    // in work order: most taps first
 };
 
-__device__ __forceinline__ void cw_bar() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-template <typename V>
-__device__ __forceinline__ void cw_load(V& dst, const void* base, unsigned off) {
-  asm volatile("global_load_dwordx4 %0, %1, %2" : "=v"(dst) : "v"(off), "s"(base));
+constexpr int CW_NX = 10, CW_NB = 4;   // requests per loader thread: halo slots of a channel group, pieces of a weight stage
+// waits of the loader waves: N = requests that may stay in flight behind the set being waited for (see the schedule in cw_walk); N = 0:
+// everything has landed.  cw_hold_b: a weight set stays alive up to here.
+template <int N, typename V>
+__device__ __forceinline__ void cw_wait_x(V (&rx)[CW_NX]) {
+  static_assert(CW_NX == 10, "DMM_V10 below");
+  DMM_VM_WAIT(N, DMM_V10(rx));
 }
-#define CW_X10(r) "+v"(r[0]), "+v"(r[1]), "+v"(r[2]), "+v"(r[3]), "+v"(r[4]), "+v"(r[5]), "+v"(r[6]), "+v"(r[7]), "+v"(r[8]), "+v"(r[9])
-#define CW_B4(r) "+v"(r[0]), "+v"(r[1]), "+v"(r[2]), "+v"(r[3])
-// waits of the loader waves: N = requests that may stay in flight behind the set being waited for (see the schedule in cw_walk)
-template <typename V, int N>
-__device__ __forceinline__ void cw_wait_halo(V (&rx)[10]) {
-  asm volatile("s_waitcnt vmcnt(%10)" : CW_X10(rx) : "n"(N));
-}
-template <typename V, int N>
-__device__ __forceinline__ void cw_wait_b(V (&rb)[4]) {
-  asm volatile("s_waitcnt vmcnt(%4)" : CW_B4(rb) : "n"(N));
+template <int N, typename V>
+__device__ __forceinline__ void cw_wait_b(V (&rb)[CW_NB]) {
+  static_assert(CW_NB == 4, "DMM_V4 below");
+  DMM_VM_WAIT(N, DMM_V4(rb));
 }
 template <typename V>
-__device__ __forceinline__ void cw_hold_x(V (&rx)[10]) { asm volatile("s_waitcnt vmcnt(0)" : CW_X10(rx)); }
-template <typename V>
-__device__ __forceinline__ void cw_hold_b(V (&rb)[4]) { asm volatile("; hold" : CW_B4(rb)); }
+__device__ __forceinline__ void cw_hold_b(V (&rb)[CW_NB]) { DMM_VM_HOLD(DMM_V4(rb)); }
 
 // One phase's share of the launch for this workgroup: items first, first + stride, ... < P.per of a phase with NTAP taps.
 template <typename T, int NTAP>
@@ -116,7 +112,7 @@ __device__ __forceinline__ void cw_walk(const CvwArgs& g, const CwPhase& P, cons
     }
     const unsigned xpitch = (unsigned)sx.ld * 2u;
     constexpr int R = NST < 4 ? NST : 4;   // weight stages in flight (register sets); NST % R == 0
-    V rx[10], rb[R][4];
+    V rx[CW_NX], rb[R][CW_NB];
     unsigned okx_cur = 0, okx_next = 0;
     // Cursors of the two request streams: the halo of (item, group), the weights of (item, group, stage).  An item's geometry is taken
     // apart (three integer divisions) when a cursor ENTERS the item, not at every request.
@@ -147,15 +143,15 @@ __device__ __forceinline__ void cw_walk(const CvwArgs& g, const CwPhase& P, cons
         const int y = hy0 + hy, x = hx0 + hx;
         if (((xin >> i) & 1) && (unsigned)y < (unsigned)sx.Hs && (unsigned)x < (unsigned)sx.Ws) okx_next |= 1u << i;
         const unsigned pix = (unsigned)((rowbase + min(max(y, 0), sx.Hs - 1)) * sx.Ws + min(max(x, 0), sx.Ws - 1));
-        if (!(CW_DBG & 4)) cw_load(rx[i], sx.src, pix * xpitch + col);
+        if (!(CW_DBG & 4)) gload16(rx[i], sx.src, pix * xpitch + col);
       }
       if (++hg == ngrp) { hg = 0; ++hk; enter_h(); }
     };
-    auto issue_b = [&](V (&rb)[4]) {   // requests weight stage (bk, bg, bs) and advances the cursor
+    auto issue_b = [&](V (&rb)[CW_NB]) {   // requests weight stage (bk, bg, bs) and advances the cursor
       const int c0 = (bs >> 1) * cpt + bg * 4 + 2 * (bs & 1);
       const unsigned base = ((unsigned)c0 * (unsigned)a.Npad + bn0) * 64u;
 #pragma unroll
-      for (int j = 0; j < 4; ++j) if (!(CW_DBG & 2)) cw_load(rb[j], P.wpack, base + bsrc[j]);
+      for (int j = 0; j < 4; ++j) if (!(CW_DBG & 2)) gload16(rb[j], P.wpack, base + bsrc[j]);
       if (++bs == NST) { bs = 0; if (++bg == ngrp) { bg = 0; ++bk; enter_b(); } }
     };
     SlotK<SLOT> kx;
@@ -171,7 +167,7 @@ __device__ __forceinline__ void cw_walk(const CvwArgs& g, const CwPhase& P, cons
       for (int i = 0; i < 10; ++i)
         if ((xin >> i) & 1) *(V*)(Xs + xlds[i]) = ((okx_cur >> i) & 1) ? bn_relu_slot(rx[i], kx) : z;
     };
-    auto store_b = [&](V (&rb)[4], int slot) {
+    auto store_b = [&](V (&rb)[CW_NB], int slot) {
       unsigned char* B = smem + CW_OFF_B + slot * CW_B_STAGE;
 #pragma unroll
       for (int j = 0; j < 4; ++j) *(V*)(B + blds[j]) = rb[j];
@@ -197,26 +193,26 @@ __device__ __forceinline__ void cw_walk(const CvwArgs& g, const CwPhase& P, cons
 #pragma unroll
         for (int st = 0; st < NST; ++st) {
           if (st == 0) {
-            cw_wait_halo<V, 4 * R>(rx);
+            cw_wait_x<CW_NB * R>(rx);
             store_halo(gcount & 1, grp);
-            cw_wait_b<V, 4 * (R - 1)>(rb[0]);
+            cw_wait_b<CW_NB * (R - 1)>(rb[0]);
             store_b(rb[0], 0);
             issue_halo();
-            cw_bar();
+            lds_barrier();
             okx_cur = okx_next;
             issue_b(rb[0]);
           } else {
-            if (st < R) cw_wait_b<V, 4 * (R - 1) + 10>(rb[st % R]); else cw_wait_b<V, 4 * (R - 1)>(rb[st % R]);
+            if (st < R) cw_wait_b<CW_NB * (R - 1) + CW_NX>(rb[st % R]); else cw_wait_b<CW_NB * (R - 1)>(rb[st % R]);
             store_b(rb[st % R], st & 1);
-            cw_bar();
+            lds_barrier();
             issue_b(rb[st % R]);
           }
         }
       }
     }
-    cw_hold_x<V>(rx);   // vmcnt(0): everything has landed; every set stays alive up to here
+    cw_wait_x<0>(rx);   // vmcnt(0): everything has landed; every set stays alive up to here
 #pragma unroll
-    for (int st = 0; st < R; ++st) cw_hold_b<V>(rb[st]);
+    for (int st = 0; st < R; ++st) cw_hold_b(rb[st]);
     (void)nstages;
     return;
   }
@@ -255,7 +251,7 @@ __device__ __forceinline__ void cw_walk(const CvwArgs& g, const CwPhase& P, cons
       const unsigned char* Xs = smem + (gcount & 1) * CW_X_BYTES;
 #pragma unroll
       for (int st = 0; st < NST; ++st) {
-        cw_bar();   // stage complete (and, at st == 0, the halo image of this group)
+        lds_barrier();   // stage complete (and, at st == 0, the halo image of this group)
         const unsigned char* B = smem + CW_OFF_B + (st & 1) * CW_B_STAGE + boff;
         const unsigned char* A = Xs + aoff[st >> 1] + (st & 1) * 128;
         // ALL sixteen fragments of the stage are requested first, into registers of their own, and the sixteen MFMAs follow in request

@@ -13,7 +13,7 @@
 //     fragments (19 chunks x 2 k-steps of one 32-column tile: 152 registers) for the whole launch - a k-step is two A reads and two
 //     MFMAs, no weight ring, no barrier inside the K stretch;
 //   * waves 4-7 (loader waves) own the global loads (inline assembly, uniform base + 32-bit offsets, two register sets, counted
-//     waits - see wg3.hip), the BN+ReLU prologue and the LDS images; TWO image sets (53 KB each: the 9 x 17-pixel halo of 128 channels
+//     waits - see isa.h), the BN+ReLU prologue and the LDS images; TWO image sets (53 KB each: the 9 x 17-pixel halo of 128 channels
 //     + the 17 x 33 raw-input slots), ONE raw barrier per item: the loaders write set (i + 1) & 1 while the matrix waves read set i & 1;
 //   * the epilogue is wave-local (a wave stages, reads back and stores its own 64 x 32 tile: no barrier), the BatchNorm sums of the
 //     stored values stay in an fp64 register for the whole walk (one round of atomics per workgroup).
@@ -31,6 +31,7 @@
 #include "common.h"
 #include "dispatch.h"
 #include "gather.h"
+#include "isa.h"
 
 #ifndef HF_DBG
 #define HF_DBG 0   // timing experiments only (tools/build_variant.sh): 1 the loaders request nothing, 2 nothing is stored, 8 no MFMA stretch, 64 no epilogue
@@ -45,7 +46,6 @@ constexpr int HF_THIN = (HF_NS1 * 16 + 255) / 256 * 256;    // 9216
 constexpr int HF_NCH0 = 16, HF_NCH1 = 3, HF_NCH = HF_NCH0 + HF_NCH1, HF_BN = 64;
 constexpr int HF_NT = 512, HF_NL = 256;
 constexpr int HF_N1 = (HF_NS1 + HF_NL - 1) / HF_NL;              // 3 raw-input slots per loader thread
-static_assert(HF_N1 == 3, "operand lists of the waits");
 
 struct HfArgs {
   ConvArgs c;
@@ -53,14 +53,6 @@ struct HfArgs {
   signed char ph_dymin0[4], ph_dxmin0[4], ph_dymin1[4], ph_dxmin1[4];  // origin of each phase's tap boxes
 };
 
-__device__ __forceinline__ void hf_bar() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-// uniform 64-bit base (scalar registers) + 32-bit per-lane byte offset: no 64-bit address arithmetic per request
-template <typename V>
-__device__ __forceinline__ void hf_load(V& dst, unsigned off, const void* base) {
-  asm volatile("global_load_dwordx4 %0, %1, %2" : "=v"(dst) : "v"(off), "s"(base));
-}
-// A loader wave's only vector-memory operations inside the walk are its own loads, issued set by set (13 per set): "all but the newest 13 have
-// returned" is exactly "the older set has landed" (wg3.hip).
 constexpr int H2_PP = 128 * 2 + 16;                          // 272: pixel pitch of the full 128-channel image (17 slots: odd)
 constexpr int H2_RP = (HF_HW * H2_PP + 255) / 256 * 256;    // 4864
 constexpr int H2_U = HF_HH * H2_RP;                         // 43776
@@ -71,17 +63,14 @@ constexpr int H2_OFF_STG = 2 * H2_SET;
 constexpr int H2_LDS = H2_OFF_STG + 4 * H2_STG;             // 126464
 constexpr int H2_NU = (HF_HH * HF_HW * 16 + HF_NL - 1) / HF_NL;   // 10 halo slots per loader thread
 constexpr int H2_KS = 2 * HF_NCH;                           // 38 k-steps
-static_assert(H2_NU == 10 && H2_LDS <= 160 * 1024, "operand lists of the waits / LDS budget");
+static_assert(H2_LDS <= 160 * 1024, "LDS budget");
 
-template <typename V>
-__device__ __forceinline__ void h2_wait(V (&u)[H2_NU], V (&t)[HF_N1]) {   // this set has landed; the other set's 13 requests stay in flight
-  asm volatile("s_waitcnt vmcnt(13)" : "+v"(u[0]), "+v"(u[1]), "+v"(u[2]), "+v"(u[3]), "+v"(u[4]), "+v"(u[5]), "+v"(u[6]), "+v"(u[7]), "+v"(u[8]), "+v"(u[9]),
-                                      "+v"(t[0]), "+v"(t[1]), "+v"(t[2]));
-}
-template <typename V>
-__device__ __forceinline__ void h2_hold(V (&u)[H2_NU], V (&t)[HF_N1]) {   // everything lands; the set is alive until here
-  asm volatile("s_waitcnt vmcnt(0)" : "+v"(u[0]), "+v"(u[1]), "+v"(u[2]), "+v"(u[3]), "+v"(u[4]), "+v"(u[5]), "+v"(u[6]), "+v"(u[7]), "+v"(u[8]), "+v"(u[9]),
-                                     "+v"(t[0]), "+v"(t[1]), "+v"(t[2]));
+// The loaders' requests (isa.h: inline assembly, uniform base + 32-bit offset) are issued set by set, H2_NU + HF_N1 per set.
+// LAND false: this set has landed, the other set's requests stay in flight; true: everything lands, the set is alive until here
+template <bool LAND, typename V>
+__device__ __forceinline__ void h2_sync(V (&u)[H2_NU], V (&t)[HF_N1]) {
+  static_assert(H2_NU == 10 && HF_N1 == 3, "DMM_V10 / DMM_V3 below");
+  DMM_VM_WAIT(LAND ? 0 : H2_NU + HF_N1, DMM_V10(u), DMM_V3(t));
 }
 
 template <typename T>
@@ -182,15 +171,15 @@ __global__ __launch_bounds__(HF_NT, 2) void hf_kernel(const HfArgs g) {
         }
       }
 #pragma unroll
-      for (int i = 0; i < H2_NU; ++i) if (!(HF_DBG & 1)) hf_load(R.u[i], ou[i], ubase);
+      for (int i = 0; i < H2_NU; ++i) if (!(HF_DBG & 1)) gload16(R.u[i], ubase, ou[i]);
 #pragma unroll
-      for (int i = 0; i < HF_N1; ++i) if (!(HF_DBG & 1)) hf_load(R.t[i], ot[i], tbase);
+      for (int i = 0; i < HF_N1; ++i) if (!(HF_DBG & 1)) gload16(R.t[i], tbase, ot[i]);
     };
     V z;
 #pragma unroll
     for (int e = 0; e < SLOT; ++e) z[e] = (T)0;
     auto store = [&](Set& R, int set, bool wait = true) {
-      if (wait && !(HF_DBG & 1)) h2_wait(R.u, R.t);
+      if (wait && !(HF_DBG & 1)) h2_sync<false>(R.u, R.t);
       unsigned char* img = smem + set * H2_SET;
       if (R.inner) {
 #pragma unroll
@@ -217,16 +206,16 @@ __global__ __launch_bounds__(HF_NT, 2) void hf_kernel(const HfArgs g) {
     int k = 0;
     for (; k + 1 < nit; k += 2) {   // (wg3.hip's loop: both halves unconditional, the odd last item behind it)
       store(R0, 0);      // waits for R0's loads only: R1's stay in flight
-      hf_bar();          // barrier k: image set 0 complete / the matrix waves have left set 1
+      lds_barrier();     // barrier k: image set 0 complete / the matrix waves have left set 1
       issue(R0, k + 2);
       store(R1, 1);
-      hf_bar();          // barrier k + 1
+      lds_barrier();     // barrier k + 1
       issue(R1, k + 3);
     }
-    if (!(HF_DBG & 1)) { h2_hold(R0.u, R0.t); h2_hold(R1.u, R1.t); }
+    if (!(HF_DBG & 1)) { h2_sync<true>(R0.u, R0.t); h2_sync<true>(R1.u, R1.t); }
     if (nit & 1) {
       store(R0, 0, false);
-      hf_bar();
+      lds_barrier();
     }
     return;
   }
@@ -282,7 +271,7 @@ __global__ __launch_bounds__(HF_NT, 2) void hf_kernel(const HfArgs g) {
     for (int j = 0; j < 2; ++j)
 #pragma unroll
       for (int i = 0; i < 16; ++i) acc[j][i] = 0.f;
-    hf_bar();   // barrier it: image set it & 1 is complete
+    lds_barrier();   // barrier it: image set it & 1 is complete
     const unsigned char* img = smem + (it & 1) * H2_SET;
     if (!(HF_DBG & 8)) {
 #pragma unroll

@@ -32,6 +32,7 @@
 #include "common.h"
 #include "dispatch.h"
 #include "gather.h"
+#include "isa.h"
 
 namespace dmm {
 
@@ -111,7 +112,7 @@ struct IgemmSmem {
 //   A (gathered activations): waves 0-1 stage chunk 0, waves 2-3 chunk 1.  A thread owns ONE slot column j and FOUR rows
 //     (rg + 32 i), so the chunk-level work (K-table entry, prologue constants) is shared by four slots.  The loads are
 //     issued right after the barrier and consumed (prologue + ds_write) one iteration later, behind the MFMAs.
-//   B (packed weights): never touches registers - global_load_lds_dwordx4 writes the tile image directly; the XOR
+//   B (packed weights): never touches registers - an LDS-DMA load writes the tile image directly; the XOR
 //     swizzle of the image is applied on the per-lane SOURCE address (the LDS side of an LDS-DMA is lane-linear).
 //   K walk: a table in LDS, built once per workgroup, maps (chunk, j) -> segment, tap offset and channel, so the loop
 //     has no divisions, tap-table loads or walker state.
@@ -261,12 +262,8 @@ __global__ __launch_bounds__(64 * NW) void igemm_kernel(const ConvArgs a) {
     // newer loads outstanding, so this DMA has landed before the barrier in front of mma(s).
     const unsigned dst = bdst0 + buf * (SM::A_BYTES + SM::B_BYTES);
 #pragma unroll
-    for (int q = 0; q < NB; ++q) {
-      unsigned keep;
-      if (!(IGEMM_DBG & 8))
-      asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                   : "=&s"(keep) : "v"(bsrc + boff[q]), "s"(dst + q * 1024) : "memory");
-    }
+    for (int q = 0; q < NB; ++q)
+      if (!(IGEMM_DBG & 8)) lds_dma16(bsrc + boff[q], dst + q * 1024);
 #else
     unsigned char* Bs = smem + buf * (SM::A_BYTES + SM::B_BYTES) + SM::A_BYTES + wave * NB * 1024;
 #pragma unroll
@@ -425,14 +422,14 @@ __global__ __launch_bounds__(64 * NW) void igemm_kernel(const ConvArgs a) {
   issue_b(0, 0);
   issue_a(RA, 0);
   if (ADIST == 2) issue_a(RB, 1);
-  // The barriers of the K loop.  __syncthreads() is a workgroup fence - on gfx9 an s_waitcnt vmcnt(0) - and drains the second register
-  // set's loads one stage after they were requested (round 3, pig.hip: that made ADIST = 2 worthless in round 2).  With two sets and a
-  // compile-time load count per issue_a the barrier is a raw s_barrier behind a COUNTED wait: everything but the newest request of
-  // the gathered operand - in particular the weight DMA of the stage, issued in front of it - has completed.
+  // The barriers of the K loop.  __syncthreads() drains the second register set's loads one stage after they were requested (round 3,
+  // pig.hip: that made ADIST = 2 worthless in round 2).  With two sets and a compile-time load count per issue_a the barrier is a raw
+  // barrier behind a COUNTED wait (isa.h vm_lds_barrier): everything but the newest request of the gathered operand - in particular
+  // the weight DMA of the stage, issued in front of it - has completed.
   constexpr bool RAWBAR = IGEMM_RAW_BAR != 0 && ADIST == 2 && MFMA && PRO >= 0 && !(IGEMM_DBG & 1);
   constexpr int NLOAD = NR * (PRO == 2 ? 2 : 1);
   auto kbar = [&]() {
-    if constexpr (RAWBAR) asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)\n\ts_barrier" ::"n"(NLOAD) : "memory");
+    if constexpr (RAWBAR) vm_lds_barrier<NLOAD>();
     else __syncthreads();  // also retires this stage's weight LDS-DMA (vmcnt(0))
   };
   for (int it = 0; it < nstages; it += 2) {

@@ -21,6 +21,7 @@
 #include "common.h"
 #include "dispatch.h"
 #include "gather.h"
+#include "isa.h"
 #include "pointwise.h"
 
 namespace dmm {
@@ -95,9 +96,9 @@ __global__ __launch_bounds__(NTHREADS, 2) void pig_kernel(const PigArgs g) {
     int c;
   };
   // Two register sets: the loads of stage s + 2 are requested while stage s is multiplied, and the barriers of the K loop are raw
-  // s_barrier instructions behind a COUNTED wait - __syncthreads() is a workgroup-scope fence, on gfx9 an s_waitcnt vmcnt(0), which
-  // drained every prefetch twice per stage: the loads of a stage then had a fraction of one MFMA block to land, and the K-deep launches
-  // (blocks 3-4, the decoder's conv_reduce with 1.5-2 K channels) ran at one HBM latency per stage.
+  // barriers behind a COUNTED wait (isa.h vm_lds_barrier) - __syncthreads() drained every prefetch twice per stage: the loads of a
+  // stage then had a fraction of one MFMA block to land, and the K-deep launches (blocks 3-4, the decoder's conv_reduce with 1.5-2 K
+  // channels) ran at one HBM latency per stage.
   ARing RA, RB;
   unsigned roff[NR];   // byte offsets of the cursor tile's rows (the launcher keeps the operand below 4 GiB)
   bool rv[NR];
@@ -138,10 +139,6 @@ __global__ __launch_bounds__(NTHREADS, 2) void pig_kernel(const PigArgs g) {
       *(V*)(As + row * ROWB + ((j ^ ((rg >> 2) & 3)) << 4)) = finish_slot<T, 1>(2, R.raw[i], kk);
     }
   };
-  // raw barriers: this wave's LDS traffic has returned (lgkmcnt) and all but its N youngest vector-memory operations have completed
-  auto bar_all = [&]() { asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory"); };
-  auto bar_keep = [&]() { asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)\n\ts_barrier" ::"n"(NR) : "memory"); };   // the newest A request stays in flight
-  auto bar_lds = [&]() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); };                        // LDS only
   f32x16 acc[NT];
   auto mma = [&](int buf) {
     const unsigned char* As = smem + buf * (PG_A_BYTES + PG_B_BYTES);
@@ -180,15 +177,16 @@ __global__ __launch_bounds__(NTHREADS, 2) void pig_kernel(const PigArgs g) {
     issue_b(0, 0);
     for (int it = 0; it < nstages; it += 2) {
       store_a(RA, 0);
-      if (it == 0) bar_all(); else bar_keep();  // the weight DMA of this stage has landed (it == 0: it was the newest request)
+      // the weight DMA of this stage has landed: the newest A request (NR loads) stays in flight; it == 0: the DMA was the newest request
+      if (it == 0) vm_lds_barrier<0>(); else vm_lds_barrier<NR>();
       issue_b(1, it + 1);
-      // bar_keep's vmcnt(NR) assumes the weight DMA is OLDER in issue order than the NR loads of issue_a: nothing else orders an
+      // vmcnt(NR) assumes the weight DMA is OLDER in issue order than the NR loads of issue_a: nothing else orders an
       // LDS-DMA builtin against plain loads it does not alias, so pin the order (no instruction crosses a sched_barrier(0))
       __builtin_amdgcn_sched_barrier(0);
       issue_a(RA);                              // stage it + 2 (or the next tile's: the cursor runs on)
       mma(0);
       store_a(RB, 1);
-      bar_keep();
+      vm_lds_barrier<NR>();
       if (it + 2 < nstages) issue_b(0, it + 2);  // (the staging below reuses the image: no DMA may be left in flight)
       __builtin_amdgcn_sched_barrier(0);
       issue_a(RB);
@@ -197,7 +195,7 @@ __global__ __launch_bounds__(NTHREADS, 2) void pig_kernel(const PigArgs g) {
     const int m0 = mtile * BM;
     const int next = mtile + g.walkers;
     const bool more = next < g.mtiles;   // (workgroup-uniform)
-    if (nstages > 0) { asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)\n\ts_barrier" ::"n"(2 * NR) : "memory"); }  // all waves done with the operand images (no DMA left: only the two A requests of the next tile fly on): stage the tile over them
+    if (nstages > 0) vm_lds_barrier<2 * NR>();  // all waves done with the operand images (no DMA left: only the two A requests of the next tile fly on): stage the tile over them
     {
       T* Cs = (T*)smem;
 #pragma unroll
@@ -213,7 +211,7 @@ __global__ __launch_bounds__(NTHREADS, 2) void pig_kernel(const PigArgs g) {
         wpart[(wave * 2 + h) * BN + 32 * t + r] = fold_swap32(ps1, ps2);  // lane half 0: the sum, half 1: the sum of squares
       }
     }
-    bar_lds();  // (LDS only: the next tile's two A requests keep flying under the epilogue)
+    lds_barrier();  // (LDS only: the next tile's two A requests keep flying under the epilogue)
     {
       const T* Cs = (const T*)smem;
 #pragma unroll
@@ -231,7 +229,7 @@ __global__ __launch_bounds__(NTHREADS, 2) void pig_kernel(const PigArgs g) {
     }
     if (!more) break;
     mtile = next;
-    bar_lds();  // staging read: the next tile's weight DMA may overwrite it
+    lds_barrier();  // staging read: the next tile's weight DMA may overwrite it
   }
   if (a.stat_sum != nullptr && tid < 2 * BN) {
     const int col = tid % BN, which = tid / BN;

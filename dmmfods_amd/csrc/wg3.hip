@@ -16,9 +16,9 @@
 //     nothing but fragment reads and MFMAs on the image set of the current tile;
 //   * waves 4-7 (loader waves) own the global loads - TWO register sets, i.e. the loads of tiles t+1 and t+2 are in flight while tile
 //     t is multiplied -, the prologues (BN+ReLU on A, effective gradient on dY) and the LDS writes of the NEXT tile's image set;
-//   * two image sets in LDS and ONE raw s_barrier per tile (behind s_waitcnt lgkmcnt(0) only: __syncthreads() is a fence, on gfx9
-//     an s_waitcnt vmcnt(0) that would drain the loaders' prefetch): the loaders write set (t+1)&1 while the matrix waves read set
-//     t&1; barrier t+1 tells the matrix waves that image t+1 is complete and the loaders that image t is free again.
+//   * two image sets in LDS and ONE raw barrier per tile (isa.h lds_barrier: the loaders' prefetch stays in flight across it): the
+//     loaders write set (t+1)&1 while the matrix waves read set t&1; barrier t+1 tells the matrix waves that image t+1 is complete
+//     and the loaders that image t is free again.
 // The partial result of a workgroup (147 KB) is either added to the packed gradient with fp32 atomics or - `part` - STORED to the
 // workgroup's slot and added up in fixed order by wg3_reduce_kernel (the recipe of bw1.hip): no float atomics, and the number of
 // workgroups no longer has to balance tiles per workgroup against 147 KB of atomics each.
@@ -29,6 +29,7 @@
 #include "common.h"
 #include "dispatch.h"
 #include "gather.h"
+#include "isa.h"
 #include "pointwise.h"
 
 #ifndef WG3_DBG
@@ -50,68 +51,18 @@ struct Wg3Args {
   float* part;  // per-workgroup slots of W3_SLOT_FLOATS (nullable: fp32 atomics into w.dpack)
 };
 
-typedef unsigned w3_u32x2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ w3_u32x2 w3_tr16(const unsigned char* p) {
-  typedef __fp16 h4 __attribute__((__vector_size__(4 * sizeof(__fp16))));
-  h4 r = __builtin_amdgcn_ds_read_tr16_b64_v4f16((__attribute__((address_space(3))) h4*)(p));
-  return __builtin_bit_cast(w3_u32x2, r);
-}
-template <typename T>
-__device__ __forceinline__ typename TT<T>::vec w3_frag(const w3_u32x2& lo, const w3_u32x2& hi) {
-  typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-  const u32x4 v = {lo[0], lo[1], hi[0], hi[1]};
-  return __builtin_bit_cast(typename TT<T>::vec, v);
-}
-// one barrier per tile for all eight waves: the wave's own LDS traffic has returned; vector-memory requests stay in flight
-__device__ __forceinline__ void w3_bar() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-
-// The loaders' global loads and their waits are INLINE ASSEMBLY.  Written as plain C++ loads hipcc counted them itself and, at the
-// header of the two-set loop, waited vmcnt(13) ... vmcnt(0) for the OLDER of two register sets in flight (27 ... 14 would do): its
-// merged wait-count state dropped the newer set, every other tile drained the whole ring, and the kernel ran no faster than the
-// four-wave one (ISA of the first version, round 4).  From assembly the compiler counts nothing: a loader wave's only vector-memory
-// operations are these loads, issued set by set in program order, so "all but the newest NLD have returned" is exactly "the older set
-// has landed".  Data flow is explicit - the load defines the register, the wait takes every register of the set as a read-write
-// operand, the prologue reads the wait's outputs - so nothing can be scheduled across; tools/check_asm_loads.py checks in the
-// disassembly that no instruction reads a loaded register between its load and its wait.
-template <typename V>
-__device__ __forceinline__ void w3_load(V& dst, const void* p) {
-  asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(dst) : "v"(p));
-}
-template <typename T, int NA, int NY, int PQ>
-__device__ __forceinline__ void w3_wait(typename TT<T>::vec (&ra)[NA], typename TT<T>::vec (&ry)[NY], typename TT<T>::vec (&ry2)[PQ == 2 ? NY : 1]) {
-  static_assert(NA == 8 && NY == 3, "operand list below");
-  if constexpr (PQ == 2)
-    asm volatile("s_waitcnt vmcnt(14)"
-                 : "+v"(ra[0]), "+v"(ra[1]), "+v"(ra[2]), "+v"(ra[3]), "+v"(ra[4]), "+v"(ra[5]), "+v"(ra[6]), "+v"(ra[7]),
-                   "+v"(ry[0]), "+v"(ry[1]), "+v"(ry[2]), "+v"(ry2[0]), "+v"(ry2[1]), "+v"(ry2[2]));
-  else
-    asm volatile("s_waitcnt vmcnt(11)"
-                 : "+v"(ra[0]), "+v"(ra[1]), "+v"(ra[2]), "+v"(ra[3]), "+v"(ra[4]), "+v"(ra[5]), "+v"(ra[6]), "+v"(ra[7]),
-                   "+v"(ry[0]), "+v"(ry[1]), "+v"(ry[2]));
-}
-
-// keeps a register set alive (operands) up to this point; DRAIN: and waits for every request in flight
-template <typename T, int NA, int NY, int PQ, bool DRAIN>
-__device__ __forceinline__ void w3_hold(typename TT<T>::vec (&ra)[NA], typename TT<T>::vec (&ry)[NY], typename TT<T>::vec (&ry2)[PQ == 2 ? NY : 1]) {
-  static_assert(NA == 8 && NY == 3, "operand list below");
-  if constexpr (DRAIN) {
-    if constexpr (PQ == 2)
-      asm volatile("s_waitcnt vmcnt(0)"
-                   : "+v"(ra[0]), "+v"(ra[1]), "+v"(ra[2]), "+v"(ra[3]), "+v"(ra[4]), "+v"(ra[5]), "+v"(ra[6]), "+v"(ra[7]),
-                     "+v"(ry[0]), "+v"(ry[1]), "+v"(ry[2]), "+v"(ry2[0]), "+v"(ry2[1]), "+v"(ry2[2]));
-    else
-      asm volatile("s_waitcnt vmcnt(0)"
-                   : "+v"(ra[0]), "+v"(ra[1]), "+v"(ra[2]), "+v"(ra[3]), "+v"(ra[4]), "+v"(ra[5]), "+v"(ra[6]), "+v"(ra[7]),
-                     "+v"(ry[0]), "+v"(ry[1]), "+v"(ry[2]));
+// The loaders' global loads and their waits are inline assembly: isa.h explains why.  The sets of this kernel: NA slots of A, NY of dY
+// and, with the effective gradient (PQ == 2), NY of its second operand - one set is NLD = NA + NY or NA + 2 NY requests.
+// MODE 0: wait until this set has landed (the other set's NLD requests stay in flight); 1: wait for everything; 2: keep alive only
+template <typename T, int NA, int NY, int PQ, int MODE>
+__device__ __forceinline__ void w3_sync(typename TT<T>::vec (&ra)[NA], typename TT<T>::vec (&ry)[NY], typename TT<T>::vec (&ry2)[PQ == 2 ? NY : 1]) {
+  static_assert(NA == 8 && NY == 3, "DMM_V8 / DMM_V3 below");
+  if constexpr (PQ == 2) {
+    if constexpr (MODE == 2) DMM_VM_HOLD(DMM_V8(ra), DMM_V3(ry), DMM_V3(ry2));
+    else DMM_VM_WAIT(MODE == 0 ? NA + 2 * NY : 0, DMM_V8(ra), DMM_V3(ry), DMM_V3(ry2));
   } else {
-    if constexpr (PQ == 2)
-      asm volatile("; hold"
-                   : "+v"(ra[0]), "+v"(ra[1]), "+v"(ra[2]), "+v"(ra[3]), "+v"(ra[4]), "+v"(ra[5]), "+v"(ra[6]), "+v"(ra[7]),
-                     "+v"(ry[0]), "+v"(ry[1]), "+v"(ry[2]), "+v"(ry2[0]), "+v"(ry2[1]), "+v"(ry2[2]));
-    else
-      asm volatile("; hold"
-                   : "+v"(ra[0]), "+v"(ra[1]), "+v"(ra[2]), "+v"(ra[3]), "+v"(ra[4]), "+v"(ra[5]), "+v"(ra[6]), "+v"(ra[7]),
-                     "+v"(ry[0]), "+v"(ry[1]), "+v"(ry[2]));
+    if constexpr (MODE == 2) DMM_VM_HOLD(DMM_V8(ra), DMM_V3(ry));
+    else DMM_VM_WAIT(MODE == 0 ? NA + NY : 0, DMM_V8(ra), DMM_V3(ry));
   }
 }
 
@@ -170,7 +121,7 @@ __global__ __launch_bounds__(W3_NT, 1) void wg3_kernel(const Wg3Args g) {
         const int y = y0 + i;
         if (y < a.Ho && xa < a.Wo) R.oka |= 1u << i;
         const size_t pix = (arow + min(y, sa.Hs - 1)) * sa.Ws + min(xa, sa.Ws - 1);
-        if (!(WG3_DBG & 4)) w3_load(R.ra[i], asrc + pix * sa.ld);
+        if (!(WG3_DBG & 4)) gload16(R.ra[i], asrc + pix * sa.ld);
       }
       const size_t yrow = (size_t)cb * sy_.Hs;
 #pragma unroll
@@ -178,15 +129,15 @@ __global__ __launch_bounds__(W3_NT, 1) void wg3_kernel(const Wg3Args g) {
         const int y = y0 + hyy[i], x = x0 + hxx[i];
         if (hy0 + 64 * i < W3_HH * W3_HW && (unsigned)y < (unsigned)sy_.Hs && (unsigned)x < (unsigned)sy_.Ws) R.oky |= 1u << i;
         const size_t pix = (yrow + min(max(y, 0), sy_.Hs - 1)) * sy_.Ws + min(max(x, 0), sy_.Ws - 1);
-        if (!(WG3_DBG & 4)) w3_load(R.ry[i], ysrc + pix * sy_.ld);
-        if constexpr (PQ == 2) { if (!(WG3_DBG & 4)) w3_load(R.ry2[i], ysrc2 + pix * sy_.ld2); }
+        if (!(WG3_DBG & 4)) gload16(R.ry[i], ysrc + pix * sy_.ld);
+        if constexpr (PQ == 2) { if (!(WG3_DBG & 4)) gload16(R.ry2[i], ysrc2 + pix * sy_.ld2); }
       }
       if (--cleft > 0) {  // (uniform) advance; the cursor parks on the last tile
         if (++ctx == g.tiles_x) { ctx = 0; if (++cty == g.tiles_y) { cty = 0; ++cb; } }
       }
     };
     auto store = [&](LSet& R, int set, bool wait = true) {
-      if (wait && !(WG3_DBG & 4)) w3_wait<T, NA, NY, PQ>(R.ra, R.ry, R.ry2);  // this set has landed; the other set's NLD requests stay in flight
+      if (wait && !(WG3_DBG & 4)) w3_sync<T, NA, NY, PQ, 0>(R.ra, R.ry, R.ry2);  // this set has landed; the other set's NLD requests stay in flight
       unsigned char* As = smem + set * W3_IMG;
       unsigned char* Ys = As + W3_A_BYTES;
       V z;
@@ -223,24 +174,24 @@ __global__ __launch_bounds__(W3_NT, 1) void wg3_kernel(const Wg3Args g) {
     // (both halves unconditional in the loop, the odd last tile behind it: with a break in the middle the compiled loop has a path
     // from the first half straight to the latch, which tools/check_asm_loads.py - it cannot know that path always leaves - must flag)
     for (int k = 0; k + 1 < nt; k += 2) {
-      store(R0, 0);   // waits for R0's loads only: R1's stay in flight
-      w3_bar();       // barrier k: image 0 complete / the matrix waves have left image 1
-      issue(R0);      // tile k + 2
+      store(R0, 0);    // waits for R0's loads only: R1's stay in flight
+      lds_barrier();   // barrier k: image 0 complete / the matrix waves have left image 1
+      issue(R0);       // tile k + 2
       store(R1, 1);
-      w3_bar();       // barrier k + 1
-      issue(R1);      // tile k + 3
+      lds_barrier();   // barrier k + 1
+      issue(R1);       // tile k + 3
     }
     // Behind the loop BOTH sets may still have requests in flight (the cursor's surplus requests for tiles past the end), and the
     // compiler - which does not know that - considers a set's registers free from its last use on: it reused R1's registers as
     // temporaries of the odd tile's prologue below while R1's loads were still landing in them (found by tools/check_asm_loads.py
     // before the first run).  So: everything lands HERE, and both sets are operands of the statements, i.e. alive until then.
     if (!(WG3_DBG & 4)) {
-      w3_hold<T, NA, NY, PQ, true>(R0.ra, R0.ry, R0.ry2);
-      w3_hold<T, NA, NY, PQ, false>(R1.ra, R1.ry, R1.ry2);
+      w3_sync<T, NA, NY, PQ, 1>(R0.ra, R0.ry, R0.ry2);
+      w3_sync<T, NA, NY, PQ, 2>(R1.ra, R1.ry, R1.ry2);
     }
     if (nt & 1) {
       store(R0, 0, false);
-      w3_bar();
+      lds_barrier();
     }
     return;
   }
@@ -265,18 +216,18 @@ __global__ __launch_bounds__(W3_NT, 1) void wg3_kernel(const Wg3Args g) {
     yoff[t] = ((1 + dy) * W3_HW + (arow + 1 + dx)) * 64 + ycol;
   }
   for (int k = 0; k < nt; ++k) {
-    w3_bar();  // barrier k: image k & 1 is complete
+    lds_barrier();  // barrier k: image k & 1 is complete
     const unsigned char* As = smem + (k & 1) * W3_IMG;
     const unsigned char* Ys = As + W3_A_BYTES;
     if (!(WG3_DBG & 2)) {
 #pragma unroll 2
       for (int ms = 0; ms < W3_TH; ++ms) {  // one tile row = 16 pixels of the contraction per step
         const unsigned char* ap = As + (16 * ms + arow) * 256 + acol;
-        const V af = w3_frag<T>(w3_tr16(ap), w3_tr16(ap + 4 * 256));
+        const V af = frag16<T>(lds_tr16(ap), lds_tr16(ap + 4 * 256));
         const unsigned char* yp = Ys + ms * (W3_HW * 64);
 #pragma unroll
         for (int t = 0; t < 9; ++t) {
-          const V bf = w3_frag<T>(w3_tr16(yp + yoff[t]), w3_tr16(yp + yoff[t] + 4 * 64));
+          const V bf = frag16<T>(lds_tr16(yp + yoff[t]), lds_tr16(yp + yoff[t] + 4 * 64));
           acc[t] = mma16(af, bf, acc[t]);
         }
       }

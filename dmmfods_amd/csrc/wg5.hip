@@ -16,6 +16,7 @@
 #include "common.h"
 #include "dispatch.h"
 #include "gather.h"
+#include "isa.h"
 
 namespace dmm {
 
@@ -47,19 +48,6 @@ struct Wg5Args {
   WgradArgs w;
   int tiles_y, tiles_x, ntiles, tiles_per_wg;
 };
-
-typedef unsigned w5_u32x2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ w5_u32x2 w5_tr16(const unsigned char* p) {
-  typedef __fp16 h4 __attribute__((__vector_size__(4 * sizeof(__fp16))));
-  h4 r = __builtin_amdgcn_ds_read_tr16_b64_v4f16((__attribute__((address_space(3))) h4*)(p));
-  return __builtin_bit_cast(w5_u32x2, r);
-}
-template <typename T>
-__device__ __forceinline__ typename TT<T>::vec w5_frag(const w5_u32x2& lo, const w5_u32x2& hi) {
-  typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-  const u32x4 v = {lo[0], lo[1], hi[0], hi[1]};
-  return __builtin_bit_cast(typename TT<T>::vec, v);
-}
 
 // The two factors of an activation on one 16-byte slot: relu(bn(x)) = scale (m x) + shift m with m = [f16(fma(x, scale, shift)) > 0]
 // (the forward's own value).  mx = m x is the STORED x or zero - exact, no rounding of its own - and mm = m; `okm` = all ones / zero
@@ -243,7 +231,6 @@ __global__ __launch_bounds__(NTHREADS, (TR == 3 ? 1 : ((PA == 3 || (PA == 0 && P
           *(V*)(Ys + hp * YP + 16) = ok ? f32_to_vec<T>(mm) : z;
         } else if constexpr (TCOL == 4) {   // the first four channels of the slot only
           typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-          typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
           const u32x4 yv = __builtin_bit_cast(u32x4, R.ry[i]);
           const bool ok = (R.oky >> i) & 1;
           const u32x2 y2 = {ok ? yv[0] : 0u, ok ? yv[1] : 0u};
@@ -291,14 +278,14 @@ __global__ __launch_bounds__(NTHREADS, (TR == 3 ? 1 : ((PA == 3 || (PA == 0 && P
 #pragma unroll 2
     for (int ms = 0; ms < W5_TH; ++ms) {  // one tile row = 16 pixels of the contraction per step
       const unsigned char* ap = As + (16 * ms + arow) * 128 + acol;
-      const V af = w5_frag<T>(w5_tr16(ap), w5_tr16(ap + 4 * 128));
+      const V af = frag16<T>(lds_tr16(ap), lds_tr16(ap + 4 * 128));
       V af1 = af;
-      if constexpr (PA == 3) af1 = w5_frag<T>(w5_tr16(ap + W5_A_BYTES), w5_tr16(ap + W5_A_BYTES + 4 * 128));
+      if constexpr (PA == 3) af1 = frag16<T>(lds_tr16(ap + W5_A_BYTES), lds_tr16(ap + W5_A_BYTES + 4 * 128));
 #pragma unroll
       for (int m = 0; m < NQ; ++m) {
         if (q0 + 2 * m < W5_NCH) {  // (wave-uniform)
           const unsigned char* yp = Ys + boff[m] + ms * bstep[m];
-          const V bf = w5_frag<T>(w5_tr16(yp), w5_tr16(yp + bsec[m]));
+          const V bf = frag16<T>(lds_tr16(yp), lds_tr16(yp + bsec[m]));
           acc[m] = mma16(af, bf, acc[m]);
           if constexpr (PA == 3) acc1[m] = mma16(af1, bf, acc1[m]);
         }

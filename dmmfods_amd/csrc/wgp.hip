@@ -18,6 +18,7 @@
 #include "common.h"
 #include "dispatch.h"
 #include "gather.h"
+#include "isa.h"
 
 namespace dmm {
 
@@ -36,19 +37,6 @@ struct WgpArgs {
   int dymin, dxmin;  // origin of the tap box
   int ph_dymin[4], ph_dxmin[4];  // ... per phase of a multi-phase launch (WgradArgs::nphase)
 };
-
-typedef unsigned wp_u32x2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ wp_u32x2 wp_tr16(const unsigned char* p) {
-  typedef __fp16 h4 __attribute__((__vector_size__(4 * sizeof(__fp16))));
-  h4 r = __builtin_amdgcn_ds_read_tr16_b64_v4f16((__attribute__((address_space(3))) h4*)(p));
-  return __builtin_bit_cast(wp_u32x2, r);
-}
-template <typename T>
-__device__ __forceinline__ typename TT<T>::vec wp_frag(const wp_u32x2& lo, const wp_u32x2& hi) {
-  typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-  const u32x4 v = {lo[0], lo[1], hi[0], hi[1]};
-  return __builtin_bit_cast(typename TT<T>::vec, v);
-}
 
 // NTAP taps of the phase (2 or 4), NJ = NCO / 32 accumulator columns of 32 output channels, PQ = prologue of dY (0 none, 2 effective
 // gradient)
@@ -214,11 +202,11 @@ __global__ __launch_bounds__(NTHREADS, 1) void wgp_kernel(const WgpArgs g) {
       const unsigned char* yp = Ys + ms * (16 * 256);
       V yf[NJ];
 #pragma unroll
-      for (int j = 0; j < NJ; ++j) yf[j] = wp_frag<T>(wp_tr16(yp + yoff[j]), wp_tr16(yp + yoff[j] + 4 * 256));
+      for (int j = 0; j < NJ; ++j) yf[j] = frag16<T>(lds_tr16(yp + yoff[j]), lds_tr16(yp + yoff[j] + 4 * 256));
       const unsigned char* xp = Xs + ms * (WP_HW * 256);
 #pragma unroll
       for (int t = 0; t < NTAP; ++t) {
-        const V xf = wp_frag<T>(wp_tr16(xp + xoff[t]), wp_tr16(xp + xoff[t] + 4 * 256));
+        const V xf = frag16<T>(lds_tr16(xp + xoff[t]), lds_tr16(xp + xoff[t] + 4 * 256));
 #pragma unroll
         for (int j = 0; j < NJ; ++j) acc[t][j] = mma16(yf[j], xf, acc[t][j]);  // rows: output channel n, columns: input channel c
       }

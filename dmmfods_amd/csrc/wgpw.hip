@@ -6,7 +6,7 @@
 //     but transposing fragment reads and MFMAs on the image set of the current 8 x 16 pixel tile;
 //   * waves 4-7 (loader waves) own the global loads - TWO register sets, the loads of tiles t+1 and t+2 in flight while tile t is
 //     multiplied -, the BN+ReLU prologue of the 9 x 17 pixel input halo and the LDS writes of the NEXT tile's image set;
-//   * two image sets (2 x 77 KB), ONE raw s_barrier per tile behind s_waitcnt lgkmcnt(0).
+//   * two image sets (2 x 77 KB), ONE raw barrier per tile (isa.h lds_barrier).
 // wgp.hip's four waves did load -> prologue -> LDS write -> 64 MFMAs one after the other at one wave per SIMD: 356 TF/s on the
 // ConvTranspose stages (0.14 of the dense fp16 peak) with SQ_WAIT_INST_ANY 0.43-0.50.  Same arithmetic, same K order
 // per workgroup: results equal wgp.hip's up to the order of the fp32 atomics at the end of the walk.
@@ -19,6 +19,7 @@
 #include "common.h"
 #include "dispatch.h"
 #include "gather.h"
+#include "isa.h"
 
 namespace dmm {
 
@@ -43,44 +44,19 @@ struct WgpwArgs {
   int ph_dymin[4], ph_dxmin[4];
 };
 
-typedef unsigned ww_u32x2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ ww_u32x2 ww_tr16(const unsigned char* p) {
-  typedef __fp16 h4 __attribute__((__vector_size__(4 * sizeof(__fp16))));
-  h4 r = __builtin_amdgcn_ds_read_tr16_b64_v4f16((__attribute__((address_space(3))) h4*)(p));
-  return __builtin_bit_cast(ww_u32x2, r);
-}
-template <typename T>
-__device__ __forceinline__ typename TT<T>::vec ww_frag(const ww_u32x2& lo, const ww_u32x2& hi) {
-  typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-  const u32x4 v = {lo[0], lo[1], hi[0], hi[1]};
-  return __builtin_bit_cast(typename TT<T>::vec, v);
-}
-__device__ __forceinline__ void ww_bar() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-
-// The loaders' global loads and waits are inline assembly (wg3.hip explains why: hipcc's merged wait-count state drains the second
-// register set at the loop header).  A loader wave's only vector-memory operations are these loads, issued set by set in program
-// order: "all but the newest NLD have returned" = "the older set has landed".  tools/check_asm_loads.py checks the ISA.
-// Address = uniform base (an SGPR pair) + a 32-bit per-lane byte offset: one VALU register and 32-bit arithmetic per load instead of a
-// 64-bit pointer (the register budget above); the launcher refuses tensors of 4 GB or more.
-template <typename V>
-__device__ __forceinline__ void ww_load(V& dst, const void* base, unsigned off) {
-  asm volatile("global_load_dwordx4 %0, %1, %2" : "=v"(dst) : "v"(off), "s"(base));
-}
-#define WW_X10(r) "+v"(r[0]), "+v"(r[1]), "+v"(r[2]), "+v"(r[3]), "+v"(r[4]), "+v"(r[5]), "+v"(r[6]), "+v"(r[7]), "+v"(r[8]), "+v"(r[9])
-#define WW_Y4(r) "+v"(r[0]), "+v"(r[1]), "+v"(r[2]), "+v"(r[3])
-#define WW_Y8(r) "+v"(r[0]), "+v"(r[1]), "+v"(r[2]), "+v"(r[3]), "+v"(r[4]), "+v"(r[5]), "+v"(r[6]), "+v"(r[7])
-// MODE 0: wait until this set has landed (the other set's NX + NY requests stay in flight); 1: wait for everything; 2: keep alive only
+// The loaders' global loads and waits are inline assembly (isa.h explains why), in the base + 32-bit offset form: one VALU register
+// per load instead of a 64-bit pointer (the register budget below); the launcher refuses tensors of 4 GB or more.
+constexpr int WW_NX = 10;   // halo slots per loader thread: 9 x 17 pixels x 16 slot columns / 256
+// MODE 0: wait until this set has landed (the other set's WW_NX + NY requests stay in flight); 1: wait for everything; 2: keep alive only
 template <typename V, int NY, int MODE>
-__device__ __forceinline__ void ww_sync(V (&rx)[10], V (&ry)[NY]) {
-  static_assert(NY == 4 || NY == 8, "operand lists below");
+__device__ __forceinline__ void ww_sync(V (&rx)[WW_NX], V (&ry)[NY]) {
+  static_assert(WW_NX == 10 && (NY == 4 || NY == 8), "DMM_V10 and DMM_V4 / DMM_V8 below");
   if constexpr (NY == 4) {
-    if constexpr (MODE == 0) asm volatile("s_waitcnt vmcnt(14)" : WW_X10(rx), WW_Y4(ry));
-    else if constexpr (MODE == 1) asm volatile("s_waitcnt vmcnt(0)" : WW_X10(rx), WW_Y4(ry));
-    else asm volatile("; hold" : WW_X10(rx), WW_Y4(ry));
+    if constexpr (MODE == 2) DMM_VM_HOLD(DMM_V10(rx), DMM_V4(ry));
+    else DMM_VM_WAIT(MODE == 0 ? WW_NX + NY : 0, DMM_V10(rx), DMM_V4(ry));
   } else {
-    if constexpr (MODE == 0) asm volatile("s_waitcnt vmcnt(18)" : WW_X10(rx), WW_Y8(ry));
-    else if constexpr (MODE == 1) asm volatile("s_waitcnt vmcnt(0)" : WW_X10(rx), WW_Y8(ry));
-    else asm volatile("; hold" : WW_X10(rx), WW_Y8(ry));
+    if constexpr (MODE == 2) DMM_VM_HOLD(DMM_V10(rx), DMM_V8(ry));
+    else DMM_VM_WAIT(MODE == 0 ? WW_NX + NY : 0, DMM_V10(rx), DMM_V8(ry));
   }
 }
 
@@ -95,7 +71,7 @@ __device__ __forceinline__ void wgpw_body(const WgpwArgs& g, const int unit, con
   constexpr int SLOT = 8;
   constexpr int NL = 256;                         // loader threads
   constexpr int NCO = 32 * NJ;
-  constexpr int NX = 10;                          // halo slots per loader thread: 9 x 17 pixels x 16 slot columns / 256
+  constexpr int NX = WW_NX;                       // halo slots per loader thread
   constexpr int YS = NCO / SLOT;                  // dY slot columns
   constexpr int NY = BM * YS / NL;                // 4 (NCO 64) or 8 (NCO 128) dY slots per loader thread
   constexpr int YRS = NL / YS;                    // dY pixel step between a thread's slots
@@ -193,9 +169,9 @@ __device__ __forceinline__ void wgpw_body(const WgpwArgs& g, const int unit, con
         }
       }
 #pragma unroll
-      for (int i = 0; i < NX; ++i) ww_load(R.rx[i], sx.src, offx[i]);
+      for (int i = 0; i < NX; ++i) gload16(R.rx[i], sx.src, offx[i]);
 #pragma unroll
-      for (int i = 0; i < NY; ++i) ww_load(R.ry[i], sy.src, offy[i]);
+      for (int i = 0; i < NY; ++i) gload16(R.ry[i], sy.src, offy[i]);
       if (--cleft > 0) {  // (uniform) advance; the cursor parks on the last tile
         if (++ctx == g.tiles_x) { ctx = 0; if (++cty == g.tiles_y) { cty = 0; ++cb; } }
       }
@@ -226,23 +202,23 @@ __device__ __forceinline__ void wgpw_body(const WgpwArgs& g, const int unit, con
     // (sched_barrier: the address arithmetic of an issue and the prologue of the next store are both VALU work the scheduler likes to
     // interleave - with both register sets alive that overflows the 256 registers of a wave at two waves per SIMD)
     for (int k = 0; k + 1 < nt; k += 2) {
-      store(R0, 0);   // waits for R0's loads only
-      ww_bar();       // barrier k: image 0 complete / the matrix waves have left image 1
+      store(R0, 0);    // waits for R0's loads only
+      lds_barrier();   // barrier k: image 0 complete / the matrix waves have left image 1
       __builtin_amdgcn_sched_barrier(0);
-      issue(R0);      // tile k + 2
+      issue(R0);       // tile k + 2
       __builtin_amdgcn_sched_barrier(0);
       store(R1, 1);
-      ww_bar();       // barrier k + 1
+      lds_barrier();   // barrier k + 1
       __builtin_amdgcn_sched_barrier(0);
-      issue(R1);      // tile k + 3
+      issue(R1);       // tile k + 3
       __builtin_amdgcn_sched_barrier(0);
     }
-    // everything lands HERE, with both sets alive as operands (wg3.hip: the compiler would reuse a dead set's registers under landing loads)
+    // everything lands HERE, with both sets alive as operands (isa.h: the compiler would reuse a dead set's registers under landing loads)
     ww_sync<V, NY, 1>(R0.rx, R0.ry);
     ww_sync<V, NY, 2>(R1.rx, R1.ry);
     if (nt & 1) {
       store(R0, 0, false);
-      ww_bar();
+      lds_barrier();
     }
     return;
   }
@@ -273,7 +249,7 @@ __device__ __forceinline__ void wgpw_body(const WgpwArgs& g, const int unit, con
   for (int j = 0; j < NJ; ++j) yoff[j] = arow * 256 + (((32 * j + 16 * (tg & 1) + 4 * tp) * 2) ^ (tq << 6));
 
   for (int k = 0; k < nt; ++k) {
-    ww_bar();  // barrier k: image k & 1 is complete
+    lds_barrier();  // barrier k: image k & 1 is complete
     const unsigned char* Xs = smem + (k & 1) * WW_X_BYTES;
     const unsigned char* Ys = smem + WW_Y0 + (k & 1) * WW_Y_BYTES;
 #pragma unroll 2
@@ -281,11 +257,11 @@ __device__ __forceinline__ void wgpw_body(const WgpwArgs& g, const int unit, con
       const unsigned char* yp = Ys + ms * (16 * 256);
       V yf[NJ];
 #pragma unroll
-      for (int j = 0; j < NJ; ++j) yf[j] = ww_frag<T>(ww_tr16(yp + yoff[j]), ww_tr16(yp + yoff[j] + 4 * 256));
+      for (int j = 0; j < NJ; ++j) yf[j] = frag16<T>(lds_tr16(yp + yoff[j]), lds_tr16(yp + yoff[j] + 4 * 256));
       const unsigned char* xp = Xs + ms * (WW_HW * 256);
 #pragma unroll
       for (int t = 0; t < NTAP; ++t) {
-        const V xf = ww_frag<T>(ww_tr16(xp + xoff[t]), ww_tr16(xp + xoff[t] + 4 * 256));
+        const V xf = frag16<T>(lds_tr16(xp + xoff[t]), lds_tr16(xp + xoff[t] + 4 * 256));
 #pragma unroll
         for (int j = 0; j < NJ; ++j) acc[t][j] = mma16(yf[j], xf, acc[t][j]);  // rows: output channel n, columns: input channel c
       }

@@ -18,6 +18,7 @@
 #include "common.h"
 #include "dispatch.h"
 #include "gather.h"
+#include "isa.h"
 
 namespace dmm {
 
@@ -55,20 +56,6 @@ struct WgradSmem {
   static constexpr int TAB = 2 * BMW * 16;       // two row tables of int4 {b, y, x, valid}
   static constexpr int bytes = 2 * BUF + TAB;
 };
-
-// ds_read_b64_tr_b16 moves 16-bit elements whatever they encode: the result is handed back as two dwords
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ u32x2 lds_tr16(const unsigned char* p) {
-  typedef __fp16 h4 __attribute__((__vector_size__(4 * sizeof(__fp16))));
-  h4 r = __builtin_amdgcn_ds_read_tr16_b64_v4f16((__attribute__((address_space(3))) h4*)(p));
-  return __builtin_bit_cast(u32x2, r);
-}
-template <typename T>
-__device__ __forceinline__ typename TT<T>::vec frag16(const u32x2& lo, const u32x2& hi) {
-  typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-  const u32x4 v = {lo[0], lo[1], hi[0], hi[1]};
-  return __builtin_bit_cast(typename TT<T>::vec, v);
-}
 
 // PP / PQ = prologue kind of the pixel-aligned operand P and of the tapped operand Q (-1 run time, 0 none, 1 BN+ReLU,
 // 2 effective gradient); LIN = both operands are plain one-tap unit-stride tensors on the row grid (1x1 layers): the

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Static check of kernels whose global loads and vmcnt waits are hand-written inline assembly (wg3.hip's loader waves).
+"""Static check of kernels whose global loads and vmcnt waits are hand-written inline assembly (the loader waves of the wave-specialised kernels; see csrc/isa.h).
 
 hipcc does not count a load issued from inline assembly, so NOTHING but the hand-written `s_waitcnt vmcnt(N)` orders a use of the
 loaded registers behind the arrival of the data.  The C++ expresses that as data flow (the wait takes the registers as read-write
