@@ -392,19 +392,16 @@ __global__ __launch_bounds__(NTHREADS, 2) void bw1_kernel(const Bw1Args g) {
   }
 }
 
-static bool g_bw1 = !lab_flag("DMM_NO_BW1");
-void bw1_set_enabled(bool on) { g_bw1 = on; }
-bool bw1_enabled() { return g_bw1; }
-
 template <typename T, int PQ, bool ACC, bool PART>
 static hipError_t launch_bw1_t(const Bw1Args& g, int nwg, hipStream_t st) {
   return launch_lds<bw1_kernel<T, PQ, ACC, PART>>(B1_LDS, nwg, NTHREADS, B1_LDS, st, g);
 }
 
 // Do these two launches - the weight gradient `w` (normal form) and the data gradient `d` (EPI_BNBWD) of one convolution - form
-// the pair this kernel fuses?  1x1, unit stride, 128 output channels, the same x / norm and the same gradient operand on both.
-bool bw1_eligible(const WgradArgs& w, const ConvArgs& d, int dtype) {
-  if (!g_bw1 || dtype == DT_F32 || w.nseg != 1 || d.nseg != 1 || d.pool2) return false;
+// the pair this kernel fuses?  1x1, unit stride, 128 output channels, the same x / norm and the same gradient operand on both - and
+// the family not switched off (deny: 1 << family, dispatch.h).
+bool bw1_eligible(const WgradArgs& w, const ConvArgs& d, int dtype, unsigned deny) {
+  if (((deny >> IMPL_BW1) & 1u) || dtype == DT_F32 || w.nseg != 1 || d.nseg != 1 || d.pool2) return false;
   const Seg& wx = w.seg[0];   // x with norm1's scale / shift
   const Seg& wg = w.dy;       // G
   const Seg& dg = d.seg[0];   // G again

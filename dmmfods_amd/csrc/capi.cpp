@@ -1,5 +1,6 @@
 // extern "C" surface of libdmmfods_hip.so (see include/dmmfods_hip.h) and the launch-list executor.
 #include <algorithm>
+#include <atomic>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -33,6 +34,11 @@ static bool g_overlap_wgrad = getenv("DMM_NO_OVERLAP") == nullptr;
 static int g_graph = getenv("DMM_GRAPH") ? std::max(1, atoi(getenv("DMM_GRAPH"))) : 0;  // off by default: see launch_list (1: both lists, 2: the forward list only)
 static unsigned long long g_option_epoch = 1;  // bumped by every dmm_set_option: captured graphs have the options of their time baked in
 static int g_bucket_mb = getenv("DMM_GRAD_BUCKET_MB") ? atoi(getenv("DMM_GRAD_BUCKET_MB")) : 25;
+// The kernel families switched off for the process, 1 << family (dmm_set_option; a lab build starts from its DMM_NO_* flags).  The one
+// switch there is: a plan copies it into dmm_plan::deny in front of each builder pass, a single-kernel entry point passes it at every call.
+static std::atomic<unsigned> g_family_off{lab_family_off()};
+// the deny mask a plan is built under: its own switch + the process-wide ones of this moment
+static unsigned plan_deny(const dmm_plan* p) { return (p->sw.no_hf ? 1u << IMPL_HF : 0u) | g_family_off; }
 
 // ------------------------------------------------------------------------------------------------ streams and events of the process
 // One pool per device, created on first use and NEVER torn down: the three helper streams (side: weight gradients, backward leaves,
@@ -112,19 +118,25 @@ extern "C" {
 const char* dmm_last_error(void) { return g_err.c_str(); }
 int dmm_version(void) { return 101; }
 
+// The names of enum Impl (dmm_impl_name), and the families dmm_set_option switches with the option name of each (hf, cf and halo
+// are not settable).
+static const char* const kImplNames[IMPL_COUNT] = {"auto", "generic", "thin", "conv3", "cvp", "halo", "wg3", "wg5", "wgp", "pig", "bw1", "hf", "cf", "wgpw", "cvw"};
+static const struct { const char* option; int family; } kFamilyOptions[] = {
+    {"thin_logits", IMPL_THIN}, {"conv3", IMPL_CONV3}, {"wg3", IMPL_WG3}, {"wgp", IMPL_WGP},
+    {"wg5", IMPL_WG5},          {"cvp", IMPL_CVP},     {"bw1", IMPL_BW1}, {"pig", IMPL_PIG},
+};
+
 int dmm_set_option(const char* name, int value) {
   if (!name) return fail(DMM_ERR_INVALID, "null argument");
   ++g_option_epoch;
   if (std::string(name) == "overlap_wgrad") { g_overlap_wgrad = value != 0; return DMM_OK; }
   if (std::string(name) == "graph") { g_graph = value; return DMM_OK; }
-  if (std::string(name) == "thin_logits") { dmm::thin_set_enabled(value != 0); return DMM_OK; }
-  if (std::string(name) == "conv3") { dmm::conv3_set_enabled(value != 0); return DMM_OK; }
-  if (std::string(name) == "wg3") { dmm::wg3_set_enabled(value != 0); return DMM_OK; }
-  if (std::string(name) == "wgp") { dmm::wgp_set_enabled(value != 0); return DMM_OK; }
-  if (std::string(name) == "wg5") { dmm::wg5_set_enabled(value != 0); return DMM_OK; }
-  if (std::string(name) == "cvp") { dmm::cvp_set_enabled(value != 0); return DMM_OK; }
-  if (std::string(name) == "bw1") { dmm::bw1_set_enabled(value != 0); return DMM_OK; }
-  if (std::string(name) == "pig") { dmm::pig_set_enabled(value != 0); return DMM_OK; }
+  for (const auto& o : kFamilyOptions)
+    if (std::string(name) == o.option) {
+      if (value != 0) g_family_off &= ~(1u << o.family);
+      else g_family_off |= 1u << o.family;
+      return DMM_OK;
+    }
   if (std::string(name) == "grad_bucket_mb") {  // applies to plans created afterwards; 0 = one bucket
     if (value < 0) return fail(DMM_ERR_INVALID, "grad_bucket_mb must be >= 0");
     g_bucket_mb = value;
@@ -145,6 +157,7 @@ int dmm_plan_create(const dmm_model_desc* desc, dmm_plan** out) {
   p->desc = *desc;
   p->sw = PlanSwitches::from_environment();   // the only place a plan's switches are read
   p->bucket_bytes = (size_t)g_bucket_mb << 20;
+  p->deny = plan_deny(p);
   try {
     plan_build_tables(p);
   } catch (const std::domain_error& e) {
@@ -240,6 +253,7 @@ int dmm_plan_bind(dmm_plan* plan, void* workspace, size_t workspace_bytes, float
   plan->buffers = buffers;
   plan->graphs[0].epoch = plan->graphs[1].epoch = 0;  // captured graphs hold the old pointers
   plan->bound = false;
+  plan->deny = plan_deny(plan);   // the switches of the moment of bind decide the launches (buffers are reserved by shape alone)
   try {
     plan_bind(plan, workspace);
   } catch (const dmm::plan_sizing_error& e) {
@@ -859,10 +873,7 @@ static void fill_one_seg(Seg& s, const dmm_conv_desc* d, const OneConv& g, const
 
 int dmm_last_impl(void) { return g_last_impl; }
 unsigned dmm_impl_mask(int reset) { const unsigned m = g_impl_mask; if (reset) g_impl_mask = 0; return m; }
-const char* dmm_impl_name(int impl) {
-  static const char* const names[IMPL_COUNT] = {"auto", "generic", "thin", "conv3", "cvp", "halo", "wg3", "wg5", "wgp", "pig", "bw1", "hf", "cf", "wgpw", "cvw"};
-  return impl >= 0 && impl < IMPL_COUNT ? names[impl] : "?";
-}
+const char* dmm_impl_name(int impl) { return impl >= 0 && impl < IMPL_COUNT ? kImplNames[impl] : "?"; }
 
 int dmm_conv_forward(const dmm_conv_desc* d, const void* x, const float* w, const float* scale, const float* shift, void* y,
                      double* stats, void* scratch, void* stream) {
@@ -888,7 +899,7 @@ int dmm_conv_forward(const dmm_conv_desc* d, const void* x, const float* w, cons
     a.out = y; a.ldo = d->Cout; a.Hout = g.Hout; a.Wout = g.Wout; a.ostride = g.ostride;
     a.py = g.phase_xy[ph].first; a.px = g.phase_xy[ph].second;
     if (stats) { a.stat_sum = stats; a.stat_sq = stats + d->Cout; }
-    HIPCHK(launch_igemm(a, d->dtype, EPI_STORE, d->use_mfma != 0, st));
+    HIPCHK(launch_igemm(a, d->dtype, EPI_STORE, d->use_mfma != 0, st, IMPL_AUTO, g_family_off));
   }
   return DMM_OK;
 }
@@ -955,12 +966,13 @@ int dmm_conv_wgrad_ex(const dmm_conv_desc* d, const void* x, const void* dy, con
     a.dpack = (float*)pd.dpack;
     void* part = nullptr;
     Resolved wg3;
-    if (d->use_mfma && wg3_enabled() && wg3_resolve(a, d->dtype, wg3)) {  // the plan gives the family its slots; so does this entry point
+    const unsigned deny = g_family_off;
+    if (d->use_mfma && !((deny >> IMPL_WG3) & 1u) && wg3_resolve(a, d->dtype, wg3)) {  // the plan gives the family its slots; so does this entry point
       HIPCHK(hipMallocAsync(&part, (size_t)W3_MAX_SLOTS * W3_SLOT_FLOATS * sizeof(float), st));
       a.part = (float*)part;
       a.part_slots = W3_MAX_SLOTS;
     }
-    const hipError_t e1 = launch_wgrad(a, d->dtype, d->use_mfma != 0, st);
+    const hipError_t e1 = launch_wgrad(a, d->dtype, d->use_mfma != 0, st, IMPL_AUTO, deny);
     if (part != nullptr) hipFreeAsync(part, st);
     HIPCHK(e1);
     HIPCHK(hipMemsetAsync(dw, 0, wn * sizeof(float), st));
@@ -990,7 +1002,7 @@ int dmm_conv_wgrad_ex(const dmm_conv_desc* d, const void* x, const void* dy, con
     set_eff_grad(a.dy, yfwd, d->Cout, q, r, zeros);
     a.N = d->Cout; a.Npad = packs[ph].Npad;
     a.dpack = (float*)packs[ph].dpack;
-    HIPCHK(launch_wgrad(a, d->dtype, d->use_mfma != 0, st));
+    HIPCHK(launch_wgrad(a, d->dtype, d->use_mfma != 0, st, IMPL_AUTO, g_family_off));
   }
   HIPCHK(hipMemsetAsync(dw, 0, wn * sizeof(float), st));
   HIPCHK(launch_unpack(dd, dp, (int)packs.size(), total_rows, d->dtype, 1.0f, st));
@@ -1035,7 +1047,7 @@ int dmm_conv5_wgrad_stats(const dmm_conv_desc* d, const void* x, const void* dy,
   a.dpack = (float*)pd.dpack;
   a.sbuf = sbuf;
   a.t_mean = shift + d->Cin; a.t_invstd = shift + 2 * d->Cin;
-  HIPCHK(launch_wgrad(a, d->dtype, true, st));
+  HIPCHK(launch_wgrad(a, d->dtype, true, st, IMPL_AUTO, g_family_off));
   if (g_last_impl != IMPL_WG5) return fail(DMM_ERR_STATE, "the factor form is wg5.hip's");
   Fin64Args f;
   memset(&f, 0, sizeof(f));
@@ -1111,7 +1123,7 @@ int dmm_conv_dgrad_ex(const dmm_conv_desc* d, const void* x, const void* dy, con
   const int npad = rup(cs, cs >= 384 || cs % 128 == 0 ? 128 : (cs >= 64 ? 64 : 32));
   const int rc = build_dgrad(d, g, x, dy, w, scale, shift, yfwd, q, r, gx, accumulate, red, S, npad, a, st);
   if (rc) return rc;
-  HIPCHK(launch_igemm(a, d->dtype, EPI_BNBWD, d->use_mfma != 0, st));
+  HIPCHK(launch_igemm(a, d->dtype, EPI_BNBWD, d->use_mfma != 0, st, IMPL_AUTO, g_family_off));
   return DMM_OK;
 }
 
@@ -1151,7 +1163,7 @@ int dmm_conv1x1_backward_fused(const dmm_conv_desc* d, const void* x, const void
   wa.dy = b.c.seg[0];
   wa.N = d->Cout; wa.Npad = packs[0].Npad;
   wa.dpack = (float*)packs[0].dpack;
-  if (!bw1_eligible(wa, b.c, d->dtype)) return fail(DMM_ERR_INVALID, "not a pair bw1.hip fuses (16-bit storage, 128 output channels, Cin % 32 == 0)");
+  if (!bw1_eligible(wa, b.c, d->dtype, g_family_off)) return fail(DMM_ERR_INVALID, "not a pair bw1.hip fuses (16-bit storage, 128 output channels, Cin % 32 == 0)");
   b.dpack = wa.dpack; b.dNpad = wa.Npad; b.wC = wa.seg[0].C;
   {  // the production form: per-workgroup slots + the reduction launch (stream-ordered scratch of this call)
     const Bw1Geom q = bw1_geometry(b.c);

@@ -229,8 +229,6 @@ __global__ __launch_bounds__(CF_NT, 2) void cf_kernel(const CfArgs g) {
   }
 }
 
-bool cf_enabled() { return !lab_flag("DMM_NO_CF"); }
-
 // Takes the forward launch (EPI_STORE) of a 3x3 unit-stride convolution over ONE plain segment of 128 BN+ReLU-normalised channels with 32
 // output channels, whole 8 x 16 tiles and at least DMM_CF_MIN_TILES of them (default: eight per CU - measured: 4800 tiles 87 -> 70 us, 1200 tiles 29 -> 30 us), 16-bit storage.
 // Refused otherwise (conv3.hip takes the launch then).

@@ -192,9 +192,10 @@ constexpr int W3_SLOT_FLOATS = 9 * 128 * 32;  // one workgroup's partial result 
 constexpr int W3_MAX_SLOTS = 256;             // = workgroups of a launch at most (device-independent: plans are sized without a GPU)
 
 // Kernel family of a convolution / weight-gradient launch.  A plan decides it ONCE per launch when it is built (igemm_pick /
-// wgrad_pick ask every family's resolve, in dispatch order, and honour the dmm_set_option switches of that moment: dispatch.h) and the
-// executor asks the recorded family's resolve alone, so a plan's labels, its profile classes and the kernels it runs cannot drift
-// apart when an option is toggled afterwards.  IMPL_AUTO (the single-kernel test entry points): decide at the call.
+// wgrad_pick ask every family's resolve, in dispatch order, but for the families of the plan's deny mask - 1 << family, the
+// dmm_set_option switches of that moment: dispatch.h) and the executor asks the recorded family's resolve alone, so a plan's labels, its
+// profile classes and the kernels it runs cannot drift apart when an option is toggled afterwards.  IMPL_AUTO (the single-kernel test
+// entry points): decide at the call, under the mask the caller passes.
 enum Impl { IMPL_AUTO = 0, IMPL_GENERIC = 1, IMPL_THIN, IMPL_CONV3, IMPL_CVP, IMPL_HALO, IMPL_WG3, IMPL_WG5, IMPL_WGP, IMPL_PIG, IMPL_BW1, IMPL_HF, IMPL_CF, IMPL_WGPW /* wgp in its wave-specialised form: noted beside IMPL_WGP */, IMPL_CVW /* likewise cvp forward (cvw.hip) */, IMPL_COUNT };
 // The family that took the calling thread's most recent convolution / weight-gradient / fused-backward launch (dmm_last_impl):
 // a per-kernel test asserts the family it names really ran - IMPL_AUTO falls back to the generic kernels silently.

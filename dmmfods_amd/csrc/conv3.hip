@@ -501,10 +501,6 @@ __global__ __launch_bounds__(NTHREADS, 2) void conv3_kernel(const Conv3Args g) {
 }
 
 // ------------------------------------------------------------------------------------------------ host side
-static bool g_conv3 = !lab_flag("DMM_NO_CONV3");
-void conv3_set_enabled(bool on) { g_conv3 = on; }
-bool conv3_enabled() { return g_conv3; }
-
 // The launcher of one instantiation (what conv3_resolve hands to conv3_launch beside the kernel's arguments).
 typedef hipError_t (*C3Inst)(const Conv3Args& g, hipStream_t st);
 

@@ -746,10 +746,6 @@ __global__ __launch_bounds__(NTHREADS, 3) void cvd3_kernel(const CvdArgs g) {
   }
 }
 
-static bool g_cvp = !lab_flag("DMM_NO_CVP");
-void cvp_set_enabled(bool on) { g_cvp = on; }
-bool cvp_enabled() { return g_cvp; }
-
 // the wave-specialised form of the forward (cvw.hip, round 5): noted as IMPL_CVW beside IMPL_CVP when it runs
 bool cvw_resolve(const ConvArgs& a, int dtype, const int* ph_dymin, const int* ph_dxmin, Resolved& r);
 hipError_t cvw_launch(const Resolved& r, hipStream_t st);

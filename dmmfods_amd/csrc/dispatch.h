@@ -1,7 +1,6 @@
 // How a convolution / weight-gradient launch finds its kernel family, and the two host helpers every launcher shares.
 //
 // A family is one row of a table (igemm.hip: kConvFamilies, wgrad.hip: kWgradFamilies; the order of a table is the dispatch order):
-//   enabled()  the family's switch (dmm_set_option, lab flags);
 //   resolve()  host-only and pure: refuses the launch (false) or fills `Resolved` with everything the launch needs that does not depend
 //              on the device - the family's argument block AND the kernel instantiation that will run (a function pointer out of the
 //              family's one ladder of instantiations: "is there an instantiation?" and "which one?" are the same question).  It does not
@@ -10,6 +9,9 @@
 //              It cannot refuse a shape: what it returns is the runtime's error.
 // igemm_pick / wgrad_pick (plan.cpp, while a plan is built) and launch_igemm / launch_wgrad (at run time) walk the SAME table with the
 // SAME resolve, so a refusal the plan cannot see does not exist.
+// A family is switched off by ONE word, the deny mask (1 << family), handed down as an argument: a plan carries the mask it was built
+// under (dmm_plan::deny = DMM_NO_HF + the process-wide switches of dmm_set_option, capi.cpp), a single-kernel entry point passes the
+// process-wide switches of the moment.  No kernel file keeps a switch of its own.
 #pragma once
 #include <new>
 
@@ -29,24 +31,30 @@ struct Resolved {
 };
 struct ConvFamily {
   int family;  // enum Impl
-  bool (*enabled)();
   bool (*resolve)(const ConvArgs& a, int dtype, int epi, Resolved& r);
   hipError_t (*launch)(const Resolved& r, hipStream_t st);
 };
 struct WgradFamily {
   int family;
-  bool (*enabled)();
   bool (*resolve)(const WgradArgs& a, int dtype, Resolved& r);
   hipError_t (*launch)(const Resolved& r, hipStream_t st);
 };
-// May `f` take a launch?  impl = IMPL_AUTO: every enabled family that `deny` (1 << family: what a plan's switches rule out, plan.h
-// PlanSwitches) does not name; otherwise only the family a plan recorded, whatever the switches say now.
+// May `f` take a launch?  impl = IMPL_AUTO: every family that `deny` (1 << family) does not name; otherwise only the family a plan
+// recorded, whatever the switches say now.
 template <typename F> inline bool family_allowed(const F& f, int impl, unsigned deny) {
-  return impl == IMPL_AUTO ? (f.enabled() && !((deny >> f.family) & 1u)) : impl == f.family;
+  return impl == IMPL_AUTO ? !((deny >> f.family) & 1u) : impl == f.family;
+}
+// The families a lab build (common.h: lab_flag) switches off from the environment: the initial value of the process-wide mask.
+// Constant 0 in the shipped library.
+inline unsigned lab_family_off() {
+  return (lab_flag("DMM_NO_CONV3") ? 1u << IMPL_CONV3 : 0) | (lab_flag("DMM_NO_WG3") ? 1u << IMPL_WG3 : 0) |
+         (lab_flag("DMM_NO_WG5") ? 1u << IMPL_WG5 : 0) | (lab_flag("DMM_NO_WGP") ? 1u << IMPL_WGP : 0) |
+         (lab_flag("DMM_NO_CVP") ? 1u << IMPL_CVP : 0) | (lab_flag("DMM_NO_PIG") ? 1u << IMPL_PIG : 0) |
+         (lab_flag("DMM_NO_BW1") ? 1u << IMPL_BW1 : 0) | (lab_flag("DMM_NO_CF") ? 1u << IMPL_CF : 0) |
+         (lab_flag("DMM_NO_HALO") ? 1u << IMPL_HALO : 0);
 }
 
 #define DMM_CONV_FAMILY(name)                                              \
-  bool name##_enabled();                                                   \
   bool name##_resolve(const ConvArgs& a, int dtype, int epi, Resolved& r); \
   hipError_t name##_launch(const Resolved& r, hipStream_t st);
 DMM_CONV_FAMILY(thin)   // thin.hip
@@ -58,7 +66,6 @@ DMM_CONV_FAMILY(pig)    // pig.hip
 DMM_CONV_FAMILY(halo)   // halo.hip
 #undef DMM_CONV_FAMILY
 #define DMM_WGRAD_FAMILY(name)                                     \
-  bool name##_enabled();                                           \
   bool name##_resolve(const WgradArgs& a, int dtype, Resolved& r); \
   hipError_t name##_launch(const Resolved& r, hipStream_t st);
 DMM_WGRAD_FAMILY(wg3)  // wg3.hip

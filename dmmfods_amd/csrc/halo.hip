@@ -411,7 +411,7 @@ static bool halo_plan(const ConvArgs& a, int dtype, int epi, HaloArgs& h) {
 }
 
 // The launcher of one (storage type, column tile, epilogue) instantiation: what halo_resolve hands to halo_launch beside the kernel's
-// arguments.  It picks the slots-per-thread variant, raises its LDS limit (every time: four kernels share the launcher) and launches.
+// arguments.  It picks the slots-per-thread variant and launches it, its LDS limit raised first.
 typedef hipError_t (*HaloInst)(const HaloArgs& h, hipStream_t st);
 
 template <typename T, int BN, int EPI, bool EFF>
@@ -419,16 +419,12 @@ static hipError_t launch_halo_ns(const HaloArgs& h, hipStream_t st) {
   const int ns = (h.nsl_total + NTHREADS - 1) / NTHREADS;
   int grid = halo_cus();
   if (grid > h.ntiles) grid = h.ntiles;
-  auto go = [&](auto kern) -> hipError_t {
-    hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(NTHREADS), h.lds_bytes, st, h);
-    return hipGetLastError();
-  };
-  if (ns <= 4) return go(halo_kernel<T, BN, EPI, EFF, 4>);
-  if (ns <= 8) return go(halo_kernel<T, BN, EPI, EFF, 8>);
-  if (ns <= 12) return go(halo_kernel<T, BN, EPI, EFF, 12>);
-  return go(halo_kernel<T, BN, EPI, EFF, HALO_MAX_NS>);
+  LdsLauncher<HaloArgs> run;
+  if (ns <= 4) run = launch_lds<halo_kernel<T, BN, EPI, EFF, 4>, HaloArgs>;
+  else if (ns <= 8) run = launch_lds<halo_kernel<T, BN, EPI, EFF, 8>, HaloArgs>;
+  else if (ns <= 12) run = launch_lds<halo_kernel<T, BN, EPI, EFF, 12>, HaloArgs>;
+  else run = launch_lds<halo_kernel<T, BN, EPI, EFF, HALO_MAX_NS>, HaloArgs>;
+  return run(160 * 1024, grid, NTHREADS, h.lds_bytes, st, h);
 }
 
 // Variants built: forward (EPI_STORE) for N <= 64, logits for N <= 32, data gradients for N <= 128 (nullptr: none for this width).
@@ -456,8 +452,6 @@ struct HaloLaunch {
   HaloArgs h;
   HaloInst run;
 };
-
-bool halo_enabled() { static const bool no_halo = lab_flag("DMM_NO_HALO"); return !no_halo; }
 
 // Multi-tap layers whose weights fit in LDS (fp32 / f16).  Refused when the layer is not eligible.
 bool halo_resolve(const ConvArgs& a, int dtype, int epi, Resolved& r) {

@@ -343,11 +343,10 @@ static bool hf_tap_box(const short* taps, int ntaps, int want_span, int& dymin, 
   return true;
 }
 
-bool hf_enabled() { return true; }   // (DMM_NO_HF is a plan's switch: PlanSwitches::no_hf, plan.h - it reaches igemm_pick as `deny`)
-
 // Takes the four-phase forward launch of the head's first convolution (ConvArgs::nphase = 4): a 128-channel BN+ReLU-normalised
 // half-resolution segment with 2x2 taps per phase, an 8-channel raw segment with 3x3 taps at stride 2, 64 output channels stored at
-// stride 2, whole 8 x 16 tiles, 16-bit storage.  Refused otherwise (conv3.hip takes the launch then).
+// stride 2, whole 8 x 16 tiles, 16-bit storage.  Refused otherwise (conv3.hip takes the launch then; so does DMM_NO_HF, a bit of the
+// plan's deny mask: plan.h).
 bool hf_resolve(const ConvArgs& a, int dtype, int epi, Resolved& r) {
   if (dtype == DT_F32 || epi != EPI_STORE || a.nphase != 4 || a.nseg != 2 || a.pool2) return false;
   const Seg& u = a.seg[0];

@@ -671,7 +671,6 @@ template <typename T, int BN, int EPI, int KSV, int NW>
 static hipError_t launch_bn_ks(const ConvArgs& a, bool mfma, hipStream_t st) {
   const int mtiles = (a.M + BM - 1) / BM;
   const int ntiles = a.Npad / BN;
-  dim3 grid(mtiles * ntiles), block(64 * NW);
   int kfl = 0;
   for (int s = 0; s < a.nseg; ++s) kfl += seg_const_floats(a.seg[s]);
   int nchunks = 0;
@@ -688,26 +687,18 @@ static hipError_t launch_bn_ks(const ConvArgs& a, bool mfma, hipStream_t st) {
     if (sg.mode == G_POOL2 || (sg.scale ? 1 : (sg.q ? 2 : 0)) != pro) pro = -1;
   }
   constexpr int P1 = EPI == EPI_BNBWD ? 2 : 1;  // the prologue this epilogue normally sees
-  void (*kern)(const ConvArgs);
-  int ai;
+  LdsLauncher<ConvArgs> run;
   if (!mfma) {
     // the scalar check kernels exist for fp32 / f16 (bring-up); bf16 arrived with the MFMA kernels already proven
     if constexpr (std::is_same<T, bf16>::value) return hipErrorNotSupported;
     else if constexpr (NW != 4) return hipErrorNotSupported;
-    else { kern = igemm_kernel<T, BN, EPI, false, false, -1, KSV, NW>; ai = 0; }
+    else run = launch_lds<igemm_kernel<T, BN, EPI, false, false, -1, KSV, NW>, ConvArgs>;
   }
-  else if (pro == P1) { kern = lin ? igemm_kernel<T, BN, EPI, true, true, P1, KSV, NW> : igemm_kernel<T, BN, EPI, true, false, P1, KSV, NW>; ai = lin ? 1 : 2; }
-  else if (pro == 0) { kern = lin ? igemm_kernel<T, BN, EPI, true, true, 0, KSV, NW> : igemm_kernel<T, BN, EPI, true, false, 0, KSV, NW>; ai = lin ? 3 : 4; }
-  else { kern = igemm_kernel<T, BN, EPI, true, false, -1, KSV, NW>; ai = 5; }
-  static int attr_bytes[6] = {0, 0, 0, 0, 0, 0};
-  if (smem > 48 * 1024 && smem > attr_bytes[ai]) {
-    hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e != hipSuccess) return e;
-    attr_bytes[ai] = 160 * 1024;
-  }
+  else if (pro == P1) run = lin ? launch_lds<igemm_kernel<T, BN, EPI, true, true, P1, KSV, NW>, ConvArgs> : launch_lds<igemm_kernel<T, BN, EPI, true, false, P1, KSV, NW>, ConvArgs>;
+  else if (pro == 0) run = lin ? launch_lds<igemm_kernel<T, BN, EPI, true, true, 0, KSV, NW>, ConvArgs> : launch_lds<igemm_kernel<T, BN, EPI, true, false, 0, KSV, NW>, ConvArgs>;
+  else run = launch_lds<igemm_kernel<T, BN, EPI, true, false, -1, KSV, NW>, ConvArgs>;
   if (smem > 160 * 1024) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(kern, grid, block, smem, st, a);
-  return hipGetLastError();
+  return run(smem > 48 * 1024 ? 160 * 1024 : 0, mtiles * ntiles, 64 * NW, smem, st, a);
 }
 
 // Chunks per stage: measured on MI355X (C2 b4) - 4 chunks per stage for the launches with <= 512 workgroups (halving their
@@ -781,13 +772,13 @@ extern template hipError_t launch_igemm_type<bf16>(const ConvArgs&, int, bool, h
 
 // The special-case families in dispatch order.
 static const ConvFamily kConvFamilies[] = {
-    {IMPL_THIN, thin_enabled, thin_resolve, thin_launch},      // few output channels x many taps: gather once, reduce the taps in LDS
-    {IMPL_HF, hf_enabled, hf_resolve, hf_launch},              // the head's first convolution, four parity phases in one launch: wave-specialised, phase weights resident in LDS
-    {IMPL_CF, cf_enabled, cf_resolve, cf_launch},              // the dense 3x3 forward on the large maps: wave-specialised, weights resident in LDS
-    {IMPL_CONV3, conv3_enabled, conv3_resolve, conv3_launch},  // 3x3 convolutions of the dense layers (16-bit storage): LDS halo tile, prologue once per element
-    {IMPL_CVP, cvp_enabled, cvp_resolve, cvp_launch},          // forward of the ConvTranspose parity phases: halo tile per 128-channel group, a tap is a fragment address
-    {IMPL_PIG, pig_enabled, pig_resolve, pig_launch},          // plain 1x1 convolutions, forward: persistent workgroups (next tile's loads under this tile's epilogue)
-    {IMPL_HALO, halo_enabled, halo_resolve, halo_launch},      // multi-tap layers whose weights fit in LDS may take the halo-tile kernel
+    {IMPL_THIN, thin_resolve, thin_launch},     // few output channels x many taps: gather once, reduce the taps in LDS
+    {IMPL_HF, hf_resolve, hf_launch},           // the head's first convolution, four parity phases in one launch: wave-specialised, phase weights resident in LDS
+    {IMPL_CF, cf_resolve, cf_launch},           // the dense 3x3 forward on the large maps: wave-specialised, weights resident in LDS
+    {IMPL_CONV3, conv3_resolve, conv3_launch},  // 3x3 convolutions of the dense layers (16-bit storage): LDS halo tile, prologue once per element
+    {IMPL_CVP, cvp_resolve, cvp_launch},        // forward of the ConvTranspose parity phases: halo tile per 128-channel group, a tap is a fragment address
+    {IMPL_PIG, pig_resolve, pig_launch},        // plain 1x1 convolutions, forward: persistent workgroups (next tile's loads under this tile's epilogue)
+    {IMPL_HALO, halo_resolve, halo_launch},     // multi-tap layers whose weights fit in LDS may take the halo-tile kernel
 };
 
 // The first family that may take the launch (family_allowed) and resolves it; nullptr: none does - the launch is the generic kernel's.
@@ -800,13 +791,14 @@ static const ConvFamily* conv_family(const ConvArgs& a, int dtype, int epi, int 
   return nullptr;
 }
 
-// impl = IMPL_AUTO: every enabled family may take the launch (the single-kernel test entry points); otherwise the family a plan
-// recorded for this launch when it was built (igemm_pick), whatever the option switches say now.
-hipError_t launch_igemm(const ConvArgs& a, int dtype, int epi, bool mfma, hipStream_t st, int impl) {
+// impl = IMPL_AUTO: every family `deny` does not name may take the launch (the single-kernel test entry points, which pass the
+// process-wide switches); otherwise the family a plan recorded for this launch when it was built (igemm_pick), whatever the option
+// switches say now.
+hipError_t launch_igemm(const ConvArgs& a, int dtype, int epi, bool mfma, hipStream_t st, int impl, unsigned deny) {
   if (a.M <= 0) return hipSuccess;
   if (mfma && impl != IMPL_GENERIC) {
     Resolved r;
-    if (const ConvFamily* f = conv_family(a, dtype, epi, impl, 0, r)) {
+    if (const ConvFamily* f = conv_family(a, dtype, epi, impl, deny, r)) {
       const hipError_t e = f->launch(r, st);
       note_impl(f->family);
       return e;
@@ -822,8 +814,7 @@ hipError_t launch_igemm(const ConvArgs& a, int dtype, int epi, bool mfma, hipStr
   return launch_igemm_type<float>(a, epi, mfma, st);
 }
 
-// Which family launch_igemm(..., IMPL_AUTO) would run for this launch right now, `deny` taken out (nothing is launched, the runtime
-// is not asked anything).
+// Which family launch_igemm(..., IMPL_AUTO, deny) would run for this launch (nothing is launched, the runtime is not asked anything).
 int igemm_pick(const ConvArgs& a, int dtype, int epi, bool mfma, unsigned deny) {
   if (!mfma) return IMPL_GENERIC;
   Resolved r;

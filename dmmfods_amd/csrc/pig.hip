@@ -240,11 +240,6 @@ __global__ __launch_bounds__(NTHREADS, 2) void pig_kernel(const PigArgs g) {
   }
 }
 
-static bool g_pig = !lab_flag("DMM_NO_PIG");
-void pig_set_enabled(bool on) { g_pig = on; }
-
-bool pig_enabled() { return g_pig; }
-
 // What pig_resolve hands to pig_launch: the kernel's arguments but for the walkers, the workgroups a CU holds, the instantiation.
 struct PigLaunch {
   PigArgs g;

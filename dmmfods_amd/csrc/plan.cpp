@@ -375,7 +375,7 @@ struct Builder {
   // ---- switches of this plan and lab knobs, read once ----
   const bool pack_tiles_on = !P.sw.no_pack_tiles;
   const bool s2_interleave = !P.sw.no_s2_interleave;
-  const unsigned deny = P.sw.no_hf ? 1u << IMPL_HF : 0u;   // families the plan's switches rule out (igemm_pick / wgrad_pick)
+  const unsigned deny = P.deny;   // families ruled out for this pass (igemm_pick / wgrad_pick / bw1_eligible)
   const bool s2_overlap = !lab_flag("DMM_NO_S2_OVERLAP");  // lab knob
   const bool front_matz = !lab_flag("DMM_NO_FRONT_MATZ");  // lab knob
   // which multi-consumer gradients are materialised (q + r*y applied once by applycorr) instead of corrected by every consumer's
@@ -1064,7 +1064,7 @@ struct Builder {
       part_slots = q.nsplit * q.nct;
       part = wptr<float>((size_t)part_slots * B1_SLOT_FLOATS);
     }
-    if (raw || !bw1_eligible(saved_w.w, dgrad_op.c, dtype)) {   // not this time
+    if (raw || !bw1_eligible(saved_w.w, dgrad_op.c, dtype, deny)) {   // not this time
       ops->pop_back();
       ops->push_back(saved_w);
       st.dgrad_op = dgrad_op;

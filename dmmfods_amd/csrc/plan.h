@@ -95,7 +95,7 @@ struct GradBucket {
 // Each selects between two correct schedules of the same arithmetic and has an A/B test (tests/test_timed_kernels_gpu.py; the host
 // harness of tests/test_host_cpu.py drives every one through create -> bind -> run -> destroy under AddressSanitizer):
 //   DMM_NO_PACK_TILES=1     weights packed / gradients unpacked by the generic kernels only
-//   DMM_NO_HF=1             the head's first convolution on conv3.hip's one-launch path instead of hf.hip
+//   DMM_NO_HF=1             the head's first convolution on conv3.hip's one-launch path instead of hf.hip (a bit of dmm_plan::deny)
 //   DMM_NO_C3_MERGE=1       ... as four launches, one per output parity
 //   DMM_NO_CVP_MERGE=1      a decoder ConvTranspose's four parity phases as four launches
 //   DMM_NO_WGP_MERGE=1      the head's weight-gradient phases as four launches
@@ -108,7 +108,8 @@ struct GradBucket {
 //   DMM_NO_RAW_STATS=1      the BatchNorm-backward sums of the head's raw-input channels from a data-gradient pass of their own
 //                           (round 4) instead of from the weight gradient's factor correlations (wg5.hip, PY = 2)
 // Process-wide (capi.cpp, read when the library is loaded; also dmm_set_option): DMM_NO_OVERLAP, DMM_GRAPH, DMM_GRAD_BUCKET_MB;
-// diagnostics: DMM_TRACE_DESTROY.  Everything else that used to be an environment switch is a compile-time lab knob (common.h).
+// dmm_set_option alone: the kernel-family switches, one word (capi.cpp: g_family_off), copied into dmm_plan::deny in front of each
+// builder pass; diagnostics: DMM_TRACE_DESTROY.  Everything else that used to be an environment switch is a compile-time lab knob (common.h).
 struct PlanSwitches {
   bool no_pack_tiles = false, no_hf = false, no_c3_merge = false, no_cvp_merge = false, no_wgp_merge = false, no_two_pass = false,
        no_eff_compact = false, no_s2_interleave = false, no_raw_stats = false, no_r1_stats = false;
@@ -119,6 +120,8 @@ struct PlanSwitches {
 struct dmm_plan {
   dmm_model_desc desc;
   PlanSwitches sw;
+  unsigned deny = 0;  // kernel families ruled out (1 << family, dispatch.h): DMM_NO_HF + the dmm_set_option switches, as they stood when the
+                      // builder pass in progress began (dmm_plan_create: sizing, dmm_plan_bind: the launch lists)
   std::vector<dmm::TensorInfo> tensors;
   int64_t nparams = 0, nbuf = 0;
   size_t zero_bytes = 0, zero_bwd_bytes = 0, main_bytes = 0;

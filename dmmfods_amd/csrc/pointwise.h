@@ -185,22 +185,15 @@ struct Bw1Args {
 struct Bw1Geom { int nct, ntiles, tiles_per_wg, nsplit, xcd_group, nwg; };
 Bw1Geom bw1_geometry(const ConvArgs& a);   // how launch_bw1 splits the launch (device-dependent: compute units)
 constexpr int B1_SLOT_FLOATS = 4 * 128 * 32;  // one workgroup's slice: 4 chunks of 32 input channels x 128 bottleneck channels
-bool bw1_eligible(const WgradArgs& w, const ConvArgs& d, int dtype);
+bool bw1_eligible(const WgradArgs& w, const ConvArgs& d, int dtype, unsigned deny);  // deny: as igemm_pick
 hipError_t launch_bw1(const Bw1Args& g, int dtype, hipStream_t st);
 hipError_t launch_bw1_reduce(const Bw1Args& g, hipStream_t st);  // dpack = sum of the slots (no-op without `part`)
-hipError_t launch_igemm(const ConvArgs& a, int dtype, int epi, bool mfma, hipStream_t st, int impl = IMPL_AUTO);
-hipError_t launch_wgrad(WgradArgs a, int dtype, bool mfma, hipStream_t st, int impl = IMPL_AUTO);
-// the family (enum Impl) that would run the launch now; deny: 1 << family for families the asking plan's switches rule out
+// impl = IMPL_AUTO: the first family of the table that `deny` (1 << family) does not name and that resolves; otherwise the recorded family
+hipError_t launch_igemm(const ConvArgs& a, int dtype, int epi, bool mfma, hipStream_t st, int impl = IMPL_AUTO, unsigned deny = 0);
+hipError_t launch_wgrad(WgradArgs a, int dtype, bool mfma, hipStream_t st, int impl = IMPL_AUTO, unsigned deny = 0);
+// the family (enum Impl) that launch_*(..., IMPL_AUTO, deny) would run; deny: 1 << family for the families switched off (dmm_plan::deny)
 int igemm_pick(const ConvArgs& a, int dtype, int epi, bool mfma, unsigned deny);
 int wgrad_pick(const WgradArgs& a, int dtype, bool mfma, unsigned deny);
-void thin_set_enabled(bool on);  // thin.hip
-void conv3_set_enabled(bool on);  // conv3.hip
-void wg3_set_enabled(bool on);    // wg3.hip
-void wgp_set_enabled(bool on);    // wgp.hip
-void wg5_set_enabled(bool on);    // wg5.hip
-void cvp_set_enabled(bool on);    // cvp.hip
-void bw1_set_enabled(bool on);    // bw1.hip
-void pig_set_enabled(bool on);    // pig.hip
 hipError_t launch_wg5_rawfin(const RawFinArgs& a, hipStream_t st);
 hipError_t launch_wg5_fin64(const Fin64Args& a, hipStream_t st);
 hipError_t launch_convert_input(const ConvertArgs& a, int dtype, hipStream_t st);

@@ -201,15 +201,10 @@ __global__ __launch_bounds__(NTHREADS, 2) void thin_logits_kernel(const ThinArgs
   }
 }
 
-static bool g_no_thin = false;
-void thin_set_enabled(bool on) { g_no_thin = !on; }
-
-bool thin_enabled() { return !g_no_thin; }
-
 // What thin_resolve hands to thin_launch: the kernel's arguments and the instantiation (storage type, tap radius, classes) that runs.
 struct ThinLaunch {
   ThinArgs a;
-  void (*kern)(const ThinArgs);
+  LdsLauncher<ThinArgs> run;
 };
 
 // Few output channels x many taps (the 5x5 logits convolution): refused unless there is an instantiation for the layer.
@@ -237,12 +232,12 @@ bool thin_resolve(const ConvArgs& c, int dtype, int epi, Resolved& r) {
     if (dy != t / kw - R || dx != t % kw - R) return false;
     a.dy[t] = (signed char)dy; a.dx[t] = (signed char)dx;
   }
-  l.kern = nullptr;
+  l.run = nullptr;
   const bool bf = dtype == DT_BF16;
-  if (R == 2 && c.N == 3) l.kern = bf ? thin_logits_kernel<bf16, 2, 3> : thin_logits_kernel<f16, 2, 3>;
-  else if (R == 2 && c.N == 1) l.kern = bf ? thin_logits_kernel<bf16, 2, 1> : thin_logits_kernel<f16, 2, 1>;
-  else if (R == 2 && c.N == 2) l.kern = bf ? thin_logits_kernel<bf16, 2, 2> : thin_logits_kernel<f16, 2, 2>;
-  if (l.kern == nullptr) return false;
+  if (R == 2 && c.N == 3) l.run = bf ? launch_lds<thin_logits_kernel<bf16, 2, 3>, ThinArgs> : launch_lds<thin_logits_kernel<f16, 2, 3>, ThinArgs>;
+  else if (R == 2 && c.N == 1) l.run = bf ? launch_lds<thin_logits_kernel<bf16, 2, 1>, ThinArgs> : launch_lds<thin_logits_kernel<f16, 2, 1>, ThinArgs>;
+  else if (R == 2 && c.N == 2) l.run = bf ? launch_lds<thin_logits_kernel<bf16, 2, 2>, ThinArgs> : launch_lds<thin_logits_kernel<f16, 2, 2>, ThinArgs>;
+  if (l.run == nullptr) return false;
   a.R = R;
   const int wout = TH_PX - 2 * R;
   a.nxs = (a.W + wout - 1) / wout;
@@ -265,14 +260,7 @@ bool thin_resolve(const ConvArgs& c, int dtype, int epi, Resolved& r) {
 
 hipError_t thin_launch(const Resolved& r, hipStream_t st) {
   const ThinLaunch& l = r.get<ThinLaunch>();
-  static const void* attr = nullptr;   // (the last instantiation whose LDS limit was raised)
-  if (attr != (const void*)l.kern) {
-    hipError_t e = hipFuncSetAttribute((const void*)l.kern, hipFuncAttributeMaxDynamicSharedMemorySize, ThinSmem::bytes);
-    if (e != hipSuccess) return e;
-    attr = (const void*)l.kern;
-  }
-  hipLaunchKernelGGL(l.kern, dim3(l.a.B * l.a.nys * l.a.nxs), dim3(NTHREADS), ThinSmem::bytes, st, l.a);
-  return hipGetLastError();
+  return l.run(ThinSmem::bytes, l.a.B * l.a.nys * l.a.nxs, NTHREADS, ThinSmem::bytes, st, l.a);
 }
 
 }  // namespace dmm

@@ -293,10 +293,6 @@ __global__ __launch_bounds__(256) void wg3_reduce_kernel(const float* __restrict
   }
 }
 
-static bool g_wg3 = !lab_flag("DMM_NO_WG3");
-void wg3_set_enabled(bool on) { g_wg3 = on; }
-bool wg3_enabled() { return g_wg3; }
-
 // What wg3_resolve hands to wg3_launch: the kernel's arguments but for the split over workgroups, and the instantiation that runs.
 struct Wg3Launch {
   Wg3Args g;

@@ -331,10 +331,6 @@ __global__ __launch_bounds__(NTHREADS, (TR == 3 ? 1 : ((PA == 3 || (PA == 0 && P
   }
 }
 
-static bool g_wg5 = !lab_flag("DMM_NO_WG5");
-void wg5_set_enabled(bool on) { g_wg5 = on; }
-bool wg5_enabled() { return g_wg5; }
-
 // The launcher of one instantiation (no LDS attribute: every form fits the default limit).
 typedef hipError_t (*Wg5Inst)(const Wg5Args& g, int nwg, hipStream_t st);
 template <typename T, int TR, int STR, int PA, int PY = 0>

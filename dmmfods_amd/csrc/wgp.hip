@@ -237,9 +237,6 @@ __global__ __launch_bounds__(NTHREADS, 1) void wgp_kernel(const WgpArgs g) {
   }
 }
 
-static bool g_wgp = !lab_flag("DMM_NO_WGP");
-void wgp_set_enabled(bool on) { g_wgp = on; }
-bool wgp_enabled() { return g_wgp; }
 // the wave-specialised form (wgpw.hip): noted as IMPL_WGPW beside IMPL_WGP when it runs
 bool wgpw_resolve(const WgradArgs& a, int dtype, int ntap, int nj, const WgpGeom& q, Resolved& r);   // operands below 4 GiB, its instantiations
 hipError_t wgpw_launch(const Resolved& r, hipStream_t st);

@@ -363,33 +363,24 @@ static hipError_t launch_w(const WgradArgs& a, bool mfma, hipStream_t st) {
   typedef WgradSmem<T, WBN> SM;
   const int ntiles = a.Npad / WBN;
   const int splits = (a.M + a.rows_per_split - 1) / a.rows_per_split;
-  dim3 grid(ntiles * a.kgroups * splits), block(NTHREADS);
   int pq = seg_pro(a.seg[0]);
   for (int s = 1; s < a.nseg; ++s) if (seg_pro(a.seg[s]) != pq) pq = -1;
   const int pp = seg_pro(a.dy);
   const bool lin = a.nseg == 1 && seg_lin(a.seg[0], a) && seg_lin(a.dy, a);
-  void (*kern)(const WgradArgs);
-  int ai;
+  LdsLauncher<WgradArgs> run;
   if (!mfma) {
     if constexpr (std::is_same<T, bf16>::value) return hipErrorNotSupported;  // no scalar check kernels for bf16 (see igemm.hip)
-    else { kern = wgrad_kernel<T, WBN, false, -1, -1, false, WDIST(WBN, -1, -1)>; ai = 0; }
+    else run = launch_lds<wgrad_kernel<T, WBN, false, -1, -1, false, WDIST(WBN, -1, -1)>, WgradArgs>;
   }
-  else if (lin && pp == 2 && pq == 1) { kern = wgrad_kernel<T, WBN, true, 2, 1, true, WDIST(WBN, 2, 1)>; ai = 1; }
-  else if (lin && pp == 0 && pq == 1) { kern = wgrad_kernel<T, WBN, true, 0, 1, true, WDIST(WBN, 0, 1)>; ai = 7; }
-  else if (pp == 0 && pq == 1) { kern = wgrad_kernel<T, WBN, true, 0, 1, false, WDIST(WBN, 0, 1)>; ai = 8; }
-  else if (pp == 2 && pq == 1) { kern = wgrad_kernel<T, WBN, true, 2, 1, false, WDIST(WBN, 2, 1)>; ai = 2; }
-  else if (pp == 1 && pq == 2) { kern = wgrad_kernel<T, WBN, true, 1, 2, false, WDIST(WBN, 1, 2)>; ai = 3; }
-  else if (pp == 2 && pq == 0) { kern = wgrad_kernel<T, WBN, true, 2, 0, false, WDIST(WBN, 2, 0)>; ai = 4; }
-  else if (pp == 1 && pq == 0) { kern = wgrad_kernel<T, WBN, true, 1, 0, false, WDIST(WBN, 1, 0)>; ai = 5; }
-  else { kern = wgrad_kernel<T, WBN, true, -1, -1, false, WDIST(WBN, -1, -1)>; ai = 6; }
-  static bool attr_done[9] = {false, false, false, false, false, false, false, false, false};
-  if (SM::bytes > 48 * 1024 && !attr_done[ai]) {
-    hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, SM::bytes);
-    if (e != hipSuccess) return e;
-    attr_done[ai] = true;
-  }
-  hipLaunchKernelGGL(kern, grid, block, SM::bytes, st, a);
-  return hipGetLastError();
+  else if (lin && pp == 2 && pq == 1) run = launch_lds<wgrad_kernel<T, WBN, true, 2, 1, true, WDIST(WBN, 2, 1)>, WgradArgs>;
+  else if (lin && pp == 0 && pq == 1) run = launch_lds<wgrad_kernel<T, WBN, true, 0, 1, true, WDIST(WBN, 0, 1)>, WgradArgs>;
+  else if (pp == 0 && pq == 1) run = launch_lds<wgrad_kernel<T, WBN, true, 0, 1, false, WDIST(WBN, 0, 1)>, WgradArgs>;
+  else if (pp == 2 && pq == 1) run = launch_lds<wgrad_kernel<T, WBN, true, 2, 1, false, WDIST(WBN, 2, 1)>, WgradArgs>;
+  else if (pp == 1 && pq == 2) run = launch_lds<wgrad_kernel<T, WBN, true, 1, 2, false, WDIST(WBN, 1, 2)>, WgradArgs>;
+  else if (pp == 2 && pq == 0) run = launch_lds<wgrad_kernel<T, WBN, true, 2, 0, false, WDIST(WBN, 2, 0)>, WgradArgs>;
+  else if (pp == 1 && pq == 0) run = launch_lds<wgrad_kernel<T, WBN, true, 1, 0, false, WDIST(WBN, 1, 0)>, WgradArgs>;
+  else run = launch_lds<wgrad_kernel<T, WBN, true, -1, -1, false, WDIST(WBN, -1, -1)>, WgradArgs>;
+  return run(SM::bytes > 48 * 1024 ? SM::bytes : 0, ntiles * a.kgroups * splits, NTHREADS, SM::bytes, st, a);
 }
 
 template <typename T>
@@ -416,9 +407,9 @@ extern template hipError_t launch_wt<bf16>(const WgradArgs&, bool, hipStream_t);
 
 // The special-case families in dispatch order.
 static const WgradFamily kWgradFamilies[] = {
-    {IMPL_WG3, wg3_enabled, wg3_resolve, wg3_launch},  // the dense layers' 3x3 growth convolution: persistent tiles, the whole result in registers
-    {IMPL_WG5, wg5_enabled, wg5_resolve, wg5_launch},  // the head's 5x5 convolution onto 3 classes: persistent tiles, the 25 x 8 (tap, class) columns as per-lane addresses
-    {IMPL_WGP, wgp_enabled, wgp_resolve, wgp_launch},  // parity-phase convolutions (ConvTranspose stages, the head's 3x3 over the upsampled map): all taps of a phase per tile
+    {IMPL_WG3, wg3_resolve, wg3_launch},  // the dense layers' 3x3 growth convolution: persistent tiles, the whole result in registers
+    {IMPL_WG5, wg5_resolve, wg5_launch},  // the head's 5x5 convolution onto 3 classes: persistent tiles, the 25 x 8 (tap, class) columns as per-lane addresses
+    {IMPL_WGP, wgp_resolve, wgp_launch},  // parity-phase convolutions (ConvTranspose stages, the head's 3x3 over the upsampled map): all taps of a phase per tile
 };
 
 // The first family that may take the launch (family_allowed) and resolves it; nullptr: none does - the launch is the generic kernel's.
@@ -428,7 +419,7 @@ static const WgradFamily* wgrad_family(const WgradArgs& a, int dtype, int impl, 
   return nullptr;
 }
 
-// Which family launch_wgrad(..., IMPL_AUTO) would run right now, `deny` taken out (nothing is launched, the runtime is not asked anything).
+// Which family launch_wgrad(..., IMPL_AUTO, deny) would run (nothing is launched, the runtime is not asked anything).
 int wgrad_pick(const WgradArgs& a, int dtype, bool mfma, unsigned deny) {
   if (!mfma || a.M <= 0) return IMPL_GENERIC;
   Resolved r;
@@ -437,11 +428,11 @@ int wgrad_pick(const WgradArgs& a, int dtype, bool mfma, unsigned deny) {
 }
 
 // Fills rows_per_split / kgroups (if zero) and launches.  impl: as launch_igemm.
-hipError_t launch_wgrad(WgradArgs a, int dtype, bool mfma, hipStream_t st, int impl) {
+hipError_t launch_wgrad(WgradArgs a, int dtype, bool mfma, hipStream_t st, int impl, unsigned deny) {
   if (a.M <= 0) return hipSuccess;
   bool wgp_took = false;
   Resolved r;
-  if (const WgradFamily* f = (mfma && impl != IMPL_GENERIC) ? wgrad_family(a, dtype, impl, 0, r) : nullptr) {
+  if (const WgradFamily* f = (mfma && impl != IMPL_GENERIC) ? wgrad_family(a, dtype, impl, deny, r) : nullptr) {
     const hipError_t e = f->launch(r, st);
     if (f->family != IMPL_WGP) { note_impl(f->family); return e; }
     if (e != hipSuccess) return e;

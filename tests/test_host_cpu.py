@@ -322,16 +322,59 @@ def test_bind_checks_the_bound_pass_against_the_sizing_pass(host_drive):
     between create and bind cannot reach the bound pass) and run with the same null / non-null pattern of pointers; (b) every buffer is
     reserved by shape alone, so a kernel family switched off through dmm_set_option between the two calls changes launches, not bytes
     (checked here for every family); (c) dmm_plan_bind compares the three region sizes and returns DMM_ERR_STATE on any difference
-    - provoked here by flipping a switch inside the plan after it was sized."""
+    - provoked here by flipping a switch inside the plan after it was sized.  The switches of the moment of BIND decide the launches
+    (include/dmmfods_hip.h): the bound plan records no launch of the family that was switched off behind create (the driver prints the
+    records per family), and every other family keeps its launches."""
     base = {k: v for k, v in os.environ.items() if not k.startswith("DMM_")}
     base.update(ASAN_OPTIONS="detect_leaks=0")
+    recorded = {}
     for fam in ("conv3", "wg3", "bw1", "cvp", "pig", "wgp", "wg5", "thin_logits"):
         r = subprocess.run([host_drive, "d121e", "f16", "2", "64", "96", "1"], env=dict(base, DRIVE_TOGGLE_BETWEEN_CREATE_AND_BIND=fam),
                            capture_output=True, text=True, timeout=600)
         assert r.returncode == 0 and "DRIVE OK" in r.stdout, (fam, (r.stdout + r.stderr)[-2000:])
+        m = re.search(r"^FAMILIES (.*)$", r.stdout, re.M)
+        assert m, (fam, r.stdout[-2000:])
+        recorded[fam] = {k: int(v) for k, v in (kv.split("=") for kv in m[1].split())}
+        assert recorded[fam][fam.replace("thin_logits", "thin")] == 0, (fam, recorded[fam])
+    for fam in recorded:   # (not vacuous: the family is recorded when another one is switched off instead)
+        other = "wg3" if fam == "conv3" else "conv3"
+        assert recorded[other][fam.replace("thin_logits", "thin")] > 0, (fam, recorded[other])
     r = subprocess.run([host_drive, "d121e", "f16", "2", "64", "96", "1"], env=dict(base, DRIVE_FLIP_SWITCH_BETWEEN_CREATE_AND_BIND="1"),
                        capture_output=True, text=True, timeout=600)
     assert r.returncode == 2 and "-> -4" in r.stderr and "sizing pass" in r.stderr, (r.stdout + r.stderr)[-2000:]
+
+
+def test_a_family_switched_off_is_in_no_launch_record(host_drive):
+    """dmm_set_option(<family>, 0) is one bit of one process-wide mask (capi.cpp: g_family_off), a plan copies the mask in front of each
+    builder pass (dmm_plan::deny) and the picks, bw1_eligible and the IMPL_AUTO launches get it as an argument.  `drive dump d121e f16
+    2 64 96`: by default every switchable family is recorded (counts of this commit's parent: conv3 177, pig 124, bw1... labels 118,
+    wg3 58, cvp 13, wgp 5, wg5 3, thin 2); with the family's option off (DRIVE_OPTIONS_OFF, before dmm_plan_create) it is in no record
+    - for bw1: no record whose label starts with bw1 - and `drive picks` of that plan still has the recorded family take every launch."""
+    base = {k: v for k, v in os.environ.items() if not k.startswith("DMM_") and not k.startswith("DRIVE_")}
+    base.update(ASAN_OPTIONS="detect_leaks=0:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
+    args = ["d121e", "f16", "2", "64", "96"]
+
+    def counts(env):
+        r = subprocess.run([host_drive, "dump"] + args, env=env, capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, (r.stdout[-500:] + r.stderr)[-3000:]
+        recs = re.findall(r"^  op kind=\d+ .* impl=(\w+) label=(\S*)", r.stdout, re.M)
+        assert len(recs) > 500, len(recs)
+        n = {}
+        for impl, label in recs:
+            n[impl] = n.get(impl, 0) + 1
+            if label.startswith("bw1"):
+                n["bw1 label"] = n.get("bw1 label", 0) + 1
+        return n
+
+    options = {"thin_logits": "thin", "conv3": "conv3", "wg3": "wg3", "wgp": "wgp", "wg5": "wg5", "cvp": "cvp", "pig": "pig", "bw1": "bw1 label"}
+    default = counts(base)
+    for option, key in options.items():
+        assert default.get(key, 0) > 0, (option, default)
+        off = counts(dict(base, DRIVE_OPTIONS_OFF=option))
+        assert off.get(key, 0) == 0, (option, off)
+        rc, bad, picks, out = _picks(host_drive, *args, {"DRIVE_OPTIONS_OFF": option})
+        assert rc == 0 and not bad and "PICKS OK" in out and len(picks) > 20, (option, bad, out[-3000:])
+        assert all(p["recorded"] != key for p in picks), option
 
 
 def _picks(host_drive, arch, dtype, b, h, w, envx=None):

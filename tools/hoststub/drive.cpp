@@ -22,6 +22,7 @@
 //                                                  sizes, every field of every launch record, pack / unpack tables, buckets.  Pointers
 //                                                  are printed as region+offset, so the text does not depend on where anything is mapped
 //                                                  (DRIVE_MAP_SHIFT_MIB=<n> moves the workspace and the three arenas, to show that).
+// DRIVE_OPTIONS_OFF=<name>[,<name>...] (any mode): dmm_set_option(name, 0) for each, before any plan is created.
 // DRIVE_NO_MFMA=1 (any mode): the description asks for use_mfma = 0.
 // DRIVE_DYN_SCALE=1 (life-cycle run and dump): the plan gets a dynamic loss scale (dmm_plan_set_dynamic_loss_scale, pointing into a
 // guard state block the driver owns: region "guard"); the life-cycle run also takes the guarded optimiser step after every backward.
@@ -164,6 +165,17 @@ static int one_life(const dmm_model_desc& d, int life) {
   // (test of the bind-time check: a plan whose switches were tampered with after it was sized reserves other bytes -> DMM_ERR_STATE)
   if (getenv("DRIVE_FLIP_SWITCH_BETWEEN_CREATE_AND_BIND")) plan->sw.no_eff_compact = !plan->sw.no_eff_compact;
   MUST(dmm_plan_bind(plan, ws, wsb, params, grads, buffers));
+  if (getenv("DRIVE_TOGGLE_BETWEEN_CREATE_AND_BIND")) {   // the families the bound plan recorded: "FAMILIES <name>=<launch records> ..." (a fused pair counts as bw1)
+    int n[IMPL_COUNT] = {};
+    for (const auto* ops : {&plan->fwd_train, &plan->fwd_eval, &plan->bwd})
+      for (const Op& o : *ops) {
+        if (o.kind == OP_IGEMM || o.kind == OP_WGRAD) ++n[o.impl];
+        if (o.kind == OP_BW1) ++n[IMPL_BW1];
+      }
+    printf("FAMILIES");
+    for (int f = 1; f < IMPL_COUNT; ++f) printf(" %s=%d", dmm_impl_name(f), n[f]);
+    printf("\n");
+  }
   // (test of the per-launch family check: a launch whose record names a family that will not take it - here a dense 3x3 weight
   // gradient recorded as wg5, which refuses it, so the generic kernel runs - makes the backward pass return DMM_ERR_STATE)
   if (getenv("DRIVE_TAMPER_RECORDED_FAMILY"))
@@ -243,11 +255,11 @@ static bool family_agrees(int kind, int impl, const WgradArgs* w, unsigned m) {
   return impl != IMPL_AUTO && recorded_ran && (impl == IMPL_GENERIC || !generic_ran || remainder);
 }
 
-static int check_list(const std::vector<Op>& ops, int dt, bool mfma, const char* name) {
+static int check_list(const std::vector<Op>& ops, int dt, bool mfma, unsigned deny, const char* name) {
   int bad = 0, n = 0;
   const int esz = dt == DT_F32 ? 4 : 2;
   for (const Op& o : ops) {
-    if (o.kind == OP_BW1) {   // decided by bw1_eligible when the plan was built: the pair must still be eligible, and the launch must succeed
+    if (o.kind == OP_BW1) {   // decided by bw1_eligible when the plan was built: under the plan's mask the pair must still be eligible, and the launch must succeed
       WgradArgs w;
       memset(&w, 0, sizeof(w));
       const ConvArgs& c = o.b1.c;
@@ -261,9 +273,9 @@ static int check_list(const std::vector<Op>& ops, int dt, bool mfma, const char*
       const hipError_t e = launch_bw1(o.b1, dt, nullptr);
       const unsigned m = dmm_impl_mask(1);
       ++n;
-      if (e != hipSuccess || m != (1u << IMPL_BW1) || !bw1_eligible(w, c, dt)) {
+      if (e != hipSuccess || m != (1u << IMPL_BW1) || !bw1_eligible(w, c, dt, deny)) {
         ++bad;
-        printf("%s MISMATCH %-40s recorded bw1 ran mask %#x rc %d eligible %d\n", name, o.label, m, (int)e, (int)bw1_eligible(w, c, dt));
+        printf("%s MISMATCH %-40s recorded bw1 ran mask %#x rc %d eligible %d\n", name, o.label, m, (int)e, (int)bw1_eligible(w, c, dt, deny));
       }
       continue;
     }
@@ -307,7 +319,8 @@ static int picks_main(int argc, char** argv) {
   MUST(dmm_plan_bind(plan, ws, wsb, params, grads, buffers));
   printf("workspace %.1f GiB, %zu + %zu + %zu launch records\n", wsb / 1073741824.0, plan->fwd_train.size(), plan->fwd_eval.size(), plan->bwd.size());
   const bool mfma = d.use_mfma != 0;
-  const int bad = check_list(plan->fwd_train, d.dtype, mfma, "fwd") + check_list(plan->fwd_eval, d.dtype, mfma, "eval") + check_list(plan->bwd, d.dtype, mfma, "bwd");
+  const int bad = check_list(plan->fwd_train, d.dtype, mfma, plan->deny, "fwd") + check_list(plan->fwd_eval, d.dtype, mfma, plan->deny, "eval") +
+                  check_list(plan->bwd, d.dtype, mfma, plan->deny, "bwd");
   MUST(dmm_plan_destroy(plan));
   munmap(ws, wsb + 4096);
   free(params); free(grads); free(buffers);
@@ -591,6 +604,13 @@ static int refuse_main() {
 }
 
 int main(int argc, char** argv) {
+  if (const char* off = getenv("DRIVE_OPTIONS_OFF")) {   // before any plan exists, in every mode
+    const std::string s = off;
+    for (size_t b = 0, e; b <= s.size(); b = e + 1) {
+      e = std::min(s.find(',', b), s.size());
+      if (e > b) MUST(dmm_set_option(s.substr(b, e - b).c_str(), 0));
+    }
+  }
   if (argc > 1 && std::string(argv[1]) == "picks") return picks_main(argc, argv);
   if (argc > 1 && std::string(argv[1]) == "dump") return dump_main(argc, argv);
   if (argc > 1 && std::string(argv[1]) == "single") return single_main(argc, argv);
