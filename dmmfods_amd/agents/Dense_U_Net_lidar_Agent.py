@@ -5,7 +5,8 @@
 Differences, all on purpose: the step body uses the fused HIP tail (``model.loss_backward``), so loss sums, IoU and accuracy
 come back as device tensors without the per-iteration host syncs of A:252-260 / H:359-363; TensorBoard is optional (not
 installed here); ``compute_dtype`` / data parallelism are new, and so is the guarded optimiser step (``max_grad_norm``, ``loss_scaler``:
-clipping by global norm, a dynamic loss scale and a skipped step on overflow, dmmfods_amd/optim.py)."""
+clipping by global norm, a dynamic loss scale and a skipped step on overflow, dmmfods_amd/optim.py) and gradient accumulation
+(``config.optimizer.accumulate_steps``: one optimiser step per N batches, on the sum of their gradients)."""
 import logging
 import os
 import warnings
@@ -79,6 +80,14 @@ class Dense_U_Net_lidar_Agent:
             elif dyn is not None:
                 loss_scaler = DynamicLossScaler(**dict(dyn))
         self.loss_scaler = loss_scaler
+        # accumulate_steps = N > 1: one optimiser step per window of N batches, on the SUM of their gradients (the loss is a sum,
+        # A:264: the gradient of the N-fold batch, BatchNorm statistics per batch).  Absent or 1: the reference's loop.
+        acc = self._optional(o, "accumulate_steps")
+        self.accumulate_steps = 1 if acc is None else int(acc)
+        if self.accumulate_steps < 1:
+            raise ValueError("optimizer.accumulate_steps must be an integer >= 1")
+        if self.accumulate_steps > 1:
+            self.model.set_grad_accumulation(True)
         self.optimizer = FusedAdam(self.model, lr=o.learning_rate, betas=(o.beta1, o.beta2), eps=o.eps,
                                    weight_decay=o.weight_decay, amsgrad=o.amsgrad, max_grad_norm=max_grad_norm,
                                    loss_scaler=loss_scaler)
@@ -192,16 +201,25 @@ class Dense_U_Net_lidar_Agent:
         ep = {k: torch.zeros((n, nc), device=self.device) for k in ("loss", "iou", "nans", "acc")}
         guard = self.optimizer._guard   # the guarded step's state (None on the plain path); read ONCE per epoch, below
         skipped0 = guard.skipped_steps if guard is not None else 0
+        window = self.accumulate_steps
+        open_batches = 0   # batches whose gradients sit in the arena waiting for a step (always 0 here when window == 1)
         for b, (image, lidar, ht_map) in enumerate(self.data_loader.train_loader):
             image, lidar, ht_map = self._to_device(image, lidar, ht_map)
+            if window > 1 and open_batches == 0:
+                self.optimizer.zero_grad()                    # A:263 (start of a window)
             with torch.no_grad():
                 self.model(image, lidar)                      # A:244
             m = self.model.loss_backward(ht_map)              # A:247-264
-            self.optimizer.step()                             # A:265
+            open_batches += 1
+            if open_batches == window:
+                self.optimizer.step()                         # A:265
+                open_batches = 0
             iou_pc, nans, acc_pc = self._batch_metrics(m)
             ep["loss"][b], ep["iou"][b], ep["nans"][b], ep["acc"][b] = m["loss_per_class"], iou_pc, nans, acc_pc
             self._log(self.train_summary_writer, "Training", m["loss_per_class"], acc_pc, iou_pc, self.current_train_iteration)
             self.current_train_iteration += 1
+        if open_batches:   # the epoch ended inside a window: step on what it holds - nothing is carried over or dropped
+            self.optimizer.step()
         if self.lr_scheduler is not None:
             self.lr_scheduler.step()
         self.train_history.append({"epoch": self.current_epoch, "loss": ep["loss"].mean(0).cpu(), "iou": ep["iou"].mean(0).cpu(),

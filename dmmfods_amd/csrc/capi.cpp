@@ -304,6 +304,9 @@ static int run_ops(dmm_plan* p, std::vector<Op>& ops, hipStream_t st, int prof_w
       evs->push_back((void*)e);
     }
   }
+  // Gradient accumulation: the list is the one of the plain mode; the arena's memset is passed over (its record, label and
+  // profiling slot stay) and the two kinds of launch that write the arena take their accumulate form.
+  const bool accumulate = p->grad_accumulate;
   const std::string& filt = p->prof_filter;
   auto selected = [&](const Op& o) { return evs != nullptr && (filt.empty() || strncmp(o.label, filt.c_str(), filt.size()) == 0); };
   // Overlap: a weight gradient only needs what the ops before it produced, and nothing but the final unpack reads it, so
@@ -384,7 +387,7 @@ static int run_ops(dmm_plan* p, std::vector<Op>& ops, hipStream_t st, int prof_w
     const unsigned mask_before = g_impl_mask;
     if (fam_check) g_impl_mask = 0;
     switch (o.kind) {
-      case OP_MEMSET: e = hipMemsetAsync(o.ms.p, 0, o.ms.bytes, lst); break;
+      case OP_MEMSET: if (!(accumulate && o.ms.p == (void*)p->grads)) e = hipMemsetAsync(o.ms.p, 0, o.ms.bytes, lst); break;
       case OP_COPY: e = hipMemcpyAsync(o.cp.dst, o.cp.src, o.cp.bytes, hipMemcpyDeviceToDevice, lst); break;
       case OP_CONVERT: e = launch_convert_input(o.cv, dt, lst); break;
       case OP_IGEMM: e = launch_igemm(o.c, dt, o.epi, mfma, lst, o.impl); break;
@@ -395,13 +398,16 @@ static int run_ops(dmm_plan* p, std::vector<Op>& ops, hipStream_t st, int prof_w
       case OP_FIN64: e = launch_wg5_fin64(o.f64, lst); break;
       case OP_JOIN: if (o.epi == 1) join_pack(); else join_side(); break;  // the main stream waits for what the side (epi 1: pack) stream has been given so far
       case OP_BNFIN: e = launch_bn_finalize(o.bf, lst); break;
-      case OP_BNBWD: e = launch_bn_bwd_finalize(o.bb, lst); break;
+      case OP_BNBWD:
+        if (accumulate) { BnBwdFinalizeArgs bb = o.bb; bb.accumulate = 1; e = launch_bn_bwd_finalize(bb, lst); }
+        else e = launch_bn_bwd_finalize(o.bb, lst);
+        break;
       case OP_POOL: e = launch_maxpool_fwd(o.mp, dt, lst); break;
       case OP_POOLBWD: e = launch_maxpool_bwd(o.mpb, dt, lst); break;
       case OP_BCE: e = launch_bce_metrics(o.bce, dt, lst); break;
       case OP_PACK: e = launch_pack(o.pk.descs, o.pk.prefix, o.pk.ndesc, o.pk.total_rows, dt, lst, o.pk.tdescs, o.pk.tiles, o.pk.nt1, o.pk.nt9); break;
       case OP_APPLYCORR: e = launch_apply_corr(o.ac, dt, lst); break;
-      case OP_UNPACK: e = launch_unpack(o.pk.descs, o.pk.prefix, o.pk.ndesc, o.pk.total_rows, dt, o.pk.grad_scale, lst, o.pk.tdescs, o.pk.tiles, o.pk.nt1, o.pk.nt9); break;
+      case OP_UNPACK: e = launch_unpack(o.pk.descs, o.pk.prefix, o.pk.ndesc, o.pk.total_rows, dt, o.pk.grad_scale, lst, o.pk.tdescs, o.pk.tiles, o.pk.nt1, o.pk.nt9, accumulate); break;
       default: join(); return fail(DMM_ERR_STATE, "unknown op");
     }
     if (host_prof && o.kind < 32) { const double t2 = now(); hp_fork[o.kind] += hp_t1 - hp_t0; hp_launch[o.kind] += t2 - hp_t1; hp_n[o.kind]++; }
@@ -591,8 +597,9 @@ int dmm_plan_backward(dmm_plan* plan, const float* dlogits, void* stream) {
   cv.src1 = dlogits; cv.C1 = b.NC; cv.dst = b.dlogits; cv.B = b.B; cv.H = b.H; cv.W = b.W;
   cv.scale = plan->desc.loss_scale;
   cv.dyn_scale = plan->dyn_scale;
-  // everything the fused path runs in front of the loss kernel (backward accumulators AND the gradient arena: unpack adds
-  // into it for merged-tap / shared-master weights), then the external d(loss)/d(logit) instead of the loss kernel
+  // everything the fused path runs in front of the loss kernel (backward accumulators AND, unless gradients accumulate, the
+  // gradient arena: unpack adds into it for merged-tap / shared-master weights), then the external d(loss)/d(logit) instead of
+  // the loss kernel
   int rc = run_ops(plan, plan->bwd, st, -1, 0, (size_t)plan->bce_op);
   if (rc) return rc;
   HIPCHK(launch_convert_input(cv, plan->desc.dtype, st));
@@ -710,6 +717,19 @@ int dmm_plan_set_dynamic_loss_scale(dmm_plan* plan, const float* scale_dev) {
   // the loss record of a bound plan shows it at once (dmm_plan_loss_backward sets it again at every call: bind rebuilds the list).
   // bce_only (validation: no gradient) never takes it.
   if (plan->bound && plan->bce_op >= 0) plan->bwd[plan->bce_op].bce.dyn_scale = scale_dev;
+  return DMM_OK;
+}
+
+int dmm_plan_set_grad_accumulate(dmm_plan* plan, int accumulate) {
+  if (!plan) return fail(DMM_ERR_INVALID, "null plan");
+  const bool on = accumulate != 0;
+  if (on == plan->grad_accumulate) return DMM_OK;
+  plan->grad_accumulate = on;
+  // The arena's memset runs eagerly in front of the loss kernel, but the unpack and BatchNorm-finalize launches sit in the replayed
+  // segment with their form baked in: drop the captured backward graph (launch_list destroys the entries of another epoch, as it
+  // does behind dmm_set_option and dmm_plan_bind, and captures again when the list has run eagerly once more).  The forward
+  // graph writes no gradient and stays.
+  plan->graphs[1].epoch = 0;
   return DMM_OK;
 }
 

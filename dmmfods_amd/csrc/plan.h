@@ -138,6 +138,9 @@ struct dmm_plan {
   dmm::Op bce_only;     // loss + metrics without gradient
   int loss_kind = 0;          // 0 BCE, 1 focal (dmm_plan_set_loss)
   float loss_alpha[8] = {1, 1, 1, 1, 1, 1, 1, 1}, loss_gamma[8] = {2, 2, 2, 2, 2, 2, 2, 2};
+  bool grad_accumulate = false;      // backward adds into the gradient arena instead of overwriting it (dmm_plan_set_grad_accumulate): a run-time
+                                     // property of the SAME launch list - run_ops skips the arena's memset and launches the arena's writers
+                                     // (OP_UNPACK, OP_BNBWD) in their accumulate form; survives dmm_plan_bind
   const float* dyn_scale = nullptr;  // device; the dynamic loss scale the loss kernel multiplies by (dmm_plan_set_dynamic_loss_scale), null = none
   double* metrics = nullptr;  // device, inside the zero region
   size_t metrics_bytes = 0;

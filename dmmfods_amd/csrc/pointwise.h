@@ -54,6 +54,7 @@ struct BnBwdFinalizeArgs {
   double count;      // positions of the normalised tensor
   float grad_scale;  // 1 / loss_scale
   int C;
+  int accumulate;    // 0: dgamma / dbeta are stored; 1: added to what the arena holds (gradient accumulation, dmm_plan_set_grad_accumulate)
 };
 
 struct MaxpoolArgs {
@@ -210,8 +211,11 @@ hipError_t launch_guard_init(dmm_guard_state* dev, float scale, int64_t applied,
 hipError_t launch_apply_corr(const ApplyCorrArgs& a, int dtype, hipStream_t st);
 hipError_t launch_pack(const PackDesc* descs_dev, const int* prefix_dev, int ndesc, int total_rows, int dtype, hipStream_t st,
                        const PackDesc* tile_descs = nullptr, const PackTile* tiles_dev = nullptr, int nt1 = 0, int nt9 = 0);
+// accumulate: every master gradient element is ADDED to (a read-modify-write where the plain form stores; the atomic adds of merged
+// taps and shared masters are adds in both forms).  false runs the kernels and the stores of a library without the mode.
 hipError_t launch_unpack(const PackDesc* descs_dev, const int* prefix_dev, int ndesc, int total_rows, int dtype, float grad_scale,
-                         hipStream_t st, const PackDesc* tile_descs = nullptr, const PackTile* tiles_dev = nullptr, int nt1 = 0, int nt9 = 0);
+                         hipStream_t st, const PackDesc* tile_descs = nullptr, const PackTile* tiles_dev = nullptr, int nt1 = 0, int nt9 = 0,
+                         bool accumulate = false);
 
 #if defined(__HIPCC__)
 // ---- the finalize steps, per channel: bodies of bn_finalize_kernel / bn_bwd_finalize_kernel ----
@@ -258,8 +262,14 @@ __device__ __forceinline__ void bn_bwd_finalize_channel(const BnBwdFinalizeArgs&
     for (int k = 1; k < STAT_REPS; ++k) { S1 += stat_load<COH>(a.red1 + c + (size_t)k * a.stat_stride); S2 += stat_load<COH>(a.red2 + c + (size_t)k * a.stat_stride); }
   const double mu = a.mean[c], is = a.invstd[c];
   const double dotp = S2;  // sum dz * xhat, reduced in centred form by the producing kernel
-  a.dgamma[c] = (float)(dotp * a.grad_scale);
-  a.dbeta[c] = (float)(S1 * a.grad_scale);
+  const float dg = (float)(dotp * a.grad_scale), db = (float)(S1 * a.grad_scale);
+  if (a.accumulate) {   // (uniform over the launch) one fp32 add of the value the plain form stores
+    a.dgamma[c] += dg;
+    a.dbeta[c] += db;
+  } else {
+    a.dgamma[c] = dg;
+    a.dbeta[c] = db;
+  }
   if (a.qd != nullptr) {
     const double s = a.scale[c];
     const double c1 = S1 / a.count, c2 = dotp / a.count;

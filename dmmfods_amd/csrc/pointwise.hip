@@ -612,7 +612,7 @@ __global__ __launch_bounds__(256) void pack_kernel(const PackDesc* descs, const 
   *(typename TT<T>::vec*)dst = f32_to_vec<T>(out);
 }
 
-template <typename T>
+template <typename T, bool ACC>
 __global__ __launch_bounds__(256) void unpack_kernel(const PackDesc* descs, const int* row_prefix, int ndesc, int total_rows,
                                                      float grad_scale) {
   constexpr int SLOT = TT<T>::SLOT, BK = 4 * SLOT;
@@ -646,6 +646,7 @@ __global__ __launch_bounds__(256) void unpack_kernel(const PackDesc* descs, cons
       const unsigned mt = (tw >> (8 * u)) & 0xff;
       if (mt == 0xff) continue;
       if (merged || d.shared_master) atomic_add_f32(d.gw + base + (size_t)mt * d.st, v);
+      else if constexpr (ACC) d.gw[base + (size_t)mt * d.st] += v;   // the one writer of this element in the launch
       else d.gw[base + (size_t)mt * d.st] = v;
     }
   }
@@ -716,7 +717,9 @@ __global__ __launch_bounds__(256) void pack_tiles_kernel(const PackDesc* __restr
   }
 }
 
-template <int RS>
+// ACC (gradient accumulation): the tile is added to the master gradient, a read-modify-write of the addresses the plain form stores
+// to - each owned by one thread of one workgroup, so no atomics; the LDS part is the same.
+template <int RS, bool ACC>
 __global__ __launch_bounds__(256) void unpack_tiles_kernel(const PackDesc* __restrict__ descs, const PackTile* __restrict__ tiles, float grad_scale) {
   constexpr int RUN = PT_N * RS, ROW = RUN + 1;
   __shared__ float tile[PT_N * ROW];
@@ -763,16 +766,23 @@ __global__ __launch_bounds__(256) void unpack_tiles_kernel(const PackDesc* __res
       const int o = idx / (RUN / 4), j = (idx - o * (RUN / 4)) * 4;
       const float* tp = tile + o * ROW + j;
       if (o < outer_valid && j + 3 < inner_valid) {
-        const f32x4 v = {tp[0] * grad_scale, tp[1] * grad_scale, tp[2] * grad_scale, tp[3] * grad_scale};
+        f32x4 v = {tp[0] * grad_scale, tp[1] * grad_scale, tp[2] * grad_scale, tp[3] * grad_scale};
+        if constexpr (ACC) v += *(const f32x4*)(base + o * ostride + j);
         *(f32x4*)(base + o * ostride + j) = v;
       } else if (o < outer_valid) {
-        for (int q = 0; q < 4; ++q) if (j + q < inner_valid) base[o * ostride + j + q] = tp[q] * grad_scale;
+        for (int q = 0; q < 4; ++q) {
+          if (j + q >= inner_valid) continue;
+          if constexpr (ACC) base[o * ostride + j + q] += tp[q] * grad_scale;
+          else base[o * ostride + j + q] = tp[q] * grad_scale;
+        }
       }
     }
   } else {
     for (int idx = tid; idx < PT_N * RUN; idx += 256) {
       const int o = idx / RUN, j = idx - o * RUN;
-      if (o < outer_valid && j < inner_valid) base[o * ostride + j] = tile[o * ROW + j] * grad_scale;
+      if (!(o < outer_valid && j < inner_valid)) continue;
+      if constexpr (ACC) base[o * ostride + j] += tile[o * ROW + j] * grad_scale;
+      else base[o * ostride + j] = tile[o * ROW + j] * grad_scale;
     }
   }
 }
@@ -797,19 +807,26 @@ hipError_t launch_pack(const PackDesc* descs_dev, const int* prefix_dev, int nde
   return hipGetLastError();
 }
 
-hipError_t launch_unpack(const PackDesc* descs_dev, const int* prefix_dev, int ndesc, int total_rows, int dtype, float grad_scale,
-                         hipStream_t st, const PackDesc* tile_descs, const PackTile* tiles_dev, int nt1, int nt9) {
+template <bool ACC>
+static hipError_t launch_unpack_form(const PackDesc* descs_dev, const int* prefix_dev, int ndesc, int total_rows, int dtype, float grad_scale,
+                                     hipStream_t st, const PackDesc* tile_descs, const PackTile* tiles_dev, int nt1, int nt9) {
   if (dtype != DT_F32 && tiles_dev != nullptr) {
-    if (nt1 > 0) hipLaunchKernelGGL(unpack_tiles_kernel<1>, dim3(nt1), dim3(256), 0, st, tile_descs, tiles_dev, grad_scale);
-    if (nt9 > 0) hipLaunchKernelGGL(unpack_tiles_kernel<9>, dim3(nt9), dim3(256), 0, st, tile_descs, tiles_dev + nt1, grad_scale);
+    if (nt1 > 0) hipLaunchKernelGGL((unpack_tiles_kernel<1, ACC>), dim3(nt1), dim3(256), 0, st, tile_descs, tiles_dev, grad_scale);
+    if (nt9 > 0) hipLaunchKernelGGL((unpack_tiles_kernel<9, ACC>), dim3(nt9), dim3(256), 0, st, tile_descs, tiles_dev + nt1, grad_scale);
   }
   if (total_rows <= 0) return hipSuccess;
   dim3 grid((total_rows * 4 + 255) / 256), block(256);
   if (dtype != DT_F32)  // the packed gradient is fp32 for every storage type: only the chunk geometry (BK = 32) matters
-    hipLaunchKernelGGL(unpack_kernel<f16>, grid, block, 0, st, descs_dev, prefix_dev, ndesc, total_rows, grad_scale);
+    hipLaunchKernelGGL((unpack_kernel<f16, ACC>), grid, block, 0, st, descs_dev, prefix_dev, ndesc, total_rows, grad_scale);
   else
-    hipLaunchKernelGGL(unpack_kernel<float>, grid, block, 0, st, descs_dev, prefix_dev, ndesc, total_rows, grad_scale);
+    hipLaunchKernelGGL((unpack_kernel<float, ACC>), grid, block, 0, st, descs_dev, prefix_dev, ndesc, total_rows, grad_scale);
   return hipGetLastError();
+}
+
+hipError_t launch_unpack(const PackDesc* descs_dev, const int* prefix_dev, int ndesc, int total_rows, int dtype, float grad_scale,
+                         hipStream_t st, const PackDesc* tile_descs, const PackTile* tiles_dev, int nt1, int nt9, bool accumulate) {
+  return accumulate ? launch_unpack_form<true>(descs_dev, prefix_dev, ndesc, total_rows, dtype, grad_scale, st, tile_descs, tiles_dev, nt1, nt9)
+                    : launch_unpack_form<false>(descs_dev, prefix_dev, ndesc, total_rows, dtype, grad_scale, st, tile_descs, tiles_dev, nt1, nt9);
 }
 
 }  // namespace dmm

@@ -5,7 +5,8 @@ behind include/dmmfods_hip.h.  There is no CPU path: calling forward on CPU tens
 Differences that are deliberate and documented:
   * parameters are views into one flat fp32 arena (and .grad into a flat gradient arena), so Adam and the
     data-parallel all-reduce each touch one contiguous buffer;
-  * backward overwrites .grad instead of accumulating (the reference always zero_grad()s first, A:263);
+  * backward overwrites .grad instead of accumulating (the reference always zero_grad()s first, A:263) unless
+    set_grad_accumulation(True) asks for torch's contract: backward adds, FusedAdam.zero_grad() clears;
   * ``pretrained=True`` needs torchvision's ImageNet checkpoint, which cannot be fetched offline.
 """
 import ctypes as C
@@ -94,6 +95,7 @@ class _Plan:
             raise
         self.loss_key = None
         self.scaler_ptr = None   # the dynamic loss scale this plan's loss kernel reads (None: none)
+        self.accumulate = False  # the plan's backward adds into the gradient arena (dmm_plan_set_grad_accumulate)
         # gradient buckets in the order backward finishes them: (offset, count) in elements of the gradient arena
         self.grad_buckets = []
         for i in range(L.dmm_plan_num_grad_buckets(self.handle)):
@@ -250,6 +252,35 @@ class Dense_U_Net_lidar(nn.Module):
         self._last = None
         self._loss = (_lib.LOSS_BCE, None, None)
         self._loss_scaler = None
+        self._grad_accumulation = False
+
+    def _live_plans(self):
+        plans = list(self._plans.values())
+        if self._last is not None and self._last[0] not in plans:
+            plans.append(self._last[0])
+        return [p for p in plans if not p.closed]
+
+    # ------------------------------------------------------------------ gradient accumulation
+    def set_grad_accumulation(self, on=True):
+        """Gradient accumulation over micro-batches.  On: loss_backward() and the autograd path (logits.backward(gradient=...))
+        ADD into the gradient arena instead of clearing and overwriting it, as torch's backward() does; clearing is the caller's
+        job (FusedAdam.zero_grad() does it while the mode is on).  The loss is a sum over the batch (A:264), so after N micro-batches
+        the arena holds the gradient of the N-fold batch, with BatchNorm statistics per micro-batch.  Applies to every plan the
+        model holds or creates later - plans of different input sizes accumulate into the one arena - and may be set on a
+        CPU-resident model.  Off (the default): the launches and numbers of a model that never had the mode."""
+        self._grad_accumulation = bool(on)
+        for plan in self._live_plans():
+            self._apply_accumulation(plan)
+        return self
+
+    @property
+    def grad_accumulation(self):
+        return self._grad_accumulation
+
+    def _apply_accumulation(self, plan):
+        if plan.accumulate != self._grad_accumulation:
+            _lib.check(_lib.lib().dmm_plan_set_grad_accumulate(plan.handle, 1 if self._grad_accumulation else 0))
+            plan.accumulate = self._grad_accumulation
 
     # ------------------------------------------------------------------ dynamic loss scale
     def set_loss_scaler(self, scaler):
@@ -261,12 +292,8 @@ class Dense_U_Net_lidar(nn.Module):
         if scaler is not None and not hasattr(scaler, "_scale_ptr"):
             raise ValueError("set_loss_scaler() takes a DynamicLossScaler or None")
         self._loss_scaler = scaler
-        plans = list(self._plans.values())
-        if self._last is not None and self._last[0] not in plans:
-            plans.append(self._last[0])
-        for plan in plans:
-            if not plan.closed:
-                self._apply_scaler(plan)
+        for plan in self._live_plans():
+            self._apply_scaler(plan)
         return self
 
     def _apply_scaler(self, plan):
@@ -392,6 +419,7 @@ class Dense_U_Net_lidar(nn.Module):
             self._plans[key] = plan
             if self._loss_scaler is not None:
                 self._apply_scaler(plan)
+            self._apply_accumulation(plan)
         else:
             self._plans.move_to_end(key)
         return plan

@@ -5,7 +5,13 @@ state_dict()/load_state_dict() use torch.optim.Adam's layout so reference checkp
 New here (the reference trains in fp32 with a bare Adam): the GUARDED step - a dynamic loss scale (torch.amp.GradScaler's rule),
 a skipped step when the gradient arena holds an inf or a NaN, and clipping by the global gradient norm
 (torch.nn.utils.clip_grad_norm_'s formula).  ``FusedAdam(model, max_grad_norm=..., loss_scaler=DynamicLossScaler())`` turns it
-on; everything is decided on the device (include/dmmfods_hip.h, dmm_adam_step_guarded), so step() never waits for the GPU."""
+on; everything is decided on the device (include/dmmfods_hip.h, dmm_adam_step_guarded), so step() never waits for the GPU.
+
+Gradient accumulation (model.set_grad_accumulation(True)): zero_grad() clears the arena at the start of a window, every backward
+of the window adds into it, step() closes it.  Neither step changes.  The guarded step reduces over the arena as stored, and the
+dynamic scale S changes only inside step(), so it is constant over a window: the arena holds S x sum_i g_i, the norm that is
+clipped is that of the summed gradient, and one non-finite micro-batch leaves an inf / NaN in the sum - the WHOLE window's step is
+then skipped and S backs off once."""
 import ctypes as C
 import math
 
@@ -215,7 +221,11 @@ class FusedAdam:
         return None if self._guard is None else self._guard.loss_scale
 
     def zero_grad(self, set_to_none=False):
-        """The HIP backward overwrites the gradient arena, so there is nothing to clear (kept for API parity)."""
+        """By default the HIP backward overwrites the gradient arena, so there is nothing to clear (kept for API parity).  While
+        the model accumulates gradients (set_grad_accumulation(True)) the arena is zeroed, in stream order on the current stream
+        and without waiting for the device; ``set_to_none`` is ignored (.grad are views of the arena)."""
+        if getattr(self.model, "grad_accumulation", False):
+            self.model.grad_arena.zero_()
 
     @torch.no_grad()
     def step(self, grad_scale=1.0):

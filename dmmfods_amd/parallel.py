@@ -47,7 +47,11 @@ class GradAllReduce:
 
     def reduce_overlapped(self):
         """Call right after model.loss_backward(): enqueues one all-reduce per plan bucket, each behind that bucket's
-        readiness event, and returns the work handles; `wait(works)` orders the current stream (Adam) behind them."""
+        readiness event, and returns the work handles; `wait(works)` orders the current stream (Adam) behind them.
+
+        With gradient accumulation (model.set_grad_accumulation(True)) call it in the LAST micro-step of a window only: the arena
+        then holds the window's local sum, which is what the ranks exchange.  The earlier micro-steps simply do not call it - torch's
+        ``no_sync``."""
         if not self._active():
             return []
         model = self._src

@@ -115,7 +115,8 @@ int dmm_plan_forward(dmm_plan* plan, const float* stream_1, const float* stream_
                      void* stream);
 
 /* After a training-mode forward: per-pixel BCE against target (B,num_classes,H,W fp32), metric counts, and the
- * backward pass of the SUM of all loss elements.  Gradients land in the bound grad arena (fully overwritten).
+ * backward pass of the SUM of all loss elements.  Gradients land in the bound grad arena: it is cleared first and every element
+ * written (the default), or, with dmm_plan_set_grad_accumulate on, added to what the arena holds.
  * metrics_out (device, doubles): [NC loss sums | NC equal-counts | B x (NC intersections, NC unions)]. */
 int dmm_plan_loss_backward(dmm_plan* plan, const float* logits, const float* target, double* metrics_out, void* stream);
 
@@ -134,6 +135,16 @@ int dmm_loss_forward(int kind, int from_prob, const float* alpha, const float* g
 /* Backward from an externally computed d(loss)/d(logit) (B,num_classes,H,W fp32), e.g. from torch autograd of any
  * loss on the returned logits (reference: loss.backward(...), agents/Dense_U_Net_lidar_Agent.py:264). */
 int dmm_plan_backward(dmm_plan* plan, const float* dlogits, void* stream);
+
+/* Gradient accumulation over micro-batches (torch's backward() contract; the reference always clears first,
+ * agents/Dense_U_Net_lidar_Agent.py:263).  accumulate != 0: dmm_plan_loss_backward and dmm_plan_backward no longer clear the
+ * gradient arena, and every launch that writes it (the weight-gradient unpack, the BatchNorm-backward finalize) adds to it; clearing
+ * the arena between windows is the caller's job (one memset of num_params floats).  The loss is a sum, so the arena then holds the
+ * gradient of the concatenated batch, with BatchNorm statistics per micro-batch.  0 (the default): the launches and the numbers of a
+ * plan that never had the mode.  The launch list, its labels, gradient buckets and events are the same in both modes.  Changing
+ * the mode drops the plan's captured backward graph (it is captured again, see dmm_plan_num_graph_replays); the setting survives
+ * dmm_plan_bind.  Several plans bound to one arena (different input sizes) accumulate into it together when each has the mode on. */
+int dmm_plan_set_grad_accumulate(dmm_plan* plan, int accumulate);
 
 /* Data-parallel training (new here; the reference's torch.distributed import, graphs/models/Dense_U_Net_lidar.py:7, is unused):
  * the gradient arena is cut into buckets of whole tensors (about dmm_set_option("grad_bucket_mb", 25) each, set before

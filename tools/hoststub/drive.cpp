@@ -22,6 +22,12 @@
 //                                                  sizes, every field of every launch record, pack / unpack tables, buckets.  Pointers
 //                                                  are printed as region+offset, so the text does not depend on where anything is mapped
 //                                                  (DRIVE_MAP_SHIFT_MIB=<n> moves the workspace and the three arenas, to show that).
+// And one drives gradient accumulation (dmm_plan_set_grad_accumulate) on one plan:
+//   drive accum <arch> <dtype> <batch> <H> <W>     create -> mode on (unbound) -> bind -> two training passes without a clear in between
+//                                                  -> mode off -> one more pass -> mode on -> external-gradient backward -> destroy.
+//                                                  Kernels do not run here but the runtime's memsets do: the gradient arena, filled with
+//                                                  a pattern, must keep it while the mode is on and read as zero behind a pass with it off;
+//                                                  both modes make the same launches from the same records.
 // DRIVE_OPTIONS_OFF=<name>[,<name>...] (any mode): dmm_set_option(name, 0) for each, before any plan is created.
 // DRIVE_NO_MFMA=1 (any mode): the description asks for use_mfma = 0.
 // DRIVE_DYN_SCALE=1 (life-cycle run and dump): the plan gets a dynamic loss scale (dmm_plan_set_dynamic_loss_scale, pointing into a
@@ -237,6 +243,75 @@ static int one_life(const dmm_model_desc& d, int life) {
   return 0;
 }
 
+// ---- accum: one plan, gradient accumulation on and off ----
+static int accum_main(int argc, char** argv) {
+  if (argc < 7) return 64;
+  dmm_model_desc d;
+  if (!fill_desc(argv[2], d)) { fprintf(stderr, "unknown arch %s\n", argv[2]); return 64; }
+  const std::string dt = argv[3];
+  d.dtype = dt == "f32" ? DMM_F32 : (dt == "f16" ? DMM_F16 : DMM_BF16);
+  d.batch = atoi(argv[4]); d.height = atoi(argv[5]); d.width = atoi(argv[6]);
+  if (dmm_plan_set_grad_accumulate(nullptr, 1) != DMM_ERR_INVALID) { fprintf(stderr, "[drive] a null plan was not refused\n"); return 2; }
+  dmm_plan* plan = nullptr;
+  MUST(dmm_plan_create(&d, &plan));
+  MUST(dmm_plan_set_grad_accumulate(plan, 1));   // on an unbound plan: must survive bind
+  const size_t wsb = dmm_plan_workspace_bytes(plan);
+  const int64_t np = dmm_plan_num_params(plan), nb = std::max<int64_t>(dmm_plan_num_buffer_elems(plan), 1);
+  uint8_t* ws = (uint8_t*)aligned_alloc(256, (wsb + 255) / 256 * 256);
+  float* params = (float*)malloc(np * 4); float* grads = (float*)malloc(np * 4); float* buffers = (float*)malloc(nb * 4);
+  const size_t px = (size_t)d.batch * d.height * d.width;
+  float* in1 = (float*)malloc(px * std::max(1, d.stream_1_in_channels) * 4);
+  float* in2 = (float*)malloc(px * std::max(1, d.stream_2_in_channels) * 4);
+  float* logits = (float*)malloc(px * d.num_classes * 4);
+  float* target = (float*)malloc(px * d.num_classes * 4);
+  double* metrics = (double*)malloc((2 * d.num_classes + (size_t)d.batch * 2 * d.num_classes) * 8);
+  g_regions = {{ws, ws + wsb, "workspace"}, {(uint8_t*)params, (uint8_t*)(params + np), "params"}, {(uint8_t*)grads, (uint8_t*)(grads + np), "grads"},
+               {(uint8_t*)buffers, (uint8_t*)(buffers + nb), "buffers"}, {(uint8_t*)in1, (uint8_t*)in1 + px * 3 * 4, "in1"},
+               {(uint8_t*)in2, (uint8_t*)in2 + px * 3 * 4, "in2"}, {(uint8_t*)logits, (uint8_t*)logits + px * d.num_classes * 4, "logits"},
+               {(uint8_t*)target, (uint8_t*)target + px * d.num_classes * 4, "target"}};
+  MUST(dmm_plan_bind(plan, ws, wsb, params, grads, buffers));
+  if (!plan->grad_accumulate) { fprintf(stderr, "[drive] the mode did not survive dmm_plan_bind\n"); return 2; }
+  const int nops_on = dmm_plan_profile_num_ops(plan, 1);
+  void* st = nullptr;
+  float* s2 = d.stream_2_in_channels ? in2 : nullptr;
+  auto arena_is = [&](unsigned char byte) {
+    const unsigned char* g = (const unsigned char*)grads;
+    for (size_t i = 0; i < (size_t)np * 4; ++i) if (g[i] != byte) return false;
+    return true;
+  };
+  int bad = 0;
+  auto expect = [&](bool ok, const char* what) { printf("ACCUM %s %s\n", what, ok ? "ok" : "WRONG"); bad += !ok; };
+  memset(grads, 0x5a, (size_t)np * 4);
+  long l0 = fakehip_launches();
+  for (int rep = 0; rep < 2; ++rep) {   // one window: two micro-batches, nothing cleared in between
+    MUST(dmm_plan_forward(plan, in1, s2, logits, 1, st));
+    MUST(dmm_plan_loss_backward(plan, logits, target, metrics, st));
+  }
+  const long launches_on = (fakehip_launches() - l0) / 2;
+  expect(arena_is(0x5a), "mode on: the arena is not cleared");
+  chk_ops(plan->bwd); chk_descs(plan);
+  MUST(dmm_plan_set_grad_accumulate(plan, 0));
+  expect(dmm_plan_profile_num_ops(plan, 1) == nops_on && nops_on > 0, "same launch records in both modes");
+  l0 = fakehip_launches();
+  MUST(dmm_plan_forward(plan, in1, s2, logits, 1, st));
+  MUST(dmm_plan_loss_backward(plan, logits, target, metrics, st));
+  expect(fakehip_launches() - l0 == launches_on, "same launches in both modes");
+  expect(arena_is(0), "mode off: the arena is cleared");
+  for (const Op& o : plan->bwd) if (o.kind == OP_BNBWD && o.bb.accumulate) { expect(false, "a launch record was rewritten"); break; }
+  MUST(dmm_plan_set_grad_accumulate(plan, 1));
+  memset(grads, 0x5a, (size_t)np * 4);
+  MUST(dmm_plan_forward(plan, in1, s2, logits, 1, st));
+  MUST(dmm_plan_backward(plan, target /*stands for d(loss)/d(logit)*/, st));
+  expect(arena_is(0x5a), "mode on, external gradient: the arena is not cleared");
+  MUST(dmm_plan_destroy(plan));
+  free(ws); free(params); free(grads); free(buffers); free(in1); free(in2); free(logits); free(target); free(metrics);
+  if (g_bad) { fprintf(stderr, "[drive] FAIL: %ld device pointers outside the caller's regions\n", g_bad); bad++; }
+  if (fakehip_violations()) { fprintf(stderr, "[drive] FAIL: %ld teardown / handle violations\n", fakehip_violations()); bad++; }
+  printf("accum: %d launch records, %ld launches per pass, %ld pointers checked\n", nops_on, launches_on, g_checked);
+  printf("%s\n", bad ? "ACCUM FAILED" : "ACCUM OK");
+  return bad ? 1 : 0;
+}
+
 // Address space without memory behind it: reserved, never committed; PROT_NONE where nothing at all may touch it.
 static void* reserve(size_t bytes, int prot) {
   void* p = mmap(nullptr, bytes + 4096, prot, MAP_PRIVATE | MAP_ANONYMOUS | MAP_NORESERVE, -1, 0);
@@ -403,7 +478,7 @@ struct Dumper {
       case OP_BNFIN: { const BnFinalizeArgs& a = o.bf; printf("    bnfin:"); DP(sum); DP(sq); DI(stat_stride); DD(count); DD(count_unbiased); DP(gamma); DP(beta);
                        DP(running_mean); DP(running_var); DP(scale); DP(shift); DP(mean); DP(invstd); DI(C); DI(training); DD(momentum); DD(eps); printf("\n"); break; }
       case OP_BNBWD: { const BnBwdFinalizeArgs& a = o.bb; printf("    bnbwd:"); DP(red1); DP(red2); DI(stat_stride); DP(mean); DP(invstd); DP(scale); DP(dgamma);
-                       DP(dbeta); DP(qd); DP(rd); DP(q); DP(r); DP(ql); DP(rl); DD(count); DD(grad_scale); DI(C); printf("\n"); break; }
+                       DP(dbeta); DP(qd); DP(rd); DP(q); DP(r); DP(ql); DP(rl); DD(count); DD(grad_scale); DI(C); DI(accumulate); printf("\n"); break; }
       case OP_POOL: { const MaxpoolArgs& a = o.mp; printf("    pool:"); DP(y0); DI(ld0); DI(H0); DI(W0); DI(B); DI(C); DP(scale); DP(shift); DP(out); DI(ldo); DI(Hp);
                       DI(Wp); DP(argmax); DP(stat_sum); DP(stat_sq); DI(stat_stride); printf("\n"); break; }
       case OP_POOLBWD: { const MaxpoolBwdArgs& a = o.mpb; printf("    poolbwd:"); DP(y0); DI(ld0); DI(H0); DI(W0); DI(B); DI(C); DP(scale); DP(shift); DP(gpool);
@@ -615,6 +690,7 @@ int main(int argc, char** argv) {
   if (argc > 1 && std::string(argv[1]) == "dump") return dump_main(argc, argv);
   if (argc > 1 && std::string(argv[1]) == "single") return single_main(argc, argv);
   if (argc > 1 && std::string(argv[1]) == "refuse") return refuse_main();
+  if (argc > 1 && std::string(argv[1]) == "accum") return accum_main(argc, argv);
   if (argc < 6) { fprintf(stderr, "usage: drive <arch> <dtype> <batch> <H> <W> [lives]\n"); return 64; }
   dmm_model_desc d;
   if (!fill_desc(argv[1], d)) { fprintf(stderr, "unknown arch %s\n", argv[1]); return 64; }
