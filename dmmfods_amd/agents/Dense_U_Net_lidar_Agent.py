@@ -6,7 +6,8 @@ Differences, all on purpose: the step body uses the fused HIP tail (``model.loss
 come back as device tensors without the per-iteration host syncs of A:252-260 / H:359-363; TensorBoard is optional (not
 installed here); ``compute_dtype`` / data parallelism are new, and so is the guarded optimiser step (``max_grad_norm``, ``loss_scaler``:
 clipping by global norm, a dynamic loss scale and a skipped step on overflow, dmmfods_amd/optim.py) and gradient accumulation
-(``config.optimizer.accumulate_steps``: one optimiser step per N batches, on the sum of their gradients)."""
+(``config.optimizer.accumulate_steps``: one optimiser step per N batches, on the sum of their gradients) and a frozen-encoder
+phase (``config.optimizer.freeze_encoder_epochs``: decoder and head train alone for the first N epochs)."""
 import logging
 import os
 import warnings
@@ -88,6 +89,14 @@ class Dense_U_Net_lidar_Agent:
             raise ValueError("optimizer.accumulate_steps must be an integer >= 1")
         if self.accumulate_steps > 1:
             self.model.set_grad_accumulation(True)
+        # freeze_encoder_epochs = N > 0: the encoder (features, stream_2_features, concat_module) is frozen for the epochs < N and released
+        # at the start of epoch N (the usual schedule on a pretrained encoder).  Absent or 0: the reference's loop.
+        fe = self._optional(o, "freeze_encoder_epochs")
+        self.freeze_encoder_epochs = 0 if fe is None else int(fe)
+        if self.freeze_encoder_epochs < 0:
+            raise ValueError("optimizer.freeze_encoder_epochs must be an integer >= 0")
+        self.current_epoch = 0
+        self._apply_freeze_phase()   # before the optimiser is built: a frozen parameter starts without optimiser state
         self.optimizer = FusedAdam(self.model, lr=o.learning_rate, betas=(o.beta1, o.beta2), eps=o.eps,
                                    weight_decay=o.weight_decay, amsgrad=o.amsgrad, max_grad_norm=max_grad_norm,
                                    loss_scaler=loss_scaler)
@@ -109,6 +118,13 @@ class Dense_U_Net_lidar_Agent:
         Path(self.config.dir.current_run.summary).mkdir(exist_ok=True, parents=True)
         mk = (lambda: SummaryWriter(log_dir=self.config.dir.current_run.summary, comment="Dense_U_Net")) if SummaryWriter else _NullWriter
         self.train_summary_writer, self.val_summary_writer = mk(), mk()
+
+    def _apply_freeze_phase(self):
+        """The phase current_epoch is in (only with freeze_encoder_epochs: otherwise the model's flags are left alone)."""
+        if self.freeze_encoder_epochs > 0:
+            want = self.current_epoch < self.freeze_encoder_epochs
+            if self.model.encoder_frozen != want:
+                self.model.freeze_encoder(want)
 
     @staticmethod
     def _optional(section, name):
@@ -143,6 +159,7 @@ class Dense_U_Net_lidar_Agent:
         self.current_val_iteration = ck[k.val_iteration]
         self.best_val_iou = ck[k.best_val_iou]
         self.model.load_state_dict(ck[k.state_dict])
+        self._apply_freeze_phase()   # the phase of the checkpoint's epoch, before the optimiser derives its step origins from the flags
         self.optimizer.load_state_dict(ck[k.optimizer])
 
     # ------------------------------------------------------------------ driver (A:165-213)
@@ -195,6 +212,7 @@ class Dense_U_Net_lidar_Agent:
             writer.add_scalars(f"{tag}/{name}", d, it)
 
     def train_one_epoch(self):
+        self._apply_freeze_phase()
         self.model.train()
         n = self.data_loader.train_iterations
         nc = self.config.model.num_classes

@@ -18,6 +18,7 @@ using namespace dmm;
 
 void plan_build_tables(dmm_plan* p);
 void plan_bind(dmm_plan* p, void* ws);
+void plan_size(dmm_plan* p);
 
 static thread_local std::string g_err;
 static int fail(int code, const std::string& msg) {
@@ -733,6 +734,24 @@ int dmm_plan_set_grad_accumulate(dmm_plan* plan, int accumulate) {
   return DMM_OK;
 }
 
+int dmm_plan_set_encoder_frozen(dmm_plan* plan, int frozen) {
+  if (!plan) return fail(DMM_ERR_INVALID, "null plan");
+  if (plan->bound) return fail(DMM_ERR_STATE, "dmm_plan_set_encoder_frozen: the plan is bound (set the mode between dmm_plan_create and dmm_plan_bind)");
+  const bool on = frozen != 0;
+  if (on == plan->encoder_frozen) return DMM_OK;
+  // the sizes, buckets and tables must be those of the mode: dmm_plan_bind compares the bytes of its pass with the sized ones exactly
+  plan->encoder_frozen = on;
+  plan->deny = plan_deny(plan);
+  try {
+    plan_size(plan);
+  } catch (const std::exception& e) {
+    plan->encoder_frozen = !on;
+    try { plan_size(plan); } catch (...) {}
+    return fail(DMM_ERR_INVALID, e.what());
+  }
+  return DMM_OK;
+}
+
 size_t dmm_grad_guard_scratch_bytes(int64_t n) {
   (void)n;  // one partial per workgroup of a fixed grid, whatever the arena's size
   return (size_t)GUARD_PARTIALS * sizeof(double);
@@ -782,6 +801,50 @@ int dmm_adam_step_guarded(float* params, const float* grads, float* exp_avg, flo
   a.beta1 = beta1; a.beta2 = beta2; a.eps = eps; a.weight_decay = weight_decay;
   a.step_size = 0.f; a.bc2_sqrt = 1.f; a.grad_scale = 0.f;   // read from *state by the kernel
   HIPCHK(launch_adam_guarded(a, state, st));
+  return DMM_OK;
+}
+
+int dmm_adam_step_guarded_ranges(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, const int64_t* offsets,
+                                 const int64_t* counts, const int64_t* t0, int nranges, float lr, float beta1, float beta2, float eps,
+                                 float weight_decay, float max_norm, float growth_factor, float backoff_factor, int32_t growth_interval,
+                                 dmm_guard_state* state, void* scratch, void* stream) {
+  // every refusal comes before the first HIP call
+  if (!params || !grads || !exp_avg || !exp_avg_sq || !offsets || !counts || !t0 || !state || !scratch)
+    return fail(DMM_ERR_INVALID, "null argument of the guarded Adam step over ranges");
+  if (nranges < 1) return fail(DMM_ERR_INVALID, "nranges must be >= 1");
+  if ((((uintptr_t)grads) & 3) != 0 || (((uintptr_t)state) & 7) != 0 || (((uintptr_t)scratch) & 7) != 0)
+    return fail(DMM_ERR_INVALID, "misaligned gradient, state or scratch pointer");
+  for (int i = 0; i < nranges; ++i) {
+    if (offsets[i] < 0 || counts[i] < 0) return fail(DMM_ERR_INVALID, "range " + std::to_string(i) + ": offset and count must be >= 0");
+    if (t0[i] < 0) return fail(DMM_ERR_INVALID, "range " + std::to_string(i) + ": t0 must be >= 0");
+    if (offsets[i] > INT64_MAX - counts[i]) return fail(DMM_ERR_INVALID, "range " + std::to_string(i) + ": offset + count overflows");
+    for (int k = 0; k < i; ++k)
+      if (offsets[i] < offsets[k] + counts[k] && offsets[k] < offsets[i] + counts[i])
+        return fail(DMM_ERR_INVALID, "ranges " + std::to_string(k) + " and " + std::to_string(i) + " overlap");
+  }
+  if (!(growth_factor >= 1.f) || !std::isfinite(growth_factor)) return fail(DMM_ERR_INVALID, "growth_factor must be a finite number >= 1");
+  if (!(backoff_factor > 0.f) || !(backoff_factor <= 1.f)) return fail(DMM_ERR_INVALID, "backoff_factor must lie in (0, 1]");
+  if (growth_interval < 0) return fail(DMM_ERR_INVALID, "growth_interval must be >= 0");
+  if (std::isnan(max_norm)) return fail(DMM_ERR_INVALID, "max_norm is NaN");
+  if (!(beta1 >= 0.f && beta1 < 1.f) || !(beta2 >= 0.f && beta2 < 1.f)) return fail(DMM_ERR_INVALID, "betas must lie in [0, 1)");
+  hipStream_t st = (hipStream_t)stream;
+  for (int i = 0; i < nranges; ++i) {   // the norm over the trainable ranges only: the first assigns the partials, the rest add
+    GradSumsqArgs r;
+    r.g = grads + offsets[i]; r.n = (size_t)counts[i]; r.partials = (double*)scratch; r.accumulate = i > 0 ? 1 : 0;
+    HIPCHK(launch_grad_sumsq(r, st));
+  }
+  GuardFinalizeArgs f;
+  f.partials = (const double*)scratch; f.state = state; f.lr = lr; f.beta1 = beta1; f.beta2 = beta2; f.max_norm = max_norm;
+  f.growth_factor = growth_factor; f.backoff_factor = backoff_factor; f.growth_interval = growth_interval;
+  HIPCHK(launch_guard_finalize(f, st));
+  for (int i = 0; i < nranges; ++i) {
+    AdamArgs a;
+    a.p = params + offsets[i]; a.g = grads + offsets[i]; a.m = exp_avg + offsets[i]; a.v = exp_avg_sq + offsets[i]; a.n = (size_t)counts[i];
+    a.beta1 = beta1; a.beta2 = beta2; a.eps = eps; a.weight_decay = weight_decay;
+    a.step_size = 0.f; a.bc2_sqrt = 1.f; a.grad_scale = 0.f;   // read from *state (t0 = 0) or formed from it (t0 > 0) by the kernel
+    if (t0[i] == 0) HIPCHK(launch_adam_guarded(a, state, st));
+    else HIPCHK(launch_adam_guarded_from(a, state, lr, t0[i], st));
+  }
   return DMM_OK;
 }
 

@@ -4,6 +4,7 @@
 //   grad_sumsq     : one streaming pass over (a range of) the gradient arena -> one fp64 partial sum of squares per workgroup
 //   guard_finalize : partials (fixed order) -> apply / skip, clip coefficient, Adam bias corrections of the APPLIED step, next scale
 //   adam_guarded   : adam_kernel's arithmetic with its scalars read from the state block; writes nothing on a skipped step
+//   adam_guarded_from : the same for a range whose own step count started late (dmm_adam_step_guarded_ranges, t0 > 0)
 //   guard_init     : fills a state block (start of training, checkpoint load)
 // No floating-point atomics anywhere: a workgroup owns its partial, the finalize kernel adds the partials in a fixed tree, so the
 // norm, the decision and the step are bit-reproducible from run to run (and equal on every rank of a data-parallel job, which reads
@@ -135,6 +136,40 @@ hipError_t launch_adam_guarded(const AdamArgs& a, const dmm_guard_state* state, 
   if (grid > 4096) grid = 4096;
   if (grid < 1) grid = 1;
   hipLaunchKernelGGL(adam_guarded_kernel, dim3(grid), dim3(256), 0, st, a, state);
+  return hipGetLastError();
+}
+
+// adam_guarded_kernel for a range of the arena that became trainable at applied step t0 > 0 (an encoder released after the decoder
+// has trained): torch counts steps per parameter, so the range is at step t - t0 with t = applied_steps, which guard_finalize has
+// already advanced for this step.  step_size and bc2_sqrt are formed here, in double, by guard_finalize's expressions (every thread
+// computes the same two numbers: a few hundred cycles against a streaming pass); grad_scale is the step's own, and the element
+// arithmetic is adam_guarded_kernel's.  A skipped step, or a count that is not positive (a state block set back behind t0), writes nothing.
+__global__ __launch_bounds__(256) void adam_guarded_from_kernel(AdamArgs a, const dmm_guard_state* state, float lr, long long t0) {
+  if (state->found_inf) return;
+  const long long t = (long long)state->applied_steps - t0;
+  if (t < 1) return;
+  const double bc1 = 1.0 - pow((double)a.beta1, (double)t), bc2 = 1.0 - pow((double)a.beta2, (double)t);
+  a.grad_scale = state->grad_scale;
+  a.step_size = (float)((double)lr / bc1);
+  a.bc2_sqrt = (float)sqrt(bc2);
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < a.n; i += (size_t)gridDim.x * blockDim.x) {
+    float g = a.g[i] * a.grad_scale;
+    float p = a.p[i];
+    if (a.weight_decay != 0.f) g = fmaf(a.weight_decay, p, g);
+    const float m = a.beta1 * a.m[i] + (1.f - a.beta1) * g;
+    const float v = a.beta2 * a.v[i] + (1.f - a.beta2) * g * g;
+    a.m[i] = m;
+    a.v[i] = v;
+    const float denom = sqrtf(v) / a.bc2_sqrt + a.eps;
+    a.p[i] = p - a.step_size * (m / denom);
+  }
+}
+
+hipError_t launch_adam_guarded_from(const AdamArgs& a, const dmm_guard_state* state, float lr, int64_t t0, hipStream_t st) {
+  int grid = (int)((a.n + 255) / 256);
+  if (grid > 4096) grid = 4096;
+  if (grid < 1) grid = 1;
+  hipLaunchKernelGGL(adam_guarded_from_kernel, dim3(grid), dim3(256), 0, st, a, state, lr, (long long)t0);
   return hipGetLastError();
 }
 

@@ -382,6 +382,20 @@ struct Builder {
   // prologue: 1 the decoder's conv_reduce outputs, 2 the last ConvTranspose's output, 4 refine0's output (A/B knob)
   const int matz_mask = lab_int("DMM_MATZ_MASK", 7);
   const bool pad_pitch = lab_flag("DMM_PITCH_PAD");  // measured: no effect on MI355X for this access pattern; off
+  // ---- frozen encoder (dmm_plan_set_encoder_frozen): the arena ranges of the tensors that are not trained, merged, in arena order ----
+  const bool frozen = P.encoder_frozen;
+  std::vector<std::pair<int64_t, int64_t>> frozen_ranges;  // [first, second) elements of the parameter / gradient arena
+
+  // "Encoder": everything under these three top-level modules (whichever the network has).
+  static bool is_encoder_name(const std::string& n) {
+    return n.rfind("features.", 0) == 0 || n.rfind("stream_2_features.", 0) == 0 || n.rfind("concat_module.", 0) == 0;
+  }
+  bool frozen_off(int64_t off) const {
+    for (auto& r : frozen_ranges)
+      if (off >= r.first && off < r.second) return true;
+    return false;
+  }
+  bool is_encoder_rec(const Rec& r) const { return r.type != 0 /* the stem's pool */ || is_encoder_name(convs[r.idx].wname); }
 
   Builder(dmm_plan& p, bool sizing_, uint8_t* ws)
       : P(p), d(p.desc), g(p.desc), dtype(p.desc.dtype), esz((int)dtype_size(p.desc.dtype)), SLOT(16 / esz), BK(4 * (16 / esz)),
@@ -400,6 +414,14 @@ struct Builder {
     Pg = sizing ? (float*)fake(4) : p.grads;
     Pb = sizing ? (float*)fake(5) : p.buffers;
     for (auto& t : P.tensors) tmap[t.name] = &t;
+    if (frozen)
+      for (auto& t : P.tensors) {
+        if (t.kind > DMM_T_BN_BIAS || !is_encoder_name(t.name)) continue;
+        int64_t n = 1;
+        for (int k = 0; k < t.ndim; ++k) n *= t.shape[k];
+        if (!frozen_ranges.empty() && frozen_ranges.back().second == t.off) frozen_ranges.back().second += n;
+        else frozen_ranges.push_back({t.off, t.off + n});
+      }
   }
 
   template <typename U> U* zptr(size_t n) { return (U*)((uintptr_t)zbase + Z.take(n * sizeof(U))); }
@@ -1536,6 +1558,7 @@ struct Builder {
     auto close = [&]() { if (cur.n > 0) { brecs.push_back(cur); cur = BucketRec(); } };
     for (auto& t : P.tensors) {
       if (t.kind > DMM_T_BN_BIAS) continue;
+      if (frozen && is_encoder_name(t.name)) { close(); continue; }   // not trained: in no bucket (a bucket stays one contiguous slice)
       int64_t n = 1;
       for (int k = 0; k < t.ndim; ++k) n *= t.shape[k];
       const size_t d1 = t.name.find('.');
@@ -1551,8 +1574,9 @@ struct Builder {
       if (target > 0 && cur.n >= target) close();
     }
     if (cur.n > 0) brecs.push_back(cur);
-    for (auto& c : convs) brecs[bucket_of(T(c.wname).off)].convs_left++;
-    for (auto& b : bns) brecs[bucket_of(b.dgamma - Pg)].bns_left++;
+    // (frozen encoder: only what backward still produces is counted - conv_grad_done / bn_grad_done are never called for the rest)
+    for (auto& c : convs) if (!frozen_off(T(c.wname).off)) brecs[bucket_of(T(c.wname).off)].convs_left++;
+    for (auto& b : bns) if (!frozen_off(b.dgamma - Pg)) brecs[bucket_of(b.dgamma - Pg)].bns_left++;
     // unpack tables: the descriptors that scatter into a master gradient, grouped by bucket
     P.unpacks.clear(); P.unpack_prefix.clear(); P.unpack_tiles.clear();
     for (size_t bi = 0; bi < brecs.size(); ++bi) {
@@ -1560,7 +1584,7 @@ struct Builder {
       bk.first_desc = (int)P.unpacks.size();
       bk.rows = 0;
       for (auto& pd : P.packs) {
-        if (pd.gw == nullptr || pd.dpack == nullptr || bucket_of(pd.gw - Pg) != (int)bi) continue;
+        if (pd.gw == nullptr || pd.dpack == nullptr || frozen_off(pd.gw - Pg) || bucket_of(pd.gw - Pg) != (int)bi) continue;
         P.unpacks.push_back(pd);
       }
       bk.ndesc = (int)P.unpacks.size() - bk.first_desc;
@@ -1705,6 +1729,14 @@ struct Builder {
     }
     for (auto& b : bufs) { b.ginit = false; b.materialized = false; b.mat_front = 0; }
     for (int i = (int)recs.size() - 1; i >= 0; --i) {
+      if (frozen && is_encoder_rec(recs[i])) {
+        // Frozen encoder: the list ends here.  Records are walked from the head back, so everything in front of this one must be
+        // the encoder's (both streams' and the concat module's); no launch of the list then writes an encoder range of the
+        // gradient arena, which the whole-arena memset above leaves zero.
+        for (int k = i; k >= 0; --k)
+          if (!is_encoder_rec(recs[k])) throw std::runtime_error("frozen encoder: a decoder / head record stands in front of an encoder record");
+        break;
+      }
       if (recs[i].type == 0) emit_conv_bwd(convs[recs[i].idx]); else emit_pool_bwd(pools[recs[i].idx]);
     }
     finish_buckets();
@@ -1735,8 +1767,10 @@ PlanSwitches PlanSwitches::from_environment() {
   return s;
 }
 
-void plan_build_tables(dmm_plan* p) {
-  build_tensor_table(p->desc, p->tensors, p->nparams, p->nbuf);
+// The sizing pass: the three workspace region sizes, the buckets and the tables of the plan's mode (dmm_plan_create; again from
+// dmm_plan_set_encoder_frozen, on an unbound plan).
+void plan_size(dmm_plan* p) {
+  p->packs.clear();
   Builder b(*p, true, nullptr);
   b.build();
   b.emit_all();
@@ -1745,6 +1779,11 @@ void plan_build_tables(dmm_plan* p) {
   p->main_bytes = (b.W.off + 255) / 256 * 256;
   p->fwd_flops = b.flops;
   p->packs.clear();
+}
+
+void plan_build_tables(dmm_plan* p) {
+  build_tensor_table(p->desc, p->tensors, p->nparams, p->nbuf);
+  plan_size(p);
 }
 
 void plan_bind(dmm_plan* p, void* ws) {

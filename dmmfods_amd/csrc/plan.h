@@ -141,6 +141,9 @@ struct dmm_plan {
   bool grad_accumulate = false;      // backward adds into the gradient arena instead of overwriting it (dmm_plan_set_grad_accumulate): a run-time
                                      // property of the SAME launch list - run_ops skips the arena's memset and launches the arena's writers
                                      // (OP_UNPACK, OP_BNBWD) in their accumulate form; survives dmm_plan_bind
+  bool encoder_frozen = false;       // the encoder (features, stream_2_features, concat_module) is not trained (dmm_plan_set_encoder_frozen): the
+                                     // backward list ends in front of the first encoder record, buckets and unpack tables hold trainable tensors
+                                     // only.  Set on an unbound plan (the sizing pass runs again); survives dmm_plan_bind
   const float* dyn_scale = nullptr;  // device; the dynamic loss scale the loss kernel multiplies by (dmm_plan_set_dynamic_loss_scale), null = none
   double* metrics = nullptr;  // device, inside the zero region
   size_t metrics_bytes = 0;

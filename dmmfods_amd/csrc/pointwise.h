@@ -207,6 +207,8 @@ hipError_t launch_adam(const AdamArgs& a, hipStream_t st);
 hipError_t launch_grad_sumsq(const GradSumsqArgs& a, hipStream_t st);
 hipError_t launch_guard_finalize(const GuardFinalizeArgs& a, hipStream_t st);
 hipError_t launch_adam_guarded(const AdamArgs& a, const dmm_guard_state* state, hipStream_t st);  // a.grad_scale / step_size / bc2_sqrt: from *state
+// the same step for a range that became trainable at applied step t0 > 0: its own Adam step count is applied_steps - t0
+hipError_t launch_adam_guarded_from(const AdamArgs& a, const dmm_guard_state* state, float lr, int64_t t0, hipStream_t st);
 hipError_t launch_guard_init(dmm_guard_state* dev, float scale, int64_t applied, int32_t tracker, hipStream_t st);
 hipError_t launch_apply_corr(const ApplyCorrArgs& a, int dtype, hipStream_t st);
 hipError_t launch_pack(const PackDesc* descs_dev, const int* prefix_dev, int ndesc, int total_rows, int dtype, hipStream_t st,

@@ -11,6 +11,7 @@ Differences that are deliberate and documented:
 """
 import ctypes as C
 import math
+import operator
 import os
 import re
 import sys
@@ -24,6 +25,10 @@ from ...utils.Dense_U_Net_lidar_helper import get_config
 
 _DTYPES = {"fp32": _lib.DMM_F32, "float32": _lib.DMM_F32, "fp16": _lib.DMM_F16, "float16": _lib.DMM_F16,
            "bf16": _lib.DMM_BF16, "bfloat16": _lib.DMM_BF16}   # storage / MFMA operand type; accumulation is always fp32
+
+
+_REQUIRES_GRAD = operator.attrgetter("requires_grad")
+ENCODER_PREFIXES = ("features.", "stream_2_features.", "concat_module.")   # what freeze_encoder() freezes
 
 
 class _Node(nn.Module):
@@ -72,6 +77,13 @@ class _Plan:
         self.handle = C.c_void_p()
         desc = _make_desc(model, batch, height, width)
         _lib.check(L.dmm_plan_create(C.byref(desc), C.byref(self.handle)))
+        self.encoder_frozen = bool(model._encoder_frozen)   # the mode the plan is sized and bound in (dmm_plan_set_encoder_frozen)
+        if self.encoder_frozen:
+            rc = L.dmm_plan_set_encoder_frozen(self.handle, 1)
+            if rc:
+                h, self.handle = self.handle, None
+                L.dmm_plan_destroy(h)
+                _lib.check(rc)
         nbytes = L.dmm_plan_workspace_bytes(self.handle)
         dev = model._param_arena.device
         # DMM_GUARD_MB=n (tests): n MiB of a known byte pattern on either side of the workspace; check_guards() tells whether any
@@ -253,6 +265,59 @@ class Dense_U_Net_lidar(nn.Module):
         self._loss = (_lib.LOSS_BCE, None, None)
         self._loss_scaler = None
         self._grad_accumulation = False
+        # the encoder's parameters (in arena order), and the trainable set the live plans were built for
+        self._encoder_params = [getattr(owner, leaf) for (name, _, _, _), (owner, leaf, kind, _, _) in zip(table, self._slots)
+                                if kind <= _lib.T_BN_BIAS and name.startswith(ENCODER_PREFIXES)]
+        self._named_params = [(name, getattr(owner, leaf)) for (name, _, _, _), (owner, leaf, kind, _, _) in zip(table, self._slots)
+                              if kind <= _lib.T_BN_BIAS]   # (a list made once: the check below runs in front of every training forward)
+        self._param_list = [p for _, p in self._named_params]
+        self._trainable_sig = None   # requires_grad of every parameter as last looked at (None: not looked at yet)
+        self._encoder_frozen = False
+
+    # ------------------------------------------------------------------ frozen encoder
+    def freeze_encoder(self, frozen=True):
+        """Train the decoder and the head on a frozen encoder (frozen=False: release it).  Sets requires_grad on every parameter
+        under ``features``, ``stream_2_features`` and ``concat_module`` and closes the live plans: the next forward builds them in the
+        new mode, whose backward stops in front of the encoder (dmm_plan_set_encoder_frozen).  Frozen parameters have ``.grad`` None,
+        their range of the gradient arena reads zero behind a backward, and FusedAdam leaves them and their moments untouched.
+        BatchNorms of a frozen encoder still use batch statistics and update their running statistics in training mode, as torch's
+        do with requires_grad=False.  ``p.requires_grad_(False)`` on the same parameters does the same: a training-mode forward
+        looks at the flags.  Exactly two trainable sets are supported - everything, or everything but the encoder.  Works on a
+        CPU-resident model.  Returns the model."""
+        for p in self._encoder_params:
+            p.requires_grad_(not frozen)
+        self._check_trainable_set()
+        return self
+
+    @property
+    def encoder_frozen(self):
+        """True when exactly the encoder's parameters have requires_grad False (ValueError for any other mixture)."""
+        self._check_trainable_set()
+        return self._encoder_frozen
+
+    def _check_trainable_set(self):
+        """Looks at requires_grad of every parameter; on a change: validates the set and closes the plans of the other mode."""
+        sig = tuple(map(_REQUIRES_GRAD, self._param_list))
+        if sig == self._trainable_sig:
+            return
+        enc = {id(p) for p in self._encoder_params}
+        frozen = [(n, p) for n, p in self._named_params if not p.requires_grad]
+        if frozen:
+            outside = [n for n, p in frozen if id(p) not in enc]
+            if outside:
+                raise ValueError(f"{outside[0]} has requires_grad=False: only the encoder (features, stream_2_features, concat_module) "
+                                 "can be frozen, as a whole")
+            if len(frozen) != len(enc):
+                left = next(n for n, p in self._named_params if id(p) in enc and p.requires_grad)
+                raise ValueError(f"{left} is trainable while other encoder parameters are frozen: the encoder is frozen as a whole "
+                                 "(model.freeze_encoder()) or not at all")
+        self._trainable_sig = sig
+        if bool(frozen) != self._encoder_frozen:
+            self._encoder_frozen = bool(frozen)
+            self.close()   # plans are sized and bound per mode
+            for p in self._encoder_params:
+                if frozen:
+                    p.grad = None
 
     def _live_plans(self):
         plans = list(self._plans.values())
@@ -391,9 +456,13 @@ class Dense_U_Net_lidar(nn.Module):
             raise err
 
     def _attach_grads(self):
+        frozen = self._encoder_frozen   # (looked at by the training forward in front of this backward)
         for owner, leaf, kind, shape, off in self._slots:
             if kind <= _lib.T_BN_BIAS:
                 p = owner._parameters[leaf]
+                if frozen and not p.requires_grad:   # no gradient, as in torch
+                    p.grad = None
+                    continue
                 if p.grad is None or p.grad.data_ptr() != self._grad_arena.data_ptr() + 4 * off:
                     p.grad = self._grad_arena[off:off + p.numel()].view(shape)
 
@@ -446,6 +515,8 @@ class Dense_U_Net_lidar(nn.Module):
             if x2.shape[1] != self.stream_2_in_channels:
                 raise RuntimeError(f"stream_2 has {x2.shape[1]} channels, expected {self.stream_2_in_channels}")
             x2 = x2.contiguous().float()
+        if self.training:
+            self._check_trainable_set()   # requires_grad flags may have been set directly: plans of the other mode are closed
         plan = self._get_plan(B, H, W)
         plan.note_stream()
         logits = torch.empty(B, self.num_classes, H, W, dtype=torch.float32, device=x1.device)

@@ -187,6 +187,72 @@ class FusedAdam:
         if loss_scaler is not None:
             model.set_loss_scaler(loss_scaler)
         self._alloc()
+        # Per-parameter step origins (torch.optim.Adam counts steps per parameter): _t0[i] is the applied-step count at which
+        # parameter i began to train (its Adam step is count - _t0[i]); None: never trainable so far (no state, as in torch).
+        # _frozen_at[i]: the count at which a parameter that has trained was frozen (None: trainable now, or never trained).
+        self._params = list(model.parameters())
+        self._t0 = [0 if p.requires_grad else None for p in self._params]
+        self._frozen_at = [None] * len(self._params)
+        self._sig = tuple(p.requires_grad for p in self._params)
+        self._ranges = None
+        self._model_sig = None   # the model's own record of the flags (an object replaced on every change) when _ranges was built
+
+    # ---- trainable ranges ----
+    def _sync_trainable(self, look=True):
+        """Rebuilds the step origins and the range list when the model's trainable set has changed since the last look.  Reads the
+        applied-step count: on the guarded path that is ONE wait for the device, at a rare event (freezing or releasing the
+        encoder).  look=False (step()): the flags are not read again while the model's record of them - renewed by
+        freeze_encoder() and by every training-mode forward that finds a flag changed - is the object this list was built from;
+        a requires_grad_() set directly between a backward and its step() is therefore honoured from the next forward on, which is
+        also when the gradients begin to match it."""
+        msig = getattr(self.model, "_trainable_sig", None)
+        if not look and msig is not None and msig is self._model_sig and self._ranges is not None:
+            return
+        if look and hasattr(self.model, "_check_trainable_set"):
+            self.model._check_trainable_set()   # validates the set, closes plans of the other mode
+            msig = self.model._trainable_sig
+        sig = tuple(p.requires_grad for p in self._params)
+        self._model_sig = msig
+        if sig == self._sig and self._ranges is not None:
+            return
+        if sig != self._sig:
+            count = self.step_count
+            for i, (now, was) in enumerate(zip(sig, self._sig)):
+                if now and not was:      # released: a first-time parameter starts at step 1; one that trained before goes on where it was
+                    if self._t0[i] is None:
+                        self._t0[i] = count
+                    elif self._frozen_at[i] is not None:
+                        self._t0[i] += count - self._frozen_at[i]
+                    self._frozen_at[i] = None
+                elif was and not now and self._t0[i] is not None:
+                    self._frozen_at[i] = count
+            self._sig = sig
+        self._ranges = []
+        off = 0
+        for i, p in enumerate(self._params):
+            n = p.numel()
+            if sig[i]:
+                last = self._ranges[-1] if self._ranges else None
+                if last is not None and last[0] + last[1] == off and last[2] == self._t0[i]:
+                    last[1] += n
+                else:
+                    self._ranges.append([off, n, self._t0[i]])
+            off += n
+        if not self._ranges:
+            raise ValueError("no parameter of the model is trainable")
+
+    def trainable_ranges(self):
+        """[(offset, count, t0)]: the contiguous trainable runs of the arena (elements), each with the applied-step count at which it
+        became trainable (0: from the start).  Adjacent runs with different origins stay apart."""
+        self._sync_trainable()
+        return [tuple(r) for r in self._ranges]
+
+    def _param_step(self, i, count):
+        """Parameter i's own Adam step count (0: no state yet)."""
+        if self._t0[i] is None:
+            return 0
+        end = count if self._frozen_at[i] is None else self._frozen_at[i]
+        return max(0, end - self._t0[i])
 
     def _alloc(self):
         p = self.model.param_arena
@@ -236,11 +302,13 @@ class FusedAdam:
         g = self.param_groups[0]
         if self._guard is not None:
             return self._step_guarded(g, grad_scale)
+        self._sync_trainable(look=False)
         self.step_count += 1
-        _lib.check(_lib.lib().dmm_adam_step(
-            m.param_arena.data_ptr(), m.grad_arena.data_ptr(), self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(),
-            m.param_arena.numel(), float(g["lr"]), float(g["betas"][0]), float(g["betas"][1]), float(g["eps"]),
-            float(g["weight_decay"]), self.step_count, float(grad_scale), _lib.stream_ptr()))
+        for off, n, t0 in self._ranges:   # one launch per trainable run (one, over the whole arena, when nothing is frozen)
+            _lib.check(_lib.lib().dmm_adam_step(
+                m.param_arena.data_ptr() + 4 * off, m.grad_arena.data_ptr() + 4 * off, self.exp_avg.data_ptr() + 4 * off,
+                self.exp_avg_sq.data_ptr() + 4 * off, n, float(g["lr"]), float(g["betas"][0]), float(g["betas"][1]), float(g["eps"]),
+                float(g["weight_decay"]), self.step_count - t0, float(grad_scale), _lib.stream_ptr()))
 
     def _step_guarded(self, g, grad_scale):
         """Arena reduction -> decision -> Adam, three launches, no host synchronisation.  In a data-parallel job call it after
@@ -251,6 +319,16 @@ class FusedAdam:
         n = m.param_arena.numel()
         state = gd._materialize(m.param_arena.device)
         scratch = gd._scratch_for(n)
+        self._sync_trainable(look=False)
+        if self._ranges != [[0, n, 0]]:   # something is or was frozen: norm and step over the trainable ranges, each at its own step count
+            k = len(self._ranges)
+            offs, cnts, t0s = ((C.c_int64 * k)(*(r[j] for r in self._ranges)) for j in range(3))
+            _lib.check(_lib.lib().dmm_adam_step_guarded_ranges(
+                m.param_arena.data_ptr(), m.grad_arena.data_ptr(), self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(), offs, cnts, t0s, k,
+                float(g["lr"]), float(g["betas"][0]), float(g["betas"][1]), float(g["eps"]), float(g["weight_decay"]),
+                float(self.max_grad_norm or 0.0), gd.growth_factor, gd.backoff_factor, gd.growth_interval,
+                state.data_ptr(), scratch.data_ptr(), _lib.stream_ptr()))
+            return
         _lib.check(_lib.lib().dmm_adam_step_guarded(
             m.param_arena.data_ptr(), m.grad_arena.data_ptr(), self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(), n,
             float(g["lr"]), float(g["betas"][0]), float(g["betas"][1]), float(g["eps"]), float(g["weight_decay"]),
@@ -260,11 +338,13 @@ class FusedAdam:
     # ---- torch.optim.Adam-compatible checkpoint format ----
     def state_dict(self):
         state, off = {}, 0
+        self._sync_trainable()
         step_count = self.step_count
         for i, p in enumerate(self.model.parameters()):
             n = p.numel()
-            if step_count > 0:
-                state[i] = {"step": torch.tensor(float(step_count)),
+            own = self._param_step(i, step_count)   # per parameter, as torch counts; a parameter that never trained has no entry
+            if own > 0:
+                state[i] = {"step": torch.tensor(float(own)),
                             "exp_avg": self.exp_avg[off:off + n].view(p.shape).clone(),
                             "exp_avg_sq": self.exp_avg_sq[off:off + n].view(p.shape).clone()}
             off += n
@@ -278,10 +358,17 @@ class FusedAdam:
     def load_state_dict(self, sd):
         off = 0
         steps = [int(float(s["step"])) for s in sd["state"].values()] or [0]
-        self.step_count = max(steps)
+        self.step_count = count = max(steps)
+        # step origins from the per-parameter steps: a checkpoint written in one phase resumes in that phase.  A trainable parameter
+        # without an entry takes its first step next (torch creates its state then); a frozen one without an entry has never trained.
+        self._sig = tuple(p.requires_grad for p in self._params)
+        self._ranges = None
         for i, p in enumerate(self.model.parameters()):
             n = p.numel()
             s = sd["state"].get(i)
+            own = int(float(s["step"])) if s is not None else 0
+            self._t0[i] = count - own if (own > 0 or self._sig[i]) else None
+            self._frozen_at[i] = count if (own > 0 and not self._sig[i]) else None
             if s is not None:
                 self.exp_avg[off:off + n].copy_(s["exp_avg"].reshape(-1))
                 self.exp_avg_sq[off:off + n].copy_(s["exp_avg_sq"].reshape(-1))

@@ -146,6 +146,21 @@ int dmm_plan_backward(dmm_plan* plan, const float* dlogits, void* stream);
  * dmm_plan_bind.  Several plans bound to one arena (different input sizes) accumulate into it together when each has the mode on. */
 int dmm_plan_set_grad_accumulate(dmm_plan* plan, int accumulate);
 
+/* Frozen encoder: train the decoder and the head on an encoder that stays as it is (e.g. loaded from a pretrained checkpoint), as
+ * requires_grad = False on every parameter under `features`, `stream_2_features` and `concat_module` does in torch.  frozen != 0:
+ *   - the backward list is the default list up to and excluding the first encoder record (records are walked from the head back, so
+ *     every decoder / head launch comes first and keeps its kernel family and arguments); no launch of it writes an encoder range of
+ *     the gradient arena, which therefore reads zero behind a backward (the arena is still cleared whole) or, with
+ *     dmm_plan_set_grad_accumulate on, keeps what it held;
+ *   - dmm_plan_num_grad_buckets / dmm_plan_grad_bucket describe trainable tensors only; the unpack tables hold no encoder tensor;
+ *   - the forward lists are unchanged: frozen BatchNorms still normalise with batch statistics and update their running statistics
+ *     in a training forward, as torch's do with requires_grad = False.
+ * Legal only between dmm_plan_create and dmm_plan_bind: the call runs the sizing pass again (dmm_plan_workspace_bytes is that of the
+ * mode and never larger than the default's); a bound plan returns DMM_ERR_STATE, a null plan DMM_ERR_INVALID.  The setting survives
+ * dmm_plan_bind.  0 on a fresh plan changes nothing.  The optimiser must leave the frozen ranges alone: dmm_adam_step_guarded_ranges,
+ * or dmm_adam_step per range. */
+int dmm_plan_set_encoder_frozen(dmm_plan* plan, int frozen);
+
 /* Data-parallel training (new here; the reference's torch.distributed import, graphs/models/Dense_U_Net_lidar.py:7, is unused):
  * the gradient arena is cut into buckets of whole tensors (about dmm_set_option("grad_bucket_mb", 25) each, set before
  * dmm_plan_create) listed in the order in which backward finishes them (head, decoder, block 4 ... stems).
@@ -225,6 +240,19 @@ int dmm_guard_state_init(dmm_guard_state* dev, float init_scale, int64_t applied
 int dmm_adam_step_guarded(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, int64_t n, float lr, float beta1,
                           float beta2, float eps, float weight_decay, float max_norm, float growth_factor, float backoff_factor,
                           int32_t growth_interval, dmm_guard_state* state, void* scratch, void* stream);
+/* The guarded step over `nranges` disjoint ranges [offsets[i], offsets[i] + counts[i]) of the arenas (elements): what lies outside
+ * them - a frozen encoder's parameters and moments - is neither read for the norm nor written, whatever weight_decay is.  Enqueues
+ * one reduction per range (the first assigns the partials, the rest add), ONE finalize (the rule above, one decision for all ranges)
+ * and one Adam launch per range.  t0[i] = the applied-step count at which range i became trainable: torch counts steps per
+ * parameter, so the range's Adam step is applied_steps - t0[i] (a range released at step k starts at t = 1 with its zero moments,
+ * not with the bias corrections of step k + 1, which would make its first updates about lr (1 - beta1) / sqrt(1 - beta2) = 3.2 lr).
+ * t0[i] == 0 launches the kernel of dmm_adam_step_guarded; t0[i] > 0 a variant that forms step_size and bc2_sqrt for its own count
+ * on the device, in fp64, from state->applied_steps.  Refuses, before any HIP call: a null pointer, nranges < 1, a negative offset,
+ * count or t0, overlapping ranges, and what dmm_adam_step_guarded refuses.  scratch: >= dmm_grad_guard_scratch_bytes(0). */
+int dmm_adam_step_guarded_ranges(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, const int64_t* offsets,
+                                 const int64_t* counts, const int64_t* t0, int nranges, float lr, float beta1, float beta2, float eps,
+                                 float weight_decay, float max_norm, float growth_factor, float backoff_factor, int32_t growth_interval,
+                                 dmm_guard_state* state, void* scratch, void* stream);
 /* The reduction alone, on elements [offset, offset + count) of `grads`: scratch = (accumulate ? scratch : 0) + partial sums of the
  * range.  dmm_adam_step_guarded runs it once over the whole arena; a data-parallel trainer can run it per gradient bucket behind
  * that bucket's all-reduce instead (not wired up yet).  Also what the unit tests and the cost measurement call. */

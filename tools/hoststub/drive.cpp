@@ -32,6 +32,9 @@
 // DRIVE_NO_MFMA=1 (any mode): the description asks for use_mfma = 0.
 // DRIVE_DYN_SCALE=1 (life-cycle run and dump): the plan gets a dynamic loss scale (dmm_plan_set_dynamic_loss_scale, pointing into a
 // guard state block the driver owns: region "guard"); the life-cycle run also takes the guarded optimiser step after every backward.
+// DRIVE_FREEZE=1 (life-cycle run and dump): the plan is built with a frozen encoder (dmm_plan_set_encoder_frozen on the unbound plan; a
+// null plan and the bound plan must be refused); the life-cycle run also takes the guarded step over two trainable ranges, one of
+// them released late (dmm_adam_step_guarded_ranges, t0 > 0), and checks that no bucket and no unpack descriptor touches an encoder tensor.
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -150,6 +153,15 @@ bool fill_desc(const std::string& arch, dmm_model_desc& d) {
 static int one_life(const dmm_model_desc& d, int life) {
   dmm_plan* plan = nullptr;
   MUST(dmm_plan_create(&d, &plan));
+  const bool freeze = getenv("DRIVE_FREEZE") != nullptr;
+  if (freeze) {
+    const size_t wsb_default = dmm_plan_workspace_bytes(plan);
+    if (dmm_plan_set_encoder_frozen(nullptr, 1) != DMM_ERR_INVALID) { fprintf(stderr, "[drive] a null plan was not refused\n"); return 2; }
+    MUST(dmm_plan_set_encoder_frozen(plan, 0));   // nothing changes
+    if (dmm_plan_workspace_bytes(plan) != wsb_default) { fprintf(stderr, "[drive] frozen = 0 changed a fresh plan\n"); return 2; }
+    MUST(dmm_plan_set_encoder_frozen(plan, 1));
+    if (dmm_plan_workspace_bytes(plan) > wsb_default) { fprintf(stderr, "[drive] the frozen plan's workspace is larger than the default's\n"); return 2; }
+  }
   const size_t wsb = dmm_plan_workspace_bytes(plan);
   const int64_t np = dmm_plan_num_params(plan), nb = std::max<int64_t>(dmm_plan_num_buffer_elems(plan), 1);
   // 256-byte aligned workspace with nothing mapped... ASan red zones sit on either side of each allocation
@@ -171,6 +183,23 @@ static int one_life(const dmm_model_desc& d, int life) {
   // (test of the bind-time check: a plan whose switches were tampered with after it was sized reserves other bytes -> DMM_ERR_STATE)
   if (getenv("DRIVE_FLIP_SWITCH_BETWEEN_CREATE_AND_BIND")) plan->sw.no_eff_compact = !plan->sw.no_eff_compact;
   MUST(dmm_plan_bind(plan, ws, wsb, params, grads, buffers));
+  int64_t enc_lo = 0, enc_hi = 0;   // the leading encoder range of the arena (`features`): [enc_lo, enc_hi)
+  if (freeze) {
+    if (!plan->encoder_frozen) { fprintf(stderr, "[drive] the frozen mode did not survive dmm_plan_bind\n"); return 2; }
+    if (dmm_plan_set_encoder_frozen(plan, 0) != DMM_ERR_STATE) { fprintf(stderr, "[drive] a bound plan was not refused\n"); return 2; }
+    auto enc = [](const std::string& n) { return n.rfind("features.", 0) == 0 || n.rfind("stream_2_features.", 0) == 0 || n.rfind("concat_module.", 0) == 0; };
+    for (const TensorInfo& t : plan->tensors) {
+      if (t.kind > DMM_T_BN_BIAS || !enc(t.name)) continue;
+      int64_t n = 1;
+      for (int k = 0; k < t.ndim; ++k) n *= t.shape[k];
+      if (t.off == enc_hi) enc_hi = t.off + n;
+      for (const GradBucket& b : plan->buckets)
+        if (t.off < b.off + b.n && b.off < t.off + n) { fprintf(stderr, "[drive] a bucket overlaps the frozen tensor %s\n", t.name.c_str()); return 2; }
+      for (const PackDesc& pd : plan->unpacks)
+        if (pd.gw >= grads + t.off && pd.gw < grads + t.off + n) { fprintf(stderr, "[drive] an unpack descriptor scatters into the frozen tensor %s\n", t.name.c_str()); return 2; }
+    }
+    if (enc_hi <= 0 || enc_hi >= np) { fprintf(stderr, "[drive] no leading encoder range\n"); return 2; }
+  }
   if (getenv("DRIVE_TOGGLE_BETWEEN_CREATE_AND_BIND")) {   // the families the bound plan recorded: "FAMILIES <name>=<launch records> ..." (a fused pair counts as bw1)
     int n[IMPL_COUNT] = {};
     for (const auto* ops : {&plan->fwd_train, &plan->fwd_eval, &plan->bwd})
@@ -190,7 +219,7 @@ static int one_life(const dmm_model_desc& d, int life) {
   const long l0 = fakehip_launches();
   void* st = nullptr;  // the caller's stream: the null stream, as torch's default
   // the guarded optimiser step's state block, scratch and moment arenas ("device" memory = heap: ASan sees every host-side touch)
-  const bool dyn = getenv("DRIVE_DYN_SCALE") != nullptr;
+  const bool dyn = getenv("DRIVE_DYN_SCALE") != nullptr || freeze;
   dmm_guard_state* gstate = (dmm_guard_state*)aligned_alloc(64, sizeof(dmm_guard_state));
   void* gscratch = malloc(dmm_grad_guard_scratch_bytes(np));
   float* mom1 = (float*)malloc(np * 4); float* mom2 = (float*)malloc(np * 4);
@@ -202,7 +231,14 @@ static int one_life(const dmm_model_desc& d, int life) {
   for (int rep = 0; rep < 2; ++rep) {
     MUST(dmm_plan_forward(plan, in1, d.stream_2_in_channels ? in2 : nullptr, logits, 1, st));
     MUST(dmm_plan_loss_backward(plan, logits, target, metrics, st));
-    if (dyn) {
+    if (freeze) {   // two trainable ranges: everything behind the leading encoder range from the start, that range released at step 1
+      const int64_t offs[2] = {enc_hi, enc_lo}, cnts[2] = {np - enc_hi, enc_hi - enc_lo}, t0s[2] = {0, 1};
+      MUST(dmm_adam_step_guarded_ranges(params, grads, mom1, mom2, offs, cnts, t0s, rep == 0 ? 1 : 2, 1e-3f, 0.9f, 0.999f, 1e-8f, 0.01f, 1.0f, 2.f, 0.5f, 2000,
+                                        gstate, gscratch, st));
+      const int64_t bad_offs[2] = {0, enc_hi - 1};
+      if (dmm_adam_step_guarded_ranges(params, grads, mom1, mom2, bad_offs, cnts, t0s, 2, 1e-3f, 0.9f, 0.999f, 1e-8f, 0.f, 1.0f, 2.f, 0.5f, 2000, gstate,
+                                       gscratch, st) != DMM_ERR_INVALID) { fprintf(stderr, "[drive] overlapping ranges were not refused\n"); return 2; }
+    } else if (dyn) {
       MUST(dmm_adam_step_guarded(params, grads, mom1, mom2, np, 1e-3f, 0.9f, 0.999f, 1e-8f, 0.f, 1.0f, 2.f, 0.5f, 2000, gstate, gscratch, st));
       MUST(dmm_grad_sumsq(grads, np / 2, np - np / 2, 1, gscratch, st));
     }
@@ -549,6 +585,7 @@ static int dump_main(int argc, char** argv) {
   const size_t shift = sh ? (size_t)atoi(sh) << 20 : 0;   // (whole MiB: the alignment of every region stays what it was)
   dmm_plan* plan = nullptr;
   MUST(dmm_plan_create(&d, &plan));
+  if (getenv("DRIVE_FREEZE")) MUST(dmm_plan_set_encoder_frozen(plan, 1));
   const size_t wsb = dmm_plan_workspace_bytes(plan);
   uint8_t* ws0 = (uint8_t*)reserve(wsb + shift, PROT_READ | PROT_WRITE);
   fakehip_skip_large_memset(1);
