@@ -38,6 +38,22 @@ class GuardState(C.Structure):
 
 assert C.sizeof(GuardState) == 64
 
+ADAM_MAX_CLASSES = 16   # DMM_ADAM_MAX_CLASSES
+
+
+class AdamSegment(C.Structure):
+    """dmm_adam_segment: elements [begin, begin + count) of the arenas belong to class `cls`."""
+    _fields_ = [("begin", C.c_int64), ("count", C.c_int64), ("cls", C.c_int32)]
+
+
+class AdamClass(C.Structure):
+    """dmm_adam_class: the hyper-parameters of a (parameter group, step origin) pair."""
+    _fields_ = [("lr", C.c_float), ("beta1", C.c_float), ("beta2", C.c_float), ("eps", C.c_float), ("weight_decay", C.c_float),
+                ("decoupled", C.c_int32), ("t0", C.c_int64)]
+
+
+assert C.sizeof(AdamSegment) == 24 and C.sizeof(AdamClass) == 32
+
 
 class DmmError(RuntimeError):
     pass
@@ -112,6 +128,12 @@ def lib():
     L.dmm_adam_step_guarded_ranges.argtypes = [vp, vp, vp, vp, C.POINTER(i64), C.POINTER(i64), C.POINTER(i64), C.c_int,
                                                f32, f32, f32, f32, f32, f32, f32, f32, i32, vp, vp, vp]
     L.dmm_plan_set_encoder_frozen.argtypes = [vp, C.c_int]
+    L.dmm_adam_table_bytes.argtypes = [C.c_int, i64]
+    L.dmm_adam_table_bytes.restype = sz
+    L.dmm_adam_table_init.argtypes = [vp, C.POINTER(AdamSegment), C.c_int, i64, C.c_int, vp]
+    L.dmm_adam_step_segmented.argtypes = [vp, vp, vp, vp, i64, vp, C.c_int, C.POINTER(AdamClass), C.c_int, i64, f32, vp]
+    L.dmm_adam_step_guarded_segmented.argtypes = [vp, vp, vp, vp, i64, vp, C.c_int, C.POINTER(AdamClass), C.c_int, f32, f32, f32, i32,
+                                                  vp, vp, vp]
     L.dmm_grad_sumsq.argtypes = [vp, i64, i64, C.c_int, vp, vp]
     L.dmm_plan_set_dynamic_loss_scale.argtypes = [vp, vp]
     L.dmm_plan_set_grad_accumulate.argtypes = [vp, C.c_int]
@@ -138,6 +160,7 @@ EXPORTS = [
     "dmm_conv_dgrad", "dmm_conv_wgrad_ex", "dmm_conv_dgrad_ex", "dmm_conv1x1_backward_fused", "dmm_conv5_wgrad_stats", "dmm_last_impl", "dmm_impl_name", "dmm_impl_mask",
     "dmm_grad_guard_scratch_bytes", "dmm_guard_state_init", "dmm_adam_step_guarded", "dmm_grad_sumsq", "dmm_plan_set_dynamic_loss_scale",
     "dmm_plan_set_grad_accumulate", "dmm_plan_set_encoder_frozen", "dmm_adam_step_guarded_ranges",
+    "dmm_adam_table_bytes", "dmm_adam_table_init", "dmm_adam_step_segmented", "dmm_adam_step_guarded_segmented",
 ]
 
 

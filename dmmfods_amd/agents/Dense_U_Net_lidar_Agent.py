@@ -7,7 +7,8 @@ come back as device tensors without the per-iteration host syncs of A:252-260 / 
 installed here); ``compute_dtype`` / data parallelism are new, and so is the guarded optimiser step (``max_grad_norm``, ``loss_scaler``:
 clipping by global norm, a dynamic loss scale and a skipped step on overflow, dmmfods_amd/optim.py) and gradient accumulation
 (``config.optimizer.accumulate_steps``: one optimiser step per N batches, on the sum of their gradients) and a frozen-encoder
-phase (``config.optimizer.freeze_encoder_epochs``: decoder and head train alone for the first N epochs)."""
+phase (``config.optimizer.freeze_encoder_epochs``: decoder and head train alone for the first N epochs) and parameter groups for
+fine-tuning (``config.optimizer.encoder_lr_scale``, ``no_decay_norm_bias``, ``decoupled_weight_decay``: dmmfods_amd.optim.fine_tune_groups)."""
 import logging
 import os
 import warnings
@@ -18,7 +19,7 @@ import torch
 
 from ..datasets.WaymoData import WaymoDataset_Loader
 from ..graphs.models.Dense_U_Net_lidar import densenet121_u_lidar
-from ..optim import DynamicLossScaler, FusedAdam
+from ..optim import DynamicLossScaler, FusedAdam, fine_tune_groups
 from ..utils import Dense_U_Net_lidar_helper as utils
 
 try:  # pragma: no cover - tensorboard is not installed in the build image
@@ -97,9 +98,18 @@ class Dense_U_Net_lidar_Agent:
             raise ValueError("optimizer.freeze_encoder_epochs must be an integer >= 0")
         self.current_epoch = 0
         self._apply_freeze_phase()   # before the optimiser is built: a frozen parameter starts without optimiser state
+        # encoder_lr_scale / no_decay_norm_bias / decoupled_weight_decay: when any is present the optimiser is built over the groups of
+        # fine_tune_groups (the encoder at encoder_lr_scale x learning_rate, no decay on BatchNorm weights and biases, AdamW's
+        # decay) and steps with one segmented launch.  All absent: the reference's single group.
+        els, ndnb, dwd = (self._optional(o, k) for k in ("encoder_lr_scale", "no_decay_norm_bias", "decoupled_weight_decay"))
+        grouped = {}
+        if els is not None or ndnb is not None or dwd is not None:
+            grouped = dict(param_groups=fine_tune_groups(self.model, o.learning_rate, o.weight_decay,
+                                                         encoder_lr_scale=1.0 if els is None else float(els), no_decay_norm_bias=bool(ndnb)),
+                           decoupled_weight_decay=bool(dwd))
         self.optimizer = FusedAdam(self.model, lr=o.learning_rate, betas=(o.beta1, o.beta2), eps=o.eps,
                                    weight_decay=o.weight_decay, amsgrad=o.amsgrad, max_grad_norm=max_grad_norm,
-                                   loss_scaler=loss_scaler)
+                                   loss_scaler=loss_scaler, **grouped)
         self.lr_scheduler = None
         if o.lr_scheduler.want:
             self.lr_scheduler = _StepLR(self.optimizer, o.lr_scheduler.every_n_epochs, o.lr_scheduler.gamma)

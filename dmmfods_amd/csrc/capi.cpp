@@ -9,6 +9,8 @@
 #include <chrono>
 #include <mutex>
 #include <string>
+#include <utility>
+#include <vector>
 #include <unistd.h>
 
 #include "dispatch.h"
@@ -845,6 +847,177 @@ int dmm_adam_step_guarded_ranges(float* params, const float* grads, float* exp_a
     if (t0[i] == 0) HIPCHK(launch_adam_guarded(a, state, st));
     else HIPCHK(launch_adam_guarded_from(a, state, lr, t0[i], st));
   }
+  return DMM_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ parameter groups: segmented Adam
+namespace {
+hipError_t upload(void* dst, const void* src, size_t bytes, hipStream_t st);   // (below: complete when it returns)
+// What dmm_adam_table_init uploaded to each table_dev: the step calls take a device pointer and cannot read the table back without
+// waiting for the device, but the guarded one needs the maximal contiguous runs (one reduction each), and both need to know that
+// what they are about to walk was validated.  Entries are replaced by the next init of the same address and never removed (a few
+// dozen bytes per table ever made).
+struct AdamTableHost {
+  int nsegs = 0, nclasses = 0;
+  int64_t n = 0;
+  std::vector<std::pair<int64_t, int64_t>> runs;   // (begin, count)
+};
+std::mutex g_adam_tables_mu;
+std::vector<std::pair<const void*, AdamTableHost>> g_adam_tables;
+
+size_t adam_table_chunks(int64_t n) { return (size_t)((n + ADAM_SEG_CHUNK - 1) / ADAM_SEG_CHUNK); }
+
+bool bad_scalar(float x) { return std::isnan(x) || x < 0.f; }
+
+// the refusals the two step calls share; on success *host is the record of the table
+int adam_seg_check(const char* who, const float* params, const float* grads, const float* exp_avg, const float* exp_avg_sq, int64_t n,
+                   const void* table_dev, int nsegs, const dmm_adam_class* classes, int nclasses, AdamTableHost* host) {
+  const std::string w(who);
+  if (!params || !grads || !exp_avg || !exp_avg_sq || !table_dev || !classes) return fail(DMM_ERR_INVALID, w + ": null argument");
+  if ((((uintptr_t)params | (uintptr_t)grads | (uintptr_t)exp_avg | (uintptr_t)exp_avg_sq) & 3) != 0 || ((uintptr_t)table_dev & 7) != 0)
+    return fail(DMM_ERR_INVALID, w + ": misaligned arena (4 bytes) or table (8 bytes) pointer");
+  if (n < 1) return fail(DMM_ERR_INVALID, w + ": n must be >= 1");
+  if (nsegs < 1) return fail(DMM_ERR_INVALID, w + ": nsegs must be >= 1");
+  if (nclasses < 1 || nclasses > ADAM_MAX_CLASSES)
+    return fail(DMM_ERR_INVALID, w + ": nclasses must lie in [1, " + std::to_string(ADAM_MAX_CLASSES) + "]");
+  for (int c = 0; c < nclasses; ++c) {
+    const dmm_adam_class& k = classes[c];
+    const std::string cw = w + ": class " + std::to_string(c) + ": ";
+    if (!(k.beta1 >= 0.f && k.beta1 < 1.f) || !(k.beta2 >= 0.f && k.beta2 < 1.f)) return fail(DMM_ERR_INVALID, cw + "betas must lie in [0, 1)");
+    if (bad_scalar(k.lr)) return fail(DMM_ERR_INVALID, cw + "lr must be >= 0 and not NaN");
+    if (bad_scalar(k.eps)) return fail(DMM_ERR_INVALID, cw + "eps must be >= 0 and not NaN");
+    if (bad_scalar(k.weight_decay)) return fail(DMM_ERR_INVALID, cw + "weight_decay must be >= 0 and not NaN");
+    if (k.t0 < 0) return fail(DMM_ERR_INVALID, cw + "t0 must be >= 0");
+  }
+  std::lock_guard<std::mutex> l(g_adam_tables_mu);
+  for (const auto& e : g_adam_tables)
+    if (e.first == table_dev) {
+      if (e.second.nsegs != nsegs || e.second.n != n)
+        return fail(DMM_ERR_INVALID, w + ": table_dev was initialised for nsegs = " + std::to_string(e.second.nsegs) + ", n = " + std::to_string(e.second.n));
+      if (e.second.nclasses != nclasses)
+        return fail(DMM_ERR_INVALID, w + ": table_dev was initialised for nclasses = " + std::to_string(e.second.nclasses));
+      *host = e.second;
+      return DMM_OK;
+    }
+  return fail(DMM_ERR_INVALID, w + ": table_dev was not initialised by dmm_adam_table_init");
+}
+
+void adam_seg_args(AdamSegArgs& a, float* params, const float* grads, float* exp_avg, float* exp_avg_sq, int64_t n, const void* table_dev,
+                   int nsegs, const dmm_adam_class* classes, int nclasses) {
+  a.p = params; a.g = grads; a.m = exp_avg; a.v = exp_avg_sq; a.n = (size_t)n;
+  a.segs = (const AdamSegDev*)table_dev;
+  a.first = (const int*)((const uint8_t*)table_dev + (size_t)nsegs * sizeof(AdamSegDev));
+  a.nsegs = nsegs; a.nchunks = (int)adam_table_chunks(n); a.nclasses = nclasses;
+  a.vec_ok = (((uintptr_t)params | (uintptr_t)grads | (uintptr_t)exp_avg | (uintptr_t)exp_avg_sq) & 15) == 0 ? 1 : 0;
+  a.grad_scale = 0.f; a.state = nullptr;
+  for (int c = 0; c < ADAM_MAX_CLASSES; ++c) {
+    AdamSegClass& k = a.cls[c];
+    k = AdamSegClass{};
+    k.bc2_sqrt = 1.f;
+    if (c >= nclasses) continue;
+    const dmm_adam_class& s = classes[c];
+    k.lr = s.lr; k.beta1 = s.beta1; k.beta2 = s.beta2; k.eps = s.eps; k.t0 = s.t0;
+    k.decoupled = s.decoupled != 0 ? 1 : 0;
+    k.weight_decay = k.decoupled ? 0.f : s.weight_decay;
+    k.decay = k.decoupled ? (float)(1.0 - (double)s.lr * (double)s.weight_decay) : 1.f;
+  }
+}
+}  // namespace
+
+size_t dmm_adam_table_bytes(int nsegs, int64_t n) {
+  if (nsegs < 1 || n < 1 || n > (int64_t)INT32_MAX * ADAM_SEG_CHUNK) return 0;
+  return (size_t)nsegs * sizeof(AdamSegDev) + adam_table_chunks(n) * sizeof(int);
+}
+
+int dmm_adam_table_init(void* table_dev, const dmm_adam_segment* segs, int nsegs, int64_t n, int nclasses, void* stream) {
+  // every refusal comes before the first HIP call
+  if (!table_dev || !segs) return fail(DMM_ERR_INVALID, "dmm_adam_table_init: null argument");
+  if (((uintptr_t)table_dev & 7) != 0) return fail(DMM_ERR_INVALID, "dmm_adam_table_init: misaligned table pointer (8 bytes)");
+  if (nsegs < 1) return fail(DMM_ERR_INVALID, "dmm_adam_table_init: nsegs must be >= 1");
+  if (n < 1 || n > (int64_t)INT32_MAX * ADAM_SEG_CHUNK) return fail(DMM_ERR_INVALID, "dmm_adam_table_init: n must be >= 1 (and below 2^41)");
+  if (nclasses < 1 || nclasses > ADAM_MAX_CLASSES)
+    return fail(DMM_ERR_INVALID, "dmm_adam_table_init: nclasses must lie in [1, " + std::to_string(ADAM_MAX_CLASSES) + "]");
+  for (int i = 0; i < nsegs; ++i) {
+    const dmm_adam_segment& s = segs[i];
+    const std::string w = "dmm_adam_table_init: segment " + std::to_string(i);
+    if (s.count < 1) return fail(DMM_ERR_INVALID, w + ": count must be >= 1");
+    if (s.begin < 0 || s.begin >= n || s.count > n - s.begin) return fail(DMM_ERR_INVALID, w + " lies outside [0, n)");
+    if (s.cls < 0 || s.cls >= nclasses) return fail(DMM_ERR_INVALID, w + ": cls outside [0, nclasses)");
+    if (i > 0 && s.begin < segs[i - 1].begin + segs[i - 1].count)
+      return fail(DMM_ERR_INVALID, w + " is unsorted or overlaps segment " + std::to_string(i - 1));
+  }
+  const size_t nchunks = adam_table_chunks(n), bytes = dmm_adam_table_bytes(nsegs, n);
+  std::vector<uint8_t> buf(bytes);
+  AdamSegDev* sd = (AdamSegDev*)buf.data();
+  int* first = (int*)(buf.data() + (size_t)nsegs * sizeof(AdamSegDev));
+  AdamTableHost host;
+  host.nsegs = nsegs; host.nclasses = nclasses; host.n = n;
+  for (int i = 0; i < nsegs; ++i) {
+    sd[i].begin = segs[i].begin; sd[i].end = segs[i].begin + segs[i].count; sd[i].cls = segs[i].cls; sd[i].pad = 0;
+    if (!host.runs.empty() && host.runs.back().first + host.runs.back().second == segs[i].begin) host.runs.back().second += segs[i].count;
+    else host.runs.emplace_back(segs[i].begin, segs[i].count);
+  }
+  int s = 0;
+  for (size_t ch = 0; ch < nchunks; ++ch) {
+    while (s < nsegs && sd[s].end <= (long long)(ch * ADAM_SEG_CHUNK)) ++s;
+    first[ch] = s;
+  }
+  HIPCHK(upload(table_dev, buf.data(), bytes, (hipStream_t)stream));
+  std::lock_guard<std::mutex> l(g_adam_tables_mu);
+  for (auto& e : g_adam_tables)
+    if (e.first == table_dev) { e.second = std::move(host); return DMM_OK; }
+  g_adam_tables.emplace_back(table_dev, std::move(host));
+  return DMM_OK;
+}
+
+int dmm_adam_step_segmented(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, int64_t n, const void* table_dev,
+                            int nsegs, const dmm_adam_class* classes, int nclasses, int64_t step, float grad_scale, void* stream) {
+  if (step < 1) return fail(DMM_ERR_INVALID, "dmm_adam_step_segmented: step must be >= 1");
+  AdamTableHost host;
+  if (int rc = adam_seg_check("dmm_adam_step_segmented", params, grads, exp_avg, exp_avg_sq, n, table_dev, nsegs, classes, nclasses, &host)) return rc;
+  AdamSegArgs a;
+  adam_seg_args(a, params, grads, exp_avg, exp_avg_sq, n, table_dev, nsegs, classes, nclasses);
+  a.grad_scale = grad_scale;
+  for (int c = 0; c < nclasses; ++c) {   // dmm_adam_step's expressions, for the class's own step
+    AdamSegClass& k = a.cls[c];
+    const int64_t t = step - k.t0;
+    k.active = t >= 1 ? 1 : 0;
+    if (!k.active) continue;
+    const double bc1 = 1.0 - std::pow((double)k.beta1, (double)t), bc2 = 1.0 - std::pow((double)k.beta2, (double)t);
+    k.step_size = (float)(k.lr / bc1);
+    k.bc2_sqrt = (float)std::sqrt(bc2);
+  }
+  HIPCHK(launch_adam_segmented(a, (hipStream_t)stream));
+  return DMM_OK;
+}
+
+int dmm_adam_step_guarded_segmented(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, int64_t n,
+                                    const void* table_dev, int nsegs, const dmm_adam_class* classes, int nclasses, float max_norm,
+                                    float growth_factor, float backoff_factor, int32_t growth_interval, dmm_guard_state* state,
+                                    void* scratch, void* stream) {
+  const char* who = "dmm_adam_step_guarded_segmented";
+  if (!state || !scratch) return fail(DMM_ERR_INVALID, std::string(who) + ": null state or scratch");
+  if ((((uintptr_t)state) & 7) != 0 || (((uintptr_t)scratch) & 7) != 0) return fail(DMM_ERR_INVALID, std::string(who) + ": misaligned state or scratch pointer");
+  if (!(growth_factor >= 1.f) || !std::isfinite(growth_factor)) return fail(DMM_ERR_INVALID, "growth_factor must be a finite number >= 1");
+  if (!(backoff_factor > 0.f) || !(backoff_factor <= 1.f)) return fail(DMM_ERR_INVALID, "backoff_factor must lie in (0, 1]");
+  if (growth_interval < 0) return fail(DMM_ERR_INVALID, "growth_interval must be >= 0");
+  if (std::isnan(max_norm)) return fail(DMM_ERR_INVALID, "max_norm is NaN");
+  AdamTableHost host;
+  if (int rc = adam_seg_check(who, params, grads, exp_avg, exp_avg_sq, n, table_dev, nsegs, classes, nclasses, &host)) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  for (size_t i = 0; i < host.runs.size(); ++i) {   // the norm over the segments only: the first run assigns the partials, the rest add
+    GradSumsqArgs r;
+    r.g = grads + host.runs[i].first; r.n = (size_t)host.runs[i].second; r.partials = (double*)scratch; r.accumulate = i > 0 ? 1 : 0;
+    HIPCHK(launch_grad_sumsq(r, st));
+  }
+  GuardFinalizeArgs f;   // the decision is one for all classes; the step_size / bc2_sqrt it leaves in the block are class 0's at t0 = 0
+  f.partials = (const double*)scratch; f.state = state; f.lr = classes[0].lr; f.beta1 = classes[0].beta1; f.beta2 = classes[0].beta2;
+  f.max_norm = max_norm; f.growth_factor = growth_factor; f.backoff_factor = backoff_factor; f.growth_interval = growth_interval;
+  HIPCHK(launch_guard_finalize(f, st));
+  AdamSegArgs a;
+  adam_seg_args(a, params, grads, exp_avg, exp_avg_sq, n, table_dev, nsegs, classes, nclasses);
+  a.state = state;   // grad_scale, the step counts and the skip are read from *state by the kernel
+  HIPCHK(launch_adam_segmented(a, st));
   return DMM_OK;
 }
 

@@ -5,6 +5,7 @@
 //   guard_finalize : partials (fixed order) -> apply / skip, clip coefficient, Adam bias corrections of the APPLIED step, next scale
 //   adam_guarded   : adam_kernel's arithmetic with its scalars read from the state block; writes nothing on a skipped step
 //   adam_guarded_from : the same for a range whose own step count started late (dmm_adam_step_guarded_ranges, t0 > 0)
+//   adam_segmented : parameter groups and frozen gaps in ONE launch: walks the arena under a segment table (plain and guarded path)
 //   guard_init     : fills a state block (start of training, checkpoint load)
 // No floating-point atomics anywhere: a workgroup owns its partial, the finalize kernel adds the partials in a fixed tree, so the
 // norm, the decision and the step are bit-reproducible from run to run (and equal on every rank of a data-parallel job, which reads
@@ -170,6 +171,124 @@ hipError_t launch_adam_guarded_from(const AdamArgs& a, const dmm_guard_state* st
   if (grid > 4096) grid = 4096;
   if (grid < 1) grid = 1;
   hipLaunchKernelGGL(adam_guarded_from_kernel, dim3(grid), dim3(256), 0, st, a, state, lr, (long long)t0);
+  return hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------------------ segmented Adam
+// adam_kernel's element arithmetic (pointwise.hip), expression for expression, with the scalars of the element's class.  Its rounding
+// points are pinned: as adam_kernel, adam_guarded_kernel and adam_guarded_from_kernel are compiled, every product and sum of the
+// moment and denominator lines is rounded on its own and only the last line, p - step_size * (m / denom), is one fused operation.
+// Left to the compiler, the four-element form below fuses the moment lines as well (packed fma) and the results differ from the
+// single-range kernels in the last bit; so contraction is off here and the one fused operation is written out.  A decoupled class
+// multiplies p by its decay factor first (one rounding of its own) and has weight_decay == 0 here.
+__device__ __forceinline__ void adam_seg_elem(float& p, float g, float& m_, float& v_, const AdamSegClass& c, float grad_scale) {
+#pragma clang fp contract(off)
+  g = g * grad_scale;
+  if (c.decoupled) p = p * c.decay;
+  if (c.weight_decay != 0.f) g = fmaf(c.weight_decay, p, g);
+  const float m = c.beta1 * m_ + (1.f - c.beta1) * g;
+  const float v = c.beta2 * v_ + (1.f - c.beta2) * g * g;
+  m_ = m;
+  v_ = v;
+  const float denom = sqrtf(v) / c.bc2_sqrt + c.eps;
+  p = fmaf(-c.step_size, m / denom, p);
+}
+
+__device__ __forceinline__ void adam_seg_vec(const AdamSegArgs& a, size_t i, const AdamSegClass& c, float grad_scale) {
+  f32x4 p = *(const f32x4*)(a.p + i), m = *(const f32x4*)(a.m + i), v = *(const f32x4*)(a.v + i);
+  const f32x4 g = *(const f32x4*)(a.g + i);
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    float pk = p[k], mk = m[k], vk = v[k];
+    adam_seg_elem(pk, g[k], mk, vk, c, grad_scale);
+    p[k] = pk; m[k] = mk; v[k] = vk;
+  }
+  *(f32x4*)(a.m + i) = m;
+  *(f32x4*)(a.v + i) = v;
+  *(f32x4*)(a.p + i) = p;
+}
+
+// One launch for every parameter group.  Grid: min(chunks, ADAM_SEG_MAX_GRID) workgroups of 256 threads; a workgroup takes chunks
+// blockIdx.x, + gridDim.x, ... of ADAM_SEG_CHUNK elements, a thread the 4 elements at chunk + 4 * threadIdx.x.  first[chunk] names the
+// first segment that can touch the chunk, so nothing is searched from the table's start:
+//   * no segment reaches into the chunk (a frozen range): the workgroup moves on without touching the arenas;
+//   * one segment covers the whole chunk (nearly every chunk of a real table): every thread takes the 16-byte path with that
+//     segment's class - the branch is uniform and no thread reads the table again;
+//   * otherwise a thread walks on from first[chunk] to its own elements: a vector that lies inside one segment still moves as 16 bytes,
+//     a vector across an edge, in a gap or past n goes element by element, each element under the class of its own segment.
+// The classes sit in LDS (a thread's class index is not uniform at an edge).  Guarded path (a.state): a skipped step returns before
+// the first store; thread c forms class c's step_size / bc2_sqrt by adam_guarded_from_kernel's expressions, once per workgroup.
+// Every element is owned by one thread of one workgroup: no atomics, and the result does not depend on the grid.
+__global__ __launch_bounds__(256) void adam_segmented_kernel(AdamSegArgs a) {
+  __shared__ AdamSegClass cls[ADAM_MAX_CLASSES];
+  if (a.state != nullptr && a.state->found_inf) return;
+  if (threadIdx.x == 0) {
+#pragma unroll
+    for (int c = 0; c < ADAM_MAX_CLASSES; ++c)
+      if (c < a.nclasses) cls[c] = a.cls[c];
+  }
+  __syncthreads();
+  float grad_scale = a.grad_scale;
+  if (a.state != nullptr) {
+    grad_scale = a.state->grad_scale;
+    if ((int)threadIdx.x < a.nclasses) {
+      AdamSegClass& c = cls[threadIdx.x];
+      const long long t = (long long)a.state->applied_steps - c.t0;
+      if (t < 1) {
+        c.active = 0;
+      } else {
+        const double bc1 = 1.0 - pow((double)c.beta1, (double)t), bc2 = 1.0 - pow((double)c.beta2, (double)t);
+        c.step_size = (float)((double)c.lr / bc1);
+        c.bc2_sqrt = (float)sqrt(bc2);
+        c.active = 1;
+      }
+    }
+    __syncthreads();
+  }
+  const long long n = (long long)a.n;
+  for (long long ch = blockIdx.x; ch < a.nchunks; ch += gridDim.x) {
+    const long long c0 = ch * ADAM_SEG_CHUNK, c1 = c0 + ADAM_SEG_CHUNK;
+    int s = a.first[ch];
+    if (s < 0 || s >= a.nsegs) continue;
+    const long long sb = a.segs[s].begin, se = a.segs[s].end;
+    if (sb >= c1) continue;                                   // nothing trainable in this chunk
+    const long long base = c0 + 4 * (long long)threadIdx.x;
+    if (a.vec_ok && sb <= c0 && c1 <= se && se <= n) {        // one segment covers the chunk
+      const AdamSegClass& c = cls[a.segs[s].cls & (ADAM_MAX_CLASSES - 1)];
+      if (c.active) adam_seg_vec(a, (size_t)base, c, grad_scale);
+      continue;
+    }
+    while (s < a.nsegs && a.segs[s].end <= base) ++s;
+    if (s >= a.nsegs) continue;
+    {
+      const long long b = a.segs[s].begin, e = a.segs[s].end;
+      if (a.vec_ok && b <= base && base + 4 <= e && e <= n) {
+        const AdamSegClass& c = cls[a.segs[s].cls & (ADAM_MAX_CLASSES - 1)];
+        if (c.active) adam_seg_vec(a, (size_t)base, c, grad_scale);
+        continue;
+      }
+    }
+    for (int k = 0; k < 4; ++k) {
+      const long long i = base + k;
+      if (i >= n) break;
+      while (s < a.nsegs && a.segs[s].end <= i) ++s;
+      if (s >= a.nsegs) break;
+      if (a.segs[s].begin > i) continue;                      // a gap
+      const AdamSegClass& c = cls[a.segs[s].cls & (ADAM_MAX_CLASSES - 1)];
+      if (!c.active) continue;
+      float p = a.p[i], m = a.m[i], v = a.v[i];
+      adam_seg_elem(p, a.g[i], m, v, c, grad_scale);
+      a.m[i] = m;
+      a.v[i] = v;
+      a.p[i] = p;
+    }
+  }
+}
+
+hipError_t launch_adam_segmented(const AdamSegArgs& a, hipStream_t st) {
+  int grid = a.nchunks < ADAM_SEG_MAX_GRID ? a.nchunks : ADAM_SEG_MAX_GRID;
+  if (grid < 1) grid = 1;
+  hipLaunchKernelGGL(adam_segmented_kernel, dim3(grid), dim3(256), 0, st, a);
   return hipGetLastError();
 }
 

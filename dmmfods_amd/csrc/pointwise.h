@@ -138,6 +138,37 @@ struct GradSumsqArgs {
   double* partials;   // GUARD_PARTIALS doubles; workgroup w owns partials[w]
   int accumulate;     // 0: partials[w] = sum of this range's share; 1: += (a later range of the same step, e.g. the next gradient bucket)
 };
+// ---- segmented Adam: parameter groups in one launch (guard.hip) ----
+constexpr int ADAM_MAX_CLASSES = DMM_ADAM_MAX_CLASSES;
+constexpr int ADAM_SEG_CHUNK = 1024;   // elements per chunk of the table = one 16-byte vector per thread of a workgroup
+constexpr int ADAM_SEG_MAX_GRID = 2048;
+struct AdamSegDev {      // device form of a segment: [begin, end) and its class
+  long long begin, end;
+  int cls, pad;
+};
+struct AdamSegClass {
+  float lr, beta1, beta2, eps;
+  float weight_decay;    // the L2 term's factor: 0 for a decoupled class
+  float decay;           // decoupled: (float)(1 - lr * weight_decay), what p is multiplied by first
+  float step_size, bc2_sqrt;   // plain path: formed on the host; guarded path: formed by the kernel from state->applied_steps - t0
+  long long t0;
+  int decoupled;
+  int active;            // 0: the class's own step count is below 1 - nothing is written
+};
+struct AdamSegArgs {
+  float* p;
+  const float* g;
+  float* m;
+  float* v;
+  size_t n;
+  const AdamSegDev* segs;   // nsegs, sorted, disjoint, inside [0, n)
+  const int* first;         // nchunks: index of the first segment whose end lies behind the chunk's first element (nsegs: none)
+  int nsegs, nchunks, nclasses;
+  int vec_ok;               // the four arenas are 16-byte aligned
+  float grad_scale;         // plain path
+  const dmm_guard_state* state;   // guarded path (else nullptr): found_inf, grad_scale, applied_steps
+  AdamSegClass cls[ADAM_MAX_CLASSES];
+};
 struct GuardFinalizeArgs {
   const double* partials;
   dmm_guard_state* state;
@@ -209,6 +240,7 @@ hipError_t launch_guard_finalize(const GuardFinalizeArgs& a, hipStream_t st);
 hipError_t launch_adam_guarded(const AdamArgs& a, const dmm_guard_state* state, hipStream_t st);  // a.grad_scale / step_size / bc2_sqrt: from *state
 // the same step for a range that became trainable at applied step t0 > 0: its own Adam step count is applied_steps - t0
 hipError_t launch_adam_guarded_from(const AdamArgs& a, const dmm_guard_state* state, float lr, int64_t t0, hipStream_t st);
+hipError_t launch_adam_segmented(const AdamSegArgs& a, hipStream_t st);
 hipError_t launch_guard_init(dmm_guard_state* dev, float scale, int64_t applied, int32_t tracker, hipStream_t st);
 hipError_t launch_apply_corr(const ApplyCorrArgs& a, int dtype, hipStream_t st);
 hipError_t launch_pack(const PackDesc* descs_dev, const int* prefix_dev, int ndesc, int total_rows, int dtype, hipStream_t st,

@@ -11,7 +11,14 @@ Gradient accumulation (model.set_grad_accumulation(True)): zero_grad() clears th
 of the window adds into it, step() closes it.  Neither step changes.  The guarded step reduces over the arena as stored, and the
 dynamic scale S changes only inside step(), so it is constant over a window: the arena holds S x sum_i g_i, the norm that is
 clipped is that of the summed gradient, and one non-finite micro-batch leaves an inf / NaN in the sum - the WHOLE window's step is
-then skipped and S backs off once."""
+then skipped and S backs off once.
+
+Parameter groups (``FusedAdam(model, param_groups=[...])``, as torch.optim.Adam takes them: the released encoder at a lower learning
+rate than the decoder, no weight decay on BatchNorm weights and biases - ``fine_tune_groups``) and decoupled weight decay
+(``decoupled_weight_decay=True``: AdamW's rule).  Groups interleave tensor by tensor in the arena, so the step is ONE launch of the
+segmented kernel (dmm_adam_step_segmented / dmm_adam_step_guarded_segmented) under a device table of (begin, count, class)
+segments; a class is a (group, step origin) pair and carries its hyper-parameters with every call.  Without either keyword the
+optimiser makes exactly the calls it made before there were groups."""
 import ctypes as C
 import math
 
@@ -169,7 +176,7 @@ class DynamicLossScaler:
 
 class FusedAdam:
     def __init__(self, model, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, amsgrad=False, max_grad_norm=None,
-                 loss_scaler=None):
+                 loss_scaler=None, param_groups=None, decoupled_weight_decay=False):
         if amsgrad:
             raise ValueError("amsgrad=True is not supported (reference default False, H:156)")
         if max_grad_norm is not None and not (float(max_grad_norm) > 0 and math.isfinite(float(max_grad_norm))):
@@ -178,7 +185,16 @@ class FusedAdam:
             raise ValueError("loss_scaler must be a DynamicLossScaler")
         self.model = model
         self.defaults = dict(lr=lr, betas=tuple(betas), eps=eps, weight_decay=weight_decay, amsgrad=False)
-        self.param_groups = [dict(self.defaults, params=list(range(sum(1 for _ in model.parameters()))))]
+        self._params = list(model.parameters())
+        # Groups: None and no decoupled decay -> the single-group optimiser as it always was (same entry points, same launches).
+        self._grouped = param_groups is not None or bool(decoupled_weight_decay)
+        if self._grouped:
+            self.defaults["decoupled_weight_decay"] = bool(decoupled_weight_decay)
+            self._build_groups(param_groups)
+        else:
+            self.param_groups = [dict(self.defaults, params=list(range(len(self._params))))]
+            self._torch_index = list(range(len(self._params)))   # arena position -> torch's parameter number
+            self._group_of = [0] * len(self._params)
         self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
         self.loss_scaler = loss_scaler
         # the guarded path's state block: the scaler's, or a private S = 1 one for clipping alone; None = the plain step
@@ -190,12 +206,61 @@ class FusedAdam:
         # Per-parameter step origins (torch.optim.Adam counts steps per parameter): _t0[i] is the applied-step count at which
         # parameter i began to train (its Adam step is count - _t0[i]); None: never trainable so far (no state, as in torch).
         # _frozen_at[i]: the count at which a parameter that has trained was frozen (None: trainable now, or never trained).
-        self._params = list(model.parameters())
         self._t0 = [0 if p.requires_grad else None for p in self._params]
         self._frozen_at = [None] * len(self._params)
         self._sig = tuple(p.requires_grad for p in self._params)
         self._ranges = None
         self._model_sig = None   # the model's own record of the flags (an object replaced on every change) when _ranges was built
+        # grouped only: [begin, count, class] over the arena, the (group, t0) of every class, and the device table built from them
+        self._segments = self._classes = self._table = None
+
+    _GROUP_KEYS = ("lr", "betas", "eps", "weight_decay", "decoupled_weight_decay")
+
+    def _build_groups(self, param_groups):
+        """self.param_groups in torch's form: the live dicts, "params" = torch's numbers (consecutive through the groups, in group
+        order).  Every parameter of the model lies in exactly one group."""
+        if param_groups is None:
+            param_groups = [{"params": list(self._params)}]
+        param_groups = list(param_groups)
+        if not param_groups or not all(isinstance(g, dict) and "params" in g for g in param_groups):
+            raise ValueError("param_groups must be a non-empty list of dicts with a 'params' entry")
+        where = {id(p): i for i, p in enumerate(self._params)}
+        self._torch_index = [None] * len(self._params)
+        self._group_of = [None] * len(self._params)
+        self.param_groups, k = [], 0
+        for gi, g in enumerate(param_groups):
+            # (torch.optim.Adam writes its defaults into the dicts it is given: a list that went through it carries these keys)
+            unknown = set(g) - set(self._GROUP_KEYS) - {"params", "amsgrad", "maximize", "foreach", "capturable", "differentiable", "fused"}
+            if unknown:
+                raise ValueError(f"param group {gi}: unknown key {sorted(unknown)[0]!r}")
+            if g.get("amsgrad"):
+                raise ValueError("amsgrad=True is not supported (reference default False, H:156)")
+            if g.get("maximize"):
+                raise ValueError("maximize=True is not supported")
+            ps = g["params"]
+            ps = [ps] if isinstance(ps, torch.Tensor) else list(ps)
+            if not ps:
+                raise ValueError(f"param group {gi} is empty")
+            own = dict(self.defaults, **{key: g[key] for key in self._GROUP_KEYS if key in g})
+            own["betas"] = tuple(own["betas"])
+            own["decoupled_weight_decay"] = bool(own["decoupled_weight_decay"])
+            own["params"] = []
+            for p in ps:
+                i = where.get(id(p)) if isinstance(p, torch.Tensor) else None
+                if i is None:
+                    raise ValueError(f"param group {gi} holds a tensor that is not a parameter of the model")
+                if self._group_of[i] is not None:
+                    raise ValueError(f"parameter {i} of the model appears in more than one parameter group ({self._group_of[i]} and {gi})")
+                self._group_of[i], self._torch_index[i] = gi, k
+                own["params"].append(k)
+                k += 1
+            self.param_groups.append(own)
+        missing = [i for i, g in enumerate(self._group_of) if g is None]
+        if missing:
+            raise ValueError(f"parameter {missing[0]} of the model is in no parameter group ({len(missing)} are missing): every parameter "
+                             "must be in exactly one")
+        if len(self.param_groups) > _lib.ADAM_MAX_CLASSES:
+            raise ValueError(f"{len(self.param_groups)} parameter groups: the segmented step carries at most {_lib.ADAM_MAX_CLASSES} classes")
 
     # ---- trainable ranges ----
     def _sync_trainable(self, look=True):
@@ -240,6 +305,54 @@ class FusedAdam:
             off += n
         if not self._ranges:
             raise ValueError("no parameter of the model is trainable")
+        if self._grouped:
+            self._build_segments(sig)
+
+    def _build_segments(self, sig):
+        """The segment list of the trainable set: a class is a (group, step origin) pair, adjacent tensors of one class merge.  The
+        device table is built from it at the next step (it needs the arena's device); hyper-parameters are not part of it."""
+        classes, segs, off = {}, [], 0
+        for i, p in enumerate(self._params):
+            n = p.numel()
+            if sig[i] and n:
+                c = classes.setdefault((self._group_of[i], self._t0[i]), len(classes))
+                if segs and segs[-1][0] + segs[-1][1] == off and segs[-1][2] == c:
+                    segs[-1][1] += n
+                else:
+                    segs.append([off, n, c])
+            off += n
+        if len(classes) > _lib.ADAM_MAX_CLASSES:
+            self._ranges = None   # (nothing half-built is kept: the next look raises again)
+            raise ValueError(f"{len(classes)} (parameter group, step origin) classes: the segmented step carries at most {_lib.ADAM_MAX_CLASSES}")
+        self._segments, self._classes, self._table = segs, list(classes), None
+
+    def segments(self):
+        """[(begin, count, group, t0)]: the segments of the grouped step (elements of the arena), None without groups."""
+        self._sync_trainable()
+        if not self._grouped:
+            return None
+        return [(b, n, *self._classes[c]) for b, n, c in self._segments]
+
+    def _ensure_table(self):
+        """The device form of the segment list (dmm_adam_table_init), rebuilt when the trainable set or the arena's device changed."""
+        dev = self.model.param_arena.device
+        if self._table is not None and self._table.device == dev:
+            return self._table
+        L, n, k = _lib.lib(), self.model.param_arena.numel(), len(self._segments)
+        segs = (_lib.AdamSegment * k)(*(_lib.AdamSegment(b, c, cls) for b, c, cls in self._segments))
+        table = torch.empty((L.dmm_adam_table_bytes(k, n) + 7) // 8, dtype=torch.int64, device=dev)
+        _lib.check(L.dmm_adam_table_init(table.data_ptr(), segs, k, n, len(self._classes), _lib.stream_ptr()))
+        self._table = table
+        return table
+
+    def _class_array(self):
+        """The classes of this step, by value: the groups' hyper-parameters as they are NOW (a scheduler writes g["lr"])."""
+        out = (_lib.AdamClass * len(self._classes))()
+        for k, (gi, t0) in enumerate(self._classes):
+            g = self.param_groups[gi]
+            out[k] = _lib.AdamClass(float(g["lr"]), float(g["betas"][0]), float(g["betas"][1]), float(g["eps"]), float(g["weight_decay"]),
+                                    1 if g.get("decoupled_weight_decay") else 0, int(t0))
+        return out
 
     def trainable_ranges(self):
         """[(offset, count, t0)]: the contiguous trainable runs of the arena (elements), each with the applied-step count at which it
@@ -299,6 +412,8 @@ class FusedAdam:
         if self.exp_avg.device != m.param_arena.device:
             self.exp_avg = self.exp_avg.to(m.param_arena.device)
             self.exp_avg_sq = self.exp_avg_sq.to(m.param_arena.device)
+        if self._grouped:
+            return self._step_grouped(grad_scale)
         g = self.param_groups[0]
         if self._guard is not None:
             return self._step_guarded(g, grad_scale)
@@ -309,6 +424,26 @@ class FusedAdam:
                 m.param_arena.data_ptr() + 4 * off, m.grad_arena.data_ptr() + 4 * off, self.exp_avg.data_ptr() + 4 * off,
                 self.exp_avg_sq.data_ptr() + 4 * off, n, float(g["lr"]), float(g["betas"][0]), float(g["betas"][1]), float(g["eps"]),
                 float(g["weight_decay"]), self.step_count - t0, float(grad_scale), _lib.stream_ptr()))
+
+    def _step_grouped(self, grad_scale):
+        """Parameter groups: one segmented Adam launch (guarded: the reductions and the finalize in front of it), whatever the number
+        of groups and frozen ranges."""
+        m, gd, L = self.model, self._guard, _lib.lib()
+        n = m.param_arena.numel()
+        if gd is not None and grad_scale != 1.0:
+            raise ValueError("grad_scale is not available on the guarded path (the loss scaler divides its scale out itself)")
+        self._sync_trainable(look=False)
+        table, classes = self._ensure_table(), self._class_array()
+        arenas = (m.param_arena.data_ptr(), m.grad_arena.data_ptr(), self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(), n,
+                  table.data_ptr(), len(self._segments), classes, len(classes))
+        if gd is None:
+            self.step_count += 1
+            _lib.check(L.dmm_adam_step_segmented(*arenas, self.step_count, float(grad_scale), _lib.stream_ptr()))
+            return
+        state = gd._materialize(m.param_arena.device)
+        scratch = gd._scratch_for(n)
+        _lib.check(L.dmm_adam_step_guarded_segmented(*arenas, float(self.max_grad_norm or 0.0), gd.growth_factor, gd.backoff_factor,
+                                                     gd.growth_interval, state.data_ptr(), scratch.data_ptr(), _lib.stream_ptr()))
 
     def _step_guarded(self, g, grad_scale):
         """Arena reduction -> decision -> Adam, three launches, no host synchronisation.  In a data-parallel job call it after
@@ -344,19 +479,28 @@ class FusedAdam:
             n = p.numel()
             own = self._param_step(i, step_count)   # per parameter, as torch counts; a parameter that never trained has no entry
             if own > 0:
-                state[i] = {"step": torch.tensor(float(own)),
+                state[self._torch_index[i]] = {"step": torch.tensor(float(own)),
                             "exp_avg": self.exp_avg[off:off + n].view(p.shape).clone(),
                             "exp_avg_sq": self.exp_avg_sq[off:off + n].view(p.shape).clone()}
             off += n
-        g = dict(self.param_groups[0])
-        g.update(maximize=False, foreach=None, capturable=False, differentiable=False, fused=None)
-        sd = {"state": state, "param_groups": [g]}
+        groups = []
+        for g in self.param_groups:
+            g = dict(g, params=list(g["params"]))
+            g.update(maximize=False, foreach=None, capturable=False, differentiable=False, fused=None)
+            groups.append(g)
+        sd = {"state": dict(sorted(state.items())), "param_groups": groups}
         if self._guard is not None:   # torch.optim.Adam.load_state_dict ignores a key it does not know
             sd[_STATE_KEY] = self._guard.state_dict()
         return sd
 
     def load_state_dict(self, sd):
         off = 0
+        if self._grouped:   # torch's own check: the same groups, each of the same size
+            theirs = sd["param_groups"]
+            if len(theirs) != len(self.param_groups):
+                raise ValueError(f"loaded state dict has {len(theirs)} parameter groups, the optimiser has {len(self.param_groups)}")
+            if any(len(a["params"]) != len(b["params"]) for a, b in zip(theirs, self.param_groups)):
+                raise ValueError("loaded state dict contains a parameter group that doesn't match the size of optimizer's group")
         steps = [int(float(s["step"])) for s in sd["state"].values()] or [0]
         self.step_count = count = max(steps)
         # step origins from the per-parameter steps: a checkpoint written in one phase resumes in that phase.  A trainable parameter
@@ -365,7 +509,7 @@ class FusedAdam:
         self._ranges = None
         for i, p in enumerate(self.model.parameters()):
             n = p.numel()
-            s = sd["state"].get(i)
+            s = sd["state"].get(self._torch_index[i])
             own = int(float(s["step"])) if s is not None else 0
             self._t0[i] = count - own if (own > 0 or self._sig[i]) else None
             self._frozen_at[i] = count if (own > 0 and not self._sig[i]) else None
@@ -373,8 +517,31 @@ class FusedAdam:
                 self.exp_avg[off:off + n].copy_(s["exp_avg"].reshape(-1))
                 self.exp_avg_sq[off:off + n].copy_(s["exp_avg_sq"].reshape(-1))
             off += n
-        for k in ("lr", "betas", "eps", "weight_decay"):
-            if k in sd["param_groups"][0]:
-                self.param_groups[0][k] = sd["param_groups"][0][k]
+        for mine, theirs in zip(self.param_groups, sd["param_groups"]):   # (without groups: the one group there is)
+            for k in self._GROUP_KEYS if self._grouped else ("lr", "betas", "eps", "weight_decay"):
+                if k in theirs:
+                    mine[k] = tuple(theirs[k]) if k == "betas" and self._grouped else theirs[k]
         if self._guard is not None and sd.get(_STATE_KEY) is not None:   # (a checkpoint of the plain path has none: the scaler keeps its state)
             self._guard.load_state_dict(sd[_STATE_KEY])
+
+
+def fine_tune_groups(model, lr, weight_decay, encoder_lr_scale=1.0, no_decay_norm_bias=False):
+    """Parameter groups of the usual fine-tuning recipe, for ``FusedAdam(model, param_groups=...)`` (or torch.optim.Adam):
+    the encoder - what ``model.freeze_encoder()`` freezes: features, stream_2_features, concat_module - at ``encoder_lr_scale * lr``,
+    and with ``no_decay_norm_bias`` no weight decay on the BatchNorm weights and biases (the DMM_T_BN_WEIGHT / DMM_T_BN_BIAS tensors
+    of the plan's table; the model's convolutions have no bias).  Order: rest, rest without decay, encoder, encoder without decay;
+    with ``encoder_lr_scale == 1`` the encoder is part of "rest"; empty groups are left out."""
+    if not (math.isfinite(float(encoder_lr_scale)) and float(encoder_lr_scale) >= 0):
+        raise ValueError("encoder_lr_scale must be a finite number >= 0")
+    enc = {id(p) for p in model._encoder_params} if float(encoder_lr_scale) != 1.0 else set()
+    kinds = [kind for _, kind, _, _ in model._table if kind <= _lib.T_BN_BIAS]
+    buckets = [[], [], [], []]
+    for (_, p), kind in zip(model._named_params, kinds):
+        norm = no_decay_norm_bias and kind in (_lib.T_BN_WEIGHT, _lib.T_BN_BIAS)
+        buckets[2 * (id(p) in enc) + norm].append(p)
+    groups = []
+    for k, ps in enumerate(buckets):
+        if ps:
+            groups.append({"params": ps, "lr": float(lr) * (float(encoder_lr_scale) if k >= 2 else 1.0),
+                           "weight_decay": 0.0 if k % 2 else float(weight_decay)})
+    return groups

@@ -13,6 +13,10 @@
  *                                          agents/Dense_U_Net_lidar_Agent.py:247-264, utils/...helper.py:311-401
  *   dmm_plan_set_loss / dmm_loss_forward . FocalLoss / ClassWiseFocalLoss  graphs/losses/FocalLoss.py:9-91
  *   dmm_adam_step ........................ torch.optim.Adam.step        agents/Dense_U_Net_lidar_Agent.py:57-61,265
+ *   dmm_adam_table_* / dmm_adam_step_segmented / dmm_adam_step_guarded_segmented
+ *                                          torch.optim.Adam built over PARAMETER GROUPS (the list-of-dicts form of the constructor
+ *                                          called at agents/Dense_U_Net_lidar_Agent.py:57-61) and stepped at :265; the guarded form
+ *                                          adds the rule of dmm_adam_step_guarded, which has nothing upstream
  *   dmm_adam_step_guarded / dmm_guard_* .. nothing upstream (the reference trains in fp32 with a bare Adam, :263-265); the rule is
  *                                          torch.amp.GradScaler's and the clip formula torch.nn.utils.clip_grad_norm_'s
  *   dmm_conv_forward / dmm_conv_wgrad .... single-kernel entry points for unit tests (torch.nn.functional.conv2d,
@@ -197,7 +201,10 @@ int dmm_plan_loss_metrics(dmm_plan* plan, const float* logits, const float* targ
  * overlap needs the bucket events at their place inside the list).  which: 0 training forward, 1 loss + backward. */
 long long dmm_plan_num_graph_replays(const dmm_plan* plan, int which);
 
-/* Flat fused Adam over n fp32 elements (amsgrad unsupported).  step is 1-based. */
+/* Flat fused Adam over n fp32 elements, one parameter group (amsgrad unsupported): torch.optim.Adam's single-tensor arithmetic in
+ * fp32, weight_decay added to the gradient (L2, not decoupled), the bias corrections of `step` (1-based) formed on the host in
+ * double.  Every gradient is multiplied by grad_scale first.  One launch; several groups, or frozen ranges in between: the
+ * segmented calls below. */
 int dmm_adam_step(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, int64_t n, float lr, float beta1,
                   float beta2, float eps, float weight_decay, int64_t step, float grad_scale, void* stream);
 
@@ -257,6 +264,55 @@ int dmm_adam_step_guarded_ranges(float* params, const float* grads, float* exp_a
  * range.  dmm_adam_step_guarded runs it once over the whole arena; a data-parallel trainer can run it per gradient bucket behind
  * that bucket's all-reduce instead (not wired up yet).  Also what the unit tests and the cost measurement call. */
 int dmm_grad_sumsq(const float* grads, int64_t offset, int64_t count, int accumulate, void* scratch, void* stream);
+/* ---- parameter groups: segmented Adam, one launch ----
+ * (torch.optim.Adam over parameter groups, agents/Dense_U_Net_lidar_Agent.py:57-61: each group has its own lr, betas, eps and
+ * weight_decay; torch counts steps per parameter.)
+ * A SEGMENT is a range [begin, begin + count) of the flat arenas (elements) with a class; segments are sorted by begin and disjoint.
+ * Elements in no segment - frozen parameters - are neither read nor written, in params, exp_avg or exp_avg_sq (nor read in grads).
+ * A CLASS is a (parameter group, step origin t0) pair: the hyper-parameters of the group and the applied-step count at which its
+ * parameters began to train, so that a class is at its own step `step - t0`.  A class whose own step is below 1 writes nothing.
+ * At most DMM_ADAM_MAX_CLASSES classes; they travel by value with every launch, so a changed lr needs no new table.
+ * decoupled == 0: dmm_adam_step's arithmetic, expression for expression.  decoupled != 0 (AdamW): the parameter is first multiplied
+ * by (float)(1.0 - (double)lr * weight_decay) and the gradient gets no weight_decay * p term; the rest is identical. */
+#define DMM_ADAM_MAX_CLASSES 16
+typedef struct dmm_adam_segment {
+  int64_t begin, count;   /*  0, 8: elements */
+  int32_t cls;            /* 16: index into the classes of the step call */
+} dmm_adam_segment;       /* 24 bytes */
+typedef struct dmm_adam_class {
+  float lr, beta1, beta2, eps, weight_decay;   /* 0 .. 16 */
+  int32_t decoupled;                           /* 20 */
+  int64_t t0;                                  /* 24 */
+} dmm_adam_class;                              /* 32 bytes */
+/* Bytes of the device form of a table of nsegs segments over arenas of n elements (the segments, and for every chunk of 1024
+ * elements the index of the first segment that reaches into it or lies behind it, so that a workgroup needs no search).
+ * 0 for nsegs < 1 or n < 1. */
+size_t dmm_adam_table_bytes(int nsegs, int64_t n);
+/* Validates the segments on the host and uploads the table to table_dev (caller-owned device memory, 8-byte aligned,
+ * >= dmm_adam_table_bytes(nsegs, n)).  Waits for `stream`, then copies: the upload is COMPLETE when the call returns (segs may be
+ * stack memory), as with the single-kernel entry points.  The library remembers, per table_dev, the sizes and the maximal contiguous
+ * runs of the table it uploaded there; the step calls refuse a table_dev they were not given by this call with the same nsegs and n.
+ * Refuses, before any HIP call: a null or misaligned pointer, nsegs < 1, n < 1, nclasses outside [1, DMM_ADAM_MAX_CLASSES],
+ * count < 1, a segment outside [0, n), unsorted or overlapping segments, cls outside [0, nclasses). */
+int dmm_adam_table_init(void* table_dev, const dmm_adam_segment* segs, int nsegs, int64_t n, int nclasses, void* stream);
+/* ONE launch over the arenas of n elements under the table: a capped grid walks the chunks with a grid-stride loop; a 4-element vector
+ * that lies inside one segment moves with 16-byte loads and stores (when the four arenas are 16-byte aligned), segment edges go
+ * element by element.  step_size and bc2_sqrt of each class are formed as in dmm_adam_step, on the host, in double, for step - t0.
+ * Refuses, before any HIP call: null or misaligned (4-byte) pointers, nsegs < 1, a table_dev not initialised for (nsegs, n),
+ * nclasses outside [1, DMM_ADAM_MAX_CLASSES] or other than the table's, betas outside [0, 1), a NaN or negative lr, eps or
+ * weight_decay, t0 < 0, step < 1. */
+int dmm_adam_step_segmented(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, int64_t n, const void* table_dev,
+                            int nsegs, const dmm_adam_class* classes, int nclasses, int64_t step, float grad_scale, void* stream);
+/* The guarded step (the rule above dmm_guard_state) under a table: one reduction per maximal contiguous run of segments, whatever
+ * their classes (the first assigns the partials, the rest add; nothing frozen: one reduction), ONE finalize fed classes[0]'s lr and
+ * betas - so step_size and bc2_sqrt in the state block describe class 0 at t0 = 0 and are not what the other classes use - and the
+ * one segmented Adam launch, which forms step_size and bc2_sqrt of every class on the device, in fp64, from
+ * state->applied_steps - t0 (the expressions of dmm_adam_step_guarded_ranges), and writes nothing on a skipped step.
+ * Refuses what dmm_adam_step_segmented and dmm_adam_step_guarded refuse (there is no step argument). */
+int dmm_adam_step_guarded_segmented(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, int64_t n,
+                                    const void* table_dev, int nsegs, const dmm_adam_class* classes, int nclasses, float max_norm,
+                                    float growth_factor, float backoff_factor, int32_t growth_interval, dmm_guard_state* state,
+                                    void* scratch, void* stream);
 /* Points the plan's loss kernel and the external-gradient conversion of dmm_plan_backward at a device float (&state->scale):
  * d(loss)/d(logit) is multiplied by loss_scale * (*scale_dev), read on the device when the kernel runs.  NULL = off: the code path
  * and the numbers of a plan that never had one.  Loss sums, metric counts and the unreduced outputs stay unscaled.  Both kernels

@@ -35,6 +35,12 @@
 // DRIVE_FREEZE=1 (life-cycle run and dump): the plan is built with a frozen encoder (dmm_plan_set_encoder_frozen on the unbound plan; a
 // null plan and the bound plan must be refused); the life-cycle run also takes the guarded step over two trainable ranges, one of
 // them released late (dmm_adam_step_guarded_ranges, t0 > 0), and checks that no bucket and no unpack descriptor touches an encoder tensor.
+// DRIVE_GROUPS=1 (life-cycle run): the parameter-group step.  A segment table over the plan's own tensors (BatchNorm tensors one class,
+// convolutions another, the tensors of the first quarter of the arena a third with t0 > 0, the first tensor left out as a gap) goes
+// through dmm_adam_table_init into a heap block of exactly dmm_adam_table_bytes; the uploaded form is checked (segments, and the
+// first-segment index of every chunk against a search); dmm_adam_step_segmented and dmm_adam_step_guarded_segmented run on it; an
+// unsorted table, a class out of range, a table that was never initialised and a wrong nclasses must be refused.
+#include <algorithm>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -242,6 +248,64 @@ static int one_life(const dmm_model_desc& d, int life) {
       MUST(dmm_adam_step_guarded(params, grads, mom1, mom2, np, 1e-3f, 0.9f, 0.999f, 1e-8f, 0.f, 1.0f, 2.f, 0.5f, 2000, gstate, gscratch, st));
       MUST(dmm_grad_sumsq(grads, np / 2, np - np / 2, 1, gscratch, st));
     }
+  }
+  if (getenv("DRIVE_GROUPS")) {
+    std::vector<dmm_adam_segment> segs;
+    bool first_tensor = true;
+    for (const TensorInfo& t : plan->tensors) {
+      if (t.kind > DMM_T_BN_BIAS) continue;
+      int64_t n = 1;
+      for (int k = 0; k < t.ndim; ++k) n *= t.shape[k];
+      if (first_tensor) { first_tensor = false; continue; }   // a gap in front of the first segment
+      const int cls = t.off < np / 4 ? 2 : (t.kind >= DMM_T_BN_WEIGHT ? 1 : 0);
+      if (!segs.empty() && segs.back().begin + segs.back().count == t.off && segs.back().cls == cls) segs.back().count += n;
+      else segs.push_back({t.off, n, cls});
+    }
+    std::sort(segs.begin(), segs.end(), [](const dmm_adam_segment& a, const dmm_adam_segment& b) { return a.begin < b.begin; });
+    const int ns = (int)segs.size();
+    const size_t tb = dmm_adam_table_bytes(ns, np);
+    if (ns < 3 || tb == 0 || dmm_adam_table_bytes(0, np) != 0 || dmm_adam_table_bytes(ns, 0) != 0) { fprintf(stderr, "[drive] dmm_adam_table_bytes\n"); return 2; }
+    uint8_t* table = (uint8_t*)aligned_alloc(8, (tb + 7) / 8 * 8);
+    uint8_t* never = (uint8_t*)aligned_alloc(8, (tb + 7) / 8 * 8);
+    MUST(dmm_adam_table_init(table, segs.data(), ns, np, 3, st));
+    {   // the uploaded form
+      const AdamSegDev* sd = (const AdamSegDev*)table;
+      const int* first = (const int*)(table + (size_t)ns * sizeof(AdamSegDev));
+      for (int i = 0; i < ns; ++i)
+        if (sd[i].begin != segs[i].begin || sd[i].end != segs[i].begin + segs[i].count || sd[i].cls != segs[i].cls) { fprintf(stderr, "[drive] table segment %d\n", i); return 2; }
+      const int64_t nch = (np + ADAM_SEG_CHUNK - 1) / ADAM_SEG_CHUNK;
+      if ((size_t)ns * sizeof(AdamSegDev) + (size_t)nch * sizeof(int) != tb) { fprintf(stderr, "[drive] table size\n"); return 2; }
+      for (int64_t ch = 0; ch < nch; ++ch) {
+        int want = 0;
+        while (want < ns && sd[want].end <= ch * ADAM_SEG_CHUNK) ++want;
+        if (first[ch] != want) { fprintf(stderr, "[drive] first[%lld] = %d, want %d\n", (long long)ch, first[ch], want); return 2; }
+      }
+    }
+    const dmm_adam_class classes[3] = {{1e-3f, 0.9f, 0.999f, 1e-8f, 0.01f, 0, 0}, {1e-3f, 0.9f, 0.999f, 1e-8f, 0.f, 0, 0}, {1e-4f, 0.8f, 0.99f, 1e-6f, 0.1f, 1, 2}};
+    MUST(dmm_adam_step_segmented(params, grads, mom1, mom2, np, table, ns, classes, 3, 1, 1.f, st));
+    MUST(dmm_adam_step_segmented(params, grads, mom1, mom2, np, table, ns, classes, 3, 3, 0.5f, st));
+    if (!dyn) MUST(dmm_guard_state_init(gstate, 1.f, 0, 0, st));
+    MUST(dmm_adam_step_guarded_segmented(params, grads, mom1, mom2, np, table, ns, classes, 3, 1.0f, 2.f, 0.5f, 2000, gstate, gscratch, st));
+    auto refused = [&](int rc, const char* what) {
+      if (rc == DMM_ERR_INVALID) return true;
+      fprintf(stderr, "[drive] %s was not refused (%d)\n", what, rc);
+      return false;
+    };
+    std::vector<dmm_adam_segment> bad = segs;
+    std::swap(bad[0], bad[1]);
+    if (!refused(dmm_adam_table_init(table, bad.data(), ns, np, 3, st), "an unsorted table")) return 2;
+    bad = segs; bad[1].begin = bad[0].begin + bad[0].count - 1;
+    if (!refused(dmm_adam_table_init(table, bad.data(), ns, np, 3, st), "overlapping segments")) return 2;
+    bad = segs; bad[2].cls = 3;
+    if (!refused(dmm_adam_table_init(table, bad.data(), ns, np, 3, st), "a class out of range")) return 2;
+    bad = segs; bad[ns - 1].count = np - bad[ns - 1].begin + 1;
+    if (!refused(dmm_adam_table_init(table, bad.data(), ns, np, 3, st), "a segment past n")) return 2;
+    if (!refused(dmm_adam_step_segmented(params, grads, mom1, mom2, np, never, ns, classes, 3, 1, 1.f, st), "a table never initialised")) return 2;
+    if (!refused(dmm_adam_step_segmented(params, grads, mom1, mom2, np, table, ns, classes, 2, 1, 1.f, st), "another nclasses")) return 2;
+    if (!refused(dmm_adam_step_segmented(params, grads, mom1, mom2, np, table, ns - 1, classes, 3, 1, 1.f, st), "another nsegs")) return 2;
+    if (!refused(dmm_adam_step_segmented(params, grads, mom1, mom2, np, table, ns, classes, 3, 0, 1.f, st), "step 0")) return 2;
+    if (!refused(dmm_adam_step_guarded_segmented(params, grads, mom1, mom2, np, table, ns, classes, 3, 1.0f, 0.5f, 0.5f, 2000, gstate, gscratch, st), "growth_factor < 1")) return 2;
+    free(table); free(never);
   }
   if (dyn && plan->bwd[plan->bce_op].bce.dyn_scale != &gstate->scale) { fprintf(stderr, "[drive] the loss record lost its dynamic scale\n"); return 2; }
   chk_ops(plan->fwd_train); chk_ops(plan->fwd_eval); chk_ops(plan->bwd); chk_descs(plan);
