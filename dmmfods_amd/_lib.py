@@ -146,6 +146,10 @@ def lib():
     L.dmm_conv_dgrad_ex.argtypes = [C.POINTER(ConvDesc), vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_int, vp, vp, vp]
     L.dmm_conv1x1_backward_fused.argtypes = [C.POINTER(ConvDesc), vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_int, vp, vp, vp, vp]
     L.dmm_conv5_wgrad_stats.argtypes = [C.POINTER(ConvDesc), vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.dmm_plan_wgrad_batch_counts.argtypes = [vp, C.POINTER(C.c_longlong * 4)]
+    L.dmm_conv_wgrad_grouped.argtypes = [C.POINTER(ConvDesc), C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_int, C.POINTER(C.c_int), vp]
+    L.dmm_bw1_reduce_grouped.argtypes = [C.c_int, vp, vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int,
+                                         C.POINTER(C.c_int), vp]
     _lib = L
     return L
 
@@ -161,6 +165,7 @@ EXPORTS = [
     "dmm_grad_guard_scratch_bytes", "dmm_guard_state_init", "dmm_adam_step_guarded", "dmm_grad_sumsq", "dmm_plan_set_dynamic_loss_scale",
     "dmm_plan_set_grad_accumulate", "dmm_plan_set_encoder_frozen", "dmm_adam_step_guarded_ranges",
     "dmm_adam_table_bytes", "dmm_adam_table_init", "dmm_adam_step_segmented", "dmm_adam_step_guarded_segmented",
+    "dmm_plan_wgrad_batch_counts", "dmm_conv_wgrad_grouped", "dmm_bw1_reduce_grouped",
 ]
 
 

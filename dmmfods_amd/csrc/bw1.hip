@@ -12,6 +12,7 @@
 // finished in the slot layout the loads came in - the raw x of the ReLU mask is still in the loading thread's registers.
 #include <algorithm>
 #include <cstdio>
+#include <cstring>
 #include <cstdlib>
 #include <type_traits>
 
@@ -466,7 +467,7 @@ hipError_t launch_bw1(const Bw1Args& g0, int dtype, hipStream_t st) {
 
 // dpack slice = sum over the row ranges of the slots; the slots hold zeros for padding channels, which dpack has rows for as well
 // (chunks of 32 channels) up to ceil(wC / 32) chunks: a thread owns 4 consecutive floats of a slice.
-__global__ __launch_bounds__(256) void bw1_reduce_kernel(const float* __restrict__ part, float* __restrict__ dpack, int nct, int nsplit, int nfloats) {
+__device__ __forceinline__ void bw1_reduce_slots(const float* __restrict__ part, float* __restrict__ dpack, int nct, int nsplit, int nfloats) {
   const int e = (blockIdx.x * 256 + threadIdx.x) * 4;  // float index into the packed gradient (all slices)
   if (e >= nct * B1_SLOT_FLOATS) return;
   f32x4 s = {0.f, 0.f, 0.f, 0.f};
@@ -488,15 +489,58 @@ __global__ __launch_bounds__(256) void bw1_reduce_kernel(const float* __restrict
   for (; k < nsplit; ++k) s += *(const f32x4*)(p + (size_t)k * pitch);
   if (e < nfloats) *(f32x4*)(dpack + e) = s;
 }
+__global__ __launch_bounds__(256) void bw1_reduce_kernel(const float* __restrict__ part, float* __restrict__ dpack, int nct, int nsplit, int nfloats) {
+  bw1_reduce_slots(part, dpack, nct, nsplit, nfloats);
+}
+// The grouped form: blockIdx.y = member, each with its own slots, split and packed gradient; gridDim.x covers the largest member and
+// the surplus workgroups of a smaller one return at once.  The table travels in the kernel argument.
+struct Bw1RedGroupArgs { Bw1RedMember m[B1_RED_GROUP_MAX]; };
+static_assert(sizeof(Bw1RedMember) % 8 == 0, "members are read with aligned scalar loads");
+__global__ __launch_bounds__(256) void bw1_reduce_group_kernel(const Bw1RedGroupArgs g) {
+  const Bw1RedMember& m = g.m[blockIdx.y];
+  bw1_reduce_slots(m.part, m.dpack, m.nct, m.nsplit, m.nfloats);
+}
+
+// What the reduction of `g` adds up (false: nothing - the fused launch added into dpack itself)
+static bool bw1_reduce_member(const Bw1Args& g, Bw1RedMember& m) {
+  const ConvArgs& a = g.c;
+  if (a.M <= 0) return false;
+  const Bw1Geom q = bw1_geometry(a);
+  if (!bw1_uses_part(g, q)) return false;
+  m.part = g.part; m.dpack = g.dpack; m.nct = q.nct; m.nsplit = q.nsplit;
+  m.nfloats = ((g.wC + 31) / 32) * g.dNpad * 32;  // size of dpack
+  return true;
+}
+
+hipError_t launch_bw1_reduce_member(const Bw1RedMember& m, hipStream_t st) {
+  const int nthreads = m.nct * B1_SLOT_FLOATS / 4;
+  hipLaunchKernelGGL(bw1_reduce_kernel, dim3((nthreads + 255) / 256), dim3(256), 0, st, m.part, m.dpack, m.nct, m.nsplit, m.nfloats);
+  return hipGetLastError();
+}
 
 hipError_t launch_bw1_reduce(const Bw1Args& g, hipStream_t st) {
-  const ConvArgs& a = g.c;
-  if (a.M <= 0) return hipSuccess;
-  const Bw1Geom q = bw1_geometry(a);
-  if (!bw1_uses_part(g, q)) return hipSuccess;  // the fused launch added into dpack itself
-  const int nfloats = ((g.wC + 31) / 32) * g.dNpad * 32;  // size of dpack
-  const int nthreads = q.nct * B1_SLOT_FLOATS / 4;
-  hipLaunchKernelGGL(bw1_reduce_kernel, dim3((nthreads + 255) / 256), dim3(256), 0, st, g.part, g.dpack, q.nct, q.nsplit, nfloats);
+  Bw1RedMember m;
+  if (!bw1_reduce_member(g, m)) return hipSuccess;
+  return launch_bw1_reduce_member(m, st);
+}
+
+bool bw1_reduce_group_add(Bw1RedGroup& G, const Bw1Args& g) {
+  Bw1RedMember m;
+  if (!bw1_reduce_member(g, m)) return true;  // nothing to add up
+  if (G.n >= B1_RED_GROUP_MAX) return false;
+  G.m[G.n++] = m;
+  return true;
+}
+
+hipError_t bw1_reduce_group_launch(Bw1RedGroup& G, hipStream_t st) {
+  if (G.n <= 0) return hipSuccess;
+  Bw1RedGroupArgs a;
+  memset(&a, 0, sizeof(a));
+  int nct = 0;
+  for (int i = 0; i < G.n; ++i) { a.m[i] = G.m[i]; nct = std::max(nct, G.m[i].nct); }
+  const int n = G.n;
+  G.n = 0;
+  hipLaunchKernelGGL(bw1_reduce_group_kernel, dim3((nct * (B1_SLOT_FLOATS / 4) + 255) / 256, n), dim3(256), 0, st, a);
   return hipGetLastError();
 }
 

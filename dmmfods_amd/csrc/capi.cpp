@@ -36,6 +36,10 @@ static int fail(int code, const std::string& msg) {
 static bool g_overlap_wgrad = getenv("DMM_NO_OVERLAP") == nullptr;
 static int g_graph = getenv("DMM_GRAPH") ? std::max(1, atoi(getenv("DMM_GRAPH"))) : 0;  // off by default: see launch_list (1: both lists, 2: the forward list only)
 static unsigned long long g_option_epoch = 1;  // bumped by every dmm_set_option: captured graphs have the options of their time baked in
+// Launch coalescing in run_ops: the dense 3x3 weight gradients (wg3) and the bw1 reductions of consecutive layers go out as grouped
+// launches.  dmm_set_option("batch_wgrad"): 0 every record is its own launch, as before the option existed; 1 (default) grouped, on
+// the CALLER's stream; 2 grouped, on the weight-gradient stream where the single launches run
+static int g_batch_wgrad = 1;
 static int g_bucket_mb = getenv("DMM_GRAD_BUCKET_MB") ? atoi(getenv("DMM_GRAD_BUCKET_MB")) : 25;
 // The kernel families switched off for the process, 1 << family (dmm_set_option; a lab build starts from its DMM_NO_* flags).  The one
 // switch there is: a plan copies it into dmm_plan::deny in front of each builder pass, a single-kernel entry point passes it at every call.
@@ -134,6 +138,11 @@ int dmm_set_option(const char* name, int value) {
   ++g_option_epoch;
   if (std::string(name) == "overlap_wgrad") { g_overlap_wgrad = value != 0; return DMM_OK; }
   if (std::string(name) == "graph") { g_graph = value; return DMM_OK; }
+  if (std::string(name) == "batch_wgrad") {
+    if (value < 0 || value > 2) return fail(DMM_ERR_INVALID, "batch_wgrad must be 0, 1 or 2");
+    g_batch_wgrad = value;
+    return DMM_OK;
+  }
   for (const auto& o : kFamilyOptions)
     if (std::string(name) == o.option) {
       if (value != 0) g_family_off &= ~(1u << o.family);
@@ -353,6 +362,50 @@ static int run_ops(dmm_plan* p, std::vector<Op>& ops, hipStream_t st, int prof_w
   };
   auto join = [&]() { join_side(); join_pack(); };
   // DMM_HOST_PROF=1: host time of the enqueue calls by op kind, printed when a list has run 20 times (tools/host_bound.py)
+  // Launch coalescing.  Within a dense block every dense 3x3 weight gradient reads only its own compact gradient, y1 and
+  // norm2 constants and writes its own packed gradient, and every bw1 reduction its own slots: consecutive ones are handed to ONE
+  // grouped launch (wg3.hip wg3_group_kernel, bw1.hip bw1_reduce_group_kernel).  A record that joins a batch is ordered behind its
+  // producer as before (fork event, stream wait) and notes its family; the launch goes out at the flush.  A batch is flushed
+  //   * before any other record of the weight-gradient side, before a join with that side, before a record that carries a bucket
+  //     signal (such a record is never batched) and at the end of the range;
+  //   * when a member does not fit (kernel instantiation, member cap, no workgroup left);
+  //   * wg3, lab builds only: as soon as the pending tiles reach DMM_WG3_BATCH_TILES.  Measured on the caller's stream (C2, profiles/r06/
+  //     ablations.txt): 2048 / 4096 / 8192 / 16384 tiles / no threshold = 25.00 / 24.88 / 24.78 / 24.78 / 24.71 ms per step against
+  //     25.13 ungrouped - a dense block's layers go out together whatever their map size, hence no threshold (0).
+  // "Weight-gradient side" is decided from the record alone, not from the streams of this call: the batches - and the bits - are the
+  // same with overlap_wgrad on or off, under capture and in a profile pass.  There the flushing member's event pair brackets the
+  // grouped launch, the other members record an empty pair.
+  const bool batch = g_batch_wgrad != 0;
+  static const long long w3_batch_tiles = lab_int("DMM_WG3_BATCH_TILES", 0);
+  Wg3Group w3g;
+  Bw1RedGroup rdg;
+  std::vector<size_t> w3_members, rd_members;
+  // The stream of the grouped launches.  They fill the chip on their own (a workgroup per compute unit, 8 waves and 86 KB of LDS
+  // each), so beside the data-gradient chain they do not fill its gaps, they hold its launches up: measured at C2 (profiles/r06),
+  // grouped on the weight-gradient stream the step is 0.1-0.2 ms SLOWER than the ungrouped launches there, on the caller's
+  // stream 0.2 ms faster.  Hence the caller's stream (batch_wgrad 1): the records of the two kinds then need no fork event either -
+  // also the ones that are launched alone (a bucket signal), which share the family's slot buffer with the batches.
+  const bool batch_main = g_batch_wgrad == 1;
+  hipStream_t batch_st = (overlap && !batch_main) ? side_st : st;
+  auto flush_members = [&](std::vector<size_t>& members, auto&& launch) -> hipError_t {
+    if (members.empty()) return hipSuccess;
+    for (size_t k = 0; k + 1 < members.size(); ++k)
+      if (selected(ops[members[k]])) {
+        hipEventRecord((hipEvent_t)(*evs)[2 * (ev_offset + members[k])], batch_st);
+        hipEventRecord((hipEvent_t)(*evs)[2 * (ev_offset + members[k]) + 1], batch_st);
+      }
+    const size_t last = members.back();
+    const bool sel_last = selected(ops[last]);
+    members.clear();
+    if (sel_last) hipEventRecord((hipEvent_t)(*evs)[2 * (ev_offset + last)], batch_st);
+    const hipError_t fe = launch();
+    if (sel_last) hipEventRecord((hipEvent_t)(*evs)[2 * (ev_offset + last) + 1], batch_st);
+    return fe;
+  };
+  auto flush_w3 = [&]() { return flush_members(w3_members, [&] { ++p->batch_counts[0]; return wg3_group_launch(w3g, batch_st); }); };
+  auto flush_rd = [&]() { return flush_members(rd_members, [&] { ++p->batch_counts[2]; return bw1_reduce_group_launch(rdg, batch_st); }); };
+  auto flush_all = [&]() { const hipError_t e1 = flush_w3(), e2 = flush_rd(); return e1 != hipSuccess ? e1 : e2; };
+  auto flush_failed = [&](hipError_t fe) { join(); return fail(DMM_ERR_HIP, std::string("grouped weight-gradient launch: ") + hipGetErrorString(fe)); };
   static const bool host_prof = lab_flag("DMM_HOST_PROF");
   static double hp_launch[32] = {0}, hp_fork[32] = {0};
   static long hp_n[32] = {0}, hp_lists = 0;
@@ -362,6 +415,27 @@ static int run_ops(dmm_plan* p, std::vector<Op>& ops, hipStream_t st, int prof_w
     hipError_t e = hipSuccess;
     const double hp_t0 = host_prof ? now() : 0.0;
     double hp_t1 = hp_t0;
+    // a record of the weight-gradient side that forks from the main stream; does it join a batch?
+    const bool forks = !o.chain && o.leaf != 2 && o.leaf != 3 && (o.kind == OP_WGRAD || o.leaf);
+    bool as_w3 = false, as_rd = false;
+    if (batch && forks && o.signal < 0) {
+      if (o.kind == OP_WGRAD && o.impl == IMPL_WG3 && mfma) {
+        as_w3 = wg3_group_add(w3g, o.w, dt);
+        if (!as_w3 && w3g.n > 0) {  // it does not fit: the batch goes first
+          if ((e = flush_w3()) != hipSuccess) return flush_failed(e);
+          as_w3 = wg3_group_add(w3g, o.w, dt);
+        }
+      } else if (o.kind == OP_BW1RED) {
+        as_rd = bw1_reduce_group_add(rdg, o.b1);
+        if (!as_rd) {
+          if ((e = flush_rd()) != hipSuccess) return flush_failed(e);
+          as_rd = bw1_reduce_group_add(rdg, o.b1);
+        }
+      }
+    }
+    const bool rd_added = as_rd && rdg.n > (int)rd_members.size();   // (false: a record without slots, nothing to add up)
+    if (!as_w3 && !as_rd && (forks || o.leaf == 3 || o.signal >= 0 || (o.kind == OP_JOIN && o.epi != 1)))
+      if ((e = flush_all()) != hipSuccess) return flush_failed(e);
     // side-stream launches: weight gradients and the leaves of the backward graph (stem, raw-input branches)
     hipStream_t lst = st;
     if (overlap && o.leaf == 3 && forked) {
@@ -370,6 +444,8 @@ static int run_ops(dmm_plan* p, std::vector<Op>& ops, hipStream_t st, int prof_w
       // the side stream is forked in THIS call: a range that starts mid-chain, or a join inside the chain, makes the next launch
       // of the chain fork again like any leaf.
       lst = side_st;
+    } else if (batch_main && forks && ((o.kind == OP_WGRAD && o.impl == IMPL_WG3) || o.kind == OP_BW1RED)) {
+      // (on the caller's stream, behind its producer: no fork)
     } else if (overlap && !o.chain && (o.kind == OP_WGRAD || o.leaf)) {
       if (nfork >= p->fork_events.size()) {
         hipEvent_t fe = pool_event(dp, false);
@@ -383,7 +459,7 @@ static int run_ops(dmm_plan* p, std::vector<Op>& ops, hipStream_t st, int prof_w
       if (o.leaf == 2) pack_pending = true; else forked = true;
       if (host_prof) hp_t1 = now();
     }
-    const bool sel = selected(o);
+    const bool sel = selected(o) && !as_w3 && !rd_added;   // (a batch member's pair is recorded at the flush)
     if (sel) hipEventRecord((hipEvent_t)(*evs)[2 * (ev_offset + i)], lst);
     // the families noted by THIS launch: the thread's mask is set aside, read behind the launch and merged back (family_check)
     const bool fam_check = (o.kind == OP_IGEMM || o.kind == OP_WGRAD) && o.impl != IMPL_AUTO;
@@ -394,9 +470,17 @@ static int run_ops(dmm_plan* p, std::vector<Op>& ops, hipStream_t st, int prof_w
       case OP_COPY: e = hipMemcpyAsync(o.cp.dst, o.cp.src, o.cp.bytes, hipMemcpyDeviceToDevice, lst); break;
       case OP_CONVERT: e = launch_convert_input(o.cv, dt, lst); break;
       case OP_IGEMM: e = launch_igemm(o.c, dt, o.epi, mfma, lst, o.impl); break;
-      case OP_WGRAD: e = launch_wgrad(o.w, dt, mfma, lst, o.impl); break;
+      case OP_WGRAD:
+        if (as_w3) { note_impl(IMPL_WG3); w3_members.push_back(i); ++p->batch_counts[1]; break; }
+        if (o.impl == IMPL_WG3 && o.w.M > 0) { ++p->batch_counts[0]; ++p->batch_counts[1]; }
+        e = launch_wgrad(o.w, dt, mfma, lst, o.impl);
+        break;
       case OP_BW1: e = launch_bw1(o.b1, dt, lst); break;
-      case OP_BW1RED: e = launch_bw1_reduce(o.b1, lst); break;
+      case OP_BW1RED:
+        if (as_rd) { if (rd_added) { rd_members.push_back(i); ++p->batch_counts[3]; } break; }
+        { Bw1RedGroup one; if (bw1_reduce_group_add(one, o.b1) && one.n > 0) { ++p->batch_counts[2]; ++p->batch_counts[3]; } }
+        e = launch_bw1_reduce(o.b1, lst);
+        break;
       case OP_RAWFIN: e = launch_wg5_rawfin(o.rf, lst); break;
       case OP_FIN64: e = launch_wg5_fin64(o.f64, lst); break;
       case OP_JOIN: if (o.epi == 1) join_pack(); else join_side(); break;  // the main stream waits for what the side (epi 1: pack) stream has been given so far
@@ -424,6 +508,7 @@ static int run_ops(dmm_plan* p, std::vector<Op>& ops, hipStream_t st, int prof_w
       if (!why.empty()) { join(); return fail(DMM_ERR_STATE, why); }
     }
     if (sel) hipEventRecord((hipEvent_t)(*evs)[2 * (ev_offset + i) + 1], lst);
+    if (as_w3 && w3_batch_tiles > 0 && w3g.tiles >= w3_batch_tiles && (e = flush_w3()) != hipSuccess) return flush_failed(e);
     if (pack_pending && o.leaf == 2) hipEventRecord((hipEvent_t)p->join_events[nside], lst);
     if (o.signal >= 0 && !capturing) {  // a gradient bucket is final on this stream from here on
       while ((int)p->bucket_events.size() <= o.signal) {
@@ -433,6 +518,10 @@ static int run_ops(dmm_plan* p, std::vector<Op>& ops, hipStream_t st, int prof_w
       }
       hipEventRecord((hipEvent_t)p->bucket_events[o.signal], lst);
     }
+  }
+  {
+    const hipError_t fe = flush_all();
+    if (fe != hipSuccess) return flush_failed(fe);
   }
   join();
   if (host_prof && ++hp_lists == 40) {
@@ -607,6 +696,12 @@ int dmm_plan_backward(dmm_plan* plan, const float* dlogits, void* stream) {
   if (rc) return rc;
   HIPCHK(launch_convert_input(cv, plan->desc.dtype, st));
   return run_ops(plan, plan->bwd, st, -1, (size_t)plan->bce_op + 1, 0);
+}
+
+int dmm_plan_wgrad_batch_counts(const dmm_plan* plan, long long counts[4]) {
+  if (!plan || !counts) return fail(DMM_ERR_INVALID, "null argument");
+  for (int i = 0; i < 4; ++i) counts[i] = plan->batch_counts[i];
+  return DMM_OK;
 }
 
 long long dmm_plan_num_graph_replays(const dmm_plan* plan, int which) {
@@ -1179,6 +1274,45 @@ static PackDesc dgrad_pack_desc(const dmm_conv_desc* d, const OneConv& g, const 
   return pd;
 }
 
+// The transposed form of a unit-stride multi-tap convolution's weight gradient (taps on the gradient side: wgrad.hip "transposed
+// form", what the plan builds for thin outputs: plan.cpp finish_conv): lays the packed gradient and its descriptor out in `scratch`,
+// uploads them and fills the launch `a`.  The result has the shape of the data-gradient pack and is scattered into the master layout
+// through that descriptor (dd, dp; `rows` rows).
+static int thin_wgrad_setup(const dmm_conv_desc* d, const OneConv& g, const void* x, const void* dy, const float* scale, const float* shift,
+                            const void* yfwd, const float* q, const float* r, float* dw, void* scratch, hipStream_t st, WgradArgs& a,
+                            PackDesc*& dd, int*& dp, int& rows) {
+  const std::vector<Tap> taps = taps_conv_dgrad(d->R, d->S, d->pad);
+  const int cs = g.Cst;
+  const int npad = rup(cs, cs >= 384 || cs % 128 == 0 ? 128 : (cs >= 64 ? 64 : 32));
+  Scratch S{(uint8_t*)scratch};
+  dd = (PackDesc*)S.take(sizeof(PackDesc));
+  dp = (int*)S.take(sizeof(int));
+  float* zeros = (float*)S.take((size_t)rup(d->Cout, 8) * sizeof(float) + 64);
+  PackDesc pd = dgrad_pack_desc(d, g, taps, dw, npad);
+  const size_t elems = (size_t)pd.seg[0].nchunks * pd.Npad * g.BK;
+  pd.dpack = (float*)S.take(elems * sizeof(float));
+  pd.gw = dw;
+  if (S.off > dmm_conv_scratch_bytes(d)) return fail(DMM_ERR_INVALID, "scratch too small");
+  HIPCHK(hipMemsetAsync(scratch, 0, S.off, st));
+  int zero = 0;
+  HIPCHK(upload(dd, &pd, sizeof(pd), st));
+  HIPCHK(upload(dp, &zero, sizeof(int), st));
+  HIPCHK(hipStreamSynchronize(st));
+  memset(&a, 0, sizeof(a));
+  a.nseg = 1;
+  Seg& sq = a.seg[0];  // Q: the output gradient under the flipped taps
+  sq.src = dy; sq.ld = d->Cout; sq.Hs = g.Hout; sq.Ws = g.Wout; sq.C = rup(d->Cout, 8); sq.Cpad = sq.C; sq.mode = G_PLAIN; sq.istride = 1;
+  set_eff_grad(sq, yfwd, d->Cout, q, r, zeros);
+  fill_seg_taps(sq, taps, g.BK);
+  a.B = d->B; a.Ho = g.Ho; a.Wo = g.Wo; a.M = d->B * g.Ho * g.Wo;
+  fill_one_seg(a.dy, d, g, x, scale, shift, taps_conv(1, 1, 0));  // P: the activated input, once
+  a.dy.istride = 1;
+  a.N = g.Cst; a.Npad = pd.Npad;
+  a.dpack = (float*)pd.dpack;
+  rows = pd.seg[0].nchunks * pd.Npad;
+  return DMM_OK;
+}
+
 int dmm_conv_wgrad_ex(const dmm_conv_desc* d, const void* x, const void* dy, const float* scale, const float* shift, const void* yfwd,
                       const float* q, const float* r, int transposed_form, float* dw, void* scratch, void* stream) {
   OneConv g;
@@ -1191,35 +1325,10 @@ int dmm_conv_wgrad_ex(const dmm_conv_desc* d, const void* x, const void* dy, con
     // the result has the shape of the data-gradient pack and is scattered into the master layout through that descriptor
     if (d->transposed || d->mode != 0 || d->stride != 1 || d->R * d->S <= 1 || !d->bn_relu)
       return fail(DMM_ERR_INVALID, "the transposed form serves unit-stride multi-tap convolutions behind BN+ReLU");
-    const std::vector<Tap> taps = taps_conv_dgrad(d->R, d->S, d->pad);
-    const int cs = g.Cst;
-    const int npad = rup(cs, cs >= 384 || cs % 128 == 0 ? 128 : (cs >= 64 ? 64 : 32));
-    Scratch S{(uint8_t*)scratch};
-    PackDesc* dd = (PackDesc*)S.take(sizeof(PackDesc));
-    int* dp = (int*)S.take(sizeof(int));
-    float* zeros = (float*)S.take((size_t)rup(d->Cout, 8) * sizeof(float) + 64);
-    PackDesc pd = dgrad_pack_desc(d, g, taps, dw, npad);
-    const size_t elems = (size_t)pd.seg[0].nchunks * pd.Npad * g.BK;
-    pd.dpack = (float*)S.take(elems * sizeof(float));
-    pd.gw = dw;
-    if (S.off > dmm_conv_scratch_bytes(d)) return fail(DMM_ERR_INVALID, "scratch too small");
-    HIPCHK(hipMemsetAsync(scratch, 0, S.off, st));
-    int zero = 0;
-    HIPCHK(upload(dd, &pd, sizeof(pd), st));
-    HIPCHK(upload(dp, &zero, sizeof(int), st));
-    HIPCHK(hipStreamSynchronize(st));
     WgradArgs a;
-    memset(&a, 0, sizeof(a));
-    a.nseg = 1;
-    Seg& sq = a.seg[0];  // Q: the output gradient under the flipped taps
-    sq.src = dy; sq.ld = d->Cout; sq.Hs = g.Hout; sq.Ws = g.Wout; sq.C = rup(d->Cout, 8); sq.Cpad = sq.C; sq.mode = G_PLAIN; sq.istride = 1;
-    set_eff_grad(sq, yfwd, d->Cout, q, r, zeros);
-    fill_seg_taps(sq, taps, g.BK);
-    a.B = d->B; a.Ho = g.Ho; a.Wo = g.Wo; a.M = d->B * g.Ho * g.Wo;
-    fill_one_seg(a.dy, d, g, x, scale, shift, taps_conv(1, 1, 0));  // P: the activated input, once
-    a.dy.istride = 1;
-    a.N = g.Cst; a.Npad = pd.Npad;
-    a.dpack = (float*)pd.dpack;
+    PackDesc* dd; int* dp; int rows;
+    const int rc = thin_wgrad_setup(d, g, x, dy, scale, shift, yfwd, q, r, dw, scratch, st, a, dd, dp, rows);
+    if (rc) return rc;
     void* part = nullptr;
     Resolved wg3;
     const unsigned deny = g_family_off;
@@ -1232,7 +1341,7 @@ int dmm_conv_wgrad_ex(const dmm_conv_desc* d, const void* x, const void* dy, con
     if (part != nullptr) hipFreeAsync(part, st);
     HIPCHK(e1);
     HIPCHK(hipMemsetAsync(dw, 0, wn * sizeof(float), st));
-    HIPCHK(launch_unpack(dd, dp, 1, pd.seg[0].nchunks * pd.Npad, d->dtype, 1.0f, st));
+    HIPCHK(launch_unpack(dd, dp, 1, rows, d->dtype, 1.0f, st));
     return DMM_OK;
   }
   std::vector<PackDesc> packs;
@@ -1435,6 +1544,76 @@ int dmm_conv1x1_backward_fused(const dmm_conv_desc* d, const void* x, const void
   const size_t wn = (size_t)d->Cin * d->Cout;
   HIPCHK(hipMemsetAsync(dw, 0, wn * sizeof(float), st));
   HIPCHK(launch_unpack(dd, dp, (int)packs.size(), total_rows, d->dtype, 1.0f, st));
+  return DMM_OK;
+}
+
+int dmm_conv_wgrad_grouped(const dmm_conv_desc* descs, int n, const void* const* x, const void* const* dy, const float* const* scale,
+                           const float* const* shift, const void* const* yfwd, const float* const* q, const float* const* r,
+                           float* const* dw, void* const* scratch, int grouped, int* launches, void* stream) {
+  if (!descs || n < 1 || !x || !dy || !scale || !shift || !dw || !scratch) return fail(DMM_ERR_INVALID, "null argument");
+  hipStream_t st = (hipStream_t)stream;
+  struct One { WgradArgs a; PackDesc* dd; int* dp; int rows; };
+  std::vector<One> v((size_t)n);
+  for (int i = 0; i < n; ++i) {
+    const dmm_conv_desc* d = &descs[i];
+    OneConv g;
+    if (!geometry(d, g)) return fail(DMM_ERR_INVALID, "unsupported conv descriptor");
+    const void* yf = yfwd ? yfwd[i] : nullptr;
+    const float *qi = q ? q[i] : nullptr, *ri = r ? r[i] : nullptr;
+    if ((qi != nullptr) != (ri != nullptr) || (qi != nullptr && yf == nullptr)) return fail(DMM_ERR_INVALID, "q, r and yfwd come together");
+    if (d->transposed || d->mode != 0 || d->stride != 1 || d->R * d->S <= 1 || !d->bn_relu || !d->use_mfma)
+      return fail(DMM_ERR_INVALID, "the transposed form serves unit-stride multi-tap convolutions behind BN+ReLU");
+    const int rc = thin_wgrad_setup(d, g, x[i], dy[i], scale[i], shift[i], yf, qi, ri, dw[i], scratch[i], st, v[i].a, v[i].dd, v[i].dp, v[i].rows);
+    if (rc) return rc;
+    Resolved res;
+    if (!wg3_resolve(v[i].a, d->dtype, res)) return fail(DMM_ERR_INVALID, "not a launch wg3.hip takes (16-bit storage, 128 -> 32 channels, 3x3)");
+  }
+  void* part = nullptr;   // one slot buffer for all of them, as in a plan
+  HIPCHK(hipMallocAsync(&part, (size_t)W3_MAX_SLOTS * W3_SLOT_FLOATS * sizeof(float), st));
+  for (One& o : v) { o.a.part = (float*)part; o.a.part_slots = W3_MAX_SLOTS; }
+  hipError_t e = hipSuccess;
+  int nl = 0;
+  if (grouped) {
+    Wg3Group G;
+    for (int i = 0; i < n && e == hipSuccess; ++i) {
+      if (wg3_group_add(G, v[i].a, descs[i].dtype)) continue;
+      if (G.n > 0) { e = wg3_group_launch(G, st); ++nl; }
+      if (e == hipSuccess && !wg3_group_add(G, v[i].a, descs[i].dtype)) e = hipErrorNotSupported;
+    }
+    if (e == hipSuccess && G.n > 0) { e = wg3_group_launch(G, st); ++nl; }
+    if (e == hipSuccess) note_impl(IMPL_WG3);
+  } else {
+    for (int i = 0; i < n && e == hipSuccess; ++i, ++nl) e = launch_wgrad(v[i].a, descs[i].dtype, true, st, IMPL_WG3);
+  }
+  hipFreeAsync(part, st);
+  HIPCHK(e);
+  for (int i = 0; i < n; ++i) {
+    const dmm_conv_desc* d = &descs[i];
+    HIPCHK(hipMemsetAsync(dw[i], 0, (size_t)d->Cin * d->Cout * d->R * d->S * sizeof(float), st));
+    HIPCHK(launch_unpack(v[i].dd, v[i].dp, 1, v[i].rows, d->dtype, 1.0f, st));
+  }
+  if (launches) *launches = nl;
+  return DMM_OK;
+}
+
+int dmm_bw1_reduce_grouped(int n, const float* const* part, float* const* dpack, const int* nct, const int* nsplit, const int* wc,
+                           int grouped, int* launches, void* stream) {
+  if (n < 1 || !part || !dpack || !nct || !nsplit || !wc) return fail(DMM_ERR_INVALID, "null argument");
+  hipStream_t st = (hipStream_t)stream;
+  Bw1RedGroup G;
+  int nl = 0;
+  for (int i = 0; i < n; ++i) {
+    if (!part[i] || !dpack[i] || nct[i] < 1 || nsplit[i] < 1 || wc[i] < 1 || wc[i] > nct[i] * 128 || wc[i] <= (nct[i] - 1) * 128)
+      return fail(DMM_ERR_INVALID, "a member needs slots, a packed gradient, nct, nsplit >= 1 and (nct - 1) * 128 < wc <= nct * 128");
+    Bw1RedMember m;
+    m.part = part[i]; m.dpack = dpack[i]; m.nct = nct[i]; m.nsplit = nsplit[i];
+    m.nfloats = ((wc[i] + 31) / 32) * 128 * 32;
+    if (!grouped) { HIPCHK(launch_bw1_reduce_member(m, st)); ++nl; continue; }
+    if (G.n >= B1_RED_GROUP_MAX) { HIPCHK(bw1_reduce_group_launch(G, st)); ++nl; }
+    G.m[G.n++] = m;
+  }
+  if (G.n > 0) { HIPCHK(bw1_reduce_group_launch(G, st)); ++nl; }
+  if (launches) *launches = nl;
   return DMM_OK;
 }
 

@@ -182,4 +182,7 @@ struct dmm_plan {
   bool dp_used = false;          // a data-parallel reducer waits for bucket events: backward stays eager (events must be real)
   unsigned long long graph_clock = 0;
   long long graph_replays[2] = {0, 0};
+  // launch coalescing (capi.cpp run_ops), summed over the plan's life: [0] wg3 launches (a grouped launch counts once; each comes with one
+  // reduction), [1] the wg3 records they served, [2] bw1 reduction launches, [3] the bw1.reduce records they served (dmm_plan_wgrad_batch_counts)
+  long long batch_counts[4] = {0, 0, 0, 0};
 };

@@ -220,6 +220,25 @@ constexpr int B1_SLOT_FLOATS = 4 * 128 * 32;  // one workgroup's slice: 4 chunks
 bool bw1_eligible(const WgradArgs& w, const ConvArgs& d, int dtype, unsigned deny);  // deny: as igemm_pick
 hipError_t launch_bw1(const Bw1Args& g, int dtype, hipStream_t st);
 hipError_t launch_bw1_reduce(const Bw1Args& g, hipStream_t st);  // dpack = sum of the slots (no-op without `part`)
+// Grouped launches (capi.cpp run_ops hands consecutive independent launches of a dense block over together).
+// bw1.hip: the reductions of up to B1_RED_GROUP_MAX fused launches as ONE launch (gridDim.y = member); each member is added up exactly
+// as launch_bw1_reduce does it alone - the same loads and additions in the same order.
+constexpr int B1_RED_GROUP_MAX = 32;
+struct Bw1RedMember { const float* part; float* dpack; int nct, nsplit, nfloats; };
+struct Bw1RedGroup { int n = 0; Bw1RedMember m[B1_RED_GROUP_MAX]; };
+bool bw1_reduce_group_add(Bw1RedGroup& G, const Bw1Args& g);  // false: the group is full (launch it first); a record without slots adds nothing
+hipError_t bw1_reduce_group_launch(Bw1RedGroup& G, hipStream_t st);  // launches the members (if any) and empties the group
+hipError_t launch_bw1_reduce_member(const Bw1RedMember& m, hipStream_t st);  // one member alone: launch_bw1_reduce's kernel
+// wg3.hip: the dense 3x3 weight gradients of up to W3_GROUP_MAX layers as one wg3 launch + one reduction (slot index = workgroup index
+// in the family's one slot buffer).  `block` holds the kernel argument being assembled (wg3.hip: Wg3GroupLaunch).
+constexpr int W3_GROUP_MAX = 32;
+struct Wg3Group {
+  int n = 0, dtype = 0, pq = 0, part_slots = 0;
+  long long tiles = 0;  // of the members so far
+  alignas(16) unsigned char block[4096];
+};
+bool wg3_group_add(Wg3Group& G, const WgradArgs& a, int dtype);  // false: `a` does not fit (launch the group first; with G.n == 0: not a launch to group)
+hipError_t wg3_group_launch(Wg3Group& G, hipStream_t st);        // launches the members (if any) and empties the group
 // impl = IMPL_AUTO: the first family of the table that `deny` (1 << family) does not name and that resolves; otherwise the recorded family
 hipError_t launch_igemm(const ConvArgs& a, int dtype, int epi, bool mfma, hipStream_t st, int impl = IMPL_AUTO, unsigned deny = 0);
 hipError_t launch_wgrad(WgradArgs a, int dtype, bool mfma, hipStream_t st, int impl = IMPL_AUTO, unsigned deny = 0);

@@ -24,7 +24,9 @@
 // workgroups no longer has to balance tiles per workgroup against 147 KB of atomics each.
 #include <algorithm>
 #include <cmath>
+#include <cstddef>
 #include <cstdlib>
+#include <cstring>
 
 #include "common.h"
 #include "dispatch.h"
@@ -51,6 +53,16 @@ struct Wg3Args {
   float* part;  // per-workgroup slots of W3_SLOT_FLOATS (nullable: fp32 atomics into w.dpack)
 };
 
+// What the walk over the tiles reads of a launch: the operands of ONE weight gradient.  wg3_kernel fills it from its WgradArgs, the
+// grouped kernel (wg3_group_kernel) from the member of its table the workgroup belongs to.
+struct W3View {
+  const void *asrc, *ysrc, *ysrc2;         // A = y1; dY (the compact copy or the block's gradient buffer) and its second operand
+  const float *ascale, *ashift, *yq, *yr;  // norm2's constants; the effective gradient's
+  float* dpack;
+  int ald, yld, yld2, Ho, Wo, tiles_y, tiles_x;
+};
+struct W3Taps { short t[12]; };  // the nine taps of dY: (dy & 0xff) | ((dx & 0xff) << 8)
+
 // The loaders' global loads and their waits are inline assembly: isa.h explains why.  The sets of this kernel: NA slots of A, NY of dY
 // and, with the effective gradient (PQ == 2), NY of its second operand - one set is NLD = NA + NY or NA + 2 NY requests.
 // MODE 0: wait until this set has landed (the other set's NLD requests stay in flight); 1: wait for everything; 2: keep alive only
@@ -67,21 +79,18 @@ __device__ __forceinline__ void w3_sync(typename TT<T>::vec (&ra)[NA], typename 
 }
 
 // PQ = prologue of dY: 0 none (materialised gradient), 2 effective gradient (q, r of the 16-bit form)
+// The walk of one workgroup over the tiles [t_beg, t_end) of `a`; the partial result goes to `slot` (null: fp32 atomics into a.dpack).
 template <typename T, int PQ>
-__global__ __launch_bounds__(W3_NT, 1) void wg3_kernel(const Wg3Args g) {
+__device__ __forceinline__ void wg3_walk(const W3View& a, const W3Taps& taps, const int t_beg, const int t_end, float* slot) {
   static_assert(sizeof(T) == 2, "16-bit storage");
   typedef typename TT<T>::vec V;
   constexpr int SLOT = 8;
   constexpr int NL = 256;                                                   // loader threads
   constexpr int NA = BM * (W3_CA / SLOT) / NL;                              // 8 A slots per loader thread
   constexpr int NY = (W3_HH * W3_HW * (W3_CY / SLOT) + NL - 1) / NL;        // 3 dY slots per loader thread
-  const WgradArgs& a = g.w;
-  const Seg& sy_ = a.seg[0];  // dY, nine taps
-  const Seg& sa = a.dy;       // A, pixel aligned
 
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int t_beg = blockIdx.x * g.tiles_per_wg, t_end = min(g.ntiles, t_beg + g.tiles_per_wg);
   if (t_beg >= t_end) return;  // (workgroup-uniform)
   const int nt = t_end - t_beg;
 
@@ -91,12 +100,12 @@ __global__ __launch_bounds__(W3_NT, 1) void wg3_kernel(const Wg3Args g) {
     const int ca = lt & 15, pa0 = lt >> 4;  // A: slot column, pixel column pa0 of tile rows i = 0..7
     const int cy = lt & 3, hy0 = lt >> 2;   // dY: slot column, halo pixels hy0 + 64 i
     SlotK<SLOT> ka, ky;
-    ka.k0 = load_fv<SLOT>(sa.scale + ca * SLOT); ka.k1 = load_fv<SLOT>(sa.shift + ca * SLOT); ka.k2 = 0.f; ka.k3 = 0.f;
+    ka.k0 = load_fv<SLOT>(a.ascale + ca * SLOT); ka.k1 = load_fv<SLOT>(a.ashift + ca * SLOT); ka.k2 = 0.f; ka.k3 = 0.f;
     ky.k0 = 0.f; ky.k1 = 0.f; ky.k2 = 0.f; ky.k3 = 0.f;
-    if (PQ == 2) { ky.k0 = load_fv<SLOT>(sy_.q + cy * SLOT); ky.k1 = load_fv<SLOT>(sy_.r + cy * SLOT); }
-    const T* asrc = (const T*)sa.src + ca * SLOT;
-    const T* ysrc = (const T*)sy_.src + cy * SLOT;
-    const T* ysrc2 = (const T*)sy_.src2 + cy * SLOT;
+    if (PQ == 2) { ky.k0 = load_fv<SLOT>(a.yq + cy * SLOT); ky.k1 = load_fv<SLOT>(a.yr + cy * SLOT); }
+    const T* asrc = (const T*)a.asrc + ca * SLOT;
+    const T* ysrc = (const T*)a.ysrc + cy * SLOT;
+    const T* ysrc2 = (const T*)a.ysrc2 + cy * SLOT;
     int hyy[NY], hxx[NY];  // this thread's halo positions (fixed over the walk)
 #pragma unroll
     for (int i = 0; i < NY; ++i) {
@@ -108,32 +117,32 @@ __global__ __launch_bounds__(W3_NT, 1) void wg3_kernel(const Wg3Args g) {
       unsigned oka, oky;  // validity bits of the slots
     };
     // the issue cursor walks the tiles of this workgroup in order, two tiles ahead of the image being written
-    const int tiles_img = g.tiles_y * g.tiles_x;
+    const int tiles_img = a.tiles_y * a.tiles_x;
     int cb = t_beg / tiles_img, cty, ctx, cleft = nt;
-    { const int tr = t_beg - cb * tiles_img; cty = tr / g.tiles_x; ctx = tr - cty * g.tiles_x; }
+    { const int tr = t_beg - cb * tiles_img; cty = tr / a.tiles_x; ctx = tr - cty * a.tiles_x; }
     auto issue = [&](LSet& R) {  // branch-free: clamped addresses, zeroed at the write if outside; past the end: the last tile again
       const int y0 = cty * W3_TH, x0 = ctx * W3_TW;
       R.oka = 0; R.oky = 0;
       const int xa = x0 + pa0;
-      const size_t arow = (size_t)cb * sa.Hs;
+      const size_t arow = (size_t)cb * a.Ho;
 #pragma unroll
       for (int i = 0; i < NA; ++i) {
         const int y = y0 + i;
         if (y < a.Ho && xa < a.Wo) R.oka |= 1u << i;
-        const size_t pix = (arow + min(y, sa.Hs - 1)) * sa.Ws + min(xa, sa.Ws - 1);
-        if (!(WG3_DBG & 4)) gload16(R.ra[i], asrc + pix * sa.ld);
+        const size_t pix = (arow + min(y, a.Ho - 1)) * a.Wo + min(xa, a.Wo - 1);
+        if (!(WG3_DBG & 4)) gload16(R.ra[i], asrc + pix * a.ald);
       }
-      const size_t yrow = (size_t)cb * sy_.Hs;
+      const size_t yrow = (size_t)cb * a.Ho;
 #pragma unroll
       for (int i = 0; i < NY; ++i) {
         const int y = y0 + hyy[i], x = x0 + hxx[i];
-        if (hy0 + 64 * i < W3_HH * W3_HW && (unsigned)y < (unsigned)sy_.Hs && (unsigned)x < (unsigned)sy_.Ws) R.oky |= 1u << i;
-        const size_t pix = (yrow + min(max(y, 0), sy_.Hs - 1)) * sy_.Ws + min(max(x, 0), sy_.Ws - 1);
-        if (!(WG3_DBG & 4)) gload16(R.ry[i], ysrc + pix * sy_.ld);
-        if constexpr (PQ == 2) { if (!(WG3_DBG & 4)) gload16(R.ry2[i], ysrc2 + pix * sy_.ld2); }
+        if (hy0 + 64 * i < W3_HH * W3_HW && (unsigned)y < (unsigned)a.Ho && (unsigned)x < (unsigned)a.Wo) R.oky |= 1u << i;
+        const size_t pix = (yrow + min(max(y, 0), a.Ho - 1)) * a.Wo + min(max(x, 0), a.Wo - 1);
+        if (!(WG3_DBG & 4)) gload16(R.ry[i], ysrc + pix * a.yld);
+        if constexpr (PQ == 2) { if (!(WG3_DBG & 4)) gload16(R.ry2[i], ysrc2 + pix * a.yld2); }
       }
       if (--cleft > 0) {  // (uniform) advance; the cursor parks on the last tile
-        if (++ctx == g.tiles_x) { ctx = 0; if (++cty == g.tiles_y) { cty = 0; ++cb; } }
+        if (++ctx == a.tiles_x) { ctx = 0; if (++cty == a.tiles_y) { cty = 0; ++cb; } }
       }
     };
     auto store = [&](LSet& R, int set, bool wait = true) {
@@ -211,7 +220,7 @@ __global__ __launch_bounds__(W3_NT, 1) void wg3_kernel(const Wg3Args g) {
   int yoff[9];  // halo offset of (pixel x = arow of the k-step's tile row, tap)
 #pragma unroll
   for (int t = 0; t < 9; ++t) {
-    const int tw = sy_.taps[t];
+    const int tw = taps.t[t];
     const int dy = (int)(signed char)(tw & 0xff), dx = (int)(signed char)((tw >> 8) & 0xff);
     yoff[t] = ((1 + dy) * W3_HW + (arow + 1 + dx)) * 64 + ycol;
   }
@@ -238,14 +247,14 @@ __global__ __launch_bounds__(W3_NT, 1) void wg3_kernel(const Wg3Args g) {
   // Slot layout = the accumulator layout: float4 j of tap t of wave w of lane l at (((t * 4 + w) * 4 + j) * 64 + l) * 4, i.e. every
   // store instruction writes 1 KB contiguous (36 per lane instead of 144 scalar ones); wg3_reduce_kernel knows the permutation.
   const int r = lane & 31, h = lane >> 5;
-  if (g.part != nullptr) {
-    f32x4* slot = (f32x4*)(g.part + (size_t)blockIdx.x * W3_SLOT_FLOATS);
+  if (slot != nullptr) {
+    f32x4* s4 = (f32x4*)slot;
 #pragma unroll
     for (int t = 0; t < 9; ++t)
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         const f32x4 v = {acc[t][4 * j], acc[t][4 * j + 1], acc[t][4 * j + 2], acc[t][4 * j + 3]};
-        if (!(WG3_DBG & 1) || v[0] == 1.2345e33f) slot[((t * 4 + wave) * 4 + j) * 64 + lane] = v;
+        if (!(WG3_DBG & 1) || v[0] == 1.2345e33f) s4[((t * 4 + wave) * 4 + j) * 64 + lane] = v;
       }
   } else {
 #pragma unroll
@@ -253,9 +262,53 @@ __global__ __launch_bounds__(W3_NT, 1) void wg3_kernel(const Wg3Args g) {
 #pragma unroll
       for (int i = 0; i < 16; ++i) {
         const int c = 32 * wave + (i & 3) + 8 * (i >> 2) + 4 * h;
-        if (!(WG3_DBG & 1) || acc[t][i] == 1.2345e33f) atomic_add_f32(a.dpack + ((size_t)t * a.Npad + c) * 32 + r, acc[t][i]);
+        if (!(WG3_DBG & 1) || acc[t][i] == 1.2345e33f) atomic_add_f32(a.dpack + ((size_t)t * W3_CA + c) * 32 + r, acc[t][i]);
       }
   }
+}
+
+template <typename T, int PQ>
+__global__ __launch_bounds__(W3_NT, 1) void wg3_kernel(const Wg3Args g) {
+  const Seg& sy_ = g.w.seg[0];  // dY, nine taps
+  const Seg& sa = g.w.dy;       // A, pixel aligned
+  // (wg3_resolve: both operands have the launch's map size, Npad = 128)
+  const W3View a = {sa.src, sy_.src, sy_.src2, sa.scale, sa.shift, sy_.q, sy_.r, g.w.dpack, sa.ld, sy_.ld, sy_.ld2, g.w.Ho, g.w.Wo, g.tiles_y, g.tiles_x};
+  W3Taps taps;
+#pragma unroll
+  for (int t = 0; t < 9; ++t) taps.t[t] = sy_.taps[t];
+  const int t_beg = blockIdx.x * g.tiles_per_wg;
+  wg3_walk<T, PQ>(a, taps, t_beg, min(g.ntiles, t_beg + g.tiles_per_wg), g.part ? g.part + (size_t)blockIdx.x * W3_SLOT_FLOATS : nullptr);
+}
+
+// The GROUPED launch: the weight gradients of up to W3_GROUP_MAX layers in one grid.  Late in the network a layer has one or two tiles
+// per workgroup, and the launch, the prologue and the 147 KB hand-over are paid for those; the layers of a dense block are independent
+// (each reads its own compact gradient and y1 and writes its own packed gradient), so the executor (capi.cpp run_ops) hands consecutive
+// ones over together.  The table travels in the kernel argument (no upload).  Workgroups [wg0[i], wg0[i + 1]) belong to member i and
+// walk its tiles exactly as wg3_kernel does; slot index = workgroup index, and wg3_group_reduce_kernel adds each member's slot range.
+struct Wg3Member {
+  W3View v;
+  int ntiles, tiles_per_wg;
+};
+struct Wg3GroupArgs {
+  float* part;
+  int n;
+  int wg0[W3_GROUP_MAX + 1];  // first workgroup of each member; [n] = the grid
+  W3Taps taps;                // (the same for every member: wg3_group_fits)
+  Wg3Member m[W3_GROUP_MAX];
+};
+static_assert(sizeof(Wg3GroupArgs) <= 3840, "the table is a kernel argument: 4 KB with the hidden arguments");
+static_assert(sizeof(Wg3Member) % 8 == 0 && offsetof(Wg3GroupArgs, m) % 8 == 0, "members are read with aligned scalar loads");
+
+template <typename T, int PQ>
+__global__ __launch_bounds__(W3_NT, 1) void wg3_group_kernel(const Wg3GroupArgs g) {
+  const int bid = blockIdx.x;
+  int mi = 0;  // (uniform scan; wg0 is ascending)
+#pragma unroll
+  for (int i = 1; i < W3_GROUP_MAX; ++i)
+    if (i < g.n && bid >= g.wg0[i]) mi = i;
+  const Wg3Member& M = g.m[mi];
+  const int t_beg = (bid - g.wg0[mi]) * M.tiles_per_wg;
+  wg3_walk<T, PQ>(M.v, g.taps, t_beg, min(M.ntiles, t_beg + M.tiles_per_wg), g.part + (size_t)bid * W3_SLOT_FLOATS);
 }
 
 // dpack += sum of the slots, in a fixed order (no float atomics).  288 workgroups: thread (o, sg) adds the slots sg, sg + 8, ... of one
@@ -265,7 +318,7 @@ __global__ __launch_bounds__(W3_NT, 1) void wg3_kernel(const Wg3Args g) {
 // float4 f of a slot = (tap t, wave w, quad j, lane l): accumulator elements 4j .. 4j+3 = channels 32 w + 8 j + 4 (l >> 5) + 0..3 of
 // column n = l & 31 (the 32x32 MFMA result layout), i.e. four dP rows 128 bytes apart.
 constexpr int W3_RG = 8;  // slot groups
-__global__ __launch_bounds__(256) void wg3_reduce_kernel(const float* __restrict__ part, float* __restrict__ dpack, int nslots) {
+__device__ __forceinline__ void wg3_reduce_slots(const float* __restrict__ part, float* __restrict__ dpack, int nslots) {
   __shared__ f32x4 red[W3_RG][32];
   const int o = threadIdx.x & 31, sg = threadIdx.x >> 5;
   const int f = blockIdx.x * 32 + o;
@@ -291,6 +344,20 @@ __global__ __launch_bounds__(256) void wg3_reduce_kernel(const float* __restrict
 #pragma unroll
     for (int q = 0; q < 4; ++q) d[q * 32] += t4[q];
   }
+}
+__global__ __launch_bounds__(256) void wg3_reduce_kernel(const float* __restrict__ part, float* __restrict__ dpack, int nslots) {
+  wg3_reduce_slots(part, dpack, nslots);
+}
+// The grouped form: blockIdx.y = member; the member's slot range in the same fixed order into the member's packed gradient.
+struct Wg3ReduceGroupArgs {
+  const float* part;
+  int wg0[W3_GROUP_MAX + 1];
+  float* dpack[W3_GROUP_MAX];
+};
+__global__ __launch_bounds__(256) void wg3_group_reduce_kernel(const Wg3ReduceGroupArgs g) {
+  const int mi = blockIdx.y;
+  const int s0 = g.wg0[mi];
+  wg3_reduce_slots(g.part + (size_t)s0 * W3_SLOT_FLOATS, g.dpack[mi], g.wg0[mi + 1] - s0);
 }
 
 // What wg3_resolve hands to wg3_launch: the kernel's arguments but for the split over workgroups, and the instantiation that runs.
@@ -326,6 +393,19 @@ bool wg3_resolve(const WgradArgs& a, int dtype, Resolved& r) {
   return true;
 }
 
+// The workgroups of a launch with slots: one per compute unit (W3_MAX_SLOTS and the slots of the buffer cap it).
+static int wg3_slot_wgs(int part_slots) {
+  static const int cus = device_cus();
+  static const int wgs_cap = lab_int("DMM_WG3_WGS", 0);
+  int nwg = std::min(std::min(cus, W3_MAX_SLOTS), part_slots);
+  if (wgs_cap > 0) nwg = std::min(nwg, wgs_cap);
+  return std::max(1, nwg);
+}
+static bool wg3_use_slots() {
+  static const bool use_slots = lab_int("DMM_WG3_SLOTS", 1) != 0;
+  return use_slots;
+}
+
 hipError_t wg3_launch(const Resolved& r, hipStream_t st) {
   const Wg3Launch& l = r.get<Wg3Launch>();
   Wg3Args g = l.g;
@@ -334,9 +414,8 @@ hipError_t wg3_launch(const Resolved& r, hipStream_t st) {
   // and the reduction reads them once.  With atomics (no slots, DMM_WG3_SLOTS=0): time ~ tiles/nwg * t_tile + nwg * (147 KB of
   // fp32 atomics at the chip-wide atomic rate of 1.3 TB/s = 0.11 us): minimum at nwg ~ sqrt(t_tile / 0.11 us * tiles), t_tile ~ 1.3 us.
   static const int cus = device_cus();
-  static const bool use_slots = lab_int("DMM_WG3_SLOTS", 1) != 0;
   static const int wgs_cap = lab_int("DMM_WG3_WGS", 0);
-  g.part = (use_slots && a.part != nullptr) ? a.part : nullptr;
+  g.part = (wg3_use_slots() && a.part != nullptr) ? a.part : nullptr;
   int nwg = g.part ? std::min(cus, a.part_slots) : (int)std::lround(std::sqrt(12.0 * g.ntiles));
   if (wgs_cap > 0) nwg = std::min(nwg, wgs_cap);
   nwg = std::max(1, std::min(std::min(nwg, cus), g.ntiles));
@@ -348,6 +427,89 @@ hipError_t wg3_launch(const Resolved& r, hipStream_t st) {
     e = hipGetLastError();
   }
   return e;
+}
+
+// ---- the grouped launch (pointwise.h: Wg3Group) ----
+struct Wg3GroupLaunch {
+  Wg3GroupArgs g;
+  LdsLauncher<Wg3GroupArgs> run;
+};
+static_assert(sizeof(Wg3GroupLaunch) <= sizeof(Wg3Group::block) && alignof(Wg3GroupLaunch) <= 16, "Wg3Group::block is too small");
+
+template <typename T> static LdsLauncher<Wg3GroupArgs> wg3_group_runner(bool pq) {
+  return pq ? launch_lds<wg3_group_kernel<T, 2>, Wg3GroupArgs> : launch_lds<wg3_group_kernel<T, 0>, Wg3GroupArgs>;
+}
+
+bool wg3_group_add(Wg3Group& G, const WgradArgs& a, int dtype) {
+  if (!wg3_use_slots() || a.part == nullptr || a.part_slots < 1 || a.M <= 0) return false;
+  Resolved r;
+  if (!wg3_resolve(a, dtype, r)) return false;
+  const Wg3Launch& l = r.get<Wg3Launch>();
+  const Seg& sy_ = a.seg[0];
+  const Seg& sa = a.dy;
+  Wg3GroupLaunch& L = *reinterpret_cast<Wg3GroupLaunch*>(G.block);
+  const int pq = sy_.q ? 2 : 0;
+  W3Taps taps;
+  memset(&taps, 0, sizeof(taps));
+  for (int t = 0; t < 9; ++t) taps.t[t] = sy_.taps[t];
+  if (G.n == 0) {
+    memset(&L, 0, sizeof(L));
+    L.g.part = a.part;
+    L.g.taps = taps;
+    L.run = dtype == DT_F16 ? wg3_group_runner<f16>(pq != 0) : wg3_group_runner<bf16>(pq != 0);
+    G.dtype = dtype; G.pq = pq; G.part_slots = a.part_slots; G.tiles = 0;
+  } else {
+    // a member that does not fit: another kernel instantiation, other slots or taps, the member cap, or no workgroup left for it
+    if (G.dtype != dtype || G.pq != pq || L.g.part != a.part || G.part_slots != a.part_slots || memcmp(&L.g.taps, &taps, sizeof(taps)) != 0) return false;
+    if (G.n >= W3_GROUP_MAX || G.n >= wg3_slot_wgs(G.part_slots)) return false;
+  }
+  Wg3Member& m = L.g.m[G.n++];
+  m.v = {sa.src, sy_.src, sy_.src2, sa.scale, sa.shift, sy_.q, sy_.r, a.dpack, sa.ld, sy_.ld, sy_.ld2, a.Ho, a.Wo, l.g.tiles_y, l.g.tiles_x};
+  m.ntiles = l.g.ntiles;
+  m.tiles_per_wg = 0;
+  G.tiles += l.g.ntiles;
+  return true;
+}
+
+// Workgroups are dealt in proportion to tiles: at least 1 per member, at most the member's tiles, at most wg3_slot_wgs in all (the
+// members number at most that: wg3_group_add).  A pure function of the members and the device's compute units.
+hipError_t wg3_group_launch(Wg3Group& G, hipStream_t st) {
+  if (G.n <= 0) return hipSuccess;
+  Wg3GroupLaunch& L = *reinterpret_cast<Wg3GroupLaunch*>(G.block);
+  Wg3GroupArgs& g = L.g;
+  const int n = G.n, W = wg3_slot_wgs(G.part_slots);
+  int w[W3_GROUP_MAX], sum = 0;
+  for (int i = 0; i < n; ++i) {
+    w[i] = (int)std::max<long long>(1, std::min<long long>(g.m[i].ntiles, (long long)W * g.m[i].ntiles / G.tiles));
+    sum += w[i];
+  }
+  while (sum > W) {  // (the rounding up to 1 of small members: taken from the member with the fewest tiles per workgroup)
+    int k = -1;
+    for (int i = 0; i < n; ++i)
+      if (w[i] > 1 && (k < 0 || (long long)g.m[i].ntiles * w[k] < (long long)g.m[k].ntiles * w[i])) k = i;
+    --w[k]; --sum;
+  }
+  for (int i = 0; i < n && sum < W; ++i)  // what the rounding down left over: one more each, in order
+    if (w[i] < g.m[i].ntiles) { ++w[i]; ++sum; }
+  int wg = 0;
+  Wg3ReduceGroupArgs rg;
+  memset(&rg, 0, sizeof(rg));
+  rg.part = g.part;
+  for (int i = 0; i < n; ++i) {
+    Wg3Member& m = g.m[i];
+    m.tiles_per_wg = (m.ntiles + w[i] - 1) / w[i];
+    g.wg0[i] = wg; rg.wg0[i] = wg;
+    rg.dpack[i] = m.v.dpack;
+    wg += (m.ntiles + m.tiles_per_wg - 1) / m.tiles_per_wg;
+  }
+  for (int i = n; i <= W3_GROUP_MAX; ++i) { g.wg0[i] = wg; rg.wg0[i] = wg; }
+  g.n = n;
+  G.n = 0; G.tiles = 0;  // (handed over, whatever the runtime says)
+  if (wg > G.part_slots) return hipErrorInvalidValue;  // (cannot happen: sum <= W <= part_slots)
+  hipError_t e = L.run(W3_LDS, wg, W3_NT, W3_LDS, st, g);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(wg3_group_reduce_kernel, dim3(W3_SLOT_FLOATS / 4 / 32, n), dim3(256), 0, st, rg);
+  return hipGetLastError();
 }
 
 }  // namespace dmm

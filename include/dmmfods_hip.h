@@ -75,7 +75,9 @@ typedef struct dmm_plan dmm_plan;
 const char* dmm_last_error(void);
 int dmm_version(void);
 /* Switches for tests and A/B timing: "graph" (1 = replay captured launch lists, 2 = the forward list only; see dmm_plan_num_graph_replays), "overlap_wgrad" (1 = weight-gradient GEMMs on a second stream beside the
- * data-gradient chain, 0 = one stream; read at every call), and the kernel families "thin_logits" (gather-once kernel for the
+ * data-gradient chain, 0 = one stream; read at every call), "batch_wgrad" (the dense 3x3 weight gradients and the bw1 reductions of consecutive layers of a dense block
+ * as grouped launches: 1, the default = on the caller's stream, 2 = on the weight-gradient stream, 0 = one launch per record as
+ * without the option; read at every call, the same batches in every mode: see dmm_plan_wgrad_batch_counts), and the kernel families "thin_logits" (gather-once kernel for the
  * heat-map head's last convolution), "conv3" (LDS halo-tile kernels of the multi-tap convolutions), "wg3" (the growth convolution's
  * weight gradient), "wgp" (weight gradients of the parity-phase convolutions), "wg5" (of the 5x5 head / 7x7 stem convolutions),
  * "cvp" (the ConvTranspose kernels), "bw1" (fused backward of the 1x1 bottleneck convolutions), "pig" (persistent forward of the
@@ -200,6 +202,11 @@ int dmm_plan_loss_metrics(dmm_plan* plan, const float* logits, const float* targ
  * dmm_plan_backward, and the backward of a plan whose gradient buckets are waited for (dmm_plan_grad_bucket_wait: data-parallel
  * overlap needs the bucket events at their place inside the list).  which: 0 training forward, 1 loss + backward. */
 long long dmm_plan_num_graph_replays(const dmm_plan* plan, int which);
+/* Launch coalescing ("batch_wgrad"), summed over every launch list the plan has run: counts[0] = launches of the dense 3x3 weight
+ * gradient kernel (a grouped launch counts once; each is followed by one reduction launch), counts[1] = the launch records they
+ * served, counts[2] = launches of the bw1 reduction, counts[3] = the bw1.reduce records they served.  With the option off
+ * counts[0] == counts[1] and counts[2] == counts[3].  (Nothing upstream: the reference has no launch lists.) */
+int dmm_plan_wgrad_batch_counts(const dmm_plan* plan, long long counts[4]);
 
 /* Flat fused Adam over n fp32 elements, one parameter group (amsgrad unsupported): torch.optim.Adam's single-tensor arithmetic in
  * fp32, weight_decay added to the gradient (L2, not decoupled), the bias corrections of `step` (1-based) formed on the host in
@@ -372,6 +379,22 @@ int dmm_conv5_wgrad_stats(const dmm_conv_desc* d, const void* x, const void* dy,
 int dmm_conv1x1_backward_fused(const dmm_conv_desc* d, const void* x, const void* dy, const float* w, const float* scale,
                                const float* shift, const void* yfwd, const float* q, const float* r, void* gx, int accumulate,
                                float* dw, double* red, void* scratch, void* stream);
+
+/* Test entry points of the grouped launches (wg3.hip, bw1.hip), as the executor issues them for consecutive layers of a dense block.
+ * n dense 3x3 weight gradients in the transposed form (each as the same call with transposed_form != 0 of dmm_conv_wgrad_ex: 16-bit storage, 128 -> 32
+ * channels, use_mfma; DMM_ERR_INVALID otherwise; descs, and every pointer array, have n entries; yfwd / q / r may be NULL or hold
+ * NULLs) sharing one slot buffer: grouped != 0 = grouped launches of at most 32 members each, filled in order; 0 = one launch per
+ * member.  *launches (nullable) = weight-gradient kernel launches made.  Members may differ in map size and batch, not in dtype or
+ * in having q / r. */
+int dmm_conv_wgrad_grouped(const dmm_conv_desc* descs, int n, const void* const* x, const void* const* dy, const float* const* scale,
+                           const float* const* shift, const void* const* yfwd, const float* const* q, const float* const* r,
+                           float* const* dw, void* const* scratch, int grouped, int* launches, void* stream);
+/* n reductions of bw1.hip's weight-gradient slots: member i adds the nsplit[i] row ranges of part[i] (slot (k, ct) = 4 x 128 x 32
+ * floats at (k * nct[i] + ct) slots) into dpack[i] (ceil(wc[i] / 32) x 128 x 32 floats, overwritten; (nct[i] - 1) * 128 < wc[i] <=
+ * nct[i] * 128).  grouped != 0: one launch per 32 members; 0: one per member.  Both add in the same order: the results are equal
+ * bit for bit.  *launches (nullable) = launches made. */
+int dmm_bw1_reduce_grouped(int n, const float* const* part, float* const* dpack, const int* nct, const int* nsplit, const int* wc,
+                           int grouped, int* launches, void* stream);
 
 /* Which kernel family ran the calling thread's most recent single-kernel launch (dmm_conv_forward / _wgrad(_ex) / _dgrad(_ex) /
  * dmm_conv1x1_backward_fused; for multi-launch entry points: the last launch).  The single-kernel entry points dispatch like a

@@ -35,6 +35,15 @@
 // DRIVE_FREEZE=1 (life-cycle run and dump): the plan is built with a frozen encoder (dmm_plan_set_encoder_frozen on the unbound plan; a
 // null plan and the bound plan must be refused); the life-cycle run also takes the guarded step over two trainable ranges, one of
 // them released late (dmm_adam_step_guarded_ranges, t0 > 0), and checks that no bucket and no unpack descriptor touches an encoder tensor.
+// Launch coalescing (dmm_set_option("batch_wgrad"), on by default; DRIVE_OPTIONS_OFF=batch_wgrad runs one launch per record,
+// DRIVE_BATCH_WGRAD=<0|1|2> sets the option's value: 2 = grouped on the weight-gradient stream instead of the caller's): every
+// life-cycle run watches the enqueue calls through the fake runtime's hook and checks, with the option on or off, that
+//   * no batch is pending where the weight-gradient side is joined or a gradient bucket is signalled: at every record of a join or
+//     bucket event, the members the reduction launches have served so far (a grouped launch: gridDim.y) are the records run_ops
+//     has taken so far (dmm_plan::batch_counts);
+//   * at the end of every call each dense 3x3 weight-gradient record and each bw1.reduce record with slots of the range it ran has
+//     been served exactly once (counted from the plan's own records);
+// and prints "batch life <n>: <records> wg3 records in <launches> launches, <records> bw1.reduce records in <launches> launches".
 // DRIVE_GROUPS=1 (life-cycle run): the parameter-group step.  A segment table over the plan's own tensors (BatchNorm tensors one class,
 // convolutions another, the tensors of the first quarter of the arena a third with t0 > 0, the first tensor left out as a gap) goes
 // through dmm_adam_table_init into a heap block of exactly dmm_adam_table_bytes; the uploaded form is checked (segments, and the
@@ -60,6 +69,7 @@ extern "C" long fakehip_live_streams();
 extern "C" long fakehip_live_events();
 extern "C" long fakehip_stream_creates();
 extern "C" long fakehip_event_creates();
+extern "C" void fakehip_set_hook(void (*hook)(int, const char*, unsigned, unsigned, const void*, const void*));
 
 using namespace dmm;
 
@@ -149,6 +159,61 @@ bool fill_desc(const std::string& arch, dmm_model_desc& d) {
   return true;
 }
 
+// ---- launch coalescing, watched from the runtime's side (see the head of the file) ----
+struct BatchWatch {
+  const dmm_plan* plan = nullptr;
+  long long w3_served = 0, rd_served = 0;      // members served by the reduction launches seen so far
+  long long w3_launches = 0, rd_launches = 0;  // wg3 kernel launches (single or grouped), bw1 reduction launches
+  long long w3_want = 0, rd_want = 0;          // records of the ranges run so far (from the plan's lists)
+  long bad = 0, syncs = 0;
+} g_watch;
+void batch_complain(const char* where) {
+  ++g_watch.bad;
+  if (g_watch.bad <= 10)
+    fprintf(stderr, "[drive] launch coalescing, %s: %lld wg3 / %lld bw1.reduce records served, run_ops has taken %lld / %lld\n", where, g_watch.w3_served,
+            g_watch.rd_served, g_watch.plan->batch_counts[1], g_watch.plan->batch_counts[3]);
+}
+void batch_hook(int what, const char* kernel, unsigned, unsigned gy, const void*, const void* event) {
+  BatchWatch& w = g_watch;
+  if (w.plan == nullptr) return;
+  if (what == 0) {
+    const std::string k = kernel;
+    if (k.find("wg3_group_reduce_kernel") != std::string::npos) w.w3_served += gy;
+    else if (k.find("wg3_reduce_kernel") != std::string::npos) w.w3_served += 1;
+    else if (k.find("bw1_reduce_group_kernel") != std::string::npos) { w.rd_served += gy; ++w.rd_launches; }
+    else if (k.find("bw1_reduce_kernel") != std::string::npos) { w.rd_served += 1; ++w.rd_launches; }
+    else if (k.find("wg3_group_kernel") != std::string::npos || k.find("wg3_kernel") != std::string::npos) ++w.w3_launches;
+  } else if (what == 1) {   // a join or bucket event is recorded: nothing may be pending
+    bool sync = false;
+    for (void* e : w.plan->join_events) sync |= e == event;
+    for (void* e : w.plan->bucket_events) sync |= e == event;
+    if (!sync) return;
+    ++w.syncs;
+    if (w.w3_served != w.plan->batch_counts[1] || w.rd_served != w.plan->batch_counts[3]) batch_complain("at a join or bucket event");
+  }
+}
+// the records of `ops` that a weight-gradient / reduction launch must serve
+void batch_expect(const std::vector<Op>& ops) {
+  for (const Op& o : ops) {
+    if (o.kind == OP_WGRAD && o.impl == IMPL_WG3 && o.w.M > 0 && o.w.part != nullptr) ++g_watch.w3_want;
+    if (o.kind == OP_BW1RED && o.b1.c.M > 0 && o.b1.part != nullptr) {
+      const Bw1Geom q = bw1_geometry(o.b1.c);
+      if (q.nsplit > 1 && q.nsplit * q.nct <= o.b1.part_slots) ++g_watch.rd_want;
+    }
+  }
+}
+bool batch_end_of_call(const char* what) {
+  const BatchWatch& w = g_watch;
+  const bool ok = w.w3_served == w.w3_want && w.rd_served == w.rd_want && w.w3_served == w.plan->batch_counts[1] && w.rd_served == w.plan->batch_counts[3] &&
+                  w.w3_launches == w.plan->batch_counts[0] && w.rd_launches == w.plan->batch_counts[2];
+  if (!ok) {
+    batch_complain(what);
+    fprintf(stderr, "[drive]   wanted %lld / %lld; launches seen %lld / %lld, counted %lld / %lld\n", w.w3_want, w.rd_want, w.w3_launches, w.rd_launches,
+            w.plan->batch_counts[0], w.plan->batch_counts[2]);
+  }
+  return ok;
+}
+
 #define MUST(call)                                                                           \
   do {                                                                                       \
     const int rc__ = (call);                                                                 \
@@ -223,6 +288,11 @@ static int one_life(const dmm_model_desc& d, int life) {
     for (Op& o : plan->bwd)
       if (o.kind == OP_WGRAD && o.impl == IMPL_WG3) { o.impl = IMPL_WG5; break; }
   const long l0 = fakehip_launches();
+  g_watch = BatchWatch();
+  g_watch.plan = plan;
+  fakehip_set_hook(batch_hook);
+  // (every backward call runs the whole list - the external-gradient one but for the loss record; no forward list has such records)
+#define BACKWARD_DONE(what) do { batch_expect(plan->bwd); if (!batch_end_of_call(what)) return 2; } while (0)
   void* st = nullptr;  // the caller's stream: the null stream, as torch's default
   // the guarded optimiser step's state block, scratch and moment arenas ("device" memory = heap: ASan sees every host-side touch)
   const bool dyn = getenv("DRIVE_DYN_SCALE") != nullptr || freeze;
@@ -237,6 +307,7 @@ static int one_life(const dmm_model_desc& d, int life) {
   for (int rep = 0; rep < 2; ++rep) {
     MUST(dmm_plan_forward(plan, in1, d.stream_2_in_channels ? in2 : nullptr, logits, 1, st));
     MUST(dmm_plan_loss_backward(plan, logits, target, metrics, st));
+    BACKWARD_DONE("end of a training step");
     if (freeze) {   // two trainable ranges: everything behind the leading encoder range from the start, that range released at step 1
       const int64_t offs[2] = {enc_hi, enc_lo}, cnts[2] = {np - enc_hi, enc_hi - enc_lo}, t0s[2] = {0, 1};
       MUST(dmm_adam_step_guarded_ranges(params, grads, mom1, mom2, offs, cnts, t0s, rep == 0 ? 1 : 2, 1e-3f, 0.9f, 0.999f, 1e-8f, 0.01f, 1.0f, 2.f, 0.5f, 2000,
@@ -311,6 +382,7 @@ static int one_life(const dmm_model_desc& d, int life) {
   chk_ops(plan->fwd_train); chk_ops(plan->fwd_eval); chk_ops(plan->bwd); chk_descs(plan);
   MUST(dmm_plan_forward(plan, in1, d.stream_2_in_channels ? in2 : nullptr, logits, 1, st));
   MUST(dmm_plan_backward(plan, target /*stands for d(loss)/d(logit)*/, st));
+  BACKWARD_DONE("end of the external-gradient backward");
   MUST(dmm_plan_forward(plan, in1, d.stream_2_in_channels ? in2 : nullptr, logits, 0, st));
   MUST(dmm_plan_loss_metrics(plan, logits, target, metrics, st));
   // the data-parallel hooks: wait for every bucket on the caller's stream
@@ -319,6 +391,7 @@ static int one_life(const dmm_model_desc& d, int life) {
   MUST(dmm_plan_profile_begin(plan, 1));
   MUST(dmm_plan_forward(plan, in1, d.stream_2_in_channels ? in2 : nullptr, logits, 1, st));
   MUST(dmm_plan_loss_backward(plan, logits, target, metrics, st));
+  BACKWARD_DONE("end of the profiled pass");
   {
     std::vector<double> ms(dmm_plan_profile_num_ops(plan, 1));
     int passes = 0;
@@ -328,10 +401,16 @@ static int one_life(const dmm_model_desc& d, int life) {
   MUST(dmm_plan_profile_begin(plan, 1));
   MUST(dmm_plan_forward(plan, in1, d.stream_2_in_channels ? in2 : nullptr, logits, 1, st));
   MUST(dmm_plan_loss_backward(plan, logits, target, metrics, st));
+  BACKWARD_DONE("end of the filtered profile pass");
   MUST(dmm_plan_profile_begin(plan, 0));
   // one more step WITHOUT synchronising anything, then destroy: teardown must not rely on the caller having drained the device
   MUST(dmm_plan_forward(plan, in1, d.stream_2_in_channels ? in2 : nullptr, logits, 1, st));
   MUST(dmm_plan_loss_backward(plan, logits, target, metrics, st));
+  BACKWARD_DONE("end of the last step");
+#undef BACKWARD_DONE
+  fakehip_set_hook(nullptr);
+  const BatchWatch watch = g_watch;
+  g_watch.plan = nullptr;
   const long launches = fakehip_launches() - l0;
   const size_t nf = plan->fwd_train.size(), nbw = plan->bwd.size();
   MUST(dmm_plan_destroy(plan));
@@ -340,6 +419,9 @@ static int one_life(const dmm_model_desc& d, int life) {
   printf("life %d: workspace %.1f MiB, %zu + %zu launch records, %ld launches, %ld pointers checked, %ld bad, streams alive %ld (created %ld), events alive %ld (created %ld), violations %ld\n",
          life, wsb / 1048576.0, nf, nbw, launches, g_checked, g_bad, fakehip_live_streams(), fakehip_stream_creates(), fakehip_live_events(),
          fakehip_event_creates(), fakehip_violations());
+  printf("batch life %d: %lld wg3 records in %lld launches, %lld bw1.reduce records in %lld launches, %ld join / bucket events checked, %ld bad\n", life,
+         watch.w3_served, watch.w3_launches, watch.rd_served, watch.rd_launches, watch.syncs, watch.bad);
+  if (watch.bad) { fprintf(stderr, "[drive] FAIL: a batch was pending at a join or bucket event\n"); return 1; }
   return 0;
 }
 
@@ -787,6 +869,7 @@ int main(int argc, char** argv) {
       if (e > b) MUST(dmm_set_option(s.substr(b, e - b).c_str(), 0));
     }
   }
+  if (const char* v = getenv("DRIVE_BATCH_WGRAD")) MUST(dmm_set_option("batch_wgrad", atoi(v)));
   if (argc > 1 && std::string(argv[1]) == "picks") return picks_main(argc, argv);
   if (argc > 1 && std::string(argv[1]) == "dump") return dump_main(argc, argv);
   if (argc > 1 && std::string(argv[1]) == "single") return single_main(argc, argv);

@@ -40,6 +40,11 @@ bool launch_trace() { static const bool on = getenv("DRIVE_TRACE_LAUNCHES") != n
 std::map<const void*, std::string>& kernel_names() { static auto* m = new std::map<const void*, std::string>(); return *m; }
 const char* kernel_name(const void* func) { auto it = kernel_names().find(func); return it == kernel_names().end() ? "?" : it->second.c_str(); }
 
+// The driver's observer (fakehip_set_hook): called for every kernel launch (what = 0: kernel name, grid), event record (1) and
+// stream wait (2) with the stream (null = the caller's) and the event - the order of enqueue calls is what a launch list IS here.
+typedef void (*FakeHook)(int what, const char* kernel, unsigned gx, unsigned gy, const void* stream, const void* event);
+FakeHook g_hook = nullptr;
+
 void violation(const std::string& what) {
   ++g_violations;
   g_violation_log.push_back(what);
@@ -68,6 +73,7 @@ extern "C" long fakehip_live_streams() { std::lock_guard<std::mutex> l(g_mu); re
 extern "C" long fakehip_live_events() { std::lock_guard<std::mutex> l(g_mu); return (long)g_events.size(); }
 extern "C" long fakehip_stream_creates() { return g_stream_creates; }
 extern "C" long fakehip_event_creates() { return g_event_creates; }
+extern "C" void fakehip_set_hook(void (*hook)(int, const char*, unsigned, unsigned, const void*, const void*)) { g_hook = hook; }
 
 extern "C" {
 
@@ -93,6 +99,7 @@ hipError_t hipLaunchKernel(const void* func, dim3 grid, dim3 block, void** args,
   if (launch_trace()) fprintf(stderr, "[fakehip] launch %s grid %u %u %u block %u %u %u lds %zu\n", kernel_name(func), grid.x, grid.y, grid.z, block.x, block.y, block.z, shmem);
   ++g_launches;
   ++s->pending;
+  if (g_hook) g_hook(0, kernel_name(func), grid.x, grid.y, st, nullptr);
   return hipSuccess;
 }
 
@@ -198,6 +205,7 @@ hipError_t hipStreamWaitEvent(hipStream_t st, hipEvent_t ev, unsigned) {
   if (!s || !e) return hipErrorInvalidResourceHandle;
   // waiting makes `st` depend on the recorded stream's work: model it as pending work on `st`
   if (e->recorded_on && e->recorded_on->pending) ++s->pending;
+  if (g_hook) g_hook(2, nullptr, 0, 0, st, ev);
   return hipSuccess;
 }
 // graph capture is not modelled: the library falls back to eager launches when a capture fails
@@ -226,6 +234,7 @@ hipError_t hipEventRecord(hipEvent_t ev, hipStream_t st) {
   if (!s || !e) return hipErrorInvalidResourceHandle;
   e->recorded_on = s;
   ++s->pending;
+  if (g_hook) g_hook(1, nullptr, 0, 0, st, ev);
   return hipSuccess;
 }
 hipError_t hipEventSynchronize(hipEvent_t ev) {
