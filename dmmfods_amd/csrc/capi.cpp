@@ -6,7 +6,6 @@
 #include <cstdlib>
 #include <cstring>
 #include <stdexcept>
-#include <chrono>
 #include <mutex>
 #include <string>
 #include <utility>
@@ -36,7 +35,7 @@ static int fail(int code, const std::string& msg) {
 static bool g_overlap_wgrad = getenv("DMM_NO_OVERLAP") == nullptr;
 static int g_graph = getenv("DMM_GRAPH") ? std::max(1, atoi(getenv("DMM_GRAPH"))) : 0;  // off by default: see launch_list (1: both lists, 2: the forward list only)
 static unsigned long long g_option_epoch = 1;  // bumped by every dmm_set_option: captured graphs have the options of their time baked in
-// Launch coalescing in run_ops: the dense 3x3 weight gradients (wg3) and the bw1 reductions of consecutive layers go out as grouped
+// Launch coalescing (WgradBatches): the dense 3x3 weight gradients (wg3) and the bw1 reductions of consecutive layers go out as grouped
 // launches.  dmm_set_option("batch_wgrad"): 0 every record is its own launch, as before the option existed; 1 (default) grouped, on
 // the CALLER's stream; 2 grouped, on the weight-gradient stream where the single launches run
 static int g_batch_wgrad = 1;
@@ -119,6 +118,342 @@ void trace_destroy(const char* what) {
   if (n > 0) { ssize_t w = write(2, buf, (size_t)std::min<int>(n, (int)sizeof(buf) - 1)); (void)w; }
 }
 }  // namespace
+
+// ------------------------------------------------------------------------------------------------ the launch-list executor
+// run_ops walks a range of launch records; each concern has one owner: the predicates (which lane, which batch - from the record alone),
+// Lanes (streams, fork and join events), ProfilePass (event pairs), WgradBatches (the two pending grouped launches), launch_record.
+// Overlap: a weight gradient only needs what the ops before it produced, and nothing but the final unpack reads it, so
+// it goes to a low-priority side stream (fork event before, one join before unpack).  Late layers launch a few hundred
+// workgroups of a few microseconds; two independent chains fill the CUs that one chain leaves idle.  The records that may run
+// beside the data-gradient chain: weight gradients and the leaves of the backward graph (stem, raw-input branches) - unless the
+// chain waits for them (Op::chain).
+static bool beside_chain(const Op& o) { return !o.chain && (o.kind == OP_WGRAD || o.leaf); }
+// the two kinds of record that have a grouped launch (batched or launched alone, they share the family's slot buffer)
+static bool grouped_family(const Op& o) { return (o.kind == OP_WGRAD && o.impl == IMPL_WG3) || o.kind == OP_BW1RED; }
+bool dmm::side_forks(const Op& o) { return beside_chain(o) && o.leaf != 2 && o.leaf != 3; }
+// A record that carries a bucket signal is never batched (the bucket is final behind ITS launch).
+BatchKind dmm::batch_kind(const Op& o, bool mfma) {
+  if (!side_forks(o) || o.signal >= 0) return BATCH_NONE;
+  if (o.kind == OP_WGRAD && o.impl == IMPL_WG3 && mfma) return BATCH_W3;
+  return o.kind == OP_BW1RED ? BATCH_RD : BATCH_NONE;
+}
+// A batch is flushed before any other record of the weight-gradient side, before a join with that side and before a record that
+// carries a bucket signal.  "Weight-gradient side" is decided from the record alone, not from the streams of this call: the batches -
+// and the bits - are the same with overlap_wgrad on or off, under capture and in a profile pass.
+bool dmm::flushes_batches(const Op& o) { return side_forks(o) || o.leaf == 3 || o.signal >= 0 || (o.kind == OP_JOIN && o.epi != 1); }
+Lane dmm::route(const Op& o, bool overlap, bool forked, bool batch_main) {
+  // A launch that continues a chain on the side stream (the second stream's encoder): everything it reads was produced by the
+  // launch in front of it on that stream, or before the chain's first launch (which forked from the main stream).  Only while
+  // the side stream is forked in THIS call: a range that starts mid-chain, or a join inside the chain, makes the next launch
+  // of the chain fork again like any leaf.
+  if (overlap && o.leaf == 3 && forked) return LANE_SIDE_CONTINUE;
+  // batch_wgrad 1: on the caller's stream, behind its producer - no fork; also the ones launched alone (see WgradBatches::st)
+  if (batch_main && side_forks(o) && grouped_family(o)) return LANE_MAIN;
+  if (overlap && beside_chain(o)) return o.leaf == 2 ? LANE_PACK_FORK : LANE_SIDE_FORK;
+  return LANE_MAIN;
+}
+
+// The invariant behind Op::impl: the family a plan recorded for a convolution launch (and shaped its launch list around: merged
+// phases, finish launches, compact gradients) is the family that took it.  `ran` = the families the launch noted.  Returns the
+// complaint, or an empty string.  The generic family beside another one is a launch that fell through; the ONE launch where that is
+// the design is wgp's two-segment form, whose 8-channel raw-input remainder stays with the generic kernel (launch_wgrad reports that
+// launch as wgp alone today; should the remainder ever be noted as well, the launch stays allowed - by this clause, not by silence).
+static std::string family_check(const Op& o, unsigned ran) {
+  if ((o.kind == OP_IGEMM ? o.c.M : o.w.M) <= 0) return std::string();   // an empty launch notes nothing
+  const bool recorded_ran = (ran >> o.impl) & 1u, generic_ran = (ran >> IMPL_GENERIC) & 1u;
+  const bool wgp_remainder = o.kind == OP_WGRAD && o.impl == IMPL_WGP && o.w.nseg == 2 && o.w.nphase == 0;
+  if (recorded_ran && (o.impl == IMPL_GENERIC || !generic_ran || wgp_remainder)) return std::string();
+  std::string names;
+  for (int f = 1; f < IMPL_COUNT; ++f)
+    if ((ran >> f) & 1u) names += (names.empty() ? "" : "+") + std::string(dmm_impl_name(f));
+  return std::string("launch '") + o.label + "': the plan recorded family " + dmm_impl_name(o.impl) + ", " + (names.empty() ? "none" : names) + " ran";
+}
+
+namespace {
+// evs[i] of a plan's event vector, which grows from the device pool up to index i on first use (null: the runtime gave none)
+hipEvent_t plan_event(const dmm_plan* p, std::vector<void*>& evs, size_t i, bool timing = false) {
+  DevicePool* dp = i < evs.size() ? nullptr : pool_of(p->device);
+  while (evs.size() <= i) {
+    hipEvent_t e = dp ? pool_event(dp, timing) : nullptr;
+    if (e == nullptr) return nullptr;
+    evs.push_back((void*)e);
+  }
+  return (hipEvent_t)evs[i];
+}
+
+// The streams of one run_ops call and what is outstanding on them.  ONE side stream: 2 and 3 side streams measured 0.3 / 0.6 ms
+// slower, and the leaf chains need one FIFO.  The pack stream: the launch that packs the weights of the LATE layers (leaf == 2) runs
+// there beside the first layers of the forward pass; OP_JOIN with epi == 1 in front of the first late layer makes the main stream
+// wait for it.  Without overlap side and pack stay null and nothing is ever forked.
+struct Lanes {
+  dmm_plan* p;
+  hipStream_t main, side = nullptr, pack = nullptr;
+  bool forked = false, pack_pending = false;   // the side / pack stream has work the main stream has not waited for
+  size_t nfork = 0;                            // fork events of the plan used by this call
+  hipEvent_t side_join() const { return (hipEvent_t)p->join_events[0]; }   // (dmm_plan::join_events: [0] side stream, [1] pack stream)
+  hipEvent_t pack_join() const { return (hipEvent_t)p->join_events[1]; }
+  const char* open_helpers() {   // with overlap: the pool's helper streams and the plan's two join events (returns what could not be had, or null)
+    DevicePool* dp = pool_of(p->device);
+    if (dp == nullptr || pool_streams(dp, false) != hipSuccess) return "side stream";
+    side = dp->side; pack = dp->pack;
+    if (plan_event(p, p->join_events, 1) == nullptr) return "hipEventCreate failed";
+    p->used_side = true;
+    return nullptr;
+  }
+  // `st` = the stream of `lane`, forked from the main stream where the lane says so (false: no fork event to be had)
+  bool enter(Lane lane, hipStream_t& st) {
+    st = lane == LANE_MAIN ? main : (lane == LANE_PACK_FORK ? pack : side);
+    if (lane == LANE_MAIN || lane == LANE_SIDE_CONTINUE) return true;
+    hipEvent_t fe = plan_event(p, p->fork_events, nfork);
+    if (fe == nullptr) return false;
+    ++nfork;
+    hipEventRecord(fe, main);
+    hipStreamWaitEvent(st, fe, 0);
+    (lane == LANE_PACK_FORK ? pack_pending : forked) = true;
+    return true;
+  }
+  // the main stream waits for what the side (pack) stream has been given so far; the pack stream's event is recorded behind its launch
+  void join_side() { if (forked) { hipEventRecord(side_join(), side); hipStreamWaitEvent(main, side_join(), 0); forked = false; } }
+  void record_pack_join(hipStream_t behind) { hipEventRecord(pack_join(), behind); }
+  void join_pack() { if (pack_pending) { hipStreamWaitEvent(main, pack_join(), 0); pack_pending = false; } }
+  void join_all() { join_side(); join_pack(); }
+};
+
+// Per-record event pairs of one recorded pass (dmm_plan_profile_begin): events [2i], [2i + 1] bracket record i on the stream it runs on.
+struct ProfilePass {
+  std::vector<void*>* evs = nullptr;     // null: this call records nothing
+  const std::string* filter = nullptr;   // only records whose label starts with it are bracketed (empty: all)
+  // takes the next pass of list `which` if the plan has one left; false: no events to be had
+  bool open(dmm_plan* p, int which, size_t nops) {
+    filter = &p->prof_filter;
+    if (which < 0 || p->prof_max_passes <= 0 || p->prof_pass[which] >= p->prof_max_passes) return true;
+    auto& sets = p->prof_events[which];
+    const int pass = p->prof_pass[which]++;
+    if ((int)sets.size() <= pass) sets.resize(pass + 1);
+    evs = &sets[pass];
+    return nops == 0 || plan_event(p, *evs, 2 * nops - 1, true) != nullptr;
+  }
+  // Per-op profiling keeps everything on one stream so that the event pairs bracket each kernel alone; a FILTERED profile (one
+  // kernel class) runs as in production.
+  bool production_schedule() const { return evs == nullptr || !filter->empty(); }
+  bool selected(const Op& o) const { return evs != nullptr && (filter->empty() || strncmp(o.label, filter->c_str(), filter->size()) == 0); }
+  void begin(size_t i, hipStream_t st) const { hipEventRecord((hipEvent_t)(*evs)[2 * i], st); }
+  void end(size_t i, hipStream_t st) const { hipEventRecord((hipEvent_t)(*evs)[2 * i + 1], st); }
+  void empty_pair(size_t i, hipStream_t st) const { begin(i, st); end(i, st); }
+};
+
+// Launch coalescing.  Within a dense block every dense 3x3 weight gradient reads only its own compact gradient, y1 and
+// norm2 constants and writes its own packed gradient, and every bw1 reduction its own slots: consecutive ones are handed to ONE
+// grouped launch (wg3.hip wg3_group_kernel, bw1.hip bw1_reduce_group_kernel).  A record that joins a batch is ordered behind its
+// producer as before (fork event, stream wait) and notes its family; the launch goes out at the flush.  A batch is flushed
+//   * where flushes_batches says so, and at the end of the range;
+//   * when a member does not fit (kernel instantiation, member cap, no workgroup left);
+//   * wg3, lab builds only: as soon as the pending tiles reach DMM_WG3_BATCH_TILES.  Measured on the caller's stream (C2, profiles/r06/
+//     ablations.txt): 2048 / 4096 / 8192 / 16384 tiles / no threshold = 25.00 / 24.88 / 24.78 / 24.78 / 24.71 ms per step against
+//     25.13 ungrouped - a dense block's layers go out together whatever their map size, hence no threshold (0).
+// In a profile pass the flushing member's event pair brackets the grouped launch, the other members record an empty pair.
+struct WgradBatches {
+  dmm_plan* p;
+  const std::vector<Op>& ops;
+  const ProfilePass& prof;
+  // The stream of the grouped launches.  They fill the chip on their own (a workgroup per compute unit, 8 waves and 86 KB of LDS
+  // each), so beside the data-gradient chain they do not fill its gaps, they hold its launches up: measured at C2 (profiles/r06),
+  // grouped on the weight-gradient stream the step is 0.1-0.2 ms SLOWER than the ungrouped launches there, on the caller's
+  // stream 0.2 ms faster.  Hence the caller's stream (batch_wgrad 1): the records of the two kinds then need no fork event either -
+  // also the ones that are launched alone (a bucket signal), which share the family's slot buffer with the batches.
+  hipStream_t st;
+  Wg3Group w3g;
+  Bw1RedGroup rdg;
+  std::vector<size_t> w3_members, rd_members;
+  enum Offer { ALONE, MEMBER, EMPTY };   // launched on its own; in a batch (launch and event pair at the flush); a bw1.reduce record without slots: nothing to add up
+  // Record i, of batch kind k, is offered to its batch; one that does not fit sends the batch off first and is offered again.
+  hipError_t offer(size_t i, const Op& o, BatchKind k, Offer& took) {
+    const int dt = p->desc.dtype;
+    hipError_t e = hipSuccess;
+    bool in = k == BATCH_W3 ? wg3_group_add(w3g, o.w, dt) : bw1_reduce_group_add(rdg, o.b1);
+    if (!in && k == BATCH_W3 && w3g.n > 0 && (e = flush_w3()) == hipSuccess) in = wg3_group_add(w3g, o.w, dt);
+    if (!in && k == BATCH_RD && (e = flush_rd()) == hipSuccess) in = bw1_reduce_group_add(rdg, o.b1);
+    took = !in ? ALONE : (k == BATCH_W3 || rdg.n > (int)rd_members.size()) ? MEMBER : EMPTY;
+    if (took == MEMBER && k == BATCH_W3) { note_impl(IMPL_WG3); w3_members.push_back(i); ++p->batch_counts[1]; }
+    if (took == MEMBER && k == BATCH_RD) { rd_members.push_back(i); ++p->batch_counts[3]; }
+    return e;
+  }
+  template <typename Launch> hipError_t flush(std::vector<size_t>& members, Launch&& launch) {
+    if (members.empty()) return hipSuccess;
+    for (size_t k = 0; k + 1 < members.size(); ++k)
+      if (prof.selected(ops[members[k]])) prof.empty_pair(members[k], st);
+    const size_t last = members.back();
+    const bool sel_last = prof.selected(ops[last]);
+    members.clear();
+    if (sel_last) prof.begin(last, st);
+    const hipError_t e = launch();
+    if (sel_last) prof.end(last, st);
+    return e;
+  }
+  hipError_t flush_w3() { return flush(w3_members, [&] { ++p->batch_counts[0]; return wg3_group_launch(w3g, st); }); }
+  hipError_t flush_rd() { return flush(rd_members, [&] { ++p->batch_counts[2]; return bw1_reduce_group_launch(rdg, st); }); }
+  hipError_t flush_all() { const hipError_t e1 = flush_w3(), e2 = flush_rd(); return e1 != hipSuccess ? e1 : e2; }
+  hipError_t flush_w3_if_full() { static const long long tiles = lab_int("DMM_WG3_BATCH_TILES", 0); return (tiles > 0 && w3g.tiles >= tiles) ? flush_w3() : hipSuccess; }
+};
+
+// The launch of one record on `st`.  Gradient accumulation: the list is the one of the plain mode; the arena's memset is passed over
+// (its record, label and profiling slot stay) and the two kinds of launch that write the arena take their accumulate form.  known = false: no such kind.
+hipError_t launch_record(dmm_plan* p, const Op& o, hipStream_t st, Lanes& lanes, bool& known) {
+  const int dt = p->desc.dtype, mfma = p->desc.use_mfma != 0, accumulate = p->grad_accumulate;
+  switch (o.kind) {
+    case OP_MEMSET: return (accumulate && o.ms.p == (void*)p->grads) ? hipSuccess : hipMemsetAsync(o.ms.p, 0, o.ms.bytes, st);
+    case OP_COPY: return hipMemcpyAsync(o.cp.dst, o.cp.src, o.cp.bytes, hipMemcpyDeviceToDevice, st);
+    case OP_CONVERT: return launch_convert_input(o.cv, dt, st);
+    case OP_IGEMM: return launch_igemm(o.c, dt, o.epi, mfma, st, o.impl);
+    case OP_WGRAD:   // (not batched: counted as a launch of one)
+      if (o.impl == IMPL_WG3 && o.w.M > 0) { ++p->batch_counts[0]; ++p->batch_counts[1]; }
+      return launch_wgrad(o.w, dt, mfma, st, o.impl);
+    case OP_BW1: return launch_bw1(o.b1, dt, st);
+    case OP_BW1RED:
+      { Bw1RedGroup one; if (bw1_reduce_group_add(one, o.b1) && one.n > 0) { ++p->batch_counts[2]; ++p->batch_counts[3]; } }
+      return launch_bw1_reduce(o.b1, st);
+    case OP_RAWFIN: return launch_wg5_rawfin(o.rf, st);
+    case OP_FIN64: return launch_wg5_fin64(o.f64, st);
+    case OP_JOIN: if (o.epi == 1) lanes.join_pack(); else lanes.join_side(); return hipSuccess;
+    case OP_BNFIN: return launch_bn_finalize(o.bf, st);
+    case OP_BNBWD:
+      if (accumulate) { BnBwdFinalizeArgs bb = o.bb; bb.accumulate = 1; return launch_bn_bwd_finalize(bb, st); }
+      return launch_bn_bwd_finalize(o.bb, st);
+    case OP_POOL: return launch_maxpool_fwd(o.mp, dt, st);
+    case OP_POOLBWD: return launch_maxpool_bwd(o.mpb, dt, st);
+    case OP_BCE: return launch_bce_metrics(o.bce, dt, st);
+    case OP_PACK: return launch_pack(o.pk.descs, o.pk.prefix, o.pk.ndesc, o.pk.total_rows, dt, st, o.pk.tdescs, o.pk.tiles, o.pk.nt1, o.pk.nt9);
+    case OP_APPLYCORR: return launch_apply_corr(o.ac, dt, st);
+    case OP_UNPACK: return launch_unpack(o.pk.descs, o.pk.prefix, o.pk.ndesc, o.pk.total_rows, dt, o.pk.grad_scale, st, o.pk.tdescs, o.pk.tiles, o.pk.nt1, o.pk.nt9, accumulate);
+    default: known = false; return hipSuccess;
+  }
+}
+
+// launch_record with the family check around it.  The families noted by THIS launch: the thread's mask is set aside, read behind the launch and
+// merged back (it keeps what earlier launches noted, also when the launch fails).  Returns DMM_OK, or the error code with its message in `why`.
+int launch_checked(dmm_plan* p, const Op& o, size_t i, hipStream_t st, Lanes& lanes, std::string& why) {
+  const bool fam_check = (o.kind == OP_IGEMM || o.kind == OP_WGRAD) && o.impl != IMPL_AUTO;
+  const unsigned mask_before = g_impl_mask;
+  if (fam_check) g_impl_mask = 0;
+  bool known = true;
+  const hipError_t e = launch_record(p, o, st, lanes, known);
+  const unsigned ran = g_impl_mask;
+  if (fam_check) g_impl_mask = mask_before | ran;
+  if (!known) { why = "unknown op"; return DMM_ERR_STATE; }
+  if (e != hipSuccess) { why = "op " + std::to_string(i) + " kind " + std::to_string(o.kind) + ": " + hipGetErrorString(e); return DMM_ERR_HIP; }
+  if (fam_check && !(why = family_check(o, ran)).empty()) return DMM_ERR_STATE;
+  return DMM_OK;
+}
+}  // namespace
+
+// Launches ops[begin, end) in order (end = 0: to the end of the list).
+// capturing: the calls are being recorded into a hipGraph (no profiling, no bucket events: launch_list records those behind the graph).
+// Per record: offer it to a batch; send the batches off if it must not overtake them; route it to its lane; bracket, launch and check it; signal
+// its bucket.  ONE exit: whatever went wrong, the main stream is left ordered after whatever the side streams already got, then the error is reported.
+static int run_ops(dmm_plan* p, std::vector<Op>& ops, hipStream_t st, int prof_which = -1, size_t begin = 0, size_t end = 0, bool capturing = false) {
+  if (end == 0 || end > ops.size()) end = ops.size();
+  ProfilePass prof;
+  if (!prof.open(p, prof_which, ops.size())) return fail(DMM_ERR_HIP, "hipEventCreate failed");
+  const bool overlap = g_overlap_wgrad && !capturing && prof.production_schedule();
+  Lanes lanes{p, st};
+  if (const char* missing = overlap ? lanes.open_helpers() : nullptr) return fail(DMM_ERR_HIP, missing);
+  const bool mfma = p->desc.use_mfma != 0, batching = g_batch_wgrad != 0, batch_main = g_batch_wgrad == 1;
+  WgradBatches batches{p, ops, prof, (overlap && !batch_main) ? lanes.side : st};
+  int rc = DMM_OK; std::string why;   // the one error of the call and its message
+  auto failed = [&](int code, std::string msg) { rc = code; why = std::move(msg); };
+  auto flush_failed = [&](hipError_t e) { failed(DMM_ERR_HIP, std::string("grouped weight-gradient launch: ") + hipGetErrorString(e)); };
+  for (size_t i = begin; i < end; ++i) {
+    const Op& o = ops[i];
+    hipError_t e = hipSuccess;
+    const BatchKind bk = batching ? batch_kind(o, mfma) : BATCH_NONE;
+    WgradBatches::Offer took = WgradBatches::ALONE;
+    if (bk != BATCH_NONE) e = batches.offer(i, o, bk, took);
+    if (e == hipSuccess && took == WgradBatches::ALONE && flushes_batches(o)) e = batches.flush_all();
+    if (e != hipSuccess) { flush_failed(e); break; }
+    hipStream_t lst = st;
+    if (!lanes.enter(route(o, overlap, lanes.forked, batch_main), lst)) { failed(DMM_ERR_HIP, "hipEventCreate failed"); break; }
+    if (took == WgradBatches::MEMBER) {   // (its launch and its event pair come with the flush)
+      if (bk == BATCH_W3 && (e = batches.flush_w3_if_full()) != hipSuccess) { flush_failed(e); break; }
+      continue;
+    }
+    const bool sel = prof.selected(o);
+    if (sel) prof.begin(i, lst);
+    if (took == WgradBatches::ALONE && (rc = launch_checked(p, o, i, lst, lanes, why)) != DMM_OK) break;
+    if (sel) prof.end(i, lst);
+    if (lanes.pack_pending && o.leaf == 2) lanes.record_pack_join(lst);
+    if (o.signal >= 0 && !capturing) {  // a gradient bucket is final on this stream from here on
+      hipEvent_t be = plan_event(p, p->bucket_events, (size_t)o.signal);
+      if (be == nullptr) { failed(DMM_ERR_HIP, "hipEventCreate failed"); break; }
+      hipEventRecord(be, lst);
+    }
+  }
+  const hipError_t at_end = rc == DMM_OK ? batches.flush_all() : hipSuccess;
+  if (at_end != hipSuccess) flush_failed(at_end);
+  lanes.join_all();
+  return rc == DMM_OK ? DMM_OK : fail(rc, why);
+}
+
+// Every bucket event of the list, recorded on `st`: behind a graph replay all buckets are final at once.
+static int record_bucket_events(dmm_plan* p, const std::vector<Op>& ops, hipStream_t st) {
+  for (const Op& o : ops) {
+    if (o.signal < 0) continue;
+    hipEvent_t be = plan_event(p, p->bucket_events, (size_t)o.signal);
+    if (be == nullptr) return fail(DMM_ERR_HIP, "hipEventCreate failed");
+    HIPCHK(hipEventRecord(be, st));
+  }
+  return DMM_OK;
+}
+
+// Runs a whole launch list.  The launches [seg_begin, seg_end) - everything that does not touch a caller pointer - are captured ONCE
+// into a hipGraph the second time the list runs (on a plan-owned stream: the caller's may be the legacy default stream, which cannot
+// be captured) as ONE chain - the weight gradients are not sent to the side stream - and replayed by one call from then on; the few
+// launches in front of and behind the segment (input conversion, the stem convolution up to the join with the weight-packing stream,
+// the logits kernel; the loss kernel) take the caller's pointers and stay eager, so the graph never has to be patched or captured
+// again.  `which`: 0 training forward, 1 loss + backward.
+// Measured on MI355X / ROCm 7.2 (round 3, tools/host_bound.py): a replay enqueues a step in 0.5 ms of host time instead of 14 ms (C1) /
+// 25 ms (C2), but the GPU time of a step does not change (C1 18.6 ms, C2 31.7 ms replayed = the same launches eager on one stream):
+// the small configurations are bound by the latency of ~700 dependent tiny-grid kernels, not by the host, and the eager
+// two-stream schedule is faster than either (C1 16.5 ms, C2 29.5 ms).  A capture of the two-stream schedule (fork / join events
+// between the streams) replayed at 37 ms (C1) / 41 ms (C2) and returned different weight gradients than the eager launches, so the
+// capture is single-stream.  Hence OFF by default (dmm_set_option("graph", 1) / DMM_GRAPH=1): it frees the host, it does not buy time.
+static int launch_list(dmm_plan* p, int which, std::vector<Op>& ops, size_t seg_begin, size_t seg_end, hipStream_t st) {
+  dmm_plan::GraphCache& gc = p->graphs[which];
+  const bool profiling = p->prof_max_passes > 0 && p->prof_pass[which] < p->prof_max_passes;
+  if (gc.epoch != g_option_epoch) {  // an option changed (or the plan was re-bound) since the graph was captured
+    if (gc.exec) hipGraphExecDestroy((hipGraphExec_t)gc.exec);
+    gc = dmm_plan::GraphCache{nullptr, 0, g_option_epoch};
+  }
+  const bool want = g_graph && !(g_graph == 2 && which == 1) && !p->graph_failed && !profiling && !(which == 1 && p->dp_used) && seg_end > seg_begin + 8;
+  if (!want) return run_ops(p, ops, st, which);
+  if (gc.exec == nullptr && gc.nseen > 0) {  // the second run of the list: capture the segment
+    DevicePool* dp = pool_of(p->device);
+    if (dp == nullptr || pool_streams(dp, true) != hipSuccess) return fail(DMM_ERR_HIP, "capture stream");
+    hipStream_t cs = dp->capture;
+    p->used_capture = true;
+    hipGraph_t graph = nullptr;
+    hipGraphExec_t exec = nullptr;
+    bool ok = hipStreamBeginCapture(cs, hipStreamCaptureModeThreadLocal) == hipSuccess;
+    if (ok) {
+      const int rc = run_ops(p, ops, cs, -1, seg_begin, seg_end, true);
+      const bool ended = hipStreamEndCapture(cs, &graph) == hipSuccess && graph != nullptr;
+      ok = rc == DMM_OK && ended;
+      if (ok) ok = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0) == hipSuccess;
+      if (graph) hipGraphDestroy(graph);
+    }
+    static const bool gtrace = lab_flag("DMM_GRAPH_TRACE");
+    if (gtrace) fprintf(stderr, "[dmm] graph capture of list %d, launches [%zu, %zu): %s\n", which, seg_begin, seg_end, ok ? "ok" : "FAILED");
+    if (ok) gc.exec = (void*)exec;
+    else { (void)hipGetLastError(); p->graph_failed = true; }  // stay eager on this plan
+  }
+  gc.nseen = 1;
+  if (gc.exec == nullptr) return run_ops(p, ops, st, which);
+  int rc = seg_begin > 0 ? run_ops(p, ops, st, -1, 0, seg_begin) : DMM_OK;
+  if (rc) return rc;
+  HIPCHK(hipGraphLaunch((hipGraphExec_t)gc.exec, st));
+  p->graph_replays[which]++;
+  if (seg_end < ops.size()) { rc = run_ops(p, ops, st, -1, seg_end, ops.size()); if (rc) return rc; }
+  return which == 1 ? record_bucket_events(p, ops, st) : DMM_OK;
+}
 
 extern "C" {
 
@@ -212,10 +547,8 @@ int dmm_plan_destroy(dmm_plan* plan) {
       note(hipStreamSynchronize(dp->capture), "hipStreamSynchronize(capture stream)");
     }
     trace_destroy("graphs");
-    for (auto& gc : plan->graphs) {
-      for (auto& e : gc.entries) note(hipGraphExecDestroy((hipGraphExec_t)e.exec), "hipGraphExecDestroy");
-      gc.entries.clear();
-    }
+    for (auto& gc : plan->graphs)
+      if (gc.exec) { note(hipGraphExecDestroy((hipGraphExec_t)gc.exec), "hipGraphExecDestroy"); gc.exec = nullptr; }
     trace_destroy("events back to the pool");
     pool_return(dp, plan->fork_events, false);
     pool_return(dp, plan->join_events, false);
@@ -276,339 +609,6 @@ int dmm_plan_bind(dmm_plan* plan, void* workspace, size_t workspace_bytes, float
   HIPCHK(hipDeviceSynchronize());
   plan->bound = true;
   return DMM_OK;
-}
-
-// The invariant behind Op::impl: the family a plan recorded for a convolution launch (and shaped its launch list around: merged
-// phases, finish launches, compact gradients) is the family that took it.  `ran` = the families the launch noted.  Returns the
-// complaint, or an empty string.  The generic family beside another one is a launch that fell through; the ONE launch where that is
-// the design is wgp's two-segment form, whose 8-channel raw-input remainder stays with the generic kernel (launch_wgrad reports that
-// launch as wgp alone today; should the remainder ever be noted as well, the launch stays allowed - by this clause, not by silence).
-static std::string family_check(const Op& o, unsigned ran) {
-  if ((o.kind == OP_IGEMM ? o.c.M : o.w.M) <= 0) return std::string();   // an empty launch notes nothing
-  const bool recorded_ran = (ran >> o.impl) & 1u;
-  const bool generic_ran = (ran >> IMPL_GENERIC) & 1u;
-  const bool wgp_remainder = o.kind == OP_WGRAD && o.impl == IMPL_WGP && o.w.nseg == 2 && o.w.nphase == 0;
-  if (recorded_ran && (o.impl == IMPL_GENERIC || !generic_ran || wgp_remainder)) return std::string();
-  std::string names;
-  for (int f = 1; f < IMPL_COUNT; ++f)
-    if ((ran >> f) & 1u) names += (names.empty() ? "" : "+") + std::string(dmm_impl_name(f));
-  return std::string("launch '") + o.label + "': the plan recorded family " + dmm_impl_name(o.impl) + ", " + (names.empty() ? "none" : names) + " ran";
-}
-
-// Launches ops[begin, end) in order (end = 0: to the end of the list).
-// capturing: the calls are being recorded into a hipGraph (no profiling, no bucket events: launch_list records those behind the graph).
-static int run_ops(dmm_plan* p, std::vector<Op>& ops, hipStream_t st, int prof_which = -1, size_t begin = 0, size_t end = 0, bool capturing = false) {
-  if (end == 0 || end > ops.size()) end = ops.size();
-  const size_t ev_offset = 0;
-  const int dt = p->desc.dtype;
-  const bool mfma = p->desc.use_mfma != 0;
-  std::vector<void*>* evs = nullptr;
-  if (prof_which >= 0 && p->prof_max_passes > 0 && p->prof_pass[prof_which] < p->prof_max_passes) {
-    auto& sets = p->prof_events[prof_which];
-    const int pass = p->prof_pass[prof_which]++;
-    if ((int)sets.size() <= pass) sets.resize(pass + 1);
-    evs = &sets[pass];
-    const size_t need = 2 * (ops.size() + ev_offset);
-    DevicePool* pdp = pool_of(p->device);
-    while (evs->size() < need) {
-      hipEvent_t e = pdp ? pool_event(pdp, true) : nullptr;
-      if (e == nullptr) return fail(DMM_ERR_HIP, "hipEventCreate failed");
-      evs->push_back((void*)e);
-    }
-  }
-  // Gradient accumulation: the list is the one of the plain mode; the arena's memset is passed over (its record, label and
-  // profiling slot stay) and the two kinds of launch that write the arena take their accumulate form.
-  const bool accumulate = p->grad_accumulate;
-  const std::string& filt = p->prof_filter;
-  auto selected = [&](const Op& o) { return evs != nullptr && (filt.empty() || strncmp(o.label, filt.c_str(), filt.size()) == 0); };
-  // Overlap: a weight gradient only needs what the ops before it produced, and nothing but the final unpack reads it, so
-  // it goes to a low-priority side stream (fork event before, one join before unpack).  Late layers launch a few hundred
-  // workgroups of a few microseconds; two independent chains fill the CUs that one chain leaves idle.  Per-op profiling keeps
-  // everything on one stream so that the event pairs bracket each kernel alone; a FILTERED profile (one kernel class) runs
-  // as in production.
-  const bool overlap = g_overlap_wgrad && !capturing && (evs == nullptr || !filt.empty());
-  constexpr int nside = 1;  // 2 and 3 side streams measured: 0.3 / 0.6 ms slower; and the leaf chains need one FIFO
-  size_t nfork = 0;
-  bool forked = false;
-  DevicePool* dp = pool_of(p->device);
-  hipStream_t side_st = nullptr, pack_st = nullptr;
-  if (overlap) {
-    if (dp == nullptr || pool_streams(dp, false) != hipSuccess) return fail(DMM_ERR_HIP, "side stream");
-    side_st = dp->side; pack_st = dp->pack;
-    while ((int)p->join_events.size() < nside + 1) {  // [nside]: the pack stream's
-      hipEvent_t je = pool_event(dp, false);
-      if (je == nullptr) return fail(DMM_ERR_HIP, "hipEventCreate failed");
-      p->join_events.push_back((void*)je);
-    }
-    p->used_side = true;
-  }
-  // The pack stream: the launch that packs the weights of the LATE layers (leaf == 2) runs there beside the first
-  // layers of the forward pass; OP_JOIN with epi == 1 in front of the first late layer makes the main stream wait for it.
-  bool pack_pending = false;
-  auto join_pack = [&]() {
-    if (pack_pending) {
-      hipStreamWaitEvent(st, (hipEvent_t)p->join_events[nside], 0);
-      pack_pending = false;
-    }
-  };
-  auto join_side = [&]() {
-    if (forked) {
-      for (int k = 0; k < nside; ++k) {
-        hipEventRecord((hipEvent_t)p->join_events[k], side_st);
-        hipStreamWaitEvent(st, (hipEvent_t)p->join_events[k], 0);
-      }
-      forked = false;
-    }
-  };
-  auto join = [&]() { join_side(); join_pack(); };
-  // DMM_HOST_PROF=1: host time of the enqueue calls by op kind, printed when a list has run 20 times (tools/host_bound.py)
-  // Launch coalescing.  Within a dense block every dense 3x3 weight gradient reads only its own compact gradient, y1 and
-  // norm2 constants and writes its own packed gradient, and every bw1 reduction its own slots: consecutive ones are handed to ONE
-  // grouped launch (wg3.hip wg3_group_kernel, bw1.hip bw1_reduce_group_kernel).  A record that joins a batch is ordered behind its
-  // producer as before (fork event, stream wait) and notes its family; the launch goes out at the flush.  A batch is flushed
-  //   * before any other record of the weight-gradient side, before a join with that side, before a record that carries a bucket
-  //     signal (such a record is never batched) and at the end of the range;
-  //   * when a member does not fit (kernel instantiation, member cap, no workgroup left);
-  //   * wg3, lab builds only: as soon as the pending tiles reach DMM_WG3_BATCH_TILES.  Measured on the caller's stream (C2, profiles/r06/
-  //     ablations.txt): 2048 / 4096 / 8192 / 16384 tiles / no threshold = 25.00 / 24.88 / 24.78 / 24.78 / 24.71 ms per step against
-  //     25.13 ungrouped - a dense block's layers go out together whatever their map size, hence no threshold (0).
-  // "Weight-gradient side" is decided from the record alone, not from the streams of this call: the batches - and the bits - are the
-  // same with overlap_wgrad on or off, under capture and in a profile pass.  There the flushing member's event pair brackets the
-  // grouped launch, the other members record an empty pair.
-  const bool batch = g_batch_wgrad != 0;
-  static const long long w3_batch_tiles = lab_int("DMM_WG3_BATCH_TILES", 0);
-  Wg3Group w3g;
-  Bw1RedGroup rdg;
-  std::vector<size_t> w3_members, rd_members;
-  // The stream of the grouped launches.  They fill the chip on their own (a workgroup per compute unit, 8 waves and 86 KB of LDS
-  // each), so beside the data-gradient chain they do not fill its gaps, they hold its launches up: measured at C2 (profiles/r06),
-  // grouped on the weight-gradient stream the step is 0.1-0.2 ms SLOWER than the ungrouped launches there, on the caller's
-  // stream 0.2 ms faster.  Hence the caller's stream (batch_wgrad 1): the records of the two kinds then need no fork event either -
-  // also the ones that are launched alone (a bucket signal), which share the family's slot buffer with the batches.
-  const bool batch_main = g_batch_wgrad == 1;
-  hipStream_t batch_st = (overlap && !batch_main) ? side_st : st;
-  auto flush_members = [&](std::vector<size_t>& members, auto&& launch) -> hipError_t {
-    if (members.empty()) return hipSuccess;
-    for (size_t k = 0; k + 1 < members.size(); ++k)
-      if (selected(ops[members[k]])) {
-        hipEventRecord((hipEvent_t)(*evs)[2 * (ev_offset + members[k])], batch_st);
-        hipEventRecord((hipEvent_t)(*evs)[2 * (ev_offset + members[k]) + 1], batch_st);
-      }
-    const size_t last = members.back();
-    const bool sel_last = selected(ops[last]);
-    members.clear();
-    if (sel_last) hipEventRecord((hipEvent_t)(*evs)[2 * (ev_offset + last)], batch_st);
-    const hipError_t fe = launch();
-    if (sel_last) hipEventRecord((hipEvent_t)(*evs)[2 * (ev_offset + last) + 1], batch_st);
-    return fe;
-  };
-  auto flush_w3 = [&]() { return flush_members(w3_members, [&] { ++p->batch_counts[0]; return wg3_group_launch(w3g, batch_st); }); };
-  auto flush_rd = [&]() { return flush_members(rd_members, [&] { ++p->batch_counts[2]; return bw1_reduce_group_launch(rdg, batch_st); }); };
-  auto flush_all = [&]() { const hipError_t e1 = flush_w3(), e2 = flush_rd(); return e1 != hipSuccess ? e1 : e2; };
-  auto flush_failed = [&](hipError_t fe) { join(); return fail(DMM_ERR_HIP, std::string("grouped weight-gradient launch: ") + hipGetErrorString(fe)); };
-  static const bool host_prof = lab_flag("DMM_HOST_PROF");
-  static double hp_launch[32] = {0}, hp_fork[32] = {0};
-  static long hp_n[32] = {0}, hp_lists = 0;
-  auto now = [] { return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-  for (size_t i = begin; i < end; ++i) {
-    Op& o = ops[i];
-    hipError_t e = hipSuccess;
-    const double hp_t0 = host_prof ? now() : 0.0;
-    double hp_t1 = hp_t0;
-    // a record of the weight-gradient side that forks from the main stream; does it join a batch?
-    const bool forks = !o.chain && o.leaf != 2 && o.leaf != 3 && (o.kind == OP_WGRAD || o.leaf);
-    bool as_w3 = false, as_rd = false;
-    if (batch && forks && o.signal < 0) {
-      if (o.kind == OP_WGRAD && o.impl == IMPL_WG3 && mfma) {
-        as_w3 = wg3_group_add(w3g, o.w, dt);
-        if (!as_w3 && w3g.n > 0) {  // it does not fit: the batch goes first
-          if ((e = flush_w3()) != hipSuccess) return flush_failed(e);
-          as_w3 = wg3_group_add(w3g, o.w, dt);
-        }
-      } else if (o.kind == OP_BW1RED) {
-        as_rd = bw1_reduce_group_add(rdg, o.b1);
-        if (!as_rd) {
-          if ((e = flush_rd()) != hipSuccess) return flush_failed(e);
-          as_rd = bw1_reduce_group_add(rdg, o.b1);
-        }
-      }
-    }
-    const bool rd_added = as_rd && rdg.n > (int)rd_members.size();   // (false: a record without slots, nothing to add up)
-    if (!as_w3 && !as_rd && (forks || o.leaf == 3 || o.signal >= 0 || (o.kind == OP_JOIN && o.epi != 1)))
-      if ((e = flush_all()) != hipSuccess) return flush_failed(e);
-    // side-stream launches: weight gradients and the leaves of the backward graph (stem, raw-input branches)
-    hipStream_t lst = st;
-    if (overlap && o.leaf == 3 && forked) {
-      // a launch that continues a chain on the side stream (the second stream's encoder): everything it reads was produced by the
-      // launch in front of it on that stream, or before the chain's first launch (which forked from the main stream).  Only while
-      // the side stream is forked in THIS call: a range that starts mid-chain, or a join inside the chain, makes the next launch
-      // of the chain fork again like any leaf.
-      lst = side_st;
-    } else if (batch_main && forks && ((o.kind == OP_WGRAD && o.impl == IMPL_WG3) || o.kind == OP_BW1RED)) {
-      // (on the caller's stream, behind its producer: no fork)
-    } else if (overlap && !o.chain && (o.kind == OP_WGRAD || o.leaf)) {
-      if (nfork >= p->fork_events.size()) {
-        hipEvent_t fe = pool_event(dp, false);
-        if (fe == nullptr) { join(); return fail(DMM_ERR_HIP, "hipEventCreate failed"); }
-        p->fork_events.push_back((void*)fe);
-      }
-      lst = o.leaf == 2 ? pack_st : side_st;
-      hipEvent_t fe = (hipEvent_t)p->fork_events[nfork++];
-      hipEventRecord(fe, st);
-      hipStreamWaitEvent(lst, fe, 0);
-      if (o.leaf == 2) pack_pending = true; else forked = true;
-      if (host_prof) hp_t1 = now();
-    }
-    const bool sel = selected(o) && !as_w3 && !rd_added;   // (a batch member's pair is recorded at the flush)
-    if (sel) hipEventRecord((hipEvent_t)(*evs)[2 * (ev_offset + i)], lst);
-    // the families noted by THIS launch: the thread's mask is set aside, read behind the launch and merged back (family_check)
-    const bool fam_check = (o.kind == OP_IGEMM || o.kind == OP_WGRAD) && o.impl != IMPL_AUTO;
-    const unsigned mask_before = g_impl_mask;
-    if (fam_check) g_impl_mask = 0;
-    switch (o.kind) {
-      case OP_MEMSET: if (!(accumulate && o.ms.p == (void*)p->grads)) e = hipMemsetAsync(o.ms.p, 0, o.ms.bytes, lst); break;
-      case OP_COPY: e = hipMemcpyAsync(o.cp.dst, o.cp.src, o.cp.bytes, hipMemcpyDeviceToDevice, lst); break;
-      case OP_CONVERT: e = launch_convert_input(o.cv, dt, lst); break;
-      case OP_IGEMM: e = launch_igemm(o.c, dt, o.epi, mfma, lst, o.impl); break;
-      case OP_WGRAD:
-        if (as_w3) { note_impl(IMPL_WG3); w3_members.push_back(i); ++p->batch_counts[1]; break; }
-        if (o.impl == IMPL_WG3 && o.w.M > 0) { ++p->batch_counts[0]; ++p->batch_counts[1]; }
-        e = launch_wgrad(o.w, dt, mfma, lst, o.impl);
-        break;
-      case OP_BW1: e = launch_bw1(o.b1, dt, lst); break;
-      case OP_BW1RED:
-        if (as_rd) { if (rd_added) { rd_members.push_back(i); ++p->batch_counts[3]; } break; }
-        { Bw1RedGroup one; if (bw1_reduce_group_add(one, o.b1) && one.n > 0) { ++p->batch_counts[2]; ++p->batch_counts[3]; } }
-        e = launch_bw1_reduce(o.b1, lst);
-        break;
-      case OP_RAWFIN: e = launch_wg5_rawfin(o.rf, lst); break;
-      case OP_FIN64: e = launch_wg5_fin64(o.f64, lst); break;
-      case OP_JOIN: if (o.epi == 1) join_pack(); else join_side(); break;  // the main stream waits for what the side (epi 1: pack) stream has been given so far
-      case OP_BNFIN: e = launch_bn_finalize(o.bf, lst); break;
-      case OP_BNBWD:
-        if (accumulate) { BnBwdFinalizeArgs bb = o.bb; bb.accumulate = 1; e = launch_bn_bwd_finalize(bb, lst); }
-        else e = launch_bn_bwd_finalize(o.bb, lst);
-        break;
-      case OP_POOL: e = launch_maxpool_fwd(o.mp, dt, lst); break;
-      case OP_POOLBWD: e = launch_maxpool_bwd(o.mpb, dt, lst); break;
-      case OP_BCE: e = launch_bce_metrics(o.bce, dt, lst); break;
-      case OP_PACK: e = launch_pack(o.pk.descs, o.pk.prefix, o.pk.ndesc, o.pk.total_rows, dt, lst, o.pk.tdescs, o.pk.tiles, o.pk.nt1, o.pk.nt9); break;
-      case OP_APPLYCORR: e = launch_apply_corr(o.ac, dt, lst); break;
-      case OP_UNPACK: e = launch_unpack(o.pk.descs, o.pk.prefix, o.pk.ndesc, o.pk.total_rows, dt, o.pk.grad_scale, lst, o.pk.tdescs, o.pk.tiles, o.pk.nt1, o.pk.nt9, accumulate); break;
-      default: join(); return fail(DMM_ERR_STATE, "unknown op");
-    }
-    if (host_prof && o.kind < 32) { const double t2 = now(); hp_fork[o.kind] += hp_t1 - hp_t0; hp_launch[o.kind] += t2 - hp_t1; hp_n[o.kind]++; }
-    if (e != hipSuccess) join();  // leave the main stream ordered after whatever the side stream already got
-    if (e != hipSuccess && fam_check) g_impl_mask |= mask_before;  // (the thread's mask keeps what earlier launches noted)
-    if (e != hipSuccess) return fail(DMM_ERR_HIP, "op " + std::to_string(i) + " kind " + std::to_string(o.kind) + ": " + hipGetErrorString(e));
-    if (fam_check) {
-      const unsigned ran = g_impl_mask;
-      g_impl_mask = mask_before | ran;
-      const std::string why = family_check(o, ran);
-      if (!why.empty()) { join(); return fail(DMM_ERR_STATE, why); }
-    }
-    if (sel) hipEventRecord((hipEvent_t)(*evs)[2 * (ev_offset + i) + 1], lst);
-    if (as_w3 && w3_batch_tiles > 0 && w3g.tiles >= w3_batch_tiles && (e = flush_w3()) != hipSuccess) return flush_failed(e);
-    if (pack_pending && o.leaf == 2) hipEventRecord((hipEvent_t)p->join_events[nside], lst);
-    if (o.signal >= 0 && !capturing) {  // a gradient bucket is final on this stream from here on
-      while ((int)p->bucket_events.size() <= o.signal) {
-        hipEvent_t be = dp ? pool_event(dp, false) : nullptr;
-        if (be == nullptr) { join(); return fail(DMM_ERR_HIP, "hipEventCreate failed"); }
-        p->bucket_events.push_back((void*)be);
-      }
-      hipEventRecord((hipEvent_t)p->bucket_events[o.signal], lst);
-    }
-  }
-  {
-    const hipError_t fe = flush_all();
-    if (fe != hipSuccess) return flush_failed(fe);
-  }
-  join();
-  if (host_prof && ++hp_lists == 40) {
-    double tot = 0;
-    for (int k = 0; k < 32; ++k) tot += hp_launch[k] + hp_fork[k];
-    fprintf(stderr, "[host] 40 lists: %.2f ms of enqueue calls per list pair\n", tot / 20 / 1e3);
-    for (int k = 0; k < 32; ++k)
-      if (hp_n[k]) fprintf(stderr, "[host] op kind %2d: %6ld calls per pair, launch %.2f us each, fork events %.2f us each\n", k, hp_n[k] / 20,
-                           hp_launch[k] / hp_n[k], hp_fork[k] / hp_n[k]);
-  }
-  return DMM_OK;
-}
-
-// Every bucket event of the list, recorded on `st`: behind a graph replay all buckets are final at once.
-static int record_bucket_events(dmm_plan* p, const std::vector<Op>& ops, hipStream_t st) {
-  for (const Op& o : ops) {
-    if (o.signal < 0) continue;
-    while ((int)p->bucket_events.size() <= o.signal) {
-      DevicePool* dp = pool_of(p->device);
-      hipEvent_t be = dp ? pool_event(dp, false) : nullptr;
-      if (be == nullptr) return fail(DMM_ERR_HIP, "hipEventCreate failed");
-      p->bucket_events.push_back((void*)be);
-    }
-    HIPCHK(hipEventRecord((hipEvent_t)p->bucket_events[o.signal], st));
-  }
-  return DMM_OK;
-}
-
-// Runs a whole launch list.  The launches [seg_begin, seg_end) - everything that does not touch a caller pointer - are captured ONCE
-// into a hipGraph the second time the list runs (on a plan-owned stream: the caller's may be the legacy default stream, which cannot
-// be captured) as ONE chain - the weight gradients are not sent to the side stream - and replayed by one call from then on; the few
-// launches in front of and behind the segment (input conversion, the stem convolution up to the join with the weight-packing stream,
-// the logits kernel; the loss kernel) take the caller's pointers and stay eager, so the graph never has to be patched or captured
-// again.  `which`: 0 training forward, 1 loss + backward.
-// Measured on MI355X / ROCm 7.2 (round 3, tools/host_bound.py): a replay enqueues a step in 0.5 ms of host time instead of 14 ms (C1) /
-// 25 ms (C2), but the GPU time of a step does not change (C1 18.6 ms, C2 31.7 ms replayed = the same launches eager on one stream):
-// the small configurations are bound by the latency of ~700 dependent tiny-grid kernels, not by the host, and the eager
-// two-stream schedule is faster than either (C1 16.5 ms, C2 29.5 ms).  A capture of the two-stream schedule (fork / join events
-// between the streams) replayed at 37 ms (C1) / 41 ms (C2) and returned different weight gradients than the eager launches, so the
-// capture is single-stream.  Hence OFF by default (dmm_set_option("graph", 1) / DMM_GRAPH=1): it frees the host, it does not buy time.
-static int launch_list(dmm_plan* p, int which, std::vector<Op>& ops, size_t seg_begin, size_t seg_end, hipStream_t st) {
-  dmm_plan::GraphCache& gc = p->graphs[which];
-  const bool profiling = p->prof_max_passes > 0 && p->prof_pass[which] < p->prof_max_passes;
-  if (gc.epoch != g_option_epoch) {  // an option changed (or the plan was re-bound) since the graph was captured
-    for (auto& e : gc.entries) hipGraphExecDestroy((hipGraphExec_t)e.exec);
-    gc.entries.clear();
-    gc.nseen = 0;
-    gc.epoch = g_option_epoch;
-  }
-  const bool want = g_graph && !(g_graph == 2 && which == 1) && !p->graph_failed && !profiling && !(which == 1 && p->dp_used) && seg_end > seg_begin + 8;
-  if (!want) return run_ops(p, ops, st, which);
-  if (gc.entries.empty() && gc.nseen > 0) {  // the second run of the list: capture the segment
-    DevicePool* dp = pool_of(p->device);
-    if (dp == nullptr || pool_streams(dp, true) != hipSuccess) return fail(DMM_ERR_HIP, "capture stream");
-    hipStream_t cs = dp->capture;
-    p->used_capture = true;
-    hipGraph_t graph = nullptr;
-    hipGraphExec_t exec = nullptr;
-    bool ok = hipStreamBeginCapture(cs, hipStreamCaptureModeThreadLocal) == hipSuccess;
-    if (ok) {
-      const int rc = run_ops(p, ops, cs, -1, seg_begin, seg_end, true);
-      const bool ended = hipStreamEndCapture(cs, &graph) == hipSuccess && graph != nullptr;
-      ok = rc == DMM_OK && ended;
-      if (ok) ok = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0) == hipSuccess;
-      if (graph) hipGraphDestroy(graph);
-    }
-    gc.captures++;
-    static const bool gtrace = lab_flag("DMM_GRAPH_TRACE");
-    if (gtrace) fprintf(stderr, "[dmm] graph capture of list %d, launches [%zu, %zu): %s\n", which, seg_begin, seg_end, ok ? "ok" : "FAILED");
-    if (!ok) {
-      (void)hipGetLastError();
-      p->graph_failed = true;  // stay eager on this plan
-    } else {
-      dmm_plan::GraphEntry e;
-      for (int i = 0; i < 4; ++i) e.key[i] = nullptr;
-      e.exec = (void*)exec; e.stamp = 0;
-      gc.entries.push_back(e);
-    }
-  }
-  gc.nseen = 1;
-  if (gc.entries.empty()) return run_ops(p, ops, st, which);
-  int rc = seg_begin > 0 ? run_ops(p, ops, st, -1, 0, seg_begin) : DMM_OK;
-  if (rc) return rc;
-  HIPCHK(hipGraphLaunch((hipGraphExec_t)gc.entries[0].exec, st));
-  p->graph_replays[which]++;
-  if (seg_end < ops.size()) { rc = run_ops(p, ops, st, -1, seg_end, ops.size()); if (rc) return rc; }
-  return which == 1 ? record_bucket_events(p, ops, st) : DMM_OK;
 }
 
 int dmm_plan_forward(dmm_plan* plan, const float* stream_1, const float* stream_2, float* logits_out, int training, void* stream) {

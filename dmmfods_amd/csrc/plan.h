@@ -80,6 +80,17 @@ struct Op {
   Op() { memset(static_cast<void*>(this), 0, sizeof(*this)); signal = -1; impl = IMPL_AUTO; }
 };
 
+// What the launch-list executor (capi.cpp: run_ops) decides from a record ALONE: pure functions of the record and the mode flags of
+// the call - no plan, no stream, no runtime call - so that each fact is written once and a table of records can be walked through
+// them without a GPU (tools/hoststub/drive.cpp `route`, tests/test_enqueue_trace_cpu.py).
+#define DMM_EXECUTOR_PREDICATES 1
+enum BatchKind { BATCH_NONE = 0, BATCH_W3, BATCH_RD };   // the grouped launch a record may join: wg3.hip's, bw1.hip's reduction
+enum Lane { LANE_MAIN = 0, LANE_SIDE_CONTINUE, LANE_SIDE_FORK, LANE_PACK_FORK };
+bool side_forks(const Op& o);               // a record of the weight-gradient side that forks from the caller's stream
+BatchKind batch_kind(const Op& o, bool mfma);
+bool flushes_batches(const Op& o);          // the pending batches go out in front of this record (unless it joined one)
+Lane route(const Op& o, bool overlap, bool forked, bool batch_main);   // forked: the side stream is forked in this call; batch_main: batch_wgrad 1
+
 }  // namespace dmm
 
 // A contiguous range of the gradient arena (whole tensors) whose gradients become final at a known point of the backward
@@ -139,7 +150,7 @@ struct dmm_plan {
   int loss_kind = 0;          // 0 BCE, 1 focal (dmm_plan_set_loss)
   float loss_alpha[8] = {1, 1, 1, 1, 1, 1, 1, 1}, loss_gamma[8] = {2, 2, 2, 2, 2, 2, 2, 2};
   bool grad_accumulate = false;      // backward adds into the gradient arena instead of overwriting it (dmm_plan_set_grad_accumulate): a run-time
-                                     // property of the SAME launch list - run_ops skips the arena's memset and launches the arena's writers
+                                     // property of the SAME launch list - launch_record skips the arena's memset and launches the arena's writers
                                      // (OP_UNPACK, OP_BNBWD) in their accumulate form; survives dmm_plan_bind
   bool encoder_frozen = false;       // the encoder (features, stream_2_features, concat_module) is not trained (dmm_plan_set_encoder_frozen): the
                                      // backward list ends in front of the first encoder record, buckets and unpack tables hold trainable tensors
@@ -168,21 +179,17 @@ struct dmm_plan {
   bool used_side = false, used_capture = false;
   std::vector<void*> join_events;          // [0] side stream, [1] pack stream
   std::vector<void*> fork_events;
-  // hipGraph replay of a launch list (capi.cpp: launch_list): instantiated graphs keyed by the caller's pointers of the call
-  struct GraphEntry { const void* key[4]; void* exec; unsigned long long stamp; };
+  // hipGraph replay of a launch list (capi.cpp: launch_list): the one instantiated graph of the list's replayed segment
   struct GraphCache {
-    std::vector<GraphEntry> entries;
-    const void* seen[4][4] = {};   // the caller pointers of the last eager runs (a list is captured when its pointers come back)
-    int nseen = 0;
-    int captures = 0;
-    unsigned long long epoch = 0;  // option epoch the entries were captured under (dmm_set_option invalidates them)
+    void* exec = nullptr;          // hipGraphExec_t (null: not captured)
+    int nseen = 0;                 // the list has run eagerly since the last drop: the next run captures it
+    unsigned long long epoch = 0;  // option epoch the graph was captured under (dmm_set_option and dmm_plan_bind invalidate it)
   };
   GraphCache graphs[2];          // [0] training forward, [1] loss + backward
   bool graph_failed = false;     // a capture did not work on this plan: stay eager
   bool dp_used = false;          // a data-parallel reducer waits for bucket events: backward stays eager (events must be real)
-  unsigned long long graph_clock = 0;
   long long graph_replays[2] = {0, 0};
-  // launch coalescing (capi.cpp run_ops), summed over the plan's life: [0] wg3 launches (a grouped launch counts once; each comes with one
+  // launch coalescing (capi.cpp WgradBatches), summed over the plan's life: [0] wg3 launches (a grouped launch counts once; each comes with one
   // reduction), [1] the wg3 records they served, [2] bw1 reduction launches, [3] the bw1.reduce records they served (dmm_plan_wgrad_batch_counts)
   long long batch_counts[4] = {0, 0, 0, 0};
 };

@@ -28,6 +28,13 @@
 //                                                  Kernels do not run here but the runtime's memsets do: the gradient arena, filled with
 //                                                  a pattern, must keep it while the mode is on and read as zero behind a pass with it off;
 //                                                  both modes make the same launches from the same records.
+// And one walks a hand-made table of launch records through the executor's pure predicates (plan.h: side_forks, batch_kind,
+// flushes_batches, route) and prints what each answers:
+//   drive route                                    one line per record and combination of mode flags (tests/test_enqueue_trace_cpu.py)
+// DRIVE_TRACE_ENQUEUE=1 (any mode): every enqueue call the fake runtime's hook reports goes to stdout as one line -
+//   T launch <kernel> <gx> <gy> s<k> | T record e<j> s<k> | T wait e<j> s<k> | T memset <bytes> s<k> | T memcpy <bytes> s<k>
+// with streams and events numbered in the order they first appear (s0: the null stream), and a library call that fails as
+// `T error <code> <message>`.  The lines of a run ARE its schedule: two builds of the executor are compared by their hash.
 // DRIVE_OPTIONS_OFF=<name>[,<name>...] (any mode): dmm_set_option(name, 0) for each, before any plan is created.
 // DRIVE_NO_MFMA=1 (any mode): the description asks for use_mfma = 0.
 // DRIVE_DYN_SCALE=1 (life-cycle run and dump): the plan gets a dynamic loss scale (dmm_plan_set_dynamic_loss_scale, pointing into a
@@ -53,6 +60,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <map>
 #include <string>
 #include <vector>
 
@@ -214,10 +222,31 @@ bool batch_end_of_call(const char* what) {
   return ok;
 }
 
+// ---- DRIVE_TRACE_ENQUEUE: the enqueue calls as text (see the head of the file) ----
+struct EnqueueTrace {
+  bool on = false;
+  std::map<const void*, int> streams{{nullptr, 0}}, events;
+  static int ordinal(std::map<const void*, int>& seen, const void* h) { return seen.emplace(h, (int)seen.size()).first->second; }
+} g_enqueue;
+void drive_hook(int what, const char* kernel, unsigned gx, unsigned gy, const void* stream, const void* event) {
+  if (g_enqueue.on) {
+    const int s = EnqueueTrace::ordinal(g_enqueue.streams, stream);
+    const unsigned long long bytes = gx | (unsigned long long)gy << 32;
+    if (what == 0) printf("T launch %s %u %u s%d\n", kernel, gx, gy, s);
+    else if (what == 1 || what == 2) printf("T %s e%d s%d\n", what == 1 ? "record" : "wait", EnqueueTrace::ordinal(g_enqueue.events, event), s);
+    else printf("T %s %llu s%d\n", what == 3 ? "memset" : "memcpy", bytes, s);
+  }
+  batch_hook(what, kernel, gx, gy, stream, event);
+}
+
 #define MUST(call)                                                                           \
   do {                                                                                       \
     const int rc__ = (call);                                                                 \
-    if (rc__ != 0) { fprintf(stderr, "[drive] %s -> %d: %s\n", #call, rc__, dmm_last_error()); return 2; } \
+    if (rc__ != 0) {                                                                         \
+      if (g_enqueue.on) printf("T error %d %s\n", rc__, dmm_last_error());                   \
+      fprintf(stderr, "[drive] %s -> %d: %s\n", #call, rc__, dmm_last_error());              \
+      return 2;                                                                              \
+    }                                                                                        \
   } while (0)
 }  // namespace
 
@@ -289,8 +318,7 @@ static int one_life(const dmm_model_desc& d, int life) {
       if (o.kind == OP_WGRAD && o.impl == IMPL_WG3) { o.impl = IMPL_WG5; break; }
   const long l0 = fakehip_launches();
   g_watch = BatchWatch();
-  g_watch.plan = plan;
-  fakehip_set_hook(batch_hook);
+  g_watch.plan = plan;   // (from here on drive_hook hands the enqueue calls to batch_hook)
   // (every backward call runs the whole list - the external-gradient one but for the loss record; no forward list has such records)
 #define BACKWARD_DONE(what) do { batch_expect(plan->bwd); if (!batch_end_of_call(what)) return 2; } while (0)
   void* st = nullptr;  // the caller's stream: the null stream, as torch's default
@@ -408,7 +436,6 @@ static int one_life(const dmm_model_desc& d, int life) {
   MUST(dmm_plan_loss_backward(plan, logits, target, metrics, st));
   BACKWARD_DONE("end of the last step");
 #undef BACKWARD_DONE
-  fakehip_set_hook(nullptr);
   const BatchWatch watch = g_watch;
   g_watch.plan = nullptr;
   const long launches = fakehip_launches() - l0;
@@ -861,7 +888,33 @@ static int refuse_main() {
   return bad ? 1 : 0;
 }
 
+// ---- route: the executor's predicates over a table of records (built against a csrc that has none: the mode does not exist) ----
+#ifdef DMM_EXECUTOR_PREDICATES
+static int route_main() {
+  static const char* const kinds[] = {"MEMSET", "CONVERT", "IGEMM", "WGRAD", "BNFIN", "BNBWD", "POOL", "POOLBWD", "BCE", "PACK", "UNPACK", "COPY", "APPLYCORR",
+                                      "BW1", "JOIN", "BW1RED", "RAWFIN", "FIN64"};
+  static const char* const batch[] = {"none", "W3", "RD"};
+  static const char* const lanes[] = {"MAIN", "SIDE_CONTINUE", "SIDE_FORK", "PACK_FORK"};
+  for (int kind = OP_MEMSET; kind <= OP_FIN64; ++kind)
+    for (int leaf = 0; leaf < 4; ++leaf)
+      for (int chain = 0; chain < 2; ++chain)
+        for (int signal = -1; signal < 1; ++signal)
+          for (int impl : {(int)IMPL_WG3, (int)IMPL_WG5})
+            for (int epi = 0; epi < (kind == OP_JOIN ? 2 : 1); ++epi) {
+              Op o;
+              o.kind = kind; o.leaf = leaf; o.chain = chain; o.signal = signal; o.impl = impl; o.epi = epi;
+              printf("R %s leaf=%d chain=%d signal=%d impl=%s epi=%d : forks=%d flushes=%d batch=%s,%s route=", kinds[kind], leaf, chain, signal,
+                     impl == IMPL_WG3 ? "wg3" : "other", epi, (int)side_forks(o), (int)flushes_batches(o), batch[batch_kind(o, false)], batch[batch_kind(o, true)]);
+              for (int m = 0; m < 8; ++m) printf("%s%s", m ? "," : "", lanes[route(o, (m & 4) != 0, (m & 2) != 0, (m & 1) != 0)]);   // (overlap, forked, batch_main)
+              printf("\n");
+            }
+  return 0;
+}
+#endif
+
 int main(int argc, char** argv) {
+  g_enqueue.on = getenv("DRIVE_TRACE_ENQUEUE") != nullptr;
+  fakehip_set_hook(drive_hook);
   if (const char* off = getenv("DRIVE_OPTIONS_OFF")) {   // before any plan exists, in every mode
     const std::string s = off;
     for (size_t b = 0, e; b <= s.size(); b = e + 1) {
@@ -875,6 +928,9 @@ int main(int argc, char** argv) {
   if (argc > 1 && std::string(argv[1]) == "single") return single_main(argc, argv);
   if (argc > 1 && std::string(argv[1]) == "refuse") return refuse_main();
   if (argc > 1 && std::string(argv[1]) == "accum") return accum_main(argc, argv);
+#ifdef DMM_EXECUTOR_PREDICATES
+  if (argc > 1 && std::string(argv[1]) == "route") return route_main();
+#endif
   if (argc < 6) { fprintf(stderr, "usage: drive <arch> <dtype> <batch> <H> <W> [lives]\n"); return 64; }
   dmm_model_desc d;
   if (!fill_desc(argv[1], d)) { fprintf(stderr, "unknown arch %s\n", argv[1]); return 64; }

@@ -41,7 +41,8 @@ std::map<const void*, std::string>& kernel_names() { static auto* m = new std::m
 const char* kernel_name(const void* func) { auto it = kernel_names().find(func); return it == kernel_names().end() ? "?" : it->second.c_str(); }
 
 // The driver's observer (fakehip_set_hook): called for every kernel launch (what = 0: kernel name, grid), event record (1) and
-// stream wait (2) with the stream (null = the caller's) and the event - the order of enqueue calls is what a launch list IS here.
+// stream wait (2) with the stream (null = the caller's) and the event, and for every hipMemsetAsync (3) and hipMemcpyAsync (4) with
+// the stream and the byte count (gx: its low 32 bits, gy: the high ones) - the order of enqueue calls is what a launch list IS here.
 typedef void (*FakeHook)(int what, const char* kernel, unsigned gx, unsigned gy, const void* stream, const void* event);
 FakeHook g_hook = nullptr;
 
@@ -138,13 +139,25 @@ static bool g_skip_large_memset = false;
 extern "C" void fakehip_skip_large_memset(int on) { g_skip_large_memset = on != 0; }
 hipError_t hipMemset(void* p, int v, size_t n) { if (!(g_skip_large_memset && n >= (1ull << 30))) memset(p, v, n); return hipSuccess; }
 hipError_t hipMemsetAsync(void* p, int v, size_t n, hipStream_t st) {
-  { std::lock_guard<std::mutex> l(g_mu); FakeStream* s = S(st); if (!s) return hipErrorInvalidResourceHandle; ++s->pending; }
+  {
+    std::lock_guard<std::mutex> l(g_mu);
+    FakeStream* s = S(st);
+    if (!s) return hipErrorInvalidResourceHandle;
+    ++s->pending;
+    if (g_hook) g_hook(3, nullptr, (unsigned)n, (unsigned)((unsigned long long)n >> 32), st, nullptr);
+  }
   memset(p, v, n);
   return hipSuccess;
 }
 hipError_t hipMemcpy(void* d, const void* s, size_t n, hipMemcpyKind) { memmove(d, s, n); return hipSuccess; }
 hipError_t hipMemcpyAsync(void* d, const void* s, size_t n, hipMemcpyKind, hipStream_t st) {
-  { std::lock_guard<std::mutex> l(g_mu); FakeStream* fs = S(st); if (!fs) return hipErrorInvalidResourceHandle; ++fs->pending; }
+  {
+    std::lock_guard<std::mutex> l(g_mu);
+    FakeStream* fs = S(st);
+    if (!fs) return hipErrorInvalidResourceHandle;
+    ++fs->pending;
+    if (g_hook) g_hook(4, nullptr, (unsigned)n, (unsigned)((unsigned long long)n >> 32), st, nullptr);
+  }
   memmove(d, s, n);
   return hipSuccess;
 }
