@@ -1,0 +1,301 @@
+"""Exact operands for the convolution kernels: inputs on which every product and every partial sum is a small dyadic number, so
+that fp32 accumulation is exact in ANY order and rounding to f16 / bf16 is the identity.  A kernel then has to equal an fp64
+reference bit for bit - outputs, BatchNorm statistics, data gradients, both BatchNorm-backward sums and weight gradients - and a
+dropped row, a duplicated tile, a wrong tap or a padded lane that leaks is a nonzero difference, not 2e-4 of a tolerance.
+
+Needs torch on the CPU only (tools/gpu_lab.py launches on these operands; tests/test_exact_operands_cpu.py checks the conditions
+below for every case the GPU tests run, so that those can neither pass vacuously nor fail because of their own inputs).
+
+Recipe: x integers in [-3, 3]; scale, invstd in {0.5, 1, 2}; shift in {-1, 0, 1}; mean integers in [-2, 2]; dy integers in [-2, 2];
+yfwd even integers in [-4, 4]; q in {-1, 0, 1}; r in {-1, -0.5, 0, 0.5, 1}; gold integers in [-2, 2]; weights in {-1, 0, +1}.
+(The data gradient of the nearest-x2 upsampled 3x3 adds 4 x 9 taps per output channel into one element: with scale = 2 no weight
+tensor that covers every tap fits bf16's 8 bits.  Those cases draw scale from {0.5, 1} and dy from [-1, 1]: `narrow`.)
+
+Conditions, asserted by Operands.check() on the reference alone:
+ (a) every tensor a kernel stores in the storage type is representable there: the activation after the prologue, the output, the
+     stored data gradient dz * scale (+ gold), the effective gradient dy + q + r * yfwd;
+ (b) outputs, data gradients and weight gradients are exact in fp32 for any summation order: sum |term| / u < 2**24 per element, u
+     the common power-of-two step of the terms (the same convolution over the operands' absolute values);
+ (c) per-channel sums (stat_sum, stat_sq, red1, red2): chain * max |term| / u < 2**24, chain = the longest fp32 partial of a kernel
+     before it reaches fp64 (at most one 128-row tile; the generic kernel's pooled data gradient: 4 pixels per row, 512);
+ (d) at least 90 % of the output elements are nonzero;
+ and the weights: entries in {-1, 0, 1}, every (tap, input channel) pair nonzero in some output channel, every output channel
+ nonzero somewhere.
+
+The weights are as dense as (a) allows BY CONSTRUCTION (worst-case bounds from the per-channel maxima of the other operand, not
+luck): per output channel the |activation| maxima of its nonzero weights add up to at most the largest representable output, per
+input channel the |gradient| maxima likewise for the stored data gradient.  bf16 holds 8 significant bits, f16 11 - f16 weights for
+the data gradient are 8 times as dense; for the forward they are 4 times as dense, because (c) for stat_sq (128 y**2 / u**2 < 2**24)
+caps |y| / u near 2**8.5 whatever the storage type (the budget of 2**10 relies on signs cancelling; check() holds the actual values
+to (c))."""
+import functools
+from types import SimpleNamespace
+
+import torch
+import torch.nn.functional as F
+
+DT = {0: torch.float32, 1: torch.float16, 2: torch.bfloat16}
+SIG_BITS = {0: 24, 1: 11, 2: 8}        # significant bits of the storage type
+FWD_BITS = {0: 10, 1: 10, 2: 8}        # budget of |y| / u (see the module docstring on stat_sq)
+DENSITY_CAP = 0.75                     # keep a quarter of the weights zero wherever the budgets would allow all of them
+
+
+def _pick(g, values, shape):
+    v = torch.tensor(values, dtype=torch.float64)
+    return v[torch.randint(0, len(values), shape, generator=g)]
+
+
+def conv(a, w, c):
+    """The case's convolution on NCHW operands (any floating type)."""
+    if c.transposed:
+        return F.conv_transpose2d(a, w, stride=2, padding=1, output_padding=1)
+    if c.mode == 1:
+        return F.conv2d(F.interpolate(a, scale_factor=2, mode="nearest"), w, padding=c.pad)
+    if c.mode == 2:
+        return F.avg_pool2d(F.conv2d(a, w), 2, 2)
+    return F.conv2d(a, w, stride=c.stride, padding=c.pad)
+
+
+def out_hw(c):
+    if c.transposed or c.mode == 1:
+        return 2 * c.H, 2 * c.W
+    if c.mode == 2:
+        return c.H // 2, c.W // 2
+    return (c.H + 2 * c.pad - c.R) // c.stride + 1, (c.W + 2 * c.pad - c.S) // c.stride + 1
+
+
+def _tap_groups(c):
+    """Sets of taps that can meet in one output element.  ConvTranspose (3x3, stride 2): the output parities see 1, 2, 2 and 4 taps."""
+    T = c.R * c.S
+    if not c.transposed:
+        return [list(range(T))]
+    cls = {}
+    for ky in range(3):
+        for kx in range(3):
+            cls.setdefault((ky == 1, kx == 1), []).append(ky * 3 + kx)
+    return list(cls.values())
+
+
+def _prefix_within(key, wts, budget):
+    """Per row: the slots, in ascending order of `key`, whose running sum of `wts` stays within `budget` (a tensor per row)."""
+    order = torch.argsort(key, dim=1)
+    cs = torch.cumsum(torch.gather(wts, 1, order), dim=1)
+    keep = torch.zeros_like(key, dtype=torch.bool)
+    keep.scatter_(1, order, cs <= budget.view(-1, 1))
+    return keep
+
+
+def build_weights(g, c, amax, effmax, scale, ylim, glim):
+    """{-1, 0, 1} weights [Cout][Cin][T], as dense as the budgets allow: per output channel and tap group sum amax[cin] |w| <= ylim,
+    per input channel gain * scale[cin] * sum effmax[cout] |w| <= glim (None: no such bound).  The slots that cover every (tap, input
+    channel) pair and every output channel come first in every order, so they are the last to go."""
+    Cout, Cin, T = c.Cout, c.Cin, c.R * c.S
+    key = torch.rand(Cout, Cin, T, generator=g, dtype=torch.float64)
+    sel = key < DENSITY_CAP
+    ci, tt = torch.meshgrid(torch.arange(Cin), torch.arange(T), indexing="ij")
+    must = torch.zeros(Cout, Cin, T, dtype=torch.bool)
+    must[(ci * T + tt) % Cout, ci, tt] = True
+    co = torch.arange(Cout)
+    must[co, co % Cin, (co // Cin) % T] |= ~must.view(Cout, -1).any(dim=1)
+    key = key - must.double()
+    sel |= must
+    if ylim is not None:
+        for grp in _tap_groups(c):
+            k = key[:, :, grp].reshape(Cout, -1)
+            s = sel[:, :, grp].reshape(Cout, -1)
+            wts = amax.view(1, Cin, 1).expand(Cout, Cin, len(grp)).reshape(Cout, -1) * s
+            sel[:, :, grp] = (s & _prefix_within(k, wts, torch.full((Cout,), float(ylim), dtype=torch.float64))).view(Cout, Cin, len(grp))
+    if glim is not None:
+        k = key.permute(1, 0, 2).reshape(Cin, -1)
+        s = sel.permute(1, 0, 2).reshape(Cin, -1)
+        wts = effmax.view(1, Cout, 1).expand(Cin, Cout, T).reshape(Cin, -1) * s
+        keep = s & _prefix_within(k, wts, glim / scale)
+        sel = keep.view(Cin, Cout, T).permute(1, 0, 2).contiguous()
+    sign = _pick(g, [-1.0, 1.0], (Cout, Cin, T))
+    return sign * sel
+
+
+class Operands(SimpleNamespace):
+    def check(self):
+        """Conditions (a)-(d) and the weight coverage, on the reference alone.  Returns the measured figures."""
+        o, c = self, self.case
+        dt, lim = DT[c.dtype], float(2 ** 24)
+        fig = {}
+
+        def rep(name, t):
+            assert torch.equal(t.to(dt).double(), t), f"(a) {name} is not representable in {dt}: max |t| = {float(t.abs().max())}"
+        rep("activation", o.a)
+        rep("effective gradient", o.eff)
+        w3 = o.wslots
+        assert bool(((w3 == 0) | (w3.abs() == 1)).all()), "weights outside {-1, 0, 1}"
+        assert bool((w3 != 0).any(dim=0).all()), "a (tap, input channel) pair is zero in every output channel"
+        assert bool((w3 != 0).view(c.Cout, -1).any(dim=1).all()), "an output channel has no nonzero weight"
+        fig["density"] = float((w3 != 0).double().mean())
+        fig["nonzero_y"] = float((o.y != 0).double().mean())
+        assert fig["nonzero_y"] >= 0.9, f"(d) only {fig['nonzero_y']:.3f} of the outputs are nonzero"
+        aa = o.a.abs().requires_grad_(True)
+        wa = o.w.abs().requires_grad_(True)
+        ya = conv(aa, wa, c)
+        if "fwd" in o.parts:
+            rep("output", o.y)
+            fig["b_y"] = float(ya.detach().max()) / o.uy
+            fig["c_sum"] = o.chain * float(o.y.abs().max()) / o.uy
+            fig["c_sq"] = o.chain * float(o.y.abs().max()) ** 2 / o.uy ** 2
+        if o.backward:
+            (ya * o.eff.abs()).sum().backward()
+            if "wgrad" in o.parts:
+                fig["b_dw"] = float(wa.grad.max()) / (o.ua * o.udz)
+            if "dgrad" in o.parts:
+                rep("stored data gradient", o.gx)
+                fig["b_dz"] = float(aa.grad.max()) / o.udz
+                fig["c_red1"] = o.chain_red * float(o.dz.abs().max()) / o.udz
+                fig["c_red2"] = o.chain_red * float((o.dz * o.xhat).abs().max()) / (o.udz * 0.5)
+        for k, v in fig.items():
+            if k[:2] in ("b_", "c_"):
+                assert v < lim, f"({k[0]}) {k[2:]}: {v:.3g} >= 2**24"
+        return fig
+
+
+def make_operands(dtype, B, H, W, Cin, Cout, R, S, stride, pad, transposed=0, mode=0, bn=1, with_q=0, acc=0,
+                  parts=("fwd", "wgrad", "dgrad"), seed=0, chain=128, chain_red=128, fwd_bits=None):
+    """Operands and fp64 reference of one case.  parts: what the caller will launch and compare - "fwd" (output and statistics), "wgrad",
+    "dgrad" (stored data gradient, red1, red2); the weights are bounded only by what is stored.  chain / chain_red: the fp32 chain of
+    condition (c) for the forward statistics / the BatchNorm-backward sums; fwd_bits: log2 of the budget of |y| / u (default: FWD_BITS).
+    NCHW fp64 tensors on the CPU."""
+    c = SimpleNamespace(dtype=dtype, B=B, H=H, W=W, Cin=Cin, Cout=Cout, R=3 if transposed else R, S=3 if transposed else S,
+                        stride=stride, pad=pad, transposed=transposed, mode=mode, bn=bn)
+    parts = tuple(parts)
+    if not bn or (mode == 0 and not transposed and stride != 1):
+        parts = tuple(p for p in parts if p != "dgrad")     # as conv_case: no BN-fused data gradient for these
+    g = torch.Generator().manual_seed(seed)
+    narrow = mode == 1 and "dgrad" in parts
+    x = torch.randint(-3, 4, (B, Cin, H, W), generator=g).double()
+    scale = _pick(g, [0.5, 1.0] if narrow else [0.5, 1.0, 2.0], (Cin,))
+    shift = _pick(g, [-1.0, 0.0, 1.0], (Cin,))
+    mean = torch.randint(-2, 3, (Cin,), generator=g).double()
+    invstd = _pick(g, [0.5, 1.0, 2.0], (Cin,))
+    v = lambda t: t.view(1, -1, 1, 1)  # noqa: E731
+    z = x * v(scale) + v(shift)
+    a = F.relu(z) if bn else x.clone()
+    Ho, Wo = out_hw(c)
+    dyr = 1 if narrow else 2
+    dy = torch.randint(-dyr, dyr + 1, (B, Cout, Ho, Wo), generator=g).double()
+    yf = q = r = None
+    eff = dy
+    if with_q:
+        yf = 2.0 * torch.randint(-2, 3, (B, Cout, Ho, Wo), generator=g).double()
+        q = _pick(g, [-1.0, 0.0, 1.0], (Cout,))
+        r = _pick(g, [-1.0, -0.5, 0.0, 0.5, 1.0], (Cout,))
+        eff = dy + v(q) + v(r) * yf
+    gold = torch.randint(-2, 3, (B, Cin, H, W), generator=g).double() if acc else None
+    # steps of the stored values, and what the storage type holds of them
+    pool = 0.25 if mode == 2 else 1.0
+    ua = 0.5 if bn else 1.0
+    uy, udz = ua * pool, pool
+    ylim = uy * 2 ** (fwd_bits or min(SIG_BITS[dtype], FWD_BITS[dtype])) if "fwd" in parts else None
+    glim = None
+    if "dgrad" in parts:   # |gx| <= gain * scale * sum effmax |w| + |gold|, in steps of udz / 2
+        gain = 4.0 if mode == 1 else pool
+        glim = (0.5 * udz * 2 ** min(SIG_BITS[dtype], 11) - (2.0 if acc else 0.0)) / gain
+    amax = a.abs().amax(dim=(0, 2, 3))
+    effmax = eff.abs().amax(dim=(0, 2, 3))
+    wslots = build_weights(g, c, amax, effmax, scale, ylim, glim)      # [Cout][Cin][T]
+    w = wslots.view(Cout, Cin, c.R, c.S)
+    if transposed:
+        w = w.permute(1, 0, 2, 3).contiguous()
+    o = Operands(case=c, parts=parts, with_q=with_q, acc=acc, chain=chain, chain_red=chain_red, x=x, scale=scale, shift=shift, mean=mean, invstd=invstd, z=z,
+                 dy=dy, yf=yf, q=q, r=r, eff=eff, gold=gold, w=w, wslots=wslots, ua=ua, uy=uy, udz=udz, Ho=Ho, Wo=Wo,
+                 backward="wgrad" in parts or "dgrad" in parts)
+    o.xhat = (x - v(mean)) * v(invstd)
+    ar = a.clone().requires_grad_(o.backward)
+    wr = w.clone().requires_grad_(o.backward)
+    y = conv(ar, wr, c)
+    o.a, o.y = a, y.detach()
+    o.stat_sum, o.stat_sq = o.y.sum(dim=(0, 2, 3)), (o.y ** 2).sum(dim=(0, 2, 3))
+    if o.backward:
+        (y * eff).sum().backward()
+        o.dw = wr.grad
+        o.dz = ar.grad * (z > 0) if bn else ar.grad
+        o.gx = o.dz * v(scale) + (gold if acc else 0.0)
+        o.red1, o.red2 = o.dz.sum(dim=(0, 2, 3)), (o.dz * o.xhat).sum(dim=(0, 2, 3))
+    return o
+
+
+@functools.lru_cache(maxsize=2)
+def cached_operands(*args, **kw):
+    """make_operands, remembered for the last two cases (the GPU tests and the CPU test share a reference per case)."""
+    return make_operands(*args, **kw)
+
+
+# ------------------------------------------------------------------------------------------------ the cases of tests/test_exact_kernels_gpu.py
+# (shared with tests/test_exact_operands_cpu.py, which checks the conditions for every one of them without a GPU)
+# forward: family, (name, B, H, W, Cin, Cout, R, S, stride, pad, transposed, mode, bn) as CASES below, make_operands arguments per dtype
+# (9 x 128 (tap, channel) pairs over 32 output channels: covering every pair takes 36 weights per output channel, whose |activation|
+# maxima add up to ~150 - above the 128 that bf16 holds of |y| in steps of 0.5.  fwd_bits = 9 lets them in; the output is then
+# representable on the actual values - 36 to 90 terms of random sign, |y| <= 100 - which check() asserts, not by the worst case.)
+_B9 = {2: dict(fwd_bits=9)}
+FORWARD = [
+    ("pig", ("1x1 224->128 1x339x339", 1, 339, 339, 224, 128, 1, 1, 1, 0, 0, 0, 1), {}),
+    ("pig", ("1x1 72->256 3x150x150", 3, 150, 150, 72, 256, 1, 1, 1, 0, 0, 0, 1), {}),
+    ("pig", ("1x1 1288->128 2x130x130", 2, 130, 130, 1288, 128, 1, 1, 1, 0, 0, 0, 1), {}),
+    ("conv3", ("3x3 128->32 3x170x330", 3, 170, 330, 128, 32, 3, 3, 1, 1, 0, 0, 1), _B9),
+    ("conv3", ("7x7s2 8->64 1x530x1010", 1, 530, 1010, 8, 64, 7, 7, 2, 3, 0, 0, 0), {}),
+    ("cf", ("3x3 128->32 1x328x816", 1, 328, 816, 128, 32, 3, 3, 1, 1, 0, 0, 1), _B9),
+    ("cf", ("3x3 128->32 3x224x416", 3, 224, 416, 128, 32, 3, 3, 1, 1, 0, 0, 1), _B9),
+    ("cvw", ("convT 128->128 3x85x125", 3, 85, 125, 128, 128, 3, 3, 2, 1, 1, 0, 1), {}),
+    ("cvw", ("convT 256->256 3x61x93", 3, 61, 93, 256, 256, 3, 3, 2, 1, 1, 0, 1), {}),
+    ("cvp", ("convT 384->256 1x11x19", 1, 11, 19, 384, 256, 3, 3, 2, 1, 1, 0, 1), {}),
+    ("generic", ("pool2 1x1 128->64 2x12x20", 2, 12, 20, 128, 64, 1, 1, 1, 0, 0, 2, 1), {}),
+]
+
+# backward through backward_case: what, family, (B, H, W, Cin, Cout, R, S, pad, transposed, mode), the (with_q, acc) pairs
+BACKWARD = [
+    ("fused", "bw1", (1, 339, 339, 224, 128, 1, 1, 0, 0, 0), [(1, 1), (1, 0), (0, 1), (0, 0)]),
+    ("fused", "bw1", (1, 16, 24, 160, 128, 1, 1, 0, 0, 0), [(1, 1), (1, 0), (0, 1), (0, 0)]),
+    ("dgrad", "conv3", (2, 12, 20, 128, 32, 3, 3, 1, 0, 0), [(1, 0), (1, 1), (0, 0)]),
+    ("dgrad", "conv3", (2, 7, 9, 128, 32, 3, 3, 1, 0, 0), [(1, 0), (1, 1), (0, 0)]),
+    ("wgradT", "wg3", (2, 12, 20, 128, 32, 3, 3, 1, 0, 0), [(1, 0), (0, 0)]),
+    ("wgradT", "wg3", (3, 5, 3, 128, 32, 3, 3, 1, 0, 0), [(1, 0), (0, 0)]),
+    ("wgradT", "wg3", (1, 40, 60, 128, 32, 3, 3, 1, 0, 0), [(1, 0), (0, 0)]),
+    ("wgrad", "wgp/wgpw", (2, 12, 20, 128, 64, 3, 3, 1, 1, 0), [(1, 0), (0, 0)]),      # with_q 1: wgp, 0: wgpw
+    ("wgrad", "wgp/wgpw", (3, 5, 3, 128, 64, 3, 3, 1, 1, 0), [(1, 0), (0, 0)]),
+    ("wgrad", "wgp/wgpw", (1, 9, 17, 256, 128, 3, 3, 1, 1, 0), [(1, 0), (0, 0)]),
+    ("wgrad", "wgp/wgpw", (1, 24, 40, 256, 64, 3, 3, 1, 1, 0), [(1, 0), (0, 0)]),
+    ("dgrad", "cvp", (1, 9, 17, 256, 256, 3, 3, 1, 1, 0), [(0, 0)]),                   # cvd3_kernel: the ConvTranspose's nine taps ...
+    ("dgrad", "cvp", (1, 9, 7, 128, 64, 3, 3, 1, 0, 1), [(0, 0)]),                     # ... and the upsampled 3x3's sixteen merged taps
+    ("dgrad", "cvp", (2, 12, 20, 128, 64, 3, 3, 1, 0, 1), [(0, 0)]),
+    ("wgradT", "wg5", (1, 13, 21, 64, 3, 5, 5, 2, 0, 0), [(0, 0)]),
+    ("wgrad", "wg5", (2, 24, 40, 8, 64, 3, 3, 1, 0, 0), [(1, 0)]),                     # the 3x3 over the normalised raw input
+]
+STEM_WGRAD = ("7x7s2 8->64 2x32x48", 2, 32, 48, 8, 64, 7, 7, 2, 3, 0, 0, 0)          # wg5 through conv_case (no BatchNorm in front)
+CONV5_STATS = (1, 13, 21)                                                             # conv5_stats_case: B, H, W
+
+# the ragged and tail cases of tests/test_kernels_gpu.py (fp32, the generic kernel; beside tools/gpu_lab.py CASES)
+EXACT_KW = {   # per case name: what make_operands needs beside the shape
+    # 25 x 64 (tap, channel) pairs over 8 output channels: covering every pair takes 200 weights per output channel, more than the
+    # default budget of |y| / u <= 2**10 holds; fp32 storage has the bits, and check() holds the actual values to (c)
+    "5x5 64->8": dict(fwd_bits=11),
+    # the generic kernel's pooled data gradient adds the 4 pixels of a pooling window per row of its 128-row tile in fp32
+    "pool2 1x1 128->64": dict(chain_red=512),
+    "pool2 2x2 map": dict(chain_red=512),
+}
+RAGGED = [("1x1 tail M=35", 1, 5, 7, 24, 40, 1, 1, 1, 0, 0, 0, 1),
+          ("3x3 1-pixel", 1, 1, 1, 16, 8, 3, 3, 1, 1, 0, 0, 1),
+          ("5x5 N=8 tail", 3, 3, 5, 8, 8, 5, 5, 1, 2, 0, 0, 1),
+          ("convT 1x1 map", 2, 1, 1, 8, 8, 3, 3, 2, 1, 1, 0, 1),
+          ("pool2 2x2 map", 1, 2, 2, 16, 8, 1, 1, 1, 0, 0, 2, 1)]
+# name, B, H, W, Cin, Cout, R, S, stride, pad, transposed, mode, bn: the parity cases of tools/gpu_lab.py run_kernels
+CASES = [
+    ("1x1 72->32", 2, 12, 20, 72, 32, 1, 1, 1, 0, 0, 0, 1),
+    ("1x1 256->128", 1, 16, 24, 256, 128, 1, 1, 1, 0, 0, 0, 1),
+    ("1x1 64->256", 1, 8, 8, 64, 256, 1, 1, 1, 0, 0, 0, 1),
+    ("3x3 128->32", 2, 12, 20, 128, 32, 3, 3, 1, 1, 0, 0, 1),
+    ("3x3 32->8", 1, 9, 7, 32, 8, 3, 3, 1, 1, 0, 0, 1),
+    ("5x5 64->8", 1, 10, 14, 64, 8, 5, 5, 1, 2, 0, 0, 1),
+    ("7x7s2 8->64", 2, 32, 32, 8, 64, 7, 7, 2, 3, 0, 0, 0),
+    ("convT 64->64", 2, 6, 10, 64, 64, 3, 3, 2, 1, 1, 0, 1),
+    ("convT 16->16", 1, 5, 3, 16, 16, 3, 3, 2, 1, 1, 0, 1),
+    ("pool2 1x1 128->64", 2, 12, 20, 128, 64, 1, 1, 1, 0, 0, 2, 1),
+    ("up2 3x3 128->64", 1, 6, 10, 128, 64, 3, 3, 1, 1, 0, 1, 1),
+    ("up2 3x3 16->8", 2, 4, 4, 16, 8, 3, 3, 1, 1, 0, 1, 1),
+]
