@@ -125,8 +125,6 @@ def lib():
     L.dmm_grad_guard_scratch_bytes.restype = sz
     L.dmm_guard_state_init.argtypes = [vp, f32, i64, i32, vp]
     L.dmm_adam_step_guarded.argtypes = [vp, vp, vp, vp, i64, f32, f32, f32, f32, f32, f32, f32, f32, i32, vp, vp, vp]
-    L.dmm_adam_step_guarded_ranges.argtypes = [vp, vp, vp, vp, C.POINTER(i64), C.POINTER(i64), C.POINTER(i64), C.c_int,
-                                               f32, f32, f32, f32, f32, f32, f32, f32, i32, vp, vp, vp]
     L.dmm_plan_set_encoder_frozen.argtypes = [vp, C.c_int]
     L.dmm_adam_table_bytes.argtypes = [C.c_int, i64]
     L.dmm_adam_table_bytes.restype = sz
@@ -163,7 +161,7 @@ EXPORTS = [
     "dmm_plan_profile_collect", "dmm_adam_step", "dmm_conv_scratch_bytes", "dmm_conv_forward", "dmm_conv_wgrad",
     "dmm_conv_dgrad", "dmm_conv_wgrad_ex", "dmm_conv_dgrad_ex", "dmm_conv1x1_backward_fused", "dmm_conv5_wgrad_stats", "dmm_last_impl", "dmm_impl_name", "dmm_impl_mask",
     "dmm_grad_guard_scratch_bytes", "dmm_guard_state_init", "dmm_adam_step_guarded", "dmm_grad_sumsq", "dmm_plan_set_dynamic_loss_scale",
-    "dmm_plan_set_grad_accumulate", "dmm_plan_set_encoder_frozen", "dmm_adam_step_guarded_ranges",
+    "dmm_plan_set_grad_accumulate", "dmm_plan_set_encoder_frozen",
     "dmm_adam_table_bytes", "dmm_adam_table_init", "dmm_adam_step_segmented", "dmm_adam_step_guarded_segmented",
     "dmm_plan_wgrad_batch_counts", "dmm_conv_wgrad_grouped", "dmm_bw1_reduce_grouped",
 ]

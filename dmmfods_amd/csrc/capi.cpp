@@ -794,20 +794,6 @@ int dmm_plan_loss_metrics(dmm_plan* plan, const float* logits, const float* targ
   return DMM_OK;
 }
 
-int dmm_adam_step(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, int64_t n, float lr, float beta1, float beta2,
-                  float eps, float weight_decay, int64_t step, float grad_scale, void* stream) {
-  if (!params || !grads || !exp_avg || !exp_avg_sq || n < 0 || step < 1) return fail(DMM_ERR_INVALID, "bad Adam argument");
-  AdamArgs a;
-  a.p = params; a.g = grads; a.m = exp_avg; a.v = exp_avg_sq; a.n = (size_t)n;
-  a.beta1 = beta1; a.beta2 = beta2; a.eps = eps; a.weight_decay = weight_decay;
-  const double bc1 = 1.0 - std::pow((double)beta1, (double)step), bc2 = 1.0 - std::pow((double)beta2, (double)step);
-  a.step_size = (float)(lr / bc1);
-  a.bc2_sqrt = (float)std::sqrt(bc2);
-  a.grad_scale = grad_scale;
-  HIPCHK(launch_adam(a, (hipStream_t)stream));
-  return DMM_OK;
-}
-
 int dmm_plan_set_dynamic_loss_scale(dmm_plan* plan, const float* scale_dev) {
   if (!plan) return fail(DMM_ERR_INVALID, "null plan");
   if (((uintptr_t)scale_dev & 3) != 0) return fail(DMM_ERR_INVALID, "dynamic loss scale pointer must be 4-byte aligned");
@@ -873,79 +859,7 @@ int dmm_grad_sumsq(const float* grads, int64_t offset, int64_t count, int accumu
   return DMM_OK;
 }
 
-int dmm_adam_step_guarded(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, int64_t n, float lr, float beta1,
-                          float beta2, float eps, float weight_decay, float max_norm, float growth_factor, float backoff_factor,
-                          int32_t growth_interval, dmm_guard_state* state, void* scratch, void* stream) {
-  if (!params || !grads || !exp_avg || !exp_avg_sq || !state || !scratch) return fail(DMM_ERR_INVALID, "null argument of the guarded Adam step");
-  if (n < 0) return fail(DMM_ERR_INVALID, "n must be >= 0");
-  if ((((uintptr_t)grads) & 3) != 0 || (((uintptr_t)state) & 7) != 0 || (((uintptr_t)scratch) & 7) != 0)
-    return fail(DMM_ERR_INVALID, "misaligned gradient, state or scratch pointer");
-  if (!(growth_factor >= 1.f) || !std::isfinite(growth_factor)) return fail(DMM_ERR_INVALID, "growth_factor must be a finite number >= 1");
-  if (!(backoff_factor > 0.f) || !(backoff_factor <= 1.f)) return fail(DMM_ERR_INVALID, "backoff_factor must lie in (0, 1]");
-  if (growth_interval < 0) return fail(DMM_ERR_INVALID, "growth_interval must be >= 0");
-  if (std::isnan(max_norm)) return fail(DMM_ERR_INVALID, "max_norm is NaN");
-  if (!(beta1 >= 0.f && beta1 < 1.f) || !(beta2 >= 0.f && beta2 < 1.f)) return fail(DMM_ERR_INVALID, "betas must lie in [0, 1)");
-  hipStream_t st = (hipStream_t)stream;
-  GradSumsqArgs r;
-  r.g = grads; r.n = (size_t)n; r.partials = (double*)scratch; r.accumulate = 0;
-  HIPCHK(launch_grad_sumsq(r, st));
-  GuardFinalizeArgs f;
-  f.partials = (const double*)scratch; f.state = state; f.lr = lr; f.beta1 = beta1; f.beta2 = beta2; f.max_norm = max_norm;
-  f.growth_factor = growth_factor; f.backoff_factor = backoff_factor; f.growth_interval = growth_interval;
-  HIPCHK(launch_guard_finalize(f, st));
-  AdamArgs a;
-  a.p = params; a.g = grads; a.m = exp_avg; a.v = exp_avg_sq; a.n = (size_t)n;
-  a.beta1 = beta1; a.beta2 = beta2; a.eps = eps; a.weight_decay = weight_decay;
-  a.step_size = 0.f; a.bc2_sqrt = 1.f; a.grad_scale = 0.f;   // read from *state by the kernel
-  HIPCHK(launch_adam_guarded(a, state, st));
-  return DMM_OK;
-}
-
-int dmm_adam_step_guarded_ranges(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, const int64_t* offsets,
-                                 const int64_t* counts, const int64_t* t0, int nranges, float lr, float beta1, float beta2, float eps,
-                                 float weight_decay, float max_norm, float growth_factor, float backoff_factor, int32_t growth_interval,
-                                 dmm_guard_state* state, void* scratch, void* stream) {
-  // every refusal comes before the first HIP call
-  if (!params || !grads || !exp_avg || !exp_avg_sq || !offsets || !counts || !t0 || !state || !scratch)
-    return fail(DMM_ERR_INVALID, "null argument of the guarded Adam step over ranges");
-  if (nranges < 1) return fail(DMM_ERR_INVALID, "nranges must be >= 1");
-  if ((((uintptr_t)grads) & 3) != 0 || (((uintptr_t)state) & 7) != 0 || (((uintptr_t)scratch) & 7) != 0)
-    return fail(DMM_ERR_INVALID, "misaligned gradient, state or scratch pointer");
-  for (int i = 0; i < nranges; ++i) {
-    if (offsets[i] < 0 || counts[i] < 0) return fail(DMM_ERR_INVALID, "range " + std::to_string(i) + ": offset and count must be >= 0");
-    if (t0[i] < 0) return fail(DMM_ERR_INVALID, "range " + std::to_string(i) + ": t0 must be >= 0");
-    if (offsets[i] > INT64_MAX - counts[i]) return fail(DMM_ERR_INVALID, "range " + std::to_string(i) + ": offset + count overflows");
-    for (int k = 0; k < i; ++k)
-      if (offsets[i] < offsets[k] + counts[k] && offsets[k] < offsets[i] + counts[i])
-        return fail(DMM_ERR_INVALID, "ranges " + std::to_string(k) + " and " + std::to_string(i) + " overlap");
-  }
-  if (!(growth_factor >= 1.f) || !std::isfinite(growth_factor)) return fail(DMM_ERR_INVALID, "growth_factor must be a finite number >= 1");
-  if (!(backoff_factor > 0.f) || !(backoff_factor <= 1.f)) return fail(DMM_ERR_INVALID, "backoff_factor must lie in (0, 1]");
-  if (growth_interval < 0) return fail(DMM_ERR_INVALID, "growth_interval must be >= 0");
-  if (std::isnan(max_norm)) return fail(DMM_ERR_INVALID, "max_norm is NaN");
-  if (!(beta1 >= 0.f && beta1 < 1.f) || !(beta2 >= 0.f && beta2 < 1.f)) return fail(DMM_ERR_INVALID, "betas must lie in [0, 1)");
-  hipStream_t st = (hipStream_t)stream;
-  for (int i = 0; i < nranges; ++i) {   // the norm over the trainable ranges only: the first assigns the partials, the rest add
-    GradSumsqArgs r;
-    r.g = grads + offsets[i]; r.n = (size_t)counts[i]; r.partials = (double*)scratch; r.accumulate = i > 0 ? 1 : 0;
-    HIPCHK(launch_grad_sumsq(r, st));
-  }
-  GuardFinalizeArgs f;
-  f.partials = (const double*)scratch; f.state = state; f.lr = lr; f.beta1 = beta1; f.beta2 = beta2; f.max_norm = max_norm;
-  f.growth_factor = growth_factor; f.backoff_factor = backoff_factor; f.growth_interval = growth_interval;
-  HIPCHK(launch_guard_finalize(f, st));
-  for (int i = 0; i < nranges; ++i) {
-    AdamArgs a;
-    a.p = params + offsets[i]; a.g = grads + offsets[i]; a.m = exp_avg + offsets[i]; a.v = exp_avg_sq + offsets[i]; a.n = (size_t)counts[i];
-    a.beta1 = beta1; a.beta2 = beta2; a.eps = eps; a.weight_decay = weight_decay;
-    a.step_size = 0.f; a.bc2_sqrt = 1.f; a.grad_scale = 0.f;   // read from *state (t0 = 0) or formed from it (t0 > 0) by the kernel
-    if (t0[i] == 0) HIPCHK(launch_adam_guarded(a, state, st));
-    else HIPCHK(launch_adam_guarded_from(a, state, lr, t0[i], st));
-  }
-  return DMM_OK;
-}
-
-// ------------------------------------------------------------------------------------------------ parameter groups: segmented Adam
+// ------------------------------------------------------------------------------------------------ the Adam step: one kernel, four entry points
 namespace {
 hipError_t upload(void* dst, const void* src, size_t bytes, hipStream_t st);   // (below: complete when it returns)
 // What dmm_adam_table_init uploaded to each table_dev: the step calls take a device pointer and cannot read the table back without
@@ -997,12 +911,13 @@ int adam_seg_check(const char* who, const float* params, const float* grads, con
   return fail(DMM_ERR_INVALID, w + ": table_dev was not initialised by dmm_adam_table_init");
 }
 
+// table_dev == nullptr: the whole-range form, one implicit segment [0, n) of class 0
 void adam_seg_args(AdamSegArgs& a, float* params, const float* grads, float* exp_avg, float* exp_avg_sq, int64_t n, const void* table_dev,
                    int nsegs, const dmm_adam_class* classes, int nclasses) {
   a.p = params; a.g = grads; a.m = exp_avg; a.v = exp_avg_sq; a.n = (size_t)n;
   a.segs = (const AdamSegDev*)table_dev;
-  a.first = (const int*)((const uint8_t*)table_dev + (size_t)nsegs * sizeof(AdamSegDev));
-  a.nsegs = nsegs; a.nchunks = (int)adam_table_chunks(n); a.nclasses = nclasses;
+  a.first = table_dev ? (const int*)((const uint8_t*)table_dev + (size_t)nsegs * sizeof(AdamSegDev)) : nullptr;
+  a.nsegs = table_dev ? nsegs : 1; a.nchunks = (int)adam_table_chunks(n); a.nclasses = nclasses;
   a.vec_ok = (((uintptr_t)params | (uintptr_t)grads | (uintptr_t)exp_avg | (uintptr_t)exp_avg_sq) & 15) == 0 ? 1 : 0;
   a.grad_scale = 0.f; a.state = nullptr;
   for (int c = 0; c < ADAM_MAX_CLASSES; ++c) {
@@ -1017,7 +932,78 @@ void adam_seg_args(AdamSegArgs& a, float* params, const float* grads, float* exp
     k.decay = k.decoupled ? (float)(1.0 - (double)s.lr * (double)s.weight_decay) : 1.f;
   }
 }
+
+// Plain path: every class's step_size and bc2_sqrt at its own step count, step - t0, in double on the host.
+hipError_t adam_launch_plain(AdamSegArgs& a, int64_t step, float grad_scale, hipStream_t st) {
+  a.grad_scale = grad_scale;
+  for (int c = 0; c < a.nclasses; ++c) {
+    AdamSegClass& k = a.cls[c];
+    const int64_t t = step - k.t0;
+    k.active = t >= 1 ? 1 : 0;
+    if (!k.active) continue;
+    const double bc1 = 1.0 - std::pow((double)k.beta1, (double)t), bc2 = 1.0 - std::pow((double)k.beta2, (double)t);
+    k.step_size = (float)(k.lr / bc1);
+    k.bc2_sqrt = (float)std::sqrt(bc2);
+  }
+  return launch_adam_segmented(a, st);
+}
+
+// The refusals of the guard's own parameters, shared by the guarded entry points (who: "" or "<entry point>: ").
+int guard_check(const std::string& who, const float* grads, const dmm_guard_state* state, const void* scratch, float max_norm,
+                float growth_factor, float backoff_factor, int32_t growth_interval) {
+  if (!state || !scratch) return fail(DMM_ERR_INVALID, who + "null state or scratch");
+  if ((((uintptr_t)grads) & 3) != 0 || (((uintptr_t)state) & 7) != 0 || (((uintptr_t)scratch) & 7) != 0)
+    return fail(DMM_ERR_INVALID, who + "misaligned gradient, state or scratch pointer");
+  if (!(growth_factor >= 1.f) || !std::isfinite(growth_factor)) return fail(DMM_ERR_INVALID, "growth_factor must be a finite number >= 1");
+  if (!(backoff_factor > 0.f) || !(backoff_factor <= 1.f)) return fail(DMM_ERR_INVALID, "backoff_factor must lie in (0, 1]");
+  if (growth_interval < 0) return fail(DMM_ERR_INVALID, "growth_interval must be >= 0");
+  if (std::isnan(max_norm)) return fail(DMM_ERR_INVALID, "max_norm is NaN");
+  return DMM_OK;
+}
+
+// Guarded path: the norm over `runs` of the gradient arena (the first run assigns the partials, the rest add), the decision - one for all
+// classes; the step_size / bc2_sqrt it leaves in the block are class 0's at t0 = 0 - and the Adam launch, which reads grad_scale, the
+// step count and the skip from *state.
+hipError_t adam_launch_guarded(AdamSegArgs& a, const std::vector<std::pair<int64_t, int64_t>>& runs, float max_norm, float growth_factor,
+                               float backoff_factor, int32_t growth_interval, dmm_guard_state* state, void* scratch, hipStream_t st) {
+  for (size_t i = 0; i < runs.size(); ++i) {
+    GradSumsqArgs r;
+    r.g = a.g + runs[i].first; r.n = (size_t)runs[i].second; r.partials = (double*)scratch; r.accumulate = i > 0 ? 1 : 0;
+    if (hipError_t e = launch_grad_sumsq(r, st)) return e;
+  }
+  GuardFinalizeArgs f;
+  f.partials = (const double*)scratch; f.state = state; f.lr = a.cls[0].lr; f.beta1 = a.cls[0].beta1; f.beta2 = a.cls[0].beta2;
+  f.max_norm = max_norm; f.growth_factor = growth_factor; f.backoff_factor = backoff_factor; f.growth_interval = growth_interval;
+  if (hipError_t e = launch_guard_finalize(f, st)) return e;
+  a.state = state;
+  return launch_adam_segmented(a, st);
+}
 }  // namespace
+
+// The two whole-range entry points: one class filled from the scalars, no table.
+int dmm_adam_step(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, int64_t n, float lr, float beta1, float beta2,
+                  float eps, float weight_decay, int64_t step, float grad_scale, void* stream) {
+  if (!params || !grads || !exp_avg || !exp_avg_sq || n < 0 || step < 1) return fail(DMM_ERR_INVALID, "bad Adam argument");
+  const dmm_adam_class one = {lr, beta1, beta2, eps, weight_decay, 0, 0};
+  AdamSegArgs a;
+  adam_seg_args(a, params, grads, exp_avg, exp_avg_sq, n, nullptr, 1, &one, 1);
+  HIPCHK(adam_launch_plain(a, step, grad_scale, (hipStream_t)stream));
+  return DMM_OK;
+}
+
+int dmm_adam_step_guarded(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, int64_t n, float lr, float beta1,
+                          float beta2, float eps, float weight_decay, float max_norm, float growth_factor, float backoff_factor,
+                          int32_t growth_interval, dmm_guard_state* state, void* scratch, void* stream) {
+  if (!params || !grads || !exp_avg || !exp_avg_sq || !state || !scratch) return fail(DMM_ERR_INVALID, "null argument of the guarded Adam step");
+  if (n < 0) return fail(DMM_ERR_INVALID, "n must be >= 0");
+  if (int rc = guard_check("", grads, state, scratch, max_norm, growth_factor, backoff_factor, growth_interval)) return rc;
+  if (!(beta1 >= 0.f && beta1 < 1.f) || !(beta2 >= 0.f && beta2 < 1.f)) return fail(DMM_ERR_INVALID, "betas must lie in [0, 1)");
+  const dmm_adam_class one = {lr, beta1, beta2, eps, weight_decay, 0, 0};
+  AdamSegArgs a;
+  adam_seg_args(a, params, grads, exp_avg, exp_avg_sq, n, nullptr, 1, &one, 1);
+  HIPCHK(adam_launch_guarded(a, {{0, n}}, max_norm, growth_factor, backoff_factor, growth_interval, state, scratch, (hipStream_t)stream));
+  return DMM_OK;
+}
 
 size_t dmm_adam_table_bytes(int nsegs, int64_t n) {
   if (nsegs < 1 || n < 1 || n > (int64_t)INT32_MAX * ADAM_SEG_CHUNK) return 0;
@@ -1072,17 +1058,7 @@ int dmm_adam_step_segmented(float* params, const float* grads, float* exp_avg, f
   if (int rc = adam_seg_check("dmm_adam_step_segmented", params, grads, exp_avg, exp_avg_sq, n, table_dev, nsegs, classes, nclasses, &host)) return rc;
   AdamSegArgs a;
   adam_seg_args(a, params, grads, exp_avg, exp_avg_sq, n, table_dev, nsegs, classes, nclasses);
-  a.grad_scale = grad_scale;
-  for (int c = 0; c < nclasses; ++c) {   // dmm_adam_step's expressions, for the class's own step
-    AdamSegClass& k = a.cls[c];
-    const int64_t t = step - k.t0;
-    k.active = t >= 1 ? 1 : 0;
-    if (!k.active) continue;
-    const double bc1 = 1.0 - std::pow((double)k.beta1, (double)t), bc2 = 1.0 - std::pow((double)k.beta2, (double)t);
-    k.step_size = (float)(k.lr / bc1);
-    k.bc2_sqrt = (float)std::sqrt(bc2);
-  }
-  HIPCHK(launch_adam_segmented(a, (hipStream_t)stream));
+  HIPCHK(adam_launch_plain(a, step, grad_scale, (hipStream_t)stream));
   return DMM_OK;
 }
 
@@ -1091,28 +1067,12 @@ int dmm_adam_step_guarded_segmented(float* params, const float* grads, float* ex
                                     float growth_factor, float backoff_factor, int32_t growth_interval, dmm_guard_state* state,
                                     void* scratch, void* stream) {
   const char* who = "dmm_adam_step_guarded_segmented";
-  if (!state || !scratch) return fail(DMM_ERR_INVALID, std::string(who) + ": null state or scratch");
-  if ((((uintptr_t)state) & 7) != 0 || (((uintptr_t)scratch) & 7) != 0) return fail(DMM_ERR_INVALID, std::string(who) + ": misaligned state or scratch pointer");
-  if (!(growth_factor >= 1.f) || !std::isfinite(growth_factor)) return fail(DMM_ERR_INVALID, "growth_factor must be a finite number >= 1");
-  if (!(backoff_factor > 0.f) || !(backoff_factor <= 1.f)) return fail(DMM_ERR_INVALID, "backoff_factor must lie in (0, 1]");
-  if (growth_interval < 0) return fail(DMM_ERR_INVALID, "growth_interval must be >= 0");
-  if (std::isnan(max_norm)) return fail(DMM_ERR_INVALID, "max_norm is NaN");
+  if (int rc = guard_check(std::string(who) + ": ", grads, state, scratch, max_norm, growth_factor, backoff_factor, growth_interval)) return rc;
   AdamTableHost host;
   if (int rc = adam_seg_check(who, params, grads, exp_avg, exp_avg_sq, n, table_dev, nsegs, classes, nclasses, &host)) return rc;
-  hipStream_t st = (hipStream_t)stream;
-  for (size_t i = 0; i < host.runs.size(); ++i) {   // the norm over the segments only: the first run assigns the partials, the rest add
-    GradSumsqArgs r;
-    r.g = grads + host.runs[i].first; r.n = (size_t)host.runs[i].second; r.partials = (double*)scratch; r.accumulate = i > 0 ? 1 : 0;
-    HIPCHK(launch_grad_sumsq(r, st));
-  }
-  GuardFinalizeArgs f;   // the decision is one for all classes; the step_size / bc2_sqrt it leaves in the block are class 0's at t0 = 0
-  f.partials = (const double*)scratch; f.state = state; f.lr = classes[0].lr; f.beta1 = classes[0].beta1; f.beta2 = classes[0].beta2;
-  f.max_norm = max_norm; f.growth_factor = growth_factor; f.backoff_factor = backoff_factor; f.growth_interval = growth_interval;
-  HIPCHK(launch_guard_finalize(f, st));
   AdamSegArgs a;
   adam_seg_args(a, params, grads, exp_avg, exp_avg_sq, n, table_dev, nsegs, classes, nclasses);
-  a.state = state;   // grad_scale, the step counts and the skip are read from *state by the kernel
-  HIPCHK(launch_adam_segmented(a, st));
+  HIPCHK(adam_launch_guarded(a, host.runs, max_norm, growth_factor, backoff_factor, growth_interval, state, scratch, (hipStream_t)stream));   // the norm over the segments only
   return DMM_OK;
 }
 

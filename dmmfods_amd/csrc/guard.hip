@@ -3,9 +3,9 @@
 // the reference trains in fp32 and has neither: agents/Dense_U_Net_lidar_Agent.py:263-265.)
 //   grad_sumsq     : one streaming pass over (a range of) the gradient arena -> one fp64 partial sum of squares per workgroup
 //   guard_finalize : partials (fixed order) -> apply / skip, clip coefficient, Adam bias corrections of the APPLIED step, next scale
-//   adam_guarded   : adam_kernel's arithmetic with its scalars read from the state block; writes nothing on a skipped step
-//   adam_guarded_from : the same for a range whose own step count started late (dmm_adam_step_guarded_ranges, t0 > 0)
-//   adam_segmented : parameter groups and frozen gaps in ONE launch: walks the arena under a segment table (plain and guarded path)
+//   adam_segmented : THE Adam kernel (torch.optim.Adam semantics, amsgrad off; AdamW's decay per class).  It walks the arena under a
+//                    segment table - parameter groups and frozen gaps in one launch - or, without a table, one whole range; plain path
+//                    (scalars from the host) and guarded path (scalars from the state block; writes nothing on a skipped step)
 //   guard_init     : fills a state block (start of training, checkpoint load)
 // No floating-point atomics anywhere: a workgroup owns its partial, the finalize kernel adds the partials in a fixed tree, so the
 // norm, the decision and the step are bit-reproducible from run to run (and equal on every rank of a data-parallel job, which reads
@@ -78,7 +78,7 @@ __global__ __launch_bounds__(64) void guard_finalize_kernel(GuardFinalizeArgs a)
     g.found_inf = 1;
     g.grad_norm = (float)s;   // inf or NaN: says which
     g.clip_coef = 0.f;
-    g.grad_scale = 0.f;       // (adam_guarded_kernel does not read it on a skipped step)
+    g.grad_scale = 0.f;       // (the Adam kernel does not read it on a skipped step)
     g.skipped_steps += 1;
     g.growth_tracker = 0;
     const float ns = S * a.backoff_factor;
@@ -112,75 +112,19 @@ hipError_t launch_guard_finalize(const GuardFinalizeArgs& a, hipStream_t st) {
   return hipGetLastError();
 }
 
-// adam_kernel (pointwise.hip) with grad_scale, step_size and bc2_sqrt from the state block: same expressions, same order, same launch
-// geometry.  A skipped step returns before the first store - no NaN reaches p, m or v through a product with zero.
-__global__ __launch_bounds__(256) void adam_guarded_kernel(AdamArgs a, const dmm_guard_state* state) {
-  if (state->found_inf) return;
-  a.grad_scale = state->grad_scale;
-  a.step_size = state->step_size;
-  a.bc2_sqrt = state->bc2_sqrt;
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < a.n; i += (size_t)gridDim.x * blockDim.x) {
-    float g = a.g[i] * a.grad_scale;
-    float p = a.p[i];
-    if (a.weight_decay != 0.f) g = fmaf(a.weight_decay, p, g);
-    const float m = a.beta1 * a.m[i] + (1.f - a.beta1) * g;
-    const float v = a.beta2 * a.v[i] + (1.f - a.beta2) * g * g;
-    a.m[i] = m;
-    a.v[i] = v;
-    const float denom = sqrtf(v) / a.bc2_sqrt + a.eps;
-    a.p[i] = p - a.step_size * (m / denom);
-  }
-}
-
-hipError_t launch_adam_guarded(const AdamArgs& a, const dmm_guard_state* state, hipStream_t st) {
-  int grid = (int)((a.n + 255) / 256);
-  if (grid > 4096) grid = 4096;
-  if (grid < 1) grid = 1;
-  hipLaunchKernelGGL(adam_guarded_kernel, dim3(grid), dim3(256), 0, st, a, state);
-  return hipGetLastError();
-}
-
-// adam_guarded_kernel for a range of the arena that became trainable at applied step t0 > 0 (an encoder released after the decoder
-// has trained): torch counts steps per parameter, so the range is at step t - t0 with t = applied_steps, which guard_finalize has
-// already advanced for this step.  step_size and bc2_sqrt are formed here, in double, by guard_finalize's expressions (every thread
-// computes the same two numbers: a few hundred cycles against a streaming pass); grad_scale is the step's own, and the element
-// arithmetic is adam_guarded_kernel's.  A skipped step, or a count that is not positive (a state block set back behind t0), writes nothing.
-__global__ __launch_bounds__(256) void adam_guarded_from_kernel(AdamArgs a, const dmm_guard_state* state, float lr, long long t0) {
-  if (state->found_inf) return;
-  const long long t = (long long)state->applied_steps - t0;
-  if (t < 1) return;
-  const double bc1 = 1.0 - pow((double)a.beta1, (double)t), bc2 = 1.0 - pow((double)a.beta2, (double)t);
-  a.grad_scale = state->grad_scale;
-  a.step_size = (float)((double)lr / bc1);
-  a.bc2_sqrt = (float)sqrt(bc2);
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < a.n; i += (size_t)gridDim.x * blockDim.x) {
-    float g = a.g[i] * a.grad_scale;
-    float p = a.p[i];
-    if (a.weight_decay != 0.f) g = fmaf(a.weight_decay, p, g);
-    const float m = a.beta1 * a.m[i] + (1.f - a.beta1) * g;
-    const float v = a.beta2 * a.v[i] + (1.f - a.beta2) * g * g;
-    a.m[i] = m;
-    a.v[i] = v;
-    const float denom = sqrtf(v) / a.bc2_sqrt + a.eps;
-    a.p[i] = p - a.step_size * (m / denom);
-  }
-}
-
-hipError_t launch_adam_guarded_from(const AdamArgs& a, const dmm_guard_state* state, float lr, int64_t t0, hipStream_t st) {
-  int grid = (int)((a.n + 255) / 256);
-  if (grid > 4096) grid = 4096;
-  if (grid < 1) grid = 1;
-  hipLaunchKernelGGL(adam_guarded_from_kernel, dim3(grid), dim3(256), 0, st, a, state, lr, (long long)t0);
-  return hipGetLastError();
-}
-
-// ------------------------------------------------------------------------------------------------ segmented Adam
-// adam_kernel's element arithmetic (pointwise.hip), expression for expression, with the scalars of the element's class.  Its rounding
-// points are pinned: as adam_kernel, adam_guarded_kernel and adam_guarded_from_kernel are compiled, every product and sum of the
-// moment and denominator lines is rounded on its own and only the last line, p - step_size * (m / denom), is one fused operation.
-// Left to the compiler, the four-element form below fuses the moment lines as well (packed fma) and the results differ from the
-// single-range kernels in the last bit; so contraction is off here and the one fused operation is written out.  A decoupled class
-// multiplies p by its decay factor first (one rounding of its own) and has weight_decay == 0 here.
+// ------------------------------------------------------------------------------------------------ Adam
+// The project's Adam arithmetic for one element, with the scalars of the element's class.  This function IS its definition, rounding
+// points included (fp32 throughout, contraction off, so nothing is fused that is not written as an fma):
+//   g  = g * grad_scale                                  one rounding
+//   p  = p * decay                                       decoupled classes only (AdamW), one rounding; they have weight_decay == 0 here
+//   g  = fma(weight_decay, p, g)                         L2 classes with weight_decay != 0 only, one rounding
+//   m  = beta1 * m + (1 - beta1) * g                     four roundings: 1 - beta1, each product, the sum
+//   v  = beta2 * v + ((1 - beta2) * g) * g               five roundings: 1 - beta2, each of the three products, the sum
+//   d  = sqrt(v) / bc2_sqrt + eps                        three roundings: root, quotient, sum
+//   p  = fma(-step_size, m / d, p)                       two roundings: the quotient, then the ONE fused multiply-add
+// (step_size = lr / (1 - beta1^t) and bc2_sqrt = sqrt(1 - beta2^t) are formed in double and rounded to fp32 once, on the host or, guarded,
+// in the kernel.)  Checkpoints and the recorded bits of tests/golden/adam_bits_sha256.json depend on every line: left to the compiler's
+// contraction, the four-element form below would fuse the moment lines (packed fma) and change last bits.
 __device__ __forceinline__ void adam_seg_elem(float& p, float g, float& m_, float& v_, const AdamSegClass& c, float grad_scale) {
 #pragma clang fp contract(off)
   g = g * grad_scale;
@@ -216,9 +160,19 @@ __device__ __forceinline__ void adam_seg_vec(const AdamSegArgs& a, size_t i, con
 //     segment's class - the branch is uniform and no thread reads the table again;
 //   * otherwise a thread walks on from first[chunk] to its own elements: a vector that lies inside one segment still moves as 16 bytes,
 //     a vector across an edge, in a gap or past n goes element by element, each element under the class of its own segment.
+// Whole-range form (a.segs == nullptr; dmm_adam_step, dmm_adam_step_guarded): the table is one implicit segment [0, n) of class 0 and
+// neither segs nor first is read - every chunk but the last is the covered case, the ragged tail and arenas that are not 16-byte aligned
+// (a caller's offset pointers) the element case.
 // The classes sit in LDS (a thread's class index is not uniform at an edge).  Guarded path (a.state): a skipped step returns before
-// the first store; thread c forms class c's step_size / bc2_sqrt by adam_guarded_from_kernel's expressions, once per workgroup.
+// the first store - no NaN reaches p, m or v through a product with zero; torch counts steps per parameter, so a class that became
+// trainable at applied step t0 is at step t = applied_steps - t0 (guard_finalize has already advanced applied_steps for this step), and
+// thread c forms class c's step_size = (float)(lr / (1 - beta1^t)) and bc2_sqrt = (float)sqrt(1 - beta2^t) in double - guard_finalize's
+// expressions - once per workgroup; a class with t < 1 (a state block set back behind t0) writes nothing.
 // Every element is owned by one thread of one workgroup: no atomics, and the result does not depend on the grid.
+__device__ __forceinline__ AdamSegDev adam_seg_at(const AdamSegArgs& a, int s, long long n) {
+  return a.segs != nullptr ? a.segs[s] : AdamSegDev{0, n, 0, 0};
+}
+
 __global__ __launch_bounds__(256) void adam_segmented_kernel(AdamSegArgs a) {
   __shared__ AdamSegClass cls[ADAM_MAX_CLASSES];
   if (a.state != nullptr && a.state->found_inf) return;
@@ -246,24 +200,29 @@ __global__ __launch_bounds__(256) void adam_segmented_kernel(AdamSegArgs a) {
     __syncthreads();
   }
   const long long n = (long long)a.n;
-  for (long long ch = blockIdx.x; ch < a.nchunks; ch += gridDim.x) {
-    const long long c0 = ch * ADAM_SEG_CHUNK, c1 = c0 + ADAM_SEG_CHUNK;
-    int s = a.first[ch];
-    if (s < 0 || s >= a.nsegs) continue;
-    const long long sb = a.segs[s].begin, se = a.segs[s].end;
+  // (a 32-bit chunk counter keeps the loop's test on the scalar unit: nchunks < 2^31 and the grid is at most ADAM_SEG_MAX_GRID)
+  for (unsigned ch = blockIdx.x; ch < (unsigned)a.nchunks; ch += gridDim.x) {
+    const long long c0 = (long long)ch * ADAM_SEG_CHUNK, c1 = c0 + ADAM_SEG_CHUNK;
+    int s = 0, sc = 0;
+    long long sb = 0, se = n;                                 // the implicit segment of the whole-range form
+    if (a.segs != nullptr) {                                  // (uniform: the three fields are fetched together, one step behind first[ch])
+      s = a.first[ch];
+      if (s < 0 || s >= a.nsegs) continue;
+      sb = a.segs[s].begin; se = a.segs[s].end; sc = a.segs[s].cls;
+    }
     if (sb >= c1) continue;                                   // nothing trainable in this chunk
     const long long base = c0 + 4 * (long long)threadIdx.x;
     if (a.vec_ok && sb <= c0 && c1 <= se && se <= n) {        // one segment covers the chunk
-      const AdamSegClass& c = cls[a.segs[s].cls & (ADAM_MAX_CLASSES - 1)];
+      const AdamSegClass& c = cls[sc & (ADAM_MAX_CLASSES - 1)];
       if (c.active) adam_seg_vec(a, (size_t)base, c, grad_scale);
       continue;
     }
-    while (s < a.nsegs && a.segs[s].end <= base) ++s;
+    while (s < a.nsegs && adam_seg_at(a, s, n).end <= base) ++s;
     if (s >= a.nsegs) continue;
     {
-      const long long b = a.segs[s].begin, e = a.segs[s].end;
-      if (a.vec_ok && b <= base && base + 4 <= e && e <= n) {
-        const AdamSegClass& c = cls[a.segs[s].cls & (ADAM_MAX_CLASSES - 1)];
+      const AdamSegDev t = adam_seg_at(a, s, n);
+      if (a.vec_ok && t.begin <= base && base + 4 <= t.end && t.end <= n) {
+        const AdamSegClass& c = cls[t.cls & (ADAM_MAX_CLASSES - 1)];
         if (c.active) adam_seg_vec(a, (size_t)base, c, grad_scale);
         continue;
       }
@@ -271,10 +230,11 @@ __global__ __launch_bounds__(256) void adam_segmented_kernel(AdamSegArgs a) {
     for (int k = 0; k < 4; ++k) {
       const long long i = base + k;
       if (i >= n) break;
-      while (s < a.nsegs && a.segs[s].end <= i) ++s;
+      while (s < a.nsegs && adam_seg_at(a, s, n).end <= i) ++s;
       if (s >= a.nsegs) break;
-      if (a.segs[s].begin > i) continue;                      // a gap
-      const AdamSegClass& c = cls[a.segs[s].cls & (ADAM_MAX_CLASSES - 1)];
+      const AdamSegDev t = adam_seg_at(a, s, n);
+      if (t.begin > i) continue;                              // a gap
+      const AdamSegClass& c = cls[t.cls & (ADAM_MAX_CLASSES - 1)];
       if (!c.active) continue;
       float p = a.p[i], m = a.m[i], v = a.v[i];
       adam_seg_elem(p, a.g[i], m, v, c, grad_scale);

@@ -121,15 +121,6 @@ struct ApplyCorrArgs {
   int C, ldg, ldy;
 };
 
-struct AdamArgs {
-  float* p;
-  const float* g;
-  float* m;
-  float* v;
-  size_t n;
-  float beta1, beta2, eps, weight_decay, step_size, bc2_sqrt, grad_scale;
-};
-
 // ---- guarded optimiser step (guard.hip) ----
 constexpr int GUARD_PARTIALS = 512;  // workgroups of the arena reduction = fp64 partial sums in its scratch: two per compute unit
 struct GradSumsqArgs {
@@ -138,7 +129,7 @@ struct GradSumsqArgs {
   double* partials;   // GUARD_PARTIALS doubles; workgroup w owns partials[w]
   int accumulate;     // 0: partials[w] = sum of this range's share; 1: += (a later range of the same step, e.g. the next gradient bucket)
 };
-// ---- segmented Adam: parameter groups in one launch (guard.hip) ----
+// ---- Adam: one kernel under a segment table (parameter groups in one launch) or over one whole range (guard.hip) ----
 constexpr int ADAM_MAX_CLASSES = DMM_ADAM_MAX_CLASSES;
 constexpr int ADAM_SEG_CHUNK = 1024;   // elements per chunk of the table = one 16-byte vector per thread of a workgroup
 constexpr int ADAM_SEG_MAX_GRID = 2048;
@@ -161,7 +152,8 @@ struct AdamSegArgs {
   float* m;
   float* v;
   size_t n;
-  const AdamSegDev* segs;   // nsegs, sorted, disjoint, inside [0, n)
+  const AdamSegDev* segs;   // nsegs, sorted, disjoint, inside [0, n); nullptr: the whole-range form, one implicit segment [0, n) of
+                            // class 0 (nsegs = 1, first is not read)
   const int* first;         // nchunks: index of the first segment whose end lies behind the chunk's first element (nsegs: none)
   int nsegs, nchunks, nclasses;
   int vec_ok;               // the four arenas are 16-byte aligned
@@ -253,12 +245,10 @@ hipError_t launch_bn_bwd_finalize(const BnBwdFinalizeArgs& a, hipStream_t st);
 hipError_t launch_maxpool_fwd(const MaxpoolArgs& a, int dtype, hipStream_t st);
 hipError_t launch_maxpool_bwd(const MaxpoolBwdArgs& a, int dtype, hipStream_t st);
 hipError_t launch_bce_metrics(const BceArgs& a, int dtype, hipStream_t st);
-hipError_t launch_adam(const AdamArgs& a, hipStream_t st);
 hipError_t launch_grad_sumsq(const GradSumsqArgs& a, hipStream_t st);
 hipError_t launch_guard_finalize(const GuardFinalizeArgs& a, hipStream_t st);
-hipError_t launch_adam_guarded(const AdamArgs& a, const dmm_guard_state* state, hipStream_t st);  // a.grad_scale / step_size / bc2_sqrt: from *state
-// the same step for a range that became trainable at applied step t0 > 0: its own Adam step count is applied_steps - t0
-hipError_t launch_adam_guarded_from(const AdamArgs& a, const dmm_guard_state* state, float lr, int64_t t0, hipStream_t st);
+// the one Adam launch.  a.state == nullptr: every class's step_size / bc2_sqrt / active and a.grad_scale come filled; a.state set: the
+// kernel reads grad_scale and the skip from *state and forms each class's step_size / bc2_sqrt at its own count, applied_steps - t0
 hipError_t launch_adam_segmented(const AdamSegArgs& a, hipStream_t st);
 hipError_t launch_guard_init(dmm_guard_state* dev, float scale, int64_t applied, int32_t tracker, hipStream_t st);
 hipError_t launch_apply_corr(const ApplyCorrArgs& a, int dtype, hipStream_t st);

@@ -4,7 +4,6 @@
 //   bn_bwd_finalize : (sum dz, sum dz*x) -> dgamma, dbeta and the deferred per-channel correction (q, r)
 //   maxpool_fwd/bwd : 3x3 s2 p1 max pooling fused with the BN+ReLU in front of it (first-max argmax saved)
 //   bce_metrics     : BCE-with-logits (sum reduction), d(loss)/d(logit), IoU / accuracy counts
-//   adam            : flat fused Adam (torch.optim.Adam semantics, amsgrad off)
 //   pack / unpack   : OIHW fp32 master weights <-> K-chunked compute layout [chunk][Npad][BK]
 #include <type_traits>
 
@@ -476,29 +475,6 @@ hipError_t launch_bce_metrics(const BceArgs& a, int dtype, hipStream_t st) {
   if (dtype == DT_F16) hipLaunchKernelGGL(bce_metrics_kernel<f16>, grid, dim3(256), 0, st, a);
   else if (dtype == DT_BF16) hipLaunchKernelGGL(bce_metrics_kernel<bf16>, grid, dim3(256), 0, st, a);
   else hipLaunchKernelGGL(bce_metrics_kernel<float>, grid, dim3(256), 0, st, a);
-  return hipGetLastError();
-}
-
-// ---------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void adam_kernel(AdamArgs a) {
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < a.n; i += (size_t)gridDim.x * blockDim.x) {
-    float g = a.g[i] * a.grad_scale;
-    float p = a.p[i];
-    if (a.weight_decay != 0.f) g = fmaf(a.weight_decay, p, g);
-    const float m = a.beta1 * a.m[i] + (1.f - a.beta1) * g;
-    const float v = a.beta2 * a.v[i] + (1.f - a.beta2) * g * g;
-    a.m[i] = m;
-    a.v[i] = v;
-    const float denom = sqrtf(v) / a.bc2_sqrt + a.eps;
-    a.p[i] = p - a.step_size * (m / denom);
-  }
-}
-
-hipError_t launch_adam(const AdamArgs& a, hipStream_t st) {
-  int grid = (int)((a.n + 255) / 256);
-  if (grid > 4096) grid = 4096;
-  if (grid < 1) grid = 1;
-  hipLaunchKernelGGL(adam_kernel, dim3(grid), dim3(256), 0, st, a);
   return hipGetLastError();
 }
 

@@ -17,8 +17,9 @@ Parameter groups (``FusedAdam(model, param_groups=[...])``, as torch.optim.Adam 
 rate than the decoder, no weight decay on BatchNorm weights and biases - ``fine_tune_groups``) and decoupled weight decay
 (``decoupled_weight_decay=True``: AdamW's rule).  Groups interleave tensor by tensor in the arena, so the step is ONE launch of the
 segmented kernel (dmm_adam_step_segmented / dmm_adam_step_guarded_segmented) under a device table of (begin, count, class)
-segments; a class is a (group, step origin) pair and carries its hyper-parameters with every call.  Without either keyword the
-optimiser makes exactly the calls it made before there were groups."""
+segments; a class is a (group, step origin) pair and carries its hyper-parameters with every call.  An optimiser without
+either keyword is an optimiser with one group: while nothing is or was frozen its step is the whole-arena call (dmm_adam_step /
+dmm_adam_step_guarded: the same kernel without a table), with a frozen or released encoder it is the same one launch under a table."""
 import ctypes as C
 import math
 
@@ -186,7 +187,8 @@ class FusedAdam:
         self.model = model
         self.defaults = dict(lr=lr, betas=tuple(betas), eps=eps, weight_decay=weight_decay, amsgrad=False)
         self._params = list(model.parameters())
-        # Groups: None and no decoupled decay -> the single-group optimiser as it always was (same entry points, same launches).
+        # An optimiser without param_groups is an optimiser with one group.  _grouped only says which checkpoint format it keeps:
+        # without either keyword the groups carry no "decoupled_weight_decay" key, betas stay as loaded, and segments() is None.
         self._grouped = param_groups is not None or bool(decoupled_weight_decay)
         if self._grouped:
             self.defaults["decoupled_weight_decay"] = bool(decoupled_weight_decay)
@@ -211,7 +213,7 @@ class FusedAdam:
         self._sig = tuple(p.requires_grad for p in self._params)
         self._ranges = None
         self._model_sig = None   # the model's own record of the flags (an object replaced on every change) when _ranges was built
-        # grouped only: [begin, count, class] over the arena, the (group, t0) of every class, and the device table built from them
+        # [begin, count, class] over the arena, the (group, t0) of every class, and the device table built from them
         self._segments = self._classes = self._table = None
 
     _GROUP_KEYS = ("lr", "betas", "eps", "weight_decay", "decoupled_weight_decay")
@@ -305,8 +307,7 @@ class FusedAdam:
             off += n
         if not self._ranges:
             raise ValueError("no parameter of the model is trainable")
-        if self._grouped:
-            self._build_segments(sig)
+        self._build_segments(sig)
 
     def _build_segments(self, sig):
         """The segment list of the trainable set: a class is a (group, step origin) pair, adjacent tensors of one class merge.  The
@@ -412,63 +413,33 @@ class FusedAdam:
         if self.exp_avg.device != m.param_arena.device:
             self.exp_avg = self.exp_avg.to(m.param_arena.device)
             self.exp_avg_sq = self.exp_avg_sq.to(m.param_arena.device)
-        if self._grouped:
-            return self._step_grouped(grad_scale)
-        g = self.param_groups[0]
-        if self._guard is not None:
-            return self._step_guarded(g, grad_scale)
-        self._sync_trainable(look=False)
-        self.step_count += 1
-        for off, n, t0 in self._ranges:   # one launch per trainable run (one, over the whole arena, when nothing is frozen)
-            _lib.check(_lib.lib().dmm_adam_step(
-                m.param_arena.data_ptr() + 4 * off, m.grad_arena.data_ptr() + 4 * off, self.exp_avg.data_ptr() + 4 * off,
-                self.exp_avg_sq.data_ptr() + 4 * off, n, float(g["lr"]), float(g["betas"][0]), float(g["betas"][1]), float(g["eps"]),
-                float(g["weight_decay"]), self.step_count - t0, float(grad_scale), _lib.stream_ptr()))
-
-    def _step_grouped(self, grad_scale):
-        """Parameter groups: one segmented Adam launch (guarded: the reductions and the finalize in front of it), whatever the number
-        of groups and frozen ranges."""
-        m, gd, L = self.model, self._guard, _lib.lib()
-        n = m.param_arena.numel()
+        gd, L = self._guard, _lib.lib()
         if gd is not None and grad_scale != 1.0:
             raise ValueError("grad_scale is not available on the guarded path (the loss scaler divides its scale out itself)")
+        n = m.param_arena.numel()
         self._sync_trainable(look=False)
-        table, classes = self._ensure_table(), self._class_array()
-        arenas = (m.param_arena.data_ptr(), m.grad_arena.data_ptr(), self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(), n,
-                  table.data_ptr(), len(self._segments), classes, len(classes))
+        arenas = (m.param_arena.data_ptr(), m.grad_arena.data_ptr(), self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(), n)
+        whole = not self._grouped and self._ranges == [[0, n, 0]]
+        if whole:
+            # Whole arena: no groups, nothing is or ever was frozen - one class, no table.
+            g = self.param_groups[0]
+            arenas += (float(g["lr"]), float(g["betas"][0]), float(g["betas"][1]), float(g["eps"]), float(g["weight_decay"]))
+        else:
+            # Table: groups, frozen ranges, step origins - one launch under the segment table, the classes by value.
+            classes = self._class_array()
+            arenas += (self._ensure_table().data_ptr(), len(self._segments), classes, len(classes))
         if gd is None:
             self.step_count += 1
-            _lib.check(L.dmm_adam_step_segmented(*arenas, self.step_count, float(grad_scale), _lib.stream_ptr()))
+            step = L.dmm_adam_step if whole else L.dmm_adam_step_segmented
+            _lib.check(step(*arenas, self.step_count, float(grad_scale), _lib.stream_ptr()))
             return
+        # Guarded: arena reduction(s) -> decision -> Adam, no host synchronisation.  In a data-parallel job call it after
+        # GradAllReduce.wait(works): every rank then reads the same summed arena and takes the same decision.
         state = gd._materialize(m.param_arena.device)
         scratch = gd._scratch_for(n)
-        _lib.check(L.dmm_adam_step_guarded_segmented(*arenas, float(self.max_grad_norm or 0.0), gd.growth_factor, gd.backoff_factor,
-                                                     gd.growth_interval, state.data_ptr(), scratch.data_ptr(), _lib.stream_ptr()))
-
-    def _step_guarded(self, g, grad_scale):
-        """Arena reduction -> decision -> Adam, three launches, no host synchronisation.  In a data-parallel job call it after
-        GradAllReduce.wait(works): every rank then reads the same summed arena and takes the same decision."""
-        if grad_scale != 1.0:
-            raise ValueError("grad_scale is not available on the guarded path (the loss scaler divides its scale out itself)")
-        m, gd = self.model, self._guard
-        n = m.param_arena.numel()
-        state = gd._materialize(m.param_arena.device)
-        scratch = gd._scratch_for(n)
-        self._sync_trainable(look=False)
-        if self._ranges != [[0, n, 0]]:   # something is or was frozen: norm and step over the trainable ranges, each at its own step count
-            k = len(self._ranges)
-            offs, cnts, t0s = ((C.c_int64 * k)(*(r[j] for r in self._ranges)) for j in range(3))
-            _lib.check(_lib.lib().dmm_adam_step_guarded_ranges(
-                m.param_arena.data_ptr(), m.grad_arena.data_ptr(), self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(), offs, cnts, t0s, k,
-                float(g["lr"]), float(g["betas"][0]), float(g["betas"][1]), float(g["eps"]), float(g["weight_decay"]),
-                float(self.max_grad_norm or 0.0), gd.growth_factor, gd.backoff_factor, gd.growth_interval,
-                state.data_ptr(), scratch.data_ptr(), _lib.stream_ptr()))
-            return
-        _lib.check(_lib.lib().dmm_adam_step_guarded(
-            m.param_arena.data_ptr(), m.grad_arena.data_ptr(), self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(), n,
-            float(g["lr"]), float(g["betas"][0]), float(g["betas"][1]), float(g["eps"]), float(g["weight_decay"]),
-            float(self.max_grad_norm or 0.0), gd.growth_factor, gd.backoff_factor, gd.growth_interval,
-            state.data_ptr(), scratch.data_ptr(), _lib.stream_ptr()))
+        step = L.dmm_adam_step_guarded if whole else L.dmm_adam_step_guarded_segmented
+        _lib.check(step(*arenas, float(self.max_grad_norm or 0.0), gd.growth_factor, gd.backoff_factor, gd.growth_interval,
+                        state.data_ptr(), scratch.data_ptr(), _lib.stream_ptr()))
 
     # ---- torch.optim.Adam-compatible checkpoint format ----
     def state_dict(self):

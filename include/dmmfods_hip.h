@@ -163,8 +163,9 @@ int dmm_plan_set_grad_accumulate(dmm_plan* plan, int accumulate);
  *     in a training forward, as torch's do with requires_grad = False.
  * Legal only between dmm_plan_create and dmm_plan_bind: the call runs the sizing pass again (dmm_plan_workspace_bytes is that of the
  * mode and never larger than the default's); a bound plan returns DMM_ERR_STATE, a null plan DMM_ERR_INVALID.  The setting survives
- * dmm_plan_bind.  0 on a fresh plan changes nothing.  The optimiser must leave the frozen ranges alone: dmm_adam_step_guarded_ranges,
- * or dmm_adam_step per range. */
+ * dmm_plan_bind.  0 on a fresh plan changes nothing.  The optimiser must leave the frozen ranges alone: the segmented
+ * calls (dmm_adam_step_segmented / dmm_adam_step_guarded_segmented) under a table of the trainable ranges, one class per step origin
+ * (they replace the guarded step over ranges that earlier versions of this header declared), or dmm_adam_step per range. */
 int dmm_plan_set_encoder_frozen(dmm_plan* plan, int frozen);
 
 /* Data-parallel training (new here; the reference's torch.distributed import, graphs/models/Dense_U_Net_lidar.py:7, is unused):
@@ -210,8 +211,9 @@ int dmm_plan_wgrad_batch_counts(const dmm_plan* plan, long long counts[4]);
 
 /* Flat fused Adam over n fp32 elements, one parameter group (amsgrad unsupported): torch.optim.Adam's single-tensor arithmetic in
  * fp32, weight_decay added to the gradient (L2, not decoupled), the bias corrections of `step` (1-based) formed on the host in
- * double.  Every gradient is multiplied by grad_scale first.  One launch; several groups, or frozen ranges in between: the
- * segmented calls below. */
+ * double.  Every gradient is multiplied by grad_scale first.  One launch of the library's one Adam kernel in its
+ * whole-range form (no table; 16-byte accesses when the four pointers are 16-byte aligned, element by element otherwise); several
+ * groups, or frozen ranges in between: the segmented calls below, the same kernel under a table. */
 int dmm_adam_step(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, int64_t n, float lr, float beta1,
                   float beta2, float eps, float weight_decay, int64_t step, float grad_scale, void* stream);
 
@@ -254,19 +256,6 @@ int dmm_guard_state_init(dmm_guard_state* dev, float init_scale, int64_t applied
 int dmm_adam_step_guarded(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, int64_t n, float lr, float beta1,
                           float beta2, float eps, float weight_decay, float max_norm, float growth_factor, float backoff_factor,
                           int32_t growth_interval, dmm_guard_state* state, void* scratch, void* stream);
-/* The guarded step over `nranges` disjoint ranges [offsets[i], offsets[i] + counts[i]) of the arenas (elements): what lies outside
- * them - a frozen encoder's parameters and moments - is neither read for the norm nor written, whatever weight_decay is.  Enqueues
- * one reduction per range (the first assigns the partials, the rest add), ONE finalize (the rule above, one decision for all ranges)
- * and one Adam launch per range.  t0[i] = the applied-step count at which range i became trainable: torch counts steps per
- * parameter, so the range's Adam step is applied_steps - t0[i] (a range released at step k starts at t = 1 with its zero moments,
- * not with the bias corrections of step k + 1, which would make its first updates about lr (1 - beta1) / sqrt(1 - beta2) = 3.2 lr).
- * t0[i] == 0 launches the kernel of dmm_adam_step_guarded; t0[i] > 0 a variant that forms step_size and bc2_sqrt for its own count
- * on the device, in fp64, from state->applied_steps.  Refuses, before any HIP call: a null pointer, nranges < 1, a negative offset,
- * count or t0, overlapping ranges, and what dmm_adam_step_guarded refuses.  scratch: >= dmm_grad_guard_scratch_bytes(0). */
-int dmm_adam_step_guarded_ranges(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, const int64_t* offsets,
-                                 const int64_t* counts, const int64_t* t0, int nranges, float lr, float beta1, float beta2, float eps,
-                                 float weight_decay, float max_norm, float growth_factor, float backoff_factor, int32_t growth_interval,
-                                 dmm_guard_state* state, void* scratch, void* stream);
 /* The reduction alone, on elements [offset, offset + count) of `grads`: scratch = (accumulate ? scratch : 0) + partial sums of the
  * range.  dmm_adam_step_guarded runs it once over the whole arena; a data-parallel trainer can run it per gradient bucket behind
  * that bucket's all-reduce instead (not wired up yet).  Also what the unit tests and the cost measurement call. */
@@ -314,7 +303,8 @@ int dmm_adam_step_segmented(float* params, const float* grads, float* exp_avg, f
  * their classes (the first assigns the partials, the rest add; nothing frozen: one reduction), ONE finalize fed classes[0]'s lr and
  * betas - so step_size and bc2_sqrt in the state block describe class 0 at t0 = 0 and are not what the other classes use - and the
  * one segmented Adam launch, which forms step_size and bc2_sqrt of every class on the device, in fp64, from
- * state->applied_steps - t0 (the expressions of dmm_adam_step_guarded_ranges), and writes nothing on a skipped step.
+ * t = state->applied_steps - t0 - step_size = (float)(lr / (1 - beta1^t)), bc2_sqrt = (float)sqrt(1 - beta2^t), the finalize kernel's
+ * expressions - and writes nothing on a skipped step or for a class with t < 1.
  * Refuses what dmm_adam_step_segmented and dmm_adam_step_guarded refuse (there is no step argument). */
 int dmm_adam_step_guarded_segmented(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, int64_t n,
                                     const void* table_dev, int nsegs, const dmm_adam_class* classes, int nclasses, float max_norm,

@@ -15,6 +15,11 @@ built with this tree's driver and fake runtime:
 so the split is shown to make the parent's calls, call for call.  A change that alters the schedule ON PURPOSE renews the file the
 same way from its own build (and says so); any other change leaves it alone.
 
+Renewed once since, from the tree that made adam_segmented_kernel the library's only Adam kernel: the two rows that take an
+optimiser step (DRIVE_FREEZE=1; DRIVE_DYN_SCALE=1 DRIVE_GROUPS=1) changed in their Adam launch lines - kernel name and grid - and the
+DRIVE_FREEZE row lost one grad_sumsq launch per life, because the driver's two adjacent trainable ranges are one run under a segment
+table; the other eleven hashes are those of 138dbf9.  profiles/r09/adam_trace_diff.txt holds the line-by-line comparison.
+
 The second test pins the pure predicates the executor routes by (plan.h: side_forks, batch_kind, flushes_batches, route): `drive route`
 walks a table of records through them, and the expected answers are written out here from the expressions run_ops had at 138dbf9."""
 import hashlib

@@ -1,4 +1,4 @@
-"""Frozen encoder (dmm_plan_set_encoder_frozen, dmm_adam_step_guarded_ranges, model.freeze_encoder, FusedAdam's trainable
+"""Frozen encoder (dmm_plan_set_encoder_frozen, the segmented Adam calls over the trainable ranges, model.freeze_encoder, FusedAdam's trainable
 ranges), everything that needs no GPU: the ABI contract, the buckets and sizes of an unbound frozen plan, the Python surface on a
 CPU-resident model, the optimiser's checkpoint format, and the sanitizer harness with DRIVE_FREEZE=1."""
 import ctypes as C
@@ -51,7 +51,7 @@ def test_new_symbols_are_declared_and_exported(lib):
     hdr = open(os.path.join(ROOT, "include", "dmmfods_hip.h")).read()
     declared = set(re.findall(r"\b(dmm_[a-z0-9_]+)\s*\(", hdr)) - {"dmm_status"}
     L = lib.lib()
-    for sym in ("dmm_plan_set_encoder_frozen", "dmm_adam_step_guarded_ranges"):
+    for sym in ("dmm_plan_set_encoder_frozen", "dmm_adam_step_segmented", "dmm_adam_step_guarded_segmented"):
         assert sym in declared and sym in lib.EXPORTS and hasattr(L, sym), sym
     assert not [s for s in sorted(declared) if not hasattr(L, s)]
     assert set(lib.EXPORTS) <= declared
@@ -77,28 +77,35 @@ def test_set_encoder_frozen_contract_without_a_gpu(lib):
 
 
 def test_guarded_ranges_refuses_bad_arguments_without_a_gpu(lib):
+    """The guarded step over trainable ranges is the guarded segmented call under a table of the ranges, one class per step origin:
+    what the table (dmm_adam_table_init) and the step (dmm_adam_step_guarded_segmented) refuse between them."""
     L = lib.lib()
     P = 1 << 20   # an address nothing dereferences: every refusal below comes before the first HIP call
-    i64 = C.c_int64
 
-    def call(offs=(0, 64), cnts=(64, 32), t0=(0, 3), n=2, **over):
-        arr = lambda v: None if v is None else (i64 * len(v))(*v)   # noqa: E731
-        a = dict(params=P, grads=P, m=P, v=P, offs=arr(offs), cnts=arr(cnts), t0=arr(t0), n=n,
-                 lr=1e-3, b1=0.9, b2=0.999, eps=1e-8, wd=0.0, max_norm=0.0, growth=2.0, backoff=0.5, interval=2000, state=P, scratch=P)
+    def table(ranges=((0, 64, 0), (64, 32, 1)), n=1000, nsegs=None, nclasses=2, table=P):
+        arr = None if ranges is None else (lib.AdamSegment * len(ranges))(*(lib.AdamSegment(*r) for r in ranges))
+        return L.dmm_adam_table_init(table, arr, (len(ranges) if ranges is not None else 2) if nsegs is None else nsegs, n, nclasses, None)
+
+    def call(t0=(0, 3), nsegs=2, b1=0.9, **over):
+        cl = None if t0 is None else (lib.AdamClass * len(t0))(*(lib.AdamClass(1e-3, b1, 0.999, 1e-8, 0.0, 0, t) for t in t0))
+        a = dict(params=P, grads=P, m=P, v=P, table=P, max_norm=0.0, growth=2.0, backoff=0.5, interval=2000, state=P, scratch=P)
         a.update(over)
-        return L.dmm_adam_step_guarded_ranges(a["params"], a["grads"], a["m"], a["v"], a["offs"], a["cnts"], a["t0"], a["n"], a["lr"], a["b1"], a["b2"],
-                                              a["eps"], a["wd"], a["max_norm"], a["growth"], a["backoff"], a["interval"], a["state"], a["scratch"], None)
+        return L.dmm_adam_step_guarded_segmented(a["params"], a["grads"], a["m"], a["v"], 1000, a["table"], nsegs, cl, 2, a["max_norm"],
+                                                 a["growth"], a["backoff"], a["interval"], a["state"], a["scratch"], None)
 
-    for name in ("params", "grads", "m", "v", "offs", "cnts", "t0", "state", "scratch"):
+    for name in ("params", "grads", "m", "v", "table", "state", "scratch"):
         _refused(lib, call(**{name: None}), "null")
-    _refused(lib, call(n=0), "nranges")
-    _refused(lib, call(n=-1), "nranges")
-    _refused(lib, call(offs=(-1, 64)), ">= 0")
-    _refused(lib, call(cnts=(64, -2)), ">= 0")
+    _refused(lib, call(t0=None), "null")
+    _refused(lib, table(ranges=None), "null")
+    _refused(lib, table(nsegs=0), "nsegs")
+    _refused(lib, table(nsegs=-1), "nsegs")
+    _refused(lib, call(nsegs=0), "nsegs")
+    _refused(lib, table(ranges=((-1, 64, 0), (64, 32, 1))), "lies outside")
+    _refused(lib, table(ranges=((0, 64, 0), (64, -2, 1))), "count")
     _refused(lib, call(t0=(0, -1)), "t0")
-    _refused(lib, call(offs=(0, 63)), "overlap")
-    _refused(lib, call(offs=(64, 0), cnts=(32, 65)), "overlap")              # whatever the order
-    _refused(lib, call(offs=(0, 2 ** 62), cnts=(1, 2 ** 62)), "overflow")
+    _refused(lib, table(ranges=((0, 64, 0), (63, 32, 1))), "overlaps")
+    _refused(lib, table(ranges=((64, 32, 0), (0, 65, 1))), "unsorted or overlaps")     # whatever the order
+    _refused(lib, table(ranges=((0, 1, 0), (2 ** 62, 2 ** 62, 1))), "lies outside")    # (begin + count would overflow)
     _refused(lib, call(grads=P + 2), "misaligned")
     _refused(lib, call(state=P + 4), "misaligned")
     _refused(lib, call(growth=0.5), "growth_factor")
@@ -106,6 +113,7 @@ def test_guarded_ranges_refuses_bad_arguments_without_a_gpu(lib):
     _refused(lib, call(interval=-1), "growth_interval")
     _refused(lib, call(max_norm=float("nan")), "max_norm")
     _refused(lib, call(b1=1.0), "betas")
+    _refused(lib, call(), "not initialised by dmm_adam_table_init")              # all else in order: the table itself is unknown
 
 
 # ------------------------------------------------------------------------------------------------ unbound plans
@@ -327,7 +335,7 @@ HARNESS_CASES = (("tiny_mid", "bf16", 2, 96, 160), ("d121e", "f16", 2, 64, 96), 
 
 def test_sanitizer_harness_with_a_frozen_plan(host_drive):
     """Life cycles with DRIVE_FREEZE=1 (the mode set on the unbound plan, null and bound plans refused, bind in the mode, every list run,
-    dmm_adam_step_guarded_ranges with two ranges and t0 > 0, overlapping ranges refused, buckets and unpack descriptors checked against
+    dmm_adam_step_guarded_segmented with two ranges and a class with t0 > 0, overlapping ranges refused, buckets and unpack descriptors checked against
     the encoder's tensors) are clean under ASan / UBSan.  `drive dump`: the forward lists are those of the default plan, the backward
     list is a strict prefix-by-labels of the default one without any encoder record, and no unpack descriptor scatters into the
     encoder.  Without the switch the dump is the parent commit's, byte for byte (tests/golden/plan_dump_sha256.json: SHA-256 of

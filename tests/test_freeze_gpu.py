@@ -1,5 +1,5 @@
 """Frozen encoder on the GPU: model.freeze_encoder() / requires_grad_ -> dmm_plan_set_encoder_frozen -> a backward list that ends in
-front of the encoder, and FusedAdam over the trainable ranges with per-range step counts (dmm_adam_step_guarded_ranges).
+front of the encoder, and FusedAdam over the trainable ranges with per-range step counts (one segmented Adam launch, a class per step origin).
 
 THE GRADIENT RULE (_check_frozen_against_default), frozen against default on the same model and batch, per tensor of the arena:
   * encoder tensors (features, stream_2_features, concat_module): all zero (the whole arena is still cleared and no launch of the

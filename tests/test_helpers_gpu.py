@@ -217,10 +217,15 @@ def test_metric_ties_at_threshold(dtype):
 
 
 # ---------------------------------------------------------------------------------------------------- Adam
-@pytest.mark.parametrize("n", [1, 255, 257, 4096 * 256 + 13])
+ADAM_STRIDE_N = 2048 * 1024 + 1024 + 13   # one chunk and a ragged tail past the kernel's grid of 2048 workgroups x 1024 elements: the stride loop's second step
+ADAM_SHIFT = {1027: 1}                    # n -> elements behind a 16-byte boundary: the element path, with a tail
+
+
+@pytest.mark.parametrize("n", [1, 255, 257, 4096 * 256 + 13, ADAM_STRIDE_N, 1027])
 def test_adam_step_every_element(n):
-    """dmm_adam_step against torch.optim.Adam (L2 weight decay, amsgrad off) restated in fp64, every element: across the grid cap
-    (4096 x 256 threads), with weight decay, a gradient scale, late steps, and gradients of 0 and 1e-30.
+    """dmm_adam_step against torch.optim.Adam (L2 weight decay, amsgrad off) restated in fp64, every element: many workgroups, past
+    the grid's cap (ADAM_STRIDE_N; one parameter combination there, the fp64 restatement of twelve takes too long), on pointers that
+    are not 16-byte aligned (n = 1027), with weight decay, a gradient scale, late steps, and gradients of 0 and 1e-30.
     m, v: 2^-21 relative (three fp32 operations each, 2x margin) plus the smallest fp32 denormal (v of a 1e-30 gradient underflows);
     |dp - dp_ref| <= 2^-20 |dp_ref| + ulp(p): about eleven roundings on the way to the update, 2x margin, and the rounding of p itself."""
     from dmmfods_amd import _lib
@@ -232,9 +237,12 @@ def test_adam_step_every_element(n):
     idx = np.arange(n)
     g0[idx % 7 == 0] = 0.0
     g0[idx % 7 == 3] = 1e-30
+    shift = ADAM_SHIFT.get(n, 0)
     for wd in (0.0, 0.01):
         for gs in (1.0, 1.0 / 1024):
             for step in (1, 2, 1000):
+                if n == ADAM_STRIDE_N and (wd, gs, step) != (0.01, 1.0 / 1024, 1000):
+                    continue
                 wd32 = np.float32(wd)
                 ge = g0.astype(np.float64) * gs + float(wd32) * p0.astype(np.float64)
                 # moments of the sign of the effective gradient (nothing cancels: the relative bound is meaningful), zero at step 1
@@ -244,7 +252,8 @@ def test_adam_step_every_element(n):
                 v = float(b2) * v0.astype(np.float64) + (1 - float(b2)) * ge * ge
                 bc1, bc2 = 1 - float(b1) ** step, 1 - float(b2) ** step
                 dp = -(float(lr) / bc1) * m / (np.sqrt(v) / np.sqrt(bc2) + float(eps))
-                P, G, M, V = (torch.from_numpy(a.copy()).to(DEV) for a in (p0, g0, m0, v0))
+                P, G, M, V = (torch.zeros(n + 4, device=DEV)[shift:shift + n].copy_(torch.from_numpy(a)) for a in (p0, g0, m0, v0))
+                assert P.data_ptr() % 16 == 4 * shift
                 _lib.check(L.dmm_adam_step(P.data_ptr(), G.data_ptr(), M.data_ptr(), V.data_ptr(), n, float(lr), float(b1), float(b2), float(eps), float(wd32), step, gs, _lib.stream_ptr()))
                 torch.cuda.synchronize()
                 gm, gv, gp = M.cpu().numpy().astype(np.float64), V.cpu().numpy().astype(np.float64), P.cpu().numpy().astype(np.float64)

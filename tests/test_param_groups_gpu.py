@@ -1,23 +1,33 @@
 """Parameter groups on the GPU: the segmented Adam kernel (dmm_adam_step_segmented, dmm_adam_step_guarded_segmented) and what stands on
 it (FusedAdam(param_groups=...), fine_tune_groups, the agent's config fields).
 
-  1. BIT EQUALITY with the single-range kernel: for decoupled = 0 the one segmented launch equals dmm_adam_step called once per segment
-     on offset pointers with the segment's scalars and step - t0, in p, m and v; what lies in no segment keeps its bits (NaN / inf
-     patterns), the gradient arena is never written.  No tolerance.
+  0. THE RECORDED BITS.  tests/golden/adam_bits_sha256.json holds, per case, the SHA-256 of the inputs, of p, m and v and (guarded) of
+     the 64-byte state block, as a library built from the csrc of the commit the file names computed them on an MI355X - the last
+     commit that had four Adam kernels (adam_kernel, two guarded ones, the segmented one).  Cases 1 and 3 and the whole-range cases
+     compare against it (_golden).  The file was written by running this file as a script against that library,
+         DMM_LIB_PATH=<that build>/libdmmfods_hip.so python tests/test_param_groups_gpu.py <commit>
+     with the guarded cases put through that commit's guarded step over ranges (an entry point the library no longer has).  A change
+     that alters Adam's bits ON PURPOSE renews it from its own build and says so; any other change leaves it alone.
+  1. BIT EQUALITY of the two forms of the kernel: for decoupled = 0 the one launch under a table equals dmm_adam_step (the whole-range
+     form) called once per segment on offset pointers with the segment's scalars and step - t0, in p, m and v; what lies in no
+     segment keeps its bits (NaN / inf patterns), the gradient arena is never written.  No tolerance.  Plus the recorded bits.
   2. Decoupled decay, every element, against the fp64 restatement of tests/test_helpers_gpu.py::test_adam_step_every_element:
      |p - p_ref| <= 2^-20 |u_ref| + 3 ulp(p0) (u_ref the Adam update term; the fp32 rounding of the decay factor, the product and the
      final subtraction are the three ulps); m and v keep that test's bounds.
-  3. The guarded segmented step against dmm_adam_step_guarded_ranges on the same runs: p, m, v, sumsq, grad_norm, clip_coef and
-     applied_steps bit-equal; an inf inside a segment skips the step, an inf in a gap is not seen.
+  3. The guarded segmented step against the recorded bits of the guarded step over ranges on the same runs: p, m, v and the state
+     block (sumsq, grad_norm, clip_coef, applied_steps, ...) bit-equal; an inf inside a segment skips the step, an inf in a gap is not
+     seen.  Then dmm_adam_step and dmm_adam_step_guarded over a whole range against their recorded bits.
   4. Model level (tiny mid-3 net, fp32, 2 x 64 x 96): three steps with fine_tune_groups against torch.optim.Adam over the same groups
      (tests/test_freeze_gpu.py's bounds), with and without decoupled decay; freeze and release on the guarded path; one Adam entry
      point per step.
   5. The agent with the three config fields, StepLR and a resume.
 Every case prints its figures ([groups] lines)."""
 import collections
-import ctypes as C
+import hashlib
+import json
 import os
 import shutil
+import sys
 
 import numpy as np
 import pytest
@@ -31,6 +41,32 @@ DEV = "cuda"
 ENCODER = ("features.", "stream_2_features.", "concat_module.")
 TINY = dict(growth_rate=8, block_config=(2, 2, 2, 2), num_init_features=16)
 GAP_BITS = np.array([0x7fc00001, 0x7f800000, 0xff800000, 0xffc12345], dtype=np.uint32)   # NaN, +inf, -inf, NaN with a payload
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "adam_bits_sha256.json")
+_RECORDING = None   # a dict while this file runs as a script: _golden fills it and compares nothing
+
+
+# ------------------------------------------------------------------------------------------------ recorded bits
+def _sha(*arrays):
+    h = hashlib.sha256()
+    for a in arrays:
+        h.update(a.detach().cpu().contiguous().numpy().tobytes() if isinstance(a, torch.Tensor) else np.ascontiguousarray(a).tobytes())
+    return h.hexdigest()
+
+
+def _golden(name, inputs, P, M, V, state=None):
+    """The result of case `name` against the bits recorded in tests/golden/adam_bits_sha256.json (the file's "commit" built them): the
+    SHA-256 of the four input arrays first - a random generator that has changed is reported as that, not as a kernel fault - then
+    of p, m and v (whole arenas, gaps included) and, guarded, of the 64-byte state block."""
+    row = {"inputs": _sha(*inputs), "p": _sha(P), "m": _sha(M), "v": _sha(V)}
+    if state is not None:
+        assert state.numel() * state.element_size() == 64
+        row["state"] = _sha(state)
+    if _RECORDING is not None:
+        _RECORDING[name] = row
+        return
+    pinned = json.load(open(GOLDEN))["cases"][name]
+    assert row["inputs"] == pinned["inputs"], (name, "the INPUTS differ from the recorded ones (random generator?), not the kernel's results")
+    assert row == pinned, (name, [k for k in row if row[k] != pinned[k]])
 
 
 # ------------------------------------------------------------------------------------------------ tables
@@ -121,7 +157,7 @@ def test_segmented_launch_is_bit_equal_to_the_single_range_kernel_per_segment(ca
     classes = _class_rows(ncls)
     step, gs = 7, 1.0 / 1024
     p0, g0, m0, v0, inside = _arenas(rows, n, seed=len(rows))
-    # the reference: the parent's kernel, once per segment, on offset pointers
+    # the reference: the whole-range form, once per segment, on offset pointers
     P, G, M, V = (_dev(a, shift) for a in (p0, g0, m0, v0))
     written = 0
     for b, c, k in rows:
@@ -148,7 +184,8 @@ def test_segmented_launch_is_bit_equal_to_the_single_range_kernel_per_segment(ca
         moved = int((gb != sb).sum())
         assert 0.9 * written <= moved <= written, (case, name, moved, written)       # the launch did something, and only inside active segments
     assert torch.equal(_bits(G2), torch.from_numpy(g0.view(np.int32))), "the gradient arena was written"
-    if case == "A":                                                                  # the class whose count is below 1 wrote nothing
+    _golden(f"segments {case} shift {shift}", (p0, g0, m0, v0), P2, M2, V2)
+    if case == "A":                                                                 # the class whose count is below 1 wrote nothing
         sleeping = [(b, c) for b, c, k in rows if step - classes[k][6] < 1]
         assert sleeping
         for b, c in sleeping:
@@ -219,15 +256,25 @@ def _read(lib, s):
     return lib.GuardState.from_buffer_copy(s.cpu().numpy().tobytes())
 
 
+def _guarded_step(lib, arenas, n, rows, classes, tail, st, scratch):
+    """One guarded step under the table of `rows` (one class per step origin).  (The recording of tests/golden/adam_bits_sha256.json
+    put the parent's guarded step over ranges here: one range per run, the run's origin as its t0.)"""
+    table = _table(lib, rows, n, len(classes))
+    cl = (lib.AdamClass * len(classes))(*(lib.AdamClass(*r) for r in classes))
+    lib.check(lib.lib().dmm_adam_step_guarded_segmented(*(t.data_ptr() for t in arenas), n, table.data_ptr(), len(rows), cl, len(classes), *tail,
+                                                        st.data_ptr(), scratch.data_ptr(), lib.stream_ptr()))
+
+
 @pytest.mark.parametrize("origins", [(0, 0, 0), (0, 2, 0)])
 def test_guarded_segmented_step_is_bit_equal_to_the_guarded_step_over_ranges(origins):
     """Three runs separated by gaps (the middle one made of two adjacent segments), one set of hyper-parameters; origins: the step
     origin of each run (all 0: one class; (0, 2, 0): the middle run released at applied step 2, a class of its own).  The state starts
-    at 5 applied steps and a scale of 8; max_norm is below the norm, so the step is clipped."""
+    at 5 applied steps and a scale of 8; max_norm is below the norm, so the step is clipped.  The guarded step over ranges is the
+    parent's, by its recorded bits: p, m, v and the whole state block (sumsq, grad_norm, clip_coef, grad_scale, scale, the counters,
+    step_size and bc2_sqrt as the finalize kernel leaves them: class 0's)."""
     from dmmfods_amd import _lib
     L = _lib.lib()
     lr, b1, b2, eps, wd = 2e-3, 0.9, 0.999, 1e-8, 0.01
-    runs = [(5, 1000), (1013, 70001), (80000, 4099)]
     n = 84200
     split = 1013 + 30003
     cls_of = {t0: k for k, t0 in enumerate(dict.fromkeys(origins))}
@@ -237,37 +284,20 @@ def test_guarded_segmented_step_is_bit_equal_to_the_guarded_step_over_ranges(ori
     g0 = (g0 * 8.0).astype(np.float32)                                            # the arena holds S x the gradients
     g0[~inside] = GAP_BITS[np.arange(n) % 4].view(np.float32)[~inside]
     scratch = torch.zeros(L.dmm_grad_guard_scratch_bytes(n) // 8, dtype=torch.float64, device=DEV)
-    i64 = C.c_int64
-    offs, cnts, t0s = ((i64 * 3)(*v) for v in ([r[0] for r in runs], [r[1] for r in runs], list(origins)))
     tail = (0.05, 2.0, 0.5, 2000)                                                 # max_norm, growth, backoff, interval
 
-    def reference(g):
+    def segmented(g, raw=False):
         P, G, M, V = (_dev(a) for a in (p0, g, m0, v0))
         st = _state(_lib, 8.0, 5)
-        _lib.check(L.dmm_adam_step_guarded_ranges(P.data_ptr(), G.data_ptr(), M.data_ptr(), V.data_ptr(), offs, cnts, t0s, 3, lr, b1, b2, eps, wd, *tail,
-                                                  st.data_ptr(), scratch.data_ptr(), _lib.stream_ptr()))
-        return P, G, M, V, _read(_lib, st)
+        _guarded_step(_lib, (P, G, M, V), n, rows, classes, tail, st, scratch)
+        return P, G, M, V, (st if raw else _read(_lib, st))
 
-    table = _table(_lib, rows, n, len(classes))
-    cl = (_lib.AdamClass * len(classes))(*(_lib.AdamClass(*r) for r in classes))
-
-    def segmented(g):
-        P, G, M, V = (_dev(a) for a in (p0, g, m0, v0))
-        st = _state(_lib, 8.0, 5)
-        _lib.check(L.dmm_adam_step_guarded_segmented(P.data_ptr(), G.data_ptr(), M.data_ptr(), V.data_ptr(), n, table.data_ptr(), len(rows), cl, len(classes), *tail,
-                                                     st.data_ptr(), scratch.data_ptr(), _lib.stream_ptr()))
-        return P, G, M, V, _read(_lib, st)
-
-    want, got = reference(g0), segmented(g0)
-    for name, a, b in zip("pgmv", got[:4], want[:4]):
-        assert torch.equal(_bits(a), _bits(b)), (origins, name)
-    sw, sg = want[4], got[4]
-    f = lambda x: np.float32(x).view(np.int32)   # noqa: E731
-    assert sg.found_inf == sw.found_inf == 0 and sg.applied_steps == sw.applied_steps == 6 and sg.skipped_steps == 0
-    assert np.float64(sg.sumsq).view(np.int64) == np.float64(sw.sumsq).view(np.int64) and sg.sumsq > 0
-    assert f(sg.grad_norm) == f(sw.grad_norm) and f(sg.clip_coef) == f(sw.clip_coef) and 0 < sg.clip_coef < 1
-    assert f(sg.grad_scale) == f(sw.grad_scale) and f(sg.scale) == f(sw.scale) and sg.growth_tracker == sw.growth_tracker
-    assert f(sg.step_size) == f(sw.step_size) and f(sg.bc2_sqrt) == f(sw.bc2_sqrt)          # class 0's, as the finalize kernel leaves them
+    got = segmented(g0, raw=True)
+    sg = _read(_lib, got[4])
+    _golden("guarded origins %d %d %d" % origins, (p0, g0, m0, v0), got[0], got[2], got[3], state=got[4])
+    assert torch.equal(_bits(got[1]), torch.from_numpy(g0.view(np.int32))), "the gradient arena was written"
+    assert sg.found_inf == 0 and sg.applied_steps == 6 and sg.skipped_steps == 0
+    assert sg.sumsq > 0 and 0 < sg.clip_coef < 1
     assert not torch.equal(_bits(got[0]), torch.from_numpy(p0.view(np.int32)))
     out = torch.from_numpy(~inside)
     for a, start in zip(got[:4], (p0, g0, m0, v0)):
@@ -287,6 +317,35 @@ def test_guarded_segmented_step_is_bit_equal_to_the_guarded_step_over_ranges(ori
     P, G, M, V, s = segmented(g_gap)
     assert s.found_inf == 0 and s.applied_steps == 6 and np.float64(s.sumsq).view(np.int64) == np.float64(sg.sumsq).view(np.int64)
     assert torch.equal(_bits(P), _bits(got[0]))
+
+
+@pytest.mark.parametrize("form", ["plain shift 0", "plain shift 1", "guarded"])
+def test_whole_range_steps_keep_the_recorded_bits(form):
+    """dmm_adam_step and dmm_adam_step_guarded over a whole range, against the parent's recorded bits.  plain: n = 4096 * 256 + 13,
+    aligned and one element behind a 16-byte boundary (the element path), weight decay 0.01 and grad_scale 1 / 1024 at step 7.
+    guarded: n = 84 200, 5 applied steps, scale 8, clipped (max_norm 0.05)."""
+    from dmmfods_amd import _lib
+    L = _lib.lib()
+    lr, b1, b2, eps, wd = 2e-3, 0.9, 0.999, 1e-8, 0.01
+    n = 84200 if form == "guarded" else 4096 * 256 + 13
+    p0, g0, m0, v0, _ = _arenas([(0, n, 0)], n, seed=11)
+    state = None
+    if form == "guarded":
+        g0 = (g0 * 8.0).astype(np.float32)
+        P, G, M, V = (_dev(a) for a in (p0, g0, m0, v0))
+        state = _state(_lib, 8.0, 5)
+        scratch = torch.zeros(L.dmm_grad_guard_scratch_bytes(n) // 8, dtype=torch.float64, device=DEV)
+        _lib.check(L.dmm_adam_step_guarded(P.data_ptr(), G.data_ptr(), M.data_ptr(), V.data_ptr(), n, lr, b1, b2, eps, wd, 0.05, 2.0, 0.5, 2000,
+                                           state.data_ptr(), scratch.data_ptr(), _lib.stream_ptr()))
+        s = _read(_lib, state)
+        assert s.found_inf == 0 and s.applied_steps == 6 and 0 < s.clip_coef < 1
+    else:
+        P, G, M, V = (_dev(a, int(form[-1])) for a in (p0, g0, m0, v0))
+        _lib.check(L.dmm_adam_step(P.data_ptr(), G.data_ptr(), M.data_ptr(), V.data_ptr(), n, lr, b1, b2, eps, wd, 7, 1.0 / 1024, _lib.stream_ptr()))
+        torch.cuda.synchronize()
+    assert torch.equal(_bits(G), torch.from_numpy(g0.view(np.int32))), "the gradient arena was written"
+    assert int((_bits(P) != torch.from_numpy(p0.view(np.int32))).sum()) > 0.9 * n
+    _golden("whole " + form, (p0, g0, m0, v0), P, M, V, state=state)
 
 
 # ------------------------------------------------------------------------------------------------ 4. model level
@@ -397,7 +456,7 @@ def test_three_grouped_steps_against_torch_adam_over_the_same_groups(decoupled, 
     # (an Adam step is at most (1 - b1) / sqrt(1 - b2) = 3.2 lr and lr on the first: under the decoder's lr the median would be near 3e-3)
     assert 0 < float(moved.median()) <= 3 * 1e-4 * 1.01 and float(moved.max()) < 1e-3, (float(moved.median()), float(moved.max()))
     assert opt.step_count == 3
-    # without groups: the optimiser's calls of before
+    # without groups and with nothing frozen: the whole-arena call, one per step
     counter.calls.clear()
     from dmmfods_amd.optim import FusedAdam
     plain = FusedAdam(model, weight_decay=0.01)
@@ -407,6 +466,17 @@ def test_three_grouped_steps_against_torch_adam_over_the_same_groups(decoupled, 
     clip.step()
     torch.cuda.synchronize()
     assert dict(counter.calls) == {"dmm_adam_step": 1, "dmm_adam_step_guarded": 1}, dict(counter.calls)
+    # without groups, the encoder frozen: the segmented call, one per step (one table each, built at the first step)
+    counter.calls.clear()
+    model.freeze_encoder()
+    plain, clip = FusedAdam(model, weight_decay=0.01), FusedAdam(model, weight_decay=0.01, max_grad_norm=1e9)
+    _fused(model, tuple(t.to(DEV) for t in R.make_inputs(arch, 2, 64, 96, seed=0)))
+    for _ in range(2):
+        plain.step()
+        clip.step()
+    torch.cuda.synchronize()
+    assert dict(counter.calls) == {"dmm_adam_table_init": 2, "dmm_adam_table_bytes": 2, "dmm_adam_step_segmented": 2,
+                                   "dmm_adam_step_guarded_segmented": 2}, dict(counter.calls)
     model.close()
 
 
@@ -533,3 +603,24 @@ def test_agent_trains_with_groups_and_a_resume_keeps_them(tmp_path, monkeypatch)
     assert ropt.step_count == 6 and bool(torch.isfinite(resumed.model.param_arena).all())
     print(f"[groups] agent: lrs after two epochs {[g['lr'] for g in opt.param_groups]}, resumed epoch losses {resumed.train_history[-1]['loss'].tolist()}")
     resumed.model.close()
+
+
+def record(commit):
+    """Runs the cases that _golden pins against the loaded library (DMM_LIB_PATH) and writes the golden file, which names `commit`."""
+    global _RECORDING
+    _RECORDING = {}
+    for case, shift in (("A", 0), ("A", 1), ("B", 0)):
+        test_segmented_launch_is_bit_equal_to_the_single_range_kernel_per_segment(case, shift)
+    for origins in ((0, 0, 0), (0, 2, 0)):
+        test_guarded_segmented_step_is_bit_equal_to_the_guarded_step_over_ranges(origins)
+    for form in ("plain shift 0", "plain shift 1", "guarded"):
+        test_whole_range_steps_keep_the_recorded_bits(form)
+    with open(GOLDEN, "w") as f:
+        json.dump({"commit": commit, "cases": _RECORDING}, f, indent=1, sort_keys=True)
+        f.write("\n")
+    print("wrote %s (%d cases, library of %s)" % (GOLDEN, len(_RECORDING), commit))
+
+
+if __name__ == "__main__":   # DMM_LIB_PATH=<library built from <commit>'s csrc> python tests/test_param_groups_gpu.py <commit>
+    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    record(sys.argv[1])

@@ -41,7 +41,7 @@
 // guard state block the driver owns: region "guard"); the life-cycle run also takes the guarded optimiser step after every backward.
 // DRIVE_FREEZE=1 (life-cycle run and dump): the plan is built with a frozen encoder (dmm_plan_set_encoder_frozen on the unbound plan; a
 // null plan and the bound plan must be refused); the life-cycle run also takes the guarded step over two trainable ranges, one of
-// them released late (dmm_adam_step_guarded_ranges, t0 > 0), and checks that no bucket and no unpack descriptor touches an encoder tensor.
+// them released late (dmm_adam_step_guarded_segmented, a class with t0 > 0), and checks that no bucket and no unpack descriptor touches an encoder tensor.
 // Launch coalescing (dmm_set_option("batch_wgrad"), on by default; DRIVE_OPTIONS_OFF=batch_wgrad runs one launch per record,
 // DRIVE_BATCH_WGRAD=<0|1|2> sets the option's value: 2 = grouped on the weight-gradient stream instead of the caller's): every
 // life-cycle run watches the enqueue calls through the fake runtime's hook and checks, with the option on or off, that
@@ -337,12 +337,17 @@ static int one_life(const dmm_model_desc& d, int life) {
     MUST(dmm_plan_loss_backward(plan, logits, target, metrics, st));
     BACKWARD_DONE("end of a training step");
     if (freeze) {   // two trainable ranges: everything behind the leading encoder range from the start, that range released at step 1
-      const int64_t offs[2] = {enc_hi, enc_lo}, cnts[2] = {np - enc_hi, enc_hi - enc_lo}, t0s[2] = {0, 1};
-      MUST(dmm_adam_step_guarded_ranges(params, grads, mom1, mom2, offs, cnts, t0s, rep == 0 ? 1 : 2, 1e-3f, 0.9f, 0.999f, 1e-8f, 0.01f, 1.0f, 2.f, 0.5f, 2000,
-                                        gstate, gscratch, st));
-      const int64_t bad_offs[2] = {0, enc_hi - 1};
-      if (dmm_adam_step_guarded_ranges(params, grads, mom1, mom2, bad_offs, cnts, t0s, 2, 1e-3f, 0.9f, 0.999f, 1e-8f, 0.f, 1.0f, 2.f, 0.5f, 2000, gstate,
-                                       gscratch, st) != DMM_ERR_INVALID) { fprintf(stderr, "[drive] overlapping ranges were not refused\n"); return 2; }
+      const dmm_adam_segment one[1] = {{enc_hi, np - enc_hi, 0}}, two[2] = {{enc_lo, enc_hi - enc_lo, 1}, {enc_hi, np - enc_hi, 0}};
+      const dmm_adam_class origins[2] = {{1e-3f, 0.9f, 0.999f, 1e-8f, 0.01f, 0, 0}, {1e-3f, 0.9f, 0.999f, 1e-8f, 0.01f, 0, 1}};
+      const int ns = rep == 0 ? 1 : 2;
+      const size_t tb = dmm_adam_table_bytes(ns, np);
+      if (tb == 0) { fprintf(stderr, "[drive] dmm_adam_table_bytes (freeze)\n"); return 2; }
+      void* table = aligned_alloc(8, (tb + 7) / 8 * 8);
+      MUST(dmm_adam_table_init(table, rep == 0 ? one : two, ns, np, ns, st));
+      MUST(dmm_adam_step_guarded_segmented(params, grads, mom1, mom2, np, table, ns, origins, ns, 1.0f, 2.f, 0.5f, 2000, gstate, gscratch, st));
+      const dmm_adam_segment bad[2] = {{0, enc_hi, 1}, {enc_hi - 1, np - enc_hi, 0}};
+      if (dmm_adam_table_init(table, bad, 2, np, 2, st) != DMM_ERR_INVALID) { fprintf(stderr, "[drive] overlapping ranges were not refused\n"); return 2; }
+      free(table);
     } else if (dyn) {
       MUST(dmm_adam_step_guarded(params, grads, mom1, mom2, np, 1e-3f, 0.9f, 0.999f, 1e-8f, 0.f, 1.0f, 2.f, 0.5f, 2000, gstate, gscratch, st));
       MUST(dmm_grad_sumsq(grads, np / 2, np - np / 2, 1, gscratch, st));
