@@ -71,7 +71,14 @@ struct Conv3Cfg {
   static constexpr int HALO1 = SEG1 ? HH1 * RP1 : 0;
   static constexpr int WSLOT = GC * BN * 64;
   static constexpr int MAIN0 = HALO0 + HALO1 + C3_WRING * WSLOT;
-  static constexpr int STAGE = BM * (BN + 8) * 2;  // accumulators staged as T (16-bit) for both epilogues
+  // accumulators staged for the epilogue: the forward's as T (16-bit, the values as stored).  The data gradient of the dense blocks'
+  // 3x3 convolution (CS == 4) stages fp32, at most 64 columns at a time: the ReLU mask, both reductions and gold + scale * dz see the
+  // UNROUNDED gradient, as in igemm.hip, bw1.hip and cvp.hip, and the stored gradient is rounded once.  The head's data gradients
+  // (CS == 8 and the thin-only 5x5) still stage T, as they always have: the mask and the sums see dz rounded to 16 bits and the stored
+  // gradient is rounded twice ("Single-rounding operands": what is left open).
+  static constexpr bool DGRAD_F32 = CS == 4;
+  static constexpr int STAGE_T = BM * (BN + 8) * 2, STAGE_F = DGRAD_F32 ? BM * ((BN < 64 ? BN : 64) + 8) * 4 : 0;
+  static constexpr int STAGE = STAGE_T > STAGE_F ? STAGE_T : STAGE_F;
   static constexpr int MAIN = MAIN0 > STAGE ? MAIN0 : STAGE;
   static constexpr int EXTRA = BM * 4 + 2 * BN * 8 + 4 * 2 * BN * 4;  // rowpix + fp64 reduction scratch + per-wave partials
   static constexpr int bytes = MAIN + EXTRA;
@@ -207,8 +214,17 @@ __global__ __launch_bounds__(NTHREADS, 2) void conv3_kernel(const Conv3Args g) {
   const int cv = tid % NCV, rr = tid / NCV;
   const int n = cv * SLOT;
   const bool colvalid = n < a.N;
-  int ppre[EPI == EPI_BNBWD ? NIT : 1];
-  V xpre[EPI == EPI_BNBWD ? NIT : 1];
+  // The data-gradient epilogue of the dense 3x3 (SM::DGRAD_F32) stages its accumulators in fp32.  Where all BN columns at once would
+  // not fit the forward's staging bytes (BN = 128) it runs in EPASS = 2 column halves of EBN = 64 columns, every thread at work in
+  // both: ENCV slot columns per pass, thread (err, ecv) takes rows err + ERPP i of slot column ep * ENCV + ecv.  (The other variants:
+  // one pass over all columns staged as T - EBN = BN, (err, ecv) = (rr, cv).)
+  constexpr bool EF32 = EPI == EPI_BNBWD && SM::DGRAD_F32;
+  constexpr int EPASS = (EF32 && NT == 4) ? 2 : 1;
+  constexpr int EBN = BN / EPASS, ENCV = EBN / SLOT, ERPP = NTHREADS / ENCV, ENIT = BM / ERPP;
+  static_assert(EPI != EPI_BNBWD || BM * (EBN + 8) * (EF32 ? 4 : 2) <= SM::MAIN, "the staging of a pass fits the images");
+  const int ecv = tid % ENCV, err = tid / ENCV;
+  int ppre[EPI == EPI_BNBWD ? EPASS * ENIT : 1];
+  V xpre[EPI == EPI_BNBWD ? EPASS * ENIT : 1];
   V z;
 #pragma unroll
   for (int e = 0; e < SLOT; ++e) z[e] = (T)0;
@@ -280,13 +296,16 @@ __global__ __launch_bounds__(NTHREADS, 2) void conv3_kernel(const Conv3Args g) {
   if constexpr (EPI == EPI_BNBWD) {
     const T* bx = (const T*)a.bx;
 #pragma unroll
-    for (int i = 0; i < NIT; ++i) {  // (rowpix is not visible yet: recompute this thread's rows)
-      const int row = rr + RPP * i;
-      const int y = y0 + row / C3_TW, x = x0 + row % C3_TW;
-      ppre[i] = (colvalid && y < a.Ho && x < a.Wo) ? (b * a.Hout + y * a.ostride + a.py) * a.Wout + x * a.ostride + a.px : -1;
+    for (int ep = 0; ep < EPASS; ++ep)
 #pragma unroll
-      for (int e = 0; e < SLOT; ++e) xpre[i][e] = (T)0;
-      if (ppre[i] >= 0) xpre[i] = *(const V*)(bx + (size_t)ppre[i] * a.ldbx + n);
+    for (int i = 0; i < ENIT; ++i) {  // (rowpix is not visible yet: recompute this thread's rows)
+      const int row = err + ERPP * i, k = ep * ENIT + i;
+      const int en = (ep * ENCV + ecv) * SLOT;
+      const int y = y0 + row / C3_TW, x = x0 + row % C3_TW;
+      ppre[k] = (en < a.N && y < a.Ho && x < a.Wo) ? (b * a.Hout + y * a.ostride + a.py) * a.Wout + x * a.ostride + a.px : -1;
+#pragma unroll
+      for (int e = 0; e < SLOT; ++e) xpre[k][e] = (T)0;
+      if (ppre[k] >= 0) xpre[k] = *(const V*)(bx + (size_t)ppre[k] * a.ldbx + en);
     }
   }
 
@@ -392,12 +411,14 @@ __global__ __launch_bounds__(NTHREADS, 2) void conv3_kernel(const Conv3Args g) {
 #pragma unroll
   for (int t = 0; t < NT; ++t) {
     ps1[t] = 0.f; ps2[t] = 0.f;
+    if constexpr (EPI == EPI_STORE) {
 #pragma unroll
-    for (int i = 0; i < 16; ++i) {
-      const int row = 32 * wave + (i & 3) + 8 * (i >> 2) + 4 * h;
-      const T v = from_f32<T>(acc[t][i]);
-      Cs[row * CPITCH + 32 * t + r] = v;
-      if (EPI == EPI_STORE && rowpix[row] >= 0) { const float f = to_f32(v); ps1[t] += f; ps2[t] = fmaf(f, f, ps2[t]); }
+      for (int i = 0; i < 16; ++i) {
+        const int row = 32 * wave + (i & 3) + 8 * (i >> 2) + 4 * h;
+        const T v = from_f32<T>(acc[t][i]);
+        Cs[row * CPITCH + 32 * t + r] = v;
+        if (rowpix[row] >= 0) { const float f = to_f32(v); ps1[t] += f; ps2[t] = fmaf(f, f, ps2[t]); }
+      }
     }
   }
   if constexpr (EPI == EPI_STORE) {
@@ -411,7 +432,7 @@ __global__ __launch_bounds__(NTHREADS, 2) void conv3_kernel(const Conv3Args g) {
   // (forward variants: a raw barrier behind an LDS-only wait - __syncthreads() drained the next tile's halo loads here, a few hundred
   // cycles after they had been requested)
   if constexpr (PERSIST && C3_RAW_EPI_BAR) lds_barrier();
-  else __syncthreads();
+  else if constexpr (EPI == EPI_STORE) __syncthreads();
 
   if constexpr (EPI == EPI_STORE) {
     T* out = (T*)a.out;
@@ -434,51 +455,76 @@ __global__ __launch_bounds__(NTHREADS, 2) void conv3_kernel(const Conv3Args g) {
       }
     }
   } else {  // EPI_BNBWD: acc = d(relu(bn(x))); mask, reduce, scatter s*dz (see igemm.hip)
-    float s1[SLOT], s2[SLOT];
-#pragma unroll
-    for (int i = 0; i < SLOT; ++i) { s1[i] = 0.f; s2[i] = 0.f; }
+    // EF32: the accumulators go through LDS in FP32 - the ReLU mask, both reductions and gold + scale * dz see the unrounded gradient, and
+    // the stored gradient is rounded ONCE (as igemm.hip, bw1.hip, cvp.hip); EPASS column halves (see above) share the staging bytes.
+    // Otherwise they are staged as T.
+    float* Cf = (float*)smem;
+    constexpr int EPITCH = EBN + 8;
     T* gout = (T*)a.out;
-    float sc[SLOT], sh[SLOT], mu[SLOT], is[SLOT];
-    if (colvalid) {
-      load_f32s<SLOT>(a.bscale + n, sc); load_f32s<SLOT>(a.bshift + n, sh);
-      load_f32s<SLOT>(a.bmean + n, mu); load_f32s<SLOT>(a.binvstd + n, is);
-    }
     // second pass of a two-pass BatchNorm backward (thin-only variants: the logits gradient under the 5x5 head convolution): the
     // correction constants are final, store s*dz + q + r*x - what apply_corr made of s*dz in a pass of its own (read g, read x, write g)
     constexpr bool TWO_PASS = !SEG0 && SEG1;
     const bool fin = TWO_PASS && a.eq != nullptr;   // (workgroup-uniform)
-    float qv[TWO_PASS ? SLOT : 1], rv[TWO_PASS ? SLOT : 1];
-    if constexpr (TWO_PASS) {
 #pragma unroll
-      for (int e = 0; e < SLOT; ++e) { qv[e] = 0.f; rv[e] = 0.f; }
-      if (fin && colvalid) { load_f32s<SLOT>(a.eq + n, qv); load_f32s<SLOT>(a.er + n, rv); }
-    }
+    for (int ep = 0; ep < EPASS; ++ep) {
+      const int en = (ep * ENCV + ecv) * SLOT;
+      const bool ecol = en < a.N;
+      if (ep > 0) __syncthreads();   // every thread has read the columns of the pass before
 #pragma unroll
-    for (int i = 0; i < NIT; ++i) {
-      if (ppre[i] < 0) continue;
-      const int row = rr + RPP * i;
-      float av[SLOT], xf[SLOT], gf[SLOT];
-      vec_to_f32<T>(*(const V*)(Cs + row * CPITCH + cv * SLOT), av);
-      vec_to_f32<T>(xpre[i], xf);
-      if (a.accumulate && gout != nullptr) vec_to_f32<T>(*(const V*)(gout + (size_t)ppre[i] * a.ldo + n), gf);
+      for (int t = 0; t < NT / EPASS; ++t)
 #pragma unroll
-      for (int e = 0; e < SLOT; ++e) {
-        const float dz = (fmaf(xf[e], sc[e], sh[e]) > 0.f) ? av[e] : 0.f;
-        s1[e] += dz;
-        s2[e] = fmaf(dz, (xf[e] - mu[e]) * is[e], s2[e]);
-        gf[e] = ((a.accumulate && gout != nullptr) ? gf[e] : 0.f) + sc[e] * dz;
-        if constexpr (TWO_PASS) gf[e] += fmaf(rv[e], xf[e], qv[e]);   // (zeros unless `fin`)
+        for (int i = 0; i < 16; ++i) {
+          const int row = 32 * wave + (i & 3) + 8 * (i >> 2) + 4 * h;
+          if constexpr (EF32) Cf[row * EPITCH + 32 * t + r] = acc[ep * (NT / EPASS) + t][i];
+          else Cs[row * EPITCH + 32 * t + r] = from_f32<T>(acc[t][i]);
+        }
+      __syncthreads();
+      float s1[SLOT], s2[SLOT];
+#pragma unroll
+      for (int i = 0; i < SLOT; ++i) { s1[i] = 0.f; s2[i] = 0.f; }
+      float sc[SLOT], sh[SLOT], mu[SLOT], is[SLOT];
+      if (ecol) {
+        load_f32s<SLOT>(a.bscale + en, sc); load_f32s<SLOT>(a.bshift + en, sh);
+        load_f32s<SLOT>(a.bmean + en, mu); load_f32s<SLOT>(a.binvstd + en, is);
       }
-      if (gout != nullptr) *(V*)(gout + (size_t)ppre[i] * a.ldo + n) = f32_to_vec<T>(gf);
+      float qv[TWO_PASS ? SLOT : 1], rv[TWO_PASS ? SLOT : 1];
+      if constexpr (TWO_PASS) {
+#pragma unroll
+        for (int e = 0; e < SLOT; ++e) { qv[e] = 0.f; rv[e] = 0.f; }
+        if (fin && ecol) { load_f32s<SLOT>(a.eq + en, qv); load_f32s<SLOT>(a.er + en, rv); }
+      }
+#pragma unroll
+      for (int i = 0; i < ENIT; ++i) {
+        const int pp = ppre[ep * ENIT + i];
+        if (pp < 0) continue;
+        const int row = err + ERPP * i;
+        float av[SLOT], xf[SLOT], gf[SLOT];
+        if constexpr (EF32) load_f32s<SLOT>(Cf + row * EPITCH + ecv * SLOT, av);
+        else vec_to_f32<T>(*(const V*)(Cs + row * EPITCH + ecv * SLOT), av);
+        vec_to_f32<T>(xpre[ep * ENIT + i], xf);
+        if (a.accumulate && gout != nullptr) vec_to_f32<T>(*(const V*)(gout + (size_t)pp * a.ldo + en), gf);
+#pragma unroll
+        for (int e = 0; e < SLOT; ++e) {
+          const float dz = (fmaf(xf[e], sc[e], sh[e]) > 0.f) ? av[e] : 0.f;
+          s1[e] += dz;
+          s2[e] = fmaf(dz, (xf[e] - mu[e]) * is[e], s2[e]);
+          gf[e] = ((a.accumulate && gout != nullptr) ? gf[e] : 0.f) + sc[e] * dz;
+          if constexpr (TWO_PASS) gf[e] += fmaf(rv[e], xf[e], qv[e]);   // (zeros unless `fin`)
+        }
+        if (gout != nullptr) *(V*)(gout + (size_t)pp * a.ldo + en) = f32_to_vec<T>(gf);
+      }
+      // per-channel reductions: lanes -> LDS (fp64) -> one fp64 atomic per channel and workgroup (see igemm.hip); the column halves
+      // keep their sums apart: red[ep * 2 * EBN + ...]
+      if (a.red1 != nullptr)   // (workgroup-uniform; null in the second pass of a two-pass BatchNorm backward)
+        fold_to_lds<ENCV, SLOT, EBN>(s1, s2, red + ep * 2 * EBN, ecv, ecol, lane);
     }
-    if (a.red1 != nullptr) {  // (workgroup-uniform; null in the second pass of a two-pass BatchNorm backward)
-      // per-channel reductions: lanes -> LDS (fp64) -> one fp64 atomic per channel and workgroup (see igemm.hip)
-      fold_to_lds<NCV, SLOT, BN>(s1, s2, red, cv, colvalid, lane);
+    if (a.red1 != nullptr) {
       __syncthreads();
       if (!(C3_DBG & (16 | 32)) && tid < BN && tid < a.N) {
         const size_t rep = (size_t)(blockIdx.x & (STAT_REPS - 1)) * a.stat_stride;
-        atomic_add_f64(a.red1 + rep + tid, red[fold_slot<NCV, SLOT>(0, tid)]);
-        atomic_add_f64(a.red2 + rep + tid, red[fold_slot<NCV, SLOT>(1, tid)]);
+        const double* rp = red + (tid / EBN) * 2 * EBN;
+        atomic_add_f64(a.red1 + rep + tid, rp[fold_slot<ENCV, SLOT>(0, tid % EBN)]);
+        atomic_add_f64(a.red2 + rep + tid, rp[fold_slot<ENCV, SLOT>(1, tid % EBN)]);
       }
     }
   }

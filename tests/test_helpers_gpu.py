@@ -26,7 +26,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 # ---------------------------------------------------------------------------------------------------- the probe
 # `name: ok` lines a complete run of each group prints (an empty or shortened run fails)
-GROUP_CASES = {"convert": 18, "bn": 24, "pool": 18, "poolbwd": 18, "corr": 8, "loss": 75}
+GROUP_CASES = {"convert": 22, "bn": 24, "pool": 18, "poolbwd": 18, "corr": 10, "loss": 75}
 _probe_dead = []   # the group that ended by signal, timeout or HIP error: nothing of the probe is started after it
 
 

@@ -27,7 +27,10 @@ luck): per output channel the |activation| maxima of its nonzero weights add up 
 input channel the |gradient| maxima likewise for the stored data gradient.  bf16 holds 8 significant bits, f16 11 - f16 weights for
 the data gradient are 8 times as dense; for the forward they are 4 times as dense, because (c) for stat_sq (128 y**2 / u**2 < 2**24)
 caps |y| / u near 2**8.5 whatever the storage type (the budget of 2**10 relies on signs cancelling; check() holds the actual values
-to (c))."""
+to (c)).
+
+Below them, the single-rounding operands (make_rounding_operands, Operands.check_rounding): the same exactness in fp32, but every
+16-bit store rounds once - see the comment there."""
 import functools
 from types import SimpleNamespace
 
@@ -299,3 +302,324 @@ CASES = [
     ("up2 3x3 128->64", 1, 6, 10, 128, 64, 3, 3, 1, 1, 0, 1, 1),
     ("up2 3x3 16->8", 2, 4, 4, 16, 8, 3, 3, 1, 1, 0, 1, 1),
 ]
+
+
+# ================================================================================================ single-rounding operands (round 10)
+# The third operand class.  As above, all fp32 arithmetic is exact in any order; but the values that reach a 16-bit store need more
+# significant bits than the storage type holds, so that every store is exactly ONE round-to-nearest-even of an exactly known number -
+# and the kernel has to hit it bit for bit, ties included.  The fp64 reference applies every rounding point the kernels document, in
+# their order (rnd = to the storage type and back, of a number asserted exact in fp32 - torch converts double to half through float,
+# the assertion takes the double rounding out of the reference):
+#   w_T = rnd(w)                          the weight pack
+#   a   = rnd(relu(x * scale + shift))    the prologue (one fp32 fma, exact by construction; ReLU commutes with the rounding; the
+#                                         pooling gather rounds the mean of the four pixels of a window, once)
+#   y   = rnd(conv(a, w_T));  stat_sum, stat_sq: sums of the ROUNDED y
+#   eff = rnd(dy + q + r * yfwd)          the effective gradient
+#   dz  = conv_backward(eff, w_T) * (x * scale + shift > 0), unrounded;  red1 = sum dz;  red2 = sum dz * xhat
+#   gx  = rnd(gold + scale * dz)          ONE rounding
+#   dw  = sum a * eff
+# Recipe ("main"): |x| < 2**(sig - 1) integers (sig = 11 / 8), scale in {0.75, 1, 1.25, 1.5, 3}, shift multiples of 0.5 in [-1.5, 1.5],
+# dy and yfwd integers below 2**(sig - 1) (dy below 2**(sig - 2) under the correction), q multiples of 0.5, r in {+-0.75, +-1.5, 0}, gold multiples of 0.25, weights
+# in {-1, 0, 1} (w_T leaves them unchanged) with every (tap, input channel) pair covered; the number of nonzero weights per output /
+# per input channel is capped so that f16 does not overflow.  "weights": w = k 2**-12, k odd of up to 13 bits, on the round-8
+# activations - the forward and the data gradient must use rnd(w).  "subnormal" (f16): the main recipe with x, shift, mean, the
+# gradients and the weights scaled by 2**-12, which puts the stored results around 2**-14 - gradual underflow, where loss-scaled f16
+# gradients live - while every value the matrix unit reads stays normal (or zero).
+ROUND_SCALE = [0.75, 1.0, 1.25, 1.5, 3.0]
+ROUND_R = [-1.5, -0.75, 0.0, 0.75, 1.5]
+NNZ_OUT = {1: 128, 2: 128}     # nonzero weights per output element / per input-gradient element ("main"): sigma(y) ~ sqrt(nnz) * rms(a) stays
+NNZ_IN = {0: 32, 1: 10}        # (by with_q) 4.5 sigma below f16's 65504 with rms(a) ~ 600 and 3 * rms(eff) ~ 2000 - and the stored gradient
+                               # only a few bits wider than the type, so that exact ties are common
+MIN_ULP = {1: 2.0 ** -24, 2: 2.0 ** -133}
+
+
+def _rnd(t, dt, name):
+    """One round-to-nearest-even to the storage type of a number that is exact in fp32."""
+    f = t.float()
+    assert torch.equal(f.double(), t), f"(a) {name} is not exact in fp32"
+    return f.to(dt).double()
+
+
+def step_of(*ts):
+    """The common power-of-two step of the (fp64, exactly known) values: the largest 2**e that divides all of them."""
+    e = None
+    for t in ts:
+        t = t[t != 0]
+        if t.numel() == 0:
+            continue
+        m, ex = torch.frexp(t.abs())
+        mi = (m * 2.0 ** 53).to(torch.int64)
+        tz = torch.log2((mi & -mi).double()).round().to(torch.int64)
+        s = int((ex.to(torch.int64) - 53 + tz).min())
+        e = s if e is None else min(e, s)
+    return 2.0 ** (0 if e is None else e)
+
+
+def rounding_shares(t, dtype):
+    """Of the exactly known values t (fp64) rounded to the storage type: the shares that are not representable, that are exact ties
+    (resolved to the even neighbour above / below), and that round up / down without being ties."""
+    r = t.float().to(DT[dtype]).double()
+    _, ex = torch.frexp(t.abs())
+    ulp = torch.clamp(torch.ldexp(torch.ones_like(t), ex - SIG_BITS[dtype]), min=MIN_ULP[dtype])
+    frac = torch.remainder(t.abs() / ulp, 1.0)
+    tie = (frac == 0.5) & (t != 0)
+    n = float(t.numel())
+    return dict(inexact=float((r != t).sum()) / n, tie=float(tie.sum()) / n, tie_up=float((tie & (r > t)).sum()) / n,
+                tie_down=float((tie & (r < t)).sum()) / n, up=float((~tie & (r > t)).sum()) / n, down=float((~tie & (r < t)).sum()) / n)
+
+
+def _round_weights(g, c, density, cover=True):
+    """{-1, 0, 1} weights [Cout][Cin][T] at the given density; cover: every (tap, input channel) pair nonzero in some output channel.
+    Every output channel has a nonzero weight."""
+    Cout, Cin, T = c.Cout, c.Cin, c.R * c.S
+    sel = torch.rand(Cout, Cin, T, generator=g, dtype=torch.float64) < density
+    ci, tt = torch.meshgrid(torch.arange(Cin), torch.arange(T), indexing="ij")
+    if cover:
+        sel[(ci * T + tt) % Cout, ci, tt] = True
+    co = torch.arange(Cout)
+    sel[co, co % Cin, (co // Cin) % T] = True
+    return _pick(g, [-1.0, 1.0], (Cout, Cin, T)) * sel
+
+
+def _check_rounding(o):
+    """Operands.check_rounding: the conditions under which every compared store is exactly one rounding of an exactly known number,
+    and under which the comparison is not empty - on the reference alone, before any launch.  Returns the measured figures."""
+    c, dt, lim = o.case, DT[o.case.dtype], float(2 ** 24)
+    fig = {}
+    ua, uw, ueff = step_of(o.a), step_of(o.w_T), step_of(o.eff)
+    aa = o.a_in.abs().requires_grad_(True)
+    wa = o.w_T.abs().requires_grad_(True)
+    ya = o.fwd(aa, wa)
+    # (a) exact in fp32 in any order: what enters a rounding point (z, the sum behind eff and gx: asserted by _rnd when the reference was
+    # built), every output, data-gradient, red1 term - the same convolution over the operands' absolute values, in units of the step
+    fig["a_y"] = float(ya.detach().max()) / (ua * uw * o.pool)
+    if o.backward:
+        (ya * o.eff.abs()).sum().backward()
+        fig["a_dz"] = float(aa.grad.max()) / (ueff * uw * o.pool)
+        fig["dw_terms"] = float(wa.grad.max()) / (ua * ueff * o.pool)       # below 2**24: the weight gradient is exact too (see dw_exact)
+    for k in ("a_y", "a_dz"):
+        assert fig.get(k, 0.0) < lim, f"(a) {k[2:]}: sum |term| / u = {fig[k]:.3g} >= 2**24"
+    # (b) the fp32 chains of the per-channel sums of stored values
+    if "fwd" in o.parts:
+        fig["b_sum"] = o.chain * float(o.y.abs().max()) / step_of(o.y)
+        assert fig["b_sum"] < lim, f"(b) stat_sum: {fig['b_sum']:.3g} >= 2**24"
+    if "dgrad" in o.parts:
+        fig["b_red1"] = o.chain_red * float(o.dz.abs().max()) / step_of(o.dz)
+        assert fig["b_red1"] < lim, f"(b) red1: {fig['b_red1']:.3g} >= 2**24"
+    # (c) nothing overflows, the outputs are not mostly zero
+    stored = [("a", o.a), ("w_T", o.w_T), ("eff", o.eff)] + ([("y", o.y)] if "fwd" in o.parts else []) + ([("gx", o.gx)] if "dgrad" in o.parts else [])
+    for name, t in stored:
+        assert bool(torch.isfinite(t).all()), f"(c) {name} overflows {dt}"
+    fig["nonzero_y"] = float((o.y != 0).double().mean())
+    assert fig["nonzero_y"] >= 0.9, f"(c) only {fig['nonzero_y']:.3f} of the outputs are nonzero"
+    # (d) / (e): the shares of values that need the rounding, per compared store and per exercised prologue point
+    sh = {}
+    if "fwd" in o.parts:
+        sh["y"] = rounding_shares(o.y_pre, c.dtype)
+    if "dgrad" in o.parts:
+        sh["gx"] = rounding_shares(o.gx_pre, c.dtype)
+    if c.bn and o.round_a:
+        sh["a"] = rounding_shares(o.a_pre, c.dtype)
+    if o.with_q and o.backward:
+        sh["eff"] = rounding_shares(o.eff_pre, c.dtype)
+    sh["w"] = rounding_shares(o.w[o.w != 0], c.dtype)
+    fig["shares"] = sh
+    if o.kind == "main":
+        for k in ("y", "gx"):
+            if k in sh:
+                s = sh[k]
+                assert s["inexact"] >= 0.25 and s["tie"] >= 0.05 and s["tie_up"] > 0 and s["tie_down"] > 0 and s["up"] >= 0.05 and s["down"] >= 0.05, \
+                    f"(d) {k}: {s}"
+        for k in ("a", "eff"):
+            if k in sh:
+                assert sh[k]["inexact"] >= 0.05 and sh[k]["tie"] >= 0.01, f"(e) {k}: {sh[k]}"
+    elif o.kind == "weights":   # the rounding point this set is for: the pack
+        assert sh["w"]["inexact"] >= 0.25 and sh["w"]["tie"] >= 0.01 and sh["w"]["up"] >= 0.05 and sh["w"]["down"] >= 0.05, f"weights: {sh['w']}"
+    else:                       # "subnormal": at least 10 % of the compared stores in (0, 2**-14), and they need the rounding
+        for k, t, pre in (("y", o.y, o.y_pre), ("gx", o.gx if "dgrad" in o.parts else None, getattr(o, "gx_pre", None))):
+            if k in sh:
+                sub = (t != 0) & (t.abs() < 2.0 ** -14)
+                fig["subnormal_" + k] = float(sub.double().mean())
+                fig["subnormal_inexact_" + k] = float((sub & (t != pre)).double().mean())
+                assert fig["subnormal_" + k] >= 0.10 and fig["subnormal_inexact_" + k] >= 0.05, (k, fig)
+    return fig
+
+
+Operands.check_rounding = _check_rounding
+
+
+def make_rounding_operands(dtype, B, H, W, Cin, Cout, R, S, stride, pad, transposed=0, mode=0, bn=1, with_q=0, acc=0,
+                           parts=("fwd", "wgrad", "dgrad"), seed=0, chain=128, chain_red=128, kind="main", nnz_out=None, nnz_in=None, cover=True, round_a=True):
+    """As make_operands - the same case tuple, the same fields - on the single-rounding operands (see above).  kind: "main", "weights"
+    (the weight-rounding set) or "subnormal" (f16).  nnz_out / nnz_in: caps on the nonzero weights that meet in one output element / in
+    one input-gradient element (defaults NNZ_OUT / NNZ_IN).  round_a=False: the activation enters UNROUNDED - the factor form of
+    dmm_conv5_wgrad_stats (wg5.hip PA = 3), which never forms the activation: dw = scale * sum m x dy + shift * sum m dy, m the ReLU mask.
+    Further fields: *_pre, the exactly known numbers in front of each
+    rounding; w_T; dw_exact, whether the weight gradient is exact in fp32 in any order (then compared bit for bit) and dw_bound, the
+    bound it is held to otherwise; sq_bound, red2_bound."""
+    assert dtype in (1, 2) and kind in ("main", "weights", "subnormal") and (kind != "subnormal" or (dtype == 1 and not acc))
+    dt, sig = DT[dtype], SIG_BITS[dtype]
+    c = SimpleNamespace(dtype=dtype, B=B, H=H, W=W, Cin=Cin, Cout=Cout, R=3 if transposed else R, S=3 if transposed else S,
+                        stride=stride, pad=pad, transposed=transposed, mode=mode, bn=bn)
+    parts = tuple(parts)
+    if not bn or (mode == 0 and not transposed and stride != 1):
+        parts = tuple(p for p in parts if p != "dgrad")
+    g = torch.Generator().manual_seed(seed)
+    v = lambda t: t.view(1, -1, 1, 1)  # noqa: E731
+    Ho, Wo = out_hw(c)
+    ri = lambda bits, shape: torch.randint(-(2 ** bits) + 1, 2 ** bits, shape, generator=g).double()  # noqa: E731
+    T = c.R * c.S
+    if kind == "weights":       # the round-8 activations and gradients (small halves)
+        x = torch.randint(-3, 4, (B, Cin, H, W), generator=g).double()
+        scale, shift = _pick(g, [0.5, 1.0, 2.0], (Cin,)), _pick(g, [-1.0, 0.0, 1.0], (Cin,))
+        dy = torch.randint(-2, 3, (B, Cout, Ho, Wo), generator=g).double()
+        yf = 2.0 * torch.randint(-2, 3, (B, Cout, Ho, Wo), generator=g).double()
+        q, r = _pick(g, [-1.0, 0.0, 1.0], (Cout,)), _pick(g, [-1.0, -0.5, 0.0, 0.5, 1.0], (Cout,))
+        gold = torch.randint(-2, 3, (B, Cin, H, W), generator=g).double()
+    else:
+        x = ri(sig - 1, (B, Cin, H, W))
+        scale = _pick(g, ROUND_SCALE, (Cin,))
+        shift = 0.5 * torch.randint(-3, 4, (Cin,), generator=g).double()
+        dy = ri(sig - 2 if with_q else sig - 1, (B, Cout, Ho, Wo))      # (narrower under the correction: the sum is what is stored)
+        yf = ri(sig - 1, (B, Cout, Ho, Wo))
+        q = 0.5 * torch.randint(-3, 4, (Cout,), generator=g).double()
+        r = _pick(g, ROUND_R, (Cout,))
+        gold = 0.25 * ri(sig - 1, (B, Cin, H, W))
+    mean = torch.randint(-2, 3, (Cin,), generator=g).double()
+    invstd = _pick(g, [0.5, 1.0, 2.0], (Cin,))
+    # weights: density from the caps
+    fan_out = Cin * (4 if transposed else T)                # taps that can meet in one output element
+    fan_in = Cout * T * (4 if mode == 1 else 1)             # ... in one input-gradient element
+    no = nnz_out or (16 if kind == "weights" else NNZ_OUT[dtype])      # ("weights": the products step in 2**-13, so few of them)
+    ni = nnz_in or (4 if kind == "weights" else NNZ_IN[with_q])
+    density = min(0.5, no / fan_out, ni / fan_in if "dgrad" in parts else 1.0)
+    wslots = _round_weights(g, c, density, cover)
+    if kind == "weights":
+        k = 2.0 * torch.randint(0, 2 ** 12, wslots.shape, generator=g).double() + 1.0     # odd, up to 13 bits
+        wslots = wslots * k * 2.0 ** -12
+    if kind == "subnormal":
+        s = 2.0 ** -12
+        x, shift, mean, dy, yf, q, wslots = x * s, shift * s, mean * s, dy * s, yf * s, q * s, wslots * s
+    w = wslots.view(Cout, Cin, c.R, c.S)
+    if transposed:
+        w = w.permute(1, 0, 2, 3).contiguous()
+    if not with_q:
+        yf = q = r = None
+    if not acc:
+        gold = None
+    for name, t in (("x", x), ("dy", dy), ("yfwd", yf), ("gold", gold)):      # the inputs stored in the storage type are representable
+        assert t is None or torch.equal(t.to(dt).double(), t), f"{name} is not representable in {dt}"
+    # ---- the reference, every rounding point in the kernels' order
+    w_T = _rnd(w, dt, "w")
+    z = x * v(scale) + v(shift)
+    pool = 0.25 if mode == 2 else 1.0
+    if bn:
+        a_pre = F.avg_pool2d(F.relu(z), 2, 2) if mode == 2 else F.relu(z)     # (the pooling gather: fp32 mean of four, rounded once)
+        a = _rnd(a_pre, dt, "relu(x * scale + shift)") if round_a else a_pre
+    else:
+        a_pre = a = x.clone()
+
+    def fwd(act, wt):
+        """The case's convolution of the (for mode 2: already pooled) activation."""
+        if mode == 2:
+            return F.conv2d(act, wt)
+        return conv(act, wt, c)
+    backward = "wgrad" in parts or "dgrad" in parts
+    eff_pre = eff = dy
+    if with_q:
+        t = v(r) * yf + v(q)
+        assert torch.equal(t.float().double(), t), "(a) fma(yfwd, r, q) is not exact in fp32"
+        eff_pre = dy + t
+        eff = _rnd(eff_pre, dt, "dy + q + r * yfwd")
+    ar = a.clone().requires_grad_(backward)
+    wr = w_T.clone().requires_grad_(backward)
+    y_pre = fwd(ar, wr)
+    o = Operands(case=c, parts=parts, kind=kind, with_q=with_q, acc=acc, chain=chain, chain_red=chain_red, x=x, scale=scale, shift=shift,
+                 mean=mean, invstd=invstd, z=z, dy=dy, yf=yf, q=q, r=r, eff=eff, eff_pre=eff_pre, gold=gold, w=w, w_T=w_T, wslots=wslots,
+                 Ho=Ho, Wo=Wo, backward=backward, a=a, a_in=a, a_pre=a_pre, pool=1.0, round_a=round_a, fwd=fwd, density=float((wslots != 0).double().mean()))
+    o.xhat = (x - v(mean)) * v(invstd)
+    o.y_pre = y_pre.detach()
+    o.y = _rnd(o.y_pre, dt, "conv(a, w_T)")
+    o.stat_sum, o.stat_sq = o.y.sum(dim=(0, 2, 3)), (o.y ** 2).sum(dim=(0, 2, 3))
+    o.sq_bound = chain * 2.0 ** -24 * o.stat_sq          # per channel: one fp32 rounding per added y**2, `chain` of them per partial
+    if backward:
+        (y_pre * eff).sum().backward()
+        o.dw = wr.grad
+        # the number of terms added into one weight-gradient element, and their magnitudes: the same sums over ones / absolute values
+        wn = torch.ones_like(w_T).requires_grad_(True)
+        fwd(torch.ones_like(a), wn).sum().backward()
+        wm = w_T.abs().clone().requires_grad_(True)
+        # (the factor form adds scale * x and shift apart: |scale x| + |shift| under the mask in place of |a|)
+        amag = a.abs() if round_a else (z > 0) * ((v(scale) * x).abs() + v(shift).abs())
+        (fwd(amag, wm) * eff.abs()).sum().backward()
+        o.dw_terms, o.dw_mag = wn.grad, wm.grad
+        o.dw_exact = float(wm.grad.max()) / (step_of(a) * step_of(eff)) < 2 ** 24
+        o.dw_bound = o.dw_terms * 2.0 ** -23 * o.dw_mag
+        da = ar.grad
+        if mode == 2:    # back through the pooling: a quarter of the pooled pixel's gradient to each pixel of the window
+            da = F.interpolate(da, scale_factor=2, mode="nearest") * 0.25
+        o.dz = da * (z > 0) if bn else da
+        sdz = v(scale) * o.dz
+        assert torch.equal(sdz.float().double(), sdz), "(a) scale * dz is not exact in fp32"
+        o.gx_pre = sdz + (gold if acc else 0.0)
+        o.gx = _rnd(o.gx_pre, dt, "gold + scale * dz")
+        o.red1, o.red2 = o.dz.sum(dim=(0, 2, 3)), (o.dz * o.xhat).sum(dim=(0, 2, 3))
+        # red2: one fp32 rounding per added product, chain_red of them per partial; `unc` is the further term of a kernel that adds
+        # dz * x in fp32 and centres the total in fp64 (|x| <= |x - mean| + |mean|): |mean| invstd sum |dz|
+        o.red2_bound = chain_red * 2.0 ** -24 * (o.dz * o.xhat).abs().sum(dim=(0, 2, 3))
+        o.red2_unc = chain_red * 2.0 ** -24 * mean.abs() * invstd * o.dz.abs().sum(dim=(0, 2, 3))
+    return o
+
+
+@functools.lru_cache(maxsize=2)
+def cached_rounding_operands(*args, **kw):
+    return make_rounding_operands(*args, **kw)
+
+
+# ------------------------------------------------------------------------------------------------ the cases of tests/test_rounding_kernels_gpu.py
+# (shared with tests/test_rounding_operands_cpu.py).  Rounding needs no multi-tile walk: the smallest shape each family's resolve
+# accepts - the backward shapes above and the parity shapes where the family takes them, else its FORWARD shape (cf: eight tiles per CU).
+# forward: family, case tuple as CASES, make_rounding_operands arguments: the fp32 chain of the statistics (header of
+# tests/test_exact_kernels_gpu.py) and, where the defaults overflow, the weight caps
+ROUND_FORWARD = [
+    ("pig", ("1x1 160->128 1x16x24", 1, 16, 24, 160, 128, 1, 1, 1, 0, 0, 0, 1), dict(chain=32)),
+    ("pig", ("1x1 72->128 2x12x20", 2, 12, 20, 72, 128, 1, 1, 1, 0, 0, 0, 1), dict(chain=32)),
+    ("conv3", ("3x3 128->32 2x7x9", 2, 7, 9, 128, 32, 3, 3, 1, 1, 0, 0, 1), dict(chain=32)),
+    ("conv3", ("3x3 128->32 2x12x20", 2, 12, 20, 128, 32, 3, 3, 1, 1, 0, 0, 1), dict(chain=32)),
+    ("conv3", ("7x7s2 8->64 2x32x32", 2, 32, 32, 8, 64, 7, 7, 2, 3, 0, 0, 0), dict(chain=32)),      # the stem: no BatchNorm in front
+    ("cf", FORWARD[5][1], dict(chain=128, nnz_out=8)),      # (2091 tiles: the largest |y| of 8.6 M outputs, times a chain of 128)
+    ("cvw", ("convT 128->128 2x7x9", 2, 7, 9, 128, 128, 3, 3, 2, 1, 1, 0, 1), dict(chain=128)),
+    ("cvp", ("convT 384->256 1x11x19", 1, 11, 19, 384, 256, 3, 3, 2, 1, 1, 0, 1), dict(chain=32)),
+]
+# the generic kernel on CASES (every other forward family switched off), by use_mfma: the MFMA forward (chain 32) and the scalar
+# kernel, f16 only - the library has no bf16 scalar kernels.  The scalar kernel's chain of 128 leaves |y| / u two bits less: fewer
+# weights per output, and where covering every (tap, channel) pair alone takes too many (5x5 64->8: 200 per output channel) or the
+# pooled activation steps in sixteenths, no coverage.
+GENERIC_KW = {1: dict(chain=32), 0: dict(chain=128, nnz_out=32)}
+SCALAR_KW = {"5x5 64->8": dict(cover=False), "pool2 1x1 128->64": dict(nnz_out=8, cover=False)}
+
+
+def generic_kw(name, mfma):
+    return {**GENERIC_KW[mfma], **(SCALAR_KW.get(name, {}) if not mfma else {})}
+
+
+_ALL4 = [(1, 1), (1, 0), (0, 1), (0, 0)]
+# backward through backward_case, as BACKWARD.  cvd3 and wg5's transposed form refuse the effective-gradient prologue (cvp.hip
+# cvd_resolve, wg5.hip wg5_resolve: the gradient segment's q must be null), so they run without it.
+ROUND_BACKWARD = [
+    ("fused", "bw1", (1, 16, 24, 160, 128, 1, 1, 0, 0, 0), _ALL4),
+    ("dgrad", "conv3", (2, 7, 9, 128, 32, 3, 3, 1, 0, 0), _ALL4),
+    ("dgrad", "cvp", (1, 9, 17, 256, 256, 3, 3, 1, 1, 0), [(0, 1), (0, 0)]),
+    ("dgrad", "cvp", (1, 9, 7, 128, 64, 3, 3, 1, 0, 1), [(0, 1), (0, 0)]),
+    ("wgradT", "wg3", (3, 5, 3, 128, 32, 3, 3, 1, 0, 0), [(1, 0), (0, 0)]),
+    ("wgradT", "wg3", (2, 12, 20, 128, 32, 3, 3, 1, 0, 0), [(1, 0), (0, 0)]),
+    ("wgrad", "wgp/wgpw", (3, 5, 3, 128, 64, 3, 3, 1, 1, 0), [(1, 0), (0, 0)]),
+    ("wgrad", "wgp/wgpw", (2, 12, 20, 128, 64, 3, 3, 1, 1, 0), [(1, 0), (0, 0)]),
+    ("wgradT", "wg5", (1, 13, 21, 64, 3, 5, 5, 2, 0, 0), [(0, 0)]),
+    ("wgrad", "wg5", (2, 12, 20, 8, 64, 3, 3, 1, 0, 0), [(1, 0), (0, 0)]),
+]
+ROUND_CONV5 = (1, 13, 21)            # conv5_stats_case: B, H, W (the factor correlations run over the workgroup's whole walk: chain_red = B H W)
+ROUND_PIG = ROUND_FORWARD[0][1]
+ROUND_GENERIC = CASES[0]             # 1x1 72->32 2x12x20: 32 output channels, which pig refuses
+ROUND_BW1 = ROUND_BACKWARD[0][2]
+ROUND_CONV3_DGRAD = ROUND_BACKWARD[1][2]

@@ -50,24 +50,56 @@ def _absdiff(a, b):
     return (a.double() - b.double()).abs().max().item()
 
 
-def _verdict(res, exact, tol):
-    """Names of the compared tensors that miss: any difference at all on exact operands, else the relative tolerance (a number or a
-    dict per tensor)."""
+def _ndiff(a, b):
+    """Number of elements of a that are not equal to b (a NaN equals nothing): what the single-rounding cases hold to zero."""
+    return float((a.double() != b.double()).sum())
+
+
+def _ratio(got, ref, bound):
+    """Worst |got - ref| / bound, element by element; a bound of zero must be met exactly (ratio 0 or inf), a NaN is infinitely far."""
+    diff = (got.double() - ref.double()).abs()
+    rk = torch.where(bound > 0, diff / bound.clamp_min(1e-300), (diff != 0).double() * float("inf"))
+    return _maxabs(rk)
+
+
+def _verdict(res, exact, tol, bounded=()):
+    """Names of the compared tensors that miss: any difference at all on exact operands - on the single-rounding operands
+    (exact="round") any differing element, and for the `bounded` quantities any |diff| / bound above 1 - else the relative tolerance
+    (a number or a dict per tensor)."""
     if exact:
-        return [k for k, v in res.items() if not (v == 0)]
+        return [k for k, v in res.items() if not ((v <= 1) if k in bounded else (v == 0))]
     return [k for k, v in res.items() if not (v < (tol[k] if isinstance(tol, dict) else tol))]
+
+
+def _show(res, exact, bounded=()):
+    if exact == "round":   # per tensor the number of differing elements; for the bounded quantities the worst |diff| / bound
+        return " ".join(f"{k}/bound={v:.3g}" if k in bounded else f"{k}={int(v)}" for k, v in res.items())
+    return " ".join(f"{k}={v:.2e}" for k, v in res.items())
+
+
+def _operands(exact, *args, **kw):
+    """The operands and fp64 reference of an exact case, their conditions checked on the reference alone before anything is launched:
+    exact=True the round-8 operands (nothing rounds), exact="round" the single-rounding operands (every store rounds once)."""
+    if exact == "round":
+        o = exact_operands.cached_rounding_operands(*args, **kw)
+        o.check_rounding()
+    else:
+        o = exact_operands.cached_operands(*args, **kw)
+        o.check()
+    return o
 
 
 def conv_case(name, dtype, mfma, B, H, W, Cin, Cout, R, S, stride, pad, transposed=0, mode=0, bn=1, seed=0, expect_wgrad=None,
               expect_fwd=None, expect_dgrad=None, exact=False, parts=("fwd", "wgrad", "dgrad"), exact_kw=None):
     """Forward (+ statistics), weight gradient and BN-fused data gradient of one convolution through the single-kernel entry points.
     expect_*: the kernel family that must have run that launch.  exact: operands of tools/exact_operands.py and an fp64 CPU reference;
-    ok only if every compared tensor is equal bit for bit (parts: which of the three launches to run and compare; exact_kw: further arguments of make_operands)."""
+    ok only if every compared tensor is equal bit for bit (parts: which of the three launches to run and compare; exact_kw: further arguments of make_operands).
+    exact="round": the single-rounding operands (make_rounding_operands) - every tensor stored in the storage type, stat_sum and red1
+    equal bit for bit; stat_sq, red2 and a weight gradient that is not exact in fp32 within the bounds derived from the reference."""
     dt = {0: torch.float32, 1: torch.float16, 2: torch.bfloat16}[dtype]
     if exact:
-        o = exact_operands.cached_operands(dtype, B, H, W, Cin, Cout, R, S, stride, pad, transposed=transposed, mode=mode, bn=bn,
-                                           parts=tuple(parts), seed=seed, **(exact_kw or {}))
-        o.check()   # the conditions that make the comparison exact, on the reference alone, before anything is launched
+        o = _operands(exact, dtype, B, H, W, Cin, Cout, R, S, stride, pad, transposed=transposed, mode=mode, bn=bn,
+                      parts=tuple(parts), seed=seed, **(exact_kw or {}))
         parts = o.parts
         x, scale, shift, w, dy, mean, invstd = (t.float() for t in (o.x, o.scale, o.shift, o.w, o.dy, o.mean, o.invstd))
         wshape = tuple(w.shape)
@@ -97,7 +129,9 @@ def conv_case(name, dtype, mfma, B, H, W, Cin, Cout, R, S, stride, pad, transpos
         # dgrad entry point wants [shift | mean | invstd]; any mean/invstd define xhat for the second reduction
         mean = torch.randn(Cin, generator=g)
         invstd = torch.rand(Cin, generator=g) + 0.5
-    err = _absdiff if exact else relerr
+    rnd = exact == "round"
+    err = _ndiff if rnd else (_absdiff if exact else relerr)
+    bounded = set()
     d = _lib.ConvDesc(dtype=dtype, use_mfma=mfma, B=B, H=H, W=W, Cin=Cin, Cout=Cout, R=R, S=S, stride=stride, pad=pad,
                       transposed=transposed, mode=mode, bn_relu=bn)
     nsc = L.dmm_conv_scratch_bytes(C.byref(d))
@@ -118,7 +152,11 @@ def conv_case(name, dtype, mfma, B, H, W, Cin, Cout, R, S, stride, pad, transpos
         yo = nchw(yd).cpu()
         res["fwd"] = err(yo, y.detach())
         res["sum"] = err(stats[:Cout].cpu(), o.stat_sum if exact else yo.double().sum(dim=(0, 2, 3)))
-        res["sq"] = err(stats[Cout:].cpu(), o.stat_sq if exact else (yo.double() ** 2).sum(dim=(0, 2, 3)))
+        if rnd:
+            res["sq"] = _ratio(stats[Cout:].cpu(), o.stat_sq, o.sq_bound)
+            bounded.add("sq")
+        else:
+            res["sq"] = err(stats[Cout:].cpu(), o.stat_sq if exact else (yo.double() ** 2).sum(dim=(0, 2, 3)))
     dyd = nhwc(dy, dt).to(DEV)
     if "wgrad" in parts:
         dwd = torch.full(wshape, float("nan"), device=DEV)
@@ -127,7 +165,11 @@ def conv_case(name, dtype, mfma, B, H, W, Cin, Cout, R, S, stride, pad, transpos
                                     scratch.data_ptr(), st))
         torch.cuda.synchronize()
         fam_ok &= _check_family(name + " wgrad", expect_wgrad)
-        res["wgrad"] = err(dwd.cpu(), o.dw if exact else wq.grad)
+        if rnd and not o.dw_exact:
+            res["wgrad"] = _ratio(dwd.cpu(), o.dw, o.dw_bound)
+            bounded.add("wgrad")
+        else:
+            res["wgrad"] = err(dwd.cpu(), o.dw if exact else wq.grad)
     # dgrad (BN fused)
     if "dgrad" in parts and bn and not (mode == 0 and not transposed and stride != 1):
         if exact:
@@ -147,10 +189,14 @@ def conv_case(name, dtype, mfma, B, H, W, Cin, Cout, R, S, stride, pad, transpos
         fam_ok &= _check_family(name + " dgrad", expect_dgrad)
         res["dgrad"] = err(nchw(gxd).cpu(), gx_ref)
         res["red1"] = err(red[:Cin].cpu(), red1_ref)
-        res["red2"] = err(red[Cin:].cpu(), red2_ref)
+        if rnd:
+            res["red2"] = _ratio(red[Cin:].cpu(), red2_ref, o.red2_bound)
+            bounded.add("red2")
+        else:
+            res["red2"] = err(red[Cin:].cpu(), red2_ref)
     tol = {0: 2e-5, 1: 3e-3, 2: 2.5e-2}[dtype]   # relative to the tensor's max: fp32 / f16 (11 bits) / bf16 (8 bits) storage
-    bad = _verdict(res, exact, tol)
-    print(f"{'FAIL' if bad else 'ok  '} {name:28s} dt={dtype} mfma={mfma}{' exact' if exact else ''} " + " ".join(f"{k}={v:.2e}" for k, v in res.items()), flush=True)
+    bad = _verdict(res, exact, tol, bounded)
+    print(f"{'FAIL' if bad else 'ok  '} {name:28s} dt={dtype} mfma={mfma}{(' round' if rnd else ' exact') if exact else ''} " + _show(res, exact, bounded), flush=True)
     return not bad and fam_ok
 
 
@@ -178,13 +224,15 @@ def backward_case(name, dtype, B, H, W, Cin, Cout, R, S, pad, transposed=0, with
              "dgrad":  dmm_conv_dgrad_ex with the effective-gradient prologue (conv3.hip PRO=2 for the dense 3x3)
              "wgradT": dmm_conv_wgrad_ex in the transposed form (wg3.hip for the dense 3x3)
              "wgrad":  dmm_conv_wgrad_ex, normal form, with the effective-gradient prologue (wgp.hip for ConvTranspose phases)
-    exact: operands of tools/exact_operands.py, fp64 CPU reference, every compared tensor equal bit for bit."""
+    exact: operands of tools/exact_operands.py, fp64 CPU reference, every compared tensor equal bit for bit.  exact="round": the
+    single-rounding operands, compared as in conv_case."""
     dt = {0: torch.float32, 1: torch.float16, 2: torch.bfloat16}[dtype]
+    rnd = exact == "round"
+    bounded = set()
     if exact:
         parts = {"fused": ("wgrad", "dgrad"), "dgrad": ("dgrad",)}.get(what, ("wgrad",))
-        o = exact_operands.cached_operands(dtype, B, H, W, Cin, Cout, R, S, 2 if transposed else 1, pad, transposed=transposed, mode=mode,
-                                           bn=1, with_q=with_q, acc=acc, parts=parts, seed=seed, **(exact_kw or {}))
-        o.check()   # on the reference alone, before anything is launched
+        o = _operands(exact, dtype, B, H, W, Cin, Cout, R, S, 2 if transposed else 1, pad, transposed=transposed, mode=mode,
+                      bn=1, with_q=with_q, acc=acc, parts=parts, seed=seed, **(exact_kw or {}))
         f32 = lambda t: t.float() if t is not None else None  # noqa: E731
         x, scale, shift, mean, invstd, w, dy, yf, q, r, gold = (f32(t) for t in (o.x, o.scale, o.shift, o.mean, o.invstd, o.w, o.dy, o.yf,
                                                                                  o.q, o.r, o.gold))
@@ -232,7 +280,7 @@ def backward_case(name, dtype, B, H, W, Cin, Cout, R, S, pad, transposed=0, with
     ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
     st = _lib.stream_ptr()
     res = {}
-    err = _absdiff if exact else relerr
+    err = _ndiff if rnd else (_absdiff if exact else relerr)
     gxd = nhwc(gold.float(), dt).to(DEV) if acc else torch.full((B, H, W, Cin), float("nan"), dtype=dt, device=DEV)
     red = torch.zeros(2 * Cin, dtype=torch.float64, device=DEV)
     dwd = torch.full(wshape, float("nan"), device=DEV)
@@ -252,16 +300,27 @@ def backward_case(name, dtype, B, H, W, Cin, Cout, R, S, pad, transposed=0, with
     if what in ("fused", "dgrad"):
         res["dgrad"] = err(nchw(gxd).cpu(), gx_ref.cpu())
         res["red1"] = err(red[:Cin].cpu(), red1_ref.cpu())
-        res["red2"] = err(red[Cin:].cpu(), red2_ref.cpu())
+        if rnd:
+            # bw1's f16 epilogue (gather.h bnbwd_slot) adds dz * x in fp32 and centres the total in fp64; every other kernel adds the
+            # centred product dz * xhat, with xhat exact in fp32 on these operands
+            unc = what == "fused" and dtype == 1
+            res["red2"] = _ratio(red[Cin:].cpu(), red2_ref, o.red2_bound + (o.red2_unc if unc else 0.0))
+            bounded.add("red2")
+        else:
+            res["red2"] = err(red[Cin:].cpu(), red2_ref.cpu())
     if what != "dgrad":
-        res["wgrad"] = err(dwd.cpu(), dw_ref.cpu())
+        if rnd and not o.dw_exact:
+            res["wgrad"] = _ratio(dwd.cpu(), dw_ref, o.dw_bound)
+            bounded.add("wgrad")
+        else:
+            res["wgrad"] = err(dwd.cpu(), dw_ref.cpu())
     tol = {0: 2e-5, 1: 3e-3, 2: 2.5e-2}[dtype]
-    bad = _verdict(res, exact, tol)
-    print(f"{'FAIL' if bad else 'ok  '} {what:6s} {name:28s} dt={dtype} q={with_q} acc={acc}{' exact' if exact else ''} " + " ".join(f"{k}={v:.2e}" for k, v in res.items()), flush=True)
+    bad = _verdict(res, exact, tol, bounded)
+    print(f"{'FAIL' if bad else 'ok  '} {what:6s} {name:28s} dt={dtype} q={with_q} acc={acc}{(' round' if rnd else ' exact') if exact else ''} " + _show(res, exact, bounded), flush=True)
     return not bad and fam_ok
 
 
-def conv5_stats_case(name, dtype, B, H, W, Cout=3, seed=0, ref_dev="cpu", exact=False):
+def conv5_stats_case(name, dtype, B, H, W, Cout=3, seed=0, ref_dev="cpu", exact=False, exact_kw=None):
     """dmm_conv5_wgrad_stats (round 5; wg5.hip PA = 3 + wg5_fin64_kernel): the head's 5x5 convolution behind BN+ReLU - weight gradient
     AND the two BatchNorm-backward sums of the norm in front of it from one pass over x and dy - against fp64 torch on the same
     16-bit-rounded operands: dz = [bn(x) > 0] * conv_dgrad(dy, w rounded to the storage type).  The sums are held to 1e-6 (f16) of the
@@ -270,8 +329,7 @@ def conv5_stats_case(name, dtype, B, H, W, Cout=3, seed=0, ref_dev="cpu", exact=
     dt = {1: torch.float16, 2: torch.bfloat16}[dtype]
     Cin = 64
     if exact:   # operands of tools/exact_operands.py: weight gradient and both sums equal to fp64 bit for bit
-        o = exact_operands.cached_operands(dtype, B, H, W, Cin, Cout, 5, 5, 1, 2, parts=("wgrad", "dgrad"), seed=seed)
-        o.check()
+        o = _operands(exact, dtype, B, H, W, Cin, Cout, 5, 5, 1, 2, parts=("wgrad", "dgrad"), seed=seed, **(exact_kw or {}))
         x, scale, shift, mean, invstd, w, dy = (t.float() for t in (o.x, o.scale, o.shift, o.mean, o.invstd, o.w, o.dy))
         red1_ref, red2_ref, dw_ref = o.red1, o.red2, o.dw
     else:
@@ -305,12 +363,20 @@ def conv5_stats_case(name, dtype, B, H, W, Cout=3, seed=0, ref_dev="cpu", exact=
                                        red.data_ptr(), scratch.data_ptr(), _lib.stream_ptr()))
     torch.cuda.synchronize()
     fam_ok = _check_family(f"conv5 {name}", "wg5")
-    err = _absdiff if exact else relerr
+    rnd = exact == "round"
+    bounded = set()
+    err = _ndiff if rnd else (_absdiff if exact else relerr)
     res = {"red1": err(red[:Cin].cpu(), red1_ref.cpu()), "red2": err(red[Cin:].cpu(), red2_ref.cpu()),
            "wgrad": err(dwd.cpu(), dw_ref.cpu())}
+    if rnd:
+        res["red2"] = _ratio(red[Cin:].cpu(), red2_ref, o.red2_bound + o.red2_unc)
+        bounded.add("red2")
+        if not o.dw_exact:
+            res["wgrad"] = _ratio(dwd.cpu(), dw_ref, o.dw_bound)
+            bounded.add("wgrad")
     tol = {"red1": 1e-6, "red2": 1e-6, "wgrad": {1: 3e-3, 2: 2.5e-2}[dtype]}
-    bad = _verdict(res, exact, tol)
-    print(f"{'FAIL' if bad else 'ok  '} conv5  {name:28s} dt={dtype}{' exact' if exact else ''} " + " ".join(f"{k}={v:.2e}" for k, v in res.items()), flush=True)
+    bad = _verdict(res, exact, tol, bounded)
+    print(f"{'FAIL' if bad else 'ok  '} conv5  {name:28s} dt={dtype}{(' round' if rnd else ' exact') if exact else ''} " + _show(res, exact, bounded), flush=True)
     return not bad and fam_ok
 
 

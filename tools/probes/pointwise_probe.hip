@@ -224,14 +224,17 @@ static void check_stats(Case& c, const char* what, const std::vector<double>& go
 }
 
 // ---------------------------------------------------------------------------------------------------- convert
-static void convert_case(int dt, const char* nm, int B, int H, int W, int C1, int C2, float scale, bool dyn, bool stats, bool dyadic) {
+// kmax: the dyadic grid is k / 4, |k| <= kmax.  1024: 11 significant bits, representable in f16.  8191 (the rounding cases): 13
+// significant bits - the store to f16 / bf16 is ONE round-to-nearest-even of an exactly known number, ties included; the reference is
+// the fp64 product followed by the conversion written out above (f2h / f2b), and the case fails if the grid does not need it.
+static void convert_case(int dt, const char* nm, int B, int H, int W, int C1, int C2, float scale, bool dyn, bool stats, bool dyadic, int kmax = 1024) {
   Case cs("convert %s %s B%d H%d W%d C1=%d C2=%d", DTN[dt], nm, B, H, W, C1, C2);
   const size_t plane = (size_t)H * W, npix = (size_t)B * plane;
   const float dynv = 8.f;   // a power of two: x * (scale * dyn) and (x * scale) * dyn are the same fp32 number
   std::vector<float> s1(npix * C1), s2(npix * C2);
   auto fill = [&](std::vector<float>& s, uint64_t seed) {
     par_for(s.size(), [&](size_t lo, size_t hi, int) {
-      for (size_t i = lo; i < hi; ++i) s[i] = dyadic ? dyad(seed, i, 1024, 0.25f) : (float)(unif(seed, i) * 6.0 - 3.0);
+      for (size_t i = lo; i < hi; ++i) s[i] = dyadic ? dyad(seed, i, kmax, 0.25f) : (float)(unif(seed, i) * 6.0 - 3.0);
     });
   };
   fill(s1, 11 + dt); fill(s2, 23 + dt);
@@ -249,10 +252,12 @@ static void convert_case(int dt, const char* nm, int B, int H, int W, int C1, in
   const int nt = n_threads();
   std::vector<double> ps(nt * 8, 0.0), pq(nt * 8, 0.0), pa(nt * 8, 0.0), pb(nt * 8, 0.0);
   std::vector<int> inexact(nt, 0);
+  std::vector<size_t> nround(nt, 0), ntie(nt, 0);
   par_for(npix, [&](size_t lo, size_t hi, int t) {
     for (size_t p = lo; p < hi; ++p)
       for (int c = 0; c < 8; ++c) {
         const float v = val(p, c);
+        if (rnd_to(dt, v) != v) { ++nround[t]; if (std::fabs((double)rnd_to(dt, v) - (double)v) == half_ulp(dt, v)) ++ntie[t]; }
         if (dyadic) {
           const size_t b = p / plane, rem = p % plane;
           const double x = c < C1 ? s1[(b * C1 + c) * plane + rem] : c < C1 + C2 ? s2[(b * C2 + (c - C1)) * plane + rem] : 0.0;
@@ -266,6 +271,11 @@ static void convert_case(int dt, const char* nm, int B, int H, int W, int C1, in
   }, 1 << 14);
   for (int t = 0; t < nt; ++t) exact = exact && !inexact[t];
   if (!exact) cs.fail("probe bug: the fp32 product is not exact on this grid");
+  if (kmax > 1024) {   // a rounding case: at least a quarter of the stores round, one in fifty is an exact tie
+    size_t nr = 0, nti = 0;
+    for (int t = 0; t < nt; ++t) { nr += nround[t]; nti += ntie[t]; }
+    if (4 * nr < npix * (size_t)(C1 + C2) || 50 * nti < npix * (size_t)(C1 + C2)) cs.fail("probe bug: only %zu of %zu values round (%zu ties)", nr, npix * (C1 + C2), nti);
+  }
   std::vector<double> rs(8, 0.0), rq(8, 0.0), ra(8, 0.0);
   for (int t = 0; t < nt; ++t) for (int c = 0; c < 8; ++c) { rs[c] += ps[t * 8 + c]; rq[c] += pq[t * 8 + c]; ra[c] += pa[t * 8 + c]; }
 
@@ -305,6 +315,10 @@ static void group_convert() {
     convert_case(dt, "no-stats dyn", 2, 3, 5, 4, 4, 0.25f, true, false, true);
     convert_case(dt, "grid-stride", 3, 419, 835, 3, 3, 0.25f, true, true, true);   // 1 049 595 pixels > 4096 x 256 threads
     convert_case(dt, "non-dyadic", 2, 3, 5, 3, 2, 0.37f, true, true, false);
+    if (dt != DT_F32) {   // 13 significant bits into 11 / 8
+      convert_case(dt, "rounding", 2, 13, 17, 3, 3, 1.f, false, true, true, 8191);
+      convert_case(dt, "rounding dyn", 2, 13, 17, 5, 3, 0.25f, true, true, true, 8191);
+    }
   }
 }
 
@@ -686,20 +700,30 @@ static void group_poolbwd() {
 // ---------------------------------------------------------------------------------------------------- apply_corr
 // g += (q + ql) + (r + rl) * y.  Grids: g, y in quarters up to +-4, r in {+-0.5, +-1, 2}, q in quarters, rl in 2^-8, ql in 2^-10: every
 // value is a multiple of 2^-10 below 32 (15 bits); the store rounds it to the storage type.
-static void corr_case(int dt, const char* nm, size_t npix, int C, int ldg, int ldy) {
+// wide (the rounding cases, 16-bit types): the stored gradient is s * dz + q + r * x as the backward forms it - g = s * dz with s in
+// {0.75, 1.5} and dz integers below 2^(sig - 3) (g itself representable), x integers below 2^sig, r in {+-0.75, +-1.5}, q in
+// halves, ql = rl = 0: the result steps in quarters up to 2^(sig + 1), up to four bits more than the type holds, and the store is ONE
+// round-to-nearest-even of it (reference: the fp64 sum and the conversion written out above; the case fails if too few values round).
+static void corr_case(int dt, const char* nm, size_t npix, int C, int ldg, int ldy, bool wide = false) {
   Case cs("corr %s %s npix=%zu C%d ldg=%d ldy=%d", DTN[dt], nm, npix, C, ldg, ldy);
   static const float RR[5] = {0.5f, -0.5f, 1.f, -1.f, 2.f};
+  static const float RW[4] = {0.75f, -0.75f, 1.5f, -1.5f};
   std::vector<float> q(C), r(C), ql(C), rl(C);
   for (int c = 0; c < C; ++c) { q[c] = dyad(401, c, 8, 0.25f); r[c] = pick(402, c, RR); ql[c] = dyad(403, c, 3, 1.f / 1024); rl[c] = dyad(404, c, 2, 1.f / 256); }
+  if (wide) for (int c = 0; c < C; ++c) { q[c] = dyad(401, c, 3, 0.5f); r[c] = pick(402, c, RW); ql[c] = 0.f; rl[c] = 0.f; }
+  const int sig = dt == DT_F16 ? 11 : 8;
   float tab[33]; uint32_t tabb[33];
   for (int k = 0; k < 33; ++k) { tab[k] = (k - 16) * 0.25f; tabb[k] = enc(dt, tab[k]); }
+  // the wide grids, from the element's index
+  auto gwide = [&](size_t i) { return ((mix(700 + dt, i) & 1) ? 0.75f : 1.5f) * dyad(701 + dt, i, (1 << (sig - 3)) - 1, 1.f); };
+  auto ywide = [&](size_t i) { return dyad(702 + dt, i, (1 << sig) - 1, 1.f); };
   const uint32_t FILLB = enc(dt, -7.5f);
   const size_t ng = npix * ldg, ny = npix * ldy;
   std::vector<uint8_t> gb(ng * esz(dt)), yb(ny * esz(dt));
   auto gidx = [&](size_t i) { return (int)(mix(500 + dt, i) % 33); };
   auto yidx = [&](size_t i) { return (int)(mix(600 + dt, i) % 33); };
-  par_for(ng, [&](size_t lo, size_t hi, int) { for (size_t i = lo; i < hi; ++i) put_bits(dt, gb.data(), i, (int)(i % ldg) < C ? tabb[gidx(i)] : FILLB); });
-  par_for(ny, [&](size_t lo, size_t hi, int) { for (size_t i = lo; i < hi; ++i) put_bits(dt, yb.data(), i, tabb[yidx(i)]); });
+  par_for(ng, [&](size_t lo, size_t hi, int) { for (size_t i = lo; i < hi; ++i) put_bits(dt, gb.data(), i, (int)(i % ldg) < C ? (wide ? enc(dt, gwide(i)) : tabb[gidx(i)]) : FILLB); });
+  par_for(ny, [&](size_t lo, size_t hi, int) { for (size_t i = lo; i < hi; ++i) put_bits(dt, yb.data(), i, wide ? enc(dt, ywide(i)) : tabb[yidx(i)]); });
   Dev dy(yb), dq(q), dr(r), dql(ql), drl(rl);
   Out og(gb.data(), gb.size());
   ApplyCorrArgs a;
@@ -708,6 +732,7 @@ static void corr_case(int dt, const char* nm, size_t npix, int C, int ldg, int l
   a.npix = npix; a.C = C; a.ldg = ldg; a.ldy = ldy;
   ran(launch_apply_corr(a, dt, nullptr), cs.name.c_str());
   std::vector<int> inexact(n_threads(), 0);
+  std::vector<size_t> nround(n_threads(), 0), ntie(n_threads(), 0);
   const bool ok = og.fetch(gb.data(), cs, "g");   // (the inputs are regenerated from their index)
   if (ok) {
     std::vector<size_t> bad(n_threads(), SIZE_MAX);
@@ -717,11 +742,13 @@ static void corr_case(int dt, const char* nm, size_t npix, int C, int ldg, int l
         const int c = (int)(i % ldg);
         uint32_t w = FILLB;
         if (c < C) {
-          const double g = tab[gidx(i)], y = tab[yidx((i / ldg) * ldy + c)];
+          const double g = wide ? gwide(i) : tab[gidx(i)], y = wide ? ywide((i / ldg) * ldy + c) : tab[yidx((i / ldg) * ldy + c)];
+          if (wide && ((double)rnd_to(dt, (float)g) != g || (double)rnd_to(dt, (float)y) != y)) inexact[t] = 1;   // (the inputs are stored exactly)
           const double e = g + ((double)q[c] + ql[c]) + ((double)r[c] + rl[c]) * y;
           float ef = r[c] * (float)y; ef += q[c]; ef += (float)g; float lo2 = rl[c] * (float)y; lo2 += ql[c]; ef += lo2;
           if ((double)ef != e) inexact[t] = 1;
           w = enc(dt, ef);
+          if (dec(dt, w) != ef) { ++nround[t]; if (std::fabs((double)dec(dt, w) - e) == half_ulp(dt, e)) ++ntie[t]; }
         }
         if (!same_value(dt, get_bits(dt, gb.data(), i), w)) { bad[t] = i; badw[t] = w; return; }
       }
@@ -729,6 +756,11 @@ static void corr_case(int dt, const char* nm, size_t npix, int C, int ldg, int l
     for (int t = 0; t < n_threads(); ++t)
       if (bad[t] != SIZE_MAX) { cs.fail("g[%zu] (pixel %zu channel %zu) got %.9g want %.9g", bad[t], bad[t] / ldg, bad[t] % ldg, dec(dt, get_bits(dt, gb.data(), bad[t])), dec(dt, badw[t])); break; }
     for (int v : inexact) if (v) cs.fail("probe bug: the corrected gradient is not exact in fp32 on this grid");
+    if (wide) {   // at least a quarter of the stores round, one in fifty is an exact tie
+      size_t nr = 0, nti = 0;
+      for (int t = 0; t < n_threads(); ++t) { nr += nround[t]; nti += ntie[t]; }
+      if (4 * nr < npix * (size_t)C || 50 * nti < npix * (size_t)C) cs.fail("probe bug: only %zu of %zu values round (%zu ties)", nr, npix * (size_t)C, nti);
+    }
   }
   cs.done();
 }
@@ -738,6 +770,7 @@ static void group_corr(bool big_only, bool small_only) {
     if (!big_only) {
       corr_case(dt, "one-slot", 7, slot_of(dt), 16, 24);
       corr_case(dt, "tail-loop", 1000, 64, 96, 64);
+      if (dt != DT_F32) corr_case(dt, "rounding", 1000, 64, 96, 64, true);
     }
     // 128 channel slots: rows = 4 Mi / 128 = 32 768, the 4-way unrolled loop runs once and the tail loop once or twice behind it.
     // (bf16 runs the f16 instance's template with another conversion, which the small cases cover.)
