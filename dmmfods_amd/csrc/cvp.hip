@@ -20,6 +20,7 @@
 #include "common.h"
 #include "dispatch.h"
 #include "gather.h"
+#include "isa.h"
 
 namespace dmm {
 
@@ -521,22 +522,65 @@ __global__ __launch_bounds__(NTHREADS, 2) void cvd_kernel(const CvdArgs g) {
 //     p * 128 + ((s ^ ((p >> 1) & 7)) << 4) - the 16 pixels of a fragment read (consecutive p) hit 16 different 16-byte slots of the
 //     256-byte bank period: the two parities of p take the halves, (p >> 1) & 7 permutes the slots inside a half -, 19.1 KB;
 //   * the fp32 staging runs in two column halves of 64 (34.8 KB over the dead images) with the epilogue of a half behind each;
-//   * no prefetch across the staging: <= 168 registers.
-// 52.9 KB of LDS: three workgroups per CU.  Same K order and epilogue arithmetic per output element as cvd_kernel: gradients
-// bit-equal, the BatchNorm sums equal up to the grouping of their fp32 partials (rows per thread: 4 instead of 8).
+//   * the weights stream through a RING of four 8 KB chunk slots (the 32 KB of the former two stage buffers) filled by LDS-DMA
+//     (isa.h lds_dma16; the XOR swizzle of the B image on the per-lane SOURCE address) three chunks ahead of their use, across tap,
+//     group and class boundaries: the walk is one flat sequence of chunks, a cursor names the source of the next one.  One raw
+//     barrier per chunk behind a COUNTED wait (vm_lds_barrier_n): the chunk about to be multiplied has landed, the two behind it
+//     and the next halo stay in flight; the refill of the slot just released is issued right behind the barrier (every fragment
+//     read of it has returned: lgkmcnt(0) in the same asm statement, conv3.hip's rule).  Formerly a stage's weights went through 16
+//     registers one stage ahead and every stage barrier was __syncthreads() - vmcnt(0): each stage began with a memory latency, and
+//     the next halo was drained at the first stage barrier behind its issue.  The halo loads are still plain loads that hipcc counts:
+//     its wait for them at the top of a group (vmcnt(0) as far as it knows) also retires the ring's two or three requests in flight -
+//     once per group, not per stage; exact there would be gload16 loads with DMM_VM_WAIT(4) (isa.h) - not built;
+//   * the 16 registers the ring frees hold the epilogue's x rows of the first column half, requested behind the LAST refill of the
+//     walk - three chunks of MFMAs in front of the staging - and counted by the walk's last three barriers; the second half's x flies
+//     under the first half's arithmetic; the old gradient of a half (a.accumulate) is requested in front of that half's staging (under
+//     the walk with x it spilled: 36 bytes of scratch in the ConvTranspose form).
+// Round 10, alone at 4 x 1280 x 1920 / the stages of C2 b4 (us, parent -> ring): head 1009 -> 905, TC_1 212 -> 208, TC_2 190 -> 186,
+// TC_3 213 -> 202; three slots of a 16 KB stage at two workgroups per CU (CVD3_RING_B): 993 / 243 / 201 / 216 (profiles/r10/ablations.txt).
+// 52.9 KB of LDS; 168 (head) / 166 (ConvTranspose form) registers, no AGPRs, no scratch: three workgroups per CU.  Same K order and
+// epilogue arithmetic per output element as
+// cvd_kernel: gradients bit-equal, the BatchNorm sums equal up to the grouping of their fp32 partials (rows per thread: 4 instead of 8).
+#ifndef CVD3_DBG
+#define CVD3_DBG 0  // timing experiments only (tools/build_variant.sh ... -DCVD3_DBG=n; the shipped library carries no switch): 1 every
+#endif              // chunk multiplies the first chunk's weights, no weight request after the prologue's; 2 no halo after the first; 4 no epilogue
+#ifndef CVD3_RING_B
+#define CVD3_RING_B 0  // experiment build: three slots of a 16 KB stage, one barrier per stage, two workgroups per CU (ablations.txt, r10)
+#endif
 constexpr int C3D_NHP = CP_HH * CP_HW;                       // 153 halo pixels
 constexpr int C3D_X_BYTES = C3D_NHP * 128;                   // 19 584
-constexpr int C3D_MAIN = C3D_X_BYTES + 2 * CP_B_STAGE;       // 52 352
+constexpr int C3D_CHUNK = CP_BN * 64;                        // 8 KB: 32 values of K for 128 columns
+constexpr int C3D_STEP = CVD3_RING_B ? 2 : 1;                // chunks per barrier
+constexpr int C3D_RING = CVD3_RING_B ? 6 : 4;                // ring slots (of one chunk)
+constexpr int C3D_AHEAD = C3D_RING / C3D_STEP - 1;           // a step's weights are requested this many steps ahead
+constexpr int C3D_PW = C3D_CHUNK / 1024 / (NTHREADS / 64);   // LDS-DMA requests per wave and chunk: 2
+constexpr int C3D_WCUR = (C3D_AHEAD - 1) * C3D_STEP * C3D_PW;  // requests that stay in flight across a step barrier: 4
+constexpr int C3D_MAIN = C3D_X_BYTES + C3D_RING * C3D_CHUNK; // 52 352
 constexpr int C3D_LDS = C3D_MAIN + BM * 4;                   // + rowpix
 constexpr int C3D_FP = 64 + 4;                               // staging pitch (floats) of a column half
 constexpr int C3D_RED = BM * C3D_FP * 4;                     // offset of the fp64 sums inside the dead images
 static_assert(C3D_RED + 2 * 128 * 8 <= C3D_MAIN, "staging of a column half + the fp64 sums fit the operand images");
-static_assert(3 * C3D_LDS <= 160 * 1024, "three workgroups per CU");
+static_assert(CVD3_RING_B || 3 * C3D_LDS <= 160 * 1024, "three workgroups per CU");
+static_assert(C3D_RING * C3D_CHUNK == (CVD3_RING_B ? 3 : 2) * CP_B_STAGE && C3D_RING % C3D_STEP == 0 && C3D_AHEAD >= 2, "ring geometry");
+
+// vm_lds_barrier<n> (isa.h) for an n that is a constant only after unrolling
+__device__ __forceinline__ void vm_lds_barrier_n(int n) {
+  switch (n) {
+    case 0: vm_lds_barrier<0>(); break;
+    case 2: vm_lds_barrier<2>(); break;
+    case 4: vm_lds_barrier<4>(); break;
+    case 6: vm_lds_barrier<6>(); break;
+    case 8: vm_lds_barrier<8>(); break;
+    case 10: vm_lds_barrier<10>(); break;
+    case 12: vm_lds_barrier<12>(); break;
+    default: vm_lds_barrier<0>(); break;
+  }
+}
 
 // UP2: the head's 16 merged taps (four per class) over ONE 64-channel group; !UP2: a ConvTranspose stage's nine taps (1, 2, 2, 4 per class)
 // over C / 64 channel groups (cvd_kernel<T, 128, false> walks them in groups of 128: 256 registers, 76.5 KB)
 template <typename T, bool UP2>
-__global__ __launch_bounds__(NTHREADS, 3) void cvd3_kernel(const CvdArgs g) {
+__global__ __launch_bounds__(NTHREADS, CVD3_RING_B ? 2 : 3) void cvd3_kernel(const CvdArgs g) {
   static_assert(sizeof(T) == 2, "16-bit storage");
   typedef typename TT<T>::vec V;
   constexpr int SLOT = 8, BN = CP_BN, NT = BN / 32;
@@ -594,28 +638,33 @@ __global__ __launch_bounds__(NTHREADS, 3) void cvd3_kernel(const CvdArgs g) {
 
   const T* wp = (const T*)a.wpack;
   const int cpt = sy.Cpad / 32;
-  V rb[2][2];
-  int blds[2];
+  const int ngrp = UP2 ? 1 : sy.C / 64;   // (the head: one group, known to the compiler - the walk is then straight-line code)
+  // ---- weights: a chunk = 128 columns x 64 bytes = 8 x 1 KB LDS-DMA pieces of 16 columns, wave w issues pieces 2 w and 2 w + 1.  Lane l
+  // of a piece writes the 16 bytes at l * 16: column l >> 2, slot l & 3 of the image, which holds slot (l & 3) ^ ((column >> 2) & 3) of
+  // the source (the swizzle the fragment reads undo).  The cursor (q_*) walks class -> group -> tap -> chunk, one chunk per request.
+  const unsigned lds0 = (unsigned)(size_t)(__attribute__((address_space(3))) unsigned char*)smem;
+  const unsigned wdst0 = __builtin_amdgcn_readfirstlane(lds0 + C3D_X_BYTES + wave * (C3D_PW * 1024));
+  const T* wsrc = wp + (size_t)n0 * 32 + (wave * (C3D_PW * 16) + (lane >> 2)) * 32 + (((lane & 3) ^ ((lane >> 4) & 3)) << 3);
+  const size_t wchunk = (size_t)a.Npad * 32;   // elements from a chunk to the next
+  int q_cls = 0, q_grp = 0, q_tt = 0, q_uu = 0, q_first = 0, q_slot = 0;
+  int q_c0 = g.tapidx[0] * cpt;   // first chunk of the cursor's tap (read when the cursor enters the tap: a step before it is used)
+  auto issue_w = [&]() {   // the next chunk of the walk -> the next slot of the ring; nothing behind the last chunk
+    if (q_cls < 4) {
+      const T* s = wsrc + (size_t)(q_c0 + q_grp * 2 + q_uu) * wchunk;
+      const unsigned dst = wdst0 + q_slot * C3D_CHUNK;
 #pragma unroll
-  for (int j = 0; j < 2; ++j) {
-    const int piece = tid + NTHREADS * j, row = piece >> 2, slot = piece & 3;
-    blds[j] = row * 64 + ((slot ^ ((row >> 2) & 3)) << 4);
-  }
-  auto issue_b = [&](int tap, int grp) {
-    const int c0 = tap * cpt + grp * 2;
-#pragma unroll
-    for (int uu = 0; uu < 2; ++uu) {
-      const T* src = wp + ((size_t)(c0 + uu) * a.Npad + n0) * 32;
-#pragma unroll
-      for (int j = 0; j < 2; ++j) rb[uu][j] = *(const V*)(src + (size_t)(tid + NTHREADS * j) * SLOT);
+      for (int q = 0; q < C3D_PW; ++q) lds_dma16(s + q * (16 * 32), dst + q * 1024);
+      q_slot = q_slot + 1 == C3D_RING ? 0 : q_slot + 1;
+      if (++q_uu == 2) {
+        q_uu = 0;
+        const int nt = UP2 ? 4 : ((q_cls >> 1) + 1) * ((q_cls & 1) + 1);
+        if (++q_tt == nt) {
+          q_tt = 0;
+          if (++q_grp == ngrp) { q_grp = 0; ++q_cls; q_first += nt; }
+        }
+        if (q_cls < 4) q_c0 = g.tapidx[q_first + q_tt] * cpt;
+      }
     }
-  };
-  auto store_b = [&](int buf) {
-    unsigned char* B = Bs + buf * CP_B_STAGE;
-#pragma unroll
-    for (int uu = 0; uu < 2; ++uu)
-#pragma unroll
-      for (int j = 0; j < 2; ++j) *(V*)(B + uu * (BN * 64) + blds[j]) = rb[uu][j];
   };
 
   const int hpl = (2 * wave + (r >> 4)) * CP_HW + (r & 15);   // this lane's halo pixel of tap (0, 0)
@@ -626,71 +675,118 @@ __global__ __launch_bounds__(NTHREADS, 3) void cvd3_kernel(const CvdArgs g) {
 #pragma unroll
     for (int i = 0; i < 16; ++i) acc[t][i] = 0.f;
 
-  // flat walk: class -> channel group of 64 -> tap of the class (one stage of 2 chunks).  Stage s of the walk uses B buffer s & 1.
-  const int ngrp = UP2 ? 1 : sy.C / 64;   // (the head: one group, known to the compiler - the walk is then straight-line code)
-  int buf = 0;
+  // ---- the epilogue's operands: x and, when accumulating, the old gradient of this thread's 4 rows of a column half.  Every load is
+  // issued by every lane (a row or column outside the picture reads row 0 / column n0 and is not used): the number of requests
+  // behind the walk's last refill is then the same in every wave, and the walk's last barriers count them (below).
+  constexpr int NCV = 64 / SLOT, RPP = NTHREADS / NCV, NIT = BM / RPP;   // 8 slot columns x 32 row phases, 4 rows per thread
+  const int cv = tid % NCV, rr = tid / NCV;
+  const T* bx = (const T*)a.bx;
+  T* gout = (T*)a.out;
+  const bool accum = a.accumulate != 0;
+  V xpre[2][NIT], gpre[2][NIT];
+  auto issue_x = [&](int ch) {
+    const int n = n0 + 64 * ch + cv * SLOT;
+    const int nn = n < a.N ? n : n0;
+#pragma unroll
+    for (int i = 0; i < NIT; ++i) {
+      xpre[ch][i] = *(const V*)(bx + (size_t)max(rowpix[rr + RPP * i], 0) * a.ldbx + nn);
+    }
+  };
+  auto issue_g = [&](int ch) {
+    const int n = n0 + 64 * ch + cv * SLOT;
+    const int nn = n < a.N ? n : n0;
+#pragma unroll
+    for (int i = 0; i < NIT; ++i) {
+#pragma unroll
+      for (int e = 0; e < SLOT; ++e) gpre[ch][i][e] = (T)0;
+      if (accum) gpre[ch][i] = *(const V*)(gout + (size_t)max(rowpix[rr + RPP * i], 0) * a.ldo + nn);
+    }
+  };
+
+  // flat walk: class -> channel group of 64 -> tap of the class -> chunk.  Chunk c of the walk sits in ring slot c % C3D_RING; a step
+  // (C3D_STEP chunks) is: the counted barrier, the refill C3D_AHEAD steps ahead into the slots the barrier released, the MFMAs.
+  // The taps' halo offsets, class by class, in scalar registers before the walk: a 16-bit load is a vector-memory request, and the
+  // wait for one inside the walk drains the ring.  Tap k of class (pa, pb): row offset (dy + pa) / 2, likewise the column.
+  constexpr int NTAPS = UP2 ? 16 : 9;
+  int toff[NTAPS];
+#pragma unroll
+  for (int k = 0; k < NTAPS; ++k) {
+    const int kc = UP2 ? k >> 2 : (k < 1 ? 0 : k < 3 ? 1 : k < 5 ? 2 : 3);
+    const int tw = sy.taps[g.tapidx[k]];
+    const int dy = (int)(signed char)(tw & 0xff), dx = (int)(signed char)((tw >> 8) & 0xff);
+    toff[k] = __builtin_amdgcn_readfirstlane(((dy + (kc >> 1)) >> 1) * CP_HW + ((dx + (kc & 1)) >> 1));
+  }
+  int c_slot = 0;
   int first_tap = 0;
   unsigned ok_cur = 0;
   issue_halo(0, 0, 0, ok_cur);
-  issue_b(g.tapidx[0], 0);
+#pragma unroll
+  for (int i = 0; i < C3D_AHEAD * C3D_STEP; ++i) issue_w();
 #pragma unroll
   for (int cls = 0; cls < 4; ++cls) {
     const int pa = cls >> 1, pb = cls & 1;
     const int ntap = UP2 ? 4 : (pa + 1) * (pb + 1);
     for (int grp = 0; grp < ngrp; ++grp) {
-      store_halo(ok_cur);
-      // the next halo - next group of this class, or group 0 of the next class - flies under this group's stages
       const bool last_grp = grp + 1 == ngrp;
-      if (!(last_grp && cls == 3)) {
+      const bool final = cls == 3 && last_grp;   // the last group of the walk: the ring runs empty, the epilogue's operands are requested
+      if (!(CVD3_DBG & 2) || (cls == 0 && grp == 0)) store_halo(ok_cur);
+      // the next halo - next group of this class, or group 0 of the next class - flies under this group's steps
+      if (!final && !(CVD3_DBG & 2)) {
         const int ncls = last_grp ? cls + 1 : cls;
         issue_halo(ncls >> 1, ncls & 1, last_grp ? 0 : grp + 1, ok_cur);
       }
 #pragma unroll
       for (int tt = 0; tt < 4; ++tt) {
         if (tt < ntap) {
-          const int tap = g.tapidx[first_tap + tt];
-          const int tw = sy.taps[tap];
-          const int dy = (int)(signed char)(tw & 0xff), dx = (int)(signed char)((tw >> 8) & 0xff);
-          // halo pixel of the tap inside the class: row offset (dy + pa) / 2, likewise the column
-          const int hpt = hpl + ((dy + pa) >> 1) * CP_HW + ((dx + pb) >> 1);
+          const int hpt = hpl + toff[first_tap + tt];
           const unsigned char* A = Xs + hpt * 128;
           const int asw = (hpt >> 1) & 7;
-          store_b(buf);
-          __syncthreads();
-          // next stage's weights
-          if (tt + 1 < ntap) issue_b(g.tapidx[first_tap + tt + 1], grp);
-          else if (!last_grp) issue_b(g.tapidx[first_tap], grp + 1);
-          else if (cls < 3) issue_b(g.tapidx[first_tap + ntap], 0);
-          const unsigned char* B = Bs + buf * CP_B_STAGE;
 #pragma unroll
-          for (int uu = 0; uu < 2; ++uu)
+          for (int uu = 0; uu < 2; ++uu) {
+            if (uu % C3D_STEP == 0) {
+              // Steps of this group behind this one.  In flight across the barrier: the requests of the min(rem, AHEAD - 1) steps
+              // behind this one - the cursor stops at the end of the walk, so the final group's last steps have fewer - and, behind
+              // the last refill (rem < AHEAD of the final group), the epilogue's 4 or 8.  Requests the compiler counts itself (the
+              // halo) are younger than a step's weights only by being issued later: they can make this wait stricter, never laxer.
+              const int rem = (2 * ntap - 1 - (2 * tt + uu)) / C3D_STEP;
+              if (CVD3_DBG & 1) vm_lds_barrier<0>();
+              else if (final && rem < C3D_AHEAD) {
+                const int nw = (rem < C3D_AHEAD - 1 ? rem : C3D_AHEAD - 1) * C3D_STEP * C3D_PW;
+                vm_lds_barrier_n(nw + NIT);
+              } else vm_lds_barrier<C3D_WCUR>();
+              if (!(CVD3_DBG & 1)) {
+#pragma unroll
+                for (int i = 0; i < C3D_STEP; ++i) issue_w();
+              }
+              if (final && rem == C3D_AHEAD) issue_x(0);   // behind the walk's last refill
+            }
+            const unsigned char* B = Bs + ((CVD3_DBG & 1) ? uu % C3D_STEP : c_slot) * C3D_CHUNK;
+            c_slot = c_slot + 1 == C3D_RING ? 0 : c_slot + 1;
 #pragma unroll
             for (int s = 0; s < 2; ++s) {
               const V av = *(const V*)(A + (((uu * 4 + s * 2 + h) ^ asw) << 4));
 #pragma unroll
               for (int t = 0; t < NT; ++t) {
-                const V bv = *(const V*)(B + (uu * BN + 32 * t + r) * 64 + (((2 * s + h) ^ bsw) << 4));
+                const V bv = *(const V*)(B + (32 * t + r) * 64 + (((2 * s + h) ^ bsw) << 4));
                 acc[t] = mma16(av, bv, acc[t]);
               }
             }
-          buf ^= 1;
+          }
         }
       }
-      __syncthreads();  // every wave is done with this halo image
+      lds_barrier();  // every wave is done with this halo image (and, behind the final group, with the ring: its last barrier waited for every request)
     }
     first_tap += ntap;
   }
 
   // ---- epilogue in two column halves: fused BN+ReLU backward (see cvd_kernel / igemm.hip) ----
-  constexpr int NCV = 64 / SLOT, RPP = NTHREADS / NCV, NIT = BM / RPP;   // 8 slot columns x 32 row phases, 4 rows per thread
-  const int cv = tid % NCV, rr = tid / NCV;
+  if ((CVD3_DBG & 4) && acc[0][0] + acc[1][1] + acc[2][2] + acc[3][3] != 123.f) return;
+  issue_g(0);                         // the old gradient of the first half flies under the staging
   if (tid < 2 * 128) red[tid] = 0.0;  // (the K loop ended with a barrier: the images are dead)
   float* Cs = (float*)smem;  // fp32 staging: the ReLU mask and the reductions see the unrounded gradient
-  const T* bx = (const T*)a.bx;
-  T* gout = (T*)a.out;
 #pragma unroll
   for (int ch = 0; ch < 2; ++ch) {
-    if (ch) __syncthreads();  // the first half's staging has been read
+    if (ch) lds_barrier();  // the first half's staging has been read
 #pragma unroll
     for (int tt = 0; tt < 2; ++tt)
 #pragma unroll
@@ -698,7 +794,8 @@ __global__ __launch_bounds__(NTHREADS, 3) void cvd3_kernel(const CvdArgs g) {
         const int row = 32 * wave + (i & 3) + 8 * (i >> 2) + 4 * h;
         Cs[row * C3D_FP + 32 * tt + r] = acc[2 * ch + tt][i];
       }
-    __syncthreads();
+    lds_barrier();
+    if (ch == 0) issue_x(1);   // the second half's x flies under the first half's arithmetic
     const int n = n0 + 64 * ch + cv * SLOT;
     const bool colvalid = n < a.N;
     float s1[SLOT], s2[SLOT], sc[SLOT], sh[SLOT], mu[SLOT], is[SLOT];
@@ -713,11 +810,7 @@ __global__ __launch_bounds__(NTHREADS, 3) void cvd3_kernel(const CvdArgs g) {
       const int row = rr + RPP * i;
       const int pix = colvalid ? rowpix[row] : -1;
       if (pix < 0) continue;
-      const V xv = *(const V*)(bx + (size_t)pix * a.ldbx + n);
-      V gv;
-#pragma unroll
-      for (int e = 0; e < SLOT; ++e) gv[e] = (T)0;
-      if (a.accumulate) gv = *(const V*)(gout + (size_t)pix * a.ldo + n);
+      const V xv = xpre[ch][i], gv = gpre[ch][i];
       float av[SLOT], xf[SLOT], gf[SLOT];
 #pragma unroll
       for (int e = 0; e < SLOT; e += 4) {
@@ -735,9 +828,10 @@ __global__ __launch_bounds__(NTHREADS, 3) void cvd3_kernel(const CvdArgs g) {
       }
       *(V*)(gout + (size_t)pix * a.ldo + n) = f32_to_vec<T>(gf);
     }
+    if (ch == 0) issue_g(1);     // (its registers are the first half's: the old gradient of the second half flies under the staging)
     fold_to_lds<NCV, SLOT, 64>(s1, s2, red + ch * 128, cv, colvalid, lane);
   }
-  __syncthreads();
+  lds_barrier();
   if (tid < BN && n0 + tid < a.N) {
     const size_t rep = (size_t)(blockIdx.x & (STAT_REPS - 1)) * a.stat_stride;
     const double* rh = red + (tid >> 6) * 128;
