@@ -52,7 +52,13 @@ class AdamClass(C.Structure):
                 ("decoupled", C.c_int32), ("t0", C.c_int64)]
 
 
-assert C.sizeof(AdamSegment) == 24 and C.sizeof(AdamClass) == 32
+class AdamEma(C.Structure):
+    """dmm_adam_ema: the parameter average of the two `_ema` step calls; k_or_t0 is the update's k (plain) or the applied-step count
+    at which averaging began (guarded)."""
+    _fields_ = [("ema", C.c_void_p), ("decay", C.c_float), ("warmup", C.c_int32), ("k_or_t0", C.c_int64)]
+
+
+assert C.sizeof(AdamSegment) == 24 and C.sizeof(AdamClass) == 32 and C.sizeof(AdamEma) == 24
 
 
 class DmmError(RuntimeError):
@@ -132,6 +138,8 @@ def lib():
     L.dmm_adam_step_segmented.argtypes = [vp, vp, vp, vp, i64, vp, C.c_int, C.POINTER(AdamClass), C.c_int, i64, f32, vp]
     L.dmm_adam_step_guarded_segmented.argtypes = [vp, vp, vp, vp, i64, vp, C.c_int, C.POINTER(AdamClass), C.c_int, f32, f32, f32, i32,
                                                   vp, vp, vp]
+    L.dmm_adam_step_segmented_ema.argtypes = L.dmm_adam_step_segmented.argtypes + [C.POINTER(AdamEma)]
+    L.dmm_adam_step_guarded_segmented_ema.argtypes = L.dmm_adam_step_guarded_segmented.argtypes + [C.POINTER(AdamEma)]
     L.dmm_grad_sumsq.argtypes = [vp, i64, i64, C.c_int, vp, vp]
     L.dmm_plan_set_dynamic_loss_scale.argtypes = [vp, vp]
     L.dmm_plan_set_grad_accumulate.argtypes = [vp, C.c_int]
@@ -163,6 +171,7 @@ EXPORTS = [
     "dmm_grad_guard_scratch_bytes", "dmm_guard_state_init", "dmm_adam_step_guarded", "dmm_grad_sumsq", "dmm_plan_set_dynamic_loss_scale",
     "dmm_plan_set_grad_accumulate", "dmm_plan_set_encoder_frozen",
     "dmm_adam_table_bytes", "dmm_adam_table_init", "dmm_adam_step_segmented", "dmm_adam_step_guarded_segmented",
+    "dmm_adam_step_segmented_ema", "dmm_adam_step_guarded_segmented_ema",
     "dmm_plan_wgrad_batch_counts", "dmm_conv_wgrad_grouped", "dmm_bw1_reduce_grouped",
 ]
 

@@ -8,7 +8,10 @@ installed here); ``compute_dtype`` / data parallelism are new, and so is the gua
 clipping by global norm, a dynamic loss scale and a skipped step on overflow, dmmfods_amd/optim.py) and gradient accumulation
 (``config.optimizer.accumulate_steps``: one optimiser step per N batches, on the sum of their gradients) and a frozen-encoder
 phase (``config.optimizer.freeze_encoder_epochs``: decoder and head train alone for the first N epochs) and parameter groups for
-fine-tuning (``config.optimizer.encoder_lr_scale``, ``no_decay_norm_bias``, ``decoupled_weight_decay``: dmmfods_amd.optim.fine_tune_groups)."""
+fine-tuning (``config.optimizer.encoder_lr_scale``, ``no_decay_norm_bias``, ``decoupled_weight_decay``: dmmfods_amd.optim.fine_tune_groups)
+and a parameter average (``config.optimizer.ema_decay``, ``ema_warmup``: validation, and with it ``best_val_iou`` and the choice of the
+best checkpoint, runs on the exponential moving average of the parameters that the Adam launch keeps; it travels inside the
+checkpoint's optimiser entry)."""
 import logging
 import os
 import warnings
@@ -107,6 +110,11 @@ class Dense_U_Net_lidar_Agent:
             grouped = dict(param_groups=fine_tune_groups(self.model, o.learning_rate, o.weight_decay,
                                                          encoder_lr_scale=1.0 if els is None else float(els), no_decay_norm_bias=bool(ndnb)),
                            decoupled_weight_decay=bool(dwd))
+        # ema_decay (and ema_warmup, default True): the optimiser keeps an exponential moving average of the parameters and
+        # validate() runs on it.  Absent: the reference's loop, which validates the last iterate (A:165-213).
+        ema_decay, ema_warmup = self._optional(o, "ema_decay"), self._optional(o, "ema_warmup")
+        if ema_decay is not None:
+            grouped.update(ema_decay=float(ema_decay), ema_warmup=True if ema_warmup is None else bool(ema_warmup))
         self.optimizer = FusedAdam(self.model, lr=o.learning_rate, betas=(o.beta1, o.beta2), eps=o.eps,
                                    weight_decay=o.weight_decay, amsgrad=o.amsgrad, max_grad_norm=max_grad_norm,
                                    loss_scaler=loss_scaler, **grouped)
@@ -262,6 +270,16 @@ class Dense_U_Net_lidar_Agent:
                          ep["acc"].mean(0).tolist())
 
     def validate(self):
+        """With a parameter average (optimizer.ema_decay) the epoch's validation runs on the averaged parameters and the live
+        BatchNorm statistics; its val_history row carries ema: True."""
+        if self.optimizer.ema_arena is None:
+            return self._validate()
+        with self.optimizer.ema_weights():
+            avg_iou = self._validate()
+        self.val_history[-1]["ema"] = True
+        return avg_iou
+
+    def _validate(self):
         self.model.eval()
         n = self.data_loader.valid_iterations
         nc = self.config.model.num_classes

@@ -859,7 +859,7 @@ int dmm_grad_sumsq(const float* grads, int64_t offset, int64_t count, int accumu
   return DMM_OK;
 }
 
-// ------------------------------------------------------------------------------------------------ the Adam step: one kernel, four entry points
+// ------------------------------------------------------------------------------------------------ the Adam step: one kernel, four entry points (+ two that keep a parameter average)
 namespace {
 hipError_t upload(void* dst, const void* src, size_t bytes, hipStream_t st);   // (below: complete when it returns)
 // What dmm_adam_table_init uploaded to each table_dev: the step calls take a device pointer and cannot read the table back without
@@ -920,6 +920,7 @@ void adam_seg_args(AdamSegArgs& a, float* params, const float* grads, float* exp
   a.nsegs = table_dev ? nsegs : 1; a.nchunks = (int)adam_table_chunks(n); a.nclasses = nclasses;
   a.vec_ok = (((uintptr_t)params | (uintptr_t)grads | (uintptr_t)exp_avg | (uintptr_t)exp_avg_sq) & 15) == 0 ? 1 : 0;
   a.grad_scale = 0.f; a.state = nullptr;
+  a.ema = nullptr; a.ema_omd = 0.f; a.ema_decay = 0.f; a.ema_warmup = 0; a.ema_t0 = 0;
   for (int c = 0; c < ADAM_MAX_CLASSES; ++c) {
     AdamSegClass& k = a.cls[c];
     k = AdamSegClass{};
@@ -931,6 +932,42 @@ void adam_seg_args(AdamSegArgs& a, float* params, const float* grads, float* exp
     k.weight_decay = k.decoupled ? 0.f : s.weight_decay;
     k.decay = k.decoupled ? (float)(1.0 - (double)s.lr * (double)s.weight_decay) : 1.f;
   }
+}
+
+// The refusals of the parameter average, in front of those of the step itself (none needs the table).
+int adam_ema_check(const char* who, const dmm_adam_ema* ema, const float* params, const float* grads, const float* exp_avg,
+                   const float* exp_avg_sq, int64_t n, bool plain) {
+  const std::string w = std::string(who) + ": ";
+  if (!ema) return fail(DMM_ERR_INVALID, w + "ema is null");
+  if (!ema->ema) return fail(DMM_ERR_INVALID, w + "ema->ema is null");
+  if (((uintptr_t)ema->ema & 3) != 0) return fail(DMM_ERR_INVALID, w + "ema->ema is misaligned (4 bytes)");
+  const uintptr_t lo = (uintptr_t)ema->ema, bytes = n > 0 ? (uintptr_t)n * sizeof(float) : sizeof(float);
+  const std::pair<const char*, const float*> others[4] = {{"params", params}, {"grads", grads}, {"exp_avg", exp_avg}, {"exp_avg_sq", exp_avg_sq}};
+  for (const auto& o : others) {
+    const uintptr_t b = (uintptr_t)o.second;
+    if (o.second && lo < b + bytes && b < lo + bytes) return fail(DMM_ERR_INVALID, w + "ema->ema aliases " + o.first);
+  }
+  if (!(ema->decay >= 0.f && ema->decay < 1.f)) return fail(DMM_ERR_INVALID, w + "ema->decay must lie in [0, 1)");
+  if (plain && ema->k_or_t0 < 1) return fail(DMM_ERR_INVALID, w + "ema->k_or_t0 (the k of this update) must be >= 1");
+  return DMM_OK;
+}
+
+// d_k of averaging update k >= 1, in double (the guarded kernel's expression)
+double adam_ema_decay_at(const dmm_adam_ema& e, int64_t k) {
+  double d = (double)e.decay;
+  if (e.warmup) {
+    const double w = (1.0 + (double)k) / (10.0 + (double)k);
+    if (w < d) d = w;
+  }
+  return d;
+}
+
+void adam_ema_args(AdamSegArgs& a, const dmm_adam_ema& e, bool plain) {
+  a.ema = e.ema;
+  if (((uintptr_t)e.ema & 15) != 0) a.vec_ok = 0;
+  a.ema_decay = e.decay; a.ema_warmup = e.warmup != 0 ? 1 : 0;
+  if (plain) a.ema_omd = (float)(1.0 - adam_ema_decay_at(e, e.k_or_t0));
+  else a.ema_t0 = (long long)e.k_or_t0;
 }
 
 // Plain path: every class's step_size and bc2_sqrt at its own step count, step - t0, in double on the host.
@@ -1073,6 +1110,37 @@ int dmm_adam_step_guarded_segmented(float* params, const float* grads, float* ex
   AdamSegArgs a;
   adam_seg_args(a, params, grads, exp_avg, exp_avg_sq, n, table_dev, nsegs, classes, nclasses);
   HIPCHK(adam_launch_guarded(a, host.runs, max_norm, growth_factor, backoff_factor, growth_interval, state, scratch, (hipStream_t)stream));   // the norm over the segments only
+  return DMM_OK;
+}
+
+int dmm_adam_step_segmented_ema(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, int64_t n, const void* table_dev,
+                                int nsegs, const dmm_adam_class* classes, int nclasses, int64_t step, float grad_scale, void* stream,
+                                const dmm_adam_ema* ema) {
+  const char* who = "dmm_adam_step_segmented_ema";
+  if (int rc = adam_ema_check(who, ema, params, grads, exp_avg, exp_avg_sq, n, true)) return rc;
+  if (step < 1) return fail(DMM_ERR_INVALID, std::string(who) + ": step must be >= 1");
+  AdamTableHost host;
+  if (int rc = adam_seg_check(who, params, grads, exp_avg, exp_avg_sq, n, table_dev, nsegs, classes, nclasses, &host)) return rc;
+  AdamSegArgs a;
+  adam_seg_args(a, params, grads, exp_avg, exp_avg_sq, n, table_dev, nsegs, classes, nclasses);
+  adam_ema_args(a, *ema, true);
+  HIPCHK(adam_launch_plain(a, step, grad_scale, (hipStream_t)stream));
+  return DMM_OK;
+}
+
+int dmm_adam_step_guarded_segmented_ema(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, int64_t n,
+                                        const void* table_dev, int nsegs, const dmm_adam_class* classes, int nclasses, float max_norm,
+                                        float growth_factor, float backoff_factor, int32_t growth_interval, dmm_guard_state* state,
+                                        void* scratch, void* stream, const dmm_adam_ema* ema) {
+  const char* who = "dmm_adam_step_guarded_segmented_ema";
+  if (int rc = adam_ema_check(who, ema, params, grads, exp_avg, exp_avg_sq, n, false)) return rc;
+  if (int rc = guard_check(std::string(who) + ": ", grads, state, scratch, max_norm, growth_factor, backoff_factor, growth_interval)) return rc;
+  AdamTableHost host;
+  if (int rc = adam_seg_check(who, params, grads, exp_avg, exp_avg_sq, n, table_dev, nsegs, classes, nclasses, &host)) return rc;
+  AdamSegArgs a;
+  adam_seg_args(a, params, grads, exp_avg, exp_avg_sq, n, table_dev, nsegs, classes, nclasses);
+  adam_ema_args(a, *ema, false);
+  HIPCHK(adam_launch_guarded(a, host.runs, max_norm, growth_factor, backoff_factor, growth_interval, state, scratch, (hipStream_t)stream));
   return DMM_OK;
 }
 

@@ -6,6 +6,7 @@
 //   adam_segmented : THE Adam kernel (torch.optim.Adam semantics, amsgrad off; AdamW's decay per class).  It walks the arena under a
 //                    segment table - parameter groups and frozen gaps in one launch - or, without a table, one whole range; plain path
 //                    (scalars from the host) and guarded path (scalars from the state block; writes nothing on a skipped step)
+//                    and, asked to (AdamSegArgs::ema), keeps an exponential moving average of the parameters it writes
 //   guard_init     : fills a state block (start of training, checkpoint load)
 // No floating-point atomics anywhere: a workgroup owns its partial, the finalize kernel adds the partials in a fixed tree, so the
 // norm, the decision and the step are bit-reproducible from run to run (and equal on every rank of a data-parallel job, which reads
@@ -138,9 +139,27 @@ __device__ __forceinline__ void adam_seg_elem(float& p, float g, float& m_, floa
   p = fmaf(-c.step_size, m / denom, p);
 }
 
-__device__ __forceinline__ void adam_seg_vec(const AdamSegArgs& a, size_t i, const AdamSegClass& c, float grad_scale) {
+// The parameter average (AdamSegArgs::ema), for one element, contraction off as above.  p is the parameter this launch has just computed,
+// e the stored average, omd = (float)(1 - d_k) with the decay d_k of this update formed in double and rounded once:
+//   d  = p - e                                           one rounding
+//   e  = fma(omd, d, e)                                  one rounding (the ONE fused multiply-add)
+// It comes after p is final and reads nothing Adam writes later, so p, m and v have the bits of a launch without an average.
+__device__ __forceinline__ void ema_elem(float& e, float p, float omd) {
+#pragma clang fp contract(off)
+  const float d = p - e;
+  e = fmaf(omd, d, e);
+}
+
+// ema: the average's arena, or nullptr (uniform over the launch: off, or this update's k is below 1)
+__device__ __forceinline__ void adam_seg_vec(const AdamSegArgs& a, size_t i, const AdamSegClass& c, float grad_scale, float* ema, float omd) {
   f32x4 p = *(const f32x4*)(a.p + i), m = *(const f32x4*)(a.m + i), v = *(const f32x4*)(a.v + i);
   const f32x4 g = *(const f32x4*)(a.g + i);
+  // The average is fetched with the other four: behind the stores below the compiler may not move the load up (the arenas could alias
+  // for all it knows), and that second round trip to memory per chunk cost 16 us on C2's arena.  It is read and written once per
+  // step and by nothing else in between, hence the non-temporal hint on both accesses: measured, 165 -> 151 us on one chip against
+  // 118 us without an average - the 8 B/element at the rate of the other 28 (profiles/r11/ema_cost.txt).
+  f32x4 e = {0.f, 0.f, 0.f, 0.f};
+  if (ema != nullptr) e = __builtin_nontemporal_load((const f32x4*)(ema + i));
 #pragma unroll
   for (int k = 0; k < 4; ++k) {
     float pk = p[k], mk = m[k], vk = v[k];
@@ -150,6 +169,15 @@ __device__ __forceinline__ void adam_seg_vec(const AdamSegArgs& a, size_t i, con
   *(f32x4*)(a.m + i) = m;
   *(f32x4*)(a.v + i) = v;
   *(f32x4*)(a.p + i) = p;
+  if (ema != nullptr) {
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      float ek = e[k];
+      ema_elem(ek, p[k], omd);
+      e[k] = ek;
+    }
+    __builtin_nontemporal_store(e, (f32x4*)(ema + i));
+  }
 }
 
 // One launch for every parameter group.  Grid: min(chunks, ADAM_SEG_MAX_GRID) workgroups of 256 threads; a workgroup takes chunks
@@ -168,6 +196,10 @@ __device__ __forceinline__ void adam_seg_vec(const AdamSegArgs& a, size_t i, con
 // trainable at applied step t0 is at step t = applied_steps - t0 (guard_finalize has already advanced applied_steps for this step), and
 // thread c forms class c's step_size = (float)(lr / (1 - beta1^t)) and bc2_sqrt = (float)sqrt(1 - beta2^t) in double - guard_finalize's
 // expressions - once per workgroup; a class with t < 1 (a state block set back behind t0) writes nothing.
+// The parameter average (a.ema, else nullptr: no instruction below touches it): the average is written exactly where p is, by the
+// thread that holds the new p in registers - nowhere on a skipped step, in a gap, past n or for an inactive class.  Plain path: omd comes
+// with the launch.  Guarded path: update k = applied_steps - a.ema_t0; thread ADAM_MAX_CLASSES forms omd = (float)(1 - d_k) in double,
+// once per workgroup, next to the classes' scalars; k < 1 writes no average.
 // Every element is owned by one thread of one workgroup: no atomics, and the result does not depend on the grid.
 __device__ __forceinline__ AdamSegDev adam_seg_at(const AdamSegArgs& a, int s, long long n) {
   return a.segs != nullptr ? a.segs[s] : AdamSegDev{0, n, 0, 0};
@@ -175,6 +207,8 @@ __device__ __forceinline__ AdamSegDev adam_seg_at(const AdamSegArgs& a, int s, l
 
 __global__ __launch_bounds__(256) void adam_segmented_kernel(AdamSegArgs a) {
   __shared__ AdamSegClass cls[ADAM_MAX_CLASSES];
+  __shared__ float ema_omd_lds;
+  __shared__ int ema_on_lds;
   if (a.state != nullptr && a.state->found_inf) return;
   if (threadIdx.x == 0) {
 #pragma unroll
@@ -197,7 +231,23 @@ __global__ __launch_bounds__(256) void adam_segmented_kernel(AdamSegArgs a) {
         c.active = 1;
       }
     }
+    if (a.ema != nullptr && threadIdx.x == ADAM_MAX_CLASSES) {
+      const long long k = (long long)a.state->applied_steps - a.ema_t0;
+      double d = (double)a.ema_decay;
+      if (a.ema_warmup) {
+        const double w = (1.0 + (double)k) / (10.0 + (double)k);
+        if (w < d) d = w;
+      }
+      ema_omd_lds = (float)(1.0 - d);
+      ema_on_lds = k >= 1 ? 1 : 0;
+    }
     __syncthreads();
+  }
+  float* ema = a.ema;
+  float omd = a.ema_omd;
+  if (a.ema != nullptr && a.state != nullptr) {   // (uniform)
+    omd = ema_omd_lds;
+    if (!ema_on_lds) ema = nullptr;
   }
   const long long n = (long long)a.n;
   // (a 32-bit chunk counter keeps the loop's test on the scalar unit: nchunks < 2^31 and the grid is at most ADAM_SEG_MAX_GRID)
@@ -214,7 +264,7 @@ __global__ __launch_bounds__(256) void adam_segmented_kernel(AdamSegArgs a) {
     const long long base = c0 + 4 * (long long)threadIdx.x;
     if (a.vec_ok && sb <= c0 && c1 <= se && se <= n) {        // one segment covers the chunk
       const AdamSegClass& c = cls[sc & (ADAM_MAX_CLASSES - 1)];
-      if (c.active) adam_seg_vec(a, (size_t)base, c, grad_scale);
+      if (c.active) adam_seg_vec(a, (size_t)base, c, grad_scale, ema, omd);
       continue;
     }
     while (s < a.nsegs && adam_seg_at(a, s, n).end <= base) ++s;
@@ -223,7 +273,7 @@ __global__ __launch_bounds__(256) void adam_segmented_kernel(AdamSegArgs a) {
       const AdamSegDev t = adam_seg_at(a, s, n);
       if (a.vec_ok && t.begin <= base && base + 4 <= t.end && t.end <= n) {
         const AdamSegClass& c = cls[t.cls & (ADAM_MAX_CLASSES - 1)];
-        if (c.active) adam_seg_vec(a, (size_t)base, c, grad_scale);
+        if (c.active) adam_seg_vec(a, (size_t)base, c, grad_scale, ema, omd);
         continue;
       }
     }
@@ -241,6 +291,11 @@ __global__ __launch_bounds__(256) void adam_segmented_kernel(AdamSegArgs a) {
       a.m[i] = m;
       a.v[i] = v;
       a.p[i] = p;
+      if (ema != nullptr) {
+        float e = ema[i];
+        ema_elem(e, p, omd);
+        ema[i] = e;
+      }
     }
   }
 }

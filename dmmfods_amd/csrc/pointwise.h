@@ -156,10 +156,16 @@ struct AdamSegArgs {
                             // class 0 (nsegs = 1, first is not read)
   const int* first;         // nchunks: index of the first segment whose end lies behind the chunk's first element (nsegs: none)
   int nsegs, nchunks, nclasses;
-  int vec_ok;               // the four arenas are 16-byte aligned
+  int vec_ok;               // the four arenas (and ema, when it is on) are 16-byte aligned
   float grad_scale;         // plain path
   const dmm_guard_state* state;   // guarded path (else nullptr): found_inf, grad_scale, applied_steps
   AdamSegClass cls[ADAM_MAX_CLASSES];
+  // Parameter average (guard.hip, ema_elem): e += omd * (p - e) wherever this launch writes p.  nullptr: off.
+  float* ema;
+  float ema_omd;            // plain path: (float)(1 - d_k), formed on the host from the caller's k
+  float ema_decay;          // guarded path: the kernel forms omd itself, from k = state->applied_steps - ema_t0 (k < 1: no average is
+  int ema_warmup;           //   written), d_k = ema_warmup ? min(ema_decay, (1 + k) / (10 + k)) : ema_decay, in double
+  long long ema_t0;
 };
 struct GuardFinalizeArgs {
   const double* partials;

@@ -19,15 +19,27 @@ rate than the decoder, no weight decay on BatchNorm weights and biases - ``fine_
 segmented kernel (dmm_adam_step_segmented / dmm_adam_step_guarded_segmented) under a device table of (begin, count, class)
 segments; a class is a (group, step origin) pair and carries its hyper-parameters with every call.  An optimiser without
 either keyword is an optimiser with one group: while nothing is or was frozen its step is the whole-arena call (dmm_adam_step /
-dmm_adam_step_guarded: the same kernel without a table), with a frozen or released encoder it is the same one launch under a table."""
+dmm_adam_step_guarded: the same kernel without a table), with a frozen or released encoder it is the same one launch under a table.
+
+Parameter average (``FusedAdam(model, ema_decay=0.999)``; the reference has none and picks its best checkpoint on the raw iterate,
+A:165-213): an exponential moving average of the trainable parameters, kept by the SAME Adam launch (dmm_adam_step_segmented_ema /
+dmm_adam_step_guarded_segmented_ema) from the new parameter each thread holds in registers: e += (1 - d_k) (p - e) wherever the step
+wrote p - not on a skipped step, not in a frozen range (there e == p holds, and a released range simply joins).  d_k = decay, or with
+``ema_warmup`` (the default) min(decay, (1 + k) / (10 + k)) at the k-th averaging update (TF's ExponentialMovingAverage with
+num_updates).  ``ema_arena`` holds it, ``with opt.ema_weights():`` runs the model on it, ``ema_state_dict()`` exports it.  The BatchNorm
+running statistics and num_batches_tracked are NOT averaged: the live ones are used (TF's ema.apply(trainable_variables) convention)."""
+import collections
+import contextlib
 import ctypes as C
 import math
+import numbers
 
 import torch
 
 from . import _lib
 
 _STATE_KEY = "loss_scaler"   # the one extra top-level key of FusedAdam.state_dict() on the guarded path
+_EMA_KEY = "ema"             # and the one of an optimiser that keeps a parameter average
 
 
 class DynamicLossScaler:
@@ -177,13 +189,22 @@ class DynamicLossScaler:
 
 class FusedAdam:
     def __init__(self, model, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, amsgrad=False, max_grad_norm=None,
-                 loss_scaler=None, param_groups=None, decoupled_weight_decay=False):
+                 loss_scaler=None, param_groups=None, decoupled_weight_decay=False, ema_decay=None, ema_warmup=True):
+        """ema_decay: None (no average: nothing of it exists and state_dict() has no "ema" key) or a number in [0, 1).  It is held as
+        the fp32 value the C ABI carries, so that ema_decay_at() is what the kernel uses.  ema_warmup: see ema_decay_at()."""
         if amsgrad:
             raise ValueError("amsgrad=True is not supported (reference default False, H:156)")
         if max_grad_norm is not None and not (float(max_grad_norm) > 0 and math.isfinite(float(max_grad_norm))):
             raise ValueError("max_grad_norm must be a finite number > 0 (None: no clipping)")
         if loss_scaler is not None and not isinstance(loss_scaler, DynamicLossScaler):
             raise ValueError("loss_scaler must be a DynamicLossScaler")
+        if ema_decay is not None:
+            if not isinstance(ema_decay, numbers.Real) or isinstance(ema_decay, bool):
+                raise ValueError("ema_decay must be None or a number in [0, 1)")
+            ema_decay = C.c_float(float(ema_decay)).value
+            if not 0.0 <= ema_decay < 1.0:   # (NaN fails both)
+                raise ValueError("ema_decay must lie in [0, 1) (as an fp32 value)")
+        self.ema_decay, self.ema_warmup = ema_decay, bool(ema_warmup)
         self.model = model
         self.defaults = dict(lr=lr, betas=tuple(betas), eps=eps, weight_decay=weight_decay, amsgrad=False)
         self._params = list(model.parameters())
@@ -215,6 +236,13 @@ class FusedAdam:
         self._model_sig = None   # the model's own record of the flags (an object replaced on every change) when _ranges was built
         # [begin, count, class] over the arena, the (group, t0) of every class, and the device table built from them
         self._segments = self._classes = self._table = None
+        # The parameter average: plain path - _ema_k averaging updates so far, counted here; guarded path - only the applied-step
+        # count at which averaging began (_ema_t0): the device knows which steps were applied.
+        self.ema_arena = None
+        self._ema_k = self._ema_t0 = 0
+        self._ema_swapped = False
+        if self.ema_decay is not None:
+            self.ema_reset()
 
     _GROUP_KEYS = ("lr", "betas", "eps", "weight_decay", "decoupled_weight_decay")
 
@@ -407,19 +435,104 @@ class FusedAdam:
         if getattr(self.model, "grad_accumulation", False):
             self.model.grad_arena.zero_()
 
+    # ---- the parameter average ----
+    def _ema_need(self):
+        if self.ema_arena is None:
+            raise RuntimeError("this optimiser keeps no parameter average (ema_decay=None)")
+
+    def _ema_follow(self):
+        if self.ema_arena.device != self.model.param_arena.device:
+            self.ema_arena = self.ema_arena.to(self.model.param_arena.device)
+
+    @torch.no_grad()
+    def ema_reset(self):
+        """The average starts again: a copy of the parameters as they are now, and the next step is averaging update 1.  (On the
+        guarded path this reads the applied-step count, i.e. waits for the device.)"""
+        if self.ema_decay is None:
+            raise RuntimeError("this optimiser keeps no parameter average (ema_decay=None)")
+        if self._ema_swapped:
+            raise RuntimeError("ema_reset() inside ema_weights(): the parameter arena holds the average")
+        self.ema_arena = self.model.param_arena.detach().clone()
+        self._ema_k = 0
+        self._ema_t0 = self.step_count if self._guard is not None else 0
+
+    @property
+    def ema_num_updates(self):
+        """Averaging updates so far.  On the guarded path the count of applied steps lives on the device: reading this waits for
+        the GPU, as step_count does."""
+        self._ema_need()
+        return max(0, self.step_count - self._ema_t0) if self._guard is not None else self._ema_k
+
+    def ema_decay_at(self, k):
+        """d_k of averaging update k >= 1, in double: ema_decay, or with ema_warmup min(ema_decay, (1 + k) / (10 + k)).  The kernel
+        multiplies (p - e) by (float)(1 - d_k)."""
+        self._ema_need()
+        k = int(k)
+        if k < 1:
+            raise ValueError("k must be >= 1")
+        return min(self.ema_decay, (1.0 + k) / (10.0 + k)) if self.ema_warmup else self.ema_decay
+
+    @torch.no_grad()
+    def _ema_exchange(self):
+        """Exchanges the CONTENTS of the parameter arena and the average (the plans are bound to the arena's address), in stream
+        order, through one scratch tensor."""
+        p, e = self.model.param_arena, self.ema_arena
+        tmp = p.detach().clone()
+        p.copy_(e)
+        e.copy_(tmp)
+        del tmp
+
+    @contextlib.contextmanager
+    def ema_weights(self):
+        """Inside the block the model runs on the averaged parameters (with the live BatchNorm statistics): validation, export.
+        Every forward packs its weights from the arena anew, so nothing derived goes stale.  A training forward taken on the other
+        weights cannot be continued: loss_backward() right behind entry or exit raises.  step(), load_state_dict(), ema_reset() and a
+        nested entry raise RuntimeError inside the block; the arenas are exchanged back also when the body raises."""
+        self._ema_need()
+        if self._ema_swapped:
+            raise RuntimeError("ema_weights() is already active")
+        self._ema_follow()
+        self._ema_exchange()
+        self._ema_swapped = True
+        self.model._last = None
+        try:
+            yield self
+        finally:
+            self._ema_exchange()
+            self._ema_swapped = False
+            self.model._last = None
+
+    def ema_state_dict(self):
+        """The model's state_dict (the reference's layout: keys, order, shapes) with the averaged parameters - clones - and the live
+        buffers: the BatchNorm running statistics and num_batches_tracked are not averaged."""
+        self._ema_need()
+        if self._ema_swapped:
+            raise RuntimeError("ema_state_dict() inside ema_weights(): model.state_dict() is the averaged one there")
+        self._ema_follow()
+        avg, off = {}, 0
+        for name, p in self.model.named_parameters():
+            n = p.numel()
+            avg[name] = self.ema_arena[off:off + n].view(p.shape).clone()
+            off += n
+        return collections.OrderedDict((k, avg[k] if k in avg else v.detach().clone()) for k, v in self.model.state_dict().items())
+
     @torch.no_grad()
     def step(self, grad_scale=1.0):
         m = self.model
+        if self._ema_swapped:
+            raise RuntimeError("step() inside ema_weights(): the parameter arena holds the average")
         if self.exp_avg.device != m.param_arena.device:
             self.exp_avg = self.exp_avg.to(m.param_arena.device)
             self.exp_avg_sq = self.exp_avg_sq.to(m.param_arena.device)
+        if self.ema_arena is not None:
+            self._ema_follow()
         gd, L = self._guard, _lib.lib()
         if gd is not None and grad_scale != 1.0:
             raise ValueError("grad_scale is not available on the guarded path (the loss scaler divides its scale out itself)")
         n = m.param_arena.numel()
         self._sync_trainable(look=False)
         arenas = (m.param_arena.data_ptr(), m.grad_arena.data_ptr(), self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(), n)
-        whole = not self._grouped and self._ranges == [[0, n, 0]]
+        whole = self.ema_arena is None and not self._grouped and self._ranges == [[0, n, 0]]   # (the average always takes the table)
         if whole:
             # Whole arena: no groups, nothing is or ever was frozen - one class, no table.
             g = self.param_groups[0]
@@ -430,6 +543,11 @@ class FusedAdam:
             arenas += (self._ensure_table().data_ptr(), len(self._segments), classes, len(classes))
         if gd is None:
             self.step_count += 1
+            if self.ema_arena is not None:
+                ema = _lib.AdamEma(self.ema_arena.data_ptr(), self.ema_decay, int(self.ema_warmup), self._ema_k + 1)
+                _lib.check(L.dmm_adam_step_segmented_ema(*arenas, self.step_count, float(grad_scale), _lib.stream_ptr(), C.byref(ema)))
+                self._ema_k += 1
+                return
             step = L.dmm_adam_step if whole else L.dmm_adam_step_segmented
             _lib.check(step(*arenas, self.step_count, float(grad_scale), _lib.stream_ptr()))
             return
@@ -437,9 +555,14 @@ class FusedAdam:
         # GradAllReduce.wait(works): every rank then reads the same summed arena and takes the same decision.
         state = gd._materialize(m.param_arena.device)
         scratch = gd._scratch_for(n)
+        tail = (float(self.max_grad_norm or 0.0), gd.growth_factor, gd.backoff_factor, gd.growth_interval, state.data_ptr(), scratch.data_ptr(),
+                _lib.stream_ptr())
+        if self.ema_arena is not None:   # the device forms k = applied_steps - _ema_t0: a skipped step is no averaging update
+            ema = _lib.AdamEma(self.ema_arena.data_ptr(), self.ema_decay, int(self.ema_warmup), self._ema_t0)
+            _lib.check(L.dmm_adam_step_guarded_segmented_ema(*arenas, *tail, C.byref(ema)))
+            return
         step = L.dmm_adam_step_guarded if whole else L.dmm_adam_step_guarded_segmented
-        _lib.check(step(*arenas, float(self.max_grad_norm or 0.0), gd.growth_factor, gd.backoff_factor, gd.growth_interval,
-                        state.data_ptr(), scratch.data_ptr(), _lib.stream_ptr()))
+        _lib.check(step(*arenas, *tail))
 
     # ---- torch.optim.Adam-compatible checkpoint format ----
     def state_dict(self):
@@ -462,9 +585,16 @@ class FusedAdam:
         sd = {"state": dict(sorted(state.items())), "param_groups": groups}
         if self._guard is not None:   # torch.optim.Adam.load_state_dict ignores a key it does not know
             sd[_STATE_KEY] = self._guard.state_dict()
+        if self.ema_arena is not None:   # (likewise; absent without an average: the key set is then what it always was)
+            if self._ema_swapped:
+                raise RuntimeError("state_dict() inside ema_weights(): the parameter arena holds the average")
+            sd[_EMA_KEY] = {"decay": self.ema_decay, "warmup": self.ema_warmup, "num_updates": self.ema_num_updates,
+                            "params": self.ema_arena.detach().cpu().clone()}
         return sd
 
     def load_state_dict(self, sd):
+        if self._ema_swapped:
+            raise RuntimeError("load_state_dict() inside ema_weights(): the parameter arena holds the average")
         off = 0
         if self._grouped:   # torch's own check: the same groups, each of the same size
             theirs = sd["param_groups"]
@@ -494,6 +624,20 @@ class FusedAdam:
                     mine[k] = tuple(theirs[k]) if k == "betas" and self._grouped else theirs[k]
         if self._guard is not None and sd.get(_STATE_KEY) is not None:   # (a checkpoint of the plain path has none: the scaler keeps its state)
             self._guard.load_state_dict(sd[_STATE_KEY])
+        # The average: from its key; a checkpoint written without one starts it at the parameters as loaded (the model's state is
+        # loaded before the optimiser's).  Decay and warm-up stay the constructor's.  Without an average the key is ignored.
+        if self.ema_arena is not None:
+            saved = sd.get(_EMA_KEY)
+            if saved is None:
+                self.ema_reset()
+            else:
+                params = saved["params"].reshape(-1)
+                if params.numel() != self.ema_arena.numel():
+                    raise ValueError(f"loaded parameter average has {params.numel()} elements, the arena has {self.ema_arena.numel()}")
+                with torch.no_grad():
+                    self.ema_arena.copy_(params)
+                self._ema_k = int(saved["num_updates"])
+                self._ema_t0 = count - self._ema_k if self._guard is not None else 0
 
 
 def fine_tune_groups(model, lr, weight_decay, encoder_lr_scale=1.0, no_decay_norm_bias=False):

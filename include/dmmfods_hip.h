@@ -17,6 +17,9 @@
  *                                          torch.optim.Adam built over PARAMETER GROUPS (the list-of-dicts form of the constructor
  *                                          called at agents/Dense_U_Net_lidar_Agent.py:57-61) and stepped at :265; the guarded form
  *                                          adds the rule of dmm_adam_step_guarded, which has nothing upstream
+ *   dmm_adam_step_segmented_ema / dmm_adam_step_guarded_segmented_ema
+ *                                          nothing upstream (the reference validates and saves the last iterate, :165-213): the
+ *                                          segmented steps, keeping an exponential moving average of the parameters in the same launch
  *   dmm_adam_step_guarded / dmm_guard_* .. nothing upstream (the reference trains in fp32 with a bare Adam, :263-265); the rule is
  *                                          torch.amp.GradScaler's and the clip formula torch.nn.utils.clip_grad_norm_'s
  *   dmm_conv_forward / dmm_conv_wgrad .... single-kernel entry points for unit tests (torch.nn.functional.conv2d,
@@ -310,6 +313,32 @@ int dmm_adam_step_guarded_segmented(float* params, const float* grads, float* ex
                                     const void* table_dev, int nsegs, const dmm_adam_class* classes, int nclasses, float max_norm,
                                     float growth_factor, float backoff_factor, int32_t growth_interval, dmm_guard_state* state,
                                     void* scratch, void* stream);
+/* ---- parameter average (EMA), kept by the Adam launch ----
+ * The two calls below are dmm_adam_step_segmented / dmm_adam_step_guarded_segmented with one more arena, `ema` (n fp32 elements):
+ * wherever the launch writes a parameter p it also writes, from the p it holds in registers,
+ *     e = fma(omd, p - e, e),   omd = (float)(1 - d_k)      (fp32; the difference and the fma round once each)
+ * with d_k = decay, or with warmup != 0 d_k = min(decay, (1 + k) / (10 + k)), formed in double; k >= 1 numbers this averaging update.
+ * Elements the launch does not write - in no segment, of a class whose own step is below 1, everything on a skipped step - keep
+ * their average bit for bit.  p, exp_avg and exp_avg_sq come out bit-equal to the call without an average.  A whole arena is the
+ * one-segment table [0, n) of class 0.
+ * k_or_t0: plain call: the k of this update (the caller counts).  Guarded call: the applied-step count at which averaging began;
+ * the kernel forms k = state->applied_steps - k_or_t0 (after this step's finalize) and omd itself, and writes no average while k < 1.
+ * Both refuse, before any HIP call, what their counterparts refuse, and: a null `ema` struct, a null or misaligned (4 bytes)
+ * ema->ema, an ema->ema whose n elements overlap params, grads, exp_avg or exp_avg_sq, a decay outside [0, 1) or NaN, and the
+ * plain call k < 1. */
+typedef struct dmm_adam_ema {
+  float* ema;         /*  0: the average, n elements (device) */
+  float decay;        /*  8 */
+  int32_t warmup;     /* 12 */
+  int64_t k_or_t0;    /* 16 */
+} dmm_adam_ema;       /* 24 bytes */
+int dmm_adam_step_segmented_ema(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, int64_t n, const void* table_dev,
+                                int nsegs, const dmm_adam_class* classes, int nclasses, int64_t step, float grad_scale, void* stream,
+                                const dmm_adam_ema* ema);
+int dmm_adam_step_guarded_segmented_ema(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, int64_t n,
+                                        const void* table_dev, int nsegs, const dmm_adam_class* classes, int nclasses, float max_norm,
+                                        float growth_factor, float backoff_factor, int32_t growth_interval, dmm_guard_state* state,
+                                        void* scratch, void* stream, const dmm_adam_ema* ema);
 /* Points the plan's loss kernel and the external-gradient conversion of dmm_plan_backward at a device float (&state->scale):
  * d(loss)/d(logit) is multiplied by loss_scale * (*scale_dev), read on the device when the kernel runs.  NULL = off: the code path
  * and the numbers of a plan that never had one.  Loss sums, metric counts and the unreduced outputs stay unscaled.  Both kernels

@@ -42,6 +42,9 @@
 // DRIVE_FREEZE=1 (life-cycle run and dump): the plan is built with a frozen encoder (dmm_plan_set_encoder_frozen on the unbound plan; a
 // null plan and the bound plan must be refused); the life-cycle run also takes the guarded step over two trainable ranges, one of
 // them released late (dmm_adam_step_guarded_segmented, a class with t0 > 0), and checks that no bucket and no unpack descriptor touches an encoder tensor.
+// DRIVE_EMA=1 (with DRIVE_FREEZE=1): behind each of those steps the two steps that keep a parameter average (dmm_adam_step_segmented_ema,
+// dmm_adam_step_guarded_segmented_ema) run under the same table - a gap in front, then a class with t0 > 0 - and each of their own
+// refusals is tried on both: a null struct, a null average, one that is or overlaps an arena, a decay of 1, below 0, above 1 and NaN, k < 1.
 // Launch coalescing (dmm_set_option("batch_wgrad"), on by default; DRIVE_OPTIONS_OFF=batch_wgrad runs one launch per record,
 // DRIVE_BATCH_WGRAD=<0|1|2> sets the option's value: 2 = grouped on the weight-gradient stream instead of the caller's): every
 // life-cycle run watches the enqueue calls through the fake runtime's hook and checks, with the option on or off, that
@@ -347,6 +350,52 @@ static int one_life(const dmm_model_desc& d, int life) {
       MUST(dmm_adam_step_guarded_segmented(params, grads, mom1, mom2, np, table, ns, origins, ns, 1.0f, 2.f, 0.5f, 2000, gstate, gscratch, st));
       const dmm_adam_segment bad[2] = {{0, enc_hi, 1}, {enc_hi - 1, np - enc_hi, 0}};
       if (dmm_adam_table_init(table, bad, 2, np, 2, st) != DMM_ERR_INVALID) { fprintf(stderr, "[drive] overlapping ranges were not refused\n"); return 2; }
+      if (getenv("DRIVE_EMA")) {   // the two steps that keep a parameter average, on the table `bad` did not replace, then every refusal of theirs
+        float* avg = (float*)malloc(np * 4);
+        dmm_adam_ema e = {avg, 0.999f, 1, 1};
+        MUST(dmm_adam_step_segmented_ema(params, grads, mom1, mom2, np, table, ns, origins, ns, 2, 1.f, st, &e));
+        e.k_or_t0 = 0;           // guarded: the applied-step count at which averaging began
+        MUST(dmm_adam_step_guarded_segmented_ema(params, grads, mom1, mom2, np, table, ns, origins, ns, 1.0f, 2.f, 0.5f, 2000, gstate, gscratch, st, &e));
+        e.warmup = 0;
+        MUST(dmm_adam_step_guarded_segmented_ema(params, grads, mom1, mom2, np, table, ns, origins, ns, 1.0f, 2.f, 0.5f, 2000, gstate, gscratch, st, &e));
+        // (refused by both calls, with a message that names the argument)
+        auto both_refuse = [&](const dmm_adam_ema* bad_ema, const char* what, const char* names) {
+          const int a = dmm_adam_step_segmented_ema(params, grads, mom1, mom2, np, table, ns, origins, ns, 2, 1.f, st, bad_ema);
+          const bool an = strstr(dmm_last_error(), names) != nullptr;
+          const int b = dmm_adam_step_guarded_segmented_ema(params, grads, mom1, mom2, np, table, ns, origins, ns, 1.0f, 2.f, 0.5f, 2000, gstate, gscratch, st, bad_ema);
+          const bool bn = strstr(dmm_last_error(), names) != nullptr;
+          if (a == DMM_ERR_INVALID && b == DMM_ERR_INVALID && an && bn) return true;
+          fprintf(stderr, "[drive] %s was not refused (%d, %d) or the message does not say '%s': %s\n", what, a, b, names, dmm_last_error());
+          return false;
+        };
+        const dmm_adam_ema good = {avg, 0.999f, 1, 1};
+        dmm_adam_ema b = good;
+        if (!both_refuse(nullptr, "a null dmm_adam_ema", "ema is null")) return 2;
+        b.ema = nullptr;
+        if (!both_refuse(&b, "a null average", "ema->ema is null")) return 2;
+        float* const arenas[4] = {params, grads, mom1, mom2};
+        for (float* a : arenas) {
+          b.ema = a;
+          if (!both_refuse(&b, "an average that is one of the arenas", "ema->ema aliases")) return 2;
+          b.ema = a + np - 1;
+          if (!both_refuse(&b, "an average that overlaps an arena's end", "ema->ema aliases")) return 2;
+        }
+        b = good;
+        const float decays[4] = {1.f, -0.1f, 1.5f, __builtin_nanf("")};
+        for (float dk : decays) {
+          b.decay = dk;
+          if (!both_refuse(&b, "a decay outside [0, 1)", "ema->decay")) return 2;
+        }
+        b = good; b.k_or_t0 = 0;
+        if (dmm_adam_step_segmented_ema(params, grads, mom1, mom2, np, table, ns, origins, ns, 2, 1.f, st, &b) != DMM_ERR_INVALID) { fprintf(stderr, "[drive] k = 0 was not refused\n"); return 2; }
+        // ... and what the counterparts refuse: step 0, another nsegs, growth_factor < 1
+        if (dmm_adam_step_segmented_ema(params, grads, mom1, mom2, np, table, ns, origins, ns, 0, 1.f, st, &good) != DMM_ERR_INVALID ||
+            dmm_adam_step_segmented_ema(params, grads, mom1, mom2, np, table, ns + 1, origins, ns, 2, 1.f, st, &good) != DMM_ERR_INVALID ||
+            dmm_adam_step_guarded_segmented_ema(params, grads, mom1, mom2, np, table, ns, origins, ns, 1.0f, 0.5f, 0.5f, 2000, gstate, gscratch, st, &good) != DMM_ERR_INVALID) {
+          fprintf(stderr, "[drive] a refusal of the step without an average is missing from the one with it\n"); return 2;
+        }
+        free(avg);
+      }
       free(table);
     } else if (dyn) {
       MUST(dmm_adam_step_guarded(params, grads, mom1, mom2, np, 1e-3f, 0.9f, 0.999f, 1e-8f, 0.f, 1.0f, 2.f, 0.5f, 2000, gstate, gscratch, st));
