@@ -115,6 +115,9 @@ def lib():
     L.dmm_plan_loss_metrics.argtypes = [vp, vp, vp, vp, vp]
     L.dmm_plan_set_loss.argtypes = [vp, C.c_int, vp, vp, C.c_int]
     L.dmm_loss_forward.argtypes = [C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp]
+    L.dmm_logit_hist_elems.argtypes = [C.c_int, C.c_int, C.c_int]
+    L.dmm_logit_hist_elems.restype = sz
+    L.dmm_logit_hist.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int, f32, C.c_int, vp, vp]
     L.dmm_plan_num_grad_buckets.argtypes = [vp]
     L.dmm_plan_num_graph_replays.argtypes = [vp, C.c_int]
     L.dmm_plan_num_graph_replays.restype = C.c_longlong
@@ -173,7 +176,9 @@ EXPORTS = [
     "dmm_adam_table_bytes", "dmm_adam_table_init", "dmm_adam_step_segmented", "dmm_adam_step_guarded_segmented",
     "dmm_adam_step_segmented_ema", "dmm_adam_step_guarded_segmented_ema",
     "dmm_plan_wgrad_batch_counts", "dmm_conv_wgrad_grouped", "dmm_bw1_reduce_grouped",
+    "dmm_logit_hist_elems", "dmm_logit_hist",
 ]
+HIST_MAX_THRESHOLDS = 255   # DMM_HIST_MAX_THRESHOLDS
 
 
 def check(rc):

@@ -11,17 +11,21 @@ phase (``config.optimizer.freeze_encoder_epochs``: decoder and head train alone 
 fine-tuning (``config.optimizer.encoder_lr_scale``, ``no_decay_norm_bias``, ``decoupled_weight_decay``: dmmfods_amd.optim.fine_tune_groups)
 and a parameter average (``config.optimizer.ema_decay``, ``ema_warmup``: validation, and with it ``best_val_iou`` and the choice of the
 best checkpoint, runs on the exponential moving average of the parameters that the Adam launch keeps; it travels inside the
-checkpoint's optimiser entry)."""
+checkpoint's optimiser entry) and a validation threshold sweep (``config.agent.threshold_sweep``: one more launch per validation batch
+takes per-class logit histograms, and the epoch's ``val_history`` row carries IoU, precision, recall, F1, accuracy and average precision
+at every threshold; ``best_val_iou`` and the checkpoints do not depend on it)."""
 import logging
 import os
 import warnings
 from datetime import datetime
 from pathlib import Path
 
+import numpy as np
 import torch
 
 from ..datasets.WaymoData import WaymoDataset_Loader
 from ..graphs.models.Dense_U_Net_lidar import densenet121_u_lidar
+from ..metrics import ThresholdSweep, logit_thresholds
 from ..optim import DynamicLossScaler, FusedAdam, fine_tune_groups
 from ..utils import Dense_U_Net_lidar_helper as utils
 
@@ -118,6 +122,9 @@ class Dense_U_Net_lidar_Agent:
         self.optimizer = FusedAdam(self.model, lr=o.learning_rate, betas=(o.beta1, o.beta2), eps=o.eps,
                                    weight_decay=o.weight_decay, amsgrad=o.amsgrad, max_grad_norm=max_grad_norm,
                                    loss_scaler=loss_scaler, **grouped)
+        # agent.threshold_sweep: validation also takes per-class logit histograms (dmmfods_amd.metrics.ThresholdSweep) and its
+        # val_history row carries every thresholded metric at every threshold.  Absent: the reference's loop, not one call more.
+        self.sweep, self.sweep_column = self._make_sweep(self._optional(self.config.agent, "threshold_sweep"))
         self.lr_scheduler = None
         if o.lr_scheduler.want:
             self.lr_scheduler = _StepLR(self.optimizer, o.lr_scheduler.every_n_epochs, o.lr_scheduler.gamma)
@@ -143,6 +150,27 @@ class Dense_U_Net_lidar_Agent:
             want = self.current_epoch < self.freeze_encoder_epochs
             if self.model.encoder_frozen != want:
                 self.model.freeze_encoder(want)
+
+    def _make_sweep(self, spec):
+        """spec: None (no sweep), an integer K (the probabilities (k + 1) / (K + 1), k = 0 .. K - 1, as logits) or a list of logit
+        thresholds.  iou_threshold is always merged in, so that the configured operating point is one of the columns; ground truth is
+        cut at iou_threshold, as the loss kernel cuts it.  Returns (sweep, column of iou_threshold)."""
+        if spec is None:
+            return None, None
+        if isinstance(spec, bool):
+            raise ValueError("agent.threshold_sweep must be an integer K >= 1 or a list of logit thresholds")
+        if isinstance(spec, int):
+            if spec < 1:
+                raise ValueError("agent.threshold_sweep must be an integer K >= 1 or a list of logit thresholds")
+            thr = logit_thresholds([(k + 1) / (spec + 1) for k in range(spec)])
+        else:
+            thr = np.asarray([float(v) for v in spec], dtype=np.float64).astype(np.float32)
+            if thr.size < 1 or not np.isfinite(thr).all() or not (np.diff(thr) > 0).all():
+                raise ValueError("agent.threshold_sweep: a list of finite, strictly ascending logit thresholds")
+        op = np.float32(self.config.agent.iou_threshold)
+        thr = np.union1d(thr, np.asarray([op], dtype=np.float32))   # sorted, without duplicates
+        sweep = ThresholdSweep(self.config.model.num_classes, thresholds=thr.tolist(), gt_threshold=float(self.config.agent.iou_threshold))
+        return sweep, int(np.nonzero(sweep.thresholds == op)[0][0])
 
     @staticmethod
     def _optional(section, name):
@@ -284,11 +312,15 @@ class Dense_U_Net_lidar_Agent:
         n = self.data_loader.valid_iterations
         nc = self.config.model.num_classes
         ep = {k: torch.zeros((n, nc), device=self.device) for k in ("loss", "iou", "nans", "acc")}
+        if self.sweep is not None:
+            self.sweep.reset()
         with torch.no_grad():
             for b, (image, lidar, ht_map) in enumerate(self.data_loader.valid_loader):
                 image, lidar, ht_map = self._to_device(image, lidar, ht_map)
                 prediction = self.model(image, lidar)
                 m = self.model.loss_metrics(prediction, ht_map)
+                if self.sweep is not None:
+                    self.sweep.update(prediction, ht_map)     # one more launch on the same stream, no synchronisation
                 iou_pc, nans, acc_pc = self._batch_metrics(m)
                 ep["loss"][b], ep["iou"][b], ep["nans"][b], ep["acc"][b] = m["loss_per_class"], iou_pc, nans, acc_pc
                 self._log(self.val_summary_writer, "Validation", m["loss_per_class"], acc_pc, iou_pc, self.current_val_iteration)
@@ -298,6 +330,12 @@ class Dense_U_Net_lidar_Agent:
                                  "nans": ep["nans"].sum(0).cpu(), "acc": ep["acc"].mean(0).cpu()})
         self.logger.info("Validation at Epoch-%d | Average Loss: %s | Average IoU: %s | Number of NaNs: %s | Average Accuracy: %s",
                          self.current_epoch, ep["loss"].mean(0).tolist(), avg_iou, ep["nans"].sum(0).tolist(), ep["acc"].mean(0).tolist())
+        if self.sweep is not None and self.sweep.counts is not None:   # one synchronisation per epoch, none per batch
+            sw = {k: v.cpu() for k, v in self.sweep.compute().items()}
+            self.val_history[-1]["sweep"] = sw
+            self.logger.info("Validation at Epoch-%d | Threshold sweep (%d logit thresholds) | Best threshold: %s | Best IoU: %s | IoU at %g: %s",
+                             self.current_epoch, self.sweep.num_thresholds, sw["best_threshold"].tolist(), sw["best_iou"].tolist(),
+                             float(self.sweep.thresholds[self.sweep_column]), sw["iou"][:, self.sweep_column].tolist())
         return avg_iou
 
     def save_hparams_json(self):

@@ -664,6 +664,35 @@ int dmm_loss_forward(int kind, int from_prob, const float* alpha, const float* g
   return DMM_OK;
 }
 
+size_t dmm_logit_hist_elems(int B, int NC, int nthr) {
+  if (B < 1 || NC < 1 || (long long)B * NC > 65535 || nthr < 1 || nthr > DMM_HIST_MAX_THRESHOLDS) return 0;
+  return (size_t)B * NC * 2 * (size_t)(nthr + 1);
+}
+
+int dmm_logit_hist(const float* logits, const float* target, int B, int NC, int H, int W, const float* thresholds, int nthr,
+                   float gt_threshold, int accumulate, int64_t* counts, void* stream) {
+  const std::string who = "dmm_logit_hist: ";
+  if (!logits || !target || !thresholds || !counts) return fail(DMM_ERR_INVALID, who + "null argument");
+  if ((uintptr_t)logits % 4 || (uintptr_t)target % 4) return fail(DMM_ERR_INVALID, who + "logits / target must be 4-byte aligned");
+  if ((uintptr_t)counts % 8) return fail(DMM_ERR_INVALID, who + "counts must be 8-byte aligned");
+  if (B < 1 || NC < 1 || H < 1 || W < 1) return fail(DMM_ERR_INVALID, who + "B, NC, H and W must be >= 1");
+  if ((long long)B * NC > 65535) return fail(DMM_ERR_INVALID, who + "B * NC must be <= 65535");
+  if ((long long)H * W >= (1ll << 31)) return fail(DMM_ERR_INVALID, who + "H * W must be < 2^31");
+  if (nthr < 1 || nthr > DMM_HIST_MAX_THRESHOLDS) return fail(DMM_ERR_INVALID, who + "nthr must be in [1, " + std::to_string(DMM_HIST_MAX_THRESHOLDS) + "]");
+  for (int k = 0; k < nthr; ++k)
+    if (!std::isfinite(thresholds[k])) return fail(DMM_ERR_INVALID, who + "thresholds[" + std::to_string(k) + "] is NaN or infinite");
+  for (int k = 1; k < nthr; ++k)
+    if (!(thresholds[k] > thresholds[k - 1])) return fail(DMM_ERR_INVALID, who + "thresholds must be strictly ascending (at index " + std::to_string(k) + ")");
+  if (std::isnan(gt_threshold)) return fail(DMM_ERR_INVALID, who + "gt_threshold is NaN");
+  LogitHistArgs a;
+  memset(&a, 0, sizeof(a));
+  a.logits = logits; a.target = target; a.counts = (unsigned long long*)counts;
+  a.B = B; a.NC = NC; a.H = H; a.W = W; a.K = nthr; a.gt = gt_threshold;
+  for (int k = 0; k < nthr; ++k) a.thr[k] = thresholds[k];
+  HIPCHK(launch_logit_hist(a, accumulate, (hipStream_t)stream));
+  return DMM_OK;
+}
+
 int dmm_plan_loss_backward(dmm_plan* plan, const float* logits, const float* target, double* metrics_out, void* stream) {
   if (!plan || !plan->bound) return fail(DMM_ERR_STATE, "plan not bound");
   if (!logits || !target) return fail(DMM_ERR_INVALID, "null argument");

@@ -110,6 +110,18 @@ struct BceArgs {
                            // loss_out, dx_out, the loss sums and the metric counts never see it
 };
 
+// ---- validation threshold sweep (lhist.hip) ----
+constexpr int HIST_MAX_THRESHOLDS = DMM_HIST_MAX_THRESHOLDS;
+struct LogitHistArgs {
+  const float* logits;  // (B, NC, H, W) fp32
+  const float* target;
+  unsigned long long* counts;  // int64 [B][NC][2][K + 1]: counts[b][n][t >= gt][#{k : x >= thr[k]}] += 1
+  int B, NC, H, W;             // H * W < 2^31, B * NC <= 65535 (gridDim.y)
+  int K;                       // 1 .. HIST_MAX_THRESHOLDS
+  float gt;
+  float thr[HIST_MAX_THRESHOLDS];  // strictly ascending, finite; by value (1020 bytes), so a launch needs no upload
+};
+
 struct ApplyCorrArgs {
   void* g;        // T gradient, pixel stride ldg: g += (q + ql) + (r + rl) * y
   const void* y;  // T forward tensor, pixel stride ldy
@@ -251,6 +263,12 @@ hipError_t launch_bn_bwd_finalize(const BnBwdFinalizeArgs& a, hipStream_t st);
 hipError_t launch_maxpool_fwd(const MaxpoolArgs& a, int dtype, hipStream_t st);
 hipError_t launch_maxpool_bwd(const MaxpoolBwdArgs& a, int dtype, hipStream_t st);
 hipError_t launch_bce_metrics(const BceArgs& a, int dtype, hipStream_t st);
+// accumulate == 0: a hipMemsetAsync of counts on `st` goes in front of the kernel; otherwise the kernel adds to what is there
+hipError_t launch_logit_hist(const LogitHistArgs& a, int accumulate, hipStream_t st);
+int logit_hist_grid_x(int planes, size_t plane);   // workgroups per (b, n) plane of that launch
+// accumulate == 0: a hipMemsetAsync of counts on `st` goes in front of the kernel; otherwise the kernel adds to what is there
+hipError_t launch_logit_hist(const LogitHistArgs& a, int accumulate, hipStream_t st);
+int logit_hist_grid_x(int planes, size_t plane);   // workgroups per (b, n) plane of that launch
 hipError_t launch_grad_sumsq(const GradSumsqArgs& a, hipStream_t st);
 hipError_t launch_guard_finalize(const GuardFinalizeArgs& a, hipStream_t st);
 // the one Adam launch.  a.state == nullptr: every class's step_size / bc2_sqrt / active and a.grad_scale come filled; a.state set: the

@@ -12,6 +12,8 @@
  *   dmm_plan_loss_backward ............... BCEWithLogitsLoss(reduction='none') + metrics + backward(ones)
  *                                          agents/Dense_U_Net_lidar_Agent.py:247-264, utils/...helper.py:311-401
  *   dmm_plan_set_loss / dmm_loss_forward . FocalLoss / ClassWiseFocalLoss  graphs/losses/FocalLoss.py:9-91
+ *   dmm_logit_hist ....................... nothing upstream: compute_IoU_whole_img_batch / calculate_accuracy
+ *                                          (utils/Dense_U_Net_lidar_helper.py:311-401) at up to 255 thresholds in one pass
  *   dmm_adam_step ........................ torch.optim.Adam.step        agents/Dense_U_Net_lidar_Agent.py:57-61,265
  *   dmm_adam_table_* / dmm_adam_step_segmented / dmm_adam_step_guarded_segmented
  *                                          torch.optim.Adam built over PARAMETER GROUPS (the list-of-dicts form of the constructor
@@ -140,6 +142,28 @@ int dmm_plan_set_loss(dmm_plan* plan, int kind, const float* alpha, const float*
  * (FocalLoss(logits=False): F.binary_cross_entropy, graphs/losses/FocalLoss.py:43-44). */
 int dmm_loss_forward(int kind, int from_prob, const float* alpha, const float* gamma, const float* input, const float* target,
                      float* loss_out, float* dinput_out, int batch, int nclass, int height, int width, void* stream);
+
+/* ---- validation threshold sweep: per-class logit histograms in one pass ----
+ * (Nothing upstream: the reference measures IoU and accuracy with raw logits cut at ONE number, config.agent.iou_threshold,
+ * utils/Dense_U_Net_lidar_helper.py:311-401.  This is the same comparison at up to 255 numbers at once.)
+ * logits and target are (B, NC, H, W) fp32 NCHW contiguous device tensors; thresholds are nthr strictly ascending finite fp32
+ * values in HOST memory (they travel by value with the launch: nothing is uploaded and they may be stack memory).  Per element
+ *   bin = #{k : x >= thresholds[k]}   0 .. nthr, compared in fp32; a NaN logit fails every comparison: bin 0
+ *   g   = target >= gt_threshold      0 or 1; a NaN target: 0
+ *   counts[b][n][g][bin] += 1         counts: int64 [B][NC][2][nthr + 1], device memory, dmm_logit_hist_elems elements
+ * so that for threshold k   tp = sum_{j > k} counts[..][1][j],   fp = sum_{j > k} counts[..][0][j]   and every thresholded metric
+ * follows from integers that are exact, independent of the launch geometry and add across batches and ranks.
+ * accumulate == 0: counts is cleared on `stream` in front of the kernel; accumulate != 0: the kernel adds to what counts holds.
+ * One launch, no plan, no synchronisation.  No limit on NC beyond B * NC <= 65535.
+ * Refuses with DMM_ERR_INVALID, before any HIP call: a null pointer; logits or target not 4-byte aligned, counts not 8-byte
+ * aligned; B, NC, H or W < 1; B * NC > 65535; H * W >= 2^31; nthr outside [1, DMM_HIST_MAX_THRESHOLDS]; a NaN or infinite
+ * threshold; thresholds not strictly ascending; a NaN gt_threshold. */
+#define DMM_HIST_MAX_THRESHOLDS 255
+/* elements (int64) of the counts array: B * NC * 2 * (nthr + 1); 0 for arguments dmm_logit_hist would refuse */
+size_t dmm_logit_hist_elems(int B, int NC, int nthr);
+int dmm_logit_hist(const float* logits, const float* target, int B, int NC, int H, int W,
+                   const float* thresholds /* host, nthr values */, int nthr, float gt_threshold,
+                   int accumulate, int64_t* counts /* device */, void* stream);
 
 /* Backward from an externally computed d(loss)/d(logit) (B,num_classes,H,W fp32), e.g. from torch autograd of any
  * loss on the returned logits (reference: loss.backward(...), agents/Dense_U_Net_lidar_Agent.py:264). */

@@ -45,6 +45,8 @@
 // DRIVE_EMA=1 (with DRIVE_FREEZE=1): behind each of those steps the two steps that keep a parameter average (dmm_adam_step_segmented_ema,
 // dmm_adam_step_guarded_segmented_ema) run under the same table - a gap in front, then a class with t0 > 0 - and each of their own
 // refusals is tried on both: a null struct, a null average, one that is or overlaps an arena, a decay of 1, below 0, above 1 and NaN, k < 1.
+// DRIVE_HIST=1 (life-cycle run): behind the lives, dmm_logit_hist on three shapes with operands that are addresses only - the memset and
+// the launch geometry of both accumulate modes - and every refusal of the entry point, each with nothing enqueued (hist_main).
 // Launch coalescing (dmm_set_option("batch_wgrad"), on by default; DRIVE_OPTIONS_OFF=batch_wgrad runs one launch per record,
 // DRIVE_BATCH_WGRAD=<0|1|2> sets the option's value: 2 = grouped on the weight-gradient stream instead of the caller's): every
 // life-cycle run watches the enqueue calls through the fake runtime's hook and checks, with the option on or off, that
@@ -231,6 +233,14 @@ struct EnqueueTrace {
   std::map<const void*, int> streams{{nullptr, 0}}, events;
   static int ordinal(std::map<const void*, int>& seen, const void* h) { return seen.emplace(h, (int)seen.size()).first->second; }
 } g_enqueue;
+// ---- DRIVE_HIST: what one dmm_logit_hist call enqueues (hist_main) ----
+struct HistWatch {
+  bool on = false;
+  long launches = 0, memsets = 0, other = 0;
+  std::string kernel;
+  unsigned gx = 0, gy = 0;
+  unsigned long long memset_bytes = 0;
+} g_hist;
 void drive_hook(int what, const char* kernel, unsigned gx, unsigned gy, const void* stream, const void* event) {
   if (g_enqueue.on) {
     const int s = EnqueueTrace::ordinal(g_enqueue.streams, stream);
@@ -240,6 +250,11 @@ void drive_hook(int what, const char* kernel, unsigned gx, unsigned gy, const vo
     else printf("T %s %llu s%d\n", what == 3 ? "memset" : "memcpy", bytes, s);
   }
   batch_hook(what, kernel, gx, gy, stream, event);
+  if (g_hist.on) {
+    if (what == 0) { ++g_hist.launches; g_hist.kernel = kernel; g_hist.gx = gx; g_hist.gy = gy; }
+    else if (what == 3) { ++g_hist.memsets; g_hist.memset_bytes = gx | (unsigned long long)gy << 32; }
+    else ++g_hist.other;
+  }
 }
 
 #define MUST(call)                                                                           \
@@ -966,6 +981,85 @@ static int route_main() {
 }
 #endif
 
+// ---- DRIVE_HIST: dmm_logit_hist (built against a csrc that has none: the case does not exist) ----
+#ifdef DMM_HIST_MAX_THRESHOLDS
+// Three shapes (a small one, one whose plane is no multiple of four, the C2 validation shape with 255 thresholds): logits and target
+// are addresses only (reserved, PROT_NONE), counts is a heap block of exactly dmm_logit_hist_elems elements, so the runtime's
+// memset is checked byte for byte.  Per shape: accumulate = 0 enqueues one memset of the whole block and one launch of the grid the
+// launcher's rule gives, accumulate = 1 the launch alone and leaves the block as it is.  Then every refusal, each with nothing enqueued.
+static int hist_main() {
+  struct Shape { int B, NC, H, W, K; };
+  const Shape shapes[3] = {{2, 3, 64, 96, 16}, {1, 1, 33, 35, 1}, {4, 3, 1280, 1920, 255}};
+  float thr[DMM_HIST_MAX_THRESHOLDS + 1];
+  for (int k = 0; k <= DMM_HIST_MAX_THRESHOLDS; ++k) thr[k] = -8.f + 0.0625f * k;
+  int bad = 0;
+  g_hist = HistWatch();
+  g_hist.on = true;
+  for (const Shape& s : shapes) {
+    const size_t px = (size_t)s.B * s.NC * s.H * s.W, elems = dmm_logit_hist_elems(s.B, s.NC, s.K);
+    const float* logits = (const float*)reserve(px * 4, PROT_NONE);
+    const float* target = (const float*)reserve(px * 4, PROT_NONE);
+    bool ok = elems == (size_t)s.B * s.NC * 2 * (s.K + 1);
+    int64_t* counts = (int64_t*)malloc(elems * 8);
+    memset(counts, 0x5a, elems * 8);
+    const unsigned want_gx = (unsigned)logit_hist_grid_x(s.B * s.NC, (size_t)s.H * s.W);
+    for (int acc = 0; acc < 2; ++acc) {
+      if (acc) memset(counts, 0x5a, elems * 8);
+      const HistWatch w0 = g_hist;
+      MUST(dmm_logit_hist(logits, target, s.B, s.NC, s.H, s.W, thr, s.K, 0.7f, acc, counts, nullptr));
+      ok = ok && g_hist.launches == w0.launches + 1 && g_hist.other == w0.other && g_hist.memsets == w0.memsets + (acc ? 0 : 1);
+      ok = ok && g_hist.kernel.find("logit_hist_kernel") != std::string::npos && g_hist.gx == want_gx && g_hist.gy == (unsigned)(s.B * s.NC);
+      ok = ok && want_gx >= 1 && (size_t)want_gx * 1024 < (size_t)s.H * s.W + 1024;   // no workgroup without a step of its own
+      if (!acc) ok = ok && g_hist.memset_bytes == elems * 8;
+      for (size_t i = 0; i < elems * 8; ++i) ok = ok && ((const unsigned char*)counts)[i] == (acc ? 0x5a : 0);
+    }
+    printf("HIST %d x %d x %d x %d K %d: grid %u x %u, %zu counts %s\n", s.B, s.NC, s.H, s.W, s.K, g_hist.gx, g_hist.gy, elems, ok ? "ok" : "WRONG");
+    bad += !ok;
+    free(counts);
+  }
+  // the refusals: nothing reaches the runtime, the message names the argument
+  const float* x = (const float*)reserve(1 << 20, PROT_NONE);
+  int64_t* c = (int64_t*)reserve(1 << 20, PROT_NONE);
+  const HistWatch w0 = g_hist;
+  auto refused = [&](int rc, const char* names) {
+    if (rc == DMM_ERR_INVALID && strstr(dmm_last_error(), names) != nullptr) return;
+    fprintf(stderr, "[drive] dmm_logit_hist: not refused (%d) or the message does not say '%s': %s\n", rc, names, dmm_last_error());
+    ++bad;
+  };
+  const float nan = __builtin_nanf(""), inf = __builtin_inff();
+  refused(dmm_logit_hist(nullptr, x, 1, 1, 8, 8, thr, 4, 0.7f, 0, c, nullptr), "null");
+  refused(dmm_logit_hist(x, nullptr, 1, 1, 8, 8, thr, 4, 0.7f, 0, c, nullptr), "null");
+  refused(dmm_logit_hist(x, x, 1, 1, 8, 8, nullptr, 4, 0.7f, 0, c, nullptr), "null");
+  refused(dmm_logit_hist(x, x, 1, 1, 8, 8, thr, 4, 0.7f, 0, nullptr, nullptr), "null");
+  refused(dmm_logit_hist((const float*)((const char*)x + 2), x, 1, 1, 8, 8, thr, 4, 0.7f, 0, c, nullptr), "4-byte aligned");
+  refused(dmm_logit_hist(x, (const float*)((const char*)x + 1), 1, 1, 8, 8, thr, 4, 0.7f, 0, c, nullptr), "4-byte aligned");
+  refused(dmm_logit_hist(x, x, 1, 1, 8, 8, thr, 4, 0.7f, 0, (int64_t*)((char*)c + 4), nullptr), "8-byte aligned");
+  refused(dmm_logit_hist(x, x, 0, 1, 8, 8, thr, 4, 0.7f, 0, c, nullptr), ">= 1");
+  refused(dmm_logit_hist(x, x, 1, 0, 8, 8, thr, 4, 0.7f, 0, c, nullptr), ">= 1");
+  refused(dmm_logit_hist(x, x, 1, 1, 0, 8, thr, 4, 0.7f, 0, c, nullptr), ">= 1");
+  refused(dmm_logit_hist(x, x, 1, 1, 8, -1, thr, 4, 0.7f, 0, c, nullptr), ">= 1");
+  refused(dmm_logit_hist(x, x, 256, 256, 8, 8, thr, 4, 0.7f, 0, c, nullptr), "B * NC");
+  refused(dmm_logit_hist(x, x, 1, 1, 65536, 32768, thr, 4, 0.7f, 0, c, nullptr), "H * W");
+  refused(dmm_logit_hist(x, x, 1, 1, 8, 8, thr, 0, 0.7f, 0, c, nullptr), "nthr");
+  refused(dmm_logit_hist(x, x, 1, 1, 8, 8, thr, DMM_HIST_MAX_THRESHOLDS + 1, 0.7f, 0, c, nullptr), "nthr");
+  const float t_nan[3] = {0.f, nan, 2.f}, t_inf[3] = {0.f, 1.f, inf}, t_eq[3] = {0.f, 1.f, 1.f}, t_desc[3] = {0.f, 1.f, 0.5f};
+  refused(dmm_logit_hist(x, x, 1, 1, 8, 8, t_nan, 3, 0.7f, 0, c, nullptr), "NaN or infinite");
+  refused(dmm_logit_hist(x, x, 1, 1, 8, 8, t_inf, 3, 0.7f, 0, c, nullptr), "NaN or infinite");
+  refused(dmm_logit_hist(x, x, 1, 1, 8, 8, t_eq, 3, 0.7f, 0, c, nullptr), "strictly ascending");
+  refused(dmm_logit_hist(x, x, 1, 1, 8, 8, t_desc, 3, 0.7f, 0, c, nullptr), "strictly ascending");
+  refused(dmm_logit_hist(x, x, 1, 1, 8, 8, thr, 4, nan, 0, c, nullptr), "gt_threshold");
+  if (g_hist.launches != w0.launches || g_hist.memsets != w0.memsets || g_hist.other != w0.other) { fprintf(stderr, "[drive] a refused dmm_logit_hist call reached the runtime\n"); ++bad; }
+  if (dmm_logit_hist_elems(0, 3, 4) || dmm_logit_hist_elems(2, 0, 4) || dmm_logit_hist_elems(256, 256, 4) || dmm_logit_hist_elems(2, 3, 0) ||
+      dmm_logit_hist_elems(2, 3, DMM_HIST_MAX_THRESHOLDS + 1) || dmm_logit_hist_elems(65535, 1, 255) != (size_t)65535 * 2 * 256) {
+    fprintf(stderr, "[drive] dmm_logit_hist_elems\n"); ++bad;
+  }
+  g_hist.on = false;
+  hipDeviceSynchronize();
+  printf("%s\n", bad ? "HIST FAILED" : "HIST OK");
+  return bad ? 1 : 0;
+}
+#endif
+
 int main(int argc, char** argv) {
   g_enqueue.on = getenv("DRIVE_TRACE_ENQUEUE") != nullptr;
   fakehip_set_hook(drive_hook);
@@ -1000,6 +1094,9 @@ int main(int argc, char** argv) {
     if (life == 0) { streams_after_first = fakehip_stream_creates(); events_after_first = fakehip_event_creates(); }
   }
   int rc = 0;
+#ifdef DMM_HIST_MAX_THRESHOLDS
+  if (getenv("DRIVE_HIST") && hist_main() != 0) rc = 1;
+#endif
   if (g_bad) { fprintf(stderr, "[drive] FAIL: %ld device pointers outside the caller's regions\n", g_bad); rc = 1; }
   if (fakehip_violations()) { fprintf(stderr, "[drive] FAIL: %ld teardown / handle violations\n", fakehip_violations()); rc = 1; }
   if (lives > 1 && fakehip_stream_creates() != streams_after_first) {
