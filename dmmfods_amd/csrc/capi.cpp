@@ -1312,6 +1312,38 @@ int dmm_conv_forward(const dmm_conv_desc* d, const void* x, const float* w, cons
   return DMM_OK;
 }
 
+// The logits launch as plan.cpp builds it for dec_out_to_heat_maps.refine1: one plain segment at stride 1 with the full tap table,
+// EPI_LOGITS, no statistics, the caller's fp32 NCHW tensor.  Everything the logits epilogues are not built for is refused before the
+// runtime is asked anything.
+int dmm_conv_logits(const dmm_conv_desc* d, const void* x, const float* w, const float* scale, const float* shift, float* logits,
+                    void* scratch, void* stream) {
+  const std::string who = "dmm_conv_logits: ";
+  if (!d || !x || !w || !logits || !scratch) return fail(DMM_ERR_INVALID, who + "null argument");
+  if (d->bn_relu && (!scale || !shift)) return fail(DMM_ERR_INVALID, who + "bn_relu needs scale and shift");
+  if (d->transposed || d->mode != 0 || d->stride != 1) return fail(DMM_ERR_INVALID, who + "a logits launch is a plain convolution at stride 1");
+  if (d->Cout < 1 || d->Cout > 32) return fail(DMM_ERR_INVALID, who + "the logits epilogues are built for at most 32 output channels");
+  OneConv g;
+  if (!geometry(d, g) || g.Ho < 1 || g.Wo < 1) return fail(DMM_ERR_INVALID, who + "unsupported conv descriptor");
+  hipStream_t st = (hipStream_t)stream;
+  std::vector<PackDesc> packs;
+  std::vector<int> prefix;
+  PackDesc* dd; int* dp; int total_rows;
+  layout_fwd(d, g, (uint8_t*)scratch, w, nullptr, packs, &dd, &dp, prefix, total_rows);
+  HIPCHK(upload(dd, packs.data(), packs.size() * sizeof(PackDesc), st));
+  HIPCHK(upload(dp, prefix.data(), prefix.size() * sizeof(int), st));
+  HIPCHK(hipStreamSynchronize(st));
+  HIPCHK(launch_pack(dd, dp, (int)packs.size(), total_rows, d->dtype, st));
+  ConvArgs a;
+  memset(&a, 0, sizeof(a));
+  a.nseg = 1;
+  fill_one_seg(a.seg[0], d, g, x, scale, shift, g.phase_taps[0]);
+  a.B = d->B; a.Ho = g.Ho; a.Wo = g.Wo; a.M = d->B * g.Ho * g.Wo;
+  a.wpack = packs[0].dst; a.N = d->Cout; a.Npad = packs[0].Npad;
+  a.out = nullptr; a.logits = logits; a.ldo = d->Cout; a.Hout = g.Ho; a.Wout = g.Wo; a.ostride = 1;
+  HIPCHK(launch_igemm(a, d->dtype, EPI_LOGITS, d->use_mfma != 0, st, IMPL_AUTO, g_family_off));
+  return DMM_OK;
+}
+
 // dy_eff = dy + q[c] + r[c] * yfwd (the deferred BatchNorm-backward correction of the plan's gradient buffers) when q != NULL
 static void set_eff_grad(Seg& s, const void* yfwd, int ldy, const float* q, const float* r, const float* zeros) {
   if (q == nullptr) return;

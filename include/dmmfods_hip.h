@@ -386,6 +386,13 @@ typedef struct {
 size_t dmm_conv_scratch_bytes(const dmm_conv_desc* d);
 int dmm_conv_forward(const dmm_conv_desc* d, const void* x, const float* w, const float* scale, const float* shift, void* y,
                      double* stats, void* scratch, void* stream);
+/* The logits launch of the network's last convolution (dec_out_to_heat_maps.refine1; reference graphs/models/Dense_U_Net_lidar.py:128-131)
+ * on its own: a plain convolution at stride 1 (optionally behind BN+ReLU) whose output is written UNROUNDED as fp32 NCHW
+ * (B, Cout, Ho, Wo) - no statistics.  It dispatches as the plan's launch does: thin.hip (16-bit storage, 64 input channels, 1..3
+ * classes), halo.hip (f16 / fp32 where the weights fit its LDS), else the generic kernel.  DMM_ERR_INVALID, before anything is
+ * launched, for transposed / mode != 0 / stride != 1 descriptors, Cout > 32 and null pointers. */
+int dmm_conv_logits(const dmm_conv_desc* d, const void* x, const float* w, const float* scale, const float* shift, float* logits,
+                    void* scratch, void* stream);
 /* dw: fp32, master layout, overwritten.  dy: T NHWC gradient of the conv output. */
 int dmm_conv_wgrad(const dmm_conv_desc* d, const void* x, const void* dy, const float* scale, const float* shift, float* dw,
                    void* scratch, void* stream);
@@ -439,8 +446,8 @@ int dmm_conv_wgrad_grouped(const dmm_conv_desc* descs, int n, const void* const*
 int dmm_bw1_reduce_grouped(int n, const float* const* part, float* const* dpack, const int* nct, const int* nsplit, const int* wc,
                            int grouped, int* launches, void* stream);
 
-/* Which kernel family ran the calling thread's most recent single-kernel launch (dmm_conv_forward / _wgrad(_ex) / _dgrad(_ex) /
- * dmm_conv1x1_backward_fused; for multi-launch entry points: the last launch).  The single-kernel entry points dispatch like a
+/* Which kernel family ran the calling thread's most recent single-kernel launch (dmm_conv_forward / _logits / _wgrad(_ex) / _dgrad(_ex) /
+ * dmm_conv1x1_backward_fused / dmm_conv5_wgrad_stats; for multi-launch entry points: the last launch).  The single-kernel entry points dispatch like a
  * plan does and fall back to the generic implicit-GEMM kernels when no specialised family accepts the shape - silently, so a
  * per-kernel parity test asserts the family it names: dmm_impl_name(dmm_last_impl()) is one of
  * "generic", "thin", "conv3", "cvp", "halo", "wg3", "wg5", "wgp", "pig", "bw1"  ("auto": nothing launched yet).

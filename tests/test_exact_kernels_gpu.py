@@ -19,8 +19,9 @@ fp32 chains of condition (c) - the stored values a kernel adds in fp32 before th
   wg5 (conv5_stats_case): the factor correlations are fp32 MFMA accumulators over a workgroup's whole walk - condition (b), not (c)
 The cases use 128 (512 where noted), the upper bound of all of these.
 
-Not here: hf.hip and thin.hip - no single-kernel entry point builds their launches, and hf is held bit-equal to conv3 inside a plan
-(tests/test_timed_kernels_gpu.py); cvd_kernel, reachable only through lab flags; cvp_multi_kernel and cvw's four-phase walk, which
+Not here: hf.hip - no single-kernel entry point builds its launch, and hf is held bit-equal to conv3 inside a plan
+(tests/test_timed_kernels_gpu.py); the logits launch (thin.hip, halo.logits, igemm.logits), which has a file of its own:
+tests/test_logits_kernels_gpu.py; cvd_kernel, reachable only through lab flags; cvp_multi_kernel and cvw's four-phase walk, which
 only a plan's launch with ConvArgs::nphase = 4 reaches (dmm_conv_forward launches each output parity on its own).
 
 Where this file departs from the shapes first proposed for it, after reading the launchers:

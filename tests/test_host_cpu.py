@@ -477,11 +477,11 @@ def test_a_launch_its_recorded_family_did_not_take_is_an_error(host_drive):
     assert re.search(r"launch 'wg3\.\S+': the plan recorded family wg5, generic ran", r.stderr), r.stderr[-2000:]
 
 
-def _single(host_drive, entry, dtype, B, H, W, Cin, Cout, R, pad, transposed=0, mode=0):
+def _single(host_drive, entry, dtype, B, H, W, Cin, Cout, R, pad, transposed=0, mode=0, flags=""):
     env = {k: v for k, v in os.environ.items() if not k.startswith("DMM_")}
     env.update(ASAN_OPTIONS="detect_leaks=0:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
-    r = subprocess.run([host_drive, "single", entry, dtype] + [str(v) for v in (B, H, W, Cin, Cout, R, pad, transposed, mode)], env=env,
-                       capture_output=True, text=True, timeout=600)
+    r = subprocess.run([host_drive, "single", entry, dtype] + [str(v) for v in (B, H, W, Cin, Cout, R, pad, transposed, mode)] + ([flags] if flags else []),
+                       env=env, capture_output=True, text=True, timeout=600)
     m = re.search(r"^SINGLE \w+ rc (-?\d+) last (\w+) ran (\S+) launches (\d+) x_bytes (\d+) y_bytes (\d+)", r.stdout, re.M)
     assert r.returncode == 0 and m, (r.stdout + r.stderr)[-3000:]
     return dict(rc=int(m[1]), last=m[2], ran=set(m[3].split("+")), x_bytes=int(m[5]), y_bytes=int(m[6]), out=r.stdout)
@@ -533,6 +533,34 @@ def test_family_refusal_boundaries_single_launch(host_drive):
     assert below["y_bytes"] < GIB4 == at["y_bytes"] and at["x_bytes"] < GIB4
     assert (below["rc"], below["last"], below["ran"]) == (0, "wgp", {"wgp", "wgpw"}), below
     assert (at["rc"], at["last"], at["ran"]) == (0, "wgp", {"wgp", "generic"}), at
+
+
+def test_logits_entry_point_families_and_refusals(host_drive):
+    """dmm_conv_logits under the fake runtime, for every (storage type, channels, classes, taps, thin on / off, MFMA / scalar) that
+    tests/test_logits_kernels_gpu.py launches: the family the dispatcher picks is the one the case names (two launches: the pack and
+    the convolution) - thin for 16-bit 64 -> 1..3; halo for f16 whenever thin refuses (4 classes, 32 channels, switched off) and for
+    fp32 where the weights fit its LDS (the 3x3 64 -> 3 AND the 5x5 8 -> 8); the generic kernel for bf16 when thin refuses, the fp32
+    5x5 64 -> 3 and every scalar launch.  What the entry point refuses returns DMM_ERR_INVALID with nothing enqueued and no family noted."""
+    from tools import exact_operands as E
+    name = {0: "f32", 1: "f16", 2: "bf16"}
+    seen = set()
+    for family, dtype, mfma, thin_off, s in [c[:5] for c in E.LOGITS] + [(f, dt, 1, off, s) for f, dt, off, s in E.ROUND_LOGITS]:
+        key = (family, dtype, mfma, thin_off, s[3:])
+        if key in seen:         # (the dispatch does not depend on the map: one run per distinct launch kind)
+            continue
+        seen.add(key)
+        B, H, W, Cin, Cout, R, pad = s
+        flags = ",".join(f for f, on in (("thinoff", thin_off), ("scalar", not mfma)) if on)
+        r = _single(host_drive, "logits", name[dtype], B, H, W, Cin, Cout, R, pad, flags=flags)
+        assert (r["rc"], r["last"], r["ran"]) == (0, family, {family}) and " launches 2 " in r["out"], (key, r)
+    assert {k[0] for k in seen} == {"thin", "halo", "generic"}
+    bad = [dict(transposed=1, R=3, pad=1), dict(mode=1), dict(mode=2), dict(flags="stride2"), dict(Cout=33), dict(Cout=0), dict(flags="nullx"),
+           dict(flags="nullw"), dict(flags="nulllogits"), dict(flags="nullscratch")]
+    for change in bad:
+        a = dict(B=1, H=9, W=13, Cin=64, Cout=3, R=5, pad=2)
+        a.update(change)
+        r = _single(host_drive, "logits", "f16", **a)
+        assert r["rc"] == -1 and r["ran"] == {"none"} and " launches 0 " in r["out"] and "error: dmm_conv_logits: " in r["out"], (change, r)
 
 
 def test_generic_weight_gradient_refuses_what_it_does_not_implement(host_drive):

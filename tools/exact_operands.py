@@ -30,7 +30,8 @@ caps |y| / u near 2**8.5 whatever the storage type (the budget of 2**10 relies o
 to (c)).
 
 Below them, the single-rounding operands (make_rounding_operands, Operands.check_rounding): the same exactness in fp32, but every
-16-bit store rounds once - see the comment there."""
+16-bit store rounds once - see the comment there.  At the end, the logits launch (part "logits" of both generators): an fp32 output
+without statistics, and the padding condition (p) - see the comment there."""
 import functools
 from types import SimpleNamespace
 
@@ -40,6 +41,7 @@ import torch.nn.functional as F
 DT = {0: torch.float32, 1: torch.float16, 2: torch.bfloat16}
 SIG_BITS = {0: 24, 1: 11, 2: 8}        # significant bits of the storage type
 FWD_BITS = {0: 10, 1: 10, 2: 8}        # budget of |y| / u (see the module docstring on stat_sq)
+LOGITS_BITS = 20                       # ... of a logits launch, which stores fp32: sum |term| / u stays 16 times below (b)'s 2**24
 DENSITY_CAP = 0.75                     # keep a quarter of the weights zero wherever the budgets would allow all of them
 
 
@@ -139,6 +141,16 @@ class Operands(SimpleNamespace):
         aa = o.a.abs().requires_grad_(True)
         wa = o.w.abs().requires_grad_(True)
         ya = conv(aa, wa, c)
+        if "logits" in o.parts:     # the logits launch stores fp32 and keeps no statistics: (a) in fp32, (b), and the padding
+            assert torch.equal(o.y.float().double(), o.y), f"(a) logits are not representable in fp32: max |y| = {float(o.y.abs().max())}"
+            fig["b_y"] = float(ya.detach().max()) / o.uy
+            # a kernel that pads BEFORE the prologue (relu(shift) in place of zero) must differ from the reference on every image's border
+            assert c.bn and bool((F.relu(o.shift) > 0).any()), "(p) no channel has relu(shift) > 0: padding before and after the prologue agree"
+            d = o.y != o.y_padnorm
+            inner = d[:, :, c.pad:o.Ho - c.pad, c.pad:o.Wo - c.pad]
+            assert not bool(inner.any()), "(p) the two references differ away from the border"
+            fig["pad_diff"] = float(d.double().mean())
+            assert bool(d.flatten(1).any(dim=1).all()), "(p) an image's border does not tell padding before the prologue from padding after it"
         if "fwd" in o.parts:
             rep("output", o.y)
             fig["b_y"] = float(ya.detach().max()) / o.uy
@@ -162,7 +174,7 @@ class Operands(SimpleNamespace):
 def make_operands(dtype, B, H, W, Cin, Cout, R, S, stride, pad, transposed=0, mode=0, bn=1, with_q=0, acc=0,
                   parts=("fwd", "wgrad", "dgrad"), seed=0, chain=128, chain_red=128, fwd_bits=None):
     """Operands and fp64 reference of one case.  parts: what the caller will launch and compare - "fwd" (output and statistics), "wgrad",
-    "dgrad" (stored data gradient, red1, red2); the weights are bounded only by what is stored.  chain / chain_red: the fp32 chain of
+    "dgrad" (stored data gradient, red1, red2), or "logits" alone (dmm_conv_logits: the output as fp32, no statistics); the weights are bounded only by what is stored.  chain / chain_red: the fp32 chain of
     condition (c) for the forward statistics / the BatchNorm-backward sums; fwd_bits: log2 of the budget of |y| / u (default: FWD_BITS).
     NCHW fp64 tensors on the CPU."""
     c = SimpleNamespace(dtype=dtype, B=B, H=H, W=W, Cin=Cin, Cout=Cout, R=3 if transposed else R, S=3 if transposed else S,
@@ -196,6 +208,9 @@ def make_operands(dtype, B, H, W, Cin, Cout, R, S, stride, pad, transposed=0, mo
     ua = 0.5 if bn else 1.0
     uy, udz = ua * pool, pool
     ylim = uy * 2 ** (fwd_bits or min(SIG_BITS[dtype], FWD_BITS[dtype])) if "fwd" in parts else None
+    if "logits" in parts:   # stored in fp32 whatever the storage type: the budget is (b)'s, with room to spare
+        assert "fwd" not in parts and mode == 0 and not transposed and stride == 1
+        ylim = uy * 2 ** (fwd_bits or LOGITS_BITS)
     glim = None
     if "dgrad" in parts:   # |gx| <= gain * scale * sum effmax |w| + |gold|, in steps of udz / 2
         gain = 4.0 if mode == 1 else pool
@@ -215,6 +230,8 @@ def make_operands(dtype, B, H, W, Cin, Cout, R, S, stride, pad, transposed=0, mo
     y = conv(ar, wr, c)
     o.a, o.y = a, y.detach()
     o.stat_sum, o.stat_sq = o.y.sum(dim=(0, 2, 3)), (o.y ** 2).sum(dim=(0, 2, 3))
+    if "logits" in parts and bn:   # what a kernel computes that normalises its padding: the prologue over the zero-padded input
+        o.y_padnorm = F.conv2d(F.relu(F.pad(x, (pad,) * 4) * v(scale) + v(shift)), w)
     if o.backward:
         (y * eff).sum().backward()
         o.dw = wr.grad
@@ -393,6 +410,8 @@ def _check_rounding(o):
     # (a) exact in fp32 in any order: what enters a rounding point (z, the sum behind eff and gx: asserted by _rnd when the reference was
     # built), every output, data-gradient, red1 term - the same convolution over the operands' absolute values, in units of the step
     fig["a_y"] = float(ya.detach().max()) / (ua * uw * o.pool)
+    if "logits" in o.parts:     # the fp32 logits: compared unrounded (y is y_pre), so no share of y is asked for - the rounding points
+        assert torch.equal(o.y, o.y_pre) and torch.equal(o.y.float().double(), o.y), "(a) logits are not representable in fp32"   # are a and w
     if o.backward:
         (ya * o.eff.abs()).sum().backward()
         fig["a_dz"] = float(aa.grad.max()) / (ueff * uw * o.pool)
@@ -491,6 +510,9 @@ def make_rounding_operands(dtype, B, H, W, Cin, Cout, R, S, stride, pad, transpo
     fan_out = Cin * (4 if transposed else T)                # taps that can meet in one output element
     fan_in = Cout * T * (4 if mode == 1 else 1)             # ... in one input-gradient element
     no = nnz_out or (16 if kind == "weights" else NNZ_OUT[dtype])      # ("weights": the products step in 2**-13, so few of them)
+    if "logits" in parts:       # fp32 logits: no stored output to overflow f16 - every weight may be nonzero ((a) holds the sums)
+        assert "fwd" not in parts and kind != "subnormal" and mode == 0 and not transposed and stride == 1
+        no = nnz_out or fan_out
     ni = nnz_in or (4 if kind == "weights" else NNZ_IN[with_q])
     density = min(0.5, no / fan_out, ni / fan_in if "dgrad" in parts else 1.0)
     wslots = _round_weights(g, c, density, cover)
@@ -539,7 +561,11 @@ def make_rounding_operands(dtype, B, H, W, Cin, Cout, R, S, stride, pad, transpo
                  Ho=Ho, Wo=Wo, backward=backward, a=a, a_in=a, a_pre=a_pre, pool=1.0, round_a=round_a, fwd=fwd, density=float((wslots != 0).double().mean()))
     o.xhat = (x - v(mean)) * v(invstd)
     o.y_pre = y_pre.detach()
-    o.y = _rnd(o.y_pre, dt, "conv(a, w_T)")
+    if "logits" in parts:       # stored unrounded
+        assert torch.equal(o.y_pre.float().double(), o.y_pre), "(a) conv(a, w_T) is not representable in fp32"
+        o.y = o.y_pre
+    else:
+        o.y = _rnd(o.y_pre, dt, "conv(a, w_T)")
     o.stat_sum, o.stat_sq = o.y.sum(dim=(0, 2, 3)), (o.y ** 2).sum(dim=(0, 2, 3))
     o.sq_bound = chain * 2.0 ** -24 * o.stat_sq          # per channel: one fp32 rounding per added y**2, `chain` of them per partial
     if backward:
@@ -623,3 +649,78 @@ ROUND_PIG = ROUND_FORWARD[0][1]
 ROUND_GENERIC = CASES[0]             # 1x1 72->32 2x12x20: 32 output channels, which pig refuses
 ROUND_BW1 = ROUND_BACKWARD[0][2]
 ROUND_CONV3_DGRAD = ROUND_BACKWARD[1][2]
+
+
+# ================================================================================================ the logits launch (round 13)
+# dmm_conv_logits: the network's last convolution (5x5, 64 -> classes, behind BN+ReLU), written UNROUNDED as fp32 NCHW.  Part "logits"
+# of make_operands / make_rounding_operands: the output has to be representable in fp32 only, there are no statistics, and - since
+# thin.hip zero-pads AFTER the prologue - the reference must tell that from padding before it on every image's border (check(): (p)).
+# The cases of tests/test_logits_kernels_gpu.py, shared with tests/test_logits_operands_cpu.py: family that must run, storage type,
+# use_mfma, whether the thin family is switched off, (B, H, W, Cin, Cout, R, pad) - all behind BN+ReLU - and why the case is there.
+def thin_geometry(B, H, W, R=2, slots=2 * 256):
+    """thin.hip thin_resolve: strips of 128 - 2R output columns, the row split whose rounds x (rows + 2R) is smallest (the finer on a tie)."""
+    wout = 128 - 2 * R
+    nxs = -(-W // wout)
+    best, rows_per_wg, nys = -1, 8, -(-H // 8)
+    for n in range(1, max(1, H // 8) + 1):
+        rows = -(-H // n)
+        wgs = B * (-(-H // rows)) * nxs
+        cost = -(-wgs // slots) * (rows + 2 * R)
+        if best < 0 or cost <= best:
+            best, rows_per_wg, nys = cost, rows, -(-H // rows)
+    return dict(nxs=nxs, last_cols=W - (nxs - 1) * wout, rows_per_wg=rows_per_wg, nys=nys, last_rows=H - (nys - 1) * rows_per_wg,
+                nwg=B * nys * nxs, steps=rows_per_wg + 2 * R + 1)
+
+
+def xcd_remap(bid, nblocks):
+    """common.h xcd_remap: the logical workgroup of hardware workgroup `bid` (every XCD one contiguous range)."""
+    x, i = bid & 7, bid >> 3
+    lo, rem = nblocks >> 3, nblocks & 7
+    return x * lo + min(x, rem) + i
+
+
+def halo_tiles(B, Ho, Wo):
+    """halo.hip halo_plan: 8 x 16 output tiles, walked by min(CUs, tiles) workgroups."""
+    return B * (-(-Ho // 8)) * (-(-Wo // 16))
+
+
+_T = "thin"
+LOGITS_THIN = [   # (B, H, W, classes), what thin_geometry must give, why
+    ((2, 37, 131, 3), dict(nxs=2, last_cols=7, rows_per_wg=10, nys=4, last_rows=7, nwg=16, steps=15), "two column strips, ragged last row strip, the ring wraps"),
+    ((3, 37, 255, 3), dict(nxs=3, nys=4, nwg=36), "a grid that is no multiple of 8: xcd_remap's remainder"),
+    ((1, 9, 125, 1), dict(nxs=2, last_cols=1, rows_per_wg=9, nys=1), "KN = 1; the second strip owns one column"),
+    ((2, 45, 249, 2), dict(nxs=3, last_cols=1, rows_per_wg=9, nys=5, last_rows=9, nwg=30), "KN = 2; three strips, the last one column wide; no ragged row strip"),
+    ((1, 7, 124, 3), dict(nxs=1, last_cols=124), "exactly one full strip"),
+    ((1, 3, 5, 3), dict(nwg=1, rows_per_wg=3), "a map smaller than the tap box, fewer rows than ring slots"),
+    ((1, 1, 1, 2), dict(nwg=1), "a single pixel"),
+]
+# family, dtype, use_mfma, thin switched off, (B, H, W, Cin, Cout, R, pad), note
+LOGITS = [(_T, dt, 1, 0, (B, H, W, 64, N, 5, 2), why) for (B, H, W, N), _, why in LOGITS_THIN for dt in (1, 2)] + [
+    ("halo", 1, 1, 0, (1, 100, 350, 64, 4, 5, 2), "thin has no 4-class instantiation; 286 tiles on 256 CUs, both map edges ragged"),
+    ("halo", 1, 1, 0, (2, 20, 24, 32, 3, 5, 2), "32 input channels: the head of every small test network"),
+    ("halo", 1, 1, 1, (2, 37, 131, 64, 3, 5, 2), "thin switched off"),
+    ("halo", 0, 1, 0, (2, 12, 20, 64, 3, 3, 1), "fp32: the 3x3's weights fit halo's LDS (72 KB; the 64-channel 5x5's 200 KB do not)"),
+    ("generic", 2, 1, 0, (2, 37, 131, 64, 4, 5, 2), "bf16, 4 classes: thin and halo both refuse"),
+    ("generic", 2, 1, 0, (2, 37, 131, 32, 3, 5, 2), "bf16, 32 input channels"),
+    ("generic", 2, 1, 1, (2, 37, 131, 64, 3, 5, 2), "bf16, thin switched off"),
+    ("generic", 0, 1, 0, (2, 37, 131, 64, 3, 5, 2), "fp32 5x5, MFMA"),
+    ("generic", 0, 0, 0, (2, 37, 131, 64, 3, 5, 2), "fp32 5x5, scalar kernel"),
+    # (8 channels x 25 taps are 13 fp32 chunks, 26 KB: THIS 5x5 fits halo's LDS, and halo takes it; the scalar kernel keeps the tail on igemm)
+    ("halo", 0, 1, 0, (3, 3, 5, 8, 8, 5, 2), "fp32 5x5 8 -> 8: the N = 8 tail"),
+    ("generic", 0, 0, 0, (3, 3, 5, 8, 8, 5, 2), "fp32 5x5 8 -> 8 on the scalar kernel: igemm's N = 8 tail"),
+    ("generic", 1, 0, 0, (1, 9, 125, 64, 3, 5, 2), "f16 scalar kernel"),
+]
+LOGITS_HALO_WALK = (1, 100, 350)      # the halo case whose tiles outnumber the compute units
+LOGITS_REPRO = (3, 37, 255, 64, 3, 5, 2)
+# single rounding: family, dtype, thin switched off, shape; each with kinds "main" and "weights"
+ROUND_LOGITS = [(_T, dt, 0, s) for s in ((2, 37, 131, 64, 3, 5, 2), (1, 9, 125, 64, 1, 5, 2)) for dt in (1, 2)] + [
+    ("halo", 1, 0, (2, 12, 20, 64, 4, 5, 2)),
+    ("generic", 2, 0, (2, 12, 20, 64, 4, 5, 2)),
+]
+ROUND_LOGITS_KINDS = ("main", "weights")
+DT_NAME = {0: "fp32", 1: "fp16", 2: "bf16"}
+
+
+def logits_id(family, dtype, mfma, thin_off, s):
+    B, H, W, Cin, Cout, R, pad = s
+    return f"{family}-{DT_NAME[dtype]}-{R}x{R}-{Cin}to{Cout}-{B}x{H}x{W}" + ("" if mfma else "-scalar") + ("-thinoff" if thin_off else "")

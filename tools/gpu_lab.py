@@ -200,6 +200,49 @@ def conv_case(name, dtype, mfma, B, H, W, Cin, Cout, R, S, stride, pad, transpos
     return not bad and fam_ok
 
 
+LOGITS_GUARD = 4096   # floats of NaN on either side of the logits tensor
+
+
+def logits_case(name, dtype, mfma, B, H, W, Cin, Cout, R, pad, exact=True, expect=None, exact_kw=None, seed=0, keep=None):
+    """The logits launch (dmm_conv_logits: the network's last convolution, fp32 NCHW output, no statistics) on the exact operands
+    (exact=True) or the single-rounding operands (exact="round") of tools/exact_operands.py, part "logits", behind BN+ReLU.  The
+    output lies between two guard bands; tensor and bands start as NaN.  ok only if every logit equals the fp64 reference, both bands
+    are still all NaN and the family `expect` ran.  keep: a dict that receives the logits as read back (for run-to-run comparisons)."""
+    assert exact in (True, "round")
+    dt = {0: torch.float32, 1: torch.float16, 2: torch.bfloat16}[dtype]
+    o = _operands(exact, dtype, B, H, W, Cin, Cout, R, R, 1, pad, bn=1, parts=("logits",), seed=seed, **(exact_kw or {}))
+    x, scale, shift, w = (t.float() for t in (o.x, o.scale, o.shift, o.w))
+    rnd = exact == "round"
+    d = _lib.ConvDesc(dtype=dtype, use_mfma=mfma, B=B, H=H, W=W, Cin=Cin, Cout=Cout, R=R, S=R, stride=1, pad=pad, transposed=0, mode=0, bn_relu=1)
+    scratch = torch.zeros(L.dmm_conv_scratch_bytes(C.byref(d)), dtype=torch.uint8, device=DEV)
+    xd, wd, sd, hd = nhwc(x, dt).to(DEV), w.to(DEV), scale.to(DEV), shift.to(DEV)
+    n = B * Cout * o.Ho * o.Wo
+    buf = torch.full((n + 2 * LOGITS_GUARD,), float("nan"), device=DEV)
+    out = buf[LOGITS_GUARD:LOGITS_GUARD + n]
+    _lib.impls_since_reset()
+    _lib.check(L.dmm_conv_logits(C.byref(d), xd.data_ptr(), wd.data_ptr(), sd.data_ptr(), hd.data_ptr(), out.data_ptr(), scratch.data_ptr(),
+                                 _lib.stream_ptr()))
+    torch.cuda.synchronize()
+    fam_ok = _check_family(name + " logits", expect)
+    host = buf.cpu()
+    got = host[LOGITS_GUARD:LOGITS_GUARD + n].view(B, Cout, o.Ho, o.Wo)
+    if keep is not None:
+        keep["logits"] = got.clone()
+    res = {"logits": (_ndiff if rnd else _absdiff)(got, o.y)}
+    guard = int((~torch.isnan(host[:LOGITS_GUARD])).sum()) + int((~torch.isnan(host[LOGITS_GUARD + n:])).sum())
+    bad = _verdict(res, exact, None) + (["guard"] if guard else [])
+    wrong = got.double() != o.y
+    where = ""
+    if bool(wrong.any()):   # where: the first differing element, how many are NaN, and whether the output is that of padding before the prologue
+        b, cl, yy, xx = (int(v) for v in wrong.nonzero()[0])
+        where = f" first at (b={b}, class={cl}, y={yy}, x={xx}) got {float(got[b, cl, yy, xx])} want {float(o.y[b, cl, yy, xx])}, {int(wrong.sum())} differ, {int(torch.isnan(got).sum())} NaN"
+        if hasattr(o, "y_padnorm") and torch.equal(got.double(), o.y_padnorm):
+            where += " - equal to the convolution with the prologue applied to the padding"
+    print(f"{'FAIL' if bad else 'ok  '} logits {name:34s} dt={dtype} mfma={mfma}{' round' if rnd else ' exact'} " + _show(res, exact) +
+          f" guard={guard}{where}", flush=True)
+    return not bad and fam_ok
+
+
 def _eff_setup(g, dt, B, Cout, Ho, Wo, with_q):
     """Incoming gradient of a convolution output as the plan's launches see it: raw gradient dy, and optionally the deferred
     BatchNorm-backward correction q + r * yfwd of the layer behind it (yfwd = that layer's input = this convolution's output)."""
@@ -599,6 +642,7 @@ def run_kernels():
                 except Exception:
                     ok = False
                     print(f"EXC  {c[0]} dt={dtype} mfma={mfma}\n" + traceback.format_exc(), flush=True)
+    ok &= all([logits_case(exact_operands.logits_id(f, dt, m, off, s), dt, m, *s, expect=f) for f, dt, m, off, s, _ in exact_operands.LOGITS if not off])
     return ok
 
 

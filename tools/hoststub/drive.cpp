@@ -14,7 +14,8 @@
 // more cost only address space here:
 //   drive picks <arch> <dtype> <batch> <H> <W>     every convolution launch of a bound plan, re-run through its launcher: the family
 //                                                  that takes it must be the one the plan recorded (workspace: reserved, never touched)
-//   drive single <fwd|wgrad|dgrad|fused> <dtype> <B> <H> <W> <Cin> <Cout> <R> <pad> <transposed> <mode>
+//   drive single <fwd|logits|wgrad|dgrad|fused> <dtype> <B> <H> <W> <Cin> <Cout> <R> <pad> <transposed> <mode> [flags]
+//                                                  flags (entry `logits`), comma-separated: thinoff, scalar, stride2, nullx, nullw, nulllogits, nullscratch
 //                                                  one call of a single-kernel entry point on operands that are addresses only
 //   drive refuse                                   launch_wgrad(..., IMPL_GENERIC) on arguments the generic kernel does not implement
 // And one prints what a plan IS, so that two builds of the plan builder can be compared byte for byte without a GPU:
@@ -893,10 +894,19 @@ static int single_main(int argc, char** argv) {
   double* stats = (double*)calloc(2 * (size_t)d.Cout, 8); double* red = (double*)calloc(2 * (size_t)d.Cin, 8);
   const size_t sb = dmm_conv_scratch_bytes(&d);
   void* scratch = calloc(sb ? sb : 1, 1);
+  const std::string flags = argc > 13 ? "," + std::string(argv[13]) + "," : ",";
+  auto flag = [&](const char* f) { return flags.find("," + std::string(f) + ",") != std::string::npos; };
+  if (flag("thinoff")) dmm_set_option("thin_logits", 0);
+  if (flag("scalar")) d.use_mfma = 0;
+  if (flag("stride2")) d.stride = 2;
   dmm_impl_mask(1);
   const long l0 = fakehip_launches();
   int rc = -99;
   if (entry == "fwd") rc = dmm_conv_forward(&d, x, w, scale, shift, y, stats, scratch, nullptr);
+  else if (entry == "logits")   // the fp32 NCHW logits are an address only, as x
+    rc = dmm_conv_logits(&d, flag("nullx") ? nullptr : x, flag("nullw") ? nullptr : w, scale, shift,
+                         flag("nulllogits") ? nullptr : (float*)reserve((size_t)d.B * d.H * d.W * up * (d.Cout > 0 ? d.Cout : 1) * 4, PROT_NONE),
+                         flag("nullscratch") ? nullptr : scratch, nullptr);
   else if (entry == "wgrad") rc = dmm_conv_wgrad_ex(&d, x, y, scale, shift, nullptr, nullptr, nullptr, 0, dw, scratch, nullptr);
   else if (entry == "dgrad") rc = dmm_conv_dgrad_ex(&d, x, y, w, scale, shift, nullptr, nullptr, nullptr, gx, 0, red, scratch, nullptr);
   else if (entry == "fused") rc = dmm_conv1x1_backward_fused(&d, x, y, w, scale, shift, nullptr, nullptr, nullptr, gx, 0, dw, red, scratch, nullptr);
