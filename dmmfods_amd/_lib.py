@@ -61,6 +61,24 @@ class AdamEma(C.Structure):
 assert C.sizeof(AdamSegment) == 24 and C.sizeof(AdamClass) == 32 and C.sizeof(AdamEma) == 24
 
 
+AUG_MAX_TENSORS, AUG_MAX_CHANNELS, AUG_LAUNCH_BATCH = 4, 8, 32   # DMM_AUG_MAX_TENSORS, DMM_AUG_MAX_CHANNELS, DMM_AUG_LAUNCH_BATCH
+
+
+class AugTensor(C.Structure):
+    """dmm_aug_tensor: one tensor of a dmm_augment_batch call; src_batch_stride in elements."""
+    _fields_ = [("src", C.c_void_p), ("dst", C.c_void_p), ("src_batch_stride", C.c_int64), ("channels", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
+class AugSample(C.Structure):
+    """dmm_aug_sample: one sample's window, mirror flag and per-channel gain / bias (channels numbered through the call's tensors)."""
+    _fields_ = [("y0", C.c_int32), ("x0", C.c_int32), ("flip", C.c_int32), ("reserved", C.c_int32),
+                ("gain", C.c_float * AUG_MAX_CHANNELS), ("bias", C.c_float * AUG_MAX_CHANNELS)]
+
+
+assert C.sizeof(AugTensor) == 32 and C.sizeof(AugSample) == 80
+
+
 class DmmError(RuntimeError):
     pass
 
@@ -118,6 +136,8 @@ def lib():
     L.dmm_logit_hist_elems.argtypes = [C.c_int, C.c_int, C.c_int]
     L.dmm_logit_hist_elems.restype = sz
     L.dmm_logit_hist.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int, f32, C.c_int, vp, vp]
+    L.dmm_augment_batch.argtypes = [C.POINTER(AugTensor), C.c_int, C.POINTER(AugSample), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                    C.POINTER(C.c_float), vp]
     L.dmm_plan_num_grad_buckets.argtypes = [vp]
     L.dmm_plan_num_graph_replays.argtypes = [vp, C.c_int]
     L.dmm_plan_num_graph_replays.restype = C.c_longlong
@@ -177,7 +197,7 @@ EXPORTS = [
     "dmm_adam_table_bytes", "dmm_adam_table_init", "dmm_adam_step_segmented", "dmm_adam_step_guarded_segmented",
     "dmm_adam_step_segmented_ema", "dmm_adam_step_guarded_segmented_ema",
     "dmm_plan_wgrad_batch_counts", "dmm_conv_wgrad_grouped", "dmm_bw1_reduce_grouped",
-    "dmm_logit_hist_elems", "dmm_logit_hist",
+    "dmm_logit_hist_elems", "dmm_logit_hist", "dmm_augment_batch",
 ]
 HIST_MAX_THRESHOLDS = 255   # DMM_HIST_MAX_THRESHOLDS
 

@@ -13,7 +13,9 @@ and a parameter average (``config.optimizer.ema_decay``, ``ema_warmup``: validat
 best checkpoint, runs on the exponential moving average of the parameters that the Adam launch keeps; it travels inside the
 checkpoint's optimiser entry) and a validation threshold sweep (``config.agent.threshold_sweep``: one more launch per validation batch
 takes per-class logit histograms, and the epoch's ``val_history`` row carries IoU, precision, recall, F1, accuracy and average precision
-at every threshold; ``best_val_iou`` and the checkpoints do not depend on it)."""
+at every threshold; ``best_val_iou`` and the checkpoints do not depend on it) and on-device augmentation of the training batches
+(``config.loader.augment``: a dict of ``dmmfods_amd.augment.BatchAugment``'s arguments - crop, flip, shift, image gain and bias, modality
+dropout in one launch per batch; its batch counter travels in the checkpoint's ``"augment"`` entry; validation is never augmented)."""
 import logging
 import os
 import warnings
@@ -23,6 +25,7 @@ from pathlib import Path
 import numpy as np
 import torch
 
+from ..augment import BatchAugment
 from ..datasets.WaymoData import WaymoDataset_Loader
 from ..graphs.models.Dense_U_Net_lidar import densenet121_u_lidar
 from ..metrics import ThresholdSweep, logit_thresholds
@@ -125,6 +128,9 @@ class Dense_U_Net_lidar_Agent:
         # agent.threshold_sweep: validation also takes per-class logit histograms (dmmfods_amd.metrics.ThresholdSweep) and its
         # val_history row carries every thresholded metric at every threshold.  Absent: the reference's loop, not one call more.
         self.sweep, self.sweep_column = self._make_sweep(self._optional(self.config.agent, "threshold_sweep"))
+        # loader.augment: a dict of BatchAugment's arguments; every training batch is cropped / flipped / shifted / scaled on the device,
+        # behind the copy to it and in front of the model, by one more launch.  Validation never is.  Absent: not one call more.
+        self.augment = self._make_augment(self._optional(self.config.loader, "augment"))
         self.lr_scheduler = None
         if o.lr_scheduler.want:
             self.lr_scheduler = _StepLR(self.optimizer, o.lr_scheduler.every_n_epochs, o.lr_scheduler.gamma)
@@ -173,6 +179,20 @@ class Dense_U_Net_lidar_Agent:
         return sweep, int(np.nonzero(sweep.thresholds == op)[0][0])
 
     @staticmethod
+    def _make_augment(spec):
+        """spec: None (no augmentation) or a dict of BatchAugment's arguments.  The model takes sizes that are multiples of 32, so
+        out_size has to be one; rank defaults to this process's torch.distributed rank, so that every rank draws its own parameters."""
+        if spec is None:
+            return None
+        kw = dict(spec)
+        if "rank" not in kw and torch.distributed.is_available() and torch.distributed.is_initialized():
+            kw["rank"] = torch.distributed.get_rank()
+        aug = BatchAugment(**kw)
+        if aug.out_size is not None and (aug.out_size[0] % 32 or aug.out_size[1] % 32):
+            raise ValueError("loader.augment: out_size must be a multiple of 32 in both dimensions")
+        return aug
+
+    @staticmethod
     def _optional(section, name):
         try:
             return getattr(section, name)
@@ -185,6 +205,8 @@ class Dense_U_Net_lidar_Agent:
         state = {k.epoch: self.current_epoch, k.train_iteration: self.current_train_iteration,
                  k.val_iteration: self.current_val_iteration, k.best_val_iou: self.best_val_iou,
                  k.state_dict: self.model.state_dict(), k.optimizer: self.optimizer.state_dict()}
+        if self.augment is not None:
+            state["augment"] = self.augment.state_dict()   # the number of batches drawn: a resumed run continues the sequence
         if is_best:
             filename = self.config.agent.best_checkpoint_name
         Path(self.config.dir.current_run.checkpoints).mkdir(exist_ok=True, parents=True)
@@ -207,6 +229,11 @@ class Dense_U_Net_lidar_Agent:
         self.model.load_state_dict(ck[k.state_dict])
         self._apply_freeze_phase()   # the phase of the checkpoint's epoch, before the optimiser derives its step origins from the flags
         self.optimizer.load_state_dict(ck[k.optimizer])
+        if self.augment is not None:
+            # seed and batch counter from the checkpoint (one without the entry: batch 0); the rank stays this process's own - every
+            # rank of a data-parallel run loads the file one of them wrote
+            st = ck.get("augment") or {"seed": self.augment.seed, "batches_drawn": 0}
+            self.augment.load_state_dict(dict(st, rank=self.augment.rank))
 
     # ------------------------------------------------------------------ driver (A:165-213)
     def run(self):
@@ -269,6 +296,8 @@ class Dense_U_Net_lidar_Agent:
         open_batches = 0   # batches whose gradients sit in the arena waiting for a step (always 0 here when window == 1)
         for b, (image, lidar, ht_map) in enumerate(self.data_loader.train_loader):
             image, lidar, ht_map = self._to_device(image, lidar, ht_map)
+            if self.augment is not None:
+                image, lidar, ht_map = self.augment(image, lidar, ht_map)
             if window > 1 and open_batches == 0:
                 self.optimizer.zero_grad()                    # A:263 (start of a window)
             with torch.no_grad():

@@ -693,6 +693,74 @@ int dmm_logit_hist(const float* logits, const float* target, int B, int NC, int 
   return DMM_OK;
 }
 
+int dmm_augment_batch(const dmm_aug_tensor* tensors, int ntensors, const dmm_aug_sample* samples, int B, int Hs, int Ws, int Ho, int Wo,
+                      const float* fill, void* stream) {
+  const std::string who = "dmm_augment_batch: ";
+  if (!tensors || !samples) return fail(DMM_ERR_INVALID, who + "null argument");
+  if (ntensors < 1 || ntensors > DMM_AUG_MAX_TENSORS) return fail(DMM_ERR_INVALID, who + "ntensors must be in [1, " + std::to_string(DMM_AUG_MAX_TENSORS) + "]");
+  if (B < 1 || Hs < 1 || Ws < 1 || Ho < 1 || Wo < 1) return fail(DMM_ERR_INVALID, who + "B, Hs, Ws, Ho and Wo must be >= 1");
+  const long long splane = (long long)Hs * Ws, dplane = (long long)Ho * Wo;
+  if (splane >= (1ll << 31)) return fail(DMM_ERR_INVALID, who + "Hs * Ws must be < 2^31");
+  if (dplane >= (1ll << 31)) return fail(DMM_ERR_INVALID, who + "Ho * Wo must be < 2^31");
+  int nch = 0;
+  for (int t = 0; t < ntensors; ++t) {
+    const dmm_aug_tensor& T = tensors[t];
+    const std::string which = who + "tensor " + std::to_string(t) + ": ";
+    if (!T.src || !T.dst) return fail(DMM_ERR_INVALID, which + "null src or dst");
+    if ((uintptr_t)T.src % 4 || (uintptr_t)T.dst % 4) return fail(DMM_ERR_INVALID, which + "src / dst must be 4-byte aligned");
+    if (T.reserved != 0) return fail(DMM_ERR_INVALID, which + "reserved must be 0");
+    if (T.channels < 1) return fail(DMM_ERR_INVALID, which + "channels must be >= 1");
+    nch += T.channels;
+    if (nch > DMM_AUG_MAX_CHANNELS) return fail(DMM_ERR_INVALID, who + "channels must sum to at most " + std::to_string(DMM_AUG_MAX_CHANNELS));
+    if (T.src_batch_stride < T.channels * splane) return fail(DMM_ERR_INVALID, which + "src_batch_stride must be >= channels * Hs * Ws");
+    // (the byte ranges of the checks below are formed in uintptr_t: a stride that would wrap them is refused here)
+    if (T.src_batch_stride > (1ll << 60) / B) return fail(DMM_ERR_INVALID, which + "src_batch_stride * B is out of range");
+  }
+  // dst [dst, dst + B * channels * Ho * Wo) against every src span [src, src + (B - 1) * stride + channels * Hs * Ws) and every other dst
+  auto overlaps = [](uintptr_t a, uintptr_t an, uintptr_t b, uintptr_t bn) { return a < b + bn && b < a + an; };
+  auto dst_bytes = [&](int t) { return (uintptr_t)B * tensors[t].channels * dplane * 4; };
+  for (int t = 0; t < ntensors; ++t)
+    for (int u = 0; u < ntensors; ++u) {
+      const uintptr_t sn = ((uintptr_t)(B - 1) * tensors[u].src_batch_stride + (uintptr_t)tensors[u].channels * splane) * 4;
+      if (overlaps((uintptr_t)tensors[t].dst, dst_bytes(t), (uintptr_t)tensors[u].src, sn))
+        return fail(DMM_ERR_INVALID, who + "dst of tensor " + std::to_string(t) + " overlaps src of tensor " + std::to_string(u) + " (in place is not supported)");
+    }
+  for (int t = 0; t < ntensors; ++t)
+    for (int u = t + 1; u < ntensors; ++u)
+      if (overlaps((uintptr_t)tensors[t].dst, dst_bytes(t), (uintptr_t)tensors[u].dst, dst_bytes(u)))
+        return fail(DMM_ERR_INVALID, who + "dst of tensor " + std::to_string(t) + " overlaps dst of tensor " + std::to_string(u));
+  for (int b = 0; b < B; ++b) {
+    const dmm_aug_sample& s = samples[b];
+    const std::string which = who + "sample " + std::to_string(b) + ": ";
+    if (s.flip != 0 && s.flip != 1) return fail(DMM_ERR_INVALID, which + "flip must be 0 or 1");
+    if (s.reserved != 0) return fail(DMM_ERR_INVALID, which + "reserved must be 0");
+    if (s.y0 > (1 << 30) || s.y0 < -(1 << 30) || s.x0 > (1 << 30) || s.x0 < -(1 << 30)) return fail(DMM_ERR_INVALID, which + "|y0| and |x0| must be <= 2^30");
+    for (int c = 0; c < nch; ++c)
+      if (!std::isfinite(s.gain[c]) || !std::isfinite(s.bias[c])) return fail(DMM_ERR_INVALID, which + "gain / bias of channel " + std::to_string(c) + " is NaN or infinite");
+  }
+  AugArgs a;
+  memset(&a, 0, sizeof(a));
+  for (int c = 0; c < nch; ++c) {
+    a.fill[c] = fill ? fill[c] : 0.f;
+    if (!std::isfinite(a.fill[c])) return fail(DMM_ERR_INVALID, who + "fill[" + std::to_string(c) + "] is NaN or infinite");
+  }
+  for (int t = 0, c = 0; t < ntensors; ++t)
+    for (int k = 0; k < tensors[t].channels; ++k, ++c) {
+      a.ch[c].src = tensors[t].src + (size_t)k * splane;
+      a.ch[c].dst = tensors[t].dst + (size_t)k * dplane;
+      a.ch[c].src_stride = tensors[t].src_batch_stride;
+      a.ch[c].dst_stride = tensors[t].channels * dplane;
+    }
+  a.Hs = Hs; a.Ws = Ws; a.Ho = Ho; a.Wo = Wo;
+  for (int b0 = 0; b0 < B; b0 += DMM_AUG_LAUNCH_BATCH) {
+    const int nb = std::min(DMM_AUG_LAUNCH_BATCH, B - b0);
+    a.b0 = b0;
+    memcpy(a.s, samples + b0, (size_t)nb * sizeof(dmm_aug_sample));
+    HIPCHK(launch_augment(a, nch, nb, (hipStream_t)stream));
+  }
+  return DMM_OK;
+}
+
 int dmm_plan_loss_backward(dmm_plan* plan, const float* logits, const float* target, double* metrics_out, void* stream) {
   if (!plan || !plan->bound) return fail(DMM_ERR_STATE, "plan not bound");
   if (!logits || !target) return fail(DMM_ERR_INVALID, "null argument");

@@ -122,6 +122,22 @@ struct LogitHistArgs {
   float thr[HIST_MAX_THRESHOLDS];  // strictly ascending, finite; by value (1020 bytes), so a launch needs no upload
 };
 
+// ---- batch augmentation (augment.hip) ----
+constexpr int AUG_MAX_CHANNELS = DMM_AUG_MAX_CHANNELS;
+constexpr int AUG_LAUNCH_BATCH = DMM_AUG_LAUNCH_BATCH;
+struct AugChannel {        // one global channel: plane `c` of its tensor, for sample 0
+  const float* src;        // tensor.src + c * Hs * Ws; sample b: + b * src_stride
+  float* dst;              // tensor.dst + c * Ho * Wo; sample b: + b * dst_stride
+  long long src_stride, dst_stride;   // elements
+};
+struct AugArgs {           // by value (about 2.9 KB), so a launch needs no upload
+  AugChannel ch[AUG_MAX_CHANNELS];    // gridDim.y of them
+  float fill[AUG_MAX_CHANNELS];
+  int Hs, Ws, Ho, Wo;      // Hs * Ws, Ho * Wo < 2^31
+  int b0;                  // sample of blockIdx.z == 0
+  dmm_aug_sample s[AUG_LAUNCH_BATCH];   // gridDim.z of them: samples b0 ...
+};
+
 struct ApplyCorrArgs {
   void* g;        // T gradient, pixel stride ldg: g += (q + ql) + (r + rl) * y
   const void* y;  // T forward tensor, pixel stride ldy
@@ -269,6 +285,9 @@ int logit_hist_grid_x(int planes, size_t plane);   // workgroups per (b, n) plan
 // accumulate == 0: a hipMemsetAsync of counts on `st` goes in front of the kernel; otherwise the kernel adds to what is there
 hipError_t launch_logit_hist(const LogitHistArgs& a, int accumulate, hipStream_t st);
 int logit_hist_grid_x(int planes, size_t plane);   // workgroups per (b, n) plane of that launch
+// one launch: gridDim = (augment_grid_x(Ho, Wo), nchannels, nsamples <= AUG_LAUNCH_BATCH)
+hipError_t launch_augment(const AugArgs& a, int nchannels, int nsamples, hipStream_t st);
+unsigned augment_grid_x(int Ho, int Wo);   // workgroups per plane: one lane per four output pixels of a row
 hipError_t launch_grad_sumsq(const GradSumsqArgs& a, hipStream_t st);
 hipError_t launch_guard_finalize(const GuardFinalizeArgs& a, hipStream_t st);
 // the one Adam launch.  a.state == nullptr: every class's step_size / bc2_sqrt / active and a.grad_scale come filled; a.state set: the

@@ -14,6 +14,8 @@
  *   dmm_plan_set_loss / dmm_loss_forward . FocalLoss / ClassWiseFocalLoss  graphs/losses/FocalLoss.py:9-91
  *   dmm_logit_hist ....................... nothing upstream: compute_IoU_whole_img_batch / calculate_accuracy
  *                                          (utils/Dense_U_Net_lidar_helper.py:311-401) at up to 255 thresholds in one pass
+ *   dmm_augment_batch .................... nothing upstream (the reference feeds the model what the loader yields, :236-244): crop,
+ *                                          flip, shift, per-channel gain and bias of a device batch in one launch
  *   dmm_adam_step ........................ torch.optim.Adam.step        agents/Dense_U_Net_lidar_Agent.py:57-61,265
  *   dmm_adam_table_* / dmm_adam_step_segmented / dmm_adam_step_guarded_segmented
  *                                          torch.optim.Adam built over PARAMETER GROUPS (the list-of-dicts form of the constructor
@@ -164,6 +166,49 @@ size_t dmm_logit_hist_elems(int B, int NC, int nthr);
 int dmm_logit_hist(const float* logits, const float* target, int B, int NC, int H, int W,
                    const float* thresholds /* host, nthr values */, int nthr, float gt_threshold,
                    int accumulate, int64_t* counts /* device */, void* stream);
+
+/* ---- on-device batch augmentation: crop, flip, shift, gain and bias in one launch ----
+ * (Nothing upstream: the reference trains on exactly what its loader yields, agents/Dense_U_Net_lidar_Agent.py:236-244.  These are
+ * per-sample, label-preserving rearrangements of a batch that already sits on the device: image, LiDAR plane and heat maps move
+ * together, so the pairing of input and label is kept.)
+ * Up to DMM_AUG_MAX_TENSORS tensors of one batch - e.g. image, LiDAR, target, which may be channel slices of one (B, 7, H, W)
+ * allocation - with at most DMM_AUG_MAX_CHANNELS channels between them, all of source size Hs x Ws and output size Ho x Wo.
+ * Channels are numbered through the tensors in list order.  For sample b, channel c, output pixel (y, x):
+ *   sy = y0 + y;   sx = x0 + (flip ? Wo - 1 - x : x)
+ *   inside (0 <= sy < Hs and 0 <= sx < Ws):   v = src[b][c][sy][sx]
+ *       gain[c] == 1 and bias[c] == 0 :  out = v, bit for bit (NaN payloads, -0 and infinities included)
+ *       otherwise                      :  out = (gain[c] * v) + bias[c]     two fp32 roundings, never fused
+ *   outside:                                  out = fill[c], untouched by gain and bias
+ * Every element of every dst is written exactly once, nothing else is written, src is only read; no atomics, so the result does not
+ * depend on the launch geometry.  All address arithmetic is 64-bit: only one plane (Hs * Ws, Ho * Wo) has to stay below 2^31.
+ * samples and fill are HOST memory and travel by value with the launch (they may be stack memory; nothing is uploaded, nothing is
+ * synchronised).  ceil(B / DMM_AUG_LAUNCH_BATCH) launches, each covering every tensor of the call; no plan.
+ * Refuses with DMM_ERR_INVALID, before any HIP call: a null tensors or samples, a null src or dst; ntensors outside
+ * [1, DMM_AUG_MAX_TENSORS]; channels < 1 or summing above DMM_AUG_MAX_CHANNELS; B, Hs, Ws, Ho or Wo < 1; Hs * Ws or Ho * Wo >= 2^31;
+ * src_batch_stride < channels * Hs * Ws; a pointer that is not 4-byte aligned; flip other than 0 or 1; |y0| or |x0| above 2^30; a
+ * NaN or infinite gain, bias (of a channel in use) or fill; a non-zero reserved field; a dst range that overlaps any tensor's src
+ * span or another dst (in place is not supported). */
+#define DMM_AUG_MAX_TENSORS   4
+#define DMM_AUG_MAX_CHANNELS  8     /* summed over the tensors of one call */
+#define DMM_AUG_LAUNCH_BATCH 32     /* samples whose parameters travel by value with one launch */
+typedef struct dmm_aug_tensor {
+  const float* src;          /*  0: (B, channels, Hs, Ws) fp32; planes and channels contiguous, samples src_batch_stride apart */
+  float* dst;                /*  8: (B, channels, Ho, Wo) fp32 NCHW contiguous */
+  int64_t src_batch_stride;  /* 16: elements, >= channels * Hs * Ws (a channel slice of an (N, 7, H, W) batch is such a tensor) */
+  int32_t channels;          /* 24 */
+  int32_t reserved;          /* 28: 0 */
+} dmm_aug_tensor;            /* 32 bytes */
+typedef struct dmm_aug_sample {
+  int32_t y0, x0;            /*  0, 4: source position of the window's top-left corner; may be negative, the window may overhang */
+  int32_t flip;              /*  8: 0 / 1: the window is read mirrored left-right */
+  int32_t reserved;          /* 12: 0 */
+  float gain[DMM_AUG_MAX_CHANNELS];   /* 16: per channel, numbered through the tensors in list order */
+  float bias[DMM_AUG_MAX_CHANNELS];   /* 48 */
+} dmm_aug_sample;            /* 80 bytes */
+int dmm_augment_batch(const dmm_aug_tensor* tensors, int ntensors,
+                      const dmm_aug_sample* samples /* host, B entries */, int B,
+                      int Hs, int Ws, int Ho, int Wo,
+                      const float* fill /* host, one value per channel; NULL = zeros */, void* stream);
 
 /* Backward from an externally computed d(loss)/d(logit) (B,num_classes,H,W fp32), e.g. from torch autograd of any
  * loss on the returned logits (reference: loss.backward(...), agents/Dense_U_Net_lidar_Agent.py:264). */
