@@ -1347,6 +1347,19 @@ static void fill_one_seg(Seg& s, const dmm_conv_desc* d, const OneConv& g, const
   fill_seg_taps(s, taps, g.BK);
 }
 
+// the forward launch of phase `ph` (dmm_conv_forward, dmm_conv_forward_merged)
+static void fill_fwd_phase(ConvArgs& a, const dmm_conv_desc* d, const OneConv& g, const void* x, const float* scale, const float* shift,
+                           void* y, double* stats, const PackDesc& pack, size_t ph) {
+  memset(&a, 0, sizeof(a));
+  a.nseg = 1;
+  fill_one_seg(a.seg[0], d, g, x, scale, shift, g.phase_taps[ph]);
+  a.B = d->B; a.Ho = g.Ho; a.Wo = g.Wo; a.M = d->B * g.Ho * g.Wo;
+  a.wpack = pack.dst; a.N = d->Cout; a.Npad = pack.Npad;
+  a.out = y; a.ldo = d->Cout; a.Hout = g.Hout; a.Wout = g.Wout; a.ostride = g.ostride;
+  a.py = g.phase_xy[ph].first; a.px = g.phase_xy[ph].second;
+  if (stats) { a.stat_sum = stats; a.stat_sq = stats + d->Cout; }
+}
+
 int dmm_last_impl(void) { return g_last_impl; }
 unsigned dmm_impl_mask(int reset) { const unsigned m = g_impl_mask; if (reset) g_impl_mask = 0; return m; }
 const char* dmm_impl_name(int impl) { return impl >= 0 && impl < IMPL_COUNT ? kImplNames[impl] : "?"; }
@@ -1367,16 +1380,54 @@ int dmm_conv_forward(const dmm_conv_desc* d, const void* x, const float* w, cons
   if (stats) HIPCHK(hipMemsetAsync(stats, 0, 2 * d->Cout * sizeof(double), st));
   for (size_t ph = 0; ph < packs.size(); ++ph) {
     ConvArgs a;
-    memset(&a, 0, sizeof(a));
-    a.nseg = 1;
-    fill_one_seg(a.seg[0], d, g, x, scale, shift, g.phase_taps[ph]);
-    a.B = d->B; a.Ho = g.Ho; a.Wo = g.Wo; a.M = d->B * g.Ho * g.Wo;
-    a.wpack = packs[ph].dst; a.N = d->Cout; a.Npad = packs[ph].Npad;
-    a.out = y; a.ldo = d->Cout; a.Hout = g.Hout; a.Wout = g.Wout; a.ostride = g.ostride;
-    a.py = g.phase_xy[ph].first; a.px = g.phase_xy[ph].second;
-    if (stats) { a.stat_sum = stats; a.stat_sq = stats + d->Cout; }
+    fill_fwd_phase(a, d, g, x, scale, shift, y, stats, packs[ph], ph);
     HIPCHK(launch_igemm(a, d->dtype, EPI_STORE, d->use_mfma != 0, st, IMPL_AUTO, g_family_off));
   }
+  return DMM_OK;
+}
+
+// A ConvTranspose forward as the plan runs it (plan.cpp emit_conv_fwd): the four per-phase records of dmm_conv_forward, each picked,
+// then merged into ONE launch by the plan's own eligibility / copy / accept functions (plan.h) - or, where those keep the phases
+// apart, the four launches.  *launches: 1 or 4.
+int dmm_conv_forward_merged(const dmm_conv_desc* d, const void* x, const float* w, const float* scale, const float* shift, void* y,
+                            double* stats, void* scratch, void* stream, int* launches) {
+  const std::string who = "dmm_conv_forward_merged: ";
+  if (!d || !x || !w || !y || !scratch || !launches) return fail(DMM_ERR_INVALID, who + "null argument");
+  if (!d->transposed) return fail(DMM_ERR_INVALID, who + "the merged launch is a ConvTranspose's (transposed = 1)");
+  if (d->bn_relu && (!scale || !shift)) return fail(DMM_ERR_INVALID, who + "bn_relu needs scale and shift");
+  OneConv g;
+  if (!geometry(d, g) || g.phase_taps.size() != 4) return fail(DMM_ERR_INVALID, who + "unsupported conv descriptor");
+  hipStream_t st = (hipStream_t)stream;
+  const bool mfma = d->use_mfma != 0;
+  const unsigned deny = g_family_off;
+  std::vector<PackDesc> packs;
+  std::vector<int> prefix;
+  PackDesc* dd; int* dp; int total_rows;
+  layout_fwd(d, g, (uint8_t*)scratch, w, nullptr, packs, &dd, &dp, prefix, total_rows);
+  HIPCHK(upload(dd, packs.data(), packs.size() * sizeof(PackDesc), st));
+  HIPCHK(upload(dp, prefix.data(), prefix.size() * sizeof(int), st));
+  HIPCHK(hipStreamSynchronize(st));
+  HIPCHK(launch_pack(dd, dp, (int)packs.size(), total_rows, d->dtype, st));
+  if (stats) HIPCHK(hipMemsetAsync(stats, 0, 2 * d->Cout * sizeof(double), st));
+  ConvArgs a[4];
+  int impl[4];
+  bool merge = true;
+  for (int ph = 0; ph < 4; ++ph) {
+    fill_fwd_phase(a[ph], d, g, x, scale, shift, y, stats, packs[ph], ph);
+    impl[ph] = igemm_pick(a[ph], d->dtype, EPI_STORE, mfma, deny);
+    merge = merge && convT_fwd_phase_eligible(a[ph], EPI_STORE, impl[ph], a[0]);
+  }
+  ConvArgs m = a[0];
+  if (merge) {
+    for (int ph = 0; ph < 4; ++ph) copy_convT_fwd_phase(m, a[ph], ph);
+    merge = accept_convT_fwd_merged(m, d->dtype, mfma, deny);
+  }
+  if (merge) {
+    HIPCHK(launch_igemm(m, d->dtype, EPI_STORE, mfma, st, IMPL_CVP));
+  } else {
+    for (int ph = 0; ph < 4; ++ph) HIPCHK(launch_igemm(a[ph], d->dtype, EPI_STORE, mfma, st, impl[ph]));
+  }
+  *launches = merge ? 1 : 4;
   return DMM_OK;
 }
 
@@ -1416,6 +1467,22 @@ int dmm_conv_logits(const dmm_conv_desc* d, const void* x, const float* w, const
 static void set_eff_grad(Seg& s, const void* yfwd, int ldy, const float* q, const float* r, const float* zeros) {
   if (q == nullptr) return;
   s.src2 = yfwd; s.ld2 = ldy; s.q = q; s.r = r; s.ql = zeros; s.rl = zeros;
+}
+
+// the normal-form weight-gradient launch of phase `ph` (dmm_conv_wgrad_ex, dmm_conv_wgrad_merged)
+static void fill_wgrad_phase(WgradArgs& a, const dmm_conv_desc* d, const OneConv& g, const void* x, const void* dy, const float* scale,
+                             const float* shift, const void* yfwd, const float* q, const float* r, const float* zeros, const PackDesc& pack,
+                             size_t ph) {
+  memset(&a, 0, sizeof(a));
+  a.nseg = 1;
+  fill_one_seg(a.seg[0], d, g, x, scale, shift, g.phase_taps[ph]);
+  a.B = d->B; a.Ho = g.Ho; a.Wo = g.Wo; a.M = d->B * g.Ho * g.Wo;
+  a.dy.src = dy; a.dy.ld = d->Cout; a.dy.Hs = g.Hout; a.dy.Ws = g.Wout; a.dy.C = rup(d->Cout, 8); a.dy.Cpad = a.dy.C;
+  a.dy.mode = G_PLAIN; a.dy.istride = g.ostride; a.dy.ntaps = 1; a.dy.nchunks = 1;
+  a.dy.taps[0] = (short)((g.phase_xy[ph].first & 0xff) | ((g.phase_xy[ph].second & 0xff) << 8));
+  set_eff_grad(a.dy, yfwd, d->Cout, q, r, zeros);
+  a.N = d->Cout; a.Npad = pack.Npad;
+  a.dpack = (float*)pack.dpack;
 }
 
 // the dgrad-shaped pack of a convolution: [chunks over (tap, output channel)][Npad input channels][BK]
@@ -1514,18 +1581,61 @@ int dmm_conv_wgrad_ex(const dmm_conv_desc* d, const void* x, const void* dy, con
   HIPCHK(hipStreamSynchronize(st));
   for (size_t ph = 0; ph < packs.size(); ++ph) {
     WgradArgs a;
-    memset(&a, 0, sizeof(a));
-    a.nseg = 1;
-    fill_one_seg(a.seg[0], d, g, x, scale, shift, g.phase_taps[ph]);
-    a.B = d->B; a.Ho = g.Ho; a.Wo = g.Wo; a.M = d->B * g.Ho * g.Wo;
-    a.dy.src = dy; a.dy.ld = d->Cout; a.dy.Hs = g.Hout; a.dy.Ws = g.Wout; a.dy.C = rup(d->Cout, 8); a.dy.Cpad = a.dy.C;
-    a.dy.mode = G_PLAIN; a.dy.istride = g.ostride; a.dy.ntaps = 1; a.dy.nchunks = 1;
-    a.dy.taps[0] = (short)((g.phase_xy[ph].first & 0xff) | ((g.phase_xy[ph].second & 0xff) << 8));
-    set_eff_grad(a.dy, yfwd, d->Cout, q, r, zeros);
-    a.N = d->Cout; a.Npad = packs[ph].Npad;
-    a.dpack = (float*)packs[ph].dpack;
+    fill_wgrad_phase(a, d, g, x, dy, scale, shift, yfwd, q, r, zeros, packs[ph], ph);
     HIPCHK(launch_wgrad(a, d->dtype, d->use_mfma != 0, st, IMPL_AUTO, g_family_off));
   }
+  HIPCHK(hipMemsetAsync(dw, 0, wn * sizeof(float), st));
+  HIPCHK(launch_unpack(dd, dp, (int)packs.size(), total_rows, d->dtype, 1.0f, st));
+  return DMM_OK;
+}
+
+// A ConvTranspose weight gradient (normal form) as the plan runs it (plan.cpp emit_wgrad_phases): the four per-phase records of
+// dmm_conv_wgrad_ex, each picked, then merged into ONE launch by the plan's own eligibility / copy / accept functions (plan.h) - or,
+// where those keep the phases apart (the deferred correction: mixed tap counts are wgpw.hip's, which takes the materialised gradient
+// only), the four launches.  *launches: 1 or 4.
+int dmm_conv_wgrad_merged(const dmm_conv_desc* d, const void* x, const void* dy, const float* scale, const float* shift, const void* yfwd,
+                          const float* q, const float* r, float* dw, void* scratch, void* stream, int* launches) {
+  const std::string who = "dmm_conv_wgrad_merged: ";
+  if (!d || !x || !dy || !dw || !scratch || !launches) return fail(DMM_ERR_INVALID, who + "null argument");
+  if (!d->transposed) return fail(DMM_ERR_INVALID, who + "the merged launch is a ConvTranspose's (transposed = 1)");
+  if (d->bn_relu && (!scale || !shift)) return fail(DMM_ERR_INVALID, who + "bn_relu needs scale and shift");
+  if ((q != nullptr) != (r != nullptr) || (q != nullptr) != (yfwd != nullptr)) return fail(DMM_ERR_INVALID, who + "q, r and yfwd come together");
+  OneConv g;
+  if (!geometry(d, g) || g.phase_taps.size() != 4) return fail(DMM_ERR_INVALID, who + "unsupported conv descriptor");
+  hipStream_t st = (hipStream_t)stream;
+  const bool mfma = d->use_mfma != 0;
+  const unsigned deny = g_family_off;
+  const size_t wn = (size_t)d->Cin * d->Cout * d->R * d->S;
+  std::vector<PackDesc> packs;
+  std::vector<int> prefix;
+  PackDesc* dd; int* dp; int total_rows;
+  const size_t used = layout_fwd(d, g, (uint8_t*)scratch, dw /*unused as w*/, dw, packs, &dd, &dp, prefix, total_rows);
+  Scratch S{(uint8_t*)scratch, used};
+  float* zeros = (float*)S.take((size_t)rup(d->Cout, 8) * sizeof(float) + 64);
+  if (S.off > dmm_conv_scratch_bytes(d)) return fail(DMM_ERR_INVALID, who + "scratch too small");
+  HIPCHK(hipMemsetAsync(scratch, 0, S.off, st));
+  HIPCHK(upload(dd, packs.data(), packs.size() * sizeof(PackDesc), st));
+  HIPCHK(upload(dp, prefix.data(), prefix.size() * sizeof(int), st));
+  HIPCHK(hipStreamSynchronize(st));
+  WgradArgs a[4];
+  int impl[4];
+  bool merge = true;
+  for (int ph = 0; ph < 4; ++ph) {
+    fill_wgrad_phase(a[ph], d, g, x, dy, scale, shift, yfwd, q, r, zeros, packs[ph], ph);
+    impl[ph] = wgrad_pick(a[ph], d->dtype, mfma, deny);
+    merge = merge && wgrad_phase_eligible(a[ph], impl[ph], a[0]);
+  }
+  WgradArgs m = a[0];
+  if (merge) {
+    for (int ph = 0; ph < 4; ++ph) copy_wgrad_phase(m, a[ph], ph);
+    merge = accept_wgrad_merged(m, d->dtype, mfma, deny);
+  }
+  if (merge) {
+    HIPCHK(launch_wgrad(m, d->dtype, mfma, st, IMPL_WGP));
+  } else {
+    for (int ph = 0; ph < 4; ++ph) HIPCHK(launch_wgrad(a[ph], d->dtype, mfma, st, impl[ph]));
+  }
+  *launches = merge ? 1 : 4;
   HIPCHK(hipMemsetAsync(dw, 0, wn * sizeof(float), st));
   HIPCHK(launch_unpack(dd, dp, (int)packs.size(), total_rows, d->dtype, 1.0f, st));
   return DMM_OK;

@@ -73,8 +73,16 @@ template <typename V>
 __device__ __forceinline__ void cw_hold_b(V (&rb)[CW_NB]) { DMM_VM_HOLD(DMM_V4(rb)); }
 
 // One phase's share of the launch for this workgroup: items first, first + stride, ... < P.per of a phase with NTAP taps.
+// gcount: the channel groups this workgroup has walked since the kernel began - the halo image of a group is gcount & 1, ACROSS the
+// phases of a merged launch.  Nothing but the double buffering orders a walk's first halo store behind the last fragment reads of
+// the walk in front of it (the loaders pass that walk's last barrier together with the matrix waves and run ahead): a count that began
+// at 0 in every walk put the first halo of a phase into image 0 while the matrix waves could still be reading image 0 for the last
+// stage of the previous phase whenever that phase had an odd number of groups - rare wrong tiles in the four-phase launch of the
+// 128-channel stage (tests/test_merged_phase_kernels_gpu.py, 3x85x125).  The weight ring needs no such care: a walk ends in slot 1
+// (NST is even) and the next one begins in slot 0.
 template <typename T, int NTAP>
-__device__ __forceinline__ void cw_walk(const CvwArgs& g, const CwPhase& P, const int first, const int stride, double (&dsum)[2], int& stat_ntile) {
+__device__ __forceinline__ void cw_walk(const CvwArgs& g, const CwPhase& P, const int first, const int stride, double (&dsum)[2], int& stat_ntile,
+                                        int& gcount) {
   typedef typename TT<T>::vec V;
   constexpr int SLOT = 8;
   constexpr int NST = 2 * NTAP;   // weight stages per channel group
@@ -187,7 +195,6 @@ __device__ __forceinline__ void cw_walk(const CvwArgs& g, const CwPhase& P, cons
     okx_cur = okx_next;
 #pragma unroll
     for (int st = 0; st < R; ++st) issue_b(rb[st]);
-    int gcount = 0;   // groups done: halo buffer = gcount & 1
     for (int k = 0; k < nitems; ++k) {
       for (int grp = 0; grp < ngrp; ++grp, ++gcount) {
 #pragma unroll
@@ -231,7 +238,6 @@ __device__ __forceinline__ void cw_walk(const CvwArgs& g, const CwPhase& P, cons
   const int boff = (64 * wc + r) * 64;
   unsigned char* stg = smem + CW_OFF_S + wave * CW_STAGE_W;
   T* out = (T*)a.out;
-  int gcount = 0;
   for (int k = 0; k < nitems; ++k) {
     const int idx = first + k * stride;
     const int ntile = idx % g.ntn;
@@ -329,6 +335,7 @@ template <typename T>
 __global__ __launch_bounds__(CW_NT, 1) void cvw_kernel(const CvwArgs g) {
   double dsum[2] = {0.0, 0.0};
   int stat_ntile = -1;
+  int gcount = 0;   // channel groups walked so far, by every wave alike: the halo image of the next group is gcount & 1 (cw_walk)
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   {  // the norm's scale | shift tables of all input channels: to LDS once (the loaders read them per channel group)
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -346,9 +353,9 @@ __global__ __launch_bounds__(CW_NT, 1) void cvw_kernel(const CvwArgs g) {
     // the stream of (phase, item) pairs is dealt round-robin: this workgroup's first item of phase p
     const int done = p * g.per;                                   // items of the phases in front
     const int first = (int)(((long)blockIdx.x - done % (int)gridDim.x + (long)gridDim.x * 2) % gridDim.x);
-    if (P.ntaps == 4) cw_walk<T, 4>(g, P, first, gridDim.x, dsum, stat_ntile);
-    else if (P.ntaps == 2) cw_walk<T, 2>(g, P, first, gridDim.x, dsum, stat_ntile);
-    else cw_walk<T, 1>(g, P, first, gridDim.x, dsum, stat_ntile);
+    if (P.ntaps == 4) cw_walk<T, 4>(g, P, first, gridDim.x, dsum, stat_ntile, gcount);
+    else if (P.ntaps == 2) cw_walk<T, 2>(g, P, first, gridDim.x, dsum, stat_ntile, gcount);
+    else cw_walk<T, 1>(g, P, first, gridDim.x, dsum, stat_ntile, gcount);
     // BatchNorm sums of the last column tile of this phase (the next phase starts at column tile 0 again; all phases write the same channels)
     if (wave < 4 && g.c.stat_sum != nullptr && stat_ntile >= 0) {
       const int r = lane & 31, h = lane >> 5, wc = wave & 1;

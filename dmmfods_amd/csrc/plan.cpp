@@ -634,12 +634,6 @@ struct Builder {
     ops->resize(first);
     ops->push_back(merged);
   }
-  static void copy_fwd_phase(ConvArgs& m, const ConvArgs& po, int ph, int ntaps0) {  // what every merged forward launch carries per phase
-    m.nphase = 4;
-    for (int t = 0; t < 4; ++t) m.ph_taps0[ph][t] = po.seg[0].taps[t < ntaps0 ? t : 0];
-    m.ph_wpack[ph] = po.wpack;
-    m.ph_py[ph] = (signed char)po.py; m.ph_px[ph] = (signed char)po.px;
-  }
 
   void emit_conv_fwd(ConvRec& c) {
     for (int s = 0; s < c.nseg; ++s) {
@@ -695,15 +689,9 @@ struct Builder {
     // rounds.  One launch deals the 2400 (4800) workgroups of all phases, the 4-tap phase first, and the slots stay full.
     if (c.nseg == 1 && c.transposed && !P.sw.no_cvp_merge)
       merge_last_four_phases(
-          [](const Op& po, const Op& f) {
-            return po.kind == OP_IGEMM && po.epi == EPI_STORE && po.impl == IMPL_CVP && po.c.nseg == 1 && po.c.seg[0].ntaps <= 4 && po.c.nphase == 0 &&
-                   po.c.out == f.c.out && po.c.seg[0].src == f.c.seg[0].src;
-          },
-          [](Op& m, const Op& po, int ph) {
-            copy_fwd_phase(m.c, po.c, ph, po.c.seg[0].ntaps);
-            m.c.ph_ntaps[ph] = (signed char)po.c.seg[0].ntaps;
-          },
-          [&](Op& m) { return igemm_pick(m.c, dtype, EPI_STORE, mfma, deny) == IMPL_CVP; });
+          [](const Op& po, const Op& f) { return po.kind == OP_IGEMM && convT_fwd_phase_eligible(po.c, po.epi, po.impl, f.c); },
+          [](Op& m, const Op& po, int ph) { copy_convT_fwd_phase(m.c, po.c, ph); },
+          [&](Op& m) { return accept_convT_fwd_merged(m.c, dtype, mfma, deny); });
   }
 
   void fill_grad_seg(Seg& s, int buf, int ch0, int C, const std::vector<Tap>& taps, int istride) {
@@ -893,24 +881,9 @@ struct Builder {
     // kernel, wgpw.hip, takes the phase's tap count per workgroup).
     if (c.phases.size() == 4 && wseg == 1 && !P.sw.no_wgp_merge)
       merge_last_four_phases(
-          [](const Op& po, const Op& f) {
-            const int nt = po.w.seg[0].ntaps;
-            return po.kind == OP_WGRAD && po.impl == IMPL_WGP && po.w.nseg == 1 && (nt == 1 || nt == 2 || nt == 4) && po.w.seg[0].src == f.w.seg[0].src &&
-                   po.w.dy.src == f.w.dy.src;
-          },
-          [](Op& m, const Op& po, int ph) {
-            m.w.nphase = 4;
-            for (int t = 0; t < 4; ++t) m.w.ph_xtaps[ph][t] = po.w.seg[0].taps[t < po.w.seg[0].ntaps ? t : 0];
-            m.w.ph_ntaps[ph] = (signed char)po.w.seg[0].ntaps;
-            m.w.ph_ytap[ph] = po.w.dy.taps[0];
-            m.w.ph_dpack[ph] = po.w.dpack;
-          },
-          [&](Op& m) {
-            bool all4 = true;   // four taps in every phase: ph_ntaps stays 0 (= seg[0].ntaps each)
-            for (int ph = 0; ph < 4; ++ph) all4 = all4 && m.w.ph_ntaps[ph] == 4;
-            if (all4) m.w.ph_ntaps[0] = m.w.ph_ntaps[1] = m.w.ph_ntaps[2] = m.w.ph_ntaps[3] = 0;
-            return wgrad_pick(m.w, dtype, d.use_mfma != 0, deny) == IMPL_WGP;
-          });
+          [](const Op& po, const Op& f) { return po.kind == OP_WGRAD && wgrad_phase_eligible(po.w, po.impl, f.w); },
+          [](Op& m, const Op& po, int ph) { copy_wgrad_phase(m.w, po.w, ph); },
+          [&](Op& m) { return accept_wgrad_merged(m.w, dtype, d.use_mfma != 0, deny); });
   }
 
   // The head's first convolution (two segments, four output-parity phases): the phase split exists for the upsampled decoder

@@ -37,6 +37,49 @@ std::vector<Tap> taps_conv_phase_s2(int e, int f);            // 3x3 p1 conv sam
 void fill_seg_taps(Seg& s, const std::vector<Tap>& taps, int BK);
 void fill_pack_seg(PackSeg& p, const std::vector<Tap>& taps, int Creal, int Cpad, int koff, int BK);
 
+// The four output-parity phases of a ConvTranspose stage as ONE launch: what the plan builder's merge (plan.cpp:
+// merge_last_four_phases) decides and copies for the forward (cvp.hip / cvw.hip) and for the weight gradient (wgpw.hip), as free
+// functions of the launches' argument records - shared with the entry points that build the same merged launch outside a plan
+// (capi.cpp: dmm_conv_forward_merged, dmm_conv_wgrad_merged), so that those hold the launch the plan builds and not a restatement of it.
+//   *_phase_eligible(record, family picked for it, record of the first phase)   may this per-phase launch join the merge?
+//   copy_*_phase(merged, record, ph)                                             what differs between the phases -> the merged record's ph_*
+//   accept_*_merged(merged, ...)                                                 does the pick still take the merged record?  (it refuses
+//                                                                                e.g. operands of 4 GiB and more: the four launches stay)
+inline bool convT_fwd_phase_eligible(const ConvArgs& po, int epi, int impl, const ConvArgs& first) {
+  return epi == EPI_STORE && impl == IMPL_CVP && po.nseg == 1 && po.seg[0].ntaps <= 4 && po.nphase == 0 && po.out == first.out &&
+         po.seg[0].src == first.seg[0].src;
+}
+inline void copy_fwd_phase(ConvArgs& m, const ConvArgs& po, int ph, int ntaps0) {  // what every merged forward launch carries per phase
+  m.nphase = 4;
+  for (int t = 0; t < 4; ++t) m.ph_taps0[ph][t] = po.seg[0].taps[t < ntaps0 ? t : 0];
+  m.ph_wpack[ph] = po.wpack;
+  m.ph_py[ph] = (signed char)po.py; m.ph_px[ph] = (signed char)po.px;
+}
+inline void copy_convT_fwd_phase(ConvArgs& m, const ConvArgs& po, int ph) {
+  copy_fwd_phase(m, po, ph, po.seg[0].ntaps);
+  m.ph_ntaps[ph] = (signed char)po.seg[0].ntaps;
+}
+inline bool accept_convT_fwd_merged(const ConvArgs& m, int dtype, bool mfma, unsigned deny) {
+  return igemm_pick(m, dtype, EPI_STORE, mfma, deny) == IMPL_CVP;
+}
+inline bool wgrad_phase_eligible(const WgradArgs& po, int impl, const WgradArgs& first) {
+  const int nt = po.seg[0].ntaps;
+  return impl == IMPL_WGP && po.nseg == 1 && (nt == 1 || nt == 2 || nt == 4) && po.seg[0].src == first.seg[0].src && po.dy.src == first.dy.src;
+}
+inline void copy_wgrad_phase(WgradArgs& m, const WgradArgs& po, int ph) {
+  m.nphase = 4;
+  for (int t = 0; t < 4; ++t) m.ph_xtaps[ph][t] = po.seg[0].taps[t < po.seg[0].ntaps ? t : 0];
+  m.ph_ntaps[ph] = (signed char)po.seg[0].ntaps;
+  m.ph_ytap[ph] = po.dy.taps[0];
+  m.ph_dpack[ph] = po.dpack;
+}
+inline bool accept_wgrad_merged(WgradArgs& m, int dtype, bool mfma, unsigned deny) {
+  bool all4 = true;   // four taps in every phase: ph_ntaps stays 0 (= seg[0].ntaps each)
+  for (int ph = 0; ph < 4; ++ph) all4 = all4 && m.ph_ntaps[ph] == 4;
+  if (all4) m.ph_ntaps[0] = m.ph_ntaps[1] = m.ph_ntaps[2] = m.ph_ntaps[3] = 0;
+  return wgrad_pick(m, dtype, mfma, deny) == IMPL_WGP;
+}
+
 enum OpKind { OP_MEMSET = 0, OP_CONVERT, OP_IGEMM, OP_WGRAD, OP_BNFIN, OP_BNBWD, OP_POOL, OP_POOLBWD, OP_BCE, OP_PACK, OP_UNPACK,
               OP_COPY, OP_APPLYCORR, OP_BW1, OP_JOIN, OP_BW1RED, OP_RAWFIN, OP_FIN64 };
 

@@ -460,6 +460,18 @@ int dmm_conv_wgrad_ex(const dmm_conv_desc* d, const void* x, const void* dy, con
 int dmm_conv_dgrad_ex(const dmm_conv_desc* d, const void* x, const void* dy, const float* w, const float* scale, const float* shift,
                       const void* yfwd, const float* q, const float* r, void* gx, int accumulate, double* red, void* scratch,
                       void* stream);
+/* A decoder ConvTranspose stage (reference graphs/models/Dense_U_Net_lidar.py:155-160) as a PLAN launches it: the four output-parity
+ * phases that dmm_conv_forward / dmm_conv_wgrad_ex launch one by one are each picked and then merged into ONE launch by the plan
+ * builder's own functions (csrc/plan.h) - cvp.hip's cvp_multi_kernel or cvw.hip's four-phase walk for the forward, wgpw.hip's
+ * wgpw_multi_kernel for the weight gradient - where those accept the merge; where they keep the phases apart (a phase on another
+ * family, the deferred correction q / r on the gradient, operands of 4 GiB and more) the four launches run, each on the family picked
+ * for it.  *launches: 1 or 4.  Arguments and results otherwise as dmm_conv_forward / dmm_conv_wgrad_ex (normal form).
+ * DMM_ERR_INVALID, before the runtime is asked anything, for transposed == 0, a null pointer (stats may be NULL), and q, r, yfwd
+ * not given together. */
+int dmm_conv_forward_merged(const dmm_conv_desc* d, const void* x, const float* w, const float* scale, const float* shift, void* y,
+                            double* stats, void* scratch, void* stream, int* launches);
+int dmm_conv_wgrad_merged(const dmm_conv_desc* d, const void* x, const void* dy, const float* scale, const float* shift, const void* yfwd,
+                          const float* q, const float* r, float* dw, void* scratch, void* stream, int* launches);
 /* The head's last convolution (5x5, 64 channels onto <= 4 classes behind BatchNorm2d + ReLU; reference
  * graphs/models/Dense_U_Net_lidar.py:128-131), 16-bit storage: its weight gradient AND the BatchNorm-backward reductions of the norm
  * in front of it - red[0..64) = sum dz, red[64..128) = sum dz*xhat over all pixels, dz = relu'(x*scale+shift) * conv_dgrad(dy) with

@@ -21,8 +21,11 @@ The cases use 128 (512 where noted), the upper bound of all of these.
 
 Not here: hf.hip - no single-kernel entry point builds its launch, and hf is held bit-equal to conv3 inside a plan
 (tests/test_timed_kernels_gpu.py); the logits launch (thin.hip, halo.logits, igemm.logits), which has a file of its own:
-tests/test_logits_kernels_gpu.py; cvd_kernel, reachable only through lab flags; cvp_multi_kernel and cvw's four-phase walk, which
-only a plan's launch with ConvArgs::nphase = 4 reaches (dmm_conv_forward launches each output parity on its own).
+tests/test_logits_kernels_gpu.py; cvp_multi_kernel, cvw's four-phase walk and wgpw_multi_kernel - the ConvTranspose stages as ONE
+launch of four output-parity phases, which dmm_conv_forward and dmm_conv_wgrad_ex never build (they launch each parity on its own) -
+which have a file of their own: tests/test_merged_phase_kernels_gpu.py.  What still has none is the head: hf.hip, conv3.hip's
+MULTI form and wgp.hip's own multi-phase path with four taps per phase (all need the head's two-segment launch), and cvd_kernel, the
+lab fallback of cvd3 that only lab flags reach.
 
 Where this file departs from the shapes first proposed for it, after reading the launchers:
   * dmm_conv_forward pads the output columns to a multiple of 32 only, and pig / cvp / cvw refuse Npad % 128 != 0: no case with a

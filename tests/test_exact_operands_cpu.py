@@ -90,6 +90,58 @@ def test_generic_fp32_cases(case):
     assert ("c_red1" in fig) == bool(bn and not strided)     # as conv_case: no BN-fused data gradient without BN or at stride 2
 
 
+# ------------------------------------------------------------------------------------------------ tests/test_merged_phase_kernels_gpu.py
+MERGED_FWD = [(f, c) for f, c, _ in E.FORWARD_MERGED] + [("generic", E.FORWARD_APART)]
+
+
+@pytest.mark.parametrize("dtype", DT, ids=DT_IDS)
+@pytest.mark.parametrize("case", range(len(MERGED_FWD)), ids=[f"{f}-{c[0].replace(' ', '_')}" for f, c in MERGED_FWD])
+def test_merged_forward_cases(case, dtype):
+    """The merged forward cases and the one kept apart, with the default value ranges (no shape needed narrower ones)."""
+    family, c = MERGED_FWD[case]
+    o = E.make_operands(dtype, *c[1:], parts=("fwd",))
+    fig = _holds(o)
+    assert {"b_y", "c_sum", "c_sq"} <= set(fig) and c[10] == 1
+    assert torch.equal(o.stat_sum, o.y.sum(dim=(0, 2, 3))) and bool((o.stat_sum != 0).all()) and bool((o.stat_sq != 0).all())
+    # every output parity carries outputs: a phase left out, or written to another parity, is seen
+    for py in (0, 1):
+        for px in (0, 1):
+            assert float((o.y[:, :, py::2, px::2] != 0).double().mean()) > 0.5, (py, px)
+
+
+@pytest.mark.parametrize("dtype", DT, ids=DT_IDS)
+@pytest.mark.parametrize("case", range(len(E.BACKWARD_MERGED) + 1),
+                         ids=["{3}to{4}-{0}x{1}x{2}-q0".format(*s) for s, _ in E.BACKWARD_MERGED] + ["{3}to{4}-{0}x{1}x{2}-q1".format(*E.BACKWARD_APART)])
+def test_merged_weight_gradient_cases(case, dtype):
+    with_q = int(case == len(E.BACKWARD_MERGED))
+    B, H, W, Cin, Cout = E.BACKWARD_APART if with_q else E.BACKWARD_MERGED[case][0]
+    o = E.make_operands(dtype, B, H, W, Cin, Cout, 3, 3, 2, 1, transposed=1, bn=1, with_q=with_q, acc=0, parts=("wgrad",))
+    fig = _holds(o)
+    assert "b_dw" in fig and (not with_q or bool((o.eff != o.dy).any()))
+    # every tap's gradient is there (the taps belong to different phases: 1, 2, 2 and 4 of the 9)
+    for t in range(9):
+        assert float((o.dw[:, :, t // 3, t % 3] != 0).double().mean()) > 0.9, t
+
+
+def test_merged_launcher_arithmetic_on_256_compute_units():
+    """What each merged case is there for, from the launchers' formulas (tools/exact_operands.py merged_*_geometry) - for the MI355X's
+    256 compute units where the launcher asks the device; the GPU test recomputes it for the device at hand."""
+    g = [E.merged_fwd_geometry(f, *c[1:6]) for f, c, _ in E.FORWARD_MERGED]
+    assert (g[0]["per"], g[0]["nwg"], g[0]["done_mod"]) == (2, 8, [0, 2, 4, 6])
+    assert (g[1]["per"], g[1]["nwg"], g[1]["done_mod"]) == (264, 256, [0, 8, 16, 24])
+    assert (g[2]["per"], g[2]["nwg"], g[2]["groups"], g[2]["ntn"]) == (288, 256, 2, 2)
+    assert (g[3]["per"], g[3]["per8"], g[3]["idle"]) == (8, 1, 0) and g[3]["groups"] == 3
+    assert (g[4]["per"], g[4]["per8"], g[4]["nwg"], g[4]["idle"]) == (12, 2, 64, 16)
+    for k in g[:3]:      # cvw: every (phase, item) pair is walked by exactly one workgroup
+        for p in range(4):
+            seen = sorted(i for b in range(k["nwg"]) for i in range(k["first"][p][b], k["per"], k["nwg"]))
+            assert seen == list(range(k["per"])), p
+            assert all((p * k["per"] + k["first"][p][b]) % k["nwg"] == b for b in range(k["nwg"]))
+    w = [E.merged_wgrad_geometry(*s, 256) for s, _ in E.BACKWARD_MERGED]
+    assert (w[0]["units"], w[0]["nwg"]) == (8, 32) and (w[1]["units"], w[1]["nwg"]) == (3, 32)
+    assert w[2] == dict(ntiles=25, pairs=4, nsplit=13, tiles_per_wg=2, units=52, nwg=224)
+
+
 def test_a_violation_is_caught():
     """check() is not vacuous: operands outside the recipe fail it."""
     c = E.CASES[0]

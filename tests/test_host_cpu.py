@@ -790,3 +790,30 @@ def test_fold_lane_algebra():
                 want[e * ncv + l % ncv] += s1[l, e]
                 want[(slot + e) * ncv + l % ncv] += s2[l, e]
         assert np.abs(red - want).max() < 1e-12, (ncv, slot)
+
+
+def test_merged_phase_entry_points_forms_and_refusals(host_drive):
+    """dmm_conv_forward_merged / dmm_conv_wgrad_merged under the fake runtime, for every shape tests/test_merged_phase_kernels_gpu.py
+    launches: the four output-parity phases of a ConvTranspose become ONE launch (two launches with the pack / unpack) on the form the
+    case names - cvw.hip for one or two channel groups, cvp.hip's own multi-phase kernel for three, wgpw.hip for the materialised
+    gradient - and stay four where the plan's merge keeps them apart: 64 input channels (the generic kernel), and the deferred
+    correction on the gradient (the one-tap phase on the generic kernel, the others on wgp.hip's own kernel, never wgpw).  What the entry
+    points refuse returns DMM_ERR_INVALID with nothing enqueued and no family noted."""
+    from tools import exact_operands as E
+    phases = lambda r: int(re.search(r" phases_as (\d+)", r["out"])[1])  # noqa: E731
+    for dt in ("f16", "bf16"):
+        for form, c, _ in E.FORWARD_MERGED:
+            r = _single(host_drive, "fwdm", dt, *c[1:6], 3, 1, transposed=1)
+            assert (r["rc"], r["last"], r["ran"], phases(r)) == (0, "cvp", {"cvp", "cvw"} if form == "cvw" else {"cvp"}, 1) and " launches 2 " in r["out"], (c, r)
+        r = _single(host_drive, "fwdm", dt, *E.FORWARD_APART[1:6], 3, 1, transposed=1)
+        assert (r["rc"], r["ran"], phases(r)) == (0, {"generic"}, 4) and " launches 5 " in r["out"], r
+        for s, _ in E.BACKWARD_MERGED:
+            r = _single(host_drive, "wgradm", dt, *s, 3, 1, transposed=1)
+            assert (r["rc"], r["last"], r["ran"], phases(r)) == (0, "wgp", {"wgp", "wgpw"}, 1) and " launches 2 " in r["out"], (s, r)
+        r = _single(host_drive, "wgradm", dt, *E.BACKWARD_APART, 3, 1, transposed=1, flags="withq")
+        assert (r["rc"], r["ran"], phases(r)) == (0, {"generic", "wgp"}, 4) and " launches 5 " in r["out"], r
+    s = E.BACKWARD_APART
+    for entry, kw in (("fwdm", dict(transposed=0)), ("fwdm", dict(transposed=1, flags="nullx")), ("fwdm", dict(transposed=1, flags="nullcount")),
+                      ("wgradm", dict(transposed=0)), ("wgradm", dict(transposed=1, flags="nulldy")), ("wgradm", dict(transposed=1, flags="qonly"))):
+        r = _single(host_drive, entry, "f16", *s, 3, 1, **kw)
+        assert r["rc"] == -1 and r["ran"] == {"none"} and " launches 0 " in r["out"] and phases(r) == 0 and "_merged: " in r["out"], (entry, kw, r)

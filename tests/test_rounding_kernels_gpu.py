@@ -19,8 +19,9 @@ on the reference before anything is launched (Operands.check_rounding) and, with
 tests/test_rounding_operands_cpu.py.  Every case asserts the kernel family that ran: a fallback to the generic kernel fails it.
 Rounding needs no multi-tile walk, so the shapes are the smallest each family's resolve accepts (cf: at least eight tiles per CU).
 
-Not here, as in tests/test_exact_kernels_gpu.py: the launches only a plan builds (hf, cvp_multi_kernel, cvw's four-phase walk,
-wgpw_multi_kernel); the logits launch, whose rounding cases are in tests/test_logits_kernels_gpu.py; fp32 storage, whose stores do not round; bf16 on the scalar kernels, which the library does not have; the
+Not here, as in tests/test_exact_kernels_gpu.py: cvp_multi_kernel, cvw's four-phase walk and wgpw_multi_kernel, whose single-rounding
+cases are in tests/test_merged_phase_kernels_gpu.py; the head's launches, which still have no file (hf, conv3's MULTI form, wgp.hip's
+own multi-phase path with four taps per phase: no entry point builds a two-segment launch) and cvd_kernel, the lab fallback; the logits launch, whose rounding cases are in tests/test_logits_kernels_gpu.py; fp32 storage, whose stores do not round; bf16 on the scalar kernels, which the library does not have; the
 effective-gradient prologue on cvd3 and on wg5's transposed form, which their resolves refuse."""
 import pytest
 import torch

@@ -88,6 +88,24 @@ def test_backward_cases(case, with_q, acc, dtype):
 
 
 @pytest.mark.parametrize("dtype", DT, ids=DT_IDS)
+def test_merged_phase_cases(dtype):
+    """The merged four-phase launches of tests/test_merged_phase_kernels_gpu.py: one cvw, one cvp_multi and one wgpw_multi case."""
+    for family, c, kw in E.ROUND_FORWARD_MERGED:
+        o = E.make_rounding_operands(dtype, *c[1:], parts=("fwd",), **kw)
+        fig, sh = _holds(o, f"merged {family} {c[0]} dt={dtype}")
+        assert c[10] == 1 and "y" in sh and "a" in sh and "b_sum" in fig
+        _main_shares(o, sh)
+        for py in (0, 1):       # every output parity has stores that need the rounding
+            for px in (0, 1):
+                assert float((o.y[:, :, py::2, px::2] != o.y_pre[:, :, py::2, px::2]).double().mean()) > 0.1, (py, px)
+    for B, H, W, Cin, Cout in E.ROUND_BACKWARD_MERGED:
+        o = E.make_rounding_operands(dtype, B, H, W, Cin, Cout, 3, 3, 2, 1, transposed=1, bn=1, with_q=0, acc=0, parts=("wgrad",))
+        fig, sh = _holds(o, f"merged wgpw {Cin}->{Cout} {B}x{H}x{W} dt={dtype}")
+        _main_shares(o, sh)
+        assert "a" in sh and float((o.dw != 0).double().mean()) > 0.9 and bool((o.dw_bound >= 0).all())
+
+
+@pytest.mark.parametrize("dtype", DT, ids=DT_IDS)
 def test_conv5_case(dtype):
     """The factor form never forms the activation (round_a=False): its weight gradient is that of the UNROUNDED activation, which is
     another tensor than the one the other weight-gradient kernels must produce."""

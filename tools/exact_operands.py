@@ -287,6 +287,60 @@ BACKWARD = [
     ("wgradT", "wg5", (1, 13, 21, 64, 3, 5, 5, 2, 0, 0), [(0, 0)]),
     ("wgrad", "wg5", (2, 24, 40, 8, 64, 3, 3, 1, 0, 0), [(1, 0)]),                     # the 3x3 over the normalised raw input
 ]
+# ------------------------------------------------------------------------------------------------ the cases of tests/test_merged_phase_kernels_gpu.py
+# A decoder ConvTranspose stage as a plan launches it: the four output-parity phases in ONE launch (dmm_conv_forward_merged,
+# dmm_conv_wgrad_merged).  The shapes are the smallest at which each path of the merged kernels can still go wrong; the launcher
+# arithmetic behind each "why" is recomputed by the test (merged_fwd_geometry / merged_wgrad_geometry below).
+# forward: the form that must run ("cvw": cvw.hip's four-phase walk, "cvp": cvp_multi_kernel), case tuple as CASES, why
+FORWARD_MERGED = [
+    ("cvw", ("convT 128->128 2x7x9", 2, 7, 9, 128, 128, 3, 3, 2, 1, 1, 0, 1), "2 items per phase on 8 workgroups: `first` with done = 2, 4, 6, fewer items than workgroups"),
+    ("cvw", FORWARD[7][1], "264 items per phase, 1056 on 256 workgroups: done % 256 = 8, 16, 24; ragged in both directions"),
+    ("cvw", FORWARD[8][1], "288 items per phase, two channel groups, two column tiles: the statistics of the last column tile at every phase end"),
+    ("cvp", FORWARD[9][1], "per = 8, per8 = 1"),
+    ("cvp", ("convT 384->256 1x11x35", 1, 11, 35, 384, 256, 3, 3, 2, 1, 1, 0, 1), "per = 12, per8 = 2: workgroups with xcd * 2 + j >= 12 exit without a store"),
+]
+# weight gradient on wgpw_multi_kernel, the materialised gradient (with_q = 0): (B, H, W, Cin, Cout), why
+BACKWARD_MERGED = [
+    ((2, 12, 20, 128, 64), "8 units, none idle"),
+    ((3, 5, 3, 128, 64), "3 units rounded to 8: 5 idle units in each of the 4 phases"),
+    ((1, 37, 70, 256, 128), "25 tiles, 4 (ci, co) pairs: more than one tile per workgroup with a short last walk, units no multiple of 8"),
+]
+# kept apart - four launches, still exact: the forward with 64 input channels (cvp refuses: the generic kernel), the weight gradient
+# under the deferred correction (mixed tap counts in one launch are wgpw.hip's, which takes the materialised gradient only)
+FORWARD_APART = ("convT 64->64 2x6x10", 2, 6, 10, 64, 64, 3, 3, 2, 1, 1, 0, 1)
+BACKWARD_APART = (2, 12, 20, 128, 64)
+FORWARD_MERGED_REPRO, BACKWARD_MERGED_REPRO = 1, 2        # run twice, equal bit for bit: indices into FORWARD_MERGED / BACKWARD_MERGED
+CW_TILE, CW_BN, WP_TILE, DESIGN_CUS = (8, 16), 128, (8, 16), 256
+
+
+def merged_fwd_geometry(form, B, H, W, Cin, Cout):
+    """cvw.hip cvw_resolve / cvp.hip cvp_resolve for a merged forward launch: items per phase, workgroups, and for cvw the first item
+    of every workgroup in every phase (cvw_kernel), for cvp the workgroups that exit at once (cvp_multi_kernel)."""
+    cd = lambda a, b: -(-a // b)  # noqa: E731
+    per = B * cd(H, CW_TILE[0]) * cd(W, CW_TILE[1]) * (Cout // CW_BN)
+    g = dict(groups=Cin // 128, ntn=Cout // CW_BN, per=per)
+    if form == "cvw":
+        nwg = min(DESIGN_CUS, 4 * per)
+        g.update(nwg=nwg, done_mod=[(p * per) % nwg for p in range(4)],
+                 first=[[(b - (p * per) % nwg + 2 * nwg) % nwg for b in range(nwg)] for p in range(4)])
+    else:
+        per8 = cd(per, 8)
+        g.update(per8=per8, nwg=8 * per8 * 4, idle=sum(1 for b in range(8 * per8 * 4) if (b & 7) * per8 + (b >> 3) % per8 >= per))
+    return g
+
+
+def merged_wgrad_geometry(B, H, W, Cin, Cout, cus):
+    """wgp.hip wgp_resolve / wgp_split for a merged weight-gradient launch (nphase = 4: 64 output channels per workgroup)."""
+    cd = lambda a, b: -(-a // b)  # noqa: E731
+    ntiles = B * cd(H, WP_TILE[0]) * cd(W, WP_TILE[1])
+    pairs = (Cin // 128) * (Cout // 64)
+    nsplit = min(max(1, cd(cus // 4, pairs)), ntiles)
+    tiles_per_wg = cd(ntiles, nsplit)
+    nsplit = cd(ntiles, tiles_per_wg)
+    units = nsplit * pairs
+    return dict(ntiles=ntiles, pairs=pairs, nsplit=nsplit, tiles_per_wg=tiles_per_wg, units=units, nwg=cd(units, 8) * 8 * 4)
+
+
 STEM_WGRAD = ("7x7s2 8->64 2x32x48", 2, 32, 48, 8, 64, 7, 7, 2, 3, 0, 0, 0)          # wg5 through conv_case (no BatchNorm in front)
 CONV5_STATS = (1, 13, 21)                                                             # conv5_stats_case: B, H, W
 
@@ -644,7 +698,11 @@ ROUND_BACKWARD = [
     ("wgradT", "wg5", (1, 13, 21, 64, 3, 5, 5, 2, 0, 0), [(0, 0)]),
     ("wgrad", "wg5", (2, 12, 20, 8, 64, 3, 3, 1, 0, 0), [(1, 0), (0, 0)]),
 ]
-ROUND_CONV5 = (1, 13, 21)            # conv5_stats_case: B, H, W (the factor correlations run over the workgroup's whole walk: chain_red = B H W)
+# the merged four-phase launches (tests/test_merged_phase_kernels_gpu.py) on the single-rounding operands: one per merged kernel, on
+# the smallest shape of FORWARD_MERGED / BACKWARD_MERGED it takes - form, case tuple, make_rounding_operands arguments (as ROUND_FORWARD)
+ROUND_FORWARD_MERGED = [("cvw",) + ROUND_FORWARD[6][1:], ("cvp",) + ROUND_FORWARD[7][1:]]
+ROUND_BACKWARD_MERGED = [BACKWARD_MERGED[1][0]]      # (3, 5, 3, 128, 64): idle units beside rounding stores
+ROUND_CONV5 = (1, 13, 21)          # conv5_stats_case: B, H, W (the factor correlations run over the workgroup's whole walk: chain_red = B H W)
 ROUND_PIG = ROUND_FORWARD[0][1]
 ROUND_GENERIC = CASES[0]             # 1x1 72->32 2x12x20: 32 output channels, which pig refuses
 ROUND_BW1 = ROUND_BACKWARD[0][2]

@@ -90,13 +90,19 @@ def _operands(exact, *args, **kw):
 
 
 def conv_case(name, dtype, mfma, B, H, W, Cin, Cout, R, S, stride, pad, transposed=0, mode=0, bn=1, seed=0, expect_wgrad=None,
-              expect_fwd=None, expect_dgrad=None, exact=False, parts=("fwd", "wgrad", "dgrad"), exact_kw=None):
+              expect_fwd=None, expect_dgrad=None, exact=False, parts=("fwd", "wgrad", "dgrad"), exact_kw=None, merged=False,
+              expect_launches=None, keep=None):
     """Forward (+ statistics), weight gradient and BN-fused data gradient of one convolution through the single-kernel entry points.
     expect_*: the kernel family that must have run that launch.  exact: operands of tools/exact_operands.py and an fp64 CPU reference;
     ok only if every compared tensor is equal bit for bit (parts: which of the three launches to run and compare; exact_kw: further arguments of make_operands).
     exact="round": the single-rounding operands (make_rounding_operands) - every tensor stored in the storage type, stat_sum and red1
-    equal bit for bit; stat_sq, red2 and a weight gradient that is not exact in fp32 within the bounds derived from the reference."""
+    equal bit for bit; stat_sq, red2 and a weight gradient that is not exact in fp32 within the bounds derived from the reference.
+    merged: the forward of a ConvTranspose as a plan launches it (dmm_conv_forward_merged: the four output-parity phases in ONE launch
+    where the plan's merge accepts them) - parts=("fwd",) only; the output and the statistics lie between guard bands of NaN, which
+    must still be NaN afterwards; expect_launches: what the entry point must report (1 merged, 4 kept apart); expect_fwd may then be
+    a set: exactly the families that must have noted the launch(es).  keep: a dict that receives output and statistics as read back."""
     dt = {0: torch.float32, 1: torch.float16, 2: torch.bfloat16}[dtype]
+    assert not merged or (transposed and exact and tuple(parts) == ("fwd",))
     if exact:
         o = _operands(exact, dtype, B, H, W, Cin, Cout, R, S, stride, pad, transposed=transposed, mode=mode, bn=bn,
                       parts=tuple(parts), seed=seed, **(exact_kw or {}))
@@ -141,7 +147,22 @@ def conv_case(name, dtype, mfma, B, H, W, Cin, Cout, R, S, stride, pad, transpos
     st = _lib.stream_ptr()
     res = {}
     fam_ok = True
-    if "fwd" in parts:
+    if "fwd" in parts and merged:
+        ny = B * y.shape[2] * y.shape[3] * Cout
+        ybuf = torch.full((ny + 2 * GUARD,), float("nan"), dtype=dt, device=DEV)
+        sbuf = torch.full((2 * Cout + 2 * GUARD,), float("nan"), dtype=torch.float64, device=DEV)
+        yd, stats = ybuf[GUARD:GUARD + ny].view(B, y.shape[2], y.shape[3], Cout), sbuf[GUARD:GUARD + 2 * Cout]
+        nl = C.c_int(-1)
+        _lib.impls_since_reset()
+        _lib.check(L.dmm_conv_forward_merged(C.byref(d), xd.data_ptr(), wd.data_ptr(), sd.data_ptr(), hd.data_ptr(), yd.data_ptr(),
+                                             stats.data_ptr(), scratch.data_ptr(), st, C.byref(nl)))
+        torch.cuda.synchronize()
+        fam_ok &= _check_merged(name + " fwd", expect_fwd, expect_launches, nl.value)
+        res["guard"] = _guard_hits(ybuf, ny) + _guard_hits(sbuf, 2 * Cout)
+        yo = nchw(yd).cpu()
+        if keep is not None:
+            keep.update(y=yd.cpu().clone(), stats=stats.cpu().clone(), launches=nl.value)
+    elif "fwd" in parts:
         yd = torch.full((B, y.shape[2], y.shape[3], Cout), float("nan"), dtype=dt, device=DEV)
         stats = torch.zeros(2 * Cout, dtype=torch.float64, device=DEV)
         _lib.impls_since_reset()
@@ -150,6 +171,7 @@ def conv_case(name, dtype, mfma, B, H, W, Cin, Cout, R, S, stride, pad, transpos
         torch.cuda.synchronize()
         fam_ok &= _check_family(name + " fwd", expect_fwd)
         yo = nchw(yd).cpu()
+    if "fwd" in parts:
         res["fwd"] = err(yo, y.detach())
         res["sum"] = err(stats[:Cout].cpu(), o.stat_sum if exact else yo.double().sum(dim=(0, 2, 3)))
         if rnd:
@@ -201,6 +223,23 @@ def conv_case(name, dtype, mfma, B, H, W, Cin, Cout, R, S, stride, pad, transpos
 
 
 LOGITS_GUARD = 4096   # floats of NaN on either side of the logits tensor
+GUARD = 4096          # elements of NaN on either side of an output of the merged-phase cases
+
+
+def _guard_hits(buf, n):
+    """Elements of the two guard bands around buf[GUARD:GUARD + n] that are no longer NaN."""
+    host = buf.cpu()
+    return float(int((~torch.isnan(host[:GUARD])).sum()) + int((~torch.isnan(host[GUARD + n:])).sum()))
+
+
+def _check_merged(res_name, expect, expect_launches, launches):
+    """A *_merged entry point: the number of launches it reports, and the families that noted them - a name (must be among them, as
+    _check_family) or a set (must be exactly them)."""
+    ran = _lib.impls_since_reset()
+    ok = (expect_launches is None or launches == expect_launches) and (expect is None or (ran == expect if isinstance(expect, (set, frozenset)) else expect in ran))
+    if not ok:
+        print(f"FAIL {res_name}: expected {expect_launches} launch(es) on {expect!r}, got {launches} on {sorted(ran)}", flush=True)
+    return ok
 
 
 def logits_case(name, dtype, mfma, B, H, W, Cin, Cout, R, pad, exact=True, expect=None, exact_kw=None, seed=0, keep=None):
@@ -260,7 +299,7 @@ def _eff_setup(g, dt, B, Cout, Ho, Wo, with_q):
 
 
 def backward_case(name, dtype, B, H, W, Cin, Cout, R, S, pad, transposed=0, with_q=1, acc=0, what="dgrad", seed=0, ref_dev="cpu", mode=0,
-                  expect=None, exact=False, exact_kw=None):
+                  expect=None, exact=False, exact_kw=None, merged=False, expect_launches=None, keep=None):
     """The backward launches of the timed configuration, each through its C-ABI entry point against autograd of
     torch.nn.functional on the CPU (fp32 reference of the same op, 16-bit-rounded operands):
       what = "fused":  dmm_conv1x1_backward_fused (bw1.hip): data + weight gradient of a 1x1 bottleneck convolution
@@ -268,8 +307,11 @@ def backward_case(name, dtype, B, H, W, Cin, Cout, R, S, pad, transposed=0, with
              "wgradT": dmm_conv_wgrad_ex in the transposed form (wg3.hip for the dense 3x3)
              "wgrad":  dmm_conv_wgrad_ex, normal form, with the effective-gradient prologue (wgp.hip for ConvTranspose phases)
     exact: operands of tools/exact_operands.py, fp64 CPU reference, every compared tensor equal bit for bit.  exact="round": the
-    single-rounding operands, compared as in conv_case."""
+    single-rounding operands, compared as in conv_case.
+    merged (what="wgrad", a ConvTranspose): dmm_conv_wgrad_merged - the four parity phases as ONE launch where the plan's merge accepts
+    them; dw lies between guard bands of NaN; expect_launches / a set as expect / keep: as conv_case."""
     dt = {0: torch.float32, 1: torch.float16, 2: torch.bfloat16}[dtype]
+    assert not merged or (transposed and exact and what == "wgrad")
     rnd = exact == "round"
     bounded = set()
     if exact:
@@ -326,9 +368,15 @@ def backward_case(name, dtype, B, H, W, Cin, Cout, R, S, pad, transposed=0, with
     err = _ndiff if rnd else (_absdiff if exact else relerr)
     gxd = nhwc(gold.float(), dt).to(DEV) if acc else torch.full((B, H, W, Cin), float("nan"), dtype=dt, device=DEV)
     red = torch.zeros(2 * Cin, dtype=torch.float64, device=DEV)
-    dwd = torch.full(wshape, float("nan"), device=DEV)
+    nw = Cin * Cout * R * S
+    wbuf = torch.full((nw + 2 * GUARD,), float("nan"), device=DEV)
+    dwd = wbuf[GUARD:GUARD + nw].view(wshape)
+    nl = C.c_int(-1)
     _lib.impls_since_reset()
-    if what == "fused":
+    if merged:
+        _lib.check(L.dmm_conv_wgrad_merged(C.byref(d), xd.data_ptr(), dyd.data_ptr(), sd.data_ptr(), hd.data_ptr(), ptr(yfd), ptr(qd), ptr(rd),
+                                           dwd.data_ptr(), scratch.data_ptr(), st, C.byref(nl)))
+    elif what == "fused":
         _lib.check(L.dmm_conv1x1_backward_fused(C.byref(d), xd.data_ptr(), dyd.data_ptr(), wd.data_ptr(), sd.data_ptr(), hd.data_ptr(),
                                                 ptr(yfd), ptr(qd), ptr(rd), gxd.data_ptr(), acc, dwd.data_ptr(), red.data_ptr(),
                                                 scratch.data_ptr(), st))
@@ -339,7 +387,11 @@ def backward_case(name, dtype, B, H, W, Cin, Cout, R, S, pad, transposed=0, with
         _lib.check(L.dmm_conv_wgrad_ex(C.byref(d), xd.data_ptr(), dyd.data_ptr(), sd.data_ptr(), hd.data_ptr(), ptr(yfd), ptr(qd), ptr(rd),
                                        1 if what == "wgradT" else 0, dwd.data_ptr(), scratch.data_ptr(), st))
     torch.cuda.synchronize()
-    fam_ok = _check_family(f"{what} {name}", expect)
+    fam_ok = _check_merged(f"{what} {name}", expect, expect_launches, nl.value) if merged else _check_family(f"{what} {name}", expect)
+    if merged:
+        res["guard"] = _guard_hits(wbuf, nw)
+        if keep is not None:
+            keep.update(dw=dwd.cpu().clone(), launches=nl.value)
     if what in ("fused", "dgrad"):
         res["dgrad"] = err(nchw(gxd).cpu(), gx_ref.cpu())
         res["red1"] = err(red[:Cin].cpu(), red1_ref.cpu())

@@ -903,13 +903,22 @@ static int single_main(int argc, char** argv) {
   if (flag("stride2")) d.stride = 2;
   dmm_impl_mask(1);
   const long l0 = fakehip_launches();
-  int rc = -99;
+  int rc = -99, merged = 0;   // merged: what the *_merged entry points report (1: one launch of four phases, 4: kept apart)
   if (entry == "fwd") rc = dmm_conv_forward(&d, x, w, scale, shift, y, stats, scratch, nullptr);
   else if (entry == "logits")   // the fp32 NCHW logits are an address only, as x
     rc = dmm_conv_logits(&d, flag("nullx") ? nullptr : x, flag("nullw") ? nullptr : w, scale, shift,
                          flag("nulllogits") ? nullptr : (float*)reserve((size_t)d.B * d.H * d.W * up * (d.Cout > 0 ? d.Cout : 1) * 4, PROT_NONE),
                          flag("nullscratch") ? nullptr : scratch, nullptr);
   else if (entry == "wgrad") rc = dmm_conv_wgrad_ex(&d, x, y, scale, shift, nullptr, nullptr, nullptr, 0, dw, scratch, nullptr);
+  // the plan's merged four-phase launches of a ConvTranspose stage; withq: the deferred correction on the gradient (q, r real, yfwd an address)
+  else if (entry == "fwdm")
+    rc = dmm_conv_forward_merged(&d, flag("nullx") ? nullptr : x, w, scale, shift, y, stats, scratch, nullptr, flag("nullcount") ? nullptr : &merged);
+  else if (entry == "wgradm") {
+    float* qr = (float*)calloc(2 * (size_t)d.Cout + 16, 4);
+    const bool wq = flag("withq");
+    rc = dmm_conv_wgrad_merged(&d, x, flag("nulldy") ? nullptr : y, scale, shift, wq ? reserve(yout, PROT_NONE) : nullptr, (wq || flag("qonly")) ? qr : nullptr,
+                               wq ? qr + d.Cout : nullptr, dw, scratch, nullptr, &merged);
+  }
   else if (entry == "dgrad") rc = dmm_conv_dgrad_ex(&d, x, y, w, scale, shift, nullptr, nullptr, nullptr, gx, 0, red, scratch, nullptr);
   else if (entry == "fused") rc = dmm_conv1x1_backward_fused(&d, x, y, w, scale, shift, nullptr, nullptr, nullptr, gx, 0, dw, red, scratch, nullptr);
   else return 64;
@@ -917,8 +926,8 @@ static int single_main(int argc, char** argv) {
   std::string names;
   for (int f = 1; f < 32; ++f)
     if ((m >> f) & 1u) names += (names.empty() ? "" : "+") + std::string(dmm_impl_name(f));
-  printf("SINGLE %s rc %d last %s ran %s launches %ld x_bytes %zu y_bytes %zu%s%s\n", entry.c_str(), rc, dmm_impl_name(dmm_last_impl()), names.empty() ? "none" : names.c_str(),
-         fakehip_launches() - l0, xin, yout, rc ? " error: " : "", rc ? dmm_last_error() : "");
+  printf("SINGLE %s rc %d last %s ran %s launches %ld x_bytes %zu y_bytes %zu phases_as %d%s%s\n", entry.c_str(), rc, dmm_impl_name(dmm_last_impl()), names.empty() ? "none" : names.c_str(),
+         fakehip_launches() - l0, xin, yout, merged, rc ? " error: " : "", rc ? dmm_last_error() : "");
   hipDeviceSynchronize();
   return fakehip_violations() ? 1 : 0;
 }
