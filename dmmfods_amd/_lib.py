@@ -78,6 +78,17 @@ class AugSample(C.Structure):
 
 assert C.sizeof(AugTensor) == 32 and C.sizeof(AugSample) == 80
 
+CC_TILE_H, CC_TILE_W, CC_MAX_PER_PLANE = 32, 32, 65536   # DMM_CC_TILE_H, DMM_CC_TILE_W, DMM_CC_MAX_PER_PLANE
+
+
+class Component(C.Structure):
+    """dmm_component: one connected component of a thresholded heat map."""
+    _fields_ = [("root", C.c_int32), ("x0", C.c_int32), ("y0", C.c_int32), ("x1", C.c_int32), ("y1", C.c_int32),
+                ("area", C.c_int32), ("score", C.c_float), ("peak", C.c_int32)]
+
+
+assert C.sizeof(Component) == 32
+
 
 class DmmError(RuntimeError):
     pass
@@ -138,6 +149,9 @@ def lib():
     L.dmm_logit_hist.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int, f32, C.c_int, vp, vp]
     L.dmm_augment_batch.argtypes = [C.POINTER(AugTensor), C.c_int, C.POINTER(AugSample), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                     C.POINTER(C.c_float), vp]
+    L.dmm_heat_components_workspace.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]
+    L.dmm_heat_components_workspace.restype = sz
+    L.dmm_heat_components.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, f32, C.c_int, C.c_int, vp, sz, vp, vp, vp, vp]
     L.dmm_plan_num_grad_buckets.argtypes = [vp]
     L.dmm_plan_num_graph_replays.argtypes = [vp, C.c_int]
     L.dmm_plan_num_graph_replays.restype = C.c_longlong
@@ -200,6 +214,7 @@ EXPORTS = [
     "dmm_adam_step_segmented_ema", "dmm_adam_step_guarded_segmented_ema",
     "dmm_plan_wgrad_batch_counts", "dmm_conv_wgrad_grouped", "dmm_bw1_reduce_grouped",
     "dmm_logit_hist_elems", "dmm_logit_hist", "dmm_augment_batch",
+    "dmm_heat_components_workspace", "dmm_heat_components",
 ]
 HIST_MAX_THRESHOLDS = 255   # DMM_HIST_MAX_THRESHOLDS
 

@@ -15,10 +15,14 @@ checkpoint's optimiser entry) and a validation threshold sweep (``config.agent.t
 takes per-class logit histograms, and the epoch's ``val_history`` row carries IoU, precision, recall, F1, accuracy and average precision
 at every threshold; ``best_val_iou`` and the checkpoints do not depend on it) and on-device augmentation of the training batches
 (``config.loader.augment``: a dict of ``dmmfods_amd.augment.BatchAugment``'s arguments - crop, flip, shift, image gain and bias, modality
-dropout in one launch per batch; its batch counter travels in the checkpoint's ``"augment"`` entry; validation is never augmented)."""
+dropout in one launch per batch; its batch counter travels in the checkpoint's ``"augment"`` entry; validation is never augmented)
+and object-level validation metrics (``config.agent.object_metrics``: the logits and the target of every validation batch are cut into
+connected components on the device, ``dmmfods_amd.detect``, and the epoch's ``val_history`` row carries precision, recall, F1 and AP
+over objects; one synchronisation per validation batch; ``best_val_iou`` and the checkpoints do not depend on it)."""
 import logging
 import os
 import warnings
+from collections.abc import Mapping
 from datetime import datetime
 from pathlib import Path
 
@@ -27,6 +31,7 @@ import torch
 
 from ..augment import BatchAugment
 from ..datasets.WaymoData import WaymoDataset_Loader
+from ..detect import HeatMapDetector, ObjectMetrics
 from ..graphs.models.Dense_U_Net_lidar import densenet121_u_lidar
 from ..metrics import ThresholdSweep, logit_thresholds
 from ..optim import DynamicLossScaler, FusedAdam, fine_tune_groups
@@ -131,6 +136,10 @@ class Dense_U_Net_lidar_Agent:
         # loader.augment: a dict of BatchAugment's arguments; every training batch is cropped / flipped / shifted / scaled on the device,
         # behind the copy to it and in front of the model, by one more launch.  Validation never is.  Absent: not one call more.
         self.augment = self._make_augment(self._optional(self.config.loader, "augment"))
+        # agent.object_metrics: a dict (iou, connectivity, max_per_plane, min_area, threshold); validation also turns the logits and
+        # the target of every batch into objects (dmmfods_amd.detect) and its val_history row carries object-level precision, recall,
+        # F1 and AP.  Absent: not one call more.
+        self.object_detector, self.object_metrics = self._make_object_metrics(self._optional(self.config.agent, "object_metrics"))
         self.lr_scheduler = None
         if o.lr_scheduler.want:
             self.lr_scheduler = _StepLR(self.optimizer, o.lr_scheduler.every_n_epochs, o.lr_scheduler.gamma)
@@ -177,6 +186,26 @@ class Dense_U_Net_lidar_Agent:
         thr = np.union1d(thr, np.asarray([op], dtype=np.float32))   # sorted, without duplicates
         sweep = ThresholdSweep(self.config.model.num_classes, thresholds=thr.tolist(), gt_threshold=float(self.config.agent.iou_threshold))
         return sweep, int(np.nonzero(sweep.thresholds == op)[0][0])
+
+    def _make_object_metrics(self, spec):
+        """spec: None (no object metrics) or a dict with any of iou (0.5), connectivity (8), max_per_plane (1024), min_area (1) and
+        threshold (iou_threshold; it cuts the logits and the target alike, as the loss kernel's counts do).  Returns (detector, metrics)."""
+        if spec is None:
+            return None, None
+        if not isinstance(spec, Mapping):
+            raise ValueError("agent.object_metrics must be a dict (iou, connectivity, max_per_plane, min_area, threshold)")
+        kw = dict(spec)
+        unknown = set(kw) - {"iou", "connectivity", "max_per_plane", "min_area", "threshold"}
+        if unknown:
+            raise ValueError(f"agent.object_metrics: unknown keys {sorted(unknown)}")
+        iou = kw.pop("iou", 0.5)
+        threshold = kw.pop("threshold", None)
+        try:
+            detector = HeatMapDetector(float(self.config.agent.iou_threshold if threshold is None else threshold), **kw)
+            metrics = ObjectMetrics(self.config.model.num_classes, iou=iou)
+        except (TypeError, ValueError) as e:
+            raise ValueError(f"agent.object_metrics: {e}") from None
+        return detector, metrics
 
     @staticmethod
     def _make_augment(spec):
@@ -343,6 +372,8 @@ class Dense_U_Net_lidar_Agent:
         ep = {k: torch.zeros((n, nc), device=self.device) for k in ("loss", "iou", "nans", "acc")}
         if self.sweep is not None:
             self.sweep.reset()
+        if self.object_metrics is not None:
+            self.object_metrics.reset()
         with torch.no_grad():
             for b, (image, lidar, ht_map) in enumerate(self.data_loader.valid_loader):
                 image, lidar, ht_map = self._to_device(image, lidar, ht_map)
@@ -350,6 +381,8 @@ class Dense_U_Net_lidar_Agent:
                 m = self.model.loss_metrics(prediction, ht_map)
                 if self.sweep is not None:
                     self.sweep.update(prediction, ht_map)     # one more launch on the same stream, no synchronisation
+                if self.object_metrics is not None:           # two calls on the same stream; pulling the records synchronises once
+                    self.object_metrics.update(self.object_detector(prediction.float()), self.object_detector(ht_map.float()))
                 iou_pc, nans, acc_pc = self._batch_metrics(m)
                 ep["loss"][b], ep["iou"][b], ep["nans"][b], ep["acc"][b] = m["loss_per_class"], iou_pc, nans, acc_pc
                 self._log(self.val_summary_writer, "Validation", m["loss_per_class"], acc_pc, iou_pc, self.current_val_iteration)
@@ -365,6 +398,13 @@ class Dense_U_Net_lidar_Agent:
             self.logger.info("Validation at Epoch-%d | Threshold sweep (%d logit thresholds) | Best threshold: %s | Best IoU: %s | IoU at %g: %s",
                              self.current_epoch, self.sweep.num_thresholds, sw["best_threshold"].tolist(), sw["best_iou"].tolist(),
                              float(self.sweep.thresholds[self.sweep_column]), sw["iou"][:, self.sweep_column].tolist())
+        if self.object_metrics is not None:
+            ob = self.object_metrics.compute()
+            self.val_history[-1]["objects"] = ob
+            for c in range(nc):
+                self.logger.info("Validation at Epoch-%d | Objects of class %d | Found: %d of %d | Predicted: %d | Precision: %g | Recall: %g | "
+                                 "F1: %g | AP: %g | Overflowed planes: %d", self.current_epoch, c, ob["tp"][c], ob["num_gt"][c],
+                                 ob["num_pred"][c], ob["precision"][c], ob["recall"][c], ob["f1"][c], ob["ap"][c], ob["overflowed_planes"])
         return avg_iou
 
     def save_hparams_json(self):

@@ -761,6 +761,47 @@ int dmm_augment_batch(const dmm_aug_tensor* tensors, int ntensors, const dmm_aug
   return DMM_OK;
 }
 
+// why dmm_heat_components would refuse these sizes ("" = it would not); shared with the workspace query
+static std::string components_refusal(int B, int NC, int H, int W, int max_per_plane) {
+  if (B < 1 || NC < 1 || H < 1 || W < 1) return "B, NC, H and W must be >= 1";
+  if ((long long)B * NC > 65535) return "B * NC must be <= 65535";
+  if ((long long)H * W >= (1ll << 31)) return "H * W must be < 2^31";
+  if (max_per_plane < 1 || max_per_plane > DMM_CC_MAX_PER_PLANE) return "max_per_plane must be in [1, " + std::to_string(DMM_CC_MAX_PER_PLANE) + "]";
+  return "";
+}
+
+size_t dmm_heat_components_workspace(int B, int NC, int H, int W, int max_per_plane) {
+  if (!components_refusal(B, NC, H, W, max_per_plane).empty()) return 0;
+  return components_layout(B * NC, (size_t)H * W).total;
+}
+
+int dmm_heat_components(const float* maps, int B, int NC, int H, int W, float threshold, int connectivity, int max_per_plane,
+                        void* workspace, size_t workspace_bytes, int32_t* labels, dmm_component* records, int32_t* counts, void* stream) {
+  const std::string who = "dmm_heat_components: ";
+  if (!maps || !workspace || !records || !counts) return fail(DMM_ERR_INVALID, who + "null argument");
+  if ((uintptr_t)maps % 4 || (uintptr_t)labels % 4 || (uintptr_t)counts % 4) return fail(DMM_ERR_INVALID, who + "maps / labels / counts must be 4-byte aligned");
+  if ((uintptr_t)records % 8) return fail(DMM_ERR_INVALID, who + "records must be 8-byte aligned");
+  if ((uintptr_t)workspace % 16) return fail(DMM_ERR_INVALID, who + "workspace must be 16-byte aligned");
+  const std::string why = components_refusal(B, NC, H, W, max_per_plane);
+  if (!why.empty()) return fail(DMM_ERR_INVALID, who + why);
+  if (connectivity != 4 && connectivity != 8) return fail(DMM_ERR_INVALID, who + "connectivity must be 4 or 8");
+  if (std::isnan(threshold)) return fail(DMM_ERR_INVALID, who + "threshold is NaN");
+  const ComponentsLayout lay = components_layout(B * NC, (size_t)H * W);
+  if (workspace_bytes < lay.total) return fail(DMM_ERR_INVALID, who + "workspace_bytes is below dmm_heat_components_workspace (" + std::to_string(lay.total) + ")");
+  ComponentsArgs a;
+  memset(&a, 0, sizeof(a));
+  a.maps = maps;
+  a.labels = labels ? labels : (int*)((char*)workspace + lay.labels);
+  a.seg = (int*)((char*)workspace + lay.seg);
+  a.records = records; a.counts = counts;
+  a.B = B; a.NC = NC; a.H = H; a.W = W;
+  a.tiles_x = (W + CC_TILE_W - 1) / CC_TILE_W; a.tiles_y = (H + CC_TILE_H - 1) / CC_TILE_H;
+  a.nseg = (int)(((size_t)H * W + CC_SEG - 1) / CC_SEG);
+  a.cap = max_per_plane; a.conn8 = connectivity == 8 ? 1 : 0; a.thr = threshold;
+  HIPCHK(launch_components(a, (hipStream_t)stream));
+  return DMM_OK;
+}
+
 int dmm_plan_loss_backward(dmm_plan* plan, const float* logits, const float* target, double* metrics_out, void* stream) {
   if (!plan || !plan->bound) return fail(DMM_ERR_STATE, "plan not bound");
   if (!logits || !target) return fail(DMM_ERR_INVALID, "null argument");

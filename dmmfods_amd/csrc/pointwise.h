@@ -122,6 +122,30 @@ struct LogitHistArgs {
   float thr[HIST_MAX_THRESHOLDS];  // strictly ascending, finite; by value (1020 bytes), so a launch needs no upload
 };
 
+// ---- heat maps to objects (components.hip) ----
+constexpr int CC_TILE_H = DMM_CC_TILE_H, CC_TILE_W = DMM_CC_TILE_W;
+constexpr int CC_SEG = 4096;   // pixels of a plane, consecutive in raster order, whose roots one workgroup counts and then ranks
+struct ComponentsArgs {
+  const float* maps;        // (B, NC, H, W) fp32
+  int* labels;              // (B, NC, H, W) int32: the caller's array, or the one carved from the workspace
+  int* seg;                 // [B * NC][nseg]: roots per segment, then (scan) the roots in front of the segment
+  dmm_component* records;   // [B * NC][cap]
+  int* counts;              // [B * NC]
+  int B, NC, H, W;          // H * W < 2^31, B * NC <= 65535 (gridDim.y)
+  int tiles_x, tiles_y;     // ceil(W / CC_TILE_W), ceil(H / CC_TILE_H)
+  int nseg;                 // ceil(H * W / CC_SEG)
+  int cap;                  // max_per_plane
+  int conn8;                // 1: 8-connectivity
+  float thr;
+};
+// where the call's two arrays lie in its workspace (bytes from its start, each a multiple of 16) and the total
+struct ComponentsLayout { size_t labels, seg, total; };
+ComponentsLayout components_layout(int planes, size_t plane);
+// the seven launches of one call, in order; each grid is (x, planes)
+constexpr int CC_LAUNCHES = 7;
+void components_grids(const ComponentsArgs& a, unsigned gx[CC_LAUNCHES]);
+hipError_t launch_components(const ComponentsArgs& a, hipStream_t st);
+
 // ---- batch augmentation (augment.hip) ----
 constexpr int AUG_MAX_CHANNELS = DMM_AUG_MAX_CHANNELS;
 constexpr int AUG_LAUNCH_BATCH = DMM_AUG_LAUNCH_BATCH;

@@ -16,6 +16,8 @@
  *                                          (utils/Dense_U_Net_lidar_helper.py:311-401) at up to 255 thresholds in one pass
  *   dmm_augment_batch .................... nothing upstream (the reference feeds the model what the loader yields, :236-244): crop,
  *                                          flip, shift, per-channel gain and bias of a device batch in one launch
+ *   dmm_heat_components .................. nothing upstream (the reference cannot "compute IoU per bounding box", helper.py:311-315):
+ *                                          connected components of a thresholded heat map, one record per object
  *   dmm_adam_step ........................ torch.optim.Adam.step        agents/Dense_U_Net_lidar_Agent.py:57-61,265
  *   dmm_adam_table_* / dmm_adam_step_segmented / dmm_adam_step_guarded_segmented
  *                                          torch.optim.Adam built over PARAMETER GROUPS (the list-of-dicts form of the constructor
@@ -209,6 +211,41 @@ int dmm_augment_batch(const dmm_aug_tensor* tensors, int ntensors,
                       const dmm_aug_sample* samples /* host, B entries */, int B,
                       int Hs, int Ws, int Ho, int Wo,
                       const float* fill /* host, one value per channel; NULL = zeros */, void* stream);
+
+/* ---- heat maps to objects: connected components and one record per component ----
+ * (Nothing upstream: the reference measures whole-image pixel counts only, utils/Dense_U_Net_lidar_helper.py
+ * compute_IoU_whole_img_per_class.  This turns a heat map - logits or a rendered target map - into the objects it shows.)
+ * maps is a (B, NC, H, W) fp32 NCHW contiguous device tensor.  A pixel is foreground iff x >= threshold, compared in fp32: a value on
+ * the threshold is foreground, NaN is not, -0.0 >= 0.0 holds.  Components are taken per (b, n) plane under 4- or 8-connectivity;
+ * planes never touch and rows do not wrap.  A component's label is its ROOT, the smallest y * W + x among its pixels (plane-relative
+ * int32); background pixels have label -1.  Per plane the records stand in ascending root order; when a plane has more components
+ * than max_per_plane the max_per_plane smallest roots are kept, counts still holds the true number, and the slots behind
+ * min(count, max_per_plane) are zero.  score is the component's largest value in the order that puts -0.0 below +0.0 (they compare
+ * equal; the order is over the bit patterns), peak the first pixel in raster order that holds that value.  Every output is an
+ * integer or a copied input value: exact, bit-reproducible, independent of the launch geometry.  No floating-point atomics.
+ * Seven kernel launches on `stream`; no plan, no synchronisation, no memset, nothing uploaded from host memory.
+ * workspace: dmm_heat_components_workspace bytes of device memory, 16-byte aligned, contents undefined before and after.
+ * Refuses with DMM_ERR_INVALID, before any HIP call: a null maps, workspace, records or counts; maps, labels or counts not 4-byte
+ * aligned, records not 8-byte aligned, workspace not 16-byte aligned; B, NC, H or W < 1; H * W >= 2^31; B * NC > 65535 (gridDim.y);
+ * connectivity other than 4 or 8; max_per_plane outside [1, 65536]; a NaN threshold; workspace_bytes below
+ * dmm_heat_components_workspace(...). */
+#define DMM_CC_TILE_H 32   /* one workgroup labels a DMM_CC_TILE_H x DMM_CC_TILE_W tile in LDS; tiles are then merged along their borders */
+#define DMM_CC_TILE_W 32
+#define DMM_CC_MAX_PER_PLANE 65536
+typedef struct dmm_component {   /* 32 bytes */
+  int32_t root;                  /* y * W + x of the component's first pixel in raster order */
+  int32_t x0, y0, x1, y1;        /* inclusive pixel box */
+  int32_t area;                  /* pixels */
+  float   score;                 /* largest value in the component */
+  int32_t peak;                  /* linear index of the first pixel in raster order holding `score` */
+} dmm_component;
+size_t dmm_heat_components_workspace(int B, int NC, int H, int W, int max_per_plane);   /* bytes; 0 for refused arguments */
+int dmm_heat_components(const float* maps, int B, int NC, int H, int W, float threshold, int connectivity /* 4 | 8 */,
+                        int max_per_plane, void* workspace, size_t workspace_bytes,
+                        int32_t* labels /* device, B*NC*H*W, may be NULL */,
+                        dmm_component* records /* device, [B*NC][max_per_plane] */,
+                        int32_t* counts /* device, [B*NC]: the TRUE number of components, may exceed max_per_plane */,
+                        void* stream);
 
 /* Backward from an externally computed d(loss)/d(logit) (B,num_classes,H,W fp32), e.g. from torch autograd of any
  * loss on the returned logits (reference: loss.backward(...), agents/Dense_U_Net_lidar_Agent.py:264). */

@@ -50,6 +50,9 @@
 // the launch geometry of both accumulate modes - and every refusal of the entry point, each with nothing enqueued (hist_main).
 // DRIVE_AUGMENT=1 (life-cycle run): behind the lives (and DRIVE_HIST's calls), one valid dmm_augment_batch call with 33 samples on operands
 // that are addresses only - two launches - and every refusal of the entry point, each with nothing enqueued (augment_main).
+// DRIVE_COMPONENTS=1 (life-cycle run): behind the lives (and the calls of the two switches above), dmm_heat_components on three shapes with
+// operands that are addresses only - seven launches each, every grid against a restatement of the tiling, the workspace carve-up inside
+// workspace_bytes - and every refusal of the entry point, each with nothing enqueued (components_main).
 // Launch coalescing (dmm_set_option("batch_wgrad"), on by default; DRIVE_OPTIONS_OFF=batch_wgrad runs one launch per record,
 // DRIVE_BATCH_WGRAD=<0|1|2> sets the option's value: 2 = grouped on the weight-gradient stream instead of the caller's): every
 // life-cycle run watches the enqueue calls through the fake runtime's hook and checks, with the option on or off, that
@@ -244,6 +247,8 @@ struct HistWatch {
   unsigned gx = 0, gy = 0;
   unsigned long long memset_bytes = 0;
 } g_hist;
+struct LaunchSeen { std::string kernel; unsigned gx, gy; };
+std::vector<LaunchSeen> g_launch_log;   // (while g_hist.on: components_main reads seven launches of one call from it)
 void drive_hook(int what, const char* kernel, unsigned gx, unsigned gy, const void* stream, const void* event) {
   if (g_enqueue.on) {
     const int s = EnqueueTrace::ordinal(g_enqueue.streams, stream);
@@ -254,7 +259,7 @@ void drive_hook(int what, const char* kernel, unsigned gx, unsigned gy, const vo
   }
   batch_hook(what, kernel, gx, gy, stream, event);
   if (g_hist.on) {
-    if (what == 0) { ++g_hist.launches; g_hist.kernel = kernel; g_hist.gx = gx; g_hist.gy = gy; }
+    if (what == 0) { ++g_hist.launches; g_hist.kernel = kernel; g_hist.gx = gx; g_hist.gy = gy; g_launch_log.push_back({kernel, gx, gy}); }
     else if (what == 3) { ++g_hist.memsets; g_hist.memset_bytes = gx | (unsigned long long)gy << 32; }
     else ++g_hist.other;
   }
@@ -1175,6 +1180,95 @@ static int augment_main() {
 }
 #endif
 
+// ---- DRIVE_COMPONENTS: dmm_heat_components (built against a csrc that has none: the case does not exist) ----
+#ifdef DMM_CC_TILE_H
+// Three shapes: a plane smaller than a tile, one ragged in both directions, many planes.  maps, labels, records, counts and the
+// workspace are addresses only (reserved, PROT_NONE): the call uploads nothing, clears nothing and touches none of them on the host.
+// Per shape, with and without a labels array: seven launches and nothing else, each grid (x, B * NC) against the tiling restated here,
+// and the two arrays the call carves from its workspace inside dmm_heat_components_workspace bytes.  Then every refusal.
+static int components_main() {
+  struct Shape { int B, NC, H, W, cap; };
+  const Shape shapes[3] = {{1, 1, 7, 9, 16}, {2, 3, 3 * DMM_CC_TILE_H + 5, 2 * DMM_CC_TILE_W + 3, 1024}, {64, 300, 40, 50, 300}};
+  const char* names[CC_LAUNCHES] = {"cc_local_kernel", "cc_merge_kernel", "cc_flatten_kernel", "cc_scan_kernel", "cc_slots_kernel",
+                                    "cc_stats_kernel", "cc_finish_kernel"};
+  int bad = 0;
+  g_hist = HistWatch();
+  g_hist.on = true;
+  for (const Shape& s : shapes) {
+    const size_t planes = (size_t)s.B * s.NC, plane = (size_t)s.H * s.W, px = planes * plane;
+    const size_t wsb = dmm_heat_components_workspace(s.B, s.NC, s.H, s.W, s.cap);
+    const size_t tiles = (size_t)((s.H + DMM_CC_TILE_H - 1) / DMM_CC_TILE_H) * ((s.W + DMM_CC_TILE_W - 1) / DMM_CC_TILE_W);
+    const size_t nseg = (plane + CC_SEG - 1) / CC_SEG;
+    const unsigned want[CC_LAUNCHES] = {(unsigned)tiles, (unsigned)tiles, (unsigned)nseg, 1u, (unsigned)nseg, (unsigned)tiles, (unsigned)((s.cap + 255) / 256)};
+    // the carve-up: labels at 0, the segment counts behind them, both 16-byte aligned, the end inside the workspace
+    const ComponentsLayout lay = components_layout((int)planes, plane);
+    bool ok = wsb != 0 && lay.total == wsb && lay.labels == 0 && lay.labels % 16 == 0 && lay.seg % 16 == 0 && lay.seg >= px * 4 &&
+              lay.seg + planes * nseg * 4 <= wsb;
+    const float* maps = (const float*)reserve(px * 4, PROT_NONE);
+    int32_t* labels = (int32_t*)reserve(px * 4, PROT_NONE);
+    dmm_component* records = (dmm_component*)reserve(planes * s.cap * sizeof(dmm_component), PROT_NONE);
+    int32_t* counts = (int32_t*)reserve(planes * 4, PROT_NONE);
+    void* ws = reserve(wsb, PROT_NONE);
+    for (int with_labels = 0; with_labels < 2; ++with_labels) {
+      const HistWatch w0 = g_hist;
+      g_launch_log.clear();
+      MUST(dmm_heat_components(maps, s.B, s.NC, s.H, s.W, 0.7f, with_labels ? 8 : 4, s.cap, ws, wsb, with_labels ? labels : nullptr, records, counts, nullptr));
+      ok = ok && g_hist.launches == w0.launches + CC_LAUNCHES && g_hist.memsets == w0.memsets && g_hist.other == w0.other && g_launch_log.size() == (size_t)CC_LAUNCHES;
+      for (int k = 0; ok && k < CC_LAUNCHES; ++k)
+        ok = g_launch_log[k].kernel.find(names[k]) != std::string::npos && g_launch_log[k].gx == want[k] && g_launch_log[k].gy == (unsigned)planes;
+    }
+    printf("COMPONENTS %d x %d x %d x %d cap %d: %zu tiles, %zu segments, workspace %zu %s\n", s.B, s.NC, s.H, s.W, s.cap, tiles, nseg, wsb, ok ? "ok" : "WRONG");
+    bad += !ok;
+  }
+  // the refusals: nothing reaches the runtime, the message names the argument
+  const float* x = (const float*)reserve(1 << 20, PROT_NONE);
+  int32_t* lab = (int32_t*)reserve(1 << 20, PROT_NONE);
+  dmm_component* rec = (dmm_component*)reserve(1 << 20, PROT_NONE);
+  int32_t* cnt = (int32_t*)reserve(1 << 20, PROT_NONE);
+  void* ws = reserve(1 << 20, PROT_NONE);
+  const size_t wsb = dmm_heat_components_workspace(1, 1, 8, 8, 4);
+  const HistWatch w0 = g_hist;
+  auto refused = [&](int rc, const char* names) {
+    if (rc == DMM_ERR_INVALID && strncmp(dmm_last_error(), "dmm_heat_components: ", 21) == 0 && strstr(dmm_last_error(), names) != nullptr) return;
+    fprintf(stderr, "[drive] dmm_heat_components: not refused (%d) or the message does not say '%s': %s\n", rc, names, dmm_last_error());
+    ++bad;
+  };
+  auto off = [](auto* p, int bytes) { return (decltype(p))((char*)p + bytes); };
+  const float nan = __builtin_nanf("");
+  refused(dmm_heat_components(nullptr, 1, 1, 8, 8, 0.f, 8, 4, ws, wsb, lab, rec, cnt, nullptr), "null");
+  refused(dmm_heat_components(x, 1, 1, 8, 8, 0.f, 8, 4, nullptr, wsb, lab, rec, cnt, nullptr), "null");
+  refused(dmm_heat_components(x, 1, 1, 8, 8, 0.f, 8, 4, ws, wsb, lab, nullptr, cnt, nullptr), "null");
+  refused(dmm_heat_components(x, 1, 1, 8, 8, 0.f, 8, 4, ws, wsb, lab, rec, nullptr, nullptr), "null");
+  refused(dmm_heat_components(off(x, 2), 1, 1, 8, 8, 0.f, 8, 4, ws, wsb, lab, rec, cnt, nullptr), "4-byte aligned");
+  refused(dmm_heat_components(x, 1, 1, 8, 8, 0.f, 8, 4, ws, wsb, off(lab, 1), rec, cnt, nullptr), "4-byte aligned");
+  refused(dmm_heat_components(x, 1, 1, 8, 8, 0.f, 8, 4, ws, wsb, lab, rec, off(cnt, 2), nullptr), "4-byte aligned");
+  refused(dmm_heat_components(x, 1, 1, 8, 8, 0.f, 8, 4, ws, wsb, lab, off(rec, 4), cnt, nullptr), "8-byte aligned");
+  refused(dmm_heat_components(x, 1, 1, 8, 8, 0.f, 8, 4, off(ws, 8), wsb, lab, rec, cnt, nullptr), "16-byte aligned");
+  refused(dmm_heat_components(x, 0, 1, 8, 8, 0.f, 8, 4, ws, wsb, lab, rec, cnt, nullptr), ">= 1");
+  refused(dmm_heat_components(x, 1, 0, 8, 8, 0.f, 8, 4, ws, wsb, lab, rec, cnt, nullptr), ">= 1");
+  refused(dmm_heat_components(x, 1, 1, 0, 8, 0.f, 8, 4, ws, wsb, lab, rec, cnt, nullptr), ">= 1");
+  refused(dmm_heat_components(x, 1, 1, 8, -1, 0.f, 8, 4, ws, wsb, lab, rec, cnt, nullptr), ">= 1");
+  refused(dmm_heat_components(x, 256, 256, 8, 8, 0.f, 8, 4, ws, wsb, lab, rec, cnt, nullptr), "B * NC");
+  refused(dmm_heat_components(x, 1, 1, 65536, 32768, 0.f, 8, 4, ws, wsb, lab, rec, cnt, nullptr), "H * W");
+  refused(dmm_heat_components(x, 1, 1, 8, 8, 0.f, 6, 4, ws, wsb, lab, rec, cnt, nullptr), "connectivity");
+  refused(dmm_heat_components(x, 1, 1, 8, 8, 0.f, 0, 4, ws, wsb, lab, rec, cnt, nullptr), "connectivity");
+  refused(dmm_heat_components(x, 1, 1, 8, 8, 0.f, 8, 0, ws, wsb, lab, rec, cnt, nullptr), "max_per_plane");
+  refused(dmm_heat_components(x, 1, 1, 8, 8, 0.f, 8, DMM_CC_MAX_PER_PLANE + 1, ws, wsb, lab, rec, cnt, nullptr), "max_per_plane");
+  refused(dmm_heat_components(x, 1, 1, 8, 8, nan, 8, 4, ws, wsb, lab, rec, cnt, nullptr), "threshold is NaN");
+  refused(dmm_heat_components(x, 1, 1, 8, 8, 0.f, 8, 4, ws, wsb - 1, lab, rec, cnt, nullptr), "workspace_bytes");
+  refused(dmm_heat_components(x, 1, 1, 8, 8, 0.f, 8, 4, ws, 0, lab, rec, cnt, nullptr), "workspace_bytes");
+  if (g_hist.launches != w0.launches || g_hist.memsets != w0.memsets || g_hist.other != w0.other) { fprintf(stderr, "[drive] a refused dmm_heat_components call reached the runtime\n"); ++bad; }
+  if (wsb == 0 || dmm_heat_components_workspace(0, 1, 8, 8, 4) || dmm_heat_components_workspace(1, 1, 8, 0, 4) || dmm_heat_components_workspace(256, 256, 8, 8, 4) ||
+      dmm_heat_components_workspace(1, 1, 65536, 32768, 4) || dmm_heat_components_workspace(1, 1, 8, 8, 0) || dmm_heat_components_workspace(1, 1, 8, 8, DMM_CC_MAX_PER_PLANE + 1)) {
+    fprintf(stderr, "[drive] dmm_heat_components_workspace\n"); ++bad;
+  }
+  g_hist.on = false;
+  hipDeviceSynchronize();
+  printf("%s\n", bad ? "COMPONENTS FAILED" : "COMPONENTS OK");
+  return bad ? 1 : 0;
+}
+#endif
+
 int main(int argc, char** argv) {
   g_enqueue.on =getenv("DRIVE_TRACE_ENQUEUE") != nullptr;
   fakehip_set_hook(drive_hook);
@@ -1214,6 +1308,9 @@ int main(int argc, char** argv) {
 #endif
 #ifdef DMM_AUG_MAX_TENSORS
   if (getenv("DRIVE_AUGMENT") && augment_main() != 0) rc = 1;
+#endif
+#ifdef DMM_CC_TILE_H
+  if (getenv("DRIVE_COMPONENTS") && components_main() != 0) rc = 1;
 #endif
   if (g_bad) { fprintf(stderr, "[drive] FAIL: %ld device pointers outside the caller's regions\n", g_bad); rc = 1; }
   if (fakehip_violations()) { fprintf(stderr, "[drive] FAIL: %ld teardown / handle violations\n", fakehip_violations()); rc = 1; }
