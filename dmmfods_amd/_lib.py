@@ -90,6 +90,17 @@ class Component(C.Structure):
 assert C.sizeof(Component) == 32
 
 
+PREP_LAUNCH_BATCH, PREP_MAX_ITEMS = 32, 1 << 23   # DMM_PREP_LAUNCH_BATCH, DMM_PREP_MAX_ITEMS
+
+
+class PrepBox(C.Structure):
+    """dmm_prep_box: one labelled box of a dmm_prep_heat_maps call; top-left corner, full-resolution pixels."""
+    _fields_ = [("type", C.c_int32), ("x", C.c_int32), ("y", C.c_int32), ("width", C.c_int32), ("height", C.c_int32)]
+
+
+assert C.sizeof(PrepBox) == 20
+
+
 class DmmError(RuntimeError):
     pass
 
@@ -152,6 +163,11 @@ def lib():
     L.dmm_heat_components_workspace.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]
     L.dmm_heat_components_workspace.restype = sz
     L.dmm_heat_components.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, f32, C.c_int, C.c_int, vp, sz, vp, vp, vp, vp]
+    L.dmm_prep_image.argtypes = [vp, i64, vp, i64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]
+    L.dmm_prep_lidar_workspace.argtypes = [C.c_int, C.c_int, C.c_int]
+    L.dmm_prep_lidar_workspace.restype = sz
+    L.dmm_prep_lidar.argtypes = [vp, C.POINTER(i32), vp, i64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, sz, vp]
+    L.dmm_prep_heat_maps.argtypes = [vp, C.POINTER(i32), vp, i64, C.c_int, C.c_int, C.c_int, C.c_int, vp]
     L.dmm_plan_num_grad_buckets.argtypes = [vp]
     L.dmm_plan_num_graph_replays.argtypes = [vp, C.c_int]
     L.dmm_plan_num_graph_replays.restype = C.c_longlong
@@ -215,6 +231,7 @@ EXPORTS = [
     "dmm_plan_wgrad_batch_counts", "dmm_conv_wgrad_grouped", "dmm_bw1_reduce_grouped",
     "dmm_logit_hist_elems", "dmm_logit_hist", "dmm_augment_batch",
     "dmm_heat_components_workspace", "dmm_heat_components",
+    "dmm_prep_image", "dmm_prep_lidar_workspace", "dmm_prep_lidar", "dmm_prep_heat_maps",
 ]
 HIST_MAX_THRESHOLDS = 255   # DMM_HIST_MAX_THRESHOLDS
 

@@ -18,7 +18,10 @@ at every threshold; ``best_val_iou`` and the checkpoints do not depend on it) an
 dropout in one launch per batch; its batch counter travels in the checkpoint's ``"augment"`` entry; validation is never augmented)
 and object-level validation metrics (``config.agent.object_metrics``: the logits and the target of every validation batch are cut into
 connected components on the device, ``dmmfods_amd.detect``, and the epoch's ``val_history`` row carries precision, recall, F1 and AP
-over objects; one synchronisation per validation batch; ``best_val_iou`` and the checkpoints do not depend on it)."""
+over objects; one synchronisation per validation batch; ``best_val_iou`` and the checkpoints do not depend on it) and batch preparation
+on the device (``config.loader.raw_frames``: a dict of ``dmmfods_amd.prepare.BatchPrepare``'s arguments; the loader yields the uint8
+image, the LiDAR points and the boxes of each frame, ``dmmfods_amd.datasets.RawFrames``, and three launches build the tensors the
+reference's host preparation would, in training and in validation; the augmentation, where configured, follows it)."""
 import logging
 import os
 import warnings
@@ -30,7 +33,9 @@ import numpy as np
 import torch
 
 from ..augment import BatchAugment
+from ..datasets.RawFrames import RawFrames_Loader
 from ..datasets.WaymoData import WaymoDataset_Loader
+from ..prepare import BatchPrepare
 from ..detect import HeatMapDetector, ObjectMetrics
 from ..graphs.models.Dense_U_Net_lidar import densenet121_u_lidar
 from ..metrics import ThresholdSweep, logit_thresholds
@@ -76,7 +81,13 @@ class Dense_U_Net_lidar_Agent:
         # the reference always builds DenseNet-121 (A:44); torchvision_init=True would download ImageNet weights (no network)
         self.model = densenet121_u_lidar(pretrained=False, config=config, compute_dtype=compute_dtype)
         self.config = self.model.config
-        self.data_loader = data_loader if data_loader is not None else WaymoDataset_Loader(self.config)
+        # loader.raw_frames: a dict of BatchPrepare's arguments (pool, kernel_size).  The loader then yields RawBatches - uint8 image,
+        # LiDAR points, boxes - and the preparation on the device takes the place of the copy of seven fp32 planes, in training and in
+        # validation.  Absent: the reference's loader and not one call more.
+        self.prepare = self._make_prepare(self._optional(self.config.loader, "raw_frames"))
+        if data_loader is None:
+            data_loader = RawFrames_Loader(self.config) if self.prepare is not None else WaymoDataset_Loader(self.config)
+        self.data_loader = data_loader
         # A:54.  The step uses the fused tail; a FocalLoss / ClassWiseFocalLoss (reference L:9-91) becomes its loss epilogue.
         self.loss = loss if loss is not None else torch.nn.BCEWithLogitsLoss(reduction="none")
         if hasattr(self.loss, "attach"):
@@ -208,6 +219,21 @@ class Dense_U_Net_lidar_Agent:
         return detector, metrics
 
     @staticmethod
+    def _make_prepare(spec):
+        """spec: None (the loader yields prepared tensors) or a dict of BatchPrepare's arguments."""
+        if spec is None:
+            return None
+        if isinstance(spec, bool) or not hasattr(spec, "keys"):
+            raise ValueError("loader.raw_frames must be a dict (pool, kernel_size)")
+        unknown = set(spec.keys()) - {"pool", "kernel_size"}
+        if unknown:
+            raise ValueError(f"loader.raw_frames: unknown keys {sorted(unknown)}")
+        try:
+            return BatchPrepare(**dict(spec))
+        except (TypeError, ValueError) as e:
+            raise ValueError(f"loader.raw_frames: {e}") from None
+
+    @staticmethod
     def _make_augment(spec):
         """spec: None (no augmentation) or a dict of BatchAugment's arguments.  The model takes sizes that are multiples of 32, so
         out_size has to be one; rank defaults to this process's torch.distributed rank, so that every rank draws its own parameters."""
@@ -297,6 +323,13 @@ class Dense_U_Net_lidar_Agent:
         nb = bool(self.config.loader.async_loading)
         return tuple(t.to(self.device, non_blocking=nb) for t in tensors)
 
+    def _batch_tensors(self, batch):
+        """What the loader yields -> (image, lidar, heat maps) on the device: the copy of the three tensors, or with loader.raw_frames
+        the preparation of a RawBatch."""
+        if self.prepare is not None:
+            return self.prepare(batch, self.device)
+        return self._to_device(*batch)
+
     @staticmethod
     def _batch_metrics(m):
         """Per-class IoU (NaN-mean over samples, NaN -> 0), NaN counts, accuracy: A:252-260 without leaving the device."""
@@ -323,8 +356,8 @@ class Dense_U_Net_lidar_Agent:
         skipped0 = guard.skipped_steps if guard is not None else 0
         window = self.accumulate_steps
         open_batches = 0   # batches whose gradients sit in the arena waiting for a step (always 0 here when window == 1)
-        for b, (image, lidar, ht_map) in enumerate(self.data_loader.train_loader):
-            image, lidar, ht_map = self._to_device(image, lidar, ht_map)
+        for b, batch in enumerate(self.data_loader.train_loader):
+            image, lidar, ht_map = self._batch_tensors(batch)
             if self.augment is not None:
                 image, lidar, ht_map = self.augment(image, lidar, ht_map)
             if window > 1 and open_batches == 0:
@@ -375,8 +408,8 @@ class Dense_U_Net_lidar_Agent:
         if self.object_metrics is not None:
             self.object_metrics.reset()
         with torch.no_grad():
-            for b, (image, lidar, ht_map) in enumerate(self.data_loader.valid_loader):
-                image, lidar, ht_map = self._to_device(image, lidar, ht_map)
+            for b, batch in enumerate(self.data_loader.valid_loader):
+                image, lidar, ht_map = self._batch_tensors(batch)
                 prediction = self.model(image, lidar)
                 m = self.model.loss_metrics(prediction, ht_map)
                 if self.sweep is not None:

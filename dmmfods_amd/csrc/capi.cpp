@@ -458,7 +458,7 @@ static int launch_list(dmm_plan* p, int which, std::vector<Op>& ops, size_t seg_
 extern "C" {
 
 const char* dmm_last_error(void) { return g_err.c_str(); }
-int dmm_version(void) { return 101; }
+int dmm_version(void) { return 102; }
 
 // The names of enum Impl (dmm_impl_name), and the families dmm_set_option switches with the option name of each (hf, cf and halo
 // are not settable).
@@ -757,6 +757,104 @@ int dmm_augment_batch(const dmm_aug_tensor* tensors, int ntensors, const dmm_aug
     a.b0 = b0;
     memcpy(a.s, samples + b0, (size_t)nb * sizeof(dmm_aug_sample));
     HIPCHK(launch_augment(a, nch, nb, (hipStream_t)stream));
+  }
+  return DMM_OK;
+}
+
+// ---- raw frames to training tensors (prepare.hip) ----
+// why the three entry points would refuse these sizes ("" = they would not)
+static std::string prep_sizes_refusal(int B, int H, int W, int pool) {
+  if (B < 1 || H < 1 || W < 1 || pool < 1) return "B, H, W and pool must be >= 1";
+  if (H % pool || W % pool) return "H and W must be multiples of pool";
+  if ((long long)H * W >= (1ll << 31)) return "H * W must be < 2^31";
+  return "";
+}
+
+static std::string prep_offsets_refusal(const int32_t* offsets, int B) {
+  if (offsets[0] != 0) return "offsets[0] must be 0";
+  for (int b = 0; b < B; ++b)
+    if (offsets[b + 1] < offsets[b]) return "offsets must not decrease (at index " + std::to_string(b + 1) + ")";
+  if (offsets[B] > DMM_PREP_MAX_ITEMS) return "offsets[B] must be <= 2^31 / 256";
+  return "";
+}
+
+int dmm_prep_image(const uint8_t* src, int64_t src_batch_stride, float* dst, int64_t dst_batch_stride, int B, int H, int W, int C, int pool,
+                   void* stream) {
+  const std::string who = "dmm_prep_image: ";
+  if (!src || !dst) return fail(DMM_ERR_INVALID, who + "null argument");
+  if ((uintptr_t)dst % 4) return fail(DMM_ERR_INVALID, who + "dst must be 4-byte aligned");
+  const std::string why = prep_sizes_refusal(B, H, W, pool);
+  if (!why.empty()) return fail(DMM_ERR_INVALID, who + why);
+  if (C < 1 || C > 4) return fail(DMM_ERR_INVALID, who + "C must be in [1, 4]");
+  const int Ho = H / pool, Wo = W / pool;
+  if (src_batch_stride < (long long)H * W * C) return fail(DMM_ERR_INVALID, who + "src_batch_stride must be >= H * W * C");
+  if (dst_batch_stride < (long long)C * Ho * Wo) return fail(DMM_ERR_INVALID, who + "dst_batch_stride must be >= C * Ho * Wo");
+  PrepImageArgs a;
+  memset(&a, 0, sizeof(a));
+  a.src = src; a.dst = dst; a.src_stride = src_batch_stride; a.dst_stride = dst_batch_stride;
+  a.H = H; a.W = W; a.C = C; a.Ho = Ho; a.Wo = Wo; a.p = pool;
+  for (int b0 = 0; b0 < B; b0 += DMM_PREP_LAUNCH_BATCH) {
+    a.b0 = b0;
+    HIPCHK(launch_prep_image(a, std::min(DMM_PREP_LAUNCH_BATCH, B - b0), (hipStream_t)stream));
+  }
+  return DMM_OK;
+}
+
+size_t dmm_prep_lidar_workspace(int B, int H, int W) {
+  if (!prep_sizes_refusal(B, H, W, 1).empty()) return 0;
+  return ((size_t)B * (size_t)H * (size_t)W * 4 + 15) / 16 * 16;
+}
+
+int dmm_prep_lidar(const float* points, const int32_t* offsets, float* dst, int64_t dst_batch_stride, int B, int H, int W, int pool,
+                   int kernel_size, void* workspace, size_t workspace_bytes, void* stream) {
+  const std::string who = "dmm_prep_lidar: ";
+  if (!offsets || !dst || !workspace) return fail(DMM_ERR_INVALID, who + "null argument");
+  if ((uintptr_t)points % 4 || (uintptr_t)dst % 4) return fail(DMM_ERR_INVALID, who + "points / dst must be 4-byte aligned");
+  if ((uintptr_t)workspace % 16) return fail(DMM_ERR_INVALID, who + "workspace must be 16-byte aligned");
+  const std::string why = prep_sizes_refusal(B, H, W, pool);
+  if (!why.empty()) return fail(DMM_ERR_INVALID, who + why);
+  if (pool >= 2 && H < 2 * pool) return fail(DMM_ERR_INVALID, who + "H must be >= 2 * pool");
+  if (kernel_size < 1 || kernel_size > 15 || kernel_size % 2 == 0) return fail(DMM_ERR_INVALID, who + "kernel_size must be odd and in [1, 15]");
+  const int Ho = H / pool, Wo = W / pool;
+  if (dst_batch_stride < (long long)Ho * Wo) return fail(DMM_ERR_INVALID, who + "dst_batch_stride must be >= Ho * Wo");
+  const std::string bad = prep_offsets_refusal(offsets, B);
+  if (!bad.empty()) return fail(DMM_ERR_INVALID, who + bad);
+  if (offsets[B] > 0 && !points) return fail(DMM_ERR_INVALID, who + "null points");
+  const size_t need = dmm_prep_lidar_workspace(B, H, W);
+  if (workspace_bytes < need) return fail(DMM_ERR_INVALID, who + "workspace_bytes is below dmm_prep_lidar_workspace (" + std::to_string(need) + ")");
+  PrepLidarArgs a;
+  memset(&a, 0, sizeof(a));
+  a.points = points; a.owner = (int*)workspace; a.dst = dst; a.dst_stride = dst_batch_stride;
+  a.H = H; a.W = W; a.Ho = Ho; a.Wo = Wo; a.p = pool; a.k = kernel_size;
+  HIPCHK(hipMemsetAsync(workspace, 0xFF, (size_t)B * (size_t)H * (size_t)W * 4, (hipStream_t)stream));   // every owner: -1
+  for (int b0 = 0; b0 < B; b0 += DMM_PREP_LAUNCH_BATCH) {
+    a.b0 = b0; a.nb = std::min(DMM_PREP_LAUNCH_BATCH, B - b0);
+    memcpy(a.off, offsets + b0, (size_t)(a.nb + 1) * sizeof(int32_t));
+    HIPCHK(launch_prep_lidar(a, (hipStream_t)stream));
+  }
+  return DMM_OK;
+}
+
+int dmm_prep_heat_maps(const dmm_prep_box* boxes, const int32_t* offsets, float* dst, int64_t dst_batch_stride, int B, int H, int W, int pool,
+                       void* stream) {
+  const std::string who = "dmm_prep_heat_maps: ";
+  if (!offsets || !dst) return fail(DMM_ERR_INVALID, who + "null argument");
+  if ((uintptr_t)boxes % 4 || (uintptr_t)dst % 4) return fail(DMM_ERR_INVALID, who + "boxes / dst must be 4-byte aligned");
+  const std::string why = prep_sizes_refusal(B, H, W, pool);
+  if (!why.empty()) return fail(DMM_ERR_INVALID, who + why);
+  const int Ho = H / pool, Wo = W / pool;
+  if (dst_batch_stride < 3ll * Ho * Wo) return fail(DMM_ERR_INVALID, who + "dst_batch_stride must be >= 3 * Ho * Wo");
+  const std::string bad = prep_offsets_refusal(offsets, B);
+  if (!bad.empty()) return fail(DMM_ERR_INVALID, who + bad);
+  if (offsets[B] > 0 && !boxes) return fail(DMM_ERR_INVALID, who + "null boxes");
+  PrepHeatArgs a;
+  memset(&a, 0, sizeof(a));
+  a.boxes = boxes; a.dst = dst; a.dst_stride = dst_batch_stride;
+  a.H = H; a.W = W; a.Ho = Ho; a.Wo = Wo; a.p = pool;
+  for (int b0 = 0; b0 < B; b0 += DMM_PREP_LAUNCH_BATCH) {
+    a.b0 = b0; a.nb = std::min(DMM_PREP_LAUNCH_BATCH, B - b0);
+    memcpy(a.off, offsets + b0, (size_t)(a.nb + 1) * sizeof(int32_t));
+    HIPCHK(launch_prep_heat(a, (hipStream_t)stream));
   }
   return DMM_OK;
 }

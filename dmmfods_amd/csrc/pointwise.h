@@ -162,6 +162,35 @@ struct AugArgs {           // by value (about 2.9 KB), so a launch needs no uplo
   dmm_aug_sample s[AUG_LAUNCH_BATCH];   // gridDim.z of them: samples b0 ...
 };
 
+// ---- raw frames to training tensors (prepare.hip) ----
+constexpr int PREP_LAUNCH_BATCH = DMM_PREP_LAUNCH_BATCH;
+constexpr int PREP_TILE = 16;          // a workgroup of the heat-map launch owns PREP_TILE x PREP_TILE output pixels
+constexpr int PREP_BOX_CHUNK = 256;    // list entries it culls into LDS at a time
+struct PrepImageArgs {
+  const unsigned char* src;            // (B, H, W, C) uint8; sample b: + b * src_stride bytes
+  float* dst;                          // (B, C, Ho, Wo); sample b: + b * dst_stride elements
+  long long src_stride, dst_stride;
+  int H, W, C, Ho, Wo, p;
+  int b0;                              // sample of blockIdx.z == 0
+};
+struct PrepLidarArgs {
+  const float* points;                 // (n, 3): x, y, d
+  int* owner;                          // (B, H, W): the highest covering point index, -1 where none
+  float* dst;                          // (B, 1, Ho, Wo)
+  long long dst_stride;
+  int H, W, Ho, Wo, p, k;
+  int b0, nb;                          // samples b0 .. b0 + nb - 1
+  int off[PREP_LAUNCH_BATCH + 1];      // their point ranges: sample b0 + s owns [off[s], off[s + 1])
+};
+struct PrepHeatArgs {
+  const dmm_prep_box* boxes;
+  float* dst;                          // (B, 3, Ho, Wo)
+  long long dst_stride;
+  int H, W, Ho, Wo, p;
+  int b0, nb;
+  int off[PREP_LAUNCH_BATCH + 1];      // box ranges, as above
+};
+
 struct ApplyCorrArgs {
   void* g;        // T gradient, pixel stride ldg: g += (q + ql) + (r + rl) * y
   const void* y;  // T forward tensor, pixel stride ldy
@@ -312,6 +341,14 @@ int logit_hist_grid_x(int planes, size_t plane);   // workgroups per (b, n) plan
 // one launch: gridDim = (augment_grid_x(Ho, Wo), nchannels, nsamples <= AUG_LAUNCH_BATCH)
 hipError_t launch_augment(const AugArgs& a, int nchannels, int nsamples, hipStream_t st);
 unsigned augment_grid_x(int Ho, int Wo);   // workgroups per plane: one lane per four output pixels of a row
+// raw frames to training tensors: one launch each for nsamples / a.nb <= PREP_LAUNCH_BATCH samples (the LiDAR form: the splat, unless
+// the samples have no point between them, then the pool; the owner planes are cleared by the caller)
+hipError_t launch_prep_image(const PrepImageArgs& a, int nsamples, hipStream_t st);   // grid (prep_plane_grid_x, C, nsamples)
+hipError_t launch_prep_lidar(const PrepLidarArgs& a, hipStream_t st);                 // (prep_splat_grid_x), then (prep_plane_grid_x, nb)
+hipError_t launch_prep_heat(const PrepHeatArgs& a, hipStream_t st);                   // grid (prep_heat_grid_x, nb)
+unsigned prep_plane_grid_x(int Ho, int Wo);        // one lane per output pixel
+unsigned prep_splat_grid_x(int npoints, int k);    // one lane per (point, window pixel)
+unsigned prep_heat_grid_x(int Ho, int Wo);         // one workgroup per PREP_TILE x PREP_TILE tile
 hipError_t launch_grad_sumsq(const GradSumsqArgs& a, hipStream_t st);
 hipError_t launch_guard_finalize(const GuardFinalizeArgs& a, hipStream_t st);
 // the one Adam launch.  a.state == nullptr: every class's step_size / bc2_sqrt / active and a.grad_scale come filled; a.state set: the

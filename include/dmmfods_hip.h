@@ -18,6 +18,10 @@
  *                                          flip, shift, per-channel gain and bias of a device batch in one launch
  *   dmm_heat_components .................. nothing upstream (the reference cannot "compute IoU per bounding box", helper.py:311-315):
  *                                          connected components of a thresholded heat map, one record per object
+ *   dmm_prep_image / dmm_prep_lidar / dmm_prep_heat_maps
+ *                                          avgpool_tensor / lidar_array_to_image_like_tensor + pool_lidar_tensor /
+ *                                          create_ground_truth_maps + maxpool_tensor  utils/Dense_U_Net_lidar_helper.py:233-305,430-515:
+ *                                          the host-side preparation of a frame's seven planes, on the device and bit for bit
  *   dmm_adam_step ........................ torch.optim.Adam.step        agents/Dense_U_Net_lidar_Agent.py:57-61,265
  *   dmm_adam_table_* / dmm_adam_step_segmented / dmm_adam_step_guarded_segmented
  *                                          torch.optim.Adam built over PARAMETER GROUPS (the list-of-dicts form of the constructor
@@ -246,6 +250,61 @@ int dmm_heat_components(const float* maps, int B, int NC, int H, int W, float th
                         dmm_component* records /* device, [B*NC][max_per_plane] */,
                         int32_t* counts /* device, [B*NC]: the TRUE number of components, may exceed max_per_plane */,
                         void* stream);
+
+/* ---- raw frames to training tensors: image, LiDAR points and boxes become the (B, 7, Ho, Wo) batch on the device ----
+ * (Upstream this is host code: avgpool_tensor / lidar_array_to_image_like_tensor / pool_lidar_tensor / create_ground_truth_maps /
+ * maxpool_tensor of utils/Dense_U_Net_lidar_helper.py, whose seven fp32 planes per frame the loader then copies to the device.)
+ * Three independent entry points; p = pool, Ho = H / p, Wo = W / p, H and W multiples of p.  Each dst is fp32 (B, channels, Ho, Wo)
+ * with planes contiguous and samples dst_batch_stride ELEMENTS apart, so the three outputs may be the channel slices 0:3, 3:4 and 4:7
+ * of one (B, 7, Ho, Wo) allocation.  Plain launches on `stream`: no plan, no synchronisation, nothing uploaded - `offsets` are HOST
+ * arrays of B + 1 entries that travel by value, DMM_PREP_LAUNCH_BATCH samples per launch.  Every dst element is written exactly once
+ * and nothing else is written (dmm_prep_lidar also writes its workspace); inputs are only read.  Every output is exact: independent
+ * of the launch geometry and bit-reproducible.  No floating-point atomics.  Address arithmetic is 64-bit: only H * W stays below 2^31.
+ *
+ * dmm_prep_image: src is uint8 (B, H, W, C), channel-last, C in 1..4, samples src_batch_stride BYTES apart.
+ *   out[b][c][i][j] = fdiv_rn(float(S), float(p * p)),  S the exact integer sum of the p x p block: one correctly rounded division
+ *   (torch.nn.AvgPool2d on the CPU; a multiplication with the reciprocal differs for p = 3, 10).  p == 1 is the plain cast.
+ *   ceil(B / 32) launches.
+ *
+ * dmm_prep_lidar: points is fp32 (n, 3) of (x, y, d), concatenated over the batch; sample b owns [offsets[b], offsets[b + 1]).
+ *   kernel_size k is odd, 1..15, s = (k - 1) / 2.  A point is valid iff x, y, d are finite and >= 0 (-0.0 is); any other writes nothing.
+ *   With cx = (int)x, cy = (int)y it covers rows [max(cy - s, 0), min(cy + s + 1, H - 1)) and columns [max(cx - s, 0),
+ *   min(cx + s + 1, W - 1)): the last row and column are never written (upstream's clip).  A pixel holds the d of the highest-indexed
+ *   point of its sample that covers it, -1 where none does.  e = 76 where the value is -1, else min(v, 75);
+ *   code = e <= 25 ? (e * -6.2f) + 255 : (e * -2) + 150, two fp32 roundings, never fused.  p >= 2 (needs H >= 2p): out[i][j] =
+ *   max(0, max of code over rows [r * p, r * p + 2p), columns [j * p, j * p + p)), r = min(i, Ho - 2) - upstream's
+ *   MaxPool2d((2p, p), stride p), one replicated bottom row and the clamp.  p == 1: out = max(0, code).
+ *   workspace: dmm_prep_lidar_workspace bytes of device memory, 16-byte aligned: an int32 owner plane per sample.  One
+ *   hipMemsetAsync, then per 32 samples the splat launch (an integer atomicMax per point and window pixel; none when those samples
+ *   have no point) and the pool launch.
+ *
+ * dmm_prep_heat_maps: boxes is an array of dmm_prep_box, concatenated over the batch, ranges from offsets as above.  type 1 -> plane
+ *   0, 2 -> plane 1, 4 -> plane 2; any other type and any box with width <= 0 or height <= 0 is ignored.  A full-resolution pixel
+ *   (Y, X) of a plane takes the pattern value of the LAST box of that class in list order with x <= X < x + width and y <= Y < y +
+ *   height (64-bit), 0 where there is none; boxes are clipped to the image, the pattern stays relative to the unclipped corner.
+ *   Pattern at r = Y - y, c = X - x, hf = height / 5, wf = width / 4: types 1 and 4 give 1; type 2, side = (c < wf || c >= 3 * wf):
+ *   r < hf && side -> 0.3f;  else r >= 3 * hf -> side ? 0.5f : 0.75f;  else 1.  The output pixel is the maximum over its p x p block.
+ *   No cap on boxes per sample.  ceil(B / 32) launches.
+ *
+ * Each refuses with DMM_ERR_INVALID, before any HIP call, its own name in front of the message: a null pointer (points / boxes may be
+ * null when the batch has none); src, dst, points, boxes not aligned to their element (1 / 4 bytes); B, H, W or pool < 1; H or W no
+ * multiple of pool; H < 2 * pool for LiDAR with pool >= 2; H * W >= 2^31; C outside 1..4; kernel_size even or outside 1..15; a batch
+ * stride below one sample; offsets[0] != 0, decreasing offsets, a total above 2^31 / 256; a workspace that is null, not 16-byte
+ * aligned or smaller than dmm_prep_lidar_workspace. */
+#define DMM_PREP_LAUNCH_BATCH 32   /* samples whose offsets travel by value with one launch */
+#define DMM_PREP_MAX_ITEMS (1 << 23)   /* 2^31 / 256: points, or boxes, of one call */
+typedef struct dmm_prep_box {
+  int32_t type;            /*  0: 1 vehicle, 2 pedestrian, 4 cyclist (upstream's label dict) */
+  int32_t x, y;            /*  4, 8: top-left corner, full-resolution pixels; may lie outside the image */
+  int32_t width, height;   /* 12, 16 */
+} dmm_prep_box;            /* 20 bytes */
+int dmm_prep_image(const uint8_t* src, int64_t src_batch_stride /* bytes */, float* dst, int64_t dst_batch_stride,
+                   int B, int H, int W, int C, int pool, void* stream);
+size_t dmm_prep_lidar_workspace(int B, int H, int W);   /* bytes; 0 for refused arguments */
+int dmm_prep_lidar(const float* points, const int32_t* offsets /* host, B + 1 */, float* dst, int64_t dst_batch_stride,
+                   int B, int H, int W, int pool, int kernel_size, void* workspace, size_t workspace_bytes, void* stream);
+int dmm_prep_heat_maps(const dmm_prep_box* boxes, const int32_t* offsets /* host, B + 1 */, float* dst, int64_t dst_batch_stride,
+                       int B, int H, int W, int pool, void* stream);
 
 /* Backward from an externally computed d(loss)/d(logit) (B,num_classes,H,W fp32), e.g. from torch autograd of any
  * loss on the returned logits (reference: loss.backward(...), agents/Dense_U_Net_lidar_Agent.py:264). */

@@ -53,6 +53,9 @@
 // DRIVE_COMPONENTS=1 (life-cycle run): behind the lives (and the calls of the two switches above), dmm_heat_components on three shapes with
 // operands that are addresses only - seven launches each, every grid against a restatement of the tiling, the workspace carve-up inside
 // workspace_bytes - and every refusal of the entry point, each with nothing enqueued (components_main).
+// DRIVE_PREPARE=1 (life-cycle run): behind the lives (and the calls of the three switches above), dmm_prep_image, dmm_prep_lidar and
+// dmm_prep_heat_maps on B = 1, 33 and 65 samples at pool 10 and 1 - the launches counted, every grid against a restatement, the memset of
+// the owner planes inside workspace_bytes - and every refusal of the three entry points, each with nothing enqueued (prepare_main).
 // Launch coalescing (dmm_set_option("batch_wgrad"), on by default; DRIVE_OPTIONS_OFF=batch_wgrad runs one launch per record,
 // DRIVE_BATCH_WGRAD=<0|1|2> sets the option's value: 2 = grouped on the weight-gradient stream instead of the caller's): every
 // life-cycle run watches the enqueue calls through the fake runtime's hook and checks, with the option on or off, that
@@ -1269,6 +1272,162 @@ static int components_main() {
 }
 #endif
 
+// ---- DRIVE_PREPARE: dmm_prep_image / dmm_prep_lidar / dmm_prep_heat_maps (built against a csrc that has none: the case does not exist) ----
+#ifdef DMM_PREP_LAUNCH_BATCH
+// B = 1, 33 and 65 samples of 40 x 30 at pool 10 and 1, the three outputs slices of one (B, 7, Ho, Wo) batch.  src, points, boxes and dst
+// are addresses only; the LiDAR workspace is real memory of exactly dmm_prep_lidar_workspace bytes with a guard band behind it, because
+// the runtime's memset does run here: it must set B * H * W * 4 bytes to 0xFF and nothing behind them.  Per call the launches are
+// counted and each grid is held against a restatement.  Samples 33 and up have no points: a chunk without points makes no splat launch.
+// Then every refusal of the three entry points, each with nothing enqueued.
+static int prepare_main() {
+  int bad = 0;
+  g_hist = HistWatch();
+  g_hist.on = true;
+  const int H = 40, W = 30, C = 3, K = 5;
+  for (int B : {1, 33, 65})
+    for (int p : {10, 1}) {
+      const int Ho = H / p, Wo = W / p, chunks = (B + DMM_PREP_LAUNCH_BATCH - 1) / DMM_PREP_LAUNCH_BATCH;
+      const size_t plane = (size_t)Ho * Wo;
+      const uint8_t* src = (const uint8_t*)reserve((size_t)B * H * W * C, PROT_NONE);
+      float* dst = (float*)reserve((size_t)B * 7 * plane * 4, PROT_NONE);
+      std::vector<int32_t> po(B + 1), bo(B + 1);
+      for (int b = 0; b <= B; ++b) { po[b] = 7 * std::min(b, 33); bo[b] = 3 * b; }   // samples 33 .. 64 have no points: the third chunk has none
+      const float* pts = (const float*)reserve((size_t)po[B] * 12 + 4096, PROT_NONE);
+      const dmm_prep_box* boxes = (const dmm_prep_box*)reserve((size_t)bo[B] * sizeof(dmm_prep_box) + 4096, PROT_NONE);
+      const size_t wsb = dmm_prep_lidar_workspace(B, H, W);
+      bool ok = wsb == ((size_t)B * H * W * 4 + 15) / 16 * 16;
+      unsigned char* ws = (unsigned char*)aligned_alloc(16, wsb + 64);
+      memset(ws, 0x5a, wsb + 64);
+      {
+        const HistWatch w0 = g_hist;
+        g_launch_log.clear();
+        MUST(dmm_prep_image(src, (int64_t)H * W * C, dst, (int64_t)(7 * plane), B, H, W, C, p, nullptr));
+        ok = ok && g_hist.launches == w0.launches + chunks && g_hist.memsets == w0.memsets && g_hist.other == w0.other;
+        for (const LaunchSeen& l : g_launch_log)
+          ok = ok && l.kernel.find("prep_image_kernel") != std::string::npos && l.gx == (unsigned)((plane + 255) / 256) && l.gx == prep_plane_grid_x(Ho, Wo) && l.gy == (unsigned)C;
+      }
+      {
+        const HistWatch w0 = g_hist;
+        g_launch_log.clear();
+        MUST(dmm_prep_lidar(pts, po.data(), dst + 3 * plane, (int64_t)(7 * plane), B, H, W, p, K, ws, wsb, nullptr));
+        int splats = 0;   // chunks that own a point
+        for (int b0 = 0; b0 < B; b0 += DMM_PREP_LAUNCH_BATCH) splats += po[std::min(B, b0 + DMM_PREP_LAUNCH_BATCH)] > po[b0];
+        ok = ok && g_hist.launches == w0.launches + chunks + splats && g_hist.memsets == w0.memsets + 1 && g_hist.other == w0.other &&
+             g_hist.memset_bytes == (unsigned long long)B * H * W * 4 && splats == std::min(chunks, 2);
+        size_t n = 0;
+        for (int b0 = 0; b0 < B && ok; b0 += DMM_PREP_LAUNCH_BATCH) {
+          const int nb = std::min(DMM_PREP_LAUNCH_BATCH, B - b0), np = po[b0 + nb] - po[b0];
+          if (np > 0) {
+            ok = ok && n < g_launch_log.size() && g_launch_log[n].kernel.find("prep_lidar_splat_kernel") != std::string::npos &&
+                 g_launch_log[n].gx == (unsigned)(((size_t)np * K * K + 255) / 256) && g_launch_log[n].gx == prep_splat_grid_x(np, K);
+            ++n;
+          }
+          ok = ok && n < g_launch_log.size() && g_launch_log[n].kernel.find("prep_lidar_pool_kernel") != std::string::npos &&
+               g_launch_log[n].gx == prep_plane_grid_x(Ho, Wo) && g_launch_log[n].gy == (unsigned)nb;
+          ++n;
+        }
+        // the carve-up: the owner planes fill the front of the workspace, the guard band behind workspace_bytes is untouched
+        for (size_t i = 0; i < (size_t)B * H * W * 4; ++i) ok = ok && ws[i] == 0xFF;
+        for (size_t i = wsb; i < wsb + 64; ++i) ok = ok && ws[i] == 0x5a;
+      }
+      {
+        const HistWatch w0 = g_hist;
+        g_launch_log.clear();
+        MUST(dmm_prep_heat_maps(boxes, bo.data(), dst + 4 * plane, (int64_t)(7 * plane), B, H, W, p, nullptr));
+        ok = ok && g_hist.launches == w0.launches + chunks && g_hist.memsets == w0.memsets && g_hist.other == w0.other;
+        const unsigned tiles = (unsigned)((Ho + 15) / 16) * (unsigned)((Wo + 15) / 16);
+        int b0 = 0;
+        for (const LaunchSeen& l : g_launch_log) {
+          ok = ok && l.kernel.find("prep_heat_kernel") != std::string::npos && l.gx == tiles && l.gx == prep_heat_grid_x(Ho, Wo) &&
+               l.gy == (unsigned)std::min(DMM_PREP_LAUNCH_BATCH, B - b0);
+          b0 += DMM_PREP_LAUNCH_BATCH;
+        }
+      }
+      printf("PREPARE %d samples pool %d: workspace %zu %s\n", B, p, wsb, ok ? "ok" : "WRONG");
+      bad += !ok;
+      free(ws);
+    }
+  // the refusals: nothing reaches the runtime, the message starts with the entry point's name and names the argument
+  const uint8_t* src = (const uint8_t*)reserve(1 << 20, PROT_NONE);
+  float* dst = (float*)reserve(1 << 20, PROT_NONE);
+  const float* pts = (const float*)reserve(1 << 20, PROT_NONE);
+  const dmm_prep_box* bx = (const dmm_prep_box*)reserve(1 << 20, PROT_NONE);
+  void* ws = reserve(1 << 20, PROT_NONE);
+  const int32_t off[3] = {0, 2, 5}, off_first[3] = {1, 2, 5}, off_desc[3] = {0, 3, 2}, off_big[3] = {0, 2, DMM_PREP_MAX_ITEMS + 1};
+  const size_t wsb = dmm_prep_lidar_workspace(2, 40, 30);
+  const HistWatch w0 = g_hist;
+  const char* who = "";
+  auto refused = [&](int rc, const char* names) {
+    if (rc == DMM_ERR_INVALID && strncmp(dmm_last_error(), who, strlen(who)) == 0 && strstr(dmm_last_error(), names) != nullptr) return;
+    fprintf(stderr, "[drive] %snot refused (%d) or the message does not say '%s': %s\n", who, rc, names, dmm_last_error());
+    ++bad;
+  };
+  auto off_by = [](auto* p, int bytes) { return (decltype(p))((char*)p + bytes); };
+  who = "dmm_prep_image: ";
+  refused(dmm_prep_image(nullptr, 3600, dst, 36, 2, 40, 30, 3, 10, nullptr), "null");
+  refused(dmm_prep_image(src, 3600, nullptr, 36, 2, 40, 30, 3, 10, nullptr), "null");
+  refused(dmm_prep_image(src, 3600, off_by(dst, 2), 36, 2, 40, 30, 3, 10, nullptr), "4-byte aligned");
+  refused(dmm_prep_image(src, 3600, dst, 36, 0, 40, 30, 3, 10, nullptr), ">= 1");
+  refused(dmm_prep_image(src, 3600, dst, 36, 2, 0, 30, 3, 10, nullptr), ">= 1");
+  refused(dmm_prep_image(src, 3600, dst, 36, 2, 40, -30, 3, 10, nullptr), ">= 1");
+  refused(dmm_prep_image(src, 3600, dst, 36, 2, 40, 30, 3, 0, nullptr), ">= 1");
+  refused(dmm_prep_image(src, 3600, dst, 36, 2, 45, 30, 3, 10, nullptr), "multiples of pool");
+  refused(dmm_prep_image(src, 3600, dst, 36, 2, 40, 35, 3, 10, nullptr), "multiples of pool");
+  refused(dmm_prep_image(src, 1ll << 33, dst, 1ll << 33, 1, 65536, 32768, 3, 1, nullptr), "H * W");
+  refused(dmm_prep_image(src, 3600, dst, 36, 2, 40, 30, 0, 10, nullptr), "C must be");
+  refused(dmm_prep_image(src, 6000, dst, 60, 2, 40, 30, 5, 10, nullptr), "C must be");
+  refused(dmm_prep_image(src, 3599, dst, 36, 2, 40, 30, 3, 10, nullptr), "src_batch_stride");
+  refused(dmm_prep_image(src, 3600, dst, 35, 2, 40, 30, 3, 10, nullptr), "dst_batch_stride");
+  who = "dmm_prep_lidar: ";
+  refused(dmm_prep_lidar(nullptr, off, dst, 12, 2, 40, 30, 10, 5, ws, wsb, nullptr), "null points");
+  refused(dmm_prep_lidar(pts, nullptr, dst, 12, 2, 40, 30, 10, 5, ws, wsb, nullptr), "null");
+  refused(dmm_prep_lidar(pts, off, nullptr, 12, 2, 40, 30, 10, 5, ws, wsb, nullptr), "null");
+  refused(dmm_prep_lidar(pts, off, dst, 12, 2, 40, 30, 10, 5, nullptr, wsb, nullptr), "null");
+  refused(dmm_prep_lidar(off_by(pts, 2), off, dst, 12, 2, 40, 30, 10, 5, ws, wsb, nullptr), "4-byte aligned");
+  refused(dmm_prep_lidar(pts, off, off_by(dst, 1), 12, 2, 40, 30, 10, 5, ws, wsb, nullptr), "4-byte aligned");
+  refused(dmm_prep_lidar(pts, off, dst, 12, 2, 40, 30, 10, 5, off_by(ws, 8), wsb, nullptr), "16-byte aligned");
+  refused(dmm_prep_lidar(pts, off, dst, 12, 0, 40, 30, 10, 5, ws, wsb, nullptr), ">= 1");
+  refused(dmm_prep_lidar(pts, off, dst, 12, 2, 40, 0, 10, 5, ws, wsb, nullptr), ">= 1");
+  refused(dmm_prep_lidar(pts, off, dst, 12, 2, 40, 30, -1, 5, ws, wsb, nullptr), ">= 1");
+  refused(dmm_prep_lidar(pts, off, dst, 12, 2, 40, 33, 10, 5, ws, wsb, nullptr), "multiples of pool");
+  refused(dmm_prep_lidar(pts, off, dst, 3, 2, 10, 30, 10, 5, ws, wsb, nullptr), "2 * pool");
+  refused(dmm_prep_lidar(pts, off, dst, 1ll << 33, 1, 65536, 32768, 1, 5, ws, wsb, nullptr), "H * W");
+  refused(dmm_prep_lidar(pts, off, dst, 12, 2, 40, 30, 10, 4, ws, wsb, nullptr), "kernel_size");
+  refused(dmm_prep_lidar(pts, off, dst, 12, 2, 40, 30, 10, 17, ws, wsb, nullptr), "kernel_size");
+  refused(dmm_prep_lidar(pts, off, dst, 12, 2, 40, 30, 10, -1, ws, wsb, nullptr), "kernel_size");
+  refused(dmm_prep_lidar(pts, off, dst, 11, 2, 40, 30, 10, 5, ws, wsb, nullptr), "dst_batch_stride");
+  refused(dmm_prep_lidar(pts, off_first, dst, 12, 2, 40, 30, 10, 5, ws, wsb, nullptr), "offsets[0]");
+  refused(dmm_prep_lidar(pts, off_desc, dst, 12, 2, 40, 30, 10, 5, ws, wsb, nullptr), "must not decrease");
+  refused(dmm_prep_lidar(pts, off_big, dst, 12, 2, 40, 30, 10, 5, ws, wsb, nullptr), "2^31 / 256");
+  refused(dmm_prep_lidar(pts, off, dst, 12, 2, 40, 30, 10, 5, ws, wsb - 1, nullptr), "workspace_bytes");
+  refused(dmm_prep_lidar(pts, off, dst, 12, 2, 40, 30, 10, 5, ws, 0, nullptr), "workspace_bytes");
+  who = "dmm_prep_heat_maps: ";
+  refused(dmm_prep_heat_maps(nullptr, off, dst, 36, 2, 40, 30, 10, nullptr), "null boxes");
+  refused(dmm_prep_heat_maps(bx, nullptr, dst, 36, 2, 40, 30, 10, nullptr), "null");
+  refused(dmm_prep_heat_maps(bx, off, nullptr, 36, 2, 40, 30, 10, nullptr), "null");
+  refused(dmm_prep_heat_maps(off_by(bx, 2), off, dst, 36, 2, 40, 30, 10, nullptr), "4-byte aligned");
+  refused(dmm_prep_heat_maps(bx, off, off_by(dst, 3), 36, 2, 40, 30, 10, nullptr), "4-byte aligned");
+  refused(dmm_prep_heat_maps(bx, off, dst, 36, -2, 40, 30, 10, nullptr), ">= 1");
+  refused(dmm_prep_heat_maps(bx, off, dst, 36, 2, 0, 30, 10, nullptr), ">= 1");
+  refused(dmm_prep_heat_maps(bx, off, dst, 36, 2, 40, 30, 0, nullptr), ">= 1");
+  refused(dmm_prep_heat_maps(bx, off, dst, 36, 2, 40, 30, 7, nullptr), "multiples of pool");
+  refused(dmm_prep_heat_maps(bx, off, dst, 1ll << 34, 1, 65536, 32768, 1, nullptr), "H * W");
+  refused(dmm_prep_heat_maps(bx, off, dst, 35, 2, 40, 30, 10, nullptr), "dst_batch_stride");
+  refused(dmm_prep_heat_maps(bx, off_first, dst, 36, 2, 40, 30, 10, nullptr), "offsets[0]");
+  refused(dmm_prep_heat_maps(bx, off_desc, dst, 36, 2, 40, 30, 10, nullptr), "must not decrease");
+  refused(dmm_prep_heat_maps(bx, off_big, dst, 36, 2, 40, 30, 10, nullptr), "2^31 / 256");
+  if (g_hist.launches != w0.launches || g_hist.memsets != w0.memsets || g_hist.other != w0.other) { fprintf(stderr, "[drive] a refused dmm_prep_* call reached the runtime\n"); ++bad; }
+  if (wsb != 2 * 40 * 30 * 4 || dmm_prep_lidar_workspace(0, 8, 8) || dmm_prep_lidar_workspace(1, 0, 8) || dmm_prep_lidar_workspace(1, 8, -8) ||
+      dmm_prep_lidar_workspace(1, 65536, 32768) || dmm_prep_lidar_workspace(1, 3, 1) != 16) {
+    fprintf(stderr, "[drive] dmm_prep_lidar_workspace\n"); ++bad;
+  }
+  g_hist.on = false;
+  hipDeviceSynchronize();
+  printf("%s\n", bad ? "PREPARE FAILED" : "PREPARE OK");
+  return bad ? 1 : 0;
+}
+#endif
+
 int main(int argc, char** argv) {
   g_enqueue.on =getenv("DRIVE_TRACE_ENQUEUE") != nullptr;
   fakehip_set_hook(drive_hook);
@@ -1311,6 +1470,9 @@ int main(int argc, char** argv) {
 #endif
 #ifdef DMM_CC_TILE_H
   if (getenv("DRIVE_COMPONENTS") && components_main() != 0) rc = 1;
+#endif
+#ifdef DMM_PREP_LAUNCH_BATCH
+  if (getenv("DRIVE_PREPARE") && prepare_main() != 0) rc = 1;
 #endif
   if (g_bad) { fprintf(stderr, "[drive] FAIL: %ld device pointers outside the caller's regions\n", g_bad); rc = 1; }
   if (fakehip_violations()) { fprintf(stderr, "[drive] FAIL: %ld teardown / handle violations\n", fakehip_violations()); rc = 1; }
