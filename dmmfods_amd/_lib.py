@@ -78,6 +78,24 @@ class AugSample(C.Structure):
 
 assert C.sizeof(AugTensor) == 32 and C.sizeof(AugSample) == 80
 
+# DMM_WARP_NEAREST, DMM_WARP_BILINEAR, DMM_WARP_FRAC_BITS, DMM_WARP_LAUNCH_BATCH, DMM_WARP_MAX_A, DMM_WARP_MAX_B
+WARP_NEAREST, WARP_BILINEAR, WARP_FRAC_BITS, WARP_LAUNCH_BATCH, WARP_MAX_A, WARP_MAX_B = 0, 1, 20, 32, 64 << 20, 1 << 50
+
+
+class WarpTensor(C.Structure):
+    """dmm_warp_tensor: one tensor of a dmm_warp_batch call; as AugTensor, with the way it is sampled."""
+    _fields_ = [("src", C.c_void_p), ("dst", C.c_void_p), ("src_batch_stride", C.c_int64), ("channels", C.c_int32), ("mode", C.c_int32),
+                ("reserved", C.c_int32 * 2)]
+
+
+class WarpSample(C.Structure):
+    """dmm_warp_sample: one sample's affine map (x, y) -> (a00 x + a01 y + b0, a10 x + a11 y + b1) in Q20 and per-channel gain / bias."""
+    _fields_ = [("a00", C.c_int32), ("a01", C.c_int32), ("a10", C.c_int32), ("a11", C.c_int32), ("b0", C.c_int64), ("b1", C.c_int64),
+                ("gain", C.c_float * AUG_MAX_CHANNELS), ("bias", C.c_float * AUG_MAX_CHANNELS)]
+
+
+assert C.sizeof(WarpTensor) == 40 and C.sizeof(WarpSample) == 96
+
 CC_TILE_H, CC_TILE_W, CC_MAX_PER_PLANE = 32, 32, 65536   # DMM_CC_TILE_H, DMM_CC_TILE_W, DMM_CC_MAX_PER_PLANE
 
 
@@ -160,6 +178,8 @@ def lib():
     L.dmm_logit_hist.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int, f32, C.c_int, vp, vp]
     L.dmm_augment_batch.argtypes = [C.POINTER(AugTensor), C.c_int, C.POINTER(AugSample), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                     C.POINTER(C.c_float), vp]
+    L.dmm_warp_batch.argtypes = [C.POINTER(WarpTensor), C.c_int, C.POINTER(WarpSample), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                 C.POINTER(C.c_float), vp]
     L.dmm_heat_components_workspace.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]
     L.dmm_heat_components_workspace.restype = sz
     L.dmm_heat_components.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, f32, C.c_int, C.c_int, vp, sz, vp, vp, vp, vp]
@@ -229,7 +249,7 @@ EXPORTS = [
     "dmm_adam_table_bytes", "dmm_adam_table_init", "dmm_adam_step_segmented", "dmm_adam_step_guarded_segmented",
     "dmm_adam_step_segmented_ema", "dmm_adam_step_guarded_segmented_ema",
     "dmm_plan_wgrad_batch_counts", "dmm_conv_wgrad_grouped", "dmm_bw1_reduce_grouped",
-    "dmm_logit_hist_elems", "dmm_logit_hist", "dmm_augment_batch",
+    "dmm_logit_hist_elems", "dmm_logit_hist", "dmm_augment_batch", "dmm_warp_batch",
     "dmm_heat_components_workspace", "dmm_heat_components",
     "dmm_prep_image", "dmm_prep_lidar_workspace", "dmm_prep_lidar", "dmm_prep_heat_maps",
 ]

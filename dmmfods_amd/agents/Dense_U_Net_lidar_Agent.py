@@ -236,10 +236,15 @@ class Dense_U_Net_lidar_Agent:
     @staticmethod
     def _make_augment(spec):
         """spec: None (no augmentation) or a dict of BatchAugment's arguments.  The model takes sizes that are multiples of 32, so
-        out_size has to be one; rank defaults to this process's torch.distributed rank, so that every rank draws its own parameters."""
+        out_size has to be one; rank defaults to this process's torch.distributed rank, so that every rank draws its own parameters.
+        The field takes the whole-pixel arguments only: BatchAugment's `scale` and `rotate` are not wired through the
+        config yet and are refused like any unknown key - a caller who wants them sets `agent.augment` to a BatchAugment of their own."""
         if spec is None:
             return None
         kw = dict(spec)
+        for name in ("scale", "rotate"):
+            if name in kw:
+                raise TypeError(f"loader.augment got an unexpected keyword argument '{name}' (set agent.augment = BatchAugment(...) to zoom or rotate)")
         if "rank" not in kw and torch.distributed.is_available() and torch.distributed.is_initialized():
             kw["rank"] = torch.distributed.get_rank()
         aug = BatchAugment(**kw)

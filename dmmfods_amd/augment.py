@@ -4,7 +4,9 @@ loader yields).
 ``dmm_augment_batch`` (csrc/augment.hip) reads a per-sample window of every plane of image, LiDAR and target - cropped or shifted,
 optionally mirrored left-right, with a per-channel gain and bias - and writes new tensors, in one launch per 32 samples.  The
 rearrangements are label-preserving: the three tensors move together, the heat-map values are left-right symmetric, and targets
-never get a gain or a bias.  The parameters are drawn on the host from a counter-based generator, so batch number ``i`` of rank
+never get a gain or a bias.  With a ``scale`` or a ``rotate`` the launch is ``dmm_warp_batch`` (csrc/warp.hip) instead: the same
+window seen through a zoom and a rotation about its centre, a fixed-point affine map per sample; the image is interpolated
+bilinearly, LiDAR and target are sampled nearest, so a heat-map level stays a level and a LiDAR code is never averaged.  The parameters are drawn on the host from a counter-based generator, so batch number ``i`` of rank
 ``r`` has the same parameters wherever and whenever it is drawn; nothing is drawn on the device and nothing is synchronised."""
 import ctypes as C
 import math
@@ -16,6 +18,7 @@ import torch
 from . import _lib
 
 MAX_CHANNELS = _lib.AUG_MAX_CHANNELS
+WARP_ONE = 1 << _lib.WARP_FRAC_BITS
 
 
 def _pair(v, name):
@@ -44,6 +47,9 @@ class BatchAugment:
                     The gain of an image channel is contrast_draw * per_channel_draw (formed in double, rounded to fp32 once).
     lidar_dropout   probability that a sample's LiDAR tensor is blanked (gain 0, bias 0).
     image_dropout   the same for the image tensor; never the same sample as lidar_dropout (lidar_dropout + image_dropout <= 1).
+    scale           zoom factor s, uniform in [1 - scale, 1 + scale], one draw per sample; scale in [0, 63/64] (the launch takes matrix
+                    entries up to 64, and 1 / s is one).  s > 1 magnifies.
+    rotate          degrees, in [0, 180]; the angle is uniform in [-rotate, rotate], one draw per sample.
     fill            what a window shows outside the source: None (zeros), one number, or one number per channel (image channels,
                     then LiDAR, then target).  Gain and bias do not touch it.
     seed, rank      the generator's key.  Give every data-parallel rank its own `rank`.
@@ -61,11 +67,21 @@ class BatchAugment:
       7. channel gain  uniform(1 - channel_gain, 1 + channel_gain, (B, 8))      an image of C channels uses the first C columns
       8. brightness    uniform(-brightness, brightness, B)
       9. dropout       u = random(B):  u < lidar_dropout blanks the LiDAR tensor,  lidar_dropout <= u < lidar_dropout + image_dropout the image
+     10. zoom          uniform(1 - scale, 1 + scale, B)
+     11. angle         uniform(-rotate, rotate, B)              degrees
+    THE MAP.  Zoom and rotation act about the window's centre; today's window and flip follow.  For output pixel (x, y) of a sample with
+    zoom s and angle t, with u = x - (Wo - 1) / 2 and v = y - (Ho - 1) / 2:
+        (u', v') = (1 / s) R(t) (u, v),     R(t) = [[cos t, -sin t], [sin t, cos t]]
+        xw = u' + (Wo - 1) / 2;   yw = v' + (Ho - 1) / 2
+        sx = x0 + (flip ? Wo - 1 - xw : xw);   sy = y0 + yw
+    ``matrices`` forms the six coefficients of (x, y) -> (sx, sy) in double and rounds each with ``numpy.rint`` to Q20, the fixed point
+    of ``dmm_warp_batch``; at s = 1, t = 0 they are whole numbers and the map is the window's.  With scale == 0 and rotate == 0
+    ``__call__`` issues ``dmm_augment_batch`` as it always did; otherwise ``dmm_warp_batch`` with the image bilinear, LiDAR and target nearest.
     Targets always get gain 1 and bias 0.  ``__call__`` draws batch number ``batches_drawn`` and advances; ``state_dict`` carries
     that counter, so a resumed run continues the sequence."""
 
     def __init__(self, out_size=None, hflip=0.0, translate=(0, 0), brightness=0.0, contrast=0.0, channel_gain=0.0, lidar_dropout=0.0,
-                 image_dropout=0.0, fill=None, seed=0, rank=0):
+                 image_dropout=0.0, fill=None, seed=0, rank=0, scale=0.0, rotate=0.0):
         if out_size is not None:
             out_size = _pair(out_size, "out_size")
             if min(out_size) < 1:
@@ -84,6 +100,11 @@ class BatchAugment:
                 raise ValueError(f"{name} must lie in [0, 1)")
         if not (float(brightness) >= 0.0 and math.isfinite(float(brightness))):
             raise ValueError("brightness must be finite and >= 0")
+        if not 0.0 <= float(scale) <= 63.0 / 64.0:
+            raise ValueError("scale must lie in [0, 63/64]")
+        if not 0.0 <= float(rotate) <= 180.0:
+            raise ValueError("rotate is in degrees: it must lie in [0, 180]")
+        self.scale, self.rotate = float(scale), float(rotate)
         if fill is not None:
             fill = [float(fill)] if isinstance(fill, (int, float, np.number)) else [float(v) for v in fill]
             if not 1 <= len(fill) <= MAX_CHANNELS or not all(math.isfinite(v) for v in fill):
@@ -103,7 +124,8 @@ class BatchAugment:
 
     def params_at(self, i, B, Hs, Ws):
         """The parameters of batch number `i` (B samples of Hs x Ws); does not advance.  A namespace of numpy arrays over the samples:
-        y0, x0, flip (int32), image_gain (B, 8) and image_bias (B,) (float32), drop_lidar, drop_image (bool); out_size (Ho, Wo)."""
+        y0, x0, flip (int32), image_gain (B, 8) and image_bias (B,) (float32), drop_lidar, drop_image (bool), zoom and angle (float64, the
+        angle in degrees); out_size (Ho, Wo)."""
         i, B, Hs, Ws = int(i), int(B), int(Hs), int(Ws)
         if i < 0 or B < 1 or Hs < 1 or Ws < 1:
             raise ValueError("params_at(i, B, Hs, Ws): i >= 0 and B, Hs, Ws >= 1")
@@ -120,11 +142,13 @@ class BatchAugment:
         per_channel = rng.uniform(1.0 - self.channel_gain, 1.0 + self.channel_gain, (B, MAX_CHANNELS))
         bias = rng.uniform(-self.brightness, self.brightness, B)
         u = rng.random(B)
+        zoom = rng.uniform(1.0 - self.scale, 1.0 + self.scale, B)
+        angle = rng.uniform(-self.rotate, self.rotate, B)
         return types.SimpleNamespace(
             y0=y0.astype(np.int32), x0=x0.astype(np.int32), flip=flip.astype(np.int32),
             image_gain=(contrast[:, None] * per_channel).astype(np.float32), image_bias=bias.astype(np.float32),
             drop_lidar=u < self.lidar_dropout, drop_image=(u >= self.lidar_dropout) & (u < self.lidar_dropout + self.image_dropout),
-            out_size=(Ho, Wo))
+            zoom=zoom, angle=angle, out_size=(Ho, Wo))
 
     @staticmethod
     def channel_tables(params, image_channels, lidar_channels, target_channels):
@@ -140,6 +164,24 @@ class BatchAugment:
         bias[params.drop_image, :ci] = 0.0
         gain[params.drop_lidar, ci:ci + cl] = 0.0
         return gain, bias
+
+    @staticmethod
+    def matrices(params, Hs=None, Ws=None):
+        """(a, b): int32 (B, 2, 2) and int64 (B, 2) - a00, a01, a10, a11 and b0, b1 of every sample in Q20, as dmm_warp_batch gets them
+        (see THE MAP above; the source size does not enter the map and is accepted for symmetry with params_at)."""
+        Ho, Wo = params.out_size
+        cx, cy = (Wo - 1) / 2.0, (Ho - 1) / 2.0
+        t = np.deg2rad(np.asarray(params.angle, dtype=np.float64))
+        s = np.asarray(params.zoom, dtype=np.float64)
+        m = np.empty((len(s), 2, 2), dtype=np.float64)
+        m[:, 0, 0], m[:, 0, 1], m[:, 1, 0], m[:, 1, 1] = np.cos(t) / s, -np.sin(t) / s, np.sin(t) / s, np.cos(t) / s
+        off = np.array([cx, cy]) - m @ np.array([cx, cy])           # (xw, yw) = m (x, y) + off
+        flip = np.asarray(params.flip) != 0
+        m[flip, 0, :] = -m[flip, 0, :]
+        off[:, 0] = np.where(flip, (Wo - 1) - off[:, 0], off[:, 0])
+        off[:, 0] += np.asarray(params.x0, dtype=np.float64)
+        off[:, 1] += np.asarray(params.y0, dtype=np.float64)
+        return np.rint(m * WARP_ONE).astype(np.int32), np.rint(off * WARP_ONE).astype(np.int64)
 
     # ------------------------------------------------------------------ the launch
     def __call__(self, image, lidar, target, params=None):
@@ -167,15 +209,24 @@ class BatchAugment:
             raise ValueError("params were drawn for another batch size")
         Ho, Wo = params.out_size
         gain, bias = self.channel_tables(params, image.shape[1], 0 if lidar is None else lidar.shape[1], target.shape[1])
-        samples = (_lib.AugSample * B)()
+        warp = self.scale != 0.0 or self.rotate != 0.0
+        samples = ((_lib.WarpSample if warp else _lib.AugSample) * B)()
+        if warp:
+            ma, mb = self.matrices(params, Hs, Ws)
         for b in range(B):
             s = samples[b]
-            s.y0, s.x0, s.flip = int(params.y0[b]), int(params.x0[b]), int(params.flip[b])
+            if warp:
+                (s.a00, s.a01), (s.a10, s.a11) = ma[b].tolist()
+                s.b0, s.b1 = mb[b].tolist()
+            else:
+                s.y0, s.x0, s.flip = int(params.y0[b]), int(params.x0[b]), int(params.flip[b])
             s.gain[:sum(nch)] = gain[b].tolist()
             s.bias[:sum(nch)] = bias[b].tolist()
-        descs = (_lib.AugTensor * len(tensors))()
+        descs = ((_lib.WarpTensor if warp else _lib.AugTensor) * len(tensors))()
         outs = []
         for d, t in zip(descs, tensors):
+            if warp:
+                d.mode = _lib.WARP_BILINEAR if t is image else _lib.WARP_NEAREST
             ch = t.shape[1]
             t = t.detach()
             sb, sc, sh, sw = t.stride()
@@ -193,7 +244,8 @@ class BatchAugment:
                 raise ValueError(f"fill has {len(self.fill)} values, the call has {sum(nch)} channels")
             fill = (C.c_float * sum(nch))(*(self.fill * sum(nch) if len(self.fill) == 1 else self.fill))
         with torch.cuda.device(image.device):
-            _lib.check(_lib.lib().dmm_augment_batch(descs, len(tensors), samples, B, Hs, Ws, Ho, Wo, fill, _lib.stream_ptr()))
+            entry = _lib.lib().dmm_warp_batch if warp else _lib.lib().dmm_augment_batch
+            _lib.check(entry(descs, len(tensors), samples, B, Hs, Ws, Ho, Wo, fill, _lib.stream_ptr()))
         res = [o for _, o in outs]
         return (res[0], None, res[1]) if lidar is None else (res[0], res[1], res[2])
 

@@ -693,28 +693,32 @@ int dmm_logit_hist(const float* logits, const float* target, int B, int NC, int 
   return DMM_OK;
 }
 
-int dmm_augment_batch(const dmm_aug_tensor* tensors, int ntensors, const dmm_aug_sample* samples, int B, int Hs, int Ws, int Ho, int Wo,
-                      const float* fill, void* stream) {
-  const std::string who = "dmm_augment_batch: ";
-  if (!tensors || !samples) return fail(DMM_ERR_INVALID, who + "null argument");
-  if (ntensors < 1 || ntensors > DMM_AUG_MAX_TENSORS) return fail(DMM_ERR_INVALID, who + "ntensors must be in [1, " + std::to_string(DMM_AUG_MAX_TENSORS) + "]");
-  if (B < 1 || Hs < 1 || Ws < 1 || Ho < 1 || Wo < 1) return fail(DMM_ERR_INVALID, who + "B, Hs, Ws, Ho and Wo must be >= 1");
+// ---- batch augmentation (augment.hip) and affine warp (warp.hip): two entry points with one set of conventions ----
+extern "C++" {   // (templates, inside the file's extern "C" block)
+static bool aug_reserved_set(const dmm_aug_tensor& T) { return T.reserved != 0; }
+static bool aug_reserved_set(const dmm_warp_tensor& T) { return T.reserved[0] != 0 || T.reserved[1] != 0; }
+
+// What both refuse about sizes and tensors; *nch: the call's channels.  "" = nothing to refuse.
+template <class Tensor>
+static std::string aug_refuse_tensors(const Tensor* tensors, int ntensors, int B, int Hs, int Ws, int Ho, int Wo, int* nch_out) {
+  if (ntensors < 1 || ntensors > DMM_AUG_MAX_TENSORS) return "ntensors must be in [1, " + std::to_string(DMM_AUG_MAX_TENSORS) + "]";
+  if (B < 1 || Hs < 1 || Ws < 1 || Ho < 1 || Wo < 1) return "B, Hs, Ws, Ho and Wo must be >= 1";
   const long long splane = (long long)Hs * Ws, dplane = (long long)Ho * Wo;
-  if (splane >= (1ll << 31)) return fail(DMM_ERR_INVALID, who + "Hs * Ws must be < 2^31");
-  if (dplane >= (1ll << 31)) return fail(DMM_ERR_INVALID, who + "Ho * Wo must be < 2^31");
+  if (splane >= (1ll << 31)) return "Hs * Ws must be < 2^31";
+  if (dplane >= (1ll << 31)) return "Ho * Wo must be < 2^31";
   int nch = 0;
   for (int t = 0; t < ntensors; ++t) {
-    const dmm_aug_tensor& T = tensors[t];
-    const std::string which = who + "tensor " + std::to_string(t) + ": ";
-    if (!T.src || !T.dst) return fail(DMM_ERR_INVALID, which + "null src or dst");
-    if ((uintptr_t)T.src % 4 || (uintptr_t)T.dst % 4) return fail(DMM_ERR_INVALID, which + "src / dst must be 4-byte aligned");
-    if (T.reserved != 0) return fail(DMM_ERR_INVALID, which + "reserved must be 0");
-    if (T.channels < 1) return fail(DMM_ERR_INVALID, which + "channels must be >= 1");
+    const Tensor& T = tensors[t];
+    const std::string which = "tensor " + std::to_string(t) + ": ";
+    if (!T.src || !T.dst) return which + "null src or dst";
+    if ((uintptr_t)T.src % 4 || (uintptr_t)T.dst % 4) return which + "src / dst must be 4-byte aligned";
+    if (aug_reserved_set(T)) return which + "reserved must be 0";
+    if (T.channels < 1) return which + "channels must be >= 1";
     nch += T.channels;
-    if (nch > DMM_AUG_MAX_CHANNELS) return fail(DMM_ERR_INVALID, who + "channels must sum to at most " + std::to_string(DMM_AUG_MAX_CHANNELS));
-    if (T.src_batch_stride < T.channels * splane) return fail(DMM_ERR_INVALID, which + "src_batch_stride must be >= channels * Hs * Ws");
+    if (nch > DMM_AUG_MAX_CHANNELS) return "channels must sum to at most " + std::to_string(DMM_AUG_MAX_CHANNELS);
+    if (T.src_batch_stride < T.channels * splane) return which + "src_batch_stride must be >= channels * Hs * Ws";
     // (the byte ranges of the checks below are formed in uintptr_t: a stride that would wrap them is refused here)
-    if (T.src_batch_stride > (1ll << 60) / B) return fail(DMM_ERR_INVALID, which + "src_batch_stride * B is out of range");
+    if (T.src_batch_stride > (1ll << 60) / B) return which + "src_batch_stride * B is out of range";
   }
   // dst [dst, dst + B * channels * Ho * Wo) against every src span [src, src + (B - 1) * stride + channels * Hs * Ws) and every other dst
   auto overlaps = [](uintptr_t a, uintptr_t an, uintptr_t b, uintptr_t bn) { return a < b + bn && b < a + an; };
@@ -723,12 +727,44 @@ int dmm_augment_batch(const dmm_aug_tensor* tensors, int ntensors, const dmm_aug
     for (int u = 0; u < ntensors; ++u) {
       const uintptr_t sn = ((uintptr_t)(B - 1) * tensors[u].src_batch_stride + (uintptr_t)tensors[u].channels * splane) * 4;
       if (overlaps((uintptr_t)tensors[t].dst, dst_bytes(t), (uintptr_t)tensors[u].src, sn))
-        return fail(DMM_ERR_INVALID, who + "dst of tensor " + std::to_string(t) + " overlaps src of tensor " + std::to_string(u) + " (in place is not supported)");
+        return "dst of tensor " + std::to_string(t) + " overlaps src of tensor " + std::to_string(u) + " (in place is not supported)";
     }
   for (int t = 0; t < ntensors; ++t)
     for (int u = t + 1; u < ntensors; ++u)
       if (overlaps((uintptr_t)tensors[t].dst, dst_bytes(t), (uintptr_t)tensors[u].dst, dst_bytes(u)))
-        return fail(DMM_ERR_INVALID, who + "dst of tensor " + std::to_string(t) + " overlaps dst of tensor " + std::to_string(u));
+        return "dst of tensor " + std::to_string(t) + " overlaps dst of tensor " + std::to_string(u);
+  *nch_out = nch;
+  return "";
+}
+
+// the call's channels and fill into the launch arguments (AugArgs / WarpArgs); "" or what to refuse about fill
+template <class Args, class Tensor>
+static std::string aug_fill_args(Args& a, const Tensor* tensors, int ntensors, int nch, int Hs, int Ws, int Ho, int Wo, const float* fill) {
+  const long long splane = (long long)Hs * Ws, dplane = (long long)Ho * Wo;
+  for (int c = 0; c < nch; ++c) {
+    a.fill[c] = fill ? fill[c] : 0.f;
+    if (!std::isfinite(a.fill[c])) return "fill[" + std::to_string(c) + "] is NaN or infinite";
+  }
+  for (int t = 0, c = 0; t < ntensors; ++t)
+    for (int k = 0; k < tensors[t].channels; ++k, ++c) {
+      a.ch[c].src = tensors[t].src + (size_t)k * splane;
+      a.ch[c].dst = tensors[t].dst + (size_t)k * dplane;
+      a.ch[c].src_stride = tensors[t].src_batch_stride;
+      a.ch[c].dst_stride = tensors[t].channels * dplane;
+    }
+  a.Hs = Hs; a.Ws = Ws; a.Ho = Ho; a.Wo = Wo;
+  return "";
+}
+
+}  // extern "C++"
+
+int dmm_augment_batch(const dmm_aug_tensor* tensors, int ntensors, const dmm_aug_sample* samples, int B, int Hs, int Ws, int Ho, int Wo,
+                      const float* fill, void* stream) {
+  const std::string who = "dmm_augment_batch: ";
+  if (!tensors || !samples) return fail(DMM_ERR_INVALID, who + "null argument");
+  int nch = 0;
+  std::string why = aug_refuse_tensors(tensors, ntensors, B, Hs, Ws, Ho, Wo, &nch);
+  if (!why.empty()) return fail(DMM_ERR_INVALID, who + why);
   for (int b = 0; b < B; ++b) {
     const dmm_aug_sample& s = samples[b];
     const std::string which = who + "sample " + std::to_string(b) + ": ";
@@ -740,23 +776,49 @@ int dmm_augment_batch(const dmm_aug_tensor* tensors, int ntensors, const dmm_aug
   }
   AugArgs a;
   memset(&a, 0, sizeof(a));
-  for (int c = 0; c < nch; ++c) {
-    a.fill[c] = fill ? fill[c] : 0.f;
-    if (!std::isfinite(a.fill[c])) return fail(DMM_ERR_INVALID, who + "fill[" + std::to_string(c) + "] is NaN or infinite");
-  }
-  for (int t = 0, c = 0; t < ntensors; ++t)
-    for (int k = 0; k < tensors[t].channels; ++k, ++c) {
-      a.ch[c].src = tensors[t].src + (size_t)k * splane;
-      a.ch[c].dst = tensors[t].dst + (size_t)k * dplane;
-      a.ch[c].src_stride = tensors[t].src_batch_stride;
-      a.ch[c].dst_stride = tensors[t].channels * dplane;
-    }
-  a.Hs = Hs; a.Ws = Ws; a.Ho = Ho; a.Wo = Wo;
+  why = aug_fill_args(a, tensors, ntensors, nch, Hs, Ws, Ho, Wo, fill);
+  if (!why.empty()) return fail(DMM_ERR_INVALID, who + why);
   for (int b0 = 0; b0 < B; b0 += DMM_AUG_LAUNCH_BATCH) {
     const int nb = std::min(DMM_AUG_LAUNCH_BATCH, B - b0);
     a.b0 = b0;
     memcpy(a.s, samples + b0, (size_t)nb * sizeof(dmm_aug_sample));
     HIPCHK(launch_augment(a, nch, nb, (hipStream_t)stream));
+  }
+  return DMM_OK;
+}
+
+int dmm_warp_batch(const dmm_warp_tensor* tensors, int ntensors, const dmm_warp_sample* samples, int B, int Hs, int Ws, int Ho, int Wo,
+                   const float* fill, void* stream) {
+  const std::string who = "dmm_warp_batch: ";
+  if (!tensors || !samples) return fail(DMM_ERR_INVALID, who + "null argument");
+  int nch = 0;
+  std::string why = aug_refuse_tensors(tensors, ntensors, B, Hs, Ws, Ho, Wo, &nch);
+  if (!why.empty()) return fail(DMM_ERR_INVALID, who + why);
+  for (int t = 0; t < ntensors; ++t)
+    if (tensors[t].mode != DMM_WARP_NEAREST && tensors[t].mode != DMM_WARP_BILINEAR)
+      return fail(DMM_ERR_INVALID, who + "tensor " + std::to_string(t) + ": mode must be 0 (nearest) or 1 (bilinear)");
+  for (int b = 0; b < B; ++b) {
+    const dmm_warp_sample& s = samples[b];
+    const std::string which = who + "sample " + std::to_string(b) + ": ";
+    // with these bounds SX and SY stay below 2^59 for x, y < 2^31 (derived at the entry point's declaration): nothing wraps
+    for (const int32_t v : {s.a00, s.a01, s.a10, s.a11})
+      if (v > DMM_WARP_MAX_A || v < -DMM_WARP_MAX_A) return fail(DMM_ERR_INVALID, which + "|a00|, |a01|, |a10| and |a11| must be <= 64 << 20");
+    if (s.b0 > DMM_WARP_MAX_B || s.b0 < -DMM_WARP_MAX_B || s.b1 > DMM_WARP_MAX_B || s.b1 < -DMM_WARP_MAX_B)
+      return fail(DMM_ERR_INVALID, which + "|b0| and |b1| must be <= 2^50");
+    for (int c = 0; c < nch; ++c)
+      if (!std::isfinite(s.gain[c]) || !std::isfinite(s.bias[c])) return fail(DMM_ERR_INVALID, which + "gain / bias of channel " + std::to_string(c) + " is NaN or infinite");
+  }
+  WarpArgs a;
+  memset(&a, 0, sizeof(a));
+  why = aug_fill_args(a, tensors, ntensors, nch, Hs, Ws, Ho, Wo, fill);
+  if (!why.empty()) return fail(DMM_ERR_INVALID, who + why);
+  for (int t = 0, c = 0; t < ntensors; ++t)
+    for (int k = 0; k < tensors[t].channels; ++k, ++c) a.mode[c] = tensors[t].mode;
+  for (int b0 = 0; b0 < B; b0 += DMM_WARP_LAUNCH_BATCH) {
+    const int nb = std::min(DMM_WARP_LAUNCH_BATCH, B - b0);
+    a.b0 = b0;
+    memcpy(a.s, samples + b0, (size_t)nb * sizeof(dmm_warp_sample));
+    HIPCHK(launch_warp(a, nch, nb, (hipStream_t)stream));
   }
   return DMM_OK;
 }

@@ -162,6 +162,19 @@ struct AugArgs {           // by value (about 2.9 KB), so a launch needs no uplo
   dmm_aug_sample s[AUG_LAUNCH_BATCH];   // gridDim.z of them: samples b0 ...
 };
 
+// ---- affine warp (warp.hip) ----
+constexpr int WARP_LAUNCH_BATCH = DMM_WARP_LAUNCH_BATCH;
+struct WarpArgs {          // by value (3416 bytes), so a launch needs no upload
+  AugChannel ch[AUG_MAX_CHANNELS];    // gridDim.y of them
+  float fill[AUG_MAX_CHANNELS];
+  int mode[AUG_MAX_CHANNELS];         // DMM_WARP_NEAREST / DMM_WARP_BILINEAR, per global channel
+  int Hs, Ws, Ho, Wo;      // Hs * Ws, Ho * Wo < 2^31
+  int b0;                  // sample of blockIdx.z == 0
+  int reserved;
+  dmm_warp_sample s[WARP_LAUNCH_BATCH];   // gridDim.z of them: samples b0 ...
+};
+static_assert(sizeof(WarpArgs) == 3416 && 2 * sizeof(WarpArgs) > 4096, "DMM_WARP_LAUNCH_BATCH: the largest power of two that fits 4 KB");
+
 // ---- raw frames to training tensors (prepare.hip) ----
 constexpr int PREP_LAUNCH_BATCH = DMM_PREP_LAUNCH_BATCH;
 constexpr int PREP_TILE = 16;          // a workgroup of the heat-map launch owns PREP_TILE x PREP_TILE output pixels
@@ -341,6 +354,9 @@ int logit_hist_grid_x(int planes, size_t plane);   // workgroups per (b, n) plan
 // one launch: gridDim = (augment_grid_x(Ho, Wo), nchannels, nsamples <= AUG_LAUNCH_BATCH)
 hipError_t launch_augment(const AugArgs& a, int nchannels, int nsamples, hipStream_t st);
 unsigned augment_grid_x(int Ho, int Wo);   // workgroups per plane: one lane per four output pixels of a row
+// one launch: gridDim = (warp_grid_x(Ho, Wo), nchannels, nsamples <= WARP_LAUNCH_BATCH)
+hipError_t launch_warp(const WarpArgs& a, int nchannels, int nsamples, hipStream_t st);
+unsigned warp_grid_x(int Ho, int Wo);      // workgroups per plane: one per WARP_TILE_W x WARP_TILE_H output tile
 // raw frames to training tensors: one launch each for nsamples / a.nb <= PREP_LAUNCH_BATCH samples (the LiDAR form: the splat, unless
 // the samples have no point between them, then the pool; the owner planes are cleared by the caller)
 hipError_t launch_prep_image(const PrepImageArgs& a, int nsamples, hipStream_t st);   // grid (prep_plane_grid_x, C, nsamples)

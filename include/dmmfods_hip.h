@@ -16,6 +16,8 @@
  *                                          (utils/Dense_U_Net_lidar_helper.py:311-401) at up to 255 thresholds in one pass
  *   dmm_augment_batch .................... nothing upstream (the reference feeds the model what the loader yields, :236-244): crop,
  *                                          flip, shift, per-channel gain and bias of a device batch in one launch
+ *   dmm_warp_batch ....................... nothing upstream: scale and rotation of a device batch - a fixed-point affine map per sample,
+ *                                          heat maps and LiDAR sampled nearest, the image bilinear - in one launch
  *   dmm_heat_components .................. nothing upstream (the reference cannot "compute IoU per bounding box", helper.py:311-315):
  *                                          connected components of a thresholded heat map, one record per object
  *   dmm_prep_image / dmm_prep_lidar / dmm_prep_heat_maps
@@ -215,6 +217,57 @@ int dmm_augment_batch(const dmm_aug_tensor* tensors, int ntensors,
                       const dmm_aug_sample* samples /* host, B entries */, int B,
                       int Hs, int Ws, int Ho, int Wo,
                       const float* fill /* host, one value per channel; NULL = zeros */, void* stream);
+
+/* ---- on-device affine warp: scale and rotation (and every window of dmm_augment_batch) in one launch ----
+ * (Nothing upstream.)  The sibling of dmm_augment_batch for maps that do not land on whole pixels.  Tensors, channels, sizes, strides,
+ * fill, the by-value travel of samples and fill, the 64-bit address arithmetic and the absence of a plan are dmm_augment_batch's; a
+ * tensor also names how it is SAMPLED, and a sample carries an affine map in fixed point, F = DMM_WARP_FRAC_BITS, ONE = 1 << F,
+ * HALF = ONE / 2, MASK = ONE - 1.  For sample b, channel c of a tensor, output pixel (x, y), all in int64 and exact:
+ *   SX = a00 * x + a01 * y + b0          SY = a10 * x + a11 * y + b1
+ * DMM_WARP_NEAREST:
+ *   sx = (SX + HALF) >> F, sy = (SY + HALF) >> F          (arithmetic shifts: floors, so a half rounds up)
+ *   inside (0 <= sx < Ws and 0 <= sy < Hs):  v = src[b][c][sy][sx], then the gain / bias rule of dmm_augment_batch:
+ *       gain[c] == 1 and bias[c] == 0 :  out = v, bit for bit;     otherwise :  out = (gain[c] * v) + bias[c], two fp32 roundings
+ *   outside:                                 out = fill[c], untouched by gain and bias
+ * DMM_WARP_BILINEAR:
+ *   x0 = SX >> F, fx = SX & MASK, wx = float(fx) * 2^-F (exact);  y0, fy, wy likewise.  Taps (x0, y0), (x0 + 1, y0), (x0, y0 + 1),
+ *   (x0 + 1, y0 + 1) have the values v00, v01, v10, v11; a tap outside the source has the value fill[c].
+ *   fx == 0 and fy == 0:     the pixel is tap 00 alone, exactly as DMM_WARP_NEAREST treats (sx, sy) = (x0, y0): inside, the source's bits
+ *                            and then the gain / bias rule; outside, fill[c] untouched.  A map whose six coefficients are multiples of
+ *                            ONE is therefore a pure rearrangement and equals dmm_augment_batch on the same window bit for bit.
+ *   all four taps outside:   out = fill[c], untouched by gain and bias
+ *   otherwise, each operation one fp32 rounding, never fused, in this order:
+ *       top = v00 + wx * (v01 - v00);   bot = v10 + wx * (v11 - v10);   v = top + wy * (bot - top);   then the gain / bias rule on v
+ * Every element of every dst is written exactly once, nothing else is written, src is only read; no atomics, so the result does not
+ * depend on the launch geometry.  ceil(B / DMM_WARP_LAUNCH_BATCH) launches.
+ * Refuses with DMM_ERR_INVALID, before any HIP call, everything dmm_augment_batch refuses (with flip, y0 and x0 gone) and: a mode other
+ * than 0 or 1; a matrix entry with |a| > DMM_WARP_MAX_A (64 in fixed point); an offset with |b| > DMM_WARP_MAX_B (2^50).
+ * With x, y < 2^31 (a plane is smaller): |a * x| < 2^26 * 2^31 = 2^57, two such terms < 2^58, and with |b| + HALF <= 2^50 + 2^19 the sums
+ * stay below 2^58 + 2^51 < 2^59: nothing wraps in int64, and a coordinate after the shift is below 2^39 in magnitude. */
+#define DMM_WARP_NEAREST       0
+#define DMM_WARP_BILINEAR      1
+#define DMM_WARP_FRAC_BITS    20
+#define DMM_WARP_LAUNCH_BATCH 32     /* 32 records of 96 bytes and 344 bytes of channels, fill, modes and sizes: 3416 of the 4096 bytes */
+#define DMM_WARP_MAX_A  (64 << DMM_WARP_FRAC_BITS)
+#define DMM_WARP_MAX_B  (1ll << 50)
+typedef struct dmm_warp_tensor {
+  const float* src;          /*  0: as dmm_aug_tensor */
+  float* dst;                /*  8 */
+  int64_t src_batch_stride;  /* 16 */
+  int32_t channels;          /* 24 */
+  int32_t mode;              /* 28: DMM_WARP_NEAREST / DMM_WARP_BILINEAR, for every channel of the tensor */
+  int32_t reserved[2];       /* 32: 0 */
+} dmm_warp_tensor;           /* 40 bytes */
+typedef struct dmm_warp_sample {
+  int32_t a00, a01, a10, a11;         /*  0, 4, 8, 12: the matrix, Q20 */
+  int64_t b0, b1;                     /* 16, 24: the offsets, Q20 */
+  float gain[DMM_AUG_MAX_CHANNELS];   /* 32 */
+  float bias[DMM_AUG_MAX_CHANNELS];   /* 64 */
+} dmm_warp_sample;           /* 96 bytes */
+int dmm_warp_batch(const dmm_warp_tensor* tensors, int ntensors,
+                   const dmm_warp_sample* samples /* host, B entries */, int B,
+                   int Hs, int Ws, int Ho, int Wo,
+                   const float* fill /* host, one value per channel; NULL = zeros */, void* stream);
 
 /* ---- heat maps to objects: connected components and one record per component ----
  * (Nothing upstream: the reference measures whole-image pixel counts only, utils/Dense_U_Net_lidar_helper.py

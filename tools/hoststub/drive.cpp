@@ -50,6 +50,7 @@
 // the launch geometry of both accumulate modes - and every refusal of the entry point, each with nothing enqueued (hist_main).
 // DRIVE_AUGMENT=1 (life-cycle run): behind the lives (and DRIVE_HIST's calls), one valid dmm_augment_batch call with 33 samples on operands
 // that are addresses only - two launches - and every refusal of the entry point, each with nothing enqueued (augment_main).
+// DRIVE_WARP=1 (life-cycle run): the same for dmm_warp_batch, behind DRIVE_AUGMENT's calls (warp_main).
 // DRIVE_COMPONENTS=1 (life-cycle run): behind the lives (and the calls of the two switches above), dmm_heat_components on three shapes with
 // operands that are addresses only - seven launches each, every grid against a restatement of the tiling, the workspace carve-up inside
 // workspace_bytes - and every refusal of the entry point, each with nothing enqueued (components_main).
@@ -1183,6 +1184,106 @@ static int augment_main() {
 }
 #endif
 
+// ---- DRIVE_WARP: dmm_warp_batch (built against a csrc that has none: the case does not exist) ----
+#ifdef DMM_WARP_LAUNCH_BATCH
+// One valid call: B = 33 samples of three tensors (3 bilinear + 1 + 3 nearest channels, slices of one (33, 7, 37, 70) batch: addresses
+// only) to 32 x 64 outputs - two launches (32 samples, then 1) of the launcher's grid over all 7 channels.  Then every refusal, each
+// with nothing enqueued.
+static int warp_main() {
+  int bad = 0;
+  g_hist = HistWatch();
+  g_hist.on = true;
+  const int B = 33, Hs = 37, Ws = 70, Ho = 32, Wo = 64;
+  const size_t sp = (size_t)Hs * Ws, dp = (size_t)Ho * Wo;
+  float* src = (float*)reserve((size_t)B * 7 * sp * 4, PROT_NONE);
+  float* dst = (float*)reserve((size_t)B * 7 * dp * 4, PROT_NONE);
+  const dmm_warp_tensor good[3] = {{src, dst, (int64_t)(7 * sp), 3, DMM_WARP_BILINEAR, {0, 0}},
+                                   {src + 3 * sp, dst + (size_t)B * 3 * dp, (int64_t)(7 * sp), 1, DMM_WARP_NEAREST, {0, 0}},
+                                   {src + 4 * sp, dst + (size_t)B * 4 * dp, (int64_t)(7 * sp), 3, DMM_WARP_NEAREST, {0, 0}}};
+  const int32_t one = 1 << DMM_WARP_FRAC_BITS;
+  std::vector<dmm_warp_sample> smp(B);
+  for (int b = 0; b < B; ++b) {
+    memset(&smp[b], 0, sizeof(dmm_warp_sample));
+    smp[b].a00 = one - 1000 * b; smp[b].a01 = -777 * b; smp[b].a10 = 777 * b; smp[b].a11 = one - 1000 * b;
+    smp[b].b0 = (int64_t)(b % 11 - 5) * one + 12345; smp[b].b1 = (int64_t)(b % 7 - 3) * one - 54321;
+    for (int c = 0; c < DMM_AUG_MAX_CHANNELS; ++c) { smp[b].gain[c] = c < 3 ? 1.f + 0.01f * b : 1.f; smp[b].bias[c] = 0.f; }
+  }
+  const float fill[DMM_AUG_MAX_CHANNELS] = {1.f, 2.f, 3.f, 4.f, 5.f, 6.f, 7.f, 8.f};
+  {
+    const HistWatch w0 = g_hist;
+    MUST(dmm_warp_batch(good, 3, smp.data(), B, Hs, Ws, Ho, Wo, fill, nullptr));
+    const bool ok = g_hist.launches == w0.launches + 2 && g_hist.memsets == w0.memsets && g_hist.other == w0.other &&
+                    g_hist.kernel.find("warp_kernel") != std::string::npos && g_hist.gx == warp_grid_x(Ho, Wo) && g_hist.gx == 2 && g_hist.gy == 7;
+    printf("WARP %d samples: %ld launches, grid %u x %u %s\n", B, g_hist.launches - w0.launches, g_hist.gx, g_hist.gy, ok ? "ok" : "WRONG");
+    bad += !ok;
+  }
+  const HistWatch w0 = g_hist;
+  auto refused = [&](int rc, const char* names) {
+    if (rc == DMM_ERR_INVALID && strstr(dmm_last_error(), names) != nullptr && strstr(dmm_last_error(), "dmm_warp_batch: ") == dmm_last_error()) return;
+    fprintf(stderr, "[drive] dmm_warp_batch: not refused (%d) or the message does not say '%s': %s\n", rc, names, dmm_last_error());
+    ++bad;
+  };
+  // one tensor / one sample changed at a time
+  auto with_tensor = [&](int t, auto change, int nt = 3, int b = B, int hs = Hs, int ws = Ws, int ho = Ho, int wo = Wo) {
+    dmm_warp_tensor T[3] = {good[0], good[1], good[2]};
+    change(T[t]);
+    return dmm_warp_batch(T, nt, smp.data(), b, hs, ws, ho, wo, fill, nullptr);
+  };
+  auto with_sample = [&](int b, auto change) {
+    std::vector<dmm_warp_sample> s = smp;
+    change(s[b]);
+    return dmm_warp_batch(good, 3, s.data(), B, Hs, Ws, Ho, Wo, fill, nullptr);
+  };
+  auto same = [](dmm_warp_tensor&) {};
+  const float nan = __builtin_nanf(""), inf = __builtin_inff();
+  refused(dmm_warp_batch(nullptr, 3, smp.data(), B, Hs, Ws, Ho, Wo, fill, nullptr), "null");
+  refused(dmm_warp_batch(good, 3, nullptr, B, Hs, Ws, Ho, Wo, fill, nullptr), "null");
+  refused(with_tensor(1, [](dmm_warp_tensor& T) { T.src = nullptr; }), "null src or dst");
+  refused(with_tensor(2, [](dmm_warp_tensor& T) { T.dst = nullptr; }), "null src or dst");
+  refused(with_tensor(0, same, 0), "ntensors");
+  refused(with_tensor(0, same, DMM_AUG_MAX_TENSORS + 1), "ntensors");
+  refused(with_tensor(1, [](dmm_warp_tensor& T) { T.channels = 0; }), "channels must be >= 1");
+  refused(with_tensor(1, [](dmm_warp_tensor& T) { T.channels = 3; }), "sum to at most");
+  refused(with_tensor(0, same, 3, 0), ">= 1");
+  refused(with_tensor(0, same, 3, B, 0), ">= 1");
+  refused(with_tensor(0, same, 3, B, Hs, -1), ">= 1");
+  refused(with_tensor(0, same, 3, B, Hs, Ws, 0), ">= 1");
+  refused(with_tensor(0, same, 3, B, Hs, Ws, Ho, 0), ">= 1");
+  refused(with_tensor(0, same, 3, 1, 65536, 32768), "Hs * Ws");
+  refused(with_tensor(0, same, 3, 1, Hs, Ws, 32768, 65536), "Ho * Wo");
+  refused(with_tensor(0, [&](dmm_warp_tensor& T) { T.src_batch_stride = (int64_t)(3 * sp) - 1; }), "src_batch_stride");
+  refused(with_tensor(2, [](dmm_warp_tensor& T) { T.src = (const float*)((const char*)T.src + 2); }), "4-byte aligned");
+  refused(with_tensor(0, [](dmm_warp_tensor& T) { T.dst = (float*)((char*)T.dst + 1); }), "4-byte aligned");
+  refused(with_tensor(1, [](dmm_warp_tensor& T) { T.reserved[0] = 1; }), "reserved");
+  refused(with_tensor(2, [](dmm_warp_tensor& T) { T.reserved[1] = -1; }), "reserved");
+  refused(with_tensor(0, [](dmm_warp_tensor& T) { T.mode = 2; }), "mode");
+  refused(with_tensor(2, [](dmm_warp_tensor& T) { T.mode = -1; }), "mode");
+  refused(with_sample(32, [](dmm_warp_sample& s) { s.a00 = DMM_WARP_MAX_A + 1; }), "64 << 20");
+  refused(with_sample(0, [](dmm_warp_sample& s) { s.a01 = -DMM_WARP_MAX_A - 1; }), "64 << 20");
+  refused(with_sample(5, [](dmm_warp_sample& s) { s.a10 = INT32_MIN; }), "64 << 20");
+  refused(with_sample(5, [](dmm_warp_sample& s) { s.a11 = INT32_MAX; }), "64 << 20");
+  refused(with_sample(5, [](dmm_warp_sample& s) { s.b0 = DMM_WARP_MAX_B + 1; }), "2^50");
+  refused(with_sample(32, [](dmm_warp_sample& s) { s.b1 = INT64_MIN; }), "2^50");
+  refused(with_sample(32, [&](dmm_warp_sample& s) { s.gain[6] = nan; }), "NaN or infinite");
+  refused(with_sample(1, [&](dmm_warp_sample& s) { s.bias[0] = -inf; }), "NaN or infinite");
+  {
+    float f[DMM_AUG_MAX_CHANNELS]; memcpy(f, fill, sizeof(f)); f[3] = inf;
+    refused(dmm_warp_batch(good, 3, smp.data(), B, Hs, Ws, Ho, Wo, f, nullptr), "fill");
+    f[3] = nan;
+    refused(dmm_warp_batch(good, 3, smp.data(), B, Hs, Ws, Ho, Wo, f, nullptr), "fill");
+  }
+  // overlaps: in place, dst inside another tensor's src span (the last sample's planes), dst on another dst
+  refused(with_tensor(0, [](dmm_warp_tensor& T) { T.dst = (float*)T.src; }), "overlaps src");
+  refused(with_tensor(0, [&](dmm_warp_tensor& T) { T.dst = src + (size_t)(B - 1) * 7 * sp + 7 * sp - 1; }), "overlaps src");
+  refused(with_tensor(1, [&](dmm_warp_tensor& T) { T.dst = dst + (size_t)B * 3 * dp - 1; }), "overlaps dst");
+  if (g_hist.launches != w0.launches || g_hist.memsets != w0.memsets || g_hist.other != w0.other) { fprintf(stderr, "[drive] a refused dmm_warp_batch call reached the runtime\n"); ++bad; }
+  g_hist.on = false;
+  hipDeviceSynchronize();
+  printf("%s\n", bad ? "WARP FAILED" : "WARP OK");
+  return bad ? 1 : 0;
+}
+#endif
+
 // ---- DRIVE_COMPONENTS: dmm_heat_components (built against a csrc that has none: the case does not exist) ----
 #ifdef DMM_CC_TILE_H
 // Three shapes: a plane smaller than a tile, one ragged in both directions, many planes.  maps, labels, records, counts and the
@@ -1467,6 +1568,9 @@ int main(int argc, char** argv) {
 #endif
 #ifdef DMM_AUG_MAX_TENSORS
   if (getenv("DRIVE_AUGMENT") && augment_main() != 0) rc = 1;
+#endif
+#ifdef DMM_WARP_LAUNCH_BATCH
+  if (getenv("DRIVE_WARP") && warp_main() != 0) rc = 1;
 #endif
 #ifdef DMM_CC_TILE_H
   if (getenv("DRIVE_COMPONENTS") && components_main() != 0) rc = 1;
