@@ -29,19 +29,9 @@ namespace dmm {
                   // GEMM, 4 no data-gradient GEMM, 8 no epilogue (staging, norm1 backward, store), 16 every load hits row 0,
                   // 32 the old gradient is not read (as if not accumulating), 64 the gradient is not stored
 #endif
-#ifndef B1_LATE_PREFETCH
-#define B1_LATE_PREFETCH 0  // experiment: the next tile's loads requested behind the GEMMs and the old gradient instead of in front of them
-#endif
-#ifndef B1_RAW_BAR
-#define B1_RAW_BAR 0        // experiment: raw s_barrier behind an LDS-only wait for the three barriers behind the prefetch
-#endif
-#ifndef B1_NT
-#define B1_NT 0  // experiment: 1 x / old gradient loads non-temporal, 2 the gradient store non-temporal (3 both): streamed once, they
-                 // should not evict the G / y tiles that the sibling workgroups of a row range share through the XCD's L2
-#endif
-#ifndef B1_GOLD_EARLY
-#define B1_GOLD_EARLY 0  // 1: request the old gradient in front of the MFMAs (round 2; 16 more live registers across both GEMMs)
-#endif
+// Tried on the tile loop and measured as no gain (profiles/r03/ablations.txt, profiles/r04/ablations.txt): the next tile's loads
+// requested behind the GEMMs and the old gradient, with raw LDS-only barriers from there to the end of the tile; non-temporal hints on
+// the x / old-gradient loads and on the gradient store.
 constexpr int B1_TM = 64;                       // pixels per tile
 constexpr int B1_NB = 128;                      // bottleneck channels (K of the data gradient, N of the weight gradient)
 constexpr int B1_CT = 128;                      // input channels per workgroup
@@ -140,8 +130,7 @@ __global__ __launch_bounds__(NTHREADS, 2) void bw1_kernel(const Bw1Args g) {
       const int m = tile * B1_TM + p0 + 16 * i;
       if (m < a.M) okp |= 1u << i;
       const unsigned mm = (B1_DBG & 16) ? 0u : (unsigned)min(m, a.M - 1);
-      if (B1_NT & 1) rx[i] = __builtin_nontemporal_load((const V*)(xbase + (size_t)(mm * xpitch + xcol)));
-      else rx[i] = *(const V*)(xbase + (size_t)(mm * xpitch + xcol));
+      rx[i] = *(const V*)(xbase + (size_t)(mm * xpitch + xcol));
       rg[i] = *(const V*)(gbase + (size_t)(mm * gpitch + gcol));
       if constexpr (PQ == 2) ry[i] = *(const V*)(ybase + (size_t)(mm * ypitch + gcol));
     }
@@ -215,18 +204,7 @@ __global__ __launch_bounds__(NTHREADS, 2) void bw1_kernel(const Bw1Args g) {
     };
     if (UNC && full) stage(std::true_type()); else stage(std::false_type());   // (bf16: the second copy spills its generic epilogue)
     __syncthreads();  // images (and, the first time, the weight slice) complete
-#if !B1_LATE_PREFETCH
     if (tile + 1 < t_end) issue(tile + 1);
-#endif
-#if B1_GOLD_EARLY
-    if constexpr (ACC) {
-#pragma unroll
-      for (int i = 0; i < NL; ++i) {
-        const unsigned mm = (unsigned)min(tile * B1_TM + p0 + 16 * i, a.M - 1);
-        gold[i] = *(const V*)(obase + (size_t)(mm * opitch + xcol));
-      }
-    }
-#endif
 
     // ---- data gradient: dX[64 px][128 c] = G W ----
     f32x16 accd[2];
@@ -258,28 +236,15 @@ __global__ __launch_bounds__(NTHREADS, 2) void bw1_kernel(const Bw1Args g) {
         accw[j] = mma16(gf, af, accw[j]);  // rows: bottleneck channel n, columns: input channel c
       }
     }
-#if !B1_GOLD_EARLY
     if constexpr (ACC) {  // the old gradient of this tile: requested behind the MFMAs (16 registers that would otherwise live across both
                           // GEMMs), needed two barriers and the staging later; the CU's other workgroup covers what is left of the latency
 #pragma unroll
       for (int i = 0; i < NL; ++i) {
         const unsigned mm = (unsigned)min(tile * B1_TM + p0 + 16 * i, a.M - 1);
-        if (B1_NT & 1) gold[i] = __builtin_nontemporal_load((const V*)(obase + (size_t)(mm * opitch + xcol)));
-        else gold[i] = *(const V*)(obase + (size_t)(mm * opitch + xcol));
+        gold[i] = *(const V*)(obase + (size_t)(mm * opitch + xcol));
       }
     }
-#endif
-#if B1_LATE_PREFETCH
-    if (tile + 1 < t_end) issue(tile + 1);
-#endif
-#if B1_RAW_BAR
-    // (experiment) The next tile's operands, requested BEHIND the old gradient: the epilogue's wait for the old gradient then leaves these twelve
-    // loads in flight, and the barriers from here to the end of the tile are raw barriers behind an LDS-only wait (isa.h):
-    // __syncthreads() drained the prefetch at the first barrier behind it, half a microsecond after it had been issued.
-    lds_barrier();  // all waves done with the images: stage the data-gradient tile over them
-#else
     __syncthreads();  // all waves done with the images: stage the data-gradient tile over them
-#endif
     if (B1_DBG & 8) {  // keep the data-gradient GEMM alive
       float sa = 0.f;
 #pragma unroll
@@ -298,11 +263,7 @@ __global__ __launch_bounds__(NTHREADS, 2) void bw1_kernel(const Bw1Args g) {
         // half's; the readers apply the same XOR, which keeps their 16-byte groups intact)
         Cs[row * B1_CT + ((dcb + 32 * t + r) ^ (h << 5))] = accd[t][i];
       }
-#if B1_RAW_BAR
-    lds_barrier();
-#else
     __syncthreads();
-#endif
     // ---- norm1 backward in the slot layout of the loads ----
     float s1[SLOT], s2[SLOT];
 #pragma unroll
@@ -325,8 +286,7 @@ __global__ __launch_bounds__(NTHREADS, 2) void bw1_kernel(const Bw1Args g) {
         const unsigned m = (unsigned)(tile * B1_TM + p);
         if constexpr (UNC) {  // f16: mixed-precision instructions on the packed halves, uncentred second sum (gather.h bnbwd_slot)
           const V ov = bnbwd_slot<ACC>(av, xraw[i], gold[ACC ? i : 0], sc, sh, s1, s2);
-          if (B1_NT & 2) __builtin_nontemporal_store(ov, (V*)(obase + (size_t)(m * opitch + xcol)));
-          else if (!(B1_DBG & 64) || av[0] == 1.2345e33f) *(V*)(obase + (size_t)(m * opitch + xcol)) = ov;
+          if (!(B1_DBG & 64) || av[0] == 1.2345e33f) *(V*)(obase + (size_t)(m * opitch + xcol)) = ov;
         } else {
           float xf[SLOT], gf[SLOT];
           vec_to_f32<T>(xraw[i], xf);
@@ -347,11 +307,7 @@ __global__ __launch_bounds__(NTHREADS, 2) void bw1_kernel(const Bw1Args g) {
     // up with 4 of the 16 finished wave totals), then fp64 in LDS - 4 LDS atomics per lane instead of 16 on a quarter of the lanes
     fold_to_lds<16, SLOT, B1_CT>(s1, s2, red, cs, cvalid, lane);
     }  // (epilogue)
-#if B1_RAW_BAR
-    lds_barrier();  // staging read: the next tile's images may be written
-#else
     __syncthreads();  // staging read: the next tile's images may be written
-#endif
   }
 
   // ---- results of the walk: per-channel sums (one fp64 atomic per channel and workgroup), the weight-gradient slice ----

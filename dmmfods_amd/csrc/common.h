@@ -37,10 +37,7 @@ template <> struct TT<bf16> {
 };
 
 constexpr int MAX_TAPS = 52;
-#ifndef DMM_STAT_REPS
-#define DMM_STAT_REPS 8
-#endif
-constexpr int STAT_REPS = DMM_STAT_REPS;  // replicas of the BatchNorm reduction accumulators (low 3 bits of the workgroup id = XCD)
+constexpr int STAT_REPS = 8;  // replicas of the BatchNorm reduction accumulators (low 3 bits of the workgroup id = XCD)
 constexpr int DESIGN_CUS = 256; // compute units of the MI355X: launch geometries that size plan workspace are computed for it, not queried
 constexpr int BM = 128;        // rows (pixels) per workgroup tile
 constexpr int NTHREADS = 256;  // 4 waves of 64

@@ -537,21 +537,18 @@ __global__ __launch_bounds__(NTHREADS, 2) void cvd_kernel(const CvdArgs g) {
 //     under the first half's arithmetic; the old gradient of a half (a.accumulate) is requested in front of that half's staging (under
 //     the walk with x it spilled: 36 bytes of scratch in the ConvTranspose form).
 // Round 10, alone at 4 x 1280 x 1920 / the stages of C2 b4 (us, parent -> ring): head 1009 -> 905, TC_1 212 -> 208, TC_2 190 -> 186,
-// TC_3 213 -> 202; three slots of a 16 KB stage at two workgroups per CU (CVD3_RING_B): 993 / 243 / 201 / 216 (profiles/r10/ablations.txt).
+// TC_3 213 -> 202; three slots of a 16 KB stage at two workgroups per CU instead: 993 / 243 / 201 / 216 (profiles/r10/ablations.txt).
 // 52.9 KB of LDS; 168 (head) / 166 (ConvTranspose form) registers, no AGPRs, no scratch: three workgroups per CU.  Same K order and
 // epilogue arithmetic per output element as
 // cvd_kernel: gradients bit-equal, the BatchNorm sums equal up to the grouping of their fp32 partials (rows per thread: 4 instead of 8).
 #ifndef CVD3_DBG
 #define CVD3_DBG 0  // timing experiments only (tools/build_variant.sh ... -DCVD3_DBG=n; the shipped library carries no switch): 1 every
 #endif              // chunk multiplies the first chunk's weights, no weight request after the prologue's; 2 no halo after the first; 4 no epilogue
-#ifndef CVD3_RING_B
-#define CVD3_RING_B 0  // experiment build: three slots of a 16 KB stage, one barrier per stage, two workgroups per CU (ablations.txt, r10)
-#endif
 constexpr int C3D_NHP = CP_HH * CP_HW;                       // 153 halo pixels
 constexpr int C3D_X_BYTES = C3D_NHP * 128;                   // 19 584
 constexpr int C3D_CHUNK = CP_BN * 64;                        // 8 KB: 32 values of K for 128 columns
-constexpr int C3D_STEP = CVD3_RING_B ? 2 : 1;                // chunks per barrier
-constexpr int C3D_RING = CVD3_RING_B ? 6 : 4;                // ring slots (of one chunk)
+constexpr int C3D_STEP = 1;                                  // chunks per barrier
+constexpr int C3D_RING = 4;                                  // ring slots (of one chunk)
 constexpr int C3D_AHEAD = C3D_RING / C3D_STEP - 1;           // a step's weights are requested this many steps ahead
 constexpr int C3D_PW = C3D_CHUNK / 1024 / (NTHREADS / 64);   // LDS-DMA requests per wave and chunk: 2
 constexpr int C3D_WCUR = (C3D_AHEAD - 1) * C3D_STEP * C3D_PW;  // requests that stay in flight across a step barrier: 4
@@ -560,8 +557,8 @@ constexpr int C3D_LDS = C3D_MAIN + BM * 4;                   // + rowpix
 constexpr int C3D_FP = 64 + 4;                               // staging pitch (floats) of a column half
 constexpr int C3D_RED = BM * C3D_FP * 4;                     // offset of the fp64 sums inside the dead images
 static_assert(C3D_RED + 2 * 128 * 8 <= C3D_MAIN, "staging of a column half + the fp64 sums fit the operand images");
-static_assert(CVD3_RING_B || 3 * C3D_LDS <= 160 * 1024, "three workgroups per CU");
-static_assert(C3D_RING * C3D_CHUNK == (CVD3_RING_B ? 3 : 2) * CP_B_STAGE && C3D_RING % C3D_STEP == 0 && C3D_AHEAD >= 2, "ring geometry");
+static_assert(3 * C3D_LDS <= 160 * 1024, "three workgroups per CU");
+static_assert(C3D_RING * C3D_CHUNK == 2 * CP_B_STAGE && C3D_RING % C3D_STEP == 0 && C3D_AHEAD >= 2, "ring geometry");
 
 // vm_lds_barrier<n> (isa.h) for an n that is a constant only after unrolling
 __device__ __forceinline__ void vm_lds_barrier_n(int n) {
@@ -580,7 +577,7 @@ __device__ __forceinline__ void vm_lds_barrier_n(int n) {
 // UP2: the head's 16 merged taps (four per class) over ONE 64-channel group; !UP2: a ConvTranspose stage's nine taps (1, 2, 2, 4 per class)
 // over C / 64 channel groups (cvd_kernel<T, 128, false> walks them in groups of 128: 256 registers, 76.5 KB)
 template <typename T, bool UP2>
-__global__ __launch_bounds__(NTHREADS, CVD3_RING_B ? 2 : 3) void cvd3_kernel(const CvdArgs g) {
+__global__ __launch_bounds__(NTHREADS, 3) void cvd3_kernel(const CvdArgs g) {
   static_assert(sizeof(T) == 2, "16-bit storage");
   typedef typename TT<T>::vec V;
   constexpr int SLOT = 8, BN = CP_BN, NT = BN / 32;

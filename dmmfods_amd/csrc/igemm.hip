@@ -14,21 +14,6 @@
 #include <cstdlib>
 #include <type_traits>
 
-#ifndef IGEMM_FOLD_EPI   // bisect switches of the experiment build below: restrict it to one epilogue / column tile / LIN / PRO
-#define IGEMM_FOLD_EPI -1
-#endif
-#ifndef IGEMM_FOLD_BN
-#define IGEMM_FOLD_BN 0
-#endif
-#ifndef IGEMM_FOLD_LIN
-#define IGEMM_FOLD_LIN -1
-#endif
-#ifndef IGEMM_FOLD_PRO
-#define IGEMM_FOLD_PRO -2
-#endif
-#ifndef IGEMM_F32_FOLD
-#define IGEMM_F32_FOLD 0  // experiment builds only: the lane-swap fold in the fp32 instantiations too (see the comment at the fold)
-#endif
 #include "common.h"
 #include "dispatch.h"
 #include "gather.h"
@@ -53,42 +38,14 @@ template <> struct Mma<float> {
   }
 };
 
-// K-chunks per pipeline stage: 2 = twice the bytes in flight and twice the MFMAs per barrier; 1 = half the LDS, which lets
-// a third workgroup of the 128-column variants onto a CU
-#ifndef IGEMM_KS128
-#define IGEMM_KS128 2
-#endif
-constexpr int ks_for(int bn) { return bn == 128 ? IGEMM_KS128 : 2; }
-#ifndef IGEMM_FAT_F32
-#define IGEMM_FAT_F32 0  // experiment: 8-wave K-split variants for the 32-column fp32 tiles of launches with <= DMM_FAT_WGS workgroups
-#endif
-#ifndef IGEMM_FAT
-#define IGEMM_FAT 0  // instantiate the 8-wave variants (measured: no gain)
-#endif
-#ifndef IGEMM_ACCSTAT
-#define IGEMM_ACCSTAT 1  // EPI_STORE statistics from the accumulator layout
-#endif
-#ifndef IGEMM_EPI_EARLY
-#define IGEMM_EPI_EARLY 0
-#endif
-#ifndef IGEMM_ASM_DMA
-#define IGEMM_ASM_DMA 0
-#endif
-#ifndef IGEMM_RAW_BAR
-#define IGEMM_RAW_BAR 0
-#endif
-#ifndef IGEMM_ADIST
-#define IGEMM_ADIST 1
-#endif
 #ifndef IGEMM_DBG
 #define IGEMM_DBG 0  // timing experiments only: 1 no A loads, 2 no prologue math, 4 no epilogue, 8 no weight DMA, 16 no MFMA
 #endif
-constexpr int ADIST = IGEMM_ADIST;  // register prefetch distance of the gathered operand, in stages (1 or 2)
 
-template <typename T, int BN, int KSV>
+template <typename T, int BN>
 struct IgemmSmem {
   static constexpr int SLOT = TT<T>::SLOT;
-  static constexpr int KS = KSV;
+  static constexpr int KS = 2;  // K chunks per pipeline stage (1 and 4 were measured: see the note at launch_bn)
   static constexpr int A_BYTES = KS * BM * ROWB;
   static constexpr int B_BYTES = KS * BN * ROWB;
   static constexpr int STAGE_PITCH_T = BN + SLOT;  // elements of T
@@ -128,20 +85,18 @@ __device__ __forceinline__ SegU seg_uniform(const Seg& sg) {
   return r;
 }
 
-// NW = waves per workgroup.  8 ("fat"): two groups of four waves share the tile, each group takes half of the K chunks of a
-// stage (KSV counts the chunks of BOTH groups) and the accumulators are added through LDS in front of the epilogue: twice the
-// waves and half the chain of dependent stages for launches that have fewer workgroups than the chip has slots.
+// KSV (chunks per stage) and NW (waves per workgroup) are fixed: they stay template parameters only because the kernels' mangled
+// names are pinned (tests/golden/enqueue_trace_sha256.json, the recorded profiles).
 template <typename T, int BN, int EPI, bool MFMA, bool LIN, int PRO, int KSV, int NW>
-__global__ __launch_bounds__(64 * NW) void igemm_kernel(const ConvArgs a) {
-  constexpr int NTHREADS = 64 * NW;  // (shadows the 4-wave constant of common.h)
-  constexpr int NG = NW / 4;         // wave groups
+__global__ __launch_bounds__(NTHREADS) void igemm_kernel(const ConvArgs a) {
+  static_assert(KSV == 2 && NW == 4, "two chunks per stage, four waves");
   constexpr int SLOT = TT<T>::SLOT;
   constexpr int BK = 4 * SLOT;
   typedef typename TT<T>::vec V;
-  typedef IgemmSmem<T, BN, KSV> SM;
+  typedef IgemmSmem<T, BN> SM;
   constexpr int NT = BN / 32;
-  constexpr int KS = KSV;
-  constexpr bool ACCSTAT = IGEMM_ACCSTAT && MFMA && NW == 4 && sizeof(T) == 2;  // (fp32 storage keeps the row-wise form: its parity tests pin it)
+  constexpr int KS = SM::KS;
+  constexpr bool ACCSTAT = MFMA && sizeof(T) == 2;  // EPI_STORE statistics from the accumulator layout (fp32 storage keeps the row-wise form: its parity tests pin it)
   constexpr int NB = KS * BN / (16 * NW);  // 1-KiB LDS-DMA pieces of the B image per wave per stage
   constexpr int RST = NTHREADS / KS / 4;   // row groups; a thread owns rows rg + RST i
   constexpr int NR = BM / RST;             // rows per thread
@@ -243,36 +198,21 @@ __global__ __launch_bounds__(64 * NW) void igemm_kernel(const ConvArgs a) {
   }
 
   // issue-early / write-late: issue_a only issues the global loads of a later K-step; the prologue (BN+ReLU or the
-  // deferred-gradient correction) runs in store_a ADIST iterations later, behind the MFMAs of the steps in between.  With
-  // ADIST = 2 two register sets alternate, so a step's loads have a whole iteration (not just one MFMA block) to land.
-  struct ARing {
+  // deferred-gradient correction) runs in store_a one iteration later, behind the MFMAs of the step in between.
+  struct {
     RawSlot<T> raw[NR];
     int s, c, narr;
-  };
-  ARing R0, R1;
-  const unsigned bdst0 = __builtin_amdgcn_readfirstlane(
-      (unsigned)(size_t)(__attribute__((address_space(3))) unsigned char*)smem + SM::A_BYTES + wave * NB * 1024);
+  } R;
   auto issue_b = [&](int buf, int stage) {  // weights: LDS-DMA (a dead chunk re-reads chunk 0: its A slots are zero)
     const int g = stage * KS + ub;
     const T* bsrc = wp + (size_t)(g < total ? g : 0) * a.Npad * BK;
-#if IGEMM_ASM_DMA
-    // Inline-assembly form of the weight DMA: the compiler does not see it, so it does not drain vmcnt to 0 in front of the
-    // LDS reads (it does for the builtin) and the gathered operand's loads of the NEXT stage stay in flight (ADIST = 2).  The DMA
-    // of stage s is older than the A loads issued after it; the compiler's counted wait in the next store_a leaves at most those
-    // newer loads outstanding, so this DMA has landed before the barrier in front of mma(s).
-    const unsigned dst = bdst0 + buf * (SM::A_BYTES + SM::B_BYTES);
-#pragma unroll
-    for (int q = 0; q < NB; ++q)
-      if (!(IGEMM_DBG & 8)) lds_dma16(bsrc + boff[q], dst + q * 1024);
-#else
     unsigned char* Bs = smem + buf * (SM::A_BYTES + SM::B_BYTES) + SM::A_BYTES + wave * NB * 1024;
 #pragma unroll
     for (int q = 0; q < NB; ++q)
       if (!(IGEMM_DBG & 8)) __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(bsrc + boff[q]),
                                        (__attribute__((address_space(3))) void*)(Bs + q * 1024), 16, 0, 0);
-#endif
   };
-  auto issue_a = [&](ARing& R, int stage) {
+  auto issue_a = [&](int stage) {
     RawSlot<T>(&araw)[NR] = R.raw;
     const int g = stage * KS + u;
     const bool live = g < total;
@@ -331,7 +271,7 @@ __global__ __launch_bounds__(64 * NW) void igemm_kernel(const ConvArgs a) {
       araw[i].state = ok ? 1 : 3;
     }
   };
-  auto store_a = [&](const ARing& R, int buf) {
+  auto store_a = [&](int buf) {
     unsigned char* As = smem + buf * (SM::A_BYTES + SM::B_BYTES);
     const float* lk = R.s ? lk1 : lk0;
     const int cst = R.s ? su1.C : su0.C;
@@ -352,10 +292,12 @@ __global__ __launch_bounds__(64 * NW) void igemm_kernel(const ConvArgs a) {
     const unsigned char* Bs = As + SM::A_BYTES;
     if (MFMA) {
 #pragma unroll
-      for (int uq = 0; uq < KS / NG; ++uq)
+      for (int uq = 0; uq < KS; ++uq)
 #pragma unroll
         for (int s = 0; s < 2; ++s) {
-          const int uu = (wave >> 2) * (KS / NG) + uq;         // this wave group's chunks of the stage
+          // (wave >> 2 is 0 and wave & 3 is wave, as wave < 4 below is true: left from the retired 8-wave variants.  hipcc learns
+          // the range of `wave` only after its optimiser has run, so dropping them is not a no-op: registers and schedule change)
+          const int uu = (wave >> 2) * KS + uq;
           const int sw = ((2 * s + h) ^ ((r >> 2) & 3)) << 4;  // BM, BN and 32 are multiples of 16: swizzle depends on r only
           const V av = *(const V*)(As + (uu * BM + 32 * (wave & 3) + r) * ROWB + sw);
 #pragma unroll
@@ -414,68 +356,31 @@ __global__ __launch_bounds__(64 * NW) void igemm_kernel(const ConvArgs a) {
       }
     }
   };
-  // a 1x1 data gradient has one or two K stages: its epilogue operands are the bulk of the traffic, so they start first
-  constexpr bool EPI_EARLY = IGEMM_EPI_EARLY && LIN && EPI == EPI_BNBWD;
-  if constexpr (EPI_EARLY) prefetch_epi();
-  ARing& RA = R0;
-  ARing& RB = ADIST == 2 ? R1 : R0;
   issue_b(0, 0);
-  issue_a(RA, 0);
-  if (ADIST == 2) issue_a(RB, 1);
-  // The barriers of the K loop.  __syncthreads() drains the second register set's loads one stage after they were requested (round 3,
-  // pig.hip: that made ADIST = 2 worthless in round 2).  With two sets and a compile-time load count per issue_a the barrier is a raw
-  // barrier behind a COUNTED wait (isa.h vm_lds_barrier): everything but the newest request of the gathered operand - in particular
-  // the weight DMA of the stage, issued in front of it - has completed.
-  constexpr bool RAWBAR = IGEMM_RAW_BAR != 0 && ADIST == 2 && MFMA && PRO >= 0 && !(IGEMM_DBG & 1);
-  constexpr int NLOAD = NR * (PRO == 2 ? 2 : 1);
-  auto kbar = [&]() {
-    if constexpr (RAWBAR) vm_lds_barrier<NLOAD>();
-    else __syncthreads();  // also retires this stage's weight LDS-DMA (vmcnt(0))
-  };
-  for (int it = 0; it < nstages; it += 2) {
-    store_a(RA, 0);
-    kbar();
+  issue_a(0);
+  for (int it = 0; it < nstages; it += 2) {  // (each __syncthreads() also retires its stage's weight LDS-DMA: vmcnt(0))
+    store_a(0);
+    __syncthreads();
     issue_b(1, it + 1);
-    if constexpr (RAWBAR) __builtin_amdgcn_sched_barrier(0);  // the counted wait assumes DMA-before-loads in issue order (pig.hip)
-    issue_a(RA, it + ADIST);  // past the end: dead stage (clamped loads, dropped)
+    issue_a(it + 1);  // past the end: dead stage (clamped loads, dropped)
     mma(0);
-    store_a(RB, 1);
-    kbar();
+    store_a(1);
+    __syncthreads();
     if (it + 2 < nstages) issue_b(0, it + 2);  // (the staging below reuses the image: no DMA may be left in flight)
-    if constexpr (RAWBAR) __builtin_amdgcn_sched_barrier(0);
-    issue_a(RB, it + 1 + ADIST);
+    issue_a(it + 2);
     mma(1);
   }
-  if constexpr (!EPI_EARLY) prefetch_epi();
-  if constexpr (NG == 2) {  // add the second wave group's partial sums to the first's
-    __syncthreads();
-    float* Cx = (float*)smem;
-#pragma unroll
-    for (int t = 0; t < NT; ++t)
-#pragma unroll
-      for (int i = 0; i < 16; ++i) {
-        const int row = 32 * (wave & 3) + (i & 3) + 8 * (i >> 2) + 4 * h;
-        if (wave >= 4) Cx[row * SM::STAGE_PITCH_F + 32 * t + r] = acc[t][i];
-      }
-    __syncthreads();
-#pragma unroll
-    for (int t = 0; t < NT; ++t)
-#pragma unroll
-      for (int i = 0; i < 16; ++i) {
-        const int row = 32 * (wave & 3) + (i & 3) + 8 * (i >> 2) + 4 * h;
-        if (wave < 4) acc[t][i] += Cx[row * SM::STAGE_PITCH_F + 32 * t + r];
-      }
-  }
+  prefetch_epi();
   __syncthreads();  // all waves done with the operand image; reuse it for epilogue staging
   if ((IGEMM_DBG & 4) && acc[0][0] != 123.f) return;
 
   // ---- stage the accumulators through LDS: Cs[row][col] ----
-  if (wave < 4) {
+  if (wave < 4) {  // (always: see mma)
     if (EPI == EPI_STORE) {
       T* Cs = (T*)smem;
       // BatchNorm statistics straight from the accumulator layout (as conv3.hip / cvp.hip): lane (r, h) holds column 32 t + r of 16
       // rows; column sums of the values AS STORED (rounded to T), the two lane halves folded, one LDS word per column and wave
-      float* wpart = (float*)red;  // [wave][2][BN] floats over the fp64 scratch + row table (both dead here; NW == 4 only)
+      float* wpart = (float*)red;  // [wave][2][BN] floats over the fp64 scratch + row table (both dead here)
       bool rok[16];
 #pragma unroll
       for (int i = 0; i < 16; ++i) rok[i] = rowpix[32 * wave + (i & 3) + 8 * (i >> 2) + 4 * h] >= 0;
@@ -618,20 +523,19 @@ __global__ __launch_bounds__(64 * NW) void igemm_kernel(const ConvArgs a) {
   // ---- per-channel reductions: threads -> LDS -> one fp64 atomic per channel per workgroup ----
   // lanes l, l + NCV, l + 2 NCV, ... of a wave hold the same slot column: fold them with cross-lane adds first, so that one
   // lane per column and wave touches LDS (4-way instead of 16..64-way contention on every fp64 LDS atomic)
-  constexpr bool F32FOLD = IGEMM_F32_FOLD && (IGEMM_FOLD_EPI < 0 || EPI == IGEMM_FOLD_EPI) && (IGEMM_FOLD_BN == 0 || BN == IGEMM_FOLD_BN) &&
-                           (IGEMM_FOLD_LIN < 0 || (int)LIN == IGEMM_FOLD_LIN) && (IGEMM_FOLD_PRO < -1 || PRO == IGEMM_FOLD_PRO);
-  if constexpr ((sizeof(T) == 4 || !MFMA) && !F32FOLD) {  // (the scalar bring-up kernels of f16 spill as heavily as fp32's)
+  if constexpr (sizeof(T) == 4 || !MFMA) {  // (the scalar bring-up kernels of f16 spill as heavily as fp32's)
     // fp32 storage (the parity configuration) keeps the round-2 butterfly.  What round 3 saw with fold_to_lds here - and shelved as "not
-    // understood" - was run down in round 4 (tools/probes/fold_run.sh, fold_cases*.py, grad_dump.py):
-    //  * it is NOT the gfx950 lane swaps, the DPP rotations, hipcc's spilling or its pairing of fp32 operations: the same fold written
-    //    with ds_bpermute shuffles only (-DFOLD_VARIANT=3) fails the same test with the same numbers, -mllvm
-    //    -amdgpu-spill-vgpr-to-agpr=0 and -fno-slp-vectorize change nothing, the machine verifier is clean, and the lane algebra is
+    // understood" - was run down in round 4 with experiment builds that used the fold in the fp32 instantiations too, all of them or one
+    // epilogue / column tile at a time (the switches are retired; results in profiles/r04/ablations.txt and DESIGN 2):
+    //  * it was NOT the gfx950 lane swaps, the DPP rotations, hipcc's spilling or its pairing of fp32 operations: the same fold written
+    //    with ds_bpermute shuffles only failed the same test with the same numbers, -mllvm -amdgpu-spill-vgpr-to-agpr=0 and
+    //    -fno-slp-vectorize changed nothing, the machine verifier was clean, and the lane algebra is
     //    emulated exactly on the CPU (tests/test_host_cpu.py::test_fold_lane_algebra);
-    //  * the scalar bring-up kernels' symptom (rows 25 / 29 of every 32) does not reproduce on the present tree in any variant;
-    //  * every per-kernel sum of every fp32 instantiation is right to 1e-8 of the tensor with the fold (forward statistics and both
+    //  * the scalar bring-up kernels' symptom (rows 25 / 29 of every 32) did not reproduce in any variant;
+    //  * every per-kernel sum of every fp32 instantiation was right to 1e-8 of the tensor with the fold (forward statistics and both
     //    data-gradient reductions, with and without the deferred correction, accumulate on and off);
-    //  * the one failing test (tiny no-fusion model, fp32) narrows to the FORWARD statistics of the 32-column tiles
-    //    (-DIGEMM_FOLD_EPI=0 -DIGEMM_FOLD_BN=32; every data-gradient fold alone is clean): the fold adds a column's eight lane partials
+    //  * the one failing test (tiny no-fusion model, fp32) narrowed to the FORWARD statistics of the 32-column tiles
+    //    (every data-gradient fold alone was clean): the fold adds a column's eight lane partials
     //    in a different order, the batch mean / variance of ONE channel (decoder stage 4, input channel 4) move by 1.4e-7 / 6.6e-8
     //    relative, one element of that channel sits within that distance of its ReLU threshold, its mask flips in backward, and
     //    that channel's bias gradient moves by exactly one element's gradient (10.746 -> 11.947 of 768 summands); everything
@@ -667,15 +571,26 @@ __global__ __launch_bounds__(64 * NW) void igemm_kernel(const ConvArgs a) {
 }
 
 // ------------------------------------------------------------------------------------------------
-template <typename T, int BN, int EPI, int KSV, int NW>
-static hipError_t launch_bn_ks(const ConvArgs& a, bool mfma, hipStream_t st) {
+// What was tried on this kernel and did not pay (MI355X, C2 b4; rounds 2-3), each a compile-time switch up to the commit that
+// retired them: 4 K chunks per stage for launches of <= 512 workgroups (step +1.2 ms) and 1 for the 128-column tiles (a third
+// workgroup per CU: +-1 %) instead of 2; two stages of the gathered operand in flight (a second register set, an inline-assembly
+// weight DMA: store class -4 %, bnbwd class +3 % at 264 VGPRs, step +-0; with raw counted barriers in the K loop: bnbwd 0.96 ->
+// 0.93 ms, step +-0); the epilogue operands of 1x1 data gradients requested before the K loop (+-0); 8-wave workgroups that split
+// K for small grids (block-3 1x1: 25 -> 38 us; for fp32 the split changes the summation order the parity tests pin).  Records:
+// DESIGN.md 7 ("where the time went", round 2) and profiles/r03/ablations.txt.  Ablation builds
+// (tools/conv_time.py with IGEMM_DBG) say why: with every load, the prologue math and the MFMAs removed a 1x1 launch still takes
+// 70-90 % of its time - the cost is the skeleton (LDS writes, barrier, fragment reads, staging, the per-channel reductions and
+// the stores of the epilogue), not latency that more bytes or waves in flight could hide.
+template <typename T, int BN, int EPI>
+static hipError_t launch_bn(const ConvArgs& a, bool mfma, hipStream_t st) {
+  constexpr int KSV = 2, NW = 4;  // (igemm_kernel)
   const int mtiles = (a.M + BM - 1) / BM;
   const int ntiles = a.Npad / BN;
   int kfl = 0;
   for (int s = 0; s < a.nseg; ++s) kfl += seg_const_floats(a.seg[s]);
   int nchunks = 0;
   for (int s = 0; s < a.nseg; ++s) nchunks += a.seg[s].nchunks;
-  const int smem = IgemmSmem<T, BN, KSV>::bytes(EPI) + kfl * 4 + nchunks * 16 + 16;
+  const int smem = IgemmSmem<T, BN>::bytes(EPI) + kfl * 4 + nchunks * 16 + 16;
   const Seg& s0 = a.seg[0];
   const bool lin = mfma && a.nseg == 1 && s0.ntaps == 1 && s0.taps[0] == 0 && s0.mode == G_PLAIN && s0.istride == 1 &&
                    s0.Hs == a.Ho && s0.Ws == a.Wo;
@@ -691,42 +606,13 @@ static hipError_t launch_bn_ks(const ConvArgs& a, bool mfma, hipStream_t st) {
   if (!mfma) {
     // the scalar check kernels exist for fp32 / f16 (bring-up); bf16 arrived with the MFMA kernels already proven
     if constexpr (std::is_same<T, bf16>::value) return hipErrorNotSupported;
-    else if constexpr (NW != 4) return hipErrorNotSupported;
     else run = launch_lds<igemm_kernel<T, BN, EPI, false, false, -1, KSV, NW>, ConvArgs>;
   }
   else if (pro == P1) run = lin ? launch_lds<igemm_kernel<T, BN, EPI, true, true, P1, KSV, NW>, ConvArgs> : launch_lds<igemm_kernel<T, BN, EPI, true, false, P1, KSV, NW>, ConvArgs>;
   else if (pro == 0) run = lin ? launch_lds<igemm_kernel<T, BN, EPI, true, true, 0, KSV, NW>, ConvArgs> : launch_lds<igemm_kernel<T, BN, EPI, true, false, 0, KSV, NW>, ConvArgs>;
   else run = launch_lds<igemm_kernel<T, BN, EPI, true, false, -1, KSV, NW>, ConvArgs>;
   if (smem > 160 * 1024) return hipErrorInvalidValue;
-  return run(smem > 48 * 1024 ? 160 * 1024 : 0, mtiles * ntiles, 64 * NW, smem, st, a);
-}
-
-// Chunks per stage: measured on MI355X (C2 b4) - 4 chunks per stage for the launches with <= 512 workgroups (halving their
-// stage chain at 128+ KB of LDS) made the step 1.2 ms slower, 1 chunk per stage for the 128-column variants (a third workgroup
-// per CU) was +-1 %; every variant therefore takes 2 chunks per stage.
-// Measured on MI355X, C2 b4 (round 2), all kept as compile-time knobs and all OFF: (1) IGEMM_ASM_DMA + IGEMM_ADIST = 2 (counted
-// waits, two stages of the gathered operand in flight): store class -4 %, bnbwd class +3 % (264 VGPRs), step 33.8 vs 33.8 ms;
-// (1b, round 3) the same with raw counted barriers in the K loop (IGEMM_ADIST = 2 + IGEMM_RAW_BAR: __syncthreads drained the second set in
-// round 2's measurement): igemm.bnbwd 0.96 -> 0.93 ms, igemm.store +-0, step +-0 at C2; C1 (fp32) +-0 - its 60 us launches are 2048
-// v_mfma_f32_32x32x2_f32 per wave (64 cycles each) on 48 workgroups: bound by the fp32 matrix rate at 1/5 of the chip, not by loads;
-// (2) IGEMM_EPI_EARLY (epilogue operands of 1x1 data gradients requested before the K loop): +-0; (3) IGEMM_FAT (8-wave workgroups
-// that split K, for grids of <= DMM_FAT_WGS workgroups): 300-workgroup launches get SLOWER (block-3 1x1: 25 -> 38 us), step 34.1 ms.
-// Ablation builds (tools/conv_time.py with IGEMM_DBG) say why: with every load, the prologue math and the MFMAs removed a 1x1
-// launch still takes 70-90 % of its time - the cost is the skeleton (LDS writes, barrier, fragment reads, staging, the per-channel
-// reductions and the stores of the epilogue), not latency that more bytes or waves in flight could hide.
-template <typename T, int BN, int EPI>
-static hipError_t launch_bn(const ConvArgs& a, bool mfma, hipStream_t st) {
-  if constexpr (((IGEMM_FAT && sizeof(T) == 2 && BN == 128) || (IGEMM_FAT_F32 && sizeof(T) == 4 && BN == 32)) && EPI != EPI_LOGITS) {
-    static const int fat_wgs = lab_int("DMM_FAT_WGS", sizeof(T) == 4 ? 128 : 512);
-    int nchunks = 0;
-    for (int s = 0; s < a.nseg; ++s) nchunks += a.seg[s].nchunks;
-    const int wgs = ((a.M + BM - 1) / BM) * (a.Npad / BN);
-    int kfl = 0;
-    for (int s = 0; s < a.nseg; ++s) kfl += seg_const_floats(a.seg[s]);
-    const int smem = IgemmSmem<T, BN, 2 * ks_for(BN)>::bytes(EPI) + kfl * 4 + nchunks * 16 + 16;
-    if (mfma && wgs <= fat_wgs && nchunks >= 8 && smem <= 160 * 1024) return launch_bn_ks<T, BN, EPI, 2 * ks_for(BN), 8>(a, mfma, st);
-  }
-  return launch_bn_ks<T, BN, EPI, ks_for(BN), 4>(a, mfma, st);
+  return run(smem > 48 * 1024 ? 160 * 1024 : 0, mtiles * ntiles, NTHREADS, smem, st, a);
 }
 
 template <typename T, int EPI>

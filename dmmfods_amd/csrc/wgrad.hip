@@ -22,9 +22,6 @@
 
 namespace dmm {
 
-#ifndef WGRAD_DIST_HEAVY
-#define WGRAD_DIST_HEAVY 1
-#endif
 #ifndef WGRAD_DBG
 #define WGRAD_DBG 0  // timing experiments only: 1 skip atomics, 2 skip MFMA, 4 skip tile loads
 #endif
@@ -351,7 +348,7 @@ __global__ __launch_bounds__(NTHREADS, 2) void wgrad_kernel(const WgradArgs a) {
 
 // register prefetch distance per variant: two sets unless the raw operands (two tensors each for the effective
 // gradient) would not fit the register budget of two workgroups per CU
-constexpr int WDIST(int wbn, int pp, int pq) { return ((pp == 2 || pq == 2 || pp < 0) && wbn == 128) ? WGRAD_DIST_HEAVY : 2; }
+constexpr int WDIST(int wbn, int pp, int pq) { return ((pp == 2 || pq == 2 || pp < 0) && wbn == 128) ? 1 : 2; }
 
 static int seg_pro(const Seg& sg) { return sg.mode == G_POOL2 ? -1 : (sg.scale ? 1 : (sg.q ? 2 : 0)); }
 static bool seg_lin(const Seg& sg, const WgradArgs& a) {
