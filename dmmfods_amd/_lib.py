@@ -220,6 +220,8 @@ def lib():
     L.dmm_conv_scratch_bytes.restype = sz
     L.dmm_conv_forward.argtypes = [C.POINTER(ConvDesc), vp, vp, vp, vp, vp, vp, vp, vp]
     L.dmm_conv_logits.argtypes = [C.POINTER(ConvDesc), vp, vp, vp, vp, vp, vp, vp]
+    L.dmm_plan_record_output.argtypes = [vp, C.c_int, C.POINTER(i64), C.POINTER(i32 * 5)]
+    L.dmm_avgpool2_bnrelu.argtypes = [C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, C.c_int, vp]
     L.dmm_conv_forward_merged.argtypes = [C.POINTER(ConvDesc), vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(C.c_int)]
     L.dmm_conv_wgrad_merged.argtypes = [C.POINTER(ConvDesc), vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(C.c_int)]
     L.dmm_conv_wgrad.argtypes = [C.POINTER(ConvDesc), vp, vp, vp, vp, vp, vp, vp]
@@ -252,6 +254,7 @@ EXPORTS = [
     "dmm_logit_hist_elems", "dmm_logit_hist", "dmm_augment_batch", "dmm_warp_batch",
     "dmm_heat_components_workspace", "dmm_heat_components",
     "dmm_prep_image", "dmm_prep_lidar_workspace", "dmm_prep_lidar", "dmm_prep_heat_maps",
+    "dmm_avgpool2_bnrelu", "dmm_plan_record_output",
 ]
 HIST_MAX_THRESHOLDS = 255   # DMM_HIST_MAX_THRESHOLDS
 

@@ -319,7 +319,7 @@ hipError_t launch_record(dmm_plan* p, const Op& o, hipStream_t st, Lanes& lanes,
     case OP_BNBWD:
       if (accumulate) { BnBwdFinalizeArgs bb = o.bb; bb.accumulate = 1; return launch_bn_bwd_finalize(bb, st); }
       return launch_bn_bwd_finalize(o.bb, st);
-    case OP_POOL: return launch_maxpool_fwd(o.mp, dt, st);
+    case OP_POOL: return o.epi == POOL_AVG2 ? launch_avgpool2_fwd(o.ap, dt, st) : launch_maxpool_fwd(o.mp, dt, st);
     case OP_POOLBWD: return launch_maxpool_bwd(o.mpb, dt, st);
     case OP_BCE: return launch_bce_metrics(o.bce, dt, st);
     case OP_PACK: return launch_pack(o.pk.descs, o.pk.prefix, o.pk.ndesc, o.pk.total_rows, dt, st, o.pk.tdescs, o.pk.tiles, o.pk.nt1, o.pk.nt9);
@@ -1055,6 +1055,19 @@ int dmm_plan_profile_op(const dmm_plan* plan, int which, int index, const char**
   return DMM_OK;
 }
 
+// Unit-test entry point (the header's last section): where a storing convolution record of the training forward list leaves its result -
+// tests/test_transition_pool_gpu.py compares a layer's output between two plans of one network.
+int dmm_plan_record_output(const dmm_plan* plan, int index, int64_t* ws_offset, int32_t* dims /* B, H, W, N, pixel pitch */) {
+  if (!plan || !plan->bound || !ws_offset || !dims) return fail(DMM_ERR_INVALID, "bad argument");
+  const std::vector<Op>& ops = plan->fwd_train;
+  if (index < 0 || index >= (int)ops.size()) return fail(DMM_ERR_INVALID, "op index out of range");
+  const Op& o = ops[index];
+  if (o.kind != OP_IGEMM || o.epi != EPI_STORE || o.c.out == nullptr) return fail(DMM_ERR_INVALID, "not a storing convolution record");
+  *ws_offset = (int64_t)((const uint8_t*)o.c.out - (const uint8_t*)plan->ws);
+  dims[0] = o.c.B; dims[1] = o.c.Hout; dims[2] = o.c.Wout; dims[3] = o.c.N; dims[4] = o.c.ldo;
+  return DMM_OK;
+}
+
 /* Sum of per-op durations (ms) over the recorded passes; the caller must have synchronised the stream. */
 int dmm_plan_profile_collect(dmm_plan* plan, int which, double* ms_sum, int n, int* passes) {
   if (!plan || which < 0 || which > 1 || !ms_sum) return fail(DMM_ERR_INVALID, "bad argument");
@@ -1584,6 +1597,23 @@ int dmm_conv_forward(const dmm_conv_desc* d, const void* x, const float* w, cons
     fill_fwd_phase(a, d, g, x, scale, shift, y, stats, packs[ph], ph);
     HIPCHK(launch_igemm(a, d->dtype, EPI_STORE, d->use_mfma != 0, st, IMPL_AUTO, g_family_off));
   }
+  return DMM_OK;
+}
+
+// The pooling launch a plan puts in front of a transition's 1x1 convolution (plan.cpp emit_transition_pool), on a channel window.
+int dmm_avgpool2_bnrelu(int dtype, const void* x, int ld, int B, int H, int W, int C, const float* scale, const float* shift, void* out,
+                        int ldo, void* stream) {
+  const std::string who = "dmm_avgpool2_bnrelu: ";
+  if (!x || !scale || !shift || !out) return fail(DMM_ERR_INVALID, who + "null argument");
+  if (dtype != DT_F32 && dtype != DT_F16 && dtype != DT_BF16) return fail(DMM_ERR_INVALID, who + "unknown dtype");
+  const int slot = dtype == DT_F32 ? 4 : 8;
+  if (B <= 0 || H <= 0 || W <= 0 || C <= 0 || H % 2 || W % 2 || C % slot || ld % slot || ldo % slot || ld < C || ldo < C)
+    return fail(DMM_ERR_INVALID, who + "whole 2x2 windows and whole 16-byte channel slots only");
+  AvgPool2Args a;
+  a.x = x; a.ld = ld; a.H = H; a.W = W; a.B = B; a.C = C;
+  a.scale = scale; a.shift = shift;
+  a.out = out; a.ldo = ldo;
+  HIPCHK(launch_avgpool2_fwd(a, dtype, (hipStream_t)stream));
   return DMM_OK;
 }
 

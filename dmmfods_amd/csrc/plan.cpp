@@ -280,6 +280,9 @@ struct SegRec {
   int buf, ch0, C /*storage channels*/, Cw /*master channels*/, koff, mode, istride;
   int bn, bn_c0;
   int dgrad;
+  int pbuf;  // a transition above the row threshold (transition_pools): the buffer that holds avgpool2(relu(bn(x))), which the forward and
+             // the weight gradient read as a plain 1x1 operand (mode, bn, dgrad still describe x: the data gradient reads it); -1: none
+  const float *one, *zero;  // with pbuf: constant scale = 1 / shift = 0 vectors (relu(1 * p + 0) is p bit for bit, p >= 0)
 };
 struct PhaseRec { int py, px; std::vector<Tap> taps; int pack; std::vector<Tap> taps1; /* segment 1, if different */ };
 struct ConvRec {
@@ -361,6 +364,12 @@ struct Builder {
   size_t pack_cut_rec = 0;     // the first forward record whose weights the second pack launch holds
   int pt_early1 = 0, pt_early9 = 0, pt_late1 = 0, pt_late9 = 0;
   static constexpr double PACK_EARLY_ELEMS = 3.0e6;
+  // ---- transitions over a pooled buffer (transition(); plan_bind fills the constant-one vectors) ----
+  // The smallest transition measured (profiles/r19/ablations.txt section 3: 600 pooled rows, 1792 -> 896 channels: forward 0.163 -> 0.048 ms,
+  // weight gradient 0.051 -> 0.027 ms in the serial pass; every larger one gains too).  Nothing smaller was timed - there the fixed cost
+  // of one more launch is all that is known - so smaller transitions keep the pooling gather.
+  static constexpr long long TRANSITION_POOL_MIN_ROWS = 600;
+  std::vector<std::pair<float*, int>> ones;
   // ---- gradient buckets (make_buckets fills them; conv_grad_done / bn_grad_done count them down while backward is emitted;
   // finish_buckets turns them into P.buckets) ----
   std::vector<BucketRec> brecs;
@@ -566,7 +575,7 @@ struct Builder {
   double src_bytes(const ConvRec& c) const {
     double b = 0;
     for (int s = 0; s < c.nseg; ++s) {
-      const Buf& sb = bufs[c.seg[s].buf];
+      const Buf& sb = bufs[c.seg[s].pbuf >= 0 ? c.seg[s].pbuf : c.seg[s].buf];
       b += (double)sb.B * sb.H * sb.W * c.seg[s].C * esz;
     }
     return b;
@@ -610,7 +619,27 @@ struct Builder {
     s.mode = sr.mode;
     s.istride = sr.istride;
     if (sr.bn >= 0) { s.scale = bns[sr.bn].scale + sr.bn_c0; s.shift = bns[sr.bn].shift + sr.bn_c0; }
+    if (sr.pbuf >= 0) {  // the pooled, activated operand exists (emit_transition_pool): a plain tensor on the row grid, identity prologue
+      const Buf& pb = bufs[sr.pbuf];
+      s.src = pb.x; s.ld = pb.ld; s.Hs = pb.H; s.Ws = pb.W;
+      s.mode = G_PLAIN;
+      s.scale = sr.one; s.shift = sr.zero;
+    }
     fill_seg_taps(s, taps, BK);
+  }
+  // p = avgpool2(relu(bn(x))) of a transition above the row threshold, behind the norm's finalize and in front of its 1x1 launch
+  void emit_transition_pool(const ConvRec& c) {
+    const SegRec& sr = c.seg[0];
+    const Buf &xb = bufs[sr.buf], &pb = bufs[sr.pbuf];
+    Op& o = push(OP_POOL);
+    o.epi = POOL_AVG2;
+    AvgPool2Args& a = o.ap;
+    a.x = xat(sr.buf, sr.ch0); a.ld = xb.ld; a.H = xb.H; a.W = xb.W; a.B = xb.B; a.C = sr.C;
+    a.scale = bns[sr.bn].scale + sr.bn_c0; a.shift = bns[sr.bn].shift + sr.bn_c0;
+    a.out = pb.x; a.ldo = pb.ld;
+    std::string layer = short_name(c.wname);
+    if (layer.size() > 5 && layer.compare(layer.size() - 5, 5, ".conv") == 0) layer.replace(layer.size() - 5, 5, ".pool");
+    tag(o, "avgpool2.fwd", layer, 0, 1.25 * xb.B * xb.H * xb.W * sr.C * esz);
   }
 
   // The last four launch records as ONE launch of four phases - if they are four phases of one convolution (`eligible(record, first)`
@@ -641,6 +670,7 @@ struct Builder {
       if (bn < 0 || (s == 1 && bn == c.seg[0].bn)) continue;   // (the head's two segments stand under ONE norm: finalized once)
       emit_bn_finalize(bn);
     }
+    if (c.seg[0].pbuf >= 0) emit_transition_pool(c);
     const Buf& ob = bufs[c.obuf];
     const bool mfma = d.use_mfma != 0;
     for (auto& ph : c.phases) {
@@ -1172,6 +1202,7 @@ struct Builder {
     c.flops_ref = 0;
     memset(c.seg, 0, sizeof(c.seg));
     c.seg[0].bn = c.seg[1].bn = -1;
+    c.seg[0].pbuf = c.seg[1].pbuf = -1;
     convs.push_back(c);
     recs.push_back({0, (int)convs.size() - 1});
     return convs.back();
@@ -1210,6 +1241,7 @@ struct Builder {
     SegRec& sr = c.seg[s];
     sr.buf = buf; sr.ch0 = ch0; sr.Cw = Cw; sr.C = rup(Cw, 8); sr.koff = koff; sr.mode = mode; sr.istride = istride;
     sr.bn = bn; sr.bn_c0 = bn_c0; sr.dgrad = dgrad;
+    sr.pbuf = -1; sr.one = sr.zero = nullptr;
   }
 
   // stem: conv0 (7x7 s2) -> norm0 -> relu0 -> pool0, output into `obuf` channels [och0, och0+nif)
@@ -1247,11 +1279,27 @@ struct Builder {
     }
   }
 
+  // A transition of at least this many pooled rows writes p = avgpool2(relu(bn(x))) once (pointwise.hip: avgpool2_kernel) and runs its
+  // forward and its weight gradient as a plain 1x1 layer over p; below it the generic kernels pool inside their gather as before (the
+  // extra launch costs its fixed few microseconds for nothing).  By the shape alone: the sizing and the bound pass reserve the same bytes.
+  long long transition_pool_rows() const { return P.sw.transition_pool_rows >= 0 ? P.sw.transition_pool_rows : TRANSITION_POOL_MIN_ROWS; }
+  bool transition_pools(const Buf& X) const { return (long long)X.B * (X.H / 2) * (X.W / 2) >= transition_pool_rows(); }
+
   void transition(const std::string& p, int xb, int base, int C, int obuf, int och0) {
     const Buf X = bufs[xb];
     const int n = new_bn(p + ".norm", C);
     bn_range(n, xb, base, 0, C);
+    int pb = -1;
+    float *one = nullptr, *zero = nullptr;
+    if (transition_pools(X)) {
+      pb = new_buf(X.B, X.H / 2, X.W / 2, rup(C, 8), false, false);
+      const int cp = rup(C, 8) + 8;   // as a norm's scale / shift (new_bn)
+      one = wptr<float>(cp); zero = wptr<float>(cp);   // (the workspace is zeroed when it is bound; plan_bind fills `one`)
+      ones.push_back({one, cp});
+    }
     plain_conv(p + ".conv.weight", C / 2, C, 1, 0, xb, base, G_POOL2, 1, n, DG_POOL2, X.H / 2, X.W / 2, obuf, och0);
+    SegRec& sr = convs.back().seg[0];
+    sr.pbuf = pb; sr.one = one; sr.zero = zero;
   }
 
   void build() {
@@ -1737,6 +1785,8 @@ PlanSwitches PlanSwitches::from_environment() {
   s.no_r1_stats = on("DMM_NO_R1_STATS");
   const char* pc = getenv("DMM_PACK_CUT");
   s.pack_cut = pc ? std::max(1, atoi(pc)) : 0;
+  const char* tp = getenv("DMM_TRANSITION_POOL_ROWS");
+  s.transition_pool_rows = (tp && *tp) ? std::max(0LL, atoll(tp)) : -1;
   return s;
 }
 
@@ -1784,6 +1834,11 @@ void plan_bind(dmm_plan* p, void* ws) {
   p->ws = ws;
   // zero everything once: padding lanes of scale/shift tables and NHWC8 pad channels must read as 0
   hipMemset(ws, 0, p->zero_bytes + p->zero_bwd_bytes + p->main_bytes);
+  // the identity prologue of the transitions that read a pooled buffer: scale = 1 (shift = 0 is the zeroed workspace)
+  for (auto& v : b.ones) {
+    const std::vector<float> one((size_t)v.second, 1.0f);
+    hipMemcpy(v.first, one.data(), one.size() * sizeof(float), hipMemcpyHostToDevice);
+  }
   // upload the pack tables
   hipMemcpy(b.pack_dev, p->packs.data(), p->packs.size() * sizeof(PackDesc), hipMemcpyHostToDevice);
   hipMemcpy(b.prefix_dev, p->pack_prefix.data(), p->pack_prefix.size() * sizeof(int), hipMemcpyHostToDevice);

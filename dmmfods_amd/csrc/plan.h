@@ -83,6 +83,10 @@ inline bool accept_wgrad_merged(WgradArgs& m, int dtype, bool mfma, unsigned den
 enum OpKind { OP_MEMSET = 0, OP_CONVERT, OP_IGEMM, OP_WGRAD, OP_BNFIN, OP_BNBWD, OP_POOL, OP_POOLBWD, OP_BCE, OP_PACK, OP_UNPACK,
               OP_COPY, OP_APPLYCORR, OP_BW1, OP_JOIN, OP_BW1RED, OP_RAWFIN, OP_FIN64 };
 
+// What an OP_POOL record launches (Op::epi, which is no epilogue on this kind): the stem's 3x3 stride-2 max pooling (MaxpoolArgs) or the
+// 2x2 average pooling of a transition's BN+ReLU input (AvgPool2Args).
+enum PoolMode { POOL_MAX3 = 0, POOL_AVG2 = 1 };
+
 struct MemsetArgs { void* p; size_t bytes; };
 struct CopyArgs { void* dst; const void* src; size_t bytes; };
 struct PackArgs {
@@ -111,6 +115,7 @@ struct Op {
     BnFinalizeArgs bf;
     BnBwdFinalizeArgs bb;
     MaxpoolArgs mp;
+    AvgPool2Args ap;   // OP_POOL with epi == POOL_AVG2: a transition's pooled operand (POOL_MAX3: the stem's max pooling, mp)
     MaxpoolBwdArgs mpb;
     BceArgs bce;
     PackArgs pk;
@@ -159,6 +164,9 @@ struct GradBucket {
 //   DMM_PACK_CUT=<n>        the forward record in front of which the late layers' weight pack is joined (1 = behind the stem)
 //   DMM_NO_R1_STATS=1       the BatchNorm-backward sums of the head's norm1 from the reductions-only first pass of the 5x5 data gradient
 //                           instead of from the 5x5 weight gradient's factor correlations (wg5.hip, PA = 3)
+//   DMM_TRANSITION_POOL_ROWS=<n>  a transition of at least n pooled rows (B * H/2 * W/2) writes its pooled BN+ReLU input once and runs as
+//                           a plain 1x1 layer over it (plan.cpp: transition_pools); 0 = every transition, a huge n = none.  Default:
+//                           TRANSITION_POOL_MIN_ROWS
 //   DMM_NO_RAW_STATS=1      the BatchNorm-backward sums of the head's raw-input channels from a data-gradient pass of their own
 //                           (round 4) instead of from the weight gradient's factor correlations (wg5.hip, PY = 2)
 // Process-wide (capi.cpp, read when the library is loaded; also dmm_set_option): DMM_NO_OVERLAP, DMM_GRAPH, DMM_GRAD_BUCKET_MB;
@@ -168,6 +176,7 @@ struct PlanSwitches {
   bool no_pack_tiles = false, no_hf = false, no_c3_merge = false, no_cvp_merge = false, no_wgp_merge = false, no_two_pass = false,
        no_eff_compact = false, no_s2_interleave = false, no_raw_stats = false, no_r1_stats = false;
   int pack_cut = 0;  // 0: by weight count
+  long long transition_pool_rows = -1;  // -1: TRANSITION_POOL_MIN_ROWS (plan.cpp)
   static PlanSwitches from_environment();
 };
 

@@ -70,6 +70,16 @@ struct MaxpoolArgs {
   int stat_stride;  // doubles between the STAT_REPS replicas of sum / sq (0: a single copy)
 };
 
+// p = avgpool2x2(relu(x * scale + shift)): the operand of a transition's 1x1 convolution, written once (pointwise.hip: avgpool2_kernel)
+struct AvgPool2Args {
+  const void* x;       // (B, H, W, ld), pre-offset to the first channel of the window; H and W even
+  int ld, H, W, B, C;  // C: storage channels of the window, whole 16-byte slots
+  const float* scale;  // C floats each
+  const float* shift;
+  void* out;           // (B, H / 2, W / 2, ldo), pre-offset
+  int ldo;
+};
+
 struct MaxpoolBwdArgs {
   const void* y0;
   int ld0, H0, W0, B, C;
@@ -344,6 +354,7 @@ hipError_t launch_bn_finalize(const BnFinalizeArgs& a, hipStream_t st);
 hipError_t launch_bn_bwd_finalize(const BnBwdFinalizeArgs& a, hipStream_t st);
 hipError_t launch_maxpool_fwd(const MaxpoolArgs& a, int dtype, hipStream_t st);
 hipError_t launch_maxpool_bwd(const MaxpoolBwdArgs& a, int dtype, hipStream_t st);
+hipError_t launch_avgpool2_fwd(const AvgPool2Args& a, int dtype, hipStream_t st);   // hipErrorInvalidValue: not whole slots / windows
 hipError_t launch_bce_metrics(const BceArgs& a, int dtype, hipStream_t st);
 // accumulate == 0: a hipMemsetAsync of counts on `st` goes in front of the kernel; otherwise the kernel adds to what is there
 hipError_t launch_logit_hist(const LogitHistArgs& a, int accumulate, hipStream_t st);

@@ -194,6 +194,89 @@ hipError_t launch_maxpool_fwd(const MaxpoolArgs& a, int dtype, hipStream_t st) {
   return hipGetLastError();
 }
 
+// ---------------------------------------------------------------------------------------------------
+// The operand of a transition's 1x1 convolution, p = avgpool2x2(relu(bn(x))), written ONCE in the storage type: the generic gather
+// (gather.h: gather_slot, G_POOL2) forms every slot of it synchronously - four loads, four BN+ReLU, an average - again for every
+// output-column tile of the forward and of the weight gradient.  Per element exactly gather_slot's arithmetic - from 0, add
+// fmaxf(fmaf(x, sc, sh), 0) for the sub-pixels (0,0), (0,1), (1,0), (1,1) in that order, times 0.25f, ONE rounding - so p holds, bit
+// for bit, the operand the generic path builds.  A thread owns ONE channel slot (scale / shift stay in registers) and walks pooled
+// pixels two at a time (eight 16-byte loads in flight), as apply_corr does.
+template <typename T>
+__global__ __launch_bounds__(256) void avgpool2_kernel(AvgPool2Args a, unsigned rows_per_step) {
+  constexpr int SLOT = TT<T>::SLOT;
+  typedef typename TT<T>::vec V;
+  const unsigned ncs = (unsigned)(a.C / SLOT);
+  const unsigned gtid = blockIdx.x * blockDim.x + threadIdx.x;
+  const unsigned cs = gtid % ncs, prow = gtid / ncs;
+  if (prow >= rows_per_step) return;  // (the grid is rounded up to whole blocks)
+  const int c = (int)cs * SLOT;
+  float sc[SLOT], sh[SLOT];
+  load_f32s<SLOT>(a.scale + c, sc); load_f32s<SLOT>(a.shift + c, sh);
+  const T* xbase = (const T*)a.x + c;
+  T* obase = (T*)a.out + c;
+  const int Hp = a.H / 2, Wp = a.W / 2;
+  const size_t npix = (size_t)a.B * Hp * Wp;
+  auto corner = [&](size_t p) {  // source pixel (b, 2 oy, 2 ox) of pooled pixel p
+    const size_t row = p / (size_t)Wp;   // b * Hp + oy
+    const size_t b = row / (size_t)Hp;
+    return ((b * a.H + 2 * (row - b * Hp)) * (size_t)a.W + 2 * (p - row * Wp));
+  };
+  auto pool = [&](const V (&v)[4], size_t p) {
+    float acc[SLOT];
+#pragma unroll
+    for (int i = 0; i < SLOT; ++i) acc[i] = 0.f;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      float f[SLOT];
+      vec_to_f32<T>(v[k], f);
+#pragma unroll
+      for (int i = 0; i < SLOT; ++i) acc[i] += fmaxf(fmaf(f[i], sc[i], sh[i]), 0.f);
+    }
+#pragma unroll
+    for (int i = 0; i < SLOT; ++i) acc[i] *= 0.25f;
+    *(V*)(obase + p * a.ldo) = f32_to_vec<T>(acc);
+  };
+  constexpr int U = 2;
+  size_t p = prow;
+  for (; p + (size_t)(U - 1) * rows_per_step < npix; p += (size_t)U * rows_per_step) {
+    V v[U][4];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const size_t s = corner(p + (size_t)u * rows_per_step);
+#pragma unroll
+      for (int k = 0; k < 4; ++k) v[u][k] = *(const V*)(xbase + (s + (size_t)(k >> 1) * a.W + (k & 1)) * a.ld);
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u) pool(v[u], p + (size_t)u * rows_per_step);
+  }
+  for (; p < npix; p += rows_per_step) {
+    const size_t s = corner(p);
+    V v[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) v[k] = *(const V*)(xbase + (s + (size_t)(k >> 1) * a.W + (k & 1)) * a.ld);
+    pool(v, p);
+  }
+}
+
+hipError_t launch_avgpool2_fwd(const AvgPool2Args& a, int dtype, hipStream_t st) {
+  const int slot = dtype == DT_F32 ? 4 : 8;
+  // whole 16-byte slots in whole 2x2 windows, constants for every channel: anything else would read or write outside the window
+  if (a.C <= 0 || a.C % slot || a.ld % slot || a.ldo % slot || a.ld < a.C || a.ldo < a.C || a.H % 2 || a.W % 2 || a.scale == nullptr ||
+      a.shift == nullptr || a.x == nullptr || a.out == nullptr)
+    return hipErrorInvalidValue;
+  const unsigned ncs = (unsigned)(a.C / slot);
+  const size_t npix = (size_t)a.B * (a.H / 2) * (a.W / 2);
+  if (npix == 0) return hipSuccess;
+  // pooled pixels walked side by side: up to ~4 M threads, a whole number of channel-slot groups (launch_apply_corr)
+  const size_t rows = std::min<size_t>(npix, std::max<size_t>(1, (size_t)(16384 * 256) / ncs));
+  const size_t threads = rows * ncs;
+  const int grid = (int)((threads + 255) / 256);
+  if (dtype == DT_F16) hipLaunchKernelGGL(avgpool2_kernel<f16>, dim3(grid), dim3(256), 0, st, a, (unsigned)rows);
+  else if (dtype == DT_BF16) hipLaunchKernelGGL(avgpool2_kernel<bf16>, dim3(grid), dim3(256), 0, st, a, (unsigned)rows);
+  else hipLaunchKernelGGL(avgpool2_kernel<float>, dim3(grid), dim3(256), 0, st, a, (unsigned)rows);
+  return hipGetLastError();
+}
+
 // grad wrt conv0 output: dz0[y,x,c] = relu'(.) * sum over pooling windows whose saved argmax is (y,x);
 // stores s*dz0 into gy0 and reduces sum dz0, sum dz0*y0 for norm0's backward.
 template <typename T>

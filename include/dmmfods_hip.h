@@ -580,6 +580,19 @@ typedef struct {
 size_t dmm_conv_scratch_bytes(const dmm_conv_desc* d);
 int dmm_conv_forward(const dmm_conv_desc* d, const void* x, const float* w, const float* scale, const float* shift, void* y,
                      double* stats, void* scratch, void* stream);
+/* Test entry point, like the others of this section: where record `index` of a BOUND plan's training forward list (a storing convolution;
+ * DMM_ERR_INVALID otherwise) leaves its result - byte offset into the workspace and dims = {B, H, W, N, pixel pitch in elements} of the
+ * NHWC tensor in the storage type - so that a test can compare one layer's output between two plans.  (Every exported dmm_ symbol is
+ * declared here: tests/test_accum_cpu.py.) */
+int dmm_plan_record_output(const dmm_plan* plan, int index, int64_t* ws_offset, int32_t* dims);
+/* The pooling pass in front of a transition's 1x1 convolution (torchvision _Transition: norm, relu, conv, AvgPool2d(2, 2), with the
+ * pool moved in front of the linear conv) on its own: out[b, y, x, c] = 0.25 * sum of relu(x * scale[c] + shift[c]) over the 2x2 window,
+ * summed in fp32 in raster order from 0 and rounded once to the storage type - what dmm_conv_forward with mode 2 feeds its matrix
+ * core, bit for bit.  x: T NHWC with pixel pitch ld, pre-offset to a window of C channels; out: T (B, H/2, W/2) with pitch ldo,
+ * pre-offset; bytes outside the window are not touched.  DMM_ERR_INVALID for odd H / W, C / ld / ldo that are not whole 16-byte slots,
+ * pitches below C and null pointers. */
+int dmm_avgpool2_bnrelu(int dtype, const void* x, int ld, int B, int H, int W, int C, const float* scale, const float* shift, void* out,
+                        int ldo, void* stream);
 /* The logits launch of the network's last convolution (dec_out_to_heat_maps.refine1; reference graphs/models/Dense_U_Net_lidar.py:128-131)
  * on its own: a plain convolution at stride 1 (optionally behind BN+ReLU) whose output is written UNROUNDED as fp32 NCHW
  * (B, Cout, Ho, Wo) - no statistics.  It dispatches as the plan's launch does: thin.hip (16-bit storage, 64 input channels, 1..3

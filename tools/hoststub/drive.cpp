@@ -140,7 +140,8 @@ void chk_ops(const std::vector<Op>& ops) {
                      CHK(o.bf.scale); CHK(o.bf.shift); CHK(o.bf.mean); CHK(o.bf.invstd); break;
       case OP_BNBWD: CHK(o.bb.red1); CHK(o.bb.red2); CHK(o.bb.mean); CHK(o.bb.invstd); CHK(o.bb.scale); CHK(o.bb.dgamma); CHK(o.bb.dbeta);
                      CHK(o.bb.qd); CHK(o.bb.rd); CHK(o.bb.q); CHK(o.bb.r); CHK(o.bb.ql); CHK(o.bb.rl); break;
-      case OP_POOL: CHK(o.mp.y0); CHK(o.mp.scale); CHK(o.mp.shift); CHK(o.mp.out); CHK(o.mp.argmax); CHK(o.mp.stat_sum); CHK(o.mp.stat_sq); break;
+      case OP_POOL: if (o.epi == POOL_AVG2) { CHK(o.ap.x); CHK(o.ap.scale); CHK(o.ap.shift); CHK(o.ap.out); break; }
+                    CHK(o.mp.y0); CHK(o.mp.scale); CHK(o.mp.shift); CHK(o.mp.out); CHK(o.mp.argmax); CHK(o.mp.stat_sum); CHK(o.mp.stat_sq); break;
       case OP_POOLBWD: CHK(o.mpb.y0); CHK(o.mpb.scale); CHK(o.mpb.shift); CHK(o.mpb.gpool); CHK(o.mpb.xpool); CHK(o.mpb.q); CHK(o.mpb.r);
                        CHK(o.mpb.ql); CHK(o.mpb.rl); CHK(o.mpb.mean); CHK(o.mpb.invstd); CHK(o.mpb.argmax); CHK(o.mpb.gy0); CHK(o.mpb.red1);
                        CHK(o.mpb.red2); break;
@@ -769,7 +770,9 @@ struct Dumper {
                        DP(running_mean); DP(running_var); DP(scale); DP(shift); DP(mean); DP(invstd); DI(C); DI(training); DD(momentum); DD(eps); printf("\n"); break; }
       case OP_BNBWD: { const BnBwdFinalizeArgs& a = o.bb; printf("    bnbwd:"); DP(red1); DP(red2); DI(stat_stride); DP(mean); DP(invstd); DP(scale); DP(dgamma);
                        DP(dbeta); DP(qd); DP(rd); DP(q); DP(r); DP(ql); DP(rl); DD(count); DD(grad_scale); DI(C); DI(accumulate); printf("\n"); break; }
-      case OP_POOL: { const MaxpoolArgs& a = o.mp; printf("    pool:"); DP(y0); DI(ld0); DI(H0); DI(W0); DI(B); DI(C); DP(scale); DP(shift); DP(out); DI(ldo); DI(Hp);
+      case OP_POOL: if (o.epi == POOL_AVG2) { const AvgPool2Args& a = o.ap; printf("    avgpool2:"); DP(x); DI(ld); DI(H); DI(W); DI(B); DI(C); DP(scale); DP(shift); DP(out);
+                                      DI(ldo); printf("\n"); break; }
+                    { const MaxpoolArgs& a = o.mp; printf("    pool:"); DP(y0); DI(ld0); DI(H0); DI(W0); DI(B); DI(C); DP(scale); DP(shift); DP(out); DI(ldo); DI(Hp);
                       DI(Wp); DP(argmax); DP(stat_sum); DP(stat_sq); DI(stat_stride); printf("\n"); break; }
       case OP_POOLBWD: { const MaxpoolBwdArgs& a = o.mpb; printf("    poolbwd:"); DP(y0); DI(ld0); DI(H0); DI(W0); DI(B); DI(C); DP(scale); DP(shift); DP(gpool);
                          DP(xpool); DP(q); DP(r); DP(ql); DP(rl); DP(mean); DP(invstd); DI(ldg); DI(Hp); DI(Wp); DP(argmax); DP(gy0); DP(red1); DP(red2);
