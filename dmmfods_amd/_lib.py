@@ -107,6 +107,7 @@ class Component(C.Structure):
 
 assert C.sizeof(Component) == 32
 
+MATCH_MAX_PER_PLANE = 4096   # DMM_MATCH_MAX_PER_PLANE
 
 PREP_LAUNCH_BATCH, PREP_MAX_ITEMS = 32, 1 << 23   # DMM_PREP_LAUNCH_BATCH, DMM_PREP_MAX_ITEMS
 
@@ -183,6 +184,9 @@ def lib():
     L.dmm_heat_components_workspace.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]
     L.dmm_heat_components_workspace.restype = sz
     L.dmm_heat_components.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, f32, C.c_int, C.c_int, vp, sz, vp, vp, vp, vp]
+    L.dmm_match_objects_workspace.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int]
+    L.dmm_match_objects_workspace.restype = sz
+    L.dmm_match_objects.argtypes = [vp, vp, C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, vp, sz, vp, vp, vp, i64, vp]
     L.dmm_prep_image.argtypes = [vp, i64, vp, i64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]
     L.dmm_prep_lidar_workspace.argtypes = [C.c_int, C.c_int, C.c_int]
     L.dmm_prep_lidar_workspace.restype = sz
@@ -252,7 +256,7 @@ EXPORTS = [
     "dmm_adam_step_segmented_ema", "dmm_adam_step_guarded_segmented_ema",
     "dmm_plan_wgrad_batch_counts", "dmm_conv_wgrad_grouped", "dmm_bw1_reduce_grouped",
     "dmm_logit_hist_elems", "dmm_logit_hist", "dmm_augment_batch", "dmm_warp_batch",
-    "dmm_heat_components_workspace", "dmm_heat_components",
+    "dmm_heat_components_workspace", "dmm_heat_components", "dmm_match_objects_workspace", "dmm_match_objects",
     "dmm_prep_image", "dmm_prep_lidar_workspace", "dmm_prep_lidar", "dmm_prep_heat_maps",
     "dmm_avgpool2_bnrelu", "dmm_plan_record_output",
 ]

@@ -18,8 +18,8 @@ at every threshold; ``best_val_iou`` and the checkpoints do not depend on it) an
 dropout in one launch per batch; its batch counter travels in the checkpoint's ``"augment"`` entry; validation is never augmented)
 and object-level validation metrics (``config.agent.object_metrics``: the logits and the target of every validation batch are cut into
 connected components on the device, ``dmmfods_amd.detect``, and the epoch's ``val_history`` row carries precision, recall, F1 and AP
-over objects; one synchronisation per validation batch; ``best_val_iou`` and the checkpoints do not depend on it) and batch preparation
-on the device (``config.loader.raw_frames``: a dict of ``dmmfods_amd.prepare.BatchPrepare``'s arguments; the loader yields the uint8
+over objects; one synchronisation per validation batch, or with ``match: "device"`` one per epoch; ``best_val_iou`` and the
+checkpoints do not depend on it) and batch preparation on the device (``config.loader.raw_frames``: a dict of ``dmmfods_amd.prepare.BatchPrepare``'s arguments; the loader yields the uint8
 image, the LiDAR points and the boxes of each frame, ``dmmfods_amd.datasets.RawFrames``, and three launches build the tensors the
 reference's host preparation would, in training and in validation; the augmentation, where configured, follows it)."""
 import logging
@@ -36,7 +36,8 @@ from ..augment import BatchAugment
 from ..datasets.RawFrames import RawFrames_Loader
 from ..datasets.WaymoData import WaymoDataset_Loader
 from ..prepare import BatchPrepare
-from ..detect import HeatMapDetector, ObjectMetrics
+from .._lib import MATCH_MAX_PER_PLANE
+from ..detect import DeviceObjectMetrics, HeatMapDetector, ObjectMetrics
 from ..graphs.models.Dense_U_Net_lidar import densenet121_u_lidar
 from ..metrics import ThresholdSweep, logit_thresholds
 from ..optim import DynamicLossScaler, FusedAdam, fine_tune_groups
@@ -200,20 +201,33 @@ class Dense_U_Net_lidar_Agent:
 
     def _make_object_metrics(self, spec):
         """spec: None (no object metrics) or a dict with any of iou (0.5), connectivity (8), max_per_plane (1024), min_area (1) and
-        threshold (iou_threshold; it cuts the logits and the target alike, as the loss kernel's counts do).  Returns (detector, metrics)."""
+        threshold (iou_threshold; it cuts the logits and the target alike, as the loss kernel's counts do), and match: "host" (default:
+        ObjectMetrics, one synchronisation per validation batch) or "device" (DeviceObjectMetrics, one per epoch; it also takes
+        capacity, the predictions kept per class for the AP).  Returns (detector, metrics)."""
         if spec is None:
             return None, None
         if not isinstance(spec, Mapping):
-            raise ValueError("agent.object_metrics must be a dict (iou, connectivity, max_per_plane, min_area, threshold)")
+            raise ValueError("agent.object_metrics must be a dict (iou, connectivity, max_per_plane, min_area, threshold, match, capacity)")
         kw = dict(spec)
-        unknown = set(kw) - {"iou", "connectivity", "max_per_plane", "min_area", "threshold"}
+        unknown = set(kw) - {"iou", "connectivity", "max_per_plane", "min_area", "threshold", "match", "capacity"}
         if unknown:
             raise ValueError(f"agent.object_metrics: unknown keys {sorted(unknown)}")
         iou = kw.pop("iou", 0.5)
         threshold = kw.pop("threshold", None)
+        match = kw.pop("match", "host")
+        if match not in ("host", "device"):
+            raise ValueError(f"agent.object_metrics: match must be 'host' or 'device', got {match!r}")
+        if match == "host" and "capacity" in kw:
+            raise ValueError("agent.object_metrics: capacity goes with match = 'device'")
+        device_kw = {"capacity": kw.pop("capacity")} if "capacity" in kw else {}
         try:
             detector = HeatMapDetector(float(self.config.agent.iou_threshold if threshold is None else threshold), **kw)
-            metrics = ObjectMetrics(self.config.model.num_classes, iou=iou)
+            if match == "device":
+                if detector.max_per_plane > MATCH_MAX_PER_PLANE:
+                    raise ValueError(f"match = 'device' takes a max_per_plane of at most {MATCH_MAX_PER_PLANE}")
+                metrics = DeviceObjectMetrics(self.config.model.num_classes, iou=iou, **device_kw)
+            else:
+                metrics = ObjectMetrics(self.config.model.num_classes, iou=iou)
         except (TypeError, ValueError) as e:
             raise ValueError(f"agent.object_metrics: {e}") from None
         return detector, metrics
@@ -419,7 +433,8 @@ class Dense_U_Net_lidar_Agent:
                 m = self.model.loss_metrics(prediction, ht_map)
                 if self.sweep is not None:
                     self.sweep.update(prediction, ht_map)     # one more launch on the same stream, no synchronisation
-                if self.object_metrics is not None:           # two calls on the same stream; pulling the records synchronises once
+                if self.object_metrics is not None:           # two calls on the same stream; match "host" pulls the records (one
+                    # synchronisation), match "device" pairs them with three more launches and pulls nothing before compute()
                     self.object_metrics.update(self.object_detector(prediction.float()), self.object_detector(ht_map.float()))
                 iou_pc, nans, acc_pc = self._batch_metrics(m)
                 ep["loss"][b], ep["iou"][b], ep["nans"][b], ep["acc"][b] = m["loss_per_class"], iou_pc, nans, acc_pc

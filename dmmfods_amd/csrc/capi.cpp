@@ -962,6 +962,48 @@ int dmm_heat_components(const float* maps, int B, int NC, int H, int W, float th
   return DMM_OK;
 }
 
+// why dmm_match_objects would refuse these sizes ("" = it would not); shared with the workspace query
+static std::string match_refusal(int B, int NC, int cap_pred, int cap_gt) {
+  if (B < 1 || NC < 1) return "B and NC must be >= 1";
+  if ((long long)B * NC > 65535) return "B * NC must be <= 65535";
+  if (cap_pred < 1 || cap_pred > DMM_MATCH_MAX_PER_PLANE || cap_gt < 1 || cap_gt > DMM_MATCH_MAX_PER_PLANE)
+    return "cap_pred and cap_gt must be in [1, " + std::to_string(DMM_MATCH_MAX_PER_PLANE) + "] (DMM_MATCH_MAX_PER_PLANE: the matcher walks a plane's "
+           "predictions serially, it does not take dmm_heat_components' maximum of " + std::to_string(DMM_CC_MAX_PER_PLANE) + ")";
+  return "";
+}
+
+size_t dmm_match_objects_workspace(int B, int NC, int cap_pred, int cap_gt) {
+  if (!match_refusal(B, NC, cap_pred, cap_gt).empty()) return 0;
+  return match_layout(B * NC).total;
+}
+
+int dmm_match_objects(const dmm_component* pred, const int32_t* pred_counts, int cap_pred, const dmm_component* gt, const int32_t* gt_counts,
+                      int cap_gt, int B, int NC, int min_area, double iou, void* workspace, size_t workspace_bytes, uint8_t* matched,
+                      int64_t* totals, int32_t* entries, int64_t capacity, void* stream) {
+  const std::string who = "dmm_match_objects: ";
+  if (!pred || !pred_counts || !gt || !gt_counts || !workspace || !totals || !entries) return fail(DMM_ERR_INVALID, who + "null argument");
+  if ((uintptr_t)pred % 8 || (uintptr_t)gt % 8) return fail(DMM_ERR_INVALID, who + "pred / gt records must be 8-byte aligned");
+  if ((uintptr_t)pred_counts % 4 || (uintptr_t)gt_counts % 4) return fail(DMM_ERR_INVALID, who + "pred_counts / gt_counts must be 4-byte aligned");
+  if ((uintptr_t)totals % 8) return fail(DMM_ERR_INVALID, who + "totals must be 8-byte aligned");
+  if ((uintptr_t)entries % 4) return fail(DMM_ERR_INVALID, who + "entries must be 4-byte aligned");
+  if ((uintptr_t)workspace % 16) return fail(DMM_ERR_INVALID, who + "workspace must be 16-byte aligned");
+  const std::string why = match_refusal(B, NC, cap_pred, cap_gt);
+  if (!why.empty()) return fail(DMM_ERR_INVALID, who + why);
+  if (min_area < 1) return fail(DMM_ERR_INVALID, who + "min_area must be >= 1");
+  if (!(iou > 0.0 && iou <= 1.0)) return fail(DMM_ERR_INVALID, who + "iou must be in (0, 1]");   // (NaN fails both compares)
+  if (capacity < 1 || capacity > 2147483647ll) return fail(DMM_ERR_INVALID, who + "capacity must be in [1, 2^31 - 1]");
+  const MatchLayout lay = match_layout(B * NC);
+  if (workspace_bytes < lay.total) return fail(DMM_ERR_INVALID, who + "workspace_bytes is below dmm_match_objects_workspace (" + std::to_string(lay.total) + ")");
+  MatchArgs a;
+  memset(&a, 0, sizeof(a));
+  a.pred = pred; a.gt = gt; a.pred_counts = pred_counts; a.gt_counts = gt_counts;
+  a.np = (int*)((char*)workspace + lay.np); a.ng = (int*)((char*)workspace + lay.ng); a.base = (long long*)((char*)workspace + lay.base);
+  a.matched = matched; a.totals = (long long*)totals; a.entries = entries; a.capacity = capacity; a.iou = iou;
+  a.B = B; a.NC = NC; a.cap_pred = cap_pred; a.cap_gt = cap_gt; a.min_area = min_area;
+  HIPCHK(launch_match(a, (hipStream_t)stream));
+  return DMM_OK;
+}
+
 int dmm_plan_loss_backward(dmm_plan* plan, const float* logits, const float* target, double* metrics_out, void* stream) {
   if (!plan || !plan->bound) return fail(DMM_ERR_STATE, "plan not bound");
   if (!logits || !target) return fail(DMM_ERR_INVALID, "null argument");

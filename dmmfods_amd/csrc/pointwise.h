@@ -156,6 +156,32 @@ constexpr int CC_LAUNCHES = 7;
 void components_grids(const ComponentsArgs& a, unsigned gx[CC_LAUNCHES]);
 hipError_t launch_components(const ComponentsArgs& a, hipStream_t st);
 
+// ---- object matching (match.hip) ----
+struct MatchArgs {
+  const dmm_component* pred;   // [B * NC][cap_pred]
+  const dmm_component* gt;     // [B * NC][cap_gt]
+  const int* pred_counts;      // [B * NC]
+  const int* gt_counts;
+  int* np;                     // workspace, [B * NC]: participating predictions of the plane
+  int* ng;                     // workspace, [B * NC]: participating ground-truth records
+  long long* base;             // workspace, [B * NC]: where the plane's entries start in its class
+  unsigned char* matched;      // (B, NC, cap_pred), or null
+  long long* totals;           // (NC, 8)
+  int* entries;                // (NC, capacity, 2)
+  long long capacity;          // 1 .. 2^31 - 1
+  double iou;
+  int B, NC;                   // B * NC <= 65535
+  int cap_pred, cap_gt;        // 1 .. DMM_MATCH_MAX_PER_PLANE
+  int min_area;
+};
+// where the call's three arrays lie in its workspace (bytes from its start, each a multiple of 16) and the total
+struct MatchLayout { size_t np, ng, base, total; };
+MatchLayout match_layout(int planes);
+// the three launches of one call, in order; each grid is (x)
+constexpr int MATCH_LAUNCHES = 3;
+void match_grids(const MatchArgs& a, unsigned gx[MATCH_LAUNCHES]);
+hipError_t launch_match(const MatchArgs& a, hipStream_t st);
+
 // ---- batch augmentation (augment.hip) ----
 constexpr int AUG_MAX_CHANNELS = DMM_AUG_MAX_CHANNELS;
 constexpr int AUG_LAUNCH_BATCH = DMM_AUG_LAUNCH_BATCH;

@@ -6,7 +6,10 @@ labels the connected components of every plane and emits one 32-byte record per 
 bit-reproducible.  The ground truth of this project is boxes filled into maps, so the SAME call over the target recovers the
 ground-truth objects; ``match_objects`` then pairs predictions with them and ``ObjectMetrics`` accumulates an epoch.
 
-Nothing here synchronises except ``Detections.to_host()``.
+``DeviceObjectMetrics`` does the pairing on the device instead: ``dmm_match_objects`` (csrc/match.hip) restates
+``match_plane`` and keeps the epoch's counts and ranked list in device memory; the host classes stay as they are and are its reference.
+
+Nothing here synchronises except ``Detections.to_host()`` and ``DeviceObjectMetrics.state()`` / ``compute()``, once per epoch.
 """
 import numpy as np
 import torch
@@ -235,3 +238,119 @@ class ObjectMetrics:
                 "f1": _ratio(2 * self.tp, 2 * self.tp + self.fp + self.fn), "ap": ap,
                 "tp": self.tp.copy(), "fp": self.fp.copy(), "fn": self.fn.copy(),
                 "num_pred": self.num_pred.copy(), "num_gt": self.num_gt.copy(), "overflowed_planes": int(self.overflowed_planes)}
+
+
+TOTALS_FIELDS = ("tp", "fp", "fn", "num_pred", "num_gt", "overflowed_planes", "cursor", "reserved")   # dmm_match_objects' totals row
+
+
+class DeviceObjectMetrics:
+    """ObjectMetrics with the matching on the device: update() is one dmm_match_objects call on the current stream - no
+    synchronisation, no to_host() - which adds to an epoch state in device memory: totals (NC, 8) int64 and, per class, the (score
+    bits, matched) entries of up to `capacity` predictions in order of arrival.  compute() performs the one synchronisation of the
+    epoch and returns ObjectMetrics.compute()'s keys, bit-equal, plus dropped_predictions (NC, int64): the predictions of a class
+    that arrived behind its capacity.  They are counted in tp / fp / fn / num_pred; only the AP, which needs every score, is NaN for
+    that class."""
+
+    def __init__(self, num_classes, iou=0.5, capacity=1 << 20):
+        iou = float(iou)
+        if not 0.0 < iou <= 1.0:
+            raise ValueError("iou must be in (0, 1]")
+        if isinstance(capacity, bool) or int(capacity) != capacity or not 1 <= capacity <= 2 ** 31 - 1:
+            raise ValueError("capacity must be an integer in [1, 2^31 - 1]")
+        self.num_classes, self.iou, self.capacity = int(num_classes), iou, int(capacity)
+        self._totals = self._entries = None   # device state, allocated by the first update
+        self._workspace = {}                  # (device, B, NC, cap_pred, cap_gt) -> uint8 tensor, as HeatMapDetector's
+
+    def reset(self):
+        """Zeroes the epoch state where there is one: a memset on the current stream, no synchronisation."""
+        if self._totals is not None:
+            self._totals.zero_()
+
+    def _workspace_for(self, device, shape):
+        key = (device,) + tuple(shape)
+        ws = self._workspace.get(key)
+        if ws is None:
+            nbytes = _lib.lib().dmm_match_objects_workspace(*shape)
+            if nbytes == 0:
+                B, NC, cap_pred, cap_gt = shape
+                if max(cap_pred, cap_gt) > _lib.MATCH_MAX_PER_PLANE:
+                    raise ValueError(f"dmm_match_objects takes at most {_lib.MATCH_MAX_PER_PLANE} records a plane (DMM_MATCH_MAX_PER_PLANE), "
+                                     f"got max_per_plane {max(cap_pred, cap_gt)}: lower the detector's max_per_plane or match on the host")
+                raise ValueError(f"dmm_match_objects refuses the shape {tuple(shape)}")
+            ws = self._workspace[key] = torch.empty(nbytes, dtype=torch.uint8, device=device)
+        return ws
+
+    def update(self, pred, gt, return_matched=False):
+        """pred, gt: the Detections of the predictions and of the ground truth of one batch.  Three launches, no synchronisation.
+        return_matched: returns the (B, NC, max_per_plane) uint8 device tensor of dmm_match_objects' `matched`."""
+        if not isinstance(pred, Detections) or not isinstance(gt, Detections):
+            raise TypeError("DeviceObjectMetrics.update takes two Detections (device objects); host lists go to ObjectMetrics")
+        pr, gr = pred.records, gt.records
+        if pr.dim() != 4 or gr.dim() != 4 or pr.shape[:2] != gr.shape[:2] or pred.counts.shape != pr.shape[:2] or gt.counts.shape != gr.shape[:2]:
+            raise ValueError("pred and gt must cover the same samples and classes")
+        B, NC, cap_pred, _ = pr.shape
+        cap_gt = gr.shape[2]
+        if NC != self.num_classes:
+            raise ValueError(f"expected {self.num_classes} classes")
+        if pred.min_area != gt.min_area:
+            raise ValueError(f"pred and gt must share min_area, got {pred.min_area} and {gt.min_area}")
+        if not pr.is_cuda or gr.device != pr.device:
+            raise RuntimeError("dmmfods_amd computes on the GPU only; the Detections must live on one 'cuda' device (no CPU fallback)")
+        ws = self._workspace_for(pr.device, (B, NC, cap_pred, cap_gt))
+        if self._totals is None or self._totals.device != pr.device:
+            self._totals = torch.zeros((NC, 8), dtype=torch.int64, device=pr.device)
+            self._entries = torch.empty((NC, self.capacity, 2), dtype=torch.int32, device=pr.device)
+        pr, gr, pc, gc = pr.contiguous(), gr.contiguous(), pred.counts.contiguous(), gt.counts.contiguous()
+        matched = torch.empty((B, NC, cap_pred), dtype=torch.uint8, device=pr.device) if return_matched else None
+        _lib.check(_lib.lib().dmm_match_objects(pr.data_ptr(), pc.data_ptr(), cap_pred, gr.data_ptr(), gc.data_ptr(), cap_gt, B, NC,
+                                                int(pred.min_area), self.iou, ws.data_ptr(), ws.numel(),
+                                                matched.data_ptr() if return_matched else None, self._totals.data_ptr(),
+                                                self._entries.data_ptr(), self.capacity, _lib.stream_ptr()))
+        return matched
+
+    def state(self):
+        """The epoch state on the host (ONE synchronisation): a dict of numpy arrays - totals (NC, 8) int64 with the columns
+        TOTALS_FIELDS, filled (NC,) int64 = min(cursor, capacity), entries (sum(filled), 2) int32: the filled (score bits, matched)
+        rows class after class.  What a multi-rank caller gathers; merge_states() takes a list of them."""
+        nc = self.num_classes
+        if self._totals is None:
+            return {"totals": np.zeros((nc, 8), dtype=np.int64), "filled": np.zeros(nc, dtype=np.int64), "entries": np.zeros((0, 2), dtype=np.int32)}
+        totals = self._totals.cpu().numpy()
+        filled = np.minimum(totals[:, 6], self.capacity).astype(np.int64)
+        parts = [self._entries[n, :int(filled[n])] for n in range(nc)]
+        entries = torch.cat(parts).cpu().numpy() if int(filled.sum()) else np.zeros((0, 2), dtype=np.int32)
+        return {"totals": totals, "filled": filled, "entries": np.ascontiguousarray(entries, dtype=np.int32)}
+
+    def compute(self):
+        return merge_states([self.state()])
+
+
+def merge_states(states):
+    """states: a list of DeviceObjectMetrics.state() dicts (one, or one per rank).  Returns what compute() would have returned had the
+    states' updates happened in list order on one device of unbounded capacity: totals added, entries concatenated class by class,
+    then ObjectMetrics.compute()'s own arithmetic (_ratio, average_precision).  dropped_predictions adds up what each state dropped
+    (cursor - filled); the AP of a class with a dropped prediction is NaN."""
+    if not states:
+        raise ValueError("merge_states needs at least one state")
+    nc = states[0]["totals"].shape[0]
+    totals = np.zeros((nc, 8), dtype=np.int64)
+    scores, flags = [[] for _ in range(nc)], [[] for _ in range(nc)]
+    dropped = np.zeros(nc, dtype=np.int64)
+    for s in states:
+        t, filled, e = np.asarray(s["totals"], dtype=np.int64), np.asarray(s["filled"], dtype=np.int64), np.asarray(s["entries"], dtype=np.int32)
+        if t.shape != (nc, 8) or filled.shape != (nc,) or e.shape != (int(filled.sum()), 2):
+            raise ValueError("merge_states: the states do not agree on the number of classes, or one is malformed")
+        totals += t
+        dropped += t[:, 6] - filled
+        first = np.concatenate([[0], np.cumsum(filled)])
+        for n in range(nc):
+            part = e[first[n]:first[n + 1]]
+            scores[n].append(np.ascontiguousarray(part[:, 0]).view(np.float32))
+            flags[n].append(part[:, 1] != 0)
+    tp, fp, fn, num_pred, num_gt = (totals[:, k].copy() for k in range(5))
+    ap = np.empty(nc, dtype=np.float64)
+    for n in range(nc):
+        ap[n] = average_precision(np.concatenate(scores[n]), np.concatenate(flags[n]), int(num_gt[n])) if dropped[n] == 0 else float("nan")
+    return {"precision": _ratio(tp, tp + fp), "recall": _ratio(tp, tp + fn), "f1": _ratio(2 * tp, 2 * tp + fp + fn), "ap": ap,
+            "tp": tp, "fp": fp, "fn": fn, "num_pred": num_pred, "num_gt": num_gt, "overflowed_planes": int(totals[:, 5].sum()),
+            "dropped_predictions": dropped}

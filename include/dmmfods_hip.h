@@ -20,6 +20,8 @@
  *                                          heat maps and LiDAR sampled nearest, the image bilinear - in one launch
  *   dmm_heat_components .................. nothing upstream (the reference cannot "compute IoU per bounding box", helper.py:311-315):
  *                                          connected components of a thresholded heat map, one record per object
+ *   dmm_match_objects .................... nothing upstream: greedy IoU pairing of predicted and ground-truth records, the counts
+ *                                          and the ranked (score, matched) list of an epoch kept on the device
  *   dmm_prep_image / dmm_prep_lidar / dmm_prep_heat_maps
  *                                          avgpool_tensor / lidar_array_to_image_like_tensor + pool_lidar_tensor /
  *                                          create_ground_truth_maps + maxpool_tensor  utils/Dense_U_Net_lidar_helper.py:233-305,430-515:
@@ -303,6 +305,49 @@ int dmm_heat_components(const float* maps, int B, int NC, int H, int W, float th
                         dmm_component* records /* device, [B*NC][max_per_plane] */,
                         int32_t* counts /* device, [B*NC]: the TRUE number of components, may exceed max_per_plane */,
                         void* stream);
+
+/* ---- object matching: greedy IoU pairing of the records of two dmm_heat_components calls ----
+ * (Nothing upstream.  detect.match_plane / match_objects / ObjectMetrics of the Python package state the same rule on the host and
+ * are this entry point's reference.)
+ * pred and gt are the records, pred_counts and gt_counts the counts dmm_heat_components wrote for the predictions and for the targets
+ * of one batch: (B, NC, cap, 8) int32 and (B, NC), with caps of their own.  A plane's kept records are its first min(count, cap)
+ * slots (a negative count keeps none), in ascending root order; the slots behind them are never read.  A record TAKES PART iff it is
+ * kept and area >= min_area, predictions and ground truth alike.  Per (b, n) plane the participating predictions are visited in
+ * descending score - an fp32 compare: +0.0 and -0.0 tie, negative scores order correctly; ties go to the ascending root, which is the
+ * lower slot; scores are never NaN, NaN is not foreground - and the visited prediction takes the still untaken participating
+ * ground-truth record of highest IoU with IoU >= iou, ties to the lower root.  IoU is over the inclusive boxes in fp64:
+ *   iw = min(x1) - max(x0) + 1, ih likewise; 0 unless both are positive; inter = double(iw) * double(ih);
+ *   area = double(x1 - x0 + 1) * double(y1 - y0 + 1) from the corners (not the record's component area);
+ *   v = inter / (area_a + area_b - inter): every operand an exact integer, ONE correctly rounded division; v >= iou and v > best
+ *   are fp64 compares.  3 of 10 pixels match at iou = 0.3.
+ * matched (may be NULL): (B, NC, cap_pred) uint8, 1 in the slot of a matched prediction, 0 in every other slot below cap_pred -
+ *   filtered out, unmatched or unfilled; each element is written exactly once.
+ * totals: (NC, 8) int64, the state of an epoch, which the call ADDS to: tp, fp, fn, num_pred, num_gt, overflowed_planes, cursor,
+ *   reserved.  num_pred and num_gt count participating records, tp + fp = num_pred, tp + fn = num_gt; overflowed_planes counts the
+ *   planes with count > cap on the prediction side plus those on the ground-truth side.  The caller zeroes it at the epoch's start.
+ * entries: (NC, capacity, 2) int32, (score bits, matched) per participating prediction in order of arrival - call, then sample,
+ *   then ascending root: the entry's position is totals[n].cursor before the call, plus the participating predictions of class n in
+ *   the samples before this one, plus its index among those of its plane.  A position >= capacity is not written; cursor advances by
+ *   the full number whatever the capacity, so max(0, cursor - capacity) predictions were dropped.
+ * Every output is an integer or a copied input value and every reduction an integer add: exact, bit-reproducible, independent of the
+ * launch geometry and of the order of arrival.  No floating-point atomics.  Three kernel launches on `stream`; no plan, no
+ * synchronisation, no memset, nothing uploaded from host memory, nothing allocated.
+ * workspace: dmm_match_objects_workspace bytes of device memory, 16-byte aligned, contents undefined before and after.
+ * Refuses with DMM_ERR_INVALID, before any HIP call, "dmm_match_objects: " in front of the message: a null pred, pred_counts, gt,
+ * gt_counts, workspace, totals or entries; records not 8-byte aligned, counts not 4-byte aligned, totals not 8-byte aligned, entries
+ * not 4-byte aligned, workspace not 16-byte aligned; B or NC < 1; B * NC > 65535; cap_pred or cap_gt outside
+ * [1, DMM_MATCH_MAX_PER_PLANE] (the walk is serial in the predictions and the rank quadratic: dmm_heat_components' own maximum of
+ * 65536 records a plane is refused here); min_area < 1; iou NaN or outside (0, 1]; capacity < 1 or > 2^31 - 1; workspace_bytes below
+ * dmm_match_objects_workspace(...). */
+#define DMM_MATCH_MAX_PER_PLANE 4096
+size_t dmm_match_objects_workspace(int B, int NC, int cap_pred, int cap_gt);   /* bytes; 0 for refused arguments */
+int dmm_match_objects(const dmm_component* pred, const int32_t* pred_counts, int cap_pred,
+                      const dmm_component* gt, const int32_t* gt_counts, int cap_gt,
+                      int B, int NC, int min_area, double iou,
+                      void* workspace, size_t workspace_bytes,
+                      uint8_t* matched /* device, (B, NC, cap_pred), may be NULL */,
+                      int64_t* totals /* device, (NC, 8) */, int32_t* entries /* device, (NC, capacity, 2) */, int64_t capacity,
+                      void* stream);
 
 /* ---- raw frames to training tensors: image, LiDAR points and boxes become the (B, 7, Ho, Wo) batch on the device ----
  * (Upstream this is host code: avgpool_tensor / lidar_array_to_image_like_tensor / pool_lidar_tensor / create_ground_truth_maps /

@@ -14,7 +14,7 @@ CLANG=/opt/rocm/lib/llvm/bin/clang++
 FLAGS="-x hip --offload-host-only --offload-arch=gfx950 -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize=function -fno-gpu-sanitize -fno-sanitize-recover=undefined -fno-omit-frame-pointer -I/opt/rocm/include -I$SRC -D__HIP_PLATFORM_AMD__ -w $DRIVE_EXTRA_FLAGS"
 pids=()
 cc() { $CLANG $FLAGS "${@:3}" -c "$1" -o "$OUT/$2" & pids+=($!); if [ ${#pids[@]} -ge 8 ]; then wait "${pids[0]}"; pids=("${pids[@]:1}"); fi; }
-for f in augment bw1 cf components conv3 cvp cvw guard halo hf lhist pig pointwise prepare thin warp wg3 wg5 wgp wgpw; do
+for f in augment bw1 cf components conv3 cvp cvw guard halo hf lhist match pig pointwise prepare thin warp wg3 wg5 wgp wgpw; do
   [ -f "$SRC/$f.hip" ] || continue   # (DRIVE_SRC: an older commit's csrc has fewer kernel files)
   cc "$SRC/$f.hip" "$f.o"
 done

@@ -57,6 +57,9 @@
 // DRIVE_PREPARE=1 (life-cycle run): behind the lives (and the calls of the three switches above), dmm_prep_image, dmm_prep_lidar and
 // dmm_prep_heat_maps on B = 1, 33 and 65 samples at pool 10 and 1 - the launches counted, every grid against a restatement, the memset of
 // the owner planes inside workspace_bytes - and every refusal of the three entry points, each with nothing enqueued (prepare_main).
+// DRIVE_MATCH=1 (life-cycle run): behind the lives (and the calls of the four switches above), dmm_match_objects on three shapes, B * NC up
+// to the entry point's limit, with operands that are addresses only and a real workspace between guard bands - three launches each,
+// every grid against a restatement, the workspace carve-up inside workspace_bytes - and every refusal, each with nothing enqueued (match_main).
 // Launch coalescing (dmm_set_option("batch_wgrad"), on by default; DRIVE_OPTIONS_OFF=batch_wgrad runs one launch per record,
 // DRIVE_BATCH_WGRAD=<0|1|2> sets the option's value: 2 = grouped on the weight-gradient stream instead of the caller's): every
 // life-cycle run watches the enqueue calls through the fake runtime's hook and checks, with the option on or off, that
@@ -1532,6 +1535,112 @@ static int prepare_main() {
 }
 #endif
 
+// ---- DRIVE_MATCH: dmm_match_objects (built against a csrc that has none: the case does not exist) ----
+#ifdef DMM_MATCH_MAX_PER_PLANE
+// Three shapes: one plane, a small batch at the detector's default cap, and B * NC at the entry point's own limit (there is no
+// per-launch plane cap to go past: a plane is a workgroup of a one-dimensional grid).  Records, counts, matched, totals and entries
+// are addresses only (reserved, PROT_NONE): the call uploads nothing, clears nothing and touches none of them on the host.  The
+// workspace is real memory of exactly dmm_match_objects_workspace bytes between two guard bands, which the host code must leave as
+// they are, workspace included.  Per shape, with and without `matched`: three launches and nothing else, each grid against the
+// restatement here, and the three arrays the call carves from its workspace inside the query's bytes.  Then every refusal.
+static int match_main() {
+  struct Shape { int B, NC, cap_pred, cap_gt; };
+  const Shape shapes[3] = {{1, 1, 1, 1}, {4, 3, 1024, 1000}, {21845, 3, DMM_MATCH_MAX_PER_PLANE, 7}};
+  const char* names[MATCH_LAUNCHES] = {"match_count_kernel", "match_offsets_kernel", "match_plane_kernel"};
+  int bad = 0;
+  g_hist = HistWatch();
+  g_hist.on = true;
+  for (const Shape& s : shapes) {
+    const size_t planes = (size_t)s.B * s.NC;
+    const size_t wsb = dmm_match_objects_workspace(s.B, s.NC, s.cap_pred, s.cap_gt);
+    const unsigned want[MATCH_LAUNCHES] = {(unsigned)planes, (unsigned)s.NC, (unsigned)planes};
+    const MatchLayout lay = match_layout((int)planes);
+    bool ok = wsb != 0 && lay.total == wsb && lay.np == 0 && lay.ng % 16 == 0 && lay.base % 16 == 0 && lay.ng >= planes * 4 &&
+              lay.base >= lay.ng + planes * 4 && lay.base + planes * 8 <= wsb;
+    const int64_t capacity = 1 << 20;
+    const dmm_component* pred = (const dmm_component*)reserve(planes * s.cap_pred * sizeof(dmm_component), PROT_NONE);
+    const dmm_component* gt = (const dmm_component*)reserve(planes * s.cap_gt * sizeof(dmm_component), PROT_NONE);
+    const int32_t* pc = (const int32_t*)reserve(planes * 4, PROT_NONE);
+    const int32_t* gc = (const int32_t*)reserve(planes * 4, PROT_NONE);
+    uint8_t* matched = (uint8_t*)reserve(planes * s.cap_pred, PROT_NONE);
+    int64_t* totals = (int64_t*)reserve((size_t)s.NC * 64, PROT_NONE);
+    int32_t* entries = (int32_t*)reserve((size_t)s.NC * capacity * 8, PROT_NONE);
+    unsigned char* block = (unsigned char*)aligned_alloc(16, 64 + wsb + 64);
+    memset(block, 0x5a, 64 + wsb + 64);
+    for (int with_matched = 0; with_matched < 2; ++with_matched) {
+      const HistWatch w0 = g_hist;
+      g_launch_log.clear();
+      MUST(dmm_match_objects(pred, pc, s.cap_pred, gt, gc, s.cap_gt, s.B, s.NC, 1, 0.5, block + 64, wsb, with_matched ? matched : nullptr, totals, entries,
+                             capacity, nullptr));
+      ok = ok && g_hist.launches == w0.launches + MATCH_LAUNCHES && g_hist.memsets == w0.memsets && g_hist.other == w0.other && g_launch_log.size() == (size_t)MATCH_LAUNCHES;
+      for (int k = 0; ok && k < MATCH_LAUNCHES; ++k)
+        ok = g_launch_log[k].kernel.find(names[k]) != std::string::npos && g_launch_log[k].gx == want[k] && g_launch_log[k].gy == 1u;
+    }
+    for (size_t i = 0; i < 64 + wsb + 64; ++i) ok = ok && block[i] == 0x5a;
+    printf("MATCH %d x %d caps %d / %d: %zu planes, workspace %zu %s\n", s.B, s.NC, s.cap_pred, s.cap_gt, planes, wsb, ok ? "ok" : "WRONG");
+    bad += !ok;
+    free(block);
+  }
+  // the refusals: nothing reaches the runtime, the message names the argument
+  const dmm_component* p = (const dmm_component*)reserve(1 << 20, PROT_NONE);
+  const dmm_component* g = (const dmm_component*)reserve(1 << 20, PROT_NONE);
+  const int32_t* pc = (const int32_t*)reserve(1 << 20, PROT_NONE);
+  const int32_t* gc = (const int32_t*)reserve(1 << 20, PROT_NONE);
+  uint8_t* m = (uint8_t*)reserve(1 << 20, PROT_NONE);
+  int64_t* tot = (int64_t*)reserve(1 << 20, PROT_NONE);
+  int32_t* ent = (int32_t*)reserve(1 << 20, PROT_NONE);
+  void* ws = reserve(1 << 20, PROT_NONE);
+  const size_t wsb = dmm_match_objects_workspace(2, 3, 8, 8);
+  const HistWatch w0 = g_hist;
+  auto refused = [&](int rc, const char* names) {
+    if (rc == DMM_ERR_INVALID && strncmp(dmm_last_error(), "dmm_match_objects: ", 19) == 0 && strstr(dmm_last_error(), names) != nullptr) return;
+    fprintf(stderr, "[drive] dmm_match_objects: not refused (%d) or the message does not say '%s': %s\n", rc, names, dmm_last_error());
+    ++bad;
+  };
+  auto off = [](auto* q, int bytes) { return (decltype(q))((char*)q + bytes); };
+  const double nan = __builtin_nan("");
+  refused(dmm_match_objects(nullptr, pc, 8, g, gc, 8, 2, 3, 1, 0.5, ws, wsb, m, tot, ent, 100, nullptr), "null");
+  refused(dmm_match_objects(p, nullptr, 8, g, gc, 8, 2, 3, 1, 0.5, ws, wsb, m, tot, ent, 100, nullptr), "null");
+  refused(dmm_match_objects(p, pc, 8, nullptr, gc, 8, 2, 3, 1, 0.5, ws, wsb, m, tot, ent, 100, nullptr), "null");
+  refused(dmm_match_objects(p, pc, 8, g, nullptr, 8, 2, 3, 1, 0.5, ws, wsb, m, tot, ent, 100, nullptr), "null");
+  refused(dmm_match_objects(p, pc, 8, g, gc, 8, 2, 3, 1, 0.5, nullptr, wsb, m, tot, ent, 100, nullptr), "null");
+  refused(dmm_match_objects(p, pc, 8, g, gc, 8, 2, 3, 1, 0.5, ws, wsb, m, nullptr, ent, 100, nullptr), "null");
+  refused(dmm_match_objects(p, pc, 8, g, gc, 8, 2, 3, 1, 0.5, ws, wsb, m, tot, nullptr, 100, nullptr), "null");
+  refused(dmm_match_objects(off(p, 4), pc, 8, g, gc, 8, 2, 3, 1, 0.5, ws, wsb, m, tot, ent, 100, nullptr), "records must be 8-byte aligned");
+  refused(dmm_match_objects(p, pc, 8, off(g, 4), gc, 8, 2, 3, 1, 0.5, ws, wsb, m, tot, ent, 100, nullptr), "records must be 8-byte aligned");
+  refused(dmm_match_objects(p, off(pc, 2), 8, g, gc, 8, 2, 3, 1, 0.5, ws, wsb, m, tot, ent, 100, nullptr), "counts must be 4-byte aligned");
+  refused(dmm_match_objects(p, pc, 8, g, off(gc, 1), 8, 2, 3, 1, 0.5, ws, wsb, m, tot, ent, 100, nullptr), "counts must be 4-byte aligned");
+  refused(dmm_match_objects(p, pc, 8, g, gc, 8, 2, 3, 1, 0.5, ws, wsb, m, off(tot, 4), ent, 100, nullptr), "totals must be 8-byte aligned");
+  refused(dmm_match_objects(p, pc, 8, g, gc, 8, 2, 3, 1, 0.5, ws, wsb, m, tot, off(ent, 2), 100, nullptr), "entries must be 4-byte aligned");
+  refused(dmm_match_objects(p, pc, 8, g, gc, 8, 2, 3, 1, 0.5, off(ws, 8), wsb, m, tot, ent, 100, nullptr), "workspace must be 16-byte aligned");
+  refused(dmm_match_objects(p, pc, 8, g, gc, 8, 0, 3, 1, 0.5, ws, wsb, m, tot, ent, 100, nullptr), ">= 1");
+  refused(dmm_match_objects(p, pc, 8, g, gc, 8, 2, -3, 1, 0.5, ws, wsb, m, tot, ent, 100, nullptr), ">= 1");
+  refused(dmm_match_objects(p, pc, 8, g, gc, 8, 256, 256, 1, 0.5, ws, wsb, m, tot, ent, 100, nullptr), "B * NC");
+  refused(dmm_match_objects(p, pc, 0, g, gc, 8, 2, 3, 1, 0.5, ws, wsb, m, tot, ent, 100, nullptr), "DMM_MATCH_MAX_PER_PLANE");
+  refused(dmm_match_objects(p, pc, 8, g, gc, -1, 2, 3, 1, 0.5, ws, wsb, m, tot, ent, 100, nullptr), "DMM_MATCH_MAX_PER_PLANE");
+  refused(dmm_match_objects(p, pc, DMM_MATCH_MAX_PER_PLANE + 1, g, gc, 8, 2, 3, 1, 0.5, ws, wsb, m, tot, ent, 100, nullptr), "DMM_MATCH_MAX_PER_PLANE");
+  refused(dmm_match_objects(p, pc, 8, g, gc, DMM_CC_MAX_PER_PLANE, 2, 3, 1, 0.5, ws, wsb, m, tot, ent, 100, nullptr), "65536");
+  refused(dmm_match_objects(p, pc, 8, g, gc, 8, 2, 3, 0, 0.5, ws, wsb, m, tot, ent, 100, nullptr), "min_area");
+  refused(dmm_match_objects(p, pc, 8, g, gc, 8, 2, 3, 1, 0.0, ws, wsb, m, tot, ent, 100, nullptr), "iou");
+  refused(dmm_match_objects(p, pc, 8, g, gc, 8, 2, 3, 1, -0.5, ws, wsb, m, tot, ent, 100, nullptr), "iou");
+  refused(dmm_match_objects(p, pc, 8, g, gc, 8, 2, 3, 1, 1.0000001, ws, wsb, m, tot, ent, 100, nullptr), "iou");
+  refused(dmm_match_objects(p, pc, 8, g, gc, 8, 2, 3, 1, nan, ws, wsb, m, tot, ent, 100, nullptr), "iou");
+  refused(dmm_match_objects(p, pc, 8, g, gc, 8, 2, 3, 1, 0.5, ws, wsb, m, tot, ent, 0, nullptr), "capacity");
+  refused(dmm_match_objects(p, pc, 8, g, gc, 8, 2, 3, 1, 0.5, ws, wsb, m, tot, ent, 1ll << 31, nullptr), "capacity");
+  refused(dmm_match_objects(p, pc, 8, g, gc, 8, 2, 3, 1, 0.5, ws, wsb - 1, m, tot, ent, 100, nullptr), "workspace_bytes");
+  refused(dmm_match_objects(p, pc, 8, g, gc, 8, 2, 3, 1, 0.5, ws, 0, m, tot, ent, 100, nullptr), "workspace_bytes");
+  if (g_hist.launches != w0.launches || g_hist.memsets != w0.memsets || g_hist.other != w0.other) { fprintf(stderr, "[drive] a refused dmm_match_objects call reached the runtime\n"); ++bad; }
+  if (wsb != 32 + 32 + 48 || dmm_match_objects_workspace(0, 1, 8, 8) || dmm_match_objects_workspace(1, 0, 8, 8) || dmm_match_objects_workspace(256, 256, 8, 8) ||
+      dmm_match_objects_workspace(1, 1, 0, 8) || dmm_match_objects_workspace(1, 1, 8, DMM_MATCH_MAX_PER_PLANE + 1) || !dmm_match_objects_workspace(1, 1, DMM_MATCH_MAX_PER_PLANE, 1)) {
+    fprintf(stderr, "[drive] dmm_match_objects_workspace\n"); ++bad;
+  }
+  g_hist.on = false;
+  hipDeviceSynchronize();
+  printf("%s\n", bad ? "MATCH FAILED" : "MATCH OK");
+  return bad ? 1 : 0;
+}
+#endif
+
 int main(int argc, char** argv) {
   g_enqueue.on =getenv("DRIVE_TRACE_ENQUEUE") != nullptr;
   fakehip_set_hook(drive_hook);
@@ -1580,6 +1689,9 @@ int main(int argc, char** argv) {
 #endif
 #ifdef DMM_PREP_LAUNCH_BATCH
   if (getenv("DRIVE_PREPARE") && prepare_main() != 0) rc = 1;
+#endif
+#ifdef DMM_MATCH_MAX_PER_PLANE
+  if (getenv("DRIVE_MATCH") && match_main() != 0) rc = 1;
 #endif
   if (g_bad) { fprintf(stderr, "[drive] FAIL: %ld device pointers outside the caller's regions\n", g_bad); rc = 1; }
   if (fakehip_violations()) { fprintf(stderr, "[drive] FAIL: %ld teardown / handle violations\n", fakehip_violations()); rc = 1; }
